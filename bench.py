@@ -4,15 +4,16 @@ MC_PILCO.reinforce_policy (policy_learning/MC_PILCO.py:484-525) -- fused particl
 expected cost, reverse-time adjoint, [one all-reduce of gradient + cost sums], Adam update -- on
 synthetic cart-pole-shaped data.  Metric: particle-steps/s = M*T / step time, whole job.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c1|c1_script|c2_script|pms_script|pms_script_n450|c1_script_n360|c2_script_n360|ur5_script|c3|c4|c5] [--no-cpu] [--no-extra]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c1|c1_script|c2_script|pms_script|pms_script_n450|c1_script_n360|c2_script_n360|ur5_script|c3|c4|c5]
+                    [--dump-outputs DIR] [--full [--no-cpu] [--no-extra]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Workload.  One GPU: BASELINE.json configs[1] (c1: 4-D state, SE kernel, N=300, M=400 particles, T=150).  N > 1 GPUs:
-configs[3] (c4: SE + polynomial(2), 4000 particles PER GPU -- 32 000 over 8 -- T=150), weak scaling; the JSON line of an
-N > 1 run carries `one_gpu_same_workload` = the same per-GPU shard timed by rank 0 ALONE on one GPU before the ranks start, and
-`scaling_efficiency` = value / (N x that); the N = 1 line carries `scale_base` = that workload's one-GPU value (its extra `c3`),
-so a 1 -> N ratio is always formed on ONE workload.  The latency-bound c1 shard is an extra of the N > 1 line.
+configs[3] (c4: SE + polynomial(2), 4000 particles PER GPU -- 32 000 over 8 -- T=150), weak scaling; with `--full` the JSON line
+of an N > 1 run carries `one_gpu_same_workload` = the same per-GPU shard timed by rank 0 ALONE on one GPU before the ranks start,
+and `scaling_efficiency` = value / (N x that); the N = 1 line carries `scale_base` = that workload's one-GPU value (its extra `c3`),
+so a 1 -> N ratio is always formed on ONE workload.  The latency-bound c1 shard is an extra of the N > 1 `--full` line.
 
 `--gpus N` without a launcher (no WORLD_SIZE in the environment) starts the N ranks itself as child processes -- before
 this process makes any GPU call (after building the library once, in the parent) -- relays rank 0's JSON line and WATCHES the
@@ -22,8 +23,15 @@ Multi-GPU: particles are sharded; the ranks meet in ONE all-reduce per step (RCC
 status flags].  Before the workload is built every rank runs a PRE-FLIGHT (one 8-byte all-reduce under a time-out) whose
 failure names backend and transport.  Prints ONE JSON line on rank 0.
 
-The timed region: W warm-up steps, then blocks of EXACTLY K steps, each bracketed by barrier + synchronize; blocks are
-repeated until >= 1 s has been measured and the MEDIAN block is reported (`blocks`, `block_ms` in the line).
+The timed region: W warm-up steps, then ONE block of exactly K steps, bracketed by barrier + synchronize; `ms_per_step` = the
+block's time / K (`--min-seconds S`: blocks of K repeated until S seconds have been measured, the median block reported).
+A plain run does only that: set up, warm up, time, print the line.  `--full` adds everything else the line has carried: the
+extra workloads (each timed in blocks of k steps repeated until >= 1 s has been measured, median block), the drop-in loop,
+GP training, pretrain stages, the CPU baselines and, on N > 1 GPUs, the one-GPU reference of the same shard.
+
+`--dump-outputs DIR`: after the timed steps, rank 0 writes what its last timed step handed the caller -- states and inputs of the
+rollout, cost, std, the gradients and the parameters after the Adam update -- as DIR/<name>.npy (float64; at most 64 MB, else a
+fixed, seeded sample of the particles).  Inputs are seeded: the same arguments give the same inputs from run to run.
 """
 import argparse
 import datetime
@@ -57,9 +65,13 @@ def parse_args():
     ap.add_argument("--workload", default=None, help="c1 (default on one GPU), c1_script, c2_script, pms_script, ur5_script, c3, c4 (default on N > 1 GPUs), c5")
     ap.add_argument("--particles", type=int, default=0, help="particles per GPU (default: the workload's M)")
     ap.add_argument("--horizon", type=int, default=0)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline legs")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra_workloads of the default runs")
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="repeat the K-step block until this much has been measured")
+    ap.add_argument("--full", action="store_true", help="besides the headline: extra workloads, drop-in loop, GP training, pretrain, CPU baselines, "
+                    "the one-GPU reference of an N > 1 run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline legs")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the extra_workloads of the default runs")
+    ap.add_argument("--min-seconds", type=float, default=None, help="repeat the K-step block until this much has been measured and report the "
+                    "median block (default: the headline is ONE block of exactly K steps; --full's extras repeat theirs for 1 s)")
     ap.add_argument("--noise", default="philox", choices=["philox", "buffers"])
     ap.add_argument("--pms", action="store_true", help="partially measurable system: the policy sees noisy positions and filtered "
                     "finite-difference velocities (MC_PILCO4PMS.apply_policy); cart-pole workloads")
@@ -270,14 +282,15 @@ class Runner:
             share, sums = ops.local_cost(w.cost, states, self.world * M, self.shift, sums_out=self.msg.sums)
             share.backward()
             fl = torch.cat([torch.isnan(share.detach()).reshape(1).to(torch.float64), ((status & self.bits) != 0).to(torch.float64)])
-            cost, _std, fl_all, self.shift = self.sharding.finish_step(_SumsCost, self.reducer, w.params, sums, fl, self.world * M, self.shift,
-                                                                       msg=self.msg)
+            cost, std, fl_all, self.shift = self.sharding.finish_step(_SumsCost, self.reducer, w.params, sums, fl, self.world * M, self.shift,
+                                                                      msg=self.msg)
             self.flags_sum += fl_all
         else:
-            cost, _std = ops.expected_cost(w.cost, states)
+            cost, std = ops.expected_cost(w.cost, states)
             cost.backward()
         ops.fwd_events = ops.bwd_events = None
         self.opt.step()
+        self.last = (states, inputs, cost, std)  # (references only: --dump-outputs reads the last timed step's)
         return cost
 
     def barrier(self, solo=False):
@@ -429,6 +442,37 @@ class _SumsCost:
         return out[0], out[1]
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(run, d, seed=0):
+    """`--dump-outputs DIR`: what the last timed step handed its caller -- the rollout's states [T, M, S] and inputs [T, M, U], the expected cost and
+    its std, the gradient of each policy parameter and the parameters after the Adam update -- as DIR/<name>.npy in float64.  Beyond DUMP_BYTES the
+    states and inputs are cut to a fixed, seeded sample of particles (the same for both).  Returns what was written."""
+    import numpy as np
+
+    torch = run.torch
+    states, inputs, cost, std = run.last
+    names = ("log_ls", "centers", "weight")
+    arrs = {"states": states, "inputs": inputs, "cost": cost, "std": std}
+    arrs.update({"grad_" + k: p.grad for k, p in zip(names, run.w.params)})
+    arrs.update({k: p for k, p in zip(names, run.w.params)})
+    arrs = {k: v.detach().to("cpu", torch.float64).numpy() for k, v in arrs.items()}
+    M = arrs["states"].shape[1]
+    rest = sum(a.nbytes for k, a in arrs.items() if k not in ("states", "inputs"))
+    per_particle = (arrs["states"].nbytes + arrs["inputs"].nbytes) / M
+    keep = max(1, min(M, int((DUMP_BYTES - rest) / per_particle)))
+    sample = None
+    if keep < M:
+        sample = np.sort(np.random.RandomState(seed).choice(M, keep, replace=False))
+        arrs["states"], arrs["inputs"] = arrs["states"][:, sample], arrs["inputs"][:, sample]
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(a))
+    return {"dir": d, "arrays": {k: list(a.shape) for k, a in arrs.items()}, "dtype": "float64",
+            "particles": M if sample is None else {"sampled": int(keep), "of": M, "seed": seed}}
+
+
 def preflight(dist, torch, dev, args, rank, world):
     """One 8-byte all-reduce before anything is built: a broken transport shows up here, with a message, inside the process
     group's time-out -- not as a hang in step 0."""
@@ -532,13 +576,15 @@ def main():
             except Exception as e:  # noqa: BLE001  (a smoke: reported, not fatal)
                 collective["error_" + other] = repr(e)
     one_gpu = None
-    if world > 1 and not args.no_extra:
+    extras = args.full and not args.no_extra
+    extra_seconds = 1.0 if args.min_seconds is None else args.min_seconds
+    if world > 1 and extras:
         # the SAME per-GPU shard on ONE GPU, alone: rank 0 times it (no collective, median of blocks) while the other ranks wait at the
         # barrier -- N x this value is perfect weak scaling of this workload
         if rank == 0:
             k1 = max(3, args.steps // 2)
             saved = [p.detach().clone() for p in w.params]  # (rank 0's solo steps must not leave it with other parameters than its peers)
-            s1, f1, _, b1 = main_run.run(k1, 2, min(args.min_seconds, 1.0), sharded=False, solo=True)
+            s1, f1, _, b1 = main_run.run(k1, 2, min(extra_seconds, 1.0), sharded=False, solo=True)
             with torch.no_grad():
                 for p, q in zip(w.params, saved):
                     p.copy_(q)
@@ -550,11 +596,13 @@ def main():
         import torch.distributed as dist
 
         dist.barrier()
-    block_s, fwd_ms, last_cost, blocks = main_run.run(args.steps, args.warmup, args.min_seconds)
+    # (one block of exactly --steps timed steps, unless --min-seconds asks for the median of repeated blocks)
+    block_s, fwd_ms, last_cost, blocks = main_run.run(args.steps, args.warmup, args.min_seconds or 0.0)
     if rank != 0:
         note("rank %d: timed blocks done" % rank)
     if rank == 0:
         note("%s: %d block(s) of %d steps, median %.3f s" % (args.workload, len(blocks), args.steps, block_s))
+    dumped = dump_outputs(main_run, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
     ms_per_step = 1e3 * block_s / args.steps
     value = world * M * T / (block_s / args.steps)
 
@@ -598,7 +646,9 @@ def main():
             "kernel_sources_sha16": sha,
             "final_cost": last_cost,
         }
-    if world > 1 and not args.no_extra:
+        if dumped:
+            out["outputs"] = dumped
+    if world > 1 and extras:
         # the latency-bound c1 shard (M = 400 per GPU), sharded, for comparison with the single-GPU headline (lockstep on every rank:
         # it contains collectives)
         c1 = Runner(args, "c1", dev, rank, world, reducer)
@@ -611,7 +661,7 @@ def main():
         del c1
     if rank == 0:
         default_run = world == 1 and default_workload and not args.particles and not args.horizon and not args.pms
-        if default_run and not args.no_extra:
+        if default_run and extras:
             # the other single-GPU configurations of BASELINE.json, measured in the same run: the launch script's own horizon (T=60,
             # SURVEY 8d), c3 (SE+poly(2), M=4000) and c5 (UR5, 6 GPs, D=24, N=400, M=2000, T=300) -- same step definition, fewer steps
             extra = []
@@ -620,7 +670,7 @@ def main():
                             ("ur5_script", 10), ("c3", 5), ("c5", 3)):
                 note("extra workload %s" % name)
                 r = Runner(args, name, dev, rank, world, reducer)
-                e2, f2, c2, b2 = r.run(k, 2, args.min_seconds)
+                e2, f2, c2, b2 = r.run(k, 2, extra_seconds)
                 note("%s: median of %d block(s) of %d steps: %.3f s" % (name, len(b2), k, e2))
                 rf = r.roofline(f2, e2 / k, traffic_of(name if name in ("c3", "c5") else None))
                 rf.pop("achieved_basis")
@@ -662,7 +712,7 @@ def main():
             out["fit_model_ur5"] = {"what": "the same for the UR5-shaped model: N=%d, D=24, SE + polynomial(1), 6 GPs, 200 epochs each (all six trained "
                                             "epoch-synchronously: mcp_nll_epoch)" % n_tr6,
                                     "ms_per_epoch_all_6_gps": 1e3 * s_ep6, "ms_per_epoch_per_gp": 1e3 * s_ep6 / 6}
-        if default_run and not args.no_extra:
+        if default_run and extras:
             note("pretrain_gp with SOD (cart-pole N=300, UR5 N=600)")
             from mc_pilco_amd import workloads
 
@@ -674,7 +724,7 @@ def main():
                                        "Cholesky, inverse, alpha, pack, posterior at all rows, the MSE print's host syncs) and the device time of each stage "
                                        "(HIP events, median of 5)", "reference_cpu_s_per_gp_n300": 0.56,
                                "reference_cpu_source": "BASELINE.md section 2 (survey container, 1 thread)", **pre}
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             # the cores this process may actually run on (the box gives one GPU's share of the host, not os.cpu_count())
             ncores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
             ncores = max(1, min(ncores, int(os.environ.get("MCP_BENCH_MAX_THREADS", "32"))))

@@ -45,7 +45,8 @@ def _oracle_on_reordered_training_set(o, key):
     pp = orc.PolicyPar(torch.log(Tt(pi["lengthscales"])).reshape(1, -1), Tt(pi["centers"]), Tt(pi["weight"]), c["u_max"], pb["policy_kind"],
                        **pb["policy_extra"])
     cost_fn = lambda st: orc.cart_pole_cost(st, Tt(c["cost_target"]), Tt(c["cost_ls"]), c["cost_angle_index"], c["cost_pos_index"])
-    oc, os_, og, ost, oin = orc.policy_grad_step(m, pp, o["x0"], Tn, cost_fn, o["p"], o["eps"], o["masks"])
+    with rs.one_cpu_thread():
+        oc, os_, og, ost, oin = orc.policy_grad_step(m, pp, o["x0"], Tn, cost_fn, o["p"], o["eps"], o["masks"])
     return dict(cost=float(oc), grads=og, states=ost, inputs=oin)
 
 

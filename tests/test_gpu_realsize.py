@@ -9,6 +9,7 @@ real statistics of the in-kernel Philox noise (the mode every benchmark number i
 Tolerances (fp64): the oracle factorises K itself (torch Cholesky) and the HIP path its own way, so trajectories agree to the
 conditioning of K: states / inputs abs 1e-7 over 8 steps, cost rel 1e-9, gradients rel 1e-6 (tests/test_gpu_parity.py:238-243).
 """
+import contextlib
 import functools
 
 import numpy as np
@@ -34,9 +35,26 @@ def _real(key):
     return v if len(v) == 4 else v + (None,)
 
 
+@contextlib.contextmanager
+def one_cpu_thread():
+    """The oracle's answer on one CPU thread: the BLAS splits its sums by the thread count, and at the tolerances below the answer must not
+    depend on how many cores the host lends torch (1 vs 8 threads moves the oracle's own states / inputs by up to 2.5e-9 at N = 300)."""
+    nt = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        yield
+    finally:
+        torch.set_num_threads(nt)
+
+
 @functools.lru_cache(maxsize=None)
 def oracle_answer(key):
     """(cost, std, grads, states, inputs, x0, eps, masks) of the CPU oracle at the real N, small M and T, its own pretrain."""
+    with one_cpu_thread():
+        return _oracle_answer(key)
+
+
+def _oracle_answer(key):
     from mc_pilco_amd import workloads
 
     name, M, Tn, Ntr = _real(key)
