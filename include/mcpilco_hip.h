@@ -29,12 +29,13 @@
 extern "C" {
 #endif
 
-#define MCP_ABI_VERSION 6 /* 5: mcp_kernel.scal, MCP_FWD_NO_GP_SHARDING, MCP_STATUS_NONPOS_VAR now means a FINITE variance <= 0, mcp_nll_epoch, \
+#define MCP_ABI_VERSION 7 /* 5: mcp_kernel.scal, MCP_FWD_NO_GP_SHARDING, MCP_STATUS_NONPOS_VAR now means a FINITE variance <= 0, mcp_nll_epoch, \
                              mcp_adam_step_guarded, mcp_policy_step_commit (round 4).                                                            \
                              6 (round 6; the round-5 contract changes, which had kept the number 5, are part of it): mcp_sod_select needs       \
                              mcp_sod_workspace_bytes(N) = 8 (N^2 + 2 N) + the exchange area (was 8 N^2) and may report *n_out = -1;             \
                              MCP_MAX_TRAIN 1024 -> 4096; the process-wide mcp_debug_* setters are gone (mcpilco_hip_debug.h: per-call           \
-                             mcp_dispatch); mcp_adam_step_guarded skips a not-SPD epoch; new: mcp_sym_sandwich, mcp_noise.call_dev, MCP_FWD_KT_PACKED / MCP_FWD_XJ_PACKED */
+                             mcp_dispatch); mcp_adam_step_guarded skips a not-SPD epoch; new: mcp_sym_sandwich, mcp_noise.call_dev, MCP_FWD_KT_PACKED / MCP_FWD_XJ_PACKED. \
+                             7: mcp_dispatch loses the Cholesky form request, mcp_chol_factor_ex / mcp_chol_inverse_ex are gone (debug header) */
 
 #define MCP_OK 0
 #define MCP_ERR_ARG (-1)       /* null pointer / non-positive size                       */

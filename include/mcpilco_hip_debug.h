@@ -1,8 +1,9 @@
 /*
  * mcpilco_hip_debug.h -- test and diagnostic entry points of libmcpilco_hip.so.  NOT part of the drop-in boundary
  * (include/mcpilco_hip.h): the product path never needs them.  They exist so that the parity tests can force every kernel variant the
- * automatic dispatch of mcp_rollout_fwd / mcp_rollout_bwd / mcp_chol_* may choose, so that bench.py / tools can report which variant ran,
- * and so that tools/phase_stamps.py can read per-phase cycle counters.
+ * automatic dispatch of mcp_rollout_fwd / mcp_rollout_bwd / mcp_posterior_fwd may choose, so that bench.py / tools can report which
+ * variant ran, and so that tools/phase_stamps.py can read per-phase cycle counters.  (mcp_chol_factor / mcp_chol_inverse have one path
+ * per size and no `_ex` form.)
  *
  * Round 5: the request travels WITH THE CALL.  Every `_ex` entry point is its plain namesake plus a `mcp_dispatch*` (NULL or all zero =
  * automatic: the plain entry points pass NULL); the library keeps no dispatch state of its own -- no setters, nothing process-wide.
@@ -29,8 +30,6 @@ typedef struct mcp_dispatch {
   int32_t bwd_particles; /* backward sweep: particles per workgroup 1 / 2 / 4 / 8 (forces the general sweep)                            */
   int32_t bwd_lean;      /* the latency-lean sweep (rollout_bwd_lat_kernel): 1 never                                                    */
   int32_t bwd_pipe;      /* general sweep, one particle per workgroup on the wide classes: 1 never the pipelined form (chain beside the RBF stage) */
-  int32_t chol_form;     /* mcp_chol_factor / _inverse: 1 the round-1/2 kernels, 2 the round-3 one-workgroup forms, 3 the round-4 forms
-                            with one-wave inverse columns (0: left-looking / panel factorisation, column-parallel / blocked inverse)     */
   uint32_t stamp_block;  /* which workgroup of the forward launch writes its stamps                                                     */
   void* fwd_stamps;      /* device buffer of 32 uint64 per-phase cycle totals of that workgroup (NULL = off)                            */
   void* bwd_stamps;      /* device buffer of 16 uint64 (backward sweep)                                                                 */
@@ -52,8 +51,6 @@ int mcp_rollout_bwd_ex(const mcp_model* model, const mcp_policy* policy, const m
                        mcp_dispatch* d);
 int mcp_posterior_fwd_ex(const mcp_gp* gp, int M, const double* Z, double* mu, double* var, double* Jmu, double* Jvar, uint32_t* status,
                          void* stream, mcp_dispatch* d);
-int mcp_chol_factor_ex(int N, double* A, int lda, double* logdet, uint32_t* status, void* stream, const mcp_dispatch* d);
-int mcp_chol_inverse_ex(int N, const double* U, int ldu, double* Uinv, int ldi, double* Kinv, int ldk, void* stream, const mcp_dispatch* d);
 
 #ifdef __cplusplus
 }

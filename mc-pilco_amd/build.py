@@ -27,27 +27,6 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build_variant(tag, defines, verbose=True, only=None):
-    """Experiment helper: a second library libmcpilco_hip_<tag>.so with extra -D defines (select it with MCPILCO_HIP_EXPERIMENT=1 MCPILCO_HIP_LIB=<path>).
-    ``only``: the sources the defines concern (the others are linked from the main build's objects)."""
-    objs = []
-    for src in SOURCES:
-        s = os.path.join(CSRC, src)
-        if only is not None and src not in only:
-            objs.append(os.path.join(CSRC, src.replace(".hip", ".o")))
-            continue
-        o = os.path.join(CSRC, src.replace(".hip", ".%s.o" % tag))
-        if _stale(o, [s] + HEADERS):
-            cmd = [HIPCC] + FLAGS + ["-D" + d for d in defines] + ["-c", s, "-o", o]
-            if verbose:
-                print(" ".join(cmd), flush=True)
-            subprocess.check_call(cmd)
-        objs.append(o)
-    lib = os.path.join(HERE, "libmcpilco_hip_%s.so" % tag)
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-ldl", "-o", lib])
-    return lib
-
-
 def _compile_all(jobs, verbose):
     """Runs the hipcc commands of the stale sources side by side (one process each, at most the CPU count)."""
     from concurrent.futures import ThreadPoolExecutor
@@ -102,23 +81,4 @@ def build(force=False, verbose=True):
 
 
 if __name__ == "__main__":
-    if "--variant" in sys.argv:  # python build.py --variant TAG DEF1 DEF2 ...
-        i = sys.argv.index("--variant")
-        print(build_variant(sys.argv[i + 1], sys.argv[i + 2:]))
-    elif "--variant-only" in sys.argv:  # python build.py --variant-only a.hip,b.hip TAG DEF1 DEF2 ...: recompiling the named sources only
-        i = sys.argv.index("--variant-only")
-        print(build_variant(sys.argv[i + 2], sys.argv[i + 3:], only=sys.argv[i + 1].split(",")))
-    elif "--variant-fwd" in sys.argv:  # the same, recompiling rollout_fwd.hip only
-        i = sys.argv.index("--variant-fwd")
-        print(build_variant(sys.argv[i + 1], sys.argv[i + 2:], only=["rollout_fwd.hip"]))
-    elif "--variant-lean" in sys.argv:  # the same, recompiling rollout_fwd_lean.hip only
-        i = sys.argv.index("--variant-lean")
-        print(build_variant(sys.argv[i + 1], sys.argv[i + 2:], only=["rollout_fwd_lean.hip"]))
-    elif "--variant-gp" in sys.argv:  # the same, recompiling gp_pretrain.hip only
-        i = sys.argv.index("--variant-gp")
-        print(build_variant(sys.argv[i + 1], sys.argv[i + 2:], only=["gp_pretrain.hip"]))
-    elif "--variant-bwd" in sys.argv:  # the same, recompiling rollout_bwd.hip only
-        i = sys.argv.index("--variant-bwd")
-        print(build_variant(sys.argv[i + 1], sys.argv[i + 2:], only=["rollout_bwd.hip"]))
-    else:
-        build(force="--force" in sys.argv)
+    build(force="--force" in sys.argv)

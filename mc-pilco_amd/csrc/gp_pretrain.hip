@@ -7,7 +7,6 @@
 #include <type_traits>
 
 #include "mcp_device.h"
-#include "../../include/mcpilco_hip_debug.h"
 
 using namespace mcp;
 
@@ -152,47 +151,10 @@ __global__ __launch_bounds__(CH_NT) void chol_factor_kernel(int N, double* __res
   if (bad) atomicOr(status, bad);
 }
 
-// ---------------------------------------------------------------------------------------
-// Uinv = U^-1 : one thread per column, rows swept bottom-up with the row of U broadcast from LDS
-// ---------------------------------------------------------------------------------------
-#define TI_NT 64
-__global__ __launch_bounds__(TI_NT) void tri_inverse_kernel(int N, const double* __restrict__ U, int ldu, double* __restrict__ Ui,
-                                                            int ldi) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];  // [N] one row of U
-  const int j = blockIdx.x * TI_NT + threadIdx.x;                // my column
-  const int jmax = min(N - 1, blockIdx.x * TI_NT + TI_NT - 1);   // last column of this block
-  for (int i = jmax; i >= 0; --i) {
-    __syncthreads();
-    for (int m = i + threadIdx.x; m <= jmax; m += TI_NT) smem[m] = U[(size_t)i * ldu + m];
-    __syncthreads();
-    if (j < N) {
-      double x;
-      if (j < i) {
-        x = 0.0;
-      } else {
-        double s0 = (j == i) ? 1.0 : 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-        int m = i + 1;
-        for (; m + 3 <= j; m += 4) {
-          s0 = fma(-smem[m], Ui[(size_t)m * ldi + j], s0);
-          s1 = fma(-smem[m + 1], Ui[(size_t)(m + 1) * ldi + j], s1);
-          s2 = fma(-smem[m + 2], Ui[(size_t)(m + 2) * ldi + j], s2);
-          s3 = fma(-smem[m + 3], Ui[(size_t)(m + 3) * ldi + j], s3);
-        }
-        for (; m <= j; ++m) s0 = fma(-smem[m], Ui[(size_t)m * ldi + j], s0);
-        x = ((s0 + s1) + (s2 + s3)) / smem[i];
-      }
-      Ui[(size_t)i * ldi + j] = x;
-    }
-  }
-  // rows below the block's last column are zero for these columns
-  if (j < N)
-    for (int i = jmax + 1; i < N; ++i) Ui[(size_t)i * ldi + j] = 0.0;
-}
-
-// Uinv = U^-1 for N <= 1024: one WAVE per column j.  Back substitution x_i = (delta_ij - sum_{i<m<=j} U[i][m] x_m) / U[i][i],
-// i = j .. 0: lane l keeps x_m for m = l (mod 64) in registers, the row of U is one coalesced read per 64 columns (the next
-// row is fetched while the current dot product is reduced), the dot product a wave64 DPP sum.  N columns run in parallel
-// (the thread-per-column kernel above walks its own earlier results through global memory: 2 ms at N=300 against ~0.1 ms).
+// Uinv = U^-1 for N <= 1024 (mcp_chol_inverse runs it for N <= 16): one WAVE per column j.  Back substitution
+// x_i = (delta_ij - sum_{i<m<=j} U[i][m] x_m) / U[i][i], i = j .. 0: lane l keeps x_m for m = l (mod 64) in registers, the row of U is
+// one coalesced read per 64 columns (the next row is fetched while the current dot product is reduced), the dot product a wave64 DPP
+// sum.  N columns run in parallel.
 #define TW_KM 16  // 64 * TW_KM >= N
 __global__ __launch_bounds__(256) void tri_inverse_wave_kernel(int N, const double* __restrict__ U, int ldu, double* __restrict__ Ui, int ldi) {
   const int lane = threadIdx.x & 63;
@@ -240,18 +202,17 @@ __global__ __launch_bounds__(256) void tri_inverse_wave_kernel(int N, const doub
 }
 
 // ---------------------------------------------------------------------------------------
-// MFMA-blocked forms of the two kernels above (round 3; GP_prior.forward's torch.cholesky / torch.inverse, GP_prior.py:106-110,
-// once per GP per trial in pretrain and once per EPOCH in GP_prior.fit_model, GP_prior.py:179-230).  One workgroup of 16 waves
-// per matrix; the matrix stays in L2 / the CU's L1, every 16x16 block product runs on v_mfma_f64_16x16x4_f64:
+// MFMA-blocked forms of the two kernels above (GP_prior.forward's torch.cholesky / torch.inverse, GP_prior.py:106-110, once per GP
+// per trial in pretrain and once per EPOCH in GP_prior.fit_model, GP_prior.py:179-230).  Every 16x16 block product runs on
+// v_mfma_f64_16x16x4_f64:
 //   A operand  lane l -> A[i = l & 15][k = l >> 4],   B operand  lane l -> B[k = l >> 4][j = l & 15],
 //   accumulator register r of lane l -> D[(l >> 4) + 4 r][l & 15]          (so register u of an accumulator IS the B operand of
 //   step u of a following product: D2 = A2 * D needs no data movement).
-// The 16x16 diagonal blocks are factored / inverted by ONE wave in registers: lane c holds column c, scalars travel by v_readlane
-// (the LDS form above spends ~13 k cycles per block in volatile round trips; this one ~5 k).
+// The 16x16 diagonal blocks are factored / inverted by ONE wave in registers: lane c holds column c (the LDS form of chol_factor_kernel
+// spends ~13 k cycles per block in volatile round trips).
 // Measured at N = 300 (tools/time_fit_model.py, rocprofv3): see DESIGN.md 4.5.
 // ---------------------------------------------------------------------------------------
 #define CM_NT 512  // (1024 threads = 128 registers: the in-register diagonal block of wave 0 spills 26 of them)
-#define CM_NW (CM_NT / 64)
 typedef double v4d_p __attribute__((ext_vector_type(4)));
 typedef double __attribute__((address_space(1))) * gdp_t;         // explicit global pointers: a noinline device function would otherwise
 typedef const double __attribute__((address_space(1))) * gcdp_t;  // address its pointer arguments as flat (64-bit address per lane and load)
@@ -342,150 +303,10 @@ __device__ __forceinline__ void tri16_inverse(const double (&x)[16], const doubl
   }
 }
 
-__global__ __launch_bounds__(CM_NT) void chol_factor_mfma_kernel(int N, double* __restrict__ A, int lda, double* __restrict__ logdet,
-                                                                 uint32_t* __restrict__ status, size_t a_stride, size_t ld_stride) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  A += (size_t)blockIdx.x * a_stride;  // (one workgroup per matrix of a batch: the G GPs of a training epoch, mcp_nll_epoch)
-  logdet += (size_t)blockIdx.x * ld_stride;
-  double* ui = smem;        // [16][16]  U_kk^-1 (row m, column r at ui[m * 16 + r])
-  double* pn = smem + 256;  // [16][ncp] the row panel of this block row
-  const int tid = threadIdx.x, lane = tid & 63, kq = lane >> 4, li = lane & 15;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int NBK = (N + 15) >> 4;
-  double ld_acc = 0.0;  // wave 0, lanes 0..15: sum of log U[c][c] over the block rows
-  uint32_t bad = 0;
-  for (int kbk = 0; kbk < NBK; ++kbk) {
-    const int kb = kbk << 4, nb = min(16, N - kb);
-    const int j0 = kb + 16, nc = N > j0 ? N - j0 : 0, nct = (nc + 15) >> 4, ncp = nct << 4;
-    // (1) diagonal block: factor in registers, write back, invert
-    if (wv == 0) {
-      const int c = li;
-      double x[16], inv_d[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) x[r] = (r <= c && c < nb) ? A[(size_t)(kb + r) * lda + kb + c] : (r == c ? 1.0 : 0.0);  // identity beyond N
-#pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        const double dk = lane_get(x[k], k);
-        if (!(dk > 0.0)) bad |= MCP_STATUS_NOT_SPD;
-        const double sd = sqrt(dk), is = 1.0 / sd;
-        inv_d[k] = is;
-        const double uk = c == k ? sd : (c > k ? x[k] * is : 0.0);
-        x[k] = uk;
-#pragma unroll
-        for (int r = k + 1; r < 16; ++r) x[r] = fma(-lane_get(uk, r), uk, x[r]);  // (only rows r <= c are meaningful)
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        if (r > c) x[r] = 0.0;
-        if (lane < 16 && r < nb && c < nb) A[(size_t)(kb + r) * lda + kb + c] = x[r];
-      }
-      if (lane < 16 && c < nb) {
-        double dcc = 0.0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dcc = r == c ? x[r] : dcc;
-        ld_acc += log(dcc);
-      }
-      double w[16];
-      tri16_inverse(x, inv_d, c, w);
-      if (lane < 16) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ui[r * 16 + c] = w[r];
-      }
-    }
-    __syncthreads();
-    // (2) row panel P = U_kk^-T A[kb:kb+16, j0:N]:  D[i = r][j] = sum_m W[m][r] A[kb + m][j0 + j]
-    for (int tile = wv; tile < nct; tile += CM_NW) {
-      const int col = j0 + 16 * tile + li;
-      v4d_p acc = {0.0, 0.0, 0.0, 0.0};
-      double av[4], bv[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        av[u] = ui[(4 * u + kq) * 16 + li];
-        const int row = kb + 4 * u + kq;
-        bv[u] = (col < N && row < N) ? A[(size_t)row * lda + col] : 0.0;
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u], acc, 0, 0, 0);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = kq + 4 * r;
-        const bool ok = col < N && kb + i < N;
-        if (ok) A[(size_t)(kb + i) * lda + col] = acc[r];
-        pn[i * ncp + 16 * tile + li] = ok ? acc[r] : 0.0;
-      }
-    }
-    __syncthreads();
-    // (3) trailing update, blocks (I, J), I <= J, of the upper triangle:  T[i][j] -= sum_m P[m][16 I + i] P[m][16 J + j]
-    // (round 4: the tiles of a wave are independent, but each one was load -> MFMA -> store with the matrix in global memory: a memory
-    //  round trip per tile on every wave, 38 of them in a row in the first block step at N = 400.  Now the NEXT tile's accumulator
-    //  loads are in flight while the current one is multiplied and stored.)
-    const int nblk = nct * (nct + 1) / 2;
-    auto tile_of = [&](int bidx, int& I, int& J) {
-      I = 0;
-      int rem = bidx;
-      while (rem >= nct - I) {
-        rem -= nct - I;
-        ++I;
-      }
-      J = I + rem;
-    };
-    auto load_acc = [&](int I, int J, v4d_p& acc) {
-      const int col = j0 + 16 * J + li;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = j0 + 16 * I + kq + 4 * r;
-        acc[r] = (row < N && col < N) ? A[(size_t)row * lda + col] : 0.0;
-      }
-    };
-    int I = 0, J = 0, In = 0, Jn = 0;
-    v4d_p acc = {0.0, 0.0, 0.0, 0.0}, accn = {0.0, 0.0, 0.0, 0.0};
-    if (wv < nblk) {
-      tile_of(wv, I, J);
-      load_acc(I, J, acc);
-    }
-    for (int bidx = wv; bidx < nblk; bidx += CM_NW) {
-      const bool more = bidx + CM_NW < nblk;
-      if (more) {
-        tile_of(bidx + CM_NW, In, Jn);
-        load_acc(In, Jn, accn);
-      }
-      const int col = j0 + 16 * J + li;
-      double av[4], bv[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        av[u] = -pn[(4 * u + kq) * ncp + 16 * I + li];
-        bv[u] = pn[(4 * u + kq) * ncp + 16 * J + li];
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u], acc, 0, 0, 0);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = j0 + 16 * I + kq + 4 * r;
-        if (row < N && col < N) A[(size_t)row * lda + col] = acc[r];
-      }
-      I = In;
-      J = Jn;
-      acc = accn;
-    }
-    __syncthreads();
-  }
-  // zero the strictly lower part (torch.cholesky(upper=True) returns zeros there; the trailing updates wrote scratch into the
-  // lower halves of the diagonal blocks)
-  for (int idx = tid; idx < N * N; idx += CM_NT) {
-    const int r = idx / N, c = idx - r * N;
-    if (c < r) A[(size_t)r * lda + c] = 0.0;
-  }
-  if (wv == 0) {
-    const double tot = wave_sum(lane < 16 ? ld_acc : 0.0);
-    if (lane == 0) *logdet = 2.0 * tot;
-  }
-  if (bad) atomicOr(status, bad);
-}
-
-// The same factorization LEFT-looking (round 4): block row I of U is finished in one go,
+// The factorization LEFT-looking (round 4), one workgroup per matrix: block row I of U is finished in one go,
 //   T_IJ = A_IJ - sum_{k < I} U_kI^T U_kJ,   U_II = chol(T_II),   U_IJ = U_II^-T T_IJ   (J > I),
-// so every 16x16 tile of the matrix is written ONCE (the right-looking kernel above reads, updates and writes every trailing tile in
-// every block step: a store -> barrier -> load chain per step that its MFMAs wait behind), the sums over k stream finished, read-only
+// so every 16x16 tile of the matrix is written ONCE (a right-looking form reads, updates and writes every trailing tile in every
+// block step: a store -> barrier -> load chain per step that its MFMAs wait behind), the sums over k stream finished, read-only
 // rows with their loads two k-steps ahead, and the one serial chain -- factoring and inverting the diagonal block, wave 0 -- runs
 // BESIDE the other waves' sums, which do not need it until their last four MFMAs:
 //   wave 0:       T_II = P_I - U_(I-1)I^T U_(I-1)I  (P_I and the tile both wait in LDS, see below) -> columns in registers -> U_II, W_I = U_II^-1
@@ -496,13 +317,6 @@ __global__ __launch_bounds__(CM_NT) void chol_factor_mfma_kernel(int N, double* 
 //   barrier;  U_IJ = W_I^T T_IJ (register u of T IS the B operand of step u), wave 1 leaves U_I(I+1) in LDS for the next row;  barrier.
 // The chain per block row is then: 4 MFMAs, two LDS round trips, the 16 column steps, the inverse, two barriers and one tile product.
 // CL_MAXS tile slots per tile wave, up to CL_GS of them in one k loop (registers).
-#ifdef CLX_STAMPS  // experiment build only (build.py --variant-gp): cycle stamps of wave 0 / wave 1 per block row
-__device__ unsigned long long g_clx[16 * 128];
-#define CLX_T(w, slot) do { if (blockIdx.x == 0 && wv == (w) && lane == 0 && I < 128) g_clx[I * 16 + (slot)] = clock64(); } while (0)
-extern "C" int mcp_debug_read_chol_stamps(unsigned long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_clx), sizeof(g_clx)); }
-#else
-#define CLX_T(w, slot) do { } while (0)
-#endif
 // the role of wave 0 (a function of its own: its registers are then allocated apart from the tile role's)
 __device__ __noinline__ void chol_left_diag_role(int N_, gdp_t A_, int lda_, double* __restrict__ logdet, uint32_t* __restrict__ status,
                                                  double* ui, double* dg, double (*dgp)[256], double* nt) {
@@ -510,8 +324,6 @@ __device__ __noinline__ void chol_left_diag_role(int N_, gdp_t A_, int lda_, dou
   const gdp_t A = uniform_ptr(A_);
   const int tid = threadIdx.x, lane = tid & 63, kq = lane >> 4, li = lane & 15;
   const int NBK = (N + 15) >> 4;
-  const int wv = 0;
-  (void)wv;
   {
     double ld_acc = 0.0;
     uint32_t bad = 0;
@@ -525,7 +337,6 @@ __device__ __noinline__ void chol_left_diag_role(int N_, gdp_t A_, int lda_, dou
       int kb = I << 4;
       asm volatile("" : "+s"(kb));  // (or the sixteen store addresses of the block become 64-bit induction variables, spilled and reloaded every row)
       const int nb = min(16, N - kb);
-      CLX_T(0, 0);
       v4d_p acc;
 #pragma unroll
       for (int r = 0; r < 4; ++r) acc[r] = dgp[I & 1][(kq + 4 * r) * 16 + li];
@@ -545,7 +356,6 @@ __device__ __noinline__ void chol_left_diag_role(int N_, gdp_t A_, int lda_, dou
         const double v = dg[r * 16 + c];
         x[r] = r <= c ? v : 0.0;
       }
-      CLX_T(0, 1);
       Chol16Col<0>::run(x, w, c, bad);  // w[m] = Uinv[c][m]
       if (lane < 16 && c < nb) {
 #pragma unroll
@@ -556,16 +366,12 @@ __device__ __noinline__ void chol_left_diag_role(int N_, gdp_t A_, int lda_, dou
         for (int r = 0; r < 16; ++r) dcc = r == c ? x[r] : dcc;
         ld_acc += log(dcc);
       }
-      CLX_T(0, 2);
       if (lane < 16) {
 #pragma unroll
         for (int m = 0; m < 16; ++m) ui[c * 16 + m] = w[m];
       }
-      CLX_T(0, 3);
+      __syncthreads();  // (the tile role's two barriers of the row)
       __syncthreads();
-      CLX_T(0, 4);
-      __syncthreads();
-      CLX_T(0, 5);
     }
     const double tot = wave_sum(lane < 16 ? ld_acc : 0.0);
     if (lane == 0) *logdet = 2.0 * tot;
@@ -700,7 +506,6 @@ __device__ __noinline__ void chol_left_tile_role(int N_, gdp_t A_, int lda_, int
     int kb = I << 4;
     asm volatile("" : "+s"(kb));  // (keeps the per-slot addresses from becoming spilled 64-bit induction variables of the row loop)
     const int ntile = NBK - I;
-    CLX_T(1, 8);
     if (wv != 4) {
       // the mirror tiles below the diagonal: zeros, as torch.cholesky(upper=True) returns (nothing reads them; stored here, the stores
       // drain behind the k loops instead of in front of the row's second barrier)
@@ -711,13 +516,10 @@ __device__ __noinline__ void chol_left_tile_role(int N_, gdp_t A_, int lda_, int
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int mrow = kb + 16 * t + kq + 4 * r;
-#ifndef CLX_NOMIRROR
             if (mrow < N) A[(size_t)mrow * lda + kb + li] = 0.0;
-#endif
           }
         }
       }
-      CLX_T(1, 11);
       const unsigned aoff = PANEL ? (unsigned)(kq * 16 + li) : lrow + (unsigned)min(kb + li, N - 1);
       const double* panel = panels + (I & 1) * pstride;
       // P_(I+1): with six or more tiles in the row every wave has one, and the sum rides in wave hw = 0's first k loop on the operand
@@ -804,7 +606,6 @@ __device__ __noinline__ void chol_left_tile_role(int N_, gdp_t A_, int lda_, int
         }
       }
     }
-    CLX_T(1, 9);
     __syncthreads();
     if (wv != 4) {
       double wa[4];
@@ -831,7 +632,6 @@ __device__ __noinline__ void chol_left_tile_role(int N_, gdp_t A_, int lda_, int
       }
       if (I + 1 < NBK) load_tiles(I + 1);
     }
-    CLX_T(1, 10);
     __syncthreads();
   }
 }
@@ -856,100 +656,28 @@ __global__ __launch_bounds__(CM_NT) void chol_left_mfma_kernel(int N, double* __
     chol_left_tile_role<CL_MAXS, CL_GS, PANEL>(N, (gdp_t)A, lda, wv, ui, dgp, nt, panels);
 }
 
-static int launch_chol_mfma(int form, int N, double* A, int lda, double* logdet, uint32_t* status, int batch, size_t a_stride, size_t ld_stride,
-                             hipStream_t st) {
-  if (form == 1) {
-    const size_t fixed_lds = sizeof(double) * CL_LDS_FIXED, panel_lds = fixed_lds + sizeof(double) * 2 * 16 * (size_t)(((N + 15) >> 4) << 4);
-    if (N <= 400) {  // 1 + 6 * 4 tiles in the first block row
-      MCP_ENSURE_MAX_LDS((chol_left_mfma_kernel<4, 4, true>));
-      hipLaunchKernelGGL((chol_left_mfma_kernel<4, 4, true>), dim3(batch), dim3(CM_NT), panel_lds, st, N, A, lda, logdet, status, a_stride, ld_stride);
-    } else if (N <= 576) {  // (two panels of 16 x 576 doubles: 144 KiB, + 10 KiB, of the 160)
-      MCP_ENSURE_MAX_LDS((chol_left_mfma_kernel<8, 2, true>));
-      hipLaunchKernelGGL((chol_left_mfma_kernel<8, 2, true>), dim3(batch), dim3(CM_NT), panel_lds, st, N, A, lda, logdet, status, a_stride, ld_stride);
-    } else if (N <= 784) {  // 1 + 6 * 8
-      hipLaunchKernelGGL((chol_left_mfma_kernel<8, 2, false>), dim3(batch), dim3(CM_NT), fixed_lds, st, N, A, lda, logdet, status, a_stride, ld_stride);
-    } else {  // 1 + 6 * 12 >= 72 (N <= 1152)
-      hipLaunchKernelGGL((chol_left_mfma_kernel<12, 2, false>), dim3(batch), dim3(CM_NT), fixed_lds, st, N, A, lda, logdet, status, a_stride, ld_stride);
-    }
-  } else {
-    const size_t lds = sizeof(double) * (256 + (size_t)16 * (N + 16));
-    MCP_ENSURE_MAX_LDS(chol_factor_mfma_kernel);
-    hipLaunchKernelGGL(chol_factor_mfma_kernel, dim3(batch), dim3(CM_NT), lds, st, N, A, lda, logdet, status, a_stride, ld_stride);
+static int launch_chol_left(int N, double* A, int lda, double* logdet, uint32_t* status, int batch, size_t a_stride, size_t ld_stride, hipStream_t st) {
+  const size_t fixed_lds = sizeof(double) * CL_LDS_FIXED, panel_lds = fixed_lds + sizeof(double) * 2 * 16 * (size_t)(((N + 15) >> 4) << 4);
+  if (N <= 400) {  // 1 + 6 * 4 tiles in the first block row
+    MCP_ENSURE_MAX_LDS((chol_left_mfma_kernel<4, 4, true>));
+    hipLaunchKernelGGL((chol_left_mfma_kernel<4, 4, true>), dim3(batch), dim3(CM_NT), panel_lds, st, N, A, lda, logdet, status, a_stride, ld_stride);
+  } else if (N <= 576) {  // (two panels of 16 x 576 doubles: 144 KiB, + 10 KiB, of the 160)
+    MCP_ENSURE_MAX_LDS((chol_left_mfma_kernel<8, 2, true>));
+    hipLaunchKernelGGL((chol_left_mfma_kernel<8, 2, true>), dim3(batch), dim3(CM_NT), panel_lds, st, N, A, lda, logdet, status, a_stride, ld_stride);
+  } else if (N <= 784) {  // 1 + 6 * 8
+    hipLaunchKernelGGL((chol_left_mfma_kernel<8, 2, false>), dim3(batch), dim3(CM_NT), fixed_lds, st, N, A, lda, logdet, status, a_stride, ld_stride);
+  } else {  // 1 + 6 * 12 >= 72 (N <= 1152)
+    hipLaunchKernelGGL((chol_left_mfma_kernel<12, 2, false>), dim3(batch), dim3(CM_NT), fixed_lds, st, N, A, lda, logdet, status, a_stride, ld_stride);
   }
   MCP_LAUNCH_CHECK();
   return MCP_OK;
 }
 
-// Uinv = U^-1 by 16x16 blocks, one workgroup: the diagonal blocks W_I = U_II^-1 in registers (one wave each), then block diagonal
-// d = 1, 2, ...:  Uinv[I][J] = - W_I sum_{K = I+1..J} U[I][K] Uinv[K][J],  J = I + d  (every term was finished in an earlier stage).
-__global__ __launch_bounds__(CM_NT) void tri_inverse_block_kernel(int N, const double* __restrict__ U, int ldu, double* __restrict__ Ui, int ldi,
-                                                                  size_t u_stride, size_t ui_stride) {
-  U += (size_t)blockIdx.x * u_stride;
-  Ui += (size_t)blockIdx.x * ui_stride;
-  const int tid = threadIdx.x, lane = tid & 63, kq = lane >> 4, li = lane & 15;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int NBK = (N + 15) >> 4;
-  for (int idx = tid; idx < N * N; idx += CM_NT) {  // zeros below the diagonal (and everywhere a block is not written)
-    const int r = idx / N, c = idx - r * N;
-    if (c < r) Ui[(size_t)r * ldi + c] = 0.0;
-  }
-  for (int kbk = wv; kbk < NBK; kbk += CM_NW) {
-    const int kb = kbk << 4, nb = min(16, N - kb), c = li;
-    double x[16], inv_d[16], w[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) x[r] = (r <= c && c < nb) ? U[(size_t)(kb + r) * ldu + kb + c] : (r == c ? 1.0 : 0.0);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) inv_d[r] = 1.0 / lane_get(x[r], r);
-    tri16_inverse(x, inv_d, c, w);
-    if (lane < 16 && c < nb) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        if (r < nb && r <= c) Ui[(size_t)(kb + r) * ldi + kb + c] = w[r];
-    }
-  }
-  __syncthreads();
-  for (int d = 1; d < NBK; ++d) {
-    for (int I = wv; I + d < NBK; I += CM_NW) {
-      const int J = I + d;
-      const int col = 16 * J + li;
-      v4d_p acc = {0.0, 0.0, 0.0, 0.0};
-      for (int K = I + 1; K <= J; ++K) {
-        double av[4], bv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int ar = 16 * I + li, ac = 16 * K + 4 * u + kq;   // A[i = li][k]   = U[16 I + i][16 K + k]
-          const int br = 16 * K + 4 * u + kq;                     // B[k][j = li]   = Uinv[16 K + k][16 J + j]
-          av[u] = (ar < N && ac < N) ? U[(size_t)ar * ldu + ac] : 0.0;
-          bv[u] = (br < N && col < N) ? Ui[(size_t)br * ldi + col] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u], acc, 0, 0, 0);
-      }
-      // - W_I S: register u of the accumulator is row 4 u + kq of S -- the B operand of step u
-      v4d_p out = {0.0, 0.0, 0.0, 0.0};
-      double wa[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int ar = 16 * I + li, ac = 16 * I + 4 * u + kq;
-        wa[u] = (ar < N && ac < N) ? -Ui[(size_t)ar * ldi + ac] : 0.0;
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) out = __builtin_amdgcn_mfma_f64_16x16x4f64(wa[u], acc[u], out, 0, 0, 0);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 16 * I + kq + 4 * r;
-        if (row < N && col < N) Ui[(size_t)row * ldi + col] = out[r];
-      }
-    }
-    __syncthreads();
-  }
-}
-
 // Round 4: U^-1 by BLOCK COLUMNS.  Column J of X = U^-1 depends on U alone:  X[J][J] = W_J = U_JJ^-1,  X[I][J] = - W_I sum_{K = I+1..J} U[I][K]
 // X[K][J]  for I = J-1 .. 0 -- a serial chain over I inside a column, no dependence between columns.  So: one launch inverts the
-// diagonal blocks (one wave each), a second one gives every block column its own one-wave workgroup, which keeps the column's finished
-// blocks in LDS (the B operands of its later products): no workgroup barrier anywhere, NBK x G workgroups in flight instead of one
-// (the block-diagonal sweep above: NBK stages of at most NBK / 8 tile products per wave behind a barrier each -- 0.52 ms at N = 400).
+// diagonal blocks (one wave each), a second one gives every block column its own workgroup, which keeps the column's finished blocks in
+// LDS (the B operands of its later products): NBK x G workgroups in flight instead of one (a one-workgroup block-diagonal sweep: NBK
+// stages of at most NBK / 8 tile products per wave behind a barrier each -- 0.52 ms at N = 400).
 __global__ __launch_bounds__(64) void tri_diag_inverse_kernel(int N, const double* __restrict__ U, int ldu, double* __restrict__ Ui, int ldi,
                                                               size_t u_stride, size_t ui_stride) {
   U += (size_t)blockIdx.y * u_stride;
@@ -967,89 +695,7 @@ __global__ __launch_bounds__(64) void tri_diag_inverse_kernel(int N, const doubl
       if (r < nb) Ui[(size_t)(kb + r) * ldi + kb + c] = r <= c ? w[r] : 0.0;
   }
 }
-__global__ __launch_bounds__(64) void tri_inverse_cols_kernel(int N, const double* __restrict__ U, int ldu, double* __restrict__ Ui, int ldi,
-                                                              size_t u_stride, size_t ui_stride) {
-  extern __shared__ __attribute__((aligned(16))) double xs[];  // [J + 1][16][16]: the finished blocks of this column
-  U += (size_t)blockIdx.y * u_stride;
-  Ui += (size_t)blockIdx.y * ui_stride;
-  const int NBK = (N + 15) >> 4;
-  const int J = NBK - 1 - (int)blockIdx.x;  // (the longest columns start first)
-  const int lane = threadIdx.x, kq = lane >> 4, li = lane & 15;
-  const int col = 16 * J + li;
-  // X[J][J] = W_J (written by tri_diag_inverse_kernel)
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int row = 16 * J + kq + 4 * r;
-    xs[J * 256 + (kq + 4 * r) * 16 + li] = (row < N && col < N) ? Ui[(size_t)row * ldi + col] : 0.0;
-  }
-  // The chain of the column as one stream of ITEMS: for I = J-1 .. 0 the products S += U[I][K] X[K][J], K = I+1 .. J, then the item that
-  // closes the step, X[I][J] = -W_I S.  Every item is one 16x16 A operand from global memory (a block of U, or the diagonal inverse W_I)
-  // that does not depend on the chain: they are loaded TC_PF items ahead into a ring of register sets.  The loop body has no memory
-  // operation under a branch -- results stay in LDS until the end -- so the compiler can count the loads in flight.  (Round 4 first form:
-  // the prefetch sat under wave-uniform branches together with the stores of the results, the wait-count bookkeeping gave up and every
-  // item paid an L2 round trip: 78 us at N = 300 for a chain whose MFMAs take 18.)
-  constexpr int TC_PF = 6;
-  const gcdp_t Ug = (gcdp_t)U, Wg = (gcdp_t)Ui;
-  int If = J - 1, Kf = J, Ip = J - 1, Kp = J;  // fetch and process positions; K = J + 1 stands for the closing item of the step
-  double buf[TC_PF][4];
-  auto fetch = [&](double (&dst)[4]) {
-    const bool live = If >= 0;                 // (past the end of the stream: block (0, 0) of U, never used)
-    const int I = live ? If : 0;
-    const bool closing = live && Kf > J;
-    const gcdp_t base = closing ? Wg : Ug;     // (uniform)
-    const int ld = closing ? ldi : ldu, kc = live ? (closing ? I : Kf) : 0;
-    const unsigned rowoff = (unsigned)((16 * I + li) * ld);  // A[i = li][k]: block row 16 I + i (< N: I < J)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int ac = 16 * kc + 4 * u + kq;
-      const double v = base[rowoff + (unsigned)min(ac, N - 1)];
-      dst[u] = ac < N ? v : 0.0;
-    }
-    if (live && ++Kf > J + 1) {  // (scalar bookkeeping)
-      --If;
-      Kf = If + 1;
-    }
-  };
-#pragma unroll
-  for (int q = 0; q < TC_PF; ++q) fetch(buf[q]);
-  v4d_p acc = {0.0, 0.0, 0.0, 0.0};
-  const int items = J * (J + 1) / 2 + J;
-  for (int q0 = 0; q0 < items; q0 += TC_PF) {
-#pragma unroll
-    for (int q = 0; q < TC_PF; ++q) {
-      if (Ip >= 0) {  // (wave-uniform; MFMAs and LDS only)
-        if (Kp <= J) {
-          double bv[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) bv[u] = xs[Kp * 256 + (4 * u + kq) * 16 + li];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(buf[q][u], bv[u], acc, 0, 0, 0);
-          ++Kp;
-        } else {  // X[I][J] = - W_I S  (register u of the accumulator is row 4 u + kq of S: the B operand of step u)
-          v4d_p out = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-          for (int u = 0; u < 4; ++u) out = __builtin_amdgcn_mfma_f64_16x16x4f64(-buf[q][u], acc[u], out, 0, 0, 0);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) xs[Ip * 256 + (kq + 4 * r) * 16 + li] = col < N ? out[r] : 0.0;
-          acc = (v4d_p){0.0, 0.0, 0.0, 0.0};
-          --Ip;
-          Kp = Ip + 1;
-        }
-      }
-      fetch(buf[q]);  // this register set: the item TC_PF further on
-    }
-  }
-  // the column, from LDS: blocks 0 .. J-1 (block J is already there), zeros below
-  for (int idx = lane; idx < 16 * J * 16; idx += 64) {
-    const int row = idx >> 4, c = 16 * J + (idx & 15);
-    if (c < N) Ui[(size_t)row * ldi + c] = xs[idx];
-  }
-  for (int row = 16 * (J + 1) + kq; row < N; row += 4)
-    if (col < N) Ui[(size_t)row * ldi + col] = 0.0;
-}
-// Kinv = Uinv Uinv^T by 16x16 tiles on the matrix cores, one wave per tile (I <= J) of the upper triangle, mirrored into the lower:
-//   Kinv[I][J] = sum_{K >= J} Uinv[I][K] Uinv[J][K]^T      (both operands read rows of Uinv: A[i][k] = Ui[16 I + i][16 K + k], B[k][j] = Ui[16 J + j][16 K + k])
-// The same column by FOUR waves (round 4, second form).  Step I of the chain is a sum of J - I block products followed by one closing
+// One block column per workgroup of FOUR waves.  Step I of the chain is a sum of J - I block products followed by one closing
 // product: the products of a step are dealt to the four waves (item m = J - K of the step to wave m mod 4, oldest blocks first, so that the
 // one product that needs the block finished in the previous step, K = I + 1, is the last of its wave), partial sums meet in LDS, wave 0
 // adds them and closes the step while the others are already in the next one.  Per step two LDS-only barriers (s_waitcnt lgkmcnt(0) +
@@ -1204,6 +850,8 @@ __global__ __launch_bounds__(256) void tri_inverse_cols4_kernel(int N, const dou
     if (col < N) Ui[(size_t)row * ldi + col] = 0.0;
 }
 
+// Kinv = Uinv Uinv^T by 16x16 tiles on the matrix cores, one wave per tile (I <= J) of the upper triangle, mirrored into the lower:
+//   Kinv[I][J] = sum_{K >= J} Uinv[I][K] Uinv[J][K]^T      (both operands read rows of Uinv: A[i][k] = Ui[16 I + i][16 K + k], B[k][j] = Ui[16 J + j][16 K + k])
 __global__ __launch_bounds__(256) void kinv_tiles_kernel(int N, const double* __restrict__ Ui, int ldi, double* __restrict__ Kinv, int ldk,
                                                          size_t ui_stride, size_t k_stride) {
   Ui += (size_t)blockIdx.y * ui_stride;
@@ -1348,21 +996,7 @@ __global__ __launch_bounds__(SOD_NT) void sod_select_kernel(mcp_kernel kn, int N
   // the scan: point p (the n-th of the subset) has just been accepted; every later candidate gets its component n, is tested, and the
   // smallest index that passes is the next p
   int n = 0, p = 0, slot = 0;
-#ifdef SOD_STAMPS
-  unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tq;
-#define SOD_STAMP(k)                                       \
-  {                                                        \
-    unsigned long long tn_ = __builtin_amdgcn_s_memtime(); \
-    st[k] += tn_ - tq;                                     \
-    tq = tn_;                                              \
-  }
-#else
-#define SOD_STAMP(k)
-#endif
   while (true) {
-#ifdef SOD_STAMPS
-    tq = __builtin_amdgcn_s_memtime();
-#endif
     if (tid == 0) {
       idx_out[n] = p;
       s_next[slot == 2 ? 0 : slot + 1] = N;  // next round's slot: last read two rounds ago
@@ -1378,9 +1012,7 @@ __global__ __launch_bounds__(SOD_NT) void sod_select_kernel(mcp_kernel kn, int N
     const bool own0 = grp == 0 && c0 < N && c0 > p;
     double kcp0 = 0.0;
     if (own0) kcp0 = kern_eval(kn, X + (size_t)c0 * D, 1, xp, 1);
-    SOD_STAMP(0)
     __syncthreads();
-    SOD_STAMP(1)
     const double rd = piv[0];
     const int per = (n + JS - 1) / JS, j0 = grp * per, j1 = min(n, j0 + per);
     for (int q = 0; q < CPT; ++q) {
@@ -1420,11 +1052,9 @@ __global__ __launch_bounds__(SOD_NT) void sod_select_kernel(mcp_kernel kn, int N
         }
       }
       double dot = (a0 + a1) + (a2 + a3);
-      SOD_STAMP(2)
       if (JS > 1) {
         if (grp > 0) part[tid] = dot;
         __syncthreads();
-        SOD_STAMP(3)
         if (grp == 0)
           for (int g = 1; g < JS; ++g) dot += part[g * C + c0];
       }
@@ -1444,23 +1074,13 @@ __global__ __launch_bounds__(SOD_NT) void sod_select_kernel(mcp_kernel kn, int N
       const unsigned long long bal = __ballot(pass);
       if (pass && (bal & ((1ull << (tid & 63)) - 1ull)) == 0ull) atomicMin(&s_next[slot], c);
     }
-    SOD_STAMP(4)
     __syncthreads();
-    SOD_STAMP(5)
     n += 1;
     p = s_next[slot];
     slot = slot == 2 ? 0 : slot + 1;
     if (p >= N) break;
   }
   if (tid == 0) *n_out = n;
-#ifdef SOD_STAMPS
-  if (tid == 256 || tid == 0 || tid == 256 + C) {  // into the unused tail rows of W (n < N rows are written when anything was rejected)
-    unsigned long long* o = (unsigned long long*)(W + (size_t)(N - 1) * N) + (tid == 0 ? 0 : (tid == 256 ? 8 : 16));
-    for (int k = 0; k < 6; ++k) o[k] = st[k];
-    o[6] = (unsigned long long)n;
-    o[7] = __builtin_amdgcn_s_memrealtime();
-  }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1474,11 +1094,7 @@ __global__ __launch_bounds__(SOD_NT) void sod_select_kernel(mcp_kernel kn, int N
 //   gx: hdr[g][parity][4] = {index, 1/pivot lo, hi, -} | vec[g][parity][N][2]
 // Every poll is bounded; a partner that never arrives ends the kernel with *n_out = -1 (the grid must be resident: G <= 64 workgroups).
 // ---------------------------------------------------------------------------------------
-#ifdef SODM_MIN_OVERRIDE  // (experiment builds: where the multi-workgroup form starts to pay)
-constexpr int SODM_MIN = SODM_MIN_OVERRIDE;
-#else
 constexpr int SODM_MIN = 256;  // (N = 300: 1.32 -> 0.83 ms; below, the one-workgroup kernel's 12 k cycles per point are at the exchange's level)
-#endif
 constexpr unsigned SODM_SPIN = 1u << 22;
 typedef unsigned long long __attribute__((address_space(1))) * sod_gu64_t;
 __device__ __forceinline__ void sod_put(sod_gu64_t g, unsigned tag, unsigned v) {
@@ -1529,17 +1145,6 @@ __global__ __launch_bounds__(SOD_NT) void sod_select_multi_kernel(mcp_kernel kn,
   __syncthreads();
   int n = 0, p = 0;
   bool failed = false;
-#ifdef SODM_STAMPS
-  unsigned long long sst[8] = {0, 0, 0, 0, 0, 0, 0, 0}, stq = clock64();
-#define SODM_STAMP(k)                      \
-  {                                        \
-    unsigned long long tn_ = clock64();    \
-    sst[k] += tn_ - stq;                   \
-    stq = tn_;                             \
-  }
-#else
-#define SODM_STAMP(k)
-#endif
   while (true) {
     const unsigned tag = (unsigned)n + 1u;
     const int par = n & 1;
@@ -1592,9 +1197,7 @@ __global__ __launch_bounds__(SOD_NT) void sod_select_multi_kernel(mcp_kernel kn,
       }
     }
     part[tid] = (a0 + a1) + (a2 + a3);
-    SODM_STAMP(0)
     __syncthreads();
-    SODM_STAMP(1)
     if (grp == 0) {  // wave 0: the shares in wave order, component n, the test, my first passing candidate
       double dot = part[lane];
 #pragma unroll
@@ -1618,9 +1221,7 @@ __global__ __launch_bounds__(SOD_NT) void sod_select_multi_kernel(mcp_kernel kn,
         shi[0] = first < 0 ? N : 64 * g + first;
       }
     }
-    SODM_STAMP(2)
     __syncthreads();
-    SODM_STAMP(3)
     {  // my candidate's vector w_c[0 .. n] (row n from LDS: it was formed a moment ago)
       const int cg = shi[0];
       if (cg < N) {
@@ -1632,7 +1233,6 @@ __global__ __launch_bounds__(SOD_NT) void sod_select_multi_kernel(mcp_kernel kn,
     // if that block has a passing candidate it is the smallest.  Waves 1-15 therefore ask for THAT workgroup's vector while wave 0 collects the
     // indices -- one round trip instead of two; when the block had no passing candidate (it publishes no vector) wave 0's verdict in LDS ends their
     // wait and everybody reads the true owner's.
-    SODM_STAMP(4)
     const int gpred = min(G - 1, (p + 1) >> 6);
     volatile int* verdict = shi + 3;
     if (grp == 0) {  // every workgroup's index of this round; the smallest is the next point
@@ -1685,9 +1285,7 @@ __global__ __launch_bounds__(SOD_NT) void sod_select_multi_kernel(mcp_kernel kn,
         if (!done) shi[2] = 1;
       }
     }
-    SODM_STAMP(5)
     __syncthreads();
-    SODM_STAMP(6)
     const int pn = shi[1];
     const bool hit = *verdict == (int)(2u * tag);
     if (shi[2]) {
@@ -1709,18 +1307,11 @@ __global__ __launch_bounds__(SOD_NT) void sod_select_multi_kernel(mcp_kernel kn,
     }
     p = pn;
     __syncthreads();
-    SODM_STAMP(7)
     if (shi[2]) {
       failed = true;
       break;
     }
   }
-#ifdef SODM_STAMPS
-  if (g == gridDim.x / 2 && (tid == 0 || tid == 512)) {  // (wave 0's lane 0 and a thread of wave 8, workgroup G / 2: into the one-workgroup kernel's tail of the workspace)
-    unsigned long long* o = (unsigned long long*)(W + (size_t)N * N) + (tid == 0 ? 0 : 8);
-    for (int k = 0; k < 8; ++k) o[k] = sst[k];
-  }
-#endif
   if (g == 0 && tid == 0) *n_out = failed ? -1 : n;
 }
 
@@ -1901,19 +1492,13 @@ extern "C" int mcp_cov_diag(const mcp_kernel* kern, int N, const double* X, int 
 
 // U^-1 and K^-1 = U^-1 U^-T of `batch` matrices (strides in doubles): diagonal blocks, block columns, tiles -- three launches
 static int launch_inverse_mfma(int N, const double* U, int ldu, double* Ui, int ldi, double* Kinv, int ldk, int batch, size_t u_stride,
-                               size_t ui_stride, size_t k_stride, hipStream_t st, bool one_wave_columns = false) {
+                               size_t ui_stride, size_t k_stride, hipStream_t st) {
   const int NBK = (N + 15) >> 4, nt = NBK * (NBK + 1) / 2;
   hipLaunchKernelGGL(tri_diag_inverse_kernel, dim3(NBK, batch), dim3(64), 0, st, N, U, ldu, Ui, ldi, u_stride, ui_stride);
   MCP_LAUNCH_CHECK();
-  if (one_wave_columns) {
-    MCP_ENSURE_MAX_LDS(tri_inverse_cols_kernel);
-    hipLaunchKernelGGL(tri_inverse_cols_kernel, dim3(NBK, batch), dim3(64), sizeof(double) * 256 * (size_t)NBK, st, N, U, ldu, Ui, ldi, u_stride,
-                       ui_stride);
-  } else {
-    MCP_ENSURE_MAX_LDS(tri_inverse_cols4_kernel);
-    hipLaunchKernelGGL(tri_inverse_cols4_kernel, dim3(NBK, batch), dim3(256), sizeof(double) * 256 * (size_t)(NBK + 3), st, N, U, ldu, Ui, ldi,
-                       u_stride, ui_stride);
-  }
+  MCP_ENSURE_MAX_LDS(tri_inverse_cols4_kernel);
+  hipLaunchKernelGGL(tri_inverse_cols4_kernel, dim3(NBK, batch), dim3(256), sizeof(double) * 256 * (size_t)(NBK + 3), st, N, U, ldu, Ui, ldi,
+                     u_stride, ui_stride);
   MCP_LAUNCH_CHECK();
   hipLaunchKernelGGL(kinv_tiles_kernel, dim3((nt + 3) / 4, batch), dim3(256), 0, st, N, Ui, ldi, Kinv, ldk, ui_stride, k_stride);
   MCP_LAUNCH_CHECK();
@@ -2031,7 +1616,7 @@ static int launch_chol_blocked(int N, double* A, int lda, double* logdet, uint32
     double* Akk = A + (size_t)k0 * lda + k0;
     double* ldk = A + (size_t)(N - 1) * lda + k;
     if (nb > 16) {
-      const int rc = launch_chol_mfma(1, nb, Akk, lda, ldk, status, 1, 0, 0, st);
+      const int rc = launch_chol_left(nb, Akk, lda, ldk, status, 1, 0, 0, st);
       if (rc != MCP_OK) return rc;
     } else {
       const size_t lds = sizeof(double) * ((size_t)CH_NB * (CH_NB + 1) + (size_t)CH_NB * nb);
@@ -2193,19 +1778,11 @@ static int launch_inverse_blocked(int N, const double* U, int ldu, double* Ui, i
   return MCP_OK;
 }
 
-// which form of the factorisation / inverse a call runs: 1 (default) the round-4/5 kernels, 0 the round-1/2 ones, 2 the round-3 one-workgroup
-// forms, 3 the round-4 forms with one-wave inverse columns -- requested per call (mcp_dispatch.chol_form, include/mcpilco_hip_debug.h)
-static int chol_form_of(const mcp_dispatch* d) { return !d ? 1 : (d->chol_form == 1 ? 0 : (d->chol_form == 2 ? 2 : (d->chol_form == 3 ? 3 : 1))); }
-
-extern "C" int mcp_chol_factor_ex(int N, double* A, int lda, double* logdet, uint32_t* status, void* stream, const mcp_dispatch* d) {
-  const int g_chol_mfma = chol_form_of(d);
+extern "C" int mcp_chol_factor(int N, double* A, int lda, double* logdet, uint32_t* status, void* stream) {
   if (!A || !logdet || !status || N <= 0 || lda < N) return MCP_ERR_ARG;
   if (N > 8192) return MCP_ERR_LIMIT;
-  if (g_chol_mfma == 1 && N >= CHB_MIN) return launch_chol_blocked(N, A, lda, logdet, status, (hipStream_t)stream);  // panels across the chip
-  if (N > 1152) return MCP_ERR_LIMIT;  // (the one-workgroup forms: test hooks 0, 2, 3)
-  if (g_chol_mfma && N > 16) {
-    return launch_chol_mfma(g_chol_mfma == 3 ? 1 : g_chol_mfma, N, A, lda, logdet, status, 1, 0, 0, (hipStream_t)stream);
-  }
+  if (N >= CHB_MIN) return launch_chol_blocked(N, A, lda, logdet, status, (hipStream_t)stream);  // panels across the chip
+  if (N > 16) return launch_chol_left(N, A, lda, logdet, status, 1, 0, 0, (hipStream_t)stream);
   size_t lds = sizeof(double) * ((size_t)CH_NB * (CH_NB + 1) + (size_t)CH_NB * N);
   MCP_ENSURE_MAX_LDS(chol_factor_kernel);
   hipLaunchKernelGGL(chol_factor_kernel, dim3(1), dim3(CH_NT), lds, (hipStream_t)stream, N, A, lda, logdet, status);
@@ -2213,33 +1790,17 @@ extern "C" int mcp_chol_factor_ex(int N, double* A, int lda, double* logdet, uin
   return MCP_OK;
 }
 
-extern "C" int mcp_chol_factor(int N, double* A, int lda, double* logdet, uint32_t* status, void* stream) {
-  return mcp_chol_factor_ex(N, A, lda, logdet, status, stream, nullptr);
-}
-
-extern "C" int mcp_chol_inverse_ex(int N, const double* U, int ldu, double* Uinv, int ldi, double* Kinv, int ldk, void* stream, const mcp_dispatch* d) {
-  const int g_chol_mfma = chol_form_of(d);
+extern "C" int mcp_chol_inverse(int N, const double* U, int ldu, double* Uinv, int ldi, double* Kinv, int ldk, void* stream) {
   if (!U || !Uinv || !Kinv || N <= 0 || ldu < N || ldi < N || ldk < N) return MCP_ERR_ARG;
   if (N > 16384) return MCP_ERR_LIMIT;
-  if (g_chol_mfma == 1 && N > 1152) return launch_inverse_blocked(N, U, ldu, Uinv, ldi, Kinv, ldk, (hipStream_t)stream);
-  if ((g_chol_mfma == 1 || g_chol_mfma == 3) && N > 16 && N <= 1152)  // (3: the one-wave-per-column form of the inverse)
-    return launch_inverse_mfma(N, U, ldu, Uinv, ldi, Kinv, ldk, 1, 0, 0, 0, (hipStream_t)stream, g_chol_mfma == 3);
-  if (g_chol_mfma && N > 16 && N <= 1152)  // (2: the round-3 block-diagonal sweep of one workgroup, kept as a comparison form)
-    hipLaunchKernelGGL(tri_inverse_block_kernel, dim3(1), dim3(CM_NT), 0, (hipStream_t)stream, N, U, ldu, Uinv, ldi, (size_t)0, (size_t)0);
-  else if (N <= 64 * TW_KM)
-    hipLaunchKernelGGL(tri_inverse_wave_kernel, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, N, U, ldu, Uinv, ldi);
-  else
-    hipLaunchKernelGGL(tri_inverse_kernel, dim3((N + TI_NT - 1) / TI_NT), dim3(TI_NT), sizeof(double) * N, (hipStream_t)stream, N, U,
-                       ldu, Uinv, ldi);
+  if (N > 1152) return launch_inverse_blocked(N, U, ldu, Uinv, ldi, Kinv, ldk, (hipStream_t)stream);
+  if (N > 16) return launch_inverse_mfma(N, U, ldu, Uinv, ldi, Kinv, ldk, 1, 0, 0, 0, (hipStream_t)stream);
+  hipLaunchKernelGGL(tri_inverse_wave_kernel, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, N, U, ldu, Uinv, ldi);
   MCP_LAUNCH_CHECK();
   dim3 grid((N + 255) / 256, N);
   hipLaunchKernelGGL(kinv_from_uinv_kernel, grid, dim3(256), 0, (hipStream_t)stream, N, Uinv, ldi, Kinv, ldk, (size_t)0, (size_t)0);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
-}
-
-extern "C" int mcp_chol_inverse(int N, const double* U, int ldu, double* Uinv, int ldi, double* Kinv, int ldk, void* stream) {
-  return mcp_chol_inverse_ex(N, U, ldu, Uinv, ldi, Kinv, ldk, stream, nullptr);
 }
 
 // out = A G A for a SYMMETRIC A (K^-1) and any G: S = G^T A, out = S^T A -- two products in the transposed-left form of tn_gemm_kernel
@@ -2756,7 +2317,7 @@ extern "C" int mcp_nll_epoch(int G, const mcp_nll_gp* gps, int N, int D, int pol
   }
   MCP_LAUNCH_CHECK();
   {
-    const int rc = launch_chol_mfma(1, N, g0 + L.K, N, g0 + L.logdet, status, G, L.per_gp, L.per_gp, st);
+    const int rc = launch_chol_left(N, g0 + L.K, N, g0 + L.logdet, status, G, L.per_gp, L.per_gp, st);
     if (rc != MCP_OK) return rc;
   }
   {

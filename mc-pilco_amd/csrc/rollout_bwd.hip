@@ -96,15 +96,9 @@ __host__ __device__ inline BwdLayout bwd_layout(int S, int U, int D, int G, int 
   return L;
 }
 
-#ifndef BW_LAUNDER
 #define BW_LAUNDER(PFM, PB) ((PFM) > 8 || (PB) > 1)  // (narrow class, one particle per workgroup -- the latency-bound small-swarm sweep: measured 7 % slower with it)
-#endif
-#ifndef BW_MASK_FROM
 #define BW_MASK_FROM 8  // classes with PFM beyond this run the RBF stage with chunk-level tests and masked values
-#endif
-#ifndef BW_WPE_A
 #define BW_WPE_A 2
-#endif
 #define BW_RPT 5  // record elements a thread prefetches at most (PB * record length <= BW_RPT * threads)
 
 // Per particle and time step the record is  [x_t (S) | u_t (U) | dJ/dx_t (S) | dJ/du_t (U) | d delta/dz (G*D)].
@@ -400,19 +394,6 @@ __global__ __launch_bounds__(MAXNT, WPE) void rollout_bwd_kernel(BwdArgs a) {
   double tgt_c = 0.0;                       // register chain, trajectory policies: the target entry of the step to come
   double xbr = 0.0, kp1 = 0.0, kp2 = 0.0;  // register chain: adjoint of x_t without the policy path; feature-map coefficients of step t+1
   unsigned long long last_stamp = clock64();
-#ifdef BWX_WSTAMPS  // experiment build: every wave's own intervals of a step (workgroup 0): chain + prefetch | barrier 1 | RBF stage | park | barrier 2
-  unsigned long long ws_[5] = {0, 0, 0, 0, 0}, wt_ = clock64();
-#define BW_WS(k)                                              \
-  do {                                                        \
-    if (a.stamps && blockIdx.x == 0) {                        \
-      const unsigned long long n_ = clock64();                \
-      ws_[k] += n_ - wt_;                                     \
-      wt_ = n_;                                               \
-    }                                                         \
-  } while (0)
-#else
-#define BW_WS(k)
-#endif
   for (int mbase = blockIdx.x * PB; mbase < M; mbase += gridDim.x * PB) {
     const int msp = imin(mbase + sp, M - 1);  // particle of this wave's serial chain
     const bool spvalid = mbase + sp < M;
@@ -714,10 +695,8 @@ __global__ __launch_bounds__(MAXNT, WPE) void rollout_bwd_kernel(BwdArgs a) {
       if (FASTCHAIN && t > 0 && serial) prefetch(pre, t - 1, mbase);
       if (!(PIPEC && pipe)) {  // (pipelined form: the barrier comes behind the RBF stage's first half, below)
         BW_STAMP(8);
-        BW_WS(0);
         lds_barrier();
         BW_STAMP(9);
-        BW_WS(1);
       }
       // ---- RBF network, thread b owns basis b, loops over the particle slots -----------------------------
       // dropout keep bits: one Philox draw serves 4 consecutive bases of one particle (philox_keep); the lanes of a quad
@@ -809,10 +788,8 @@ __global__ __launch_bounds__(MAXNT, WPE) void rollout_bwd_kernel(BwdArgs a) {
           // ---- pipelined form: everything above ran beside the chain; the record of step t - 1 has had that time to land ----
           if (t > 0) park(pre, cur ^ 1);
           BW_STAMP(8);
-          BW_WS(0);
           lds_barrier();
           BW_STAMP(9);
-          BW_WS(1);
         }
         if (act && pv) {
           double phibar = 0.0;
@@ -867,16 +844,13 @@ __global__ __launch_bounds__(MAXNT, WPE) void rollout_bwd_kernel(BwdArgs a) {
         }
       }
       BW_STAMP(10);
-      BW_WS(2);
       if (PIPEC && pipe) {
         if (serial && t > 0) chain_prep(t - 1, cur ^ 1);  // (beside the RBF waves' adjoint half: the record was parked before the barrier)
       } else if (t > 0) {
         park(pre, cur ^ 1);
       }
       cur ^= 1;
-      BW_WS(3);
       lds_barrier();
-      BW_WS(4);
     }
     // finish step 0: adjoint of x_0
     if constexpr (FASTCHAIN) {
@@ -922,10 +896,6 @@ __global__ __launch_bounds__(MAXNT, WPE) void rollout_bwd_kernel(BwdArgs a) {
     lds_barrier();
   }
 
-#ifdef BWX_WSTAMPS
-  if (a.stamps && blockIdx.x == 0 && lane == 0)
-    for (int k = 0; k < 5; ++k) a.stamps[16 + wv * 5 + k] = ws_[k];
-#endif
   // ---- write this workgroup's partial parameter gradients ------------------------------------
   const int nparam = PF + B * PF + U * B;  // (+ U when the policy has a bias: the slab stride)
   double* out = a.slab + (size_t)blockIdx.x * (nparam + (pl.bias ? U : 0));
@@ -989,9 +959,7 @@ __global__ __launch_bounds__(MAXNT, WPE) void rollout_bwd_kernel(BwdArgs a) {
 //     (all of it depends on x_t only), so that behind it only the multiply-adds and the 8-value wave sum remain.
 // Same gradients as the general kernel up to summation order (tests/test_gpu_parity.py compares them on every policy kind it covers).
 #define BL_GM 4    // GPs
-#ifndef BL_MAX_M
 #define BL_MAX_M 3072  // largest swarm the lean sweep takes (tools/sweep_bwd_particles.py on a 256-CU device: it wins up to ~3000 particles)
-#endif
 #define BL_FL0 8   // first feature lane of wave 0
 #define BL_UL0 16  // first input lane of wave 0
 // (scalar members only: with arrays inside, part of the struct stayed a stack object -- two of its prefetched values went through
@@ -1021,9 +989,7 @@ __device__ __forceinline__ void bl_for_g(F&& f) {
     bl_for_g<g + 1, GM>(f);
   }
 }
-#ifndef BL_SW
-#define BL_SW 1  // the RBF wave whose intervals are stamped (diagnostic builds: build.py --variant)
-#endif
+#define BL_SW 1  // the RBF wave whose intervals are stamped
 #define BL_STAMP(k)                                          \
   do {                                                       \
     if (a.stamps && lane == 0 && blockIdx.x == 0 && slot == 0) { \

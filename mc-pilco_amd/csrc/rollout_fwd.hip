@@ -35,9 +35,7 @@ using namespace mcp;
 #define RF_MAX_NA 7  // accumulators per Jacobian item: 2 (SE), 3 (SE+P1), 7 (SE+P2)
 #define RF_MAX_CHUNKS (MCP_MAX_GP * (MCP_MAX_TRAIN / 128))
 #define RF_GS 8  // rows of Kinv per register buffer (two buffers in flight per wave)
-#ifndef RF_NRES
 #define RF_NRES 1  // register groups of Kinv a wave keeps resident for the whole rollout (GP-sharded 4-particle launch)
-#endif
 
 struct FwdLayout {
   int mk;  // dropout keep bits of the step, one int per (particle, 4 basis functions): drawn in phase S by idle waves
@@ -1186,13 +1184,9 @@ static int pick_particles_per_wg(int M) {
 
 // What a call may be asked to do differently from the automatic dispatch, and what it reports back: carried by the call itself
 // (mcp_dispatch, include/mcpilco_hip_debug.h) -- the library holds no dispatch state.  The values below are the ones the dispatch code reads.
-// the automatic row split of the GP-sharded 16-particle kernel: parts and deal (experiment builds may change them: -DMCP_ROW_PARTS_DEFAULT=2 ...)
-#ifndef MCP_ROW_PARTS_DEFAULT
+// the automatic row split of the GP-sharded 16-particle kernel: parts and deal
 #define MCP_ROW_PARTS_DEFAULT 3
-#endif
-#ifndef MCP_ROW_PART_MAJOR_DEFAULT
 #define MCP_ROW_PART_MAJOR_DEFAULT 1
-#endif
 struct FwdHooks {
   int force_ppw = 0;     // particles per workgroup (0 = automatic)
   int force_xlds = -1;   // -1 automatic, 0 never stage small operands in LDS

@@ -53,15 +53,7 @@ using namespace mcp;
 #define RL_UM 2   // inputs, zero padded
 #define RL_ZD (RL_DSM + RL_UM)
 #define RL_PFM 6  // policy features, zero padded
-#ifndef RL_NRES
 #define RL_NRES 2  // register buffers kept resident: RL_NRES or RL_NRES + 1, whichever leaves an even number to stream
-#endif
-#ifndef RL_NRES_CUT2
-#define RL_NRES_CUT2 0  // resident buffers the degree-2 / 4-particle instantiation gives up (experiment switch)
-#endif
-#ifndef RL_PRE
-#define RL_PRE 0  // register buffers of the Kinv stream issued ahead of the barrier that ends phase K (0, 1, 2): measured equal
-#endif           // within 1 % (what the stream gains the phase before it loses waiting at the full memory queue)
 
 // LDS plan: the regions whose size is bounded by compile-time limits come first, at compile-time offsets (no scalar register per
 // pointer); the ones sized by N and B follow
@@ -200,23 +192,12 @@ __global__ void kt_pack_kernel(mcp_model md, double* __restrict__ kt, int stride
 // accumulators with v_mov_b64 where branches meet; behind an asm statement those copies read registers the matrix core has not
 // written yet -- seen as wrong trajectories the moment the copies landed right behind an MFMA).  Measured equal in speed
 // (tools/v4_bench.hip, both forms).
-__device__ __forceinline__ void mfma4(double& acc, double a, double b) {
-#ifdef RLX_NOFMA  // experiment: the stream alone
-  asm volatile("" : "+v"(acc) : "v"(a), "v"(b));
-#else
-  acc = __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, acc, 0, 0, 0);
-#endif
-}
+__device__ __forceinline__ void mfma4(double& acc, double a, double b) { acc = __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, acc, 0, 0, 0); }
 
 // buffer b of this wave's stream = its tiles [6 b, 6 b + 6) (p: the lane's slot of tile 0).  A buffer may run past the end of the
 // stream: those tiles are the next wave's (the workspace ends with a buffer of slack) and meet k = 0.
 __device__ __forceinline__ void kt_load(v2d (&A)[KT_NL], gptr2_t p, int b) {
   const gptr2_t pb = p + (size_t)b * (KT_NL * 64);
-#ifdef RLX_NOLOAD  // experiment: the MFMAs alone
-#pragma unroll
-  for (int s = 0; s < KT_NL; ++s) asm volatile("" : "=v"(A[s]) : "v"(pb));
-  return;
-#endif
 #pragma unroll
   for (int s = 0; s < KT_NL; ++s) A[s] = pb[s * 64];
 }
@@ -257,23 +238,22 @@ __device__ __forceinline__ void kt_use(const v2d (&A)[KT_NL], const v2d (&K)[3],
     }
   }
 }
-// this wave's whole stream, double buffered; bufA / bufB hold buffers nres and nres + 1 already when npre says so (issued ahead of
-// the barrier).  The steady-state loop issues its reloads UNCONDITIONALLY (nb - nres is even and >= 2, kt_resident_count): with a
-// test around the reloads the compiler must assume at every use that no younger loads are outstanding and waits for vmcnt(5..0) --
-// for the OTHER buffer's loads as well, i.e. no double buffering at all (seen in the ISA).
+// this wave's whole stream, double buffered in bufA / bufB (the caller's arrays, declared outside its loop over segments).  The
+// steady-state loop issues its reloads UNCONDITIONALLY (nb - nres is even and >= 2, kt_resident_count): with a test around the reloads
+// the compiler must assume at every use that no younger loads are outstanding and waits for vmcnt(5..0) -- for the OTHER buffer's
+// loads as well, i.e. no double buffering at all (seen in the ISA).
 template <int P, int NRES>
 __device__ __forceinline__ void kt_stream(gptr2_t p, int nrt, int njg, const double* kb, int lane, double (&acc3)[2][3], double (&acc2)[2][2],
-                                          const v2d (&res)[NRES + 1][KT_NL], int rlo, int nres, v2d (&bufA)[KT_NL], v2d (&bufB)[KT_NL],
-                                          int npre) {
+                                          const v2d (&res)[NRES + 1][KT_NL], int rlo, int nres, v2d (&bufA)[KT_NL], v2d (&bufB)[KT_NL]) {
   // (the stream's first nres buffers are resident in res[rlo .. rlo + nres))
   const int nb = (nrt * njg + KT_NL - 1) / KT_NL;
   const int gpb = nrt == 3 ? 2 : 3;  // column groups per buffer
   const double* ka = kb + (lane >> 4) * P + ((lane & 3) < P ? (lane & 3) : 0);
   int b = nres;
   v2d kA[3], kB[3];
-  if (npre < 1) kt_load(bufA, p, b);
+  kt_load(bufA, p, b);
   kt_readk<P>(kA, ka, b * gpb);
-  if (npre < 2) kt_load(bufB, p, b + 1);
+  kt_load(bufB, p, b + 1);
   kt_readk<P>(kB, ka, (b + 1) * gpb);
 #pragma unroll
   for (int r = 0; r < NRES + 1; ++r) {
@@ -774,10 +754,10 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
   const gptr2_t vp = (gptr2_t)(a.kt + (size_t)myg * a.kt_stride + (size_t)vrt0 * vnjg * 128) + (tid0 & 63);
   const gptr2_t vpb = (gptr2_t)(a.kt + (size_t)myg * a.kt_stride + (size_t)vrt0b * vnjg * 128) + (tid0 & 63);
   const int vnt = vnrt * vnjg;  // tiles in this wave's (first) stream
-  // (degree-2 polynomial kernels at 4 particles: one resident buffer fewer -- the two halves of phase K carry six values per item
-  //  across the barrier in between, and with three resident buffers the allocator spilled one of them to scratch: its reload in
-  //  phase V waits with vmcnt(0), i.e. for the whole stream in flight: +1-2 k cycles per wave and step)
-  constexpr int NRES = (MAXDEG >= 2 && P == 4) ? (RL_NRES > 1 ? RL_NRES - RL_NRES_CUT2 : RL_NRES) : RL_NRES;
+  // (not three: in the degree-2 polynomial kernels at 4 particles the two halves of phase K carry six values per item across the
+  //  barrier in between, and with three resident buffers the allocator spilled one of them to scratch: its reload in phase V waits
+  //  with vmcnt(0), i.e. for the whole stream in flight: +1-2 k cycles per wave and step)
+  constexpr int NRES = RL_NRES;
   v2d vres[NRES + 1][KT_NL];  // (+ 1: a wave whose buffer count has the other parity keeps one more or one fewer)
   // the second segment streams an even number of buffers as well: with an odd count its first buffer takes the register array's last slot
   // (the first segment then keeps at most NRES)
@@ -1015,12 +995,7 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
       }
     }
     if (t == T - 1) break;
-    // ---- phase V, first half: issue the head of this wave's Kinv stream (independent of k) ----
-    v2d bufA[KT_NL], bufB[KT_NL];
-    if (RL_PRE > 0 && vnrt > 0) {
-      kt_load(bufA, vp, nres);
-      if (RL_PRE > 1) kt_load(bufB, vp, nres + 1);
-    }
+    v2d bufA[KT_NL], bufB[KT_NL];  // (phase V's stream buffers)
     // ---- phase K, second half: the input dimensions and the exp ----
     {
       const int Nown = gpl[0].N;
@@ -1069,7 +1044,6 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
           if (j < Npad) {
             kb[it] = kt;
             double* w = vb + it * NWC;  // the record of (j, p): it = j P + p
-#ifndef RLX_NOWREC  // (experiment switch: timing without the phase-J records of phase K)
             v2d w01;
             w01.x = kv * al_l[j];
             w01.y = kv;
@@ -1080,7 +1054,6 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
               w23.y = qa;
               *reinterpret_cast<v2d*>(__builtin_assume_aligned(w + 2, 16)) = w23;
             }
-#endif
           }
         }
       }
@@ -1089,9 +1062,6 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
     RL_STAMP(3);
     // ---- phase V, second half: v = Kinv k on the 4x4x4 MFMA, then the phase-J weights of this wave's rows ----
     const unsigned long long tv0_ = stamping ? clock64() : 0;
-#ifdef RLX_PRIO  // experiment: issue priority for the waves that end the phase (1: the younger wave of every SIMD, 2: the waves with three row tiles)
-    if (RLX_PRIO == 1 ? wv >= 4 : vnrt >= 3) __builtin_amdgcn_s_setprio(2);
-#endif
     if (vnrt > 0) {
       double jacc[NCG][2];  // this wave's partial tile of phase J (both segments)
 #pragma unroll
@@ -1104,7 +1074,7 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
         for (int r = 0; r < 3; ++r) acc3[0][r] = acc3[1][r] = 0.0;
 #pragma unroll
         for (int r = 0; r < 2; ++r) acc2[0][r] = acc2[1][r] = 0.0;
-        kt_stream<P, NRES>(sg ? vpb : vp, nrt, vnjg, kb, lane, acc3, acc2, vres, sg ? NRES : 0, sg ? nresb : nres, bufA, bufB, sg ? 0 : RL_PRE);
+        kt_stream<P, NRES>(sg ? vpb : vp, nrt, vnjg, kb, lane, acc3, acc2, vres, sg ? NRES : 0, sg ? nresb : nres, bufA, bufB);
         kt_tail<P, MAXDEG>(acc3, acc2, rt0, nrt, kb, al_l, vb, lane);
         if (stamping && lane == 0 && sg == nseg - 1) stl[16 + wv] += clock64() - tv0_;  // this wave's own phase V
         // ---- phase J over the rows this wave has just finished (wave-level ordering only) ----
@@ -1120,15 +1090,12 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
       for (int g = 0; g < NCG; ++g) red[(wv * NCG + g) * 64 + lean_j_slot(lane)] = jacc[g][0] + jacc[g][1];
       // the z-only polynomial terms of this step (2.3 k cycles of one wave: LDS round trips in series), by wave 0 behind its own phase J --
       // it owns the fewest rows of Kinv and would wait ~4 k cycles at the barrier below; phase F (wave 0 itself) reads the result.
-      // (At the end of phase K on a wave without an item in the last round it lengthened that phase by 0.9 k: profiles/r04_lean_variants.txt.)
+      // (At the end of phase K on a wave without an item in the last round it lengthened that phase by 0.9 k: round 4, profiles/NOTES.md.)
       if (MAXDEG > 0 && wv == 0) lean_prefz<P, MAXDEG>(z, kpar, pc, fz, gpl[0].lambda, D, lane);
     } else {
 #pragma unroll
       for (int g = 0; g < NCG; ++g) red[(wv * NCG + g) * 64 + lane] = 0.0;  // (a wave without rows)
     }
-#ifdef RLX_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
     lds_barrier();  // B4
     RL_STAMP(6);
     if (wv == 0) {

@@ -12,15 +12,11 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libmcpilco_hip.so")
-# Kernel experiments (tools/, variant builds of mc-pilco_amd/build.py --variant*) may load another build: only when they ask for it by
-# MCPILCO_HIP_EXPERIMENT=1 next to MCPILCO_HIP_LIB -- a stray MCPILCO_HIP_LIB alone never swaps the product library.
-if os.environ.get("MCPILCO_HIP_EXPERIMENT") == "1" and os.environ.get("MCPILCO_HIP_LIB"):
-    LIB_PATH = os.environ["MCPILCO_HIP_LIB"]
 
 MAX_GP, MAX_STATE, MAX_INPUT, MAX_GPDIM, MAX_PFEAT, MAX_BASIS, MAX_TRAIN = 8, 16, 8, 32, 32, 1024, 4096
 OK = 0
 ERRORS = {-1: "MCP_ERR_ARG", -2: "MCP_ERR_LIMIT", -3: "MCP_ERR_WORKSPACE", -4: "MCP_ERR_LAUNCH", -5: "MCP_ERR_COMM"}
-ABI_VERSION = 6
+ABI_VERSION = 7
 COMM_ID_BYTES = 128
 STATUS_NAN, STATUS_NONPOS_VAR, STATUS_NOT_SPD, STATUS_SYNC = 1, 2, 4, 8
 FWD_NO_GP_SHARDING = 2  # flag in mcp_rollout_fwd's particle_pred argument (MCP_FWD_NO_GP_SHARDING)
@@ -88,7 +84,7 @@ class Dispatch(C.Structure):
     """include/mcpilco_hip_debug.h: struct mcp_dispatch -- the request a call carries (all zero = automatic) and what it reports back."""
     _fields_ = [("fwd_particles", C.c_int32), ("gp_sharding", C.c_int32), ("fwd_lean", C.c_int32), ("policy_split", C.c_int32), ("row_split", C.c_int32),
                 ("cluster_map", C.c_int32), ("fwd_no_xlds", C.c_int32),
-                ("fwd_gb", C.c_int32), ("bwd_particles", C.c_int32), ("bwd_lean", C.c_int32), ("bwd_pipe", C.c_int32), ("chol_form", C.c_int32), ("stamp_block", C.c_uint32),
+                ("fwd_gb", C.c_int32), ("bwd_particles", C.c_int32), ("bwd_lean", C.c_int32), ("bwd_pipe", C.c_int32), ("stamp_block", C.c_uint32),
                 ("fwd_stamps", dptr), ("bwd_stamps", dptr), ("ran_particles", C.c_int32), ("ran_gp_sharded", C.c_int32), ("ran_fwd_lean", C.c_int32),
                 ("ran_bwd_lean", C.c_int32), ("ran_row_split", C.c_int32), ("ran_bwd_pipe", C.c_int32)]
 
@@ -105,8 +101,6 @@ _SIGS = {
     "mcp_cov_diag": (C.c_int, [C.POINTER(Kernel), C.c_int, dptr, C.c_int, dptr, dptr]),
     "mcp_chol_factor": (C.c_int, [C.c_int, dptr, C.c_int, dptr, dptr, dptr]),
     "mcp_chol_inverse": (C.c_int, [C.c_int, dptr, C.c_int, dptr, C.c_int, dptr, C.c_int, dptr]),
-    "mcp_chol_factor_ex": (C.c_int, [C.c_int, dptr, C.c_int, dptr, dptr, dptr, C.POINTER(Dispatch)]),
-    "mcp_chol_inverse_ex": (C.c_int, [C.c_int, dptr, C.c_int, dptr, C.c_int, dptr, C.c_int, dptr, C.POINTER(Dispatch)]),
     "mcp_sym_sandwich": (C.c_int, [C.c_int, dptr, C.c_int, dptr, C.c_int, dptr, C.c_int, dptr, dptr]),
     "mcp_gp_alpha": (C.c_int, [C.c_int, dptr, C.c_int, dptr, C.c_double, dptr, dptr]),
     "mcp_sod_workspace_bytes": (C.c_size_t, [C.c_int]),
@@ -230,9 +224,6 @@ class _Lib:
 
     def mcp_debug_last_fwd_lean(self):
         return int(DISPATCH.ran_fwd_lean)
-
-    def mcp_debug_set_chol_mfma(self, form):  # 1 default, 0 the round-1/2 kernels, 2 the round-3 forms, 3 one-wave inverse columns
-        DISPATCH.chol_form = {1: 0, 0: 1, 2: 2, 3: 3}[int(form)]
 
     def mcp_debug_set_bwd_lean(self, mode):  # -1 automatic, 0 never
         DISPATCH.bwd_lean = 1 if int(mode) == 0 else 0

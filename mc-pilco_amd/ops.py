@@ -131,8 +131,7 @@ def chol_factor(K):
     N = U.shape[0]
     logdet = torch.zeros(1, dtype=DT, device=U.device)
     status = torch.zeros(1, dtype=torch.int32, device=U.device)
-    abi.check(abi.lib().mcp_chol_factor_ex(N, abi.ptr(U), U.shape[1], abi.ptr(logdet), abi.ptr(status), abi.stream(), C.byref(abi.DISPATCH)),
-              "mcp_chol_factor")
+    abi.check(abi.lib().mcp_chol_factor(N, abi.ptr(U), U.shape[1], abi.ptr(logdet), abi.ptr(status), abi.stream()), "mcp_chol_factor")
     return U, logdet[0], status
 
 
@@ -140,8 +139,7 @@ def chol_inverse(U):
     N = U.shape[0]
     Ui = torch.zeros(N, N, dtype=DT, device=U.device)
     Kinv = torch.empty(N, N, dtype=DT, device=U.device)
-    abi.check(abi.lib().mcp_chol_inverse_ex(N, abi.ptr(U), U.shape[1], abi.ptr(Ui), N, abi.ptr(Kinv), N, abi.stream(), C.byref(abi.DISPATCH)),
-              "mcp_chol_inverse")
+    abi.check(abi.lib().mcp_chol_inverse(N, abi.ptr(U), U.shape[1], abi.ptr(Ui), N, abi.ptr(Kinv), N, abi.stream()), "mcp_chol_inverse")
     return Ui, Kinv
 
 

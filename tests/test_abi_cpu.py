@@ -44,9 +44,11 @@ def test_library_exports_every_declared_symbol():
     for n in ("mcp_debug_set_particles_per_wg", "mcp_debug_set_gp_sharding", "mcp_debug_set_bwd_particles", "mcp_debug_set_chol_mfma",
               "mcp_debug_last_fwd_lean"):
         assert not hasattr(raw, n), "the library still exports the process-wide hook %s" % n
+    for n in ("mcp_chol_factor_ex", "mcp_chol_inverse_ex"):  # (ABI 7: the Cholesky has one path, no per-call form)
+        assert not hasattr(raw, n), "the library still exports %s" % n
     # the header, the binding and the built library carry ONE version (a stale library or an old struct layout is rejected at load time)
     hdr = int(re.search(r"#define MCP_ABI_VERSION (\d+)", open(HEADER).read()).group(1))
-    assert lib.mcp_abi_version() == hipabi.ABI_VERSION == hdr == 6
+    assert lib.mcp_abi_version() == hipabi.ABI_VERSION == hdr == 7
     assert b"gfx950" in lib.mcp_build_info()
 
 

@@ -40,31 +40,16 @@ run "c1 mfma" rocprofv3 --output-format csv --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_
 run "c1 tcp" rocprofv3 --output-format csv --pmc TCP_TCC_READ_REQ_sum -d "$OUT/c1_tcp" -o c1 -- $B --steps 4 --warmup 1 > "$OUT/c1_tcp.log" 2>&1
 run "c3 mfma" rocprofv3 --output-format csv --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE -d "$OUT/c3_mfma" -o c3 -- $B --workload c3 --steps 3 --warmup 1 > "$OUT/c3_mfma.log" 2>&1
 run "c5 mfma" rocprofv3 --output-format csv --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE -d "$OUT/c5_mfma" -o c5 -- $B --workload c5 --steps 2 --warmup 1 > "$OUT/c5_mfma.log" 2>&1
-# GP training epoch (round 4): per-kernel statistics at the cart-pole and the UR5 shape, the factorisation kernels alone, and -- when the
-# CLX_STAMPS experiment build is there (python mc-pilco_amd/build.py --variant-gp stamps CLX_STAMPS) -- the Cholesky's cycles per block row
+# GP training epoch (round 4): per-kernel statistics at the cart-pole and the UR5 shape, and the factorisation kernels alone
 run "fit c1 stats" rocprofv3 --output-format csv --kernel-trace --stats -d "$OUT/fit_c1_stats" -o fit_c1 -- python3 $R/tools/time_fit_model.py 300 100 > "$OUT/fit_c1_stats.log" 2>&1
 run "fit ur5 stats" rocprofv3 --output-format csv --kernel-trace --stats -d "$OUT/fit_ur5_stats" -o fit_ur5 -- python3 $R/tools/time_fit_ur5.py 100 > "$OUT/fit_ur5_stats.log" 2>&1
 run "chol times" python3 $R/tools/time_chol.py 300 400 500 600 1000 1153 2048 4096 > "$OUT/chol_times.txt" 2>&1
 run "pretrain times" python3 $R/tools/time_pretrain.py > "$OUT/pretrain_times.txt" 2>&1
-# round 6: what bounds phase V of the lean kernel -- the kernel itself with one side compiled out (experiment builds, when they are there:
-#   python mc-pilco_amd/build.py --variant-lean nofma RLX_NOFMA;  ... --variant-lean noload RLX_NOLOAD), and the issue microbenchmark
-for t in nofma noload; do
-  if [ -f $R/mc-pilco_amd/libmcpilco_hip_$t.so ]; then
-    MCPILCO_HIP_EXPERIMENT=1 MCPILCO_HIP_LIB=$R/mc-pilco_amd/libmcpilco_hip_$t.so python3 $R/tools/phase_stamps.py c1 > "$OUT/c1_${t}_stamps.txt" 2>&1 || exit 1
-  fi
-done
+# round 6: what bounds phase V of the lean kernel -- the issue microbenchmark
 ( hipcc --offload-arch=gfx950 -O3 -w -o /tmp/vissue_bench $R/tools/vissue_bench.hip && /tmp/vissue_bench ) > "$OUT/vissue_bench.txt" 2>&1 || exit 1
-if [ -f $R/mc-pilco_amd/libmcpilco_hip_bws.so ]; then
-  for w in c3 c5; do MCPILCO_HIP_EXPERIMENT=1 MCPILCO_HIP_LIB=$R/mc-pilco_amd/libmcpilco_hip_bws.so python3 $R/tools/bwd_wave_stamps.py $w > "$OUT/${w}_bwd_wave_stamps.txt" 2>&1 || exit 1; done
-fi
 run "loop times" python3 $R/tools/time_reinforce_policy.py --capture-ab > "$OUT/loop_times.txt" 2>&1
 # the symmetric phase-V experiment of round 5 (measured and dropped) beside the full stream it would replace
 ( hipcc --offload-arch=gfx950 -O3 -w -o /tmp/vsym_bench $R/tools/vsym_bench.hip && /tmp/vsym_bench && hipcc --offload-arch=gfx950 -O3 -w -DNRES=0 -o /tmp/v4_bench $R/tools/v4_bench.hip && /tmp/v4_bench ) > "$OUT/vsym_bench.txt" 2>&1 || exit 1
-if [ -f $R/mc-pilco_amd/libmcpilco_hip_stamps.so ]; then
-  for n in 300 400; do
-    MCPILCO_HIP_EXPERIMENT=1 MCPILCO_HIP_LIB=$R/mc-pilco_amd/libmcpilco_hip_stamps.so python3 $R/tools/chol_stamps.py $n > "$OUT/chol_stamps_n$n.txt" 2>&1 || exit 1
-  done
-fi
 # keep what is cited: the per-kernel statistics, and of the counter passes only the rollout kernels' rows
 for f in $(find "$OUT" -name "*counter_collection.csv"); do
   head -1 "$f" > "$f.rollout" && grep "rollout_" "$f" >> "$f.rollout"; rm -f "$f"

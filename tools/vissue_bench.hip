@@ -1,5 +1,5 @@
 // What does a wave's MFMA issue cost in phase V of the lean kernel (rollout_fwd_lean.hip) when NOTHING is loaded?  Round 6: with its loads compiled
-// out (RLX_NOLOAD) the real kernel still spends 10.5 k cycles per step in phase V on its heavy waves -- 19 register buffers x 12
+// out (an experiment build, profiles/NOTES.md) the real kernel still spends 10.5 k cycles per step in phase V on its heavy waves -- 19 register buffers x 12
 // v_mfma_f64_4x4x4_4b_f64 = 45 cycles per MFMA and wave, where tools/mfma4x4_probe.hip measures 16.3 for independent accumulators.  This
 // model keeps the kernel's per-buffer shape (6 operand tiles of 2 doubles per lane, 3 k operands of 2 doubles from LDS, 4 or 6 accumulators by
 // the wave's row-tile count) and varies HOW the 12 MFMAs of a buffer are written:
