@@ -92,9 +92,14 @@ typedef struct mcp_gp {
   const double* aX;       /* [D]          sum_j alpha_j X_jd (used when poly_deg>=1)   */
 } mcp_gp;
 
-/* Speed-integration dynamics model -- Speed_Model_learning_RBF(_MPK)_angle_state,
- * model_learning/Model_learning.py:619-760.  GP g predicts the change of state vel[g];
- * not_vel[g] is the matching position.  GP input z=[x[not_angle], sin x[angle], cos x[angle], u]. */
+/* Dynamics model.  Speed integration -- Speed_Model_learning_RBF(_MPK)_angle_state,
+ * model_learning/Model_learning.py:619-760: GP g predicts the change of state vel[g];
+ * not_vel[g] is the matching position (v' = v + d, q' = q + Ts v + Ts/2 d).
+ * not_vel[g] == -1: GP g has no integrated position, x'[vel[g]] = x[vel[g]] + d_g -- the delta-state
+ * models Model_learning_RBF(_angle_state), Model_learning_RBF_MPK_angle_state (Model_learning.py:471-493,
+ * 495-618) are G = S, vel = 0..S-1, every not_vel = -1 (Ts then only serves a measurement model).
+ * A library older than this rule refuses such a descriptor (MCP_ERR_ARG).
+ * GP input z=[x[not_angle], sin x[angle], cos x[angle], u]. */
 typedef struct mcp_model {
   int32_t S, U, G, D;
   int32_t n_angle, n_not_angle;

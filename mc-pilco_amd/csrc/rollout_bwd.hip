@@ -241,7 +241,7 @@ __global__ __launch_bounds__(MAXNT, WPE) void rollout_bwd_kernel(BwdArgs a) {
     }
   }
   const double pm_a = pms ? -ms.a1 / ms.a0 : 0.0, pm_b0 = pms ? ms.b0 / ms.a0 : 0.0, pm_b1 = pms ? ms.b1 / ms.a0 : 0.0;
-  int pos_of_vel = 0;  // the position state integrated from this lane's velocity state
+  int pos_of_vel = 0;  // the position state integrated from this lane's velocity state (-1: none, a delta-state GP)
   for (int g = 0; g < G; ++g)
     if (md.vel[g] == lane) pos_of_vel = md.not_vel[g];
   const double umax_lane = (serial && lane < U) ? pl.u_max[lane] : 1.0;
@@ -504,7 +504,8 @@ __global__ __launch_bounds__(MAXNT, WPE) void rollout_bwd_kernel(BwdArgs a) {
             if (g < G) {
               const int lv = md.vel[g], lp = md.not_vel[g];
               const double xnv = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(xnr), lv), __builtin_amdgcn_readlane(__double2loint(xnr), lv));
-              const double xnp = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(xnr), lp), __builtin_amdgcn_readlane(__double2loint(xnr), lp));
+              // (lp == -1, a delta-state GP: no position lane -- no Ts terms; the test is uniform)
+              const double xnp = lp >= 0 ? __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(xnr), lp), __builtin_amdgcn_readlane(__double2loint(xnr), lp)) : 0.0;
               const double dbg = fma(0.5 * md.Ts, xnp, xnv);
               const double jc = zang ? fma(Ja[g], cv, -(Jb[g] * sv)) : Ja[g];
               val = fma(g == rb.w ? md.Ts : 0.0, xnp, val);
@@ -578,7 +579,8 @@ __global__ __launch_bounds__(MAXNT, WPE) void rollout_bwd_kernel(BwdArgs a) {
             if (g < G) {
               const int lv = md.vel[g], lp = md.not_vel[g];
               const double xnv = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(xnr), lv), __builtin_amdgcn_readlane(__double2loint(xnr), lv));
-              const double xnp = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(xnr), lp), __builtin_amdgcn_readlane(__double2loint(xnr), lp));
+              // (lp == -1, a delta-state GP: no position lane -- no Ts terms; the test is uniform)
+              const double xnp = lp >= 0 ? __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(xnr), lp), __builtin_amdgcn_readlane(__double2loint(xnr), lp)) : 0.0;
               const double dbg = fma(0.5 * md.Ts, xnp, xnv);
               const double jc = zang ? fma(Ja[g], cv, -(Jb[g] * sv)) : Ja[g];
               val = fma(g == rb.w ? md.Ts : 0.0, xnp, val);
@@ -626,7 +628,8 @@ __global__ __launch_bounds__(MAXNT, WPE) void rollout_bwd_kernel(BwdArgs a) {
             }
             __builtin_amdgcn_wave_barrier();
             // through the integrator:  x_{t+1}[vel] = x[vel] + delta ; x_{t+1}[pos] = x[pos] + Ts x[vel] + Ts/2 delta
-            if (lane < G) db[lane] = xn[t_vel[lane]] + 0.5 * md.Ts * xn[t_pos[lane]];
+            // (delta-state GPs, t_pos == -1: x_{t+1}[vel] = x[vel] + delta only)
+            if (lane < G) db[lane] = xn[t_vel[lane]] + (t_pos[lane] >= 0 ? 0.5 * md.Ts * xn[imax(t_pos[lane], 0)] : 0.0);
           }
           // trig of this step's angles (used now by the GP feature map, next iteration by the policy's)
           if (lane < S && need_trig) {
@@ -653,7 +656,7 @@ __global__ __launch_bounds__(MAXNT, WPE) void rollout_bwd_kernel(BwdArgs a) {
           if (lane < S) {
             xbv = r[oGX + lane];
             if (!last) {
-              if (g_vel >= 0) xbv += xn[lane] + md.Ts * xn[pos_of_vel];
+              if (g_vel >= 0) xbv += xn[lane] + (pos_of_vel >= 0 ? md.Ts * xn[pos_of_vel] : 0.0);
               if (g_pos >= 0) xbv += xn[lane];
             }
           }
@@ -1260,7 +1263,8 @@ __global__ __launch_bounds__(640) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
           if (g < G) {
             const int lv = md.vel[g], lp = md.not_vel[g];
             const double xnv = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(xn), lv), __builtin_amdgcn_readlane(__double2loint(xn), lv));
-            const double xnp = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(xn), lp), __builtin_amdgcn_readlane(__double2loint(xn), lp));
+            // (lp == -1, a delta-state GP: no position lane -- no Ts terms; the test is uniform)
+            const double xnp = lp >= 0 ? __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(xn), lp), __builtin_amdgcn_readlane(__double2loint(xn), lp)) : 0.0;
             const double dbg = fma(0.5 * md.Ts, xnp, xnv);
             val = fma(g == gvel ? md.Ts : 0.0, xnp, val);
             val = fma(dbg, Jc[g], val);

@@ -79,7 +79,8 @@ static inline bool model_ok(const mcp_model* m) {
     if (gp.kern.poly_deg < 0 || gp.kern.poly_deg > 2) return false;
     if (gp.kern.poly_deg >= 1 && (!gp.kern.w1 || !gp.aX)) return false;
     if (gp.kern.poly_deg >= 2 && (!gp.kern.w20 || !gp.kern.w21)) return false;
-    if (m->vel[g] < 0 || m->vel[g] >= m->S || m->not_vel[g] < 0 || m->not_vel[g] >= m->S) return false;
+    // not_vel[g] == -1: GP g has no integrated position (delta-state model, x'[vel] = x[vel] + delta)
+    if (m->vel[g] < 0 || m->vel[g] >= m->S || m->not_vel[g] < -1 || m->not_vel[g] >= m->S) return false;
   }
   return true;
 }

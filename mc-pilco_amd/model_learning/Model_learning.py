@@ -10,8 +10,9 @@ method signatures.  Reference lines replaced:
   get_next_state / get_one_step_gp_out / get_*_gp_estimate   Model_learning.py:210-336
   get_next_state_from_gp_output    Model_learning.py:471-493 (delta model), 685-718 (speed integration)
 
-``packed()`` returns the device-resident operands in the fused kernels' layout (mc_pilco_amd.ops.PackedModel);
-``policy_learning.MC_PILCO.apply_policy`` hands it to the fused rollout.  Out of scope: the SOR approximation
+``packed()`` returns the device-resident operands in the fused kernels' layout (mc_pilco_amd.ops.PackedModel) -- for the
+speed-integration models and for the delta-state models with one GP per state (at most 8); ``has_fused_layout()`` says
+whether it has one.  ``policy_learning.MC_PILCO.apply_policy`` hands it to the fused rollout.  Out of scope: the SOR approximation
 and SP_Speed_Model_learning_Furuta (unused by every launch script).
 """
 import numpy as np
@@ -204,8 +205,48 @@ class Model_learning(torch.nn.Module):
             raise RuntimeError("GP %d has not been pretrained (call pretrain_gp / reinforce_model first)" % gp_index)
         return self._packed_gps[gp_index]
 
-    def packed(self):
-        raise NotImplementedError("only the speed-integration models have a fused-rollout layout")
+    def has_fused_layout(self):
+        """Whether ``packed()`` describes this model to the fused rollout kernels (MC_PILCO.apply_policy then launches them;
+        otherwise it runs step by step on get_next_state)."""
+        return self._delta_layout_problem() is None
+
+    def _delta_layout_problem(self):
+        """None when the model is a delta-state model the kernels take (mcp_model with every not_vel = -1), else the reason."""
+        cls = type(self)
+        if (cls.get_next_state_from_gp_output is not Model_learning.get_next_state_from_gp_output or cls.data_to_gp_output is not Model_learning.data_to_gp_output
+                or cls.get_next_state is not Model_learning.get_next_state):
+            return "the model has an integrator of its own"
+        if cls.data_to_gp_input not in (Model_learning.data_to_gp_input, Model_learning_RBF_angle_state.data_to_gp_input):
+            return "the model has GP inputs of its own"
+        S = getattr(self, "dim_state", None)
+        if S is None:
+            return "the model has no data yet"
+        if self.num_gp != S:
+            return "a delta-state model needs one GP per state component (%d GPs, %d states)" % (self.num_gp, S)
+        if S > ops.abi.MAX_GP:
+            return "%d GPs exceed the kernels' limit of %d" % (S, ops.abi.MAX_GP)
+        return None
+
+    def packed(self, T_sampling=None):
+        """Delta-state models: the whole model in the fused kernels' layout (G = S, vel = 0..S-1, every not_vel = -1), built after every
+        pretrain.  ``T_sampling`` is only read by a measurement model (MC_PILCO4PMS); the delta integrator has no Ts term."""
+        why = self._delta_layout_problem()
+        if why is not None:
+            raise NotImplementedError("no fused-rollout layout for this model: " + why)
+        Ts = 0.0 if T_sampling is None else float(T_sampling)
+        if self._packed_model is None or self._packed_model.Ts != Ts:
+            gps = [self.packed_gp(i) for i in range(self.num_gp)]
+            S = self.dim_state
+            if type(self).data_to_gp_input is Model_learning.data_to_gp_input:
+                angle, not_angle = [], list(range(S))  # z = [x, u]
+            else:
+                angle, not_angle = [int(i) for i in self.angle_indeces], [int(i) for i in self.not_angle_indeces]
+            U = gps[0].D - len(not_angle) - 2 * len(angle)
+            if U < 1 or any(pg.D != gps[0].D for pg in gps):
+                raise NotImplementedError("no fused-rollout layout for this model: its GPs do not all read the whole input z = [x, u]")
+            scale = [float(n) ** 2 for n in self.norm_list]
+            self._packed_model = ops.PackedModel.delta(gps, S, U, angle, not_angle, Ts=Ts, var_scale=scale)
+        return self._packed_model
 
     # ---- one-step prediction ------------------------------------------------------------------------------------------
     def get_next_state(self, current_state, current_input, particle_pred=True):
@@ -315,6 +356,9 @@ class Speed_Model_learning_RBF_angle_state(Model_learning):
         nxt[:, self.not_vel_indeces] = (current_state[:, self.not_vel_indeces] + self.T_sampling * current_state[:, self.vel_indeces]
                                         + self.T_sampling / 2 * dv)
         return nxt, dv_mean, dv_var
+
+    def has_fused_layout(self):
+        return True
 
     def packed(self):
         """The whole model in the fused kernels' layout (built after every pretrain)."""

@@ -231,7 +231,16 @@ class PackedGP:
 
 
 class PackedModel:
-    """mcp_model: the speed-integration dynamics model with its G packed GPs."""
+    """mcp_model: the dynamics model with its G packed GPs.  Speed integration: ``not_vel[g]`` is the position integrated from
+    state ``vel[g]``; -1 there means none (x'[vel[g]] = x[vel[g]] + delta_g) -- ``PackedModel.delta`` builds that layout."""
+
+    @classmethod
+    def delta(cls, gps: Sequence[PackedGP], S, U, angle, not_angle, Ts=0.0, var_scale=None):
+        """Delta-state model (Model_learning.py:471-493): GP i predicts x_{t+1}[i] - x_t[i] for every state, G = S.  ``Ts`` only
+        serves a measurement model (MC_PILCO4PMS's velocity differences); the integrator has no Ts term."""
+        if len(gps) != int(S):
+            raise ValueError("a delta-state model has one GP per state component (%d GPs, %d states)" % (len(gps), int(S)))
+        return cls(gps, S, U, Ts, angle, not_angle, list(range(int(S))), [-1] * int(S), var_scale=var_scale)
 
     def __init__(self, gps: Sequence[PackedGP], S, U, Ts, angle, not_angle, vel, not_vel, var_scale=None):
         self.gps = list(gps)
@@ -245,7 +254,7 @@ class PackedModel:
         for i, v in enumerate(vel):
             m.vel[i] = int(v)
         for i, v in enumerate(not_vel):
-            m.not_vel[i] = int(v)
+            m.not_vel[i] = int(v)  # (written for every GP: -1 must not be left at the ctypes default 0, a valid position)
         m.Ts = float(Ts)
         for g in range(abi.MAX_GP):
             m.var_scale[g] = 1.0 if var_scale is None or g >= len(var_scale) else float(var_scale[g])
@@ -253,6 +262,8 @@ class PackedModel:
             pg.fill(m.gp[g])
         self.c = m
         self.S, self.U, self.G, self.D = m.S, m.U, m.G, m.D
+        self.Ts = m.Ts
+        self.is_delta = all(int(v) == -1 for v in not_vel)
         self.device = self.gps[0].device
 
 

@@ -30,6 +30,13 @@ from mc_pilco_amd.policy_learning import Policy as _Policy
 from mc_pilco_amd.simulation_class import model as _sim
 
 
+def _has_fused_layout(ml):
+    """The model has a fused-rollout layout (``packed()``): the speed-integration models and the delta-state models with one GP per
+    state.  A model object without ``has_fused_layout`` keeps the older test, a speed-integration interface."""
+    f = getattr(ml, "has_fused_layout", None)
+    return bool(f()) if callable(f) else hasattr(ml, "vel_indeces")
+
+
 class MC_PILCO(torch.nn.Module):
     def __init__(self, T_sampling, state_dim, input_dim, f_sim, f_model_learning, model_learning_par, f_rand_exploration_policy,
                  rand_exploration_policy_par, f_control_policy, control_policy_par, f_cost_function, cost_function_par, std_meas_noise=None,
@@ -165,7 +172,7 @@ class MC_PILCO(torch.nn.Module):
                                                              particles_init_up_bound, particles_init_low_bound, flg_particles_init_multi_gauss,
                                                              self._m_total), 0)
         pol, ml = self.control_policy, self.model_learning
-        if isinstance(pol, _Policy.Sum_of_gaussians) and hasattr(ml, "vel_indeces"):
+        if isinstance(pol, _Policy.Sum_of_gaussians) and _has_fused_layout(ml):
             noise, p = self._rollout_noise(M, T, p_dropout)
             states, inputs, status = ops.rollout(ml.packed(), pol.packed(), noise, x0, T, p, gp_sharding=self.gp_sharding)
             self.last_status = status
@@ -175,7 +182,7 @@ class MC_PILCO(torch.nn.Module):
         if world > 1:
             # its noise (torch draws inside get_next_state / the policy's dropout) is per LOCAL particle: identically seeded ranks
             # would simulate correlated shards, not the particles one GPU would
-            raise NotImplementedError("particle sharding needs the fused rollout (Sum_of_gaussians policy + speed-integration model)")
+            raise NotImplementedError("particle sharding needs the fused rollout (Sum_of_gaussians policy + a model with a fused layout)")
         xs = [x0]
         us = [pol(x0, t=0, p_dropout=p_dropout)]
         for t in range(1, T):
@@ -389,7 +396,7 @@ class MC_PILCO(torch.nn.Module):
         use_graph = (bool(getattr(self, "capture_attempts", False)) and depth > 0 and adam is not None and dev.type == "cuda"
                      and type(self).apply_policy is MC_PILCO.apply_policy  # (the measurement-model rollout of MC_PILCO4PMS keeps the eager loop)
                      and isinstance(pol_, _Policy.Sum_of_gaussians) and getattr(pol_, "_unit_scale", False)
-                     and hasattr(self.model_learning, "vel_indeces") and isinstance(self.cost_function, _Cost._HipExpectedCost))
+                     and _has_fused_layout(self.model_learning) and isinstance(self.cost_function, _Cost._HipExpectedCost))
         cap = dict(on=use_graph, graphs=[None, None], outs=[None, None], eager=0, rec=torch.zeros(2, abi.OPT_RECORD_DOUBLES, dtype=dt, device=dev),
                    one=torch.ones(1, dtype=dt, device=dev), last_flat=None)
         self.attempts_replayed = 0
@@ -803,7 +810,7 @@ class MC_PILCO4PMS(MC_PILCO):
                                                             self._m_total), 0)
         b, a = signal.butter(1, self.filtering_dict["fc"])
         pos, vel = list(self.pos_indeces), list(self.vel_indeces)
-        if self.fused and isinstance(pol, _Policy.Sum_of_gaussians) and hasattr(ml, "vel_indeces"):
+        if self.fused and isinstance(pol, _Policy.Sum_of_gaussians) and _has_fused_layout(ml):
             # one fused launch: the kernels carry the measurement filter's states per particle (mcp_meas)
             p = float(p_dropout) if getattr(pol, "flg_drop", True) else 0.0
             G, B = ml.num_gp, pol.num_basis
@@ -826,12 +833,15 @@ class MC_PILCO4PMS(MC_PILCO):
                 pos_noise = None
             meas = ops.MeasSpec(pos=pos, vel=vel, std_pos=[float(v) for v in np.asarray(self.std_meas_noise_sim)[pos]], b=b, a=a,
                                 pos_noise=pos_noise)
-            states, inputs, status = ops.rollout(ml.packed(), pol.packed(), noise, x, T, p, meas=meas, gp_sharding=self.gp_sharding)
+            model = ml.packed()
+            if getattr(model, "is_delta", False) and model.Ts != float(self.T_sampling):
+                model = ml.packed(T_sampling=self.T_sampling)  # (a delta-state model has no Ts: the measured velocities need one)
+            states, inputs, status = ops.rollout(model, pol.packed(), noise, x, T, p, meas=meas, gp_sharding=self.gp_sharding)
             self.last_status = status
             return states, inputs
         self.last_status = None  # (no fused launch)
         if world > 1:  # (per-LOCAL-particle torch draws: identically seeded ranks would simulate correlated shards)
-            raise NotImplementedError("particle sharding needs the fused rollout (fused=True, Sum_of_gaussians policy, speed-integration model)")
+            raise NotImplementedError("particle sharding needs the fused rollout (fused=True, Sum_of_gaussians policy, a model with a fused layout)")
         std_pos = torch.tensor(np.asarray(self.std_meas_noise_sim)[pos], dtype=self.dtype, device=self.device)
         saved_mode = getattr(pol, "noise_mode", None)
         if ref and saved_mode is not None:
