@@ -31,7 +31,7 @@ typedef struct mcp_dispatch {
   int32_t bwd_lean;      /* the latency-lean sweep (rollout_bwd_lat_kernel): 1 never                                                    */
   int32_t bwd_pipe;      /* general sweep, one particle per workgroup on the wide classes: 1 never the pipelined form (chain beside the RBF stage) */
   uint32_t stamp_block;  /* which workgroup of the forward launch writes its stamps                                                     */
-  void* fwd_stamps;      /* device buffer of 32 uint64 per-phase cycle totals of that workgroup (NULL = off)                            */
+  void* fwd_stamps;      /* device buffer of 64 uint64 per-phase cycle totals of that workgroup (NULL = off)                            */
   void* bwd_stamps;      /* device buffer of 16 uint64 (backward sweep)                                                                 */
   /* ---- report (written by the call) ---- */
   int32_t ran_particles;  /* forward / posterior: particles per workgroup launched (16 = tile kernel) */

@@ -29,9 +29,10 @@ using namespace mcp;
 //   * phase V on the matrix cores: Kinv as 16 x 8 operand tiles of v_mfma_f64_4x4x4_4b_f64 (kt_pack_kernel), every wave owns whole
 //     row tiles, so v is complete inside a wave: no cross-wave partial sums, no phase "vsum", and the wave goes straight on to its
 //     share of phase J (4x4x4 MFMA as well, the rows it has just produced) without a workgroup barrier in between.
-//   * phase F, the hand-off, the integrator and the next step's phase S run back to back in wave 0 (wave-level ordering only, the
-//     8 partial tiles of phase J summed by 64 lanes at once); the other waves meanwhile draw the next step's dropout decisions and
-//     process noise (never wave 4, which shares wave 0's SIMD).
+//   * phase F, the hand-off, the integrator and the next step's phase S run back to back in wave 0 (wave-level ordering only; delta
+//     and its granules before the Jacobian columns; no trajectory store: the last wave writes states, Jacobians and inputs to global
+//     memory behind the next barrier); the other waves meanwhile draw the next step's dropout decisions and process noise (never
+//     wave 4, which shares wave 0's SIMD).
 // Results do not depend on P (1, 2, 4): equal shards reproduce each other bit for bit, as before.  Covers SE-only models with
 // D <= 8 (<= 6 state-derived + <= 2 inputs), <= 6 policy features, 32 <= Npad <= 384; everything else runs the general kernel
 // (rollout_fwd.hip).
@@ -53,6 +54,8 @@ using namespace mcp;
 #define RL_UM 2   // inputs, zero padded
 #define RL_ZD (RL_DSM + RL_UM)
 #define RL_PFM 6  // policy features, zero padded
+#define RL_NSTAMP 64  // slots of the stamp buffer (tools/phase_stamps.py names them)
+#define RL_STORE_WAVE (RF_NW - 1)  // the wave that writes the trajectory to global memory
 #define RL_NRES 2  // register buffers kept resident: RL_NRES or RL_NRES + 1, whichever leaves an even number to stream
 
 // LDS plan: the regions whose size is bounded by compile-time limits come first, at compile-time offsets (no scalar register per
@@ -76,8 +79,8 @@ struct LatFixed {
   static constexpr int role = ((kpar + 5 * RL_MAXD + 2) + 1) & ~1;          // [64][16] ints: roles of the threads of wave 0 in the serial section
   static constexpr int sro = role + 64 * 8;                    // [64][8]: phase S of thread (p, s): 6 int LDS addresses (in doubles) | 4 scale factors
   static constexpr int dump = sro + 64 * 8;                    // where phase S writes what a state component does not feed
-  static constexpr int stl = dump + 2;                         // [16 + 8] u64 phase-cycle totals (diagnostic)
-  static constexpr int end = stl + 24;
+  static constexpr int stl = dump + 2;                         // [RL_NSTAMP] u64 phase-cycle totals (stamped instantiations only)
+  static constexpr int end = stl + RL_NSTAMP;
 };
 static_assert(LatFixed::pc % 2 == 0 && LatFixed::fz % 2 == 0 && LatFixed::gpl % 2 == 0, "16-byte alignment");
 static_assert(LatFixed::red % 2 == 0 && LatFixed::rt % 2 == 0 && LatFixed::zs % 2 == 0 && LatFixed::role % 2 == 0 && LatFixed::sro % 2 == 0 && LatFixed::end % 2 == 0, "16-byte alignment of the v2d regions");
@@ -339,7 +342,14 @@ struct LatLog2 {
 };
 
 // KR = phase-K items per thread: Npad * P <= KR * RF_NT
-// phase stamps of the lean kernel: accumulated in LDS (no global round trip inside the step), written out once at the end
+// Phase stamps of the lean kernel: a property of the INSTANTIATION (template parameter STAMPS; `stamping` is a compile-time false
+// without it, so the product kernels carry no clock read, no stamp state and no stamp branch).  Accumulated in LDS (no global round
+// trip inside the step), written out once at the end.  Slots (cycles summed over the steps of workgroup `stamp_block`):
+//   0, 1, 3, 6, 7   thread 0: the barrier intervals  S | policy + K(state) | u + K(exp) | V + J | F + hand-off + integrate
+//   11 .. 15, 10    wave 0's serial chain: partial-tile sum | mu, var, delta up to the granule stores | Jacobian columns | integrate |
+//                   phase S up to B0;  10 (and 8): the hand-off poll
+//   16 + w          wave w: its own phase V (up to the tail)
+//   24 + w, 32 + w  wave w: its policy pass, its K(state) pass;   40 + w, 48 + w: its u, its K(exp) -- own time, waits at barriers excluded
 #define RL_STAMP(k)                           \
   do {                                        \
     if (stamping && tid == 0) {               \
@@ -356,6 +366,12 @@ struct LatLog2 {
       sub_stamp = now_;                       \
     }                                         \
   } while (0)
+// (every wave: sub_stamp is per lane, wave 0 restarts it where its chain begins)
+#define RL_SUB_START()                                      \
+  do {                                                      \
+    if (stamping && lane == 0) sub_stamp = clock64();       \
+  } while (0)
+#define RL_WSUB(k) RL_SUB((k) + wv)
 // phase J of the lean kernel on the 4x4x4 MFMA:  R[c][n] = sum_j Xe[c][j] W[j][n],  Xe = [X^T; 1; 0] (8 rows),  W (N x 2P, 8 columns
 // at most).  One instruction = blocks (row half, column half) x 4 training points.  A wave sums over the rows it has just
 // produced in phase V (its own row tiles: 32 or 48 training points) -- no workgroup barrier between the two phases -- and stores
@@ -463,7 +479,7 @@ __device__ __forceinline__ void lean_prefz(const double* z, const double* kpar, 
   }
 }
 
-template <int P, int KR, int MAXDEG, bool PMS>
+template <int P, int KR, int MAXDEG, bool PMS, bool STAMPS>
 __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   constexpr int LP = LatLog2<P>::v;
@@ -493,6 +509,10 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
   double* epsb = smem + LatFixed::eps;
   double* red = smem + LatFixed::red;
   double* rtot = smem + LatFixed::rt;
+  // hand-over of wave 0's outputs to the storing wave, in tiles of `red` that are free from phase F of a step (wave 0 has read them) to
+  // phase J of the next: the Jacobian column of thread (p, c); the measurement of thread (p, s) (PMS)
+  double* jl = red;
+  double* xml = red + 64;
   double* pc = smem + LatFixed::pc;    // polynomial constants (MAXDEG > 0)
   double* fz = smem + LatFixed::fz;    // z-only polynomial terms of the step (MAXDEG > 0)
   double* pnz = smem + LatFixed::pn;   // position measurement noise (PMS)
@@ -500,7 +520,7 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
   double* kpar = smem + LatFixed::kpar;
   int* role = reinterpret_cast<int*>(smem + LatFixed::role);
   unsigned long long* stl = reinterpret_cast<unsigned long long*>(smem + LatFixed::stl);  // phase-cycle totals (diagnostic)
-  const bool stamping = a.stamps && blockIdx.x == a.stamp_block;
+  const bool stamping = STAMPS && a.stamps && blockIdx.x == a.stamp_block;
   double* gs = smem + L.gs;
   double* kb = smem + L.kb;
   double* vb = smem + L.vb;
@@ -520,7 +540,7 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
   const bool writer = myg == 0;                // states / inputs are identical in the workgroups of a cluster: one of them stores
   int* abortw = reinterpret_cast<int*>(dl + P * G);
   if (tid0 == 0) *abortw = 0;
-  if (tid0 < 24) stl[tid0] = 0;
+  if (STAMPS && tid0 < RL_NSTAMP) stl[tid0] = 0;
   const int m0 = a.m_off + cluster * P;
   const int Mend = a.m_off + a.m_cnt;
   uint32_t bad = 0;
@@ -772,7 +792,7 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
       if (r == NRES && nresb) kt_load(vres[r], vpb, 0);
     }
   }
-  unsigned long long last_stamp = clock64(), sub_stamp = last_stamp;
+  unsigned long long last_stamp = STAMPS ? clock64() : 0, sub_stamp = last_stamp;
   double pm_prev_np = 0.0, pm_prev_nv = 0.0, pm_prev_mv = 0.0;  // PMS: previous noisy position / noisy velocity / filtered velocity of this lane's pair
 
   for (int t = 0; t < T; ++t) {
@@ -821,13 +841,8 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
         const v2d sc0 = *reinterpret_cast<const v2d*>(srow + 4), sc1 = *reinterpret_cast<const v2d*>(srow + 6);
         double* xc = xs + cur * P * S;
         xc[op * S + os] = xn;
-        if (ovalid) {
-          if (writer) {
-            a.states[((size_t)t * M + m0 + op) * S + os] = xn;
-            if (PMS) pl.meas.meas[((size_t)t * M + m0 + op) * S + os] = xm;
-          }
-          if (is_bad(xn) || (PMS && is_bad(xm))) bad |= MCP_STATUS_NAN;
-        }
+        if (PMS) xml[lane] = xm;  // (for the wave that stores the trajectory)
+        if (ovalid && (is_bad(xn) || (PMS && is_bad(xm)))) bad |= MCP_STATUS_NAN;
         double sn = 0.0, cs = 0.0;
         if (zi_ang >= 0 || pi_ang >= 0) sincos_fast(xn, &sn, &cs);
         double snm = sn, csm = cs;  // trig of the measured value (policy features)
@@ -845,6 +860,30 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
     }
     if (wv == 0) RL_SUB(15);
     lds_barrier();  // B0
+    // ---- the trajectory stores of wave 0's serial section, by another wave: x_t (phase S above), and what phase F and the policy of step
+    // t - 1 left in LDS -- the Jacobian columns and the inputs.  Wave 0 issues no global store but its granules: its hand-off poll waits for
+    // every store it has outstanding (one counter for loads and stores on this target).  The last wave has the fewest phase-K items.
+    if (wv == RL_STORE_WAVE) {
+      const int* ro = role + lane * 16;
+      const int2 r0 = *reinterpret_cast<const int2*>(ro), r3 = *reinterpret_cast<const int2*>(ro + 12);
+      if (writer && lane < P * S) {
+        const int op = r0.x, os = r0.y;
+        if (m0 + op < Mend) {
+          a.states[((size_t)t * M + m0 + op) * S + os] = xs[cur * P * S + op * S + os];
+          if (PMS) pl.meas.meas[((size_t)t * M + m0 + op) * S + os] = xml[lane];
+        }
+      }
+      if (t > 0) {
+        if (lane < P * (D + 1)) {
+          const int p = r3.x, c = r3.y;
+          if (c < D && a.jac && m0 + p < Mend) a.jac[(((size_t)(t - 1) * M + m0 + p) * G + myg) * D + c] = jl[lane];
+        }
+        if (writer && lane < P * U) {  // U <= 2
+          const int ip = U == 1 ? lane : lane >> 1, ik = U == 1 ? 0 : lane & 1;
+          if (m0 + ip < Mend) a.inputs[((size_t)(t - 1) * M + m0 + ip) * U + ik] = z[ip * D + DS + ik];
+        }
+      }
+    }
     if (*abortw) {  // uniform: a partner never arrived (set by wave 0 in the previous step's hand-off)
       bad |= MCP_STATUS_SYNC;
       break;
@@ -955,16 +994,22 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
       };
       // (polynomial kernels: the policy pass first -- the six values per item that phase K carries to its second half are then not live
       //  beside the policy pass's operands; in the other order the degree-2 instantiation spilled a resident Kinv buffer to scratch)
+      RL_SUB_START();
       if (MAXDEG >= 2) {
         policy_pass();
+        RL_WSUB(24);
         k_state();
+        RL_WSUB(32);
       } else {
         k_state();
+        RL_WSUB(32);
         policy_pass();
+        RL_WSUB(24);
       }
     }
     lds_barrier();  // B1
     RL_STAMP(1);
+    RL_SUB_START();
     // ---- u = u_max tanh((W phi + b) / u_max): every thread adds the group sums of its own particle in the same fixed order ----
     double ur[RL_UM];
 #pragma unroll
@@ -995,6 +1040,7 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
       }
     }
     if (t == T - 1) break;
+    RL_WSUB(40);
     v2d bufA[KT_NL], bufB[KT_NL];  // (phase V's stream buffers)
     // ---- phase K, second half: the input dimensions and the exp ----
     {
@@ -1058,10 +1104,11 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
         }
       }
     }
+    RL_WSUB(48);
     lds_barrier();  // B2
     RL_STAMP(3);
     // ---- phase V, second half: v = Kinv k on the 4x4x4 MFMA, then the phase-J weights of this wave's rows ----
-    const unsigned long long tv0_ = stamping ? clock64() : 0;
+    RL_SUB_START();
     if (vnrt > 0) {
       double jacc[NCG][2];  // this wave's partial tile of phase J (both segments)
 #pragma unroll
@@ -1076,7 +1123,7 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
         for (int r = 0; r < 2; ++r) acc2[0][r] = acc2[1][r] = 0.0;
         kt_stream<P, NRES>(sg ? vpb : vp, nrt, vnjg, kb, lane, acc3, acc2, vres, sg ? NRES : 0, sg ? nresb : nres, bufA, bufB);
         kt_tail<P, MAXDEG>(acc3, acc2, rt0, nrt, kb, al_l, vb, lane);
-        if (stamping && lane == 0 && sg == nseg - 1) stl[16 + wv] += clock64() - tv0_;  // this wave's own phase V
+        if (sg == nseg - 1) RL_WSUB(16);  // this wave's own phase V
         // ---- phase J over the rows this wave has just finished (wave-level ordering only) ----
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -1099,24 +1146,26 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
     lds_barrier();  // B4
     RL_STAMP(6);
     if (wv == 0) {
-      sub_stamp = stamping ? clock64() : 0;
+      RL_SUB_START();
       // ---- phase F: sample delta and fold the sampling into d delta/dz; hand-off; integrate ------------
       const int* ro = role + lane * 16;
       const int4 r0 = *reinterpret_cast<const int4*>(ro), r1 = *reinterpret_cast<const int4*>(ro + 4), r2 = *reinterpret_cast<const int4*>(ro + 8),
                  r3 = *reinterpret_cast<const int4*>(ro + 12);
+      if (MAXDEG > 0) {
 #pragma unroll
-      for (int g = 0; g < NCG; ++g) {  // the 8 waves' partial tiles, added in wave order: lane l -> element (c = l >> 3, n = 8 g + (l & 7))
-        double rv[RF_NW];
+        for (int g = 0; g < NCG; ++g) {  // the 8 waves' partial tiles, added in wave order: lane l -> element (c = l >> 3, n = 8 g + (l & 7))
+          double rv[RF_NW];
 #pragma unroll
-        for (int w = 0; w < RF_NW; ++w) rv[w] = red[(w * NCG + g) * 64 + lane];
-        double sr = rv[0];
+          for (int w = 0; w < RF_NW; ++w) rv[w] = red[(w * NCG + g) * 64 + lane];
+          double sr = rv[0];
 #pragma unroll
-        for (int w = 1; w < RF_NW; ++w) sr += rv[w];
-        rtot[g * 64 + lane] = sr;
+          for (int w = 1; w < RF_NW; ++w) sr += rv[w];
+          rtot[g * 64 + lane] = sr;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       if (lane < P * (D + 1)) {
         const int p = r3.x, c = r3.y, crow = r3.w;  // (crow: the row of R that belongs to column c -- the sums come out in xq's row order)
         const GpL& gp = gpl[0];
@@ -1134,13 +1183,30 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
         v2d RD, RC;
         double mu, var;
         if (MAXDEG == 0) {
-          RD = *reinterpret_cast<const v2d*>(__builtin_assume_aligned(rtot + ROW1 * 8 + 2 * p, 16));
-          RC = *reinterpret_cast<const v2d*>(__builtin_assume_aligned(rtot + crow * 8 + 2 * p, 16));
+          // the two pairs this thread needs, straight from the 8 waves' partial tiles and added in wave order (what a sum over whole
+          // tiles, parked in LDS and read back, would give: the same additions in the same order, without the round trip)
+          v2d pd[RF_NW], pq[RF_NW];
+#pragma unroll
+          for (int w = 0; w < RF_NW; ++w) {
+            pd[w] = *reinterpret_cast<const v2d*>(__builtin_assume_aligned(red + w * 64 + ROW1 * 8 + 2 * p, 16));
+            pq[w] = *reinterpret_cast<const v2d*>(__builtin_assume_aligned(red + w * 64 + crow * 8 + 2 * p, 16));
+          }
+          RD = pd[0];
+          RC = pq[0];
+#pragma unroll
+          for (int w = 1; w < RF_NW; ++w) {
+            RD.x += pd[w].x;
+            RD.y += pd[w].y;
+            RC.x += pq[w].x;
+            RC.y += pq[w].y;
+          }
+          RL_SUB(11);
           RC.x *= lc;
           RC.y *= lc;
           mu = gp.mean + RD.x;
           var = (gp.lambda - RD.y) * vscale;  // k(z,z) = lambda: Stationary_GP.py:172-181
         } else {
+          RL_SUB(11);
           RD.x = Rp(ROW1, 0);
           RD.y = Rp(ROW1, 1);
           RC.x = Rp(crow, 0) * lc;
@@ -1154,6 +1220,8 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
           sd = sqrt(var);
           wj = eps / (2.0 * sd);
         }
+        // delta first: the partner workgroups wait for the granules, nobody for the Jacobian columns (two ifs, not if / else: the two
+        // sides of one branch may come out in either order)
         if (c == D) {
           const double dv = a.particle_pred ? fma(sd, eps, mu) : mu;
           dl[p * G + myg] = dv;
@@ -1165,7 +1233,10 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
             if (a.particle_pred && var <= 0.0) bad |= MCP_STATUS_NONPOS_VAR;  // (finite and not positive: a NaN variance is MCP_STATUS_NAN, the retry case)
             if (is_bad(mu) || is_bad(var)) bad |= MCP_STATUS_NAN;
           }
-        } else if (a.jac && m0 + p < Mend) {
+        }
+        asm volatile("" ::: "memory");
+        RL_SUB(12);
+        if (c < D && a.jac && m0 + p < Mend) {
           // centred sums  sum_j w_j (z_c - X_jc) = z_c R[D][.] - R[c][.]
           const double il = kpar[KP_INVLS(D) + c], il2 = il * il, zc = z[p * D + c];
           double Jmu = -2.0 * il2 * fma(zc, RD.x, -RC.x);
@@ -1181,13 +1252,12 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
               Jvar += 2.0 * zc * (a_ * fz[p * 4 + 3] + b_ * fz[p * 4 + 2]) - 2.0 * lc * (a_ * Rp(crow, 2) + b_ * Rp(crow, 3));
             }
           }
-          a.jac[(((size_t)t * M + m0 + p) * G + myg) * D + c] = a.particle_pred ? fma(wj, Jvar * vscale, Jmu) : Jmu;
+          jl[lane] = a.particle_pred ? fma(wj, Jvar * vscale, Jmu) : Jmu;  // (to global memory by the storing wave, behind B0)
         }
       }
-      RL_SUB(9);
+      RL_SUB(13);
       {
         // collect the other GPs' increments: lane -> (other GP, particle, half); every pass re-reads every granule
-        const unsigned long long tx0_ = stamping ? clock64() : 0;
         const int ngr = (G - 1) * P * 2;
         const bool act = lane < ngr;
         const int go = act ? lane / (2 * P) : 0, r = act ? lane - go * 2 * P : 0;
@@ -1210,7 +1280,6 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
         }
         if (act) reinterpret_cast<unsigned*>(dl)[2 * ((r >> 1) * G + gq) + (r & 1)] = val;
         if (!done && lane == 0) *abortw = 1;
-        if (stamping && lane == 0) stl[8] += clock64() - tx0_;
       }
       RL_SUB(10);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1225,30 +1294,36 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
         if (g_pos >= 0) nx = xc[os] + Ts * xc[vel_of_pos] + 0.5 * Ts * dl[op * G + g_pos];
         xn = nx;
       }
-      if (writer && lane < P * U) {  // the inputs of this step (off the critical path here); U <= 2
-        const int ip = U == 1 ? lane : lane >> 1, ik = U == 1 ? 0 : lane & 1;
-        if (m0 + ip < Mend) a.inputs[((size_t)t * M + m0 + ip) * U + ik] = z[ip * D + DS + ik];
-      }
+      RL_SUB(14);
     } else {
       draw_step(t + 1, wv, lane);
     }
     cur ^= 1;  // x_{t+1} goes to the other buffer
     RL_STAMP(7);
-    if (wv == 0) sub_stamp = stamping ? clock64() : 0;
+    if (wv == 0) RL_SUB_START();
   }
-  if (stamping && tid0 < 24) a.stamps[tid0] += stl[tid0];  // (the stamp buffer of this kernel has 24 slots: tools/phase_stamps.py)
+  if (stamping && tid0 < RL_NSTAMP) a.stamps[tid0] += stl[tid0];
   if (bad) atomicOr(a.status, bad);
 }
 
 
 // the latency-lean GP-sharded kernel: narrow SE-only models (cart-pole class); KR = phase-K items per thread
 static int gsh_grid(int nclusters, int G) { return ((nclusters + 7) / 8) * 8 * G; }  // (whole groups of 8 clusters: rollout_fwd.hip)
-template <int P, int KR, int MAXDEG, bool PMS>
-static int launch_fwd_lean_i(const FwdArgs& a, size_t lds, hipStream_t st) {
-  MCP_ENSURE_MAX_LDS(rollout_fwd_lat_kernel<P, KR, MAXDEG, PMS>);
-  hipLaunchKernelGGL((rollout_fwd_lat_kernel<P, KR, MAXDEG, PMS>), dim3(gsh_grid(a.nclusters, a.model.G)), dim3(RF_NT), lds, st, a);
+template <int P, int KR, int MAXDEG, bool PMS, bool STAMPS>
+static int launch_fwd_lean_s(const FwdArgs& a, size_t lds, hipStream_t st) {
+  MCP_ENSURE_MAX_LDS(rollout_fwd_lat_kernel<P, KR, MAXDEG, PMS, STAMPS>);
+  hipLaunchKernelGGL((rollout_fwd_lat_kernel<P, KR, MAXDEG, PMS, STAMPS>), dim3(gsh_grid(a.nclusters, a.model.G)), dim3(RF_NT), lds, st, a);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
+}
+// The stamped twin runs only when the caller passed a stamp buffer (mcp_dispatch.fwd_stamps) and exists for the base instantiations
+// at four particles per workgroup (every degree, with and without the measurement model: what tools/phase_stamps.py serves); any other
+// shape runs the product kernel and leaves the buffer as it was.
+template <int P, int KR, int MAXDEG, bool PMS>
+static int launch_fwd_lean_i(const FwdArgs& a, size_t lds, hipStream_t st) {
+  if constexpr (P == 4 && KR == 3)
+    if (a.stamps) return launch_fwd_lean_s<P, KR, MAXDEG, PMS, true>(a, lds, st);
+  return launch_fwd_lean_s<P, KR, MAXDEG, PMS, false>(a, lds, st);
 }
 // MAXDEGS: the polynomial degrees this (P, KR) pair is instantiated for (0 .. MAXDEGS)
 template <int P, int KR, int MAXDEGS>

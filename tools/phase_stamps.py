@@ -11,7 +11,7 @@ Mo = int(sys.argv[3]) if len(sys.argv) > 3 else None
 To = int(sys.argv[4]) if len(sys.argv) > 4 else None
 pd = float(sys.argv[5]) if len(sys.argv) > 5 else 0.25
 w = workloads.build(name, device=dev, M=Mo, T=To, p_drop=pd)
-buf = torch.zeros(32, dtype=torch.int64, device=dev)
+buf = torch.zeros(64, dtype=torch.int64, device=dev)  # (the lean kernel names 64 slots, the others 32)
 x0 = w.sample_x0()
 hipabi.lib().mcp_debug_set_particles_per_wg(ppw % 100)
 hipabi.lib().mcp_debug_set_fwd_lean(0 if 100 <= ppw < 200 else -1)  # 1xx: the general sharded kernel; 2xx / automatic: the lean one where it applies
@@ -53,17 +53,24 @@ else:
     else:
         print("bwd per step cycles: serial(wave0) %.0f | barrier1 %.0f | RBF stage %.0f | park+barrier2 %.0f" % tuple(x / w.T for x in (v2[8], v2[9], v2[10], v2[11])))
 print("workload", name, "T", w.T, "M", w.M, "ppw forced", ppw, "launched", hipabi.lib().mcp_debug_last_particles_per_wg(), "gp-sharded", hipabi.lib().mcp_debug_last_gp_sharded(), "lean", hipabi.lib().mcp_debug_last_fwd_lean(), "total cycles", tot, "-> per step", tot / (w.T - 1))
-print("tile kernel detail (wave 0, per step, all GPs): K setup %.0f, K tiles %.0f | J setup %.0f, J batches %.0f cyc" % tuple((0 if (i == 14 and hipabi.lib().mcp_debug_last_row_split()) else v[i]) / (w.T - 1) for i in (12, 13, 14, 15)))
-if not hipabi.lib().mcp_debug_last_row_split():  # (the row-split cluster's phase F uses these slots: printed at the end)
+lean_ran = bool(hipabi.lib().mcp_debug_last_fwd_lean())  # (the lean kernel uses these slots for wave 0's chain: printed below)
+if not lean_ran:
+    print("tile kernel detail (wave 0, per step, all GPs): K setup %.0f, K tiles %.0f | J setup %.0f, J batches %.0f cyc" % tuple((0 if (i == 14 and hipabi.lib().mcp_debug_last_row_split()) else v[i]) / (w.T - 1) for i in (12, 13, 14, 15)))
+if not lean_ran and not hipabi.lib().mcp_debug_last_row_split():  # (the row-split cluster's phase F uses these slots: printed at the end)
     print("J finish (wave 0, per step, all GPs): wait for the other waves %.0f, park + barrier %.0f, add + barrier %.0f cyc" % tuple(v[i] / (w.T - 1) for i in (9, 10, 11)))
 if hipabi.lib().mcp_debug_last_particles_per_wg() == 16:
     print("tile kernel, phase K per wave (own time, all GPs):", " ".join("%.0f" % (v[16 + i] / (w.T - 1)) for i in range(8)))
     print("tile kernel, phase V per wave (own time to the barrier, all GPs):", " ".join("%.0f" % (v[24 + i] / (w.T - 1)) for i in range(8)))
 if hipabi.lib().mcp_debug_last_fwd_lean():
-    print("lean kernel, wave 0 per step: S compute (to the barrier) %.0f | F compute (delta, granules, Jacobian stores) %.0f | hand-off poll %.0f | J (own rows) %.0f cyc"
-          % tuple(v[i] / (w.T - 1) for i in (15, 9, 10, 12)))
-    print("lean kernel, phase V per wave (own time, before the barrier):", " ".join("%.0f" % (v[16 + i] / (w.T - 1)) for i in range(8)))
-for n, c in zip(names, v):
+    if tot == 0:
+        sys.exit("no stamps: the lean kernel has stamped instantiations at 4 particles per workgroup and Npad <= 384 only (tools/README.md)")
+    per = lambda i: v[i] / (w.T - 1)
+    print("lean kernel, wave 0's chain per step: partial-tile sum %.0f | mu, var, delta -> granule stores %.0f | Jacobian columns %.0f | hand-off poll %.0f | "
+          "integrate %.0f | S (to the barrier) %.0f cyc" % tuple(per(i) for i in (11, 12, 13, 10, 14, 15)))
+    for label, base in (("policy pass", 24), ("K(state)", 32), ("u", 40), ("K(exp)", 48), ("phase V", 16)):
+        print("lean kernel, %-11s per wave (own time, waits excluded):" % label, " ".join("%.0f" % per(base + i) for i in range(8)))
+    v[8] = v[10]  # (the table below lists the poll in the general kernel's slot)
+for n, c in zip(names, v):  # (the barrier intervals as thread 0 sees them)
     print("%-14s %12d  %5.1f%%  %8.0f cyc/step" % (n, c, 100.0 * c / tot, c / (w.T - 1)))
 if hipabi.lib().mcp_debug_last_row_split():
     print("row-split cluster, phase F (thread 0, per step, all GPs): my sums %.0f | partner poll %.0f | finish %.0f | end of J -> end of hand-off %.0f cyc"
