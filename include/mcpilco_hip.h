@@ -280,6 +280,18 @@ size_t mcp_rollout_workspace_bytes(const mcp_model* model, const mcp_policy* pol
 int mcp_rollout_fwd(const mcp_model* model, const mcp_policy* policy, const mcp_noise* noise, int M, int T, int particle_pred,
                     const double* x0, double* states, double* inputs, double* jac, uint32_t* status, void* workspace,
                     size_t workspace_bytes, void* stream);
+/* Open-loop rollout: M trajectories advanced T steps by the model alone, the input of step t read from `u` (the inputs recorded on
+ * the system) -- no policy, no Jacobians, no workspace, one launch.  Replaces the step loop of MC_PILCO.rollout
+ * (policy_learning/MC_PILCO.py:347-373) over Model_learning.get_next_state (model_learning/Model_learning.py:210-229, 685-718).
+ * x0 [M][S]; u [T-1][Mu][U] with Mu == M, or Mu == 1: one input sequence shared by every trajectory; states [T][M][S].
+ * particle_pred bit 0 clear: delta = posterior mean, and unless `var` is asked for no Kinv is read (one workgroup per trajectory);
+ * set: delta = mu + sqrt(var) eps with var = var_scale (k(z,z) - k^T Kinv k), eps from noise->eps [T-1][M][G] or Philox keyed by
+ * (seed, call, m + particle_offset): trajectories [a, b) launched with particle_offset = a carry the bits of rows [a, b) of one launch
+ * over all of them.  lengths (optional, [M], 1 <= len <= T, clamped): trajectory m is advanced to row len - 1, its later rows are
+ * zeros and its inputs from row len - 1 on are never read.  mu / var (optional, [T-1][M][G]): the GP means and scaled variances of
+ * every step (what get_next_state returns; rows beyond a length are not written).  status: MCP_STATUS_NAN | MCP_STATUS_NONPOS_VAR. */
+int mcp_rollout_open(const mcp_model* model, const mcp_noise* noise, int M, int T, int particle_pred, const double* x0, const double* u,
+                     int Mu, const int32_t* lengths, double* states, double* mu, double* var, uint32_t* status, void* stream);
 /* Reverse-time adjoint of the rollout: given dJ/dstates, dJ/dinputs (either may be NULL) returns
  * dJ/d{log_lengthscales [P], centers [B][P], f_linear.weight [U][B]} (overwritten, this rank's
  * particles only; with policy->bias also dJ/dbias into policy->g_bias) and optionally dJ/dx0 [M][S].  Replaces autograd's backward through

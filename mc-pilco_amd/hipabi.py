@@ -114,6 +114,8 @@ _SIGS = {
     "mcp_rollout_workspace_bytes": (C.c_size_t, [C.POINTER(Model), C.POINTER(Policy), C.c_int, C.c_int]),
     "mcp_rollout_fwd": (C.c_int, [C.POINTER(Model), C.POINTER(Policy), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr, dptr,
                                   dptr, dptr, dptr, C.c_size_t, dptr]),
+    "mcp_rollout_open": (C.c_int, [C.POINTER(Model), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr, C.c_int, dptr, dptr, dptr, dptr,
+                                   dptr, dptr]),
     "mcp_rollout_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(Policy), C.POINTER(Noise), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr,
                                   dptr, dptr, dptr, dptr, dptr, C.c_size_t, dptr]),
     "mcp_rollout_fwd_ex": (C.c_int, [C.POINTER(Model), C.POINTER(Policy), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr, dptr,

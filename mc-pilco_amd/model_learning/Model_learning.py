@@ -248,6 +248,31 @@ class Model_learning(torch.nn.Module):
             self._packed_model = ops.PackedModel.delta(gps, S, U, angle, not_angle, Ts=Ts, var_scale=scale)
         return self._packed_model
 
+    # ---- open-loop rollout of given inputs, one launch ------------------------------------------------------------------
+    def steps_like_the_packed_model(self):
+        """Whether ``get_next_state`` is still the step ``packed()`` describes: a subclass that overrides the step (or the GP input map)
+        has to be rolled out step by step even though a layout exists."""
+        if not self.has_fused_layout():
+            return False
+        cls = type(self)
+        own = [c for c in cls.__mro__ if "packed" in c.__dict__][0]  # the class whose layout packed() builds
+        known_inputs = (Model_learning.data_to_gp_input, Model_learning_RBF_angle_state.data_to_gp_input,
+                        Speed_Model_learning_RBF_angle_state.data_to_gp_input)
+        return (all(getattr(cls, n) is getattr(own, n) for n in ("get_next_state", "get_next_state_from_gp_output", "get_one_step_gp_out"))
+                and cls.data_to_gp_input in known_inputs)
+
+    def open_loop_rollout(self, initial_states, inputs, particle_pred=False, lengths=None, noise=None, moments=False):
+        """Drives the model open loop by given inputs in ONE fused launch (ops.rollout_open): initial_states [M,S], inputs [T-1,M,U] or
+        [T-1,U] (shared by all trajectories) -> states [T,M,S] (+ GP means and variances [T-1,M,G] with ``moments``) and the status word.
+        Mean prediction unless ``particle_pred``; ``noise``: ops.NoiseSpec (eps buffer, or Philox seed / call).  The T-loop over
+        get_next_state of MC_PILCO.rollout (reference policy_learning/MC_PILCO.py:347-373) without its per-step launches."""
+        if not self.has_fused_layout():
+            raise NotImplementedError("no fused-rollout layout for this model: roll it out step by step on get_next_state")
+        t = lambda a: a if isinstance(a, torch.Tensor) else torch.as_tensor(a, dtype=self.dtype)
+        with torch.no_grad():
+            return ops.rollout_open(self.packed(), t(initial_states).to(self.device), t(inputs).to(self.device), lengths=lengths, noise=noise,
+                                    particle_pred=particle_pred, moments=moments)
+
     # ---- one-step prediction ------------------------------------------------------------------------------------------
     def get_next_state(self, current_state, current_input, particle_pred=True):
         """x_{t+1} samples (or means) with the mean and variance of the GP outputs."""

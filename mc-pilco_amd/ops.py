@@ -468,6 +468,50 @@ def rollout_forward_raw(model: Optional[PackedModel], policy: PackedPolicy, nois
     return states, inputs, jac, status
 
 
+def rollout_open(model: PackedModel, x0, u, *, lengths=None, noise: Optional[NoiseSpec] = None, particle_pred=False, moments=False, status=None):
+    """Open-loop rollout of recorded inputs in ONE launch (mcp_rollout_open): x0 [M,S], u [T-1,M,U] or [T-1,U] / [T-1,1,U] (one input
+    sequence shared by all trajectories) -> states [T,M,S].  ``particle_pred``: sampled increments (``noise``: an eps buffer [T-1,M,G] or
+    Philox by seed / call / particle_offset), else the posterior mean.  ``lengths`` [M] (1 <= len <= T): trajectory m stops at row
+    len - 1, its later rows are zeros.  ``moments``: also the GP means and scaled variances of every step, [T-1,M,G] (rows beyond a
+    length stay zero).  Returns (states, status) or (states, mu, var, status).  No autograd: nothing here is differentiated."""
+    for name, t in (("x0", x0), ("u", u)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError("rollout_open operates on GPU memory only (%s is not a GPU tensor); there is no CPU path" % name)
+        if t.requires_grad:
+            raise RuntimeError("rollout_open has no gradient: %s requires grad (detach it; the closed-loop ops.rollout is the differentiable one)" % name)
+    dev = model.device
+    x0 = x0.to(device=dev, dtype=DT).contiguous()
+    u = u.to(device=dev, dtype=DT).contiguous()
+    if x0.dim() != 2 or x0.shape[1] != model.S:
+        raise RuntimeError("x0 must be [M,%d]" % model.S)
+    M = int(x0.shape[0])
+    if u.dim() == 2:
+        u = u.reshape(u.shape[0], 1, u.shape[1])
+    if u.dim() != 3 or u.shape[2] != model.U or u.shape[1] not in (1, M) or u.shape[0] < 1:
+        raise RuntimeError("u must be [T-1,M,%d] or [T-1,%d]" % (model.U, model.U))
+    T, Mu = int(u.shape[0]) + 1, int(u.shape[1])
+    noise = NoiseSpec() if noise is None else noise
+    if particle_pred:
+        _check_noise(noise, T, M, model.G, 0, 0.0, True)
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths, dtype=torch.int32).to(dev).contiguous()
+        if tuple(lengths.shape) != (M,):
+            raise RuntimeError("lengths must have one entry per trajectory")
+    states = torch.empty(T, M, model.S, dtype=DT, device=dev)
+    mu = torch.zeros(T - 1, M, model.G, dtype=DT, device=dev) if moments else None
+    var = torch.zeros(T - 1, M, model.G, dtype=DT, device=dev) if moments else None
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    elif status.dtype != torch.int32 or status.numel() != 1 or status.device != x0.device or not status.is_contiguous():
+        raise RuntimeError("status must be a one-element int32 tensor on the rollout's device")
+    nz = noise.to_c()
+    abi.check(abi.lib().mcp_rollout_open(_mc(model), C.byref(nz), M, T, int(bool(particle_pred)), abi.ptr(x0), abi.ptr(u), Mu, abi.ptr(lengths),
+                                         abi.ptr(states), abi.ptr(mu), abi.ptr(var), abi.ptr(status), abi.stream()), "mcp_rollout_open")
+    if moments:
+        return states, mu, var, status
+    return states, status
+
+
 # measurement hook (bench.py): a pair of torch.cuda.Event recorded on the launch stream right around mcp_rollout_bwd -- the adjoint sweep
 # runs inside autograd's backward, where the caller cannot bracket it.  None (the default) = nothing is recorded.  ``fwd_events``: the same
 # around mcp_rollout_fwd (operand packing + hand-off buffer reset + the rollout kernel, without the host's tensor allocations).

@@ -69,6 +69,8 @@ class MC_PILCO(torch.nn.Module):
         self.noise_mode = "philox"
         self.seed = 0
         self._rollout_calls = 0
+        self.fused_open_loop = True       # MC_PILCO.rollout's mean chain as one fused launch (False: the step loop on get_next_state)
+        self.last_open_loop_fused = False  # what the last rollout() ran
         self.dist_group = None
         self.last_status = None
         self.gp_sharding = True    # cleared for good once a GP-sharded launch reports MCP_STATUS_SYNC (co-residency was not there)
@@ -704,17 +706,85 @@ class MC_PILCO(torch.nn.Module):
         self.num_data_collection += 1
         self.model_learning.add_data(new_state_samples=noisy, new_input_samples=inputs)
 
+    def _open_loop_fused(self):
+        """The open-loop rollouts go through the fused kernel: switched on (``fused_open_loop``) and the model's step is the one its fused
+        layout describes (Model_learning.steps_like_the_packed_model)."""
+        f = getattr(self.model_learning, "steps_like_the_packed_model", None)
+        return bool(self.fused_open_loop) and callable(f) and bool(f())
+
     def rollout(self, data_collection_index, T_rollout=None, particle_pred=False):
-        """Open-loop prediction of one recorded trajectory with the learned model (mean prediction by default)."""
+        """Open-loop prediction of one recorded trajectory with the learned model (mean prediction by default).  The mean chain of a model
+        with a fused layout is ONE launch (Model_learning.open_loop_rollout); the sampled single path (``particle_pred``) draws from the
+        torch generator in the reference's order and keeps the step loop, as do models whose step the layout does not describe."""
         xs = self.state_samples_history[data_collection_index]
-        us = torch.tensor(self.input_samples_history[data_collection_index], dtype=self.dtype, device=self.device)
         n = xs.shape[0] if T_rollout is None else T_rollout
+        self.last_open_loop_fused = bool(not particle_pred and n >= 2 and self._open_loop_fused())
+        if self.last_open_loop_fused:
+            x0 = torch.tensor(np.asarray(xs[0:1, :]), dtype=self.dtype, device=self.device)
+            us = torch.tensor(np.asarray(self.input_samples_history[data_collection_index])[0:n - 1, :], dtype=self.dtype, device=self.device)
+            states, status = self.model_learning.open_loop_rollout(x0, us)
+            self.last_status = status
+            return states[:, 0, :].cpu().numpy()
+        us = torch.tensor(self.input_samples_history[data_collection_index], dtype=self.dtype, device=self.device)
         traj = torch.zeros([n, self.state_dim], dtype=self.dtype, device=self.device)
         traj[0:1, :] = torch.tensor(xs[0:1, :], dtype=self.dtype, device=self.device)
         for t in range(1, n):
             traj[t:t + 1, :], _, _ = self.model_learning.get_next_state(current_state=traj[t - 1:t, :], current_input=us[t - 1:t, :],
                                                                          particle_pred=particle_pred)
         return traj.detach().cpu().numpy()
+
+    def rollout_ensemble(self, data_collection_index=None, num_particles=400, T_rollout=None, seed=None):
+        """The particle picture of the open-loop check: ``num_particles`` sampled open-loop trajectories per recorded run, each started at
+        the run's first recorded state and driven by its recorded inputs -- for every recorded run (``data_collection_index`` None; or one
+        index, or a list) in ONE launch (ragged lengths, M = runs x particles).  Returns a list with one array [T_run, num_particles, S] per
+        run (the array itself for a single index) and prints, per state, the MSE of the particle mean and the share of recorded samples
+        within mean +- 2 std.  The draws are Philox keyed by (``seed``, default ``self.seed``; the run's index; the particle): a run's
+        particles do not depend on which other runs share the launch."""
+        f = getattr(self.model_learning, "steps_like_the_packed_model", None)
+        if not (callable(f) and f()):  # (the predicate of rollout(): a model whose own step the layout does not describe must not be simulated by it)
+            raise NotImplementedError("rollout_ensemble needs a model with a fused-rollout layout whose get_next_state is the step that layout "
+                                      "describes (Model_learning.steps_like_the_packed_model)")
+        single = data_collection_index is not None and np.isscalar(data_collection_index)
+        runs = (list(range(len(self.state_samples_history))) if data_collection_index is None
+                else [int(data_collection_index)] if single else [int(i) for i in data_collection_index])
+        runs = [r % len(self.state_samples_history) for r in runs]
+        P = int(num_particles)
+        lens = [int(self.state_samples_history[r].shape[0]) if T_rollout is None else min(int(T_rollout), int(self.state_samples_history[r].shape[0]))
+                for r in runs]
+        if not runs or P < 1 or min(lens) < 2:
+            raise ValueError("rollout_ensemble needs at least one recorded run of two samples and one particle")
+        # global trajectory id = run index * num_particles + particle (mcp_noise.particle_offset): a run's draws are the same whether it is
+        # launched alone or with the others.  Consecutive run indices share a launch -- every recorded run: ONE launch.
+        groups = [[0]]
+        for k in range(1, len(runs)):
+            if runs[k] == runs[k - 1] + 1:
+                groups[-1].append(k)
+            else:
+                groups.append([k])
+        sd = self.seed if seed is None else int(seed)
+        stat = torch.zeros(1, dtype=torch.int32, device=self.device)
+        t_dev = lambda a, dt: torch.tensor(a, dtype=dt, device=self.device)
+        U, parts, out = self.input_dim, {}, []
+        for grp in groups:
+            Tm = max(max(lens[k] for k in grp), 2)
+            x0 = np.concatenate([np.repeat(np.asarray(self.state_samples_history[runs[k]])[0:1, :], P, 0) for k in grp], 0)
+            u = np.zeros([Tm - 1, len(grp) * P, U])
+            for i, k in enumerate(grp):
+                u[:lens[k] - 1, i * P:(i + 1) * P, :] = np.asarray(self.input_samples_history[runs[k]])[:lens[k] - 1, None, :]
+            noise = ops.NoiseSpec(seed=sd, call=0, particle_offset=runs[grp[0]] * P)
+            states, _ = ops.rollout_open(self.model_learning.packed(), t_dev(x0, self.dtype), t_dev(u, self.dtype),
+                                         lengths=t_dev(np.repeat([lens[k] for k in grp], P), torch.int32), noise=noise, particle_pred=True, status=stat)
+            for i, k in enumerate(grp):
+                parts[k] = states[:lens[k], i * P:(i + 1) * P, :].cpu().numpy()
+        self.last_status = stat
+        for k, r in enumerate(runs):
+            part = parts[k]
+            obs = np.asarray(self.state_samples_history[r])[:lens[k]]
+            mean, std = part.mean(1), part.std(1)
+            print("Run", r, "ensemble mean MSE per state:", np.mean((mean - obs) ** 2, 0), " inside mean +- 2 std:",
+                  np.mean(np.abs(obs - mean) <= 2 * std, 0))
+            out.append(part)
+        return out[0] if single else out
 
     def get_model_learning_performance(self, data_collection_index, flg_pretrain=False):
         """One-step GP predictions on the data of one interaction with the system (MC_PILCO.py:260-306): prints the MSE per GP,
