@@ -304,15 +304,20 @@ int mcp_rollout_bwd(const mcp_model* model, const mcp_policy* policy, const mcp_
 /* ---- cost (policy_learning/Cost_function.py) ------------------------------------------ */
 #define MCP_COST_CARTPOLE 0 /* cart_pole_cost, Cost_function.py:170-182                          */
 #define MCP_COST_TRAJ 1     /* saturated_distance_from_trajectory, Cost_function.py:124-147      */
+/* Target-state costs (Cost_function.py:39-101) over d = sum_i ((x[used[i]] - target[i]) / lengthscales[i])^2, i < n_used.
+ * They reuse the trajectory cost's fields, with ONE difference: target_traj points at ONE row [n_used], indexed like
+ * lengthscales (by position in `used`) and read at every t -- not MCP_COST_TRAJ's [T][S] rows indexed by state. */
+#define MCP_COST_TARGET 2      /* saturated_distance_from_target: 1 - exp(-d)                    */
+#define MCP_COST_TARGET_QUAD 3 /* distance_from_target: d                                        */
 typedef struct mcp_cost {
   int32_t kind;
   int32_t S;
   int32_t angle_index, pos_index;       /* cart-pole                                    */
   double target_angle, target_pos;      /* target_state = [theta*, x*]                  */
   double ls_angle, ls_pos;              /* lengthscales = [l_theta, l_x]                */
-  int32_t n_used;                       /* trajectory cost: used_indeces                */
+  int32_t n_used;                       /* trajectory / target costs: used_indeces      */
   int32_t used[MCP_MAX_STATE];
-  const double* target_traj;            /* [T][S]                                       */
+  const double* target_traj;            /* [T][S]; MCP_COST_TARGET*: [n_used]           */
   const double* lengthscales;           /* [n_used]                                     */
 } mcp_cost;
 /* costs[t][m] = c(x_{t,m});  moments[t] = {mean_m c, sum_m (c-mean)^2} over THIS rank's M

@@ -1,6 +1,10 @@
 // Expected-cost kernels for gfx950: Expected_cost.forward (policy_learning/Cost_function.py:25-36)
-// with cart_pole_cost (:170-182) or saturated_distance_from_trajectory (:124-147), and their
-// state gradient.  HBM-bound elementwise + per-time-step reductions over the particle axis.
+// with cart_pole_cost (:170-182), saturated_distance_from_trajectory (:124-147) or the target-state
+// costs distance_from_target / saturated_distance_from_target (:53-101), and their state gradient.
+// HBM-bound elementwise + per-time-step reductions over the particle axis.
+// The target-state distance is summed in the difference form sum_i ((x_i - x*_i) / l_i)^2; the reference
+// expands it (||x/l||^2 + ||x*/l||^2 - 2 (x/l).(x*/l)), which only adds cancellation: the two agree to the
+// rounding of the expanded form, within the 1e-12 the reference's fixture is held to.
 #include "mcp_device.h"
 
 using namespace mcp;
@@ -11,14 +15,20 @@ __device__ __forceinline__ double cost_point(const mcp_cost& c, const double* x,
     double a = (fabs(x[c.angle_index]) - c.target_angle) / c.ls_angle;
     double b = (x[c.pos_index] - c.target_pos) / c.ls_pos;
     dist = a * a + b * b;
-  } else {
+  } else if (c.kind == MCP_COST_TRAJ) {
     for (int i = 0; i < c.n_used; ++i) {
       int s = c.used[i];
       double r = (x[s] - c.target_traj[(size_t)t * c.S + s]) / c.lengthscales[i];
       dist = fma(r, r, dist);
     }
+  } else {  // MCP_COST_TARGET / _QUAD: ONE target row [n_used], the same at every t
+    for (int i = 0; i < c.n_used; ++i) {
+      double r = (x[c.used[i]] - c.target_traj[i]) / c.lengthscales[i];
+      dist = fma(r, r, dist);
+    }
   }
   if (dist_out) *dist_out = dist;
+  if (c.kind == MCP_COST_TARGET_QUAD) return dist;
   return 1.0 - exp(-dist);
 }
 
@@ -149,7 +159,8 @@ __global__ void cost_bwd_kernel(mcp_cost c, int T, int M, const double* __restri
   double* g = g_states + i * c.S;
   double dist;
   cost_point(c, x, t, &dist);
-  double e = (g_cost ? *g_cost : 1.0) * gscale * exp(-dist);  // d c / d dist = exp(-dist)
+  double e = (g_cost ? *g_cost : 1.0) * gscale;
+  if (c.kind != MCP_COST_TARGET_QUAD) e *= exp(-dist);  // d c / d dist = exp(-dist); 1 for the plain distance
   for (int s = 0; s < c.S; ++s) g[s] = 0.0;
   if (c.kind == MCP_COST_CARTPOLE) {
     double th = x[c.angle_index];
@@ -158,10 +169,16 @@ __global__ void cost_bwd_kernel(mcp_cost c, int T, int M, const double* __restri
     double sg = th > 0.0 ? 1.0 : (th < 0.0 ? -1.0 : 0.0);  // d|theta|/dtheta, 0 at 0 like torch.abs
     g[c.angle_index] += e * 2.0 * a * sg / c.ls_angle;
     g[c.pos_index] += e * 2.0 * b / c.ls_pos;
-  } else {
+  } else if (c.kind == MCP_COST_TRAJ) {
     for (int k = 0; k < c.n_used; ++k) {
       int s = c.used[k];
       double r = (x[s] - c.target_traj[(size_t)t * c.S + s]) / c.lengthscales[k];
+      g[s] += e * 2.0 * r / c.lengthscales[k];
+    }
+  } else {  // (an index listed twice accumulates, as torch's indexing backward does)
+    for (int k = 0; k < c.n_used; ++k) {
+      int s = c.used[k];
+      double r = (x[s] - c.target_traj[k]) / c.lengthscales[k];
       g[s] += e * 2.0 * r / c.lengthscales[k];
     }
   }
@@ -172,7 +189,7 @@ static bool cost_ok(const mcp_cost* c) {
   if (c->kind == MCP_COST_CARTPOLE)
     return c->angle_index >= 0 && c->angle_index < c->S && c->pos_index >= 0 && c->pos_index < c->S && c->ls_angle != 0.0 &&
            c->ls_pos != 0.0;
-  if (c->kind == MCP_COST_TRAJ) {
+  if (c->kind == MCP_COST_TRAJ || c->kind == MCP_COST_TARGET || c->kind == MCP_COST_TARGET_QUAD) {
     if (c->n_used <= 0 || c->n_used > MCP_MAX_STATE || !c->target_traj || !c->lengthscales) return false;
     for (int i = 0; i < c->n_used; ++i)
       if (c->used[i] < 0 || c->used[i] >= c->S) return false;

@@ -32,6 +32,10 @@ def _t(x, device):
     return torch.as_tensor(np.asarray(x, dtype=np.float64)).to(device).contiguous()
 
 
+def _count(x):
+    return int(x.numel()) if isinstance(x, torch.Tensor) else int(np.asarray(x).size)
+
+
 def pad16(n):
     return (int(n) + 15) // 16 * 16
 
@@ -629,6 +633,25 @@ class PackedCost:
             self._keep = [tt, ls]
             c.target_traj, c.lengthscales = tt.data_ptr(), ls.data_ptr()
             self.traj_len = int(tt.shape[0])
+        elif kind == "target":
+            # target-state costs (Cost_function.py:39-101): ONE target row over ``active_dims``; saturate False = the plain distance.
+            # Everything is checked on the host values first: a bad descriptor never reaches the device.
+            c.kind = abi.COST_TARGET if kw.get("saturate", True) else abi.COST_TARGET_QUAD
+            act = [int(i) for i in np.asarray(kw["active_dims"]).reshape(-1)]
+            n_t, n_l = _count(kw["target_state"]), _count(kw["lengthscales"])
+            if not (len(act) == n_t == n_l):
+                raise ValueError("target cost: %d active dims, %d target entries (one row) and %d lengthscales must agree" % (len(act), n_t, n_l))
+            if not 1 <= len(act) <= abi.MAX_STATE:
+                raise ValueError("target cost: 1..%d active dims are supported (%d given)" % (abi.MAX_STATE, len(act)))
+            if any(i < 0 or i >= int(S) for i in act):
+                raise ValueError("target cost: active dims %s outside the state [0, %d)" % (act, int(S)))
+            c.n_used = len(act)
+            for i, u in enumerate(act):
+                c.used[i] = u
+            tg = _t(kw["target_state"], dev).reshape(-1)
+            ls = _t(kw["lengthscales"], dev).reshape(-1)
+            self._keep = [tg, ls]
+            c.target_traj, c.lengthscales = tg.data_ptr(), ls.data_ptr()
         else:
             raise ValueError(kind)
         self.kind, self.c, self.device = kind, c, dev

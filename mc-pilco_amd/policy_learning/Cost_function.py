@@ -3,10 +3,14 @@
   Expected_cost.forward                          Cost_function.py:25-36    sum_t mean_m c , sum_t std_m c (unbiased, detached)
   Cart_pole_cost / cart_pole_cost                Cost_function.py:150-182
   Expected_saturated_distance_from_trajectory    Cost_function.py:104-147
+  Expected_distance / Expected_saturated_distance    Cost_function.py:39-101
 
-The two costs the launch scripts use run in the HIP cost kernels (forward and state gradient).  A generic
-``Expected_cost(cost_function)`` with a user-supplied torch function keeps working (it is user code and runs
-as ordinary torch ops on the GPU), as do the simple distance variants built on it (:39-101).
+The two costs the launch scripts use run in the HIP cost kernels (forward and state gradient), and so do the two
+target-state costs whenever they have ONE target row and are handed float64 GPU states (``runs_on_kernels``): three
+launches for cost + gradient, eligible for the recorded attempts of ``MC_PILCO.reinforce_policy`` and for the pooled
+sums of a sharded step.  With several target rows, on CPU tensors or in another dtype they evaluate their
+``cost_function`` (kept as an attribute: user code may call it) as ordinary torch ops, exactly as before.  A generic
+``Expected_cost(cost_function)`` with a user-supplied torch function keeps working the same way (it is user code).
 ``forward(..., group=None)``: with a torch.distributed group the mean / std pool every rank's particles.
 """
 import numpy as np
@@ -77,6 +81,11 @@ class _HipExpectedCost(Expected_cost):
 
     def _pack(self, states):
         raise NotImplementedError()
+
+    def runs_on_kernels(self, states=None):
+        """Whether this cost (for these states, when given) is evaluated by the HIP cost kernels: what makes an attempt recordable into a
+        HIP graph (MC_PILCO.reinforce_policy).  A subclass that keeps a torch path for some instances or inputs answers for them here."""
+        return True
 
     def forward(self, states_sequence, inputs_sequence=None, trial_index=None, group=None, counts=None):
         if self._packed is None or self._packed.device != states_sequence.device:
@@ -174,11 +183,89 @@ def saturated_distance_from_target(states_sequence, inputs_sequence, trial_index
     return 1 - torch.exp(-distance_from_target(states_sequence, inputs_sequence, trial_index, target_state, lengthscales, active_dims))
 
 
-class Expected_distance(Expected_cost):
+class _TargetStateCost(_HipExpectedCost):
+    """A cost over the scaled distance from ONE target state, d = sum_i ((x[active_dims[i]] - x*_i) / l_i)^2.  On float64 GPU states it
+    runs in the HIP cost kernels (ops.PackedCost("target")); everything else the torch formula accepts -- K target rows [K, n] (the
+    reference then sums K per-target stds, which the kernels' [T][2] moments do not hold), CPU tensors, another dtype, parameters that
+    require grad, more than MCP_MAX_STATE indices -- is evaluated by ``cost_function`` through ``Expected_cost``, call by call."""
+
+    _saturate = True
+    _torch_cost = None
+
     def __init__(self, target_state, lengthscales, active_dims):
-        super().__init__(lambda x, u, k: distance_from_target(x, u, k, target_state, lengthscales, active_dims))
+        super().__init__()
+        f = type(self)._torch_cost
+        self.cost_function = lambda x, u, k: f(x, u, k, target_state, lengthscales, active_dims)
+        self.target_state, self.lengthscales, self.active_dims = target_state, lengthscales, active_dims
+        self._act = self._one_target(target_state, lengthscales, active_dims)
+        if self._act is None:
+            self.from_sums = Expected_cost.from_sums  # (this instance never leaves the torch path)
+
+    @staticmethod
+    def _one_target(target_state, lengthscales, active_dims):
+        """The active dims as ints when the descriptor fits the kernels (one target row, one lengthscale per index), else None."""
+        try:
+            act = [int(i) for i in np.asarray(active_dims).reshape(-1)]
+        except (TypeError, ValueError):  # (a slice, a mask: torch indexing takes them, the kernels' index list does not)
+            return None
+        if np.asarray(active_dims).dtype == bool or not 1 <= len(act) <= ops.abi.MAX_STATE:
+            return None
+        for v in (target_state, lengthscales):
+            if isinstance(v, torch.Tensor) and v.requires_grad:
+                return None
+        tg = target_state if isinstance(target_state, torch.Tensor) else np.asarray(target_state)
+        one_row = tg.ndim == 1 or (tg.ndim == 2 and tg.shape[0] == 1)
+        if not one_row or tg.shape[-1] != len(act) or ops._count(lengthscales) != len(act):
+            return None
+        return act
+
+    def runs_on_kernels(self, states=None):
+        if self._act is None:
+            return False
+        if states is None:
+            return True
+        S = states.shape[-1]
+        return (states.is_cuda and states.dtype == torch.float64 and states.dim() == 3 and S <= ops.abi.MAX_STATE
+                and all(-S <= i < S for i in self._act))
+
+    def _pack(self, states):
+        S = states.shape[2]
+        return ops.PackedCost("target", S, states.device, target_state=_np(self.target_state), lengthscales=_np(self.lengthscales),
+                              active_dims=[i % S for i in self._act], saturate=self._saturate)
+
+    def _select(self, states, trial_index=None):
+        if self._packed is not None and self._packed.c.S != states.shape[2]:
+            self._packed = None
+
+    def forward(self, states_sequence, inputs_sequence=None, trial_index=None, group=None, counts=None):
+        if not self.runs_on_kernels(states_sequence):
+            return Expected_cost.forward(self, states_sequence, inputs_sequence, trial_index, group, counts)
+        self._select(states_sequence)
+        return super().forward(states_sequence, inputs_sequence, trial_index, group, counts)
+
+    def local_moments(self, states_sequence, inputs_sequence, trial_index, m_total, shift=None, sums_out=None):
+        if not self.runs_on_kernels(states_sequence):
+            return Expected_cost.local_moments(self, states_sequence, inputs_sequence, trial_index, m_total, shift, sums_out)
+        self._select(states_sequence)
+        return super().local_moments(states_sequence, inputs_sequence, trial_index, m_total, shift, sums_out)
+
+    @staticmethod
+    def from_sums(sums, n_total, shift=None, mean_out=None):
+        # (the sums of either path have one meaning; they are pooled where local_moments left them)
+        if sums.is_cuda and sums.dtype == torch.float64:
+            return _HipExpectedCost.from_sums(sums, n_total, shift, mean_out)
+        return Expected_cost.from_sums(sums, n_total, shift, mean_out)
 
 
-class Expected_saturated_distance(Expected_cost):
-    def __init__(self, target_state, lengthscales, active_dims):
-        super().__init__(lambda x, u, k: saturated_distance_from_target(x, u, k, target_state, lengthscales, active_dims))
+class Expected_distance(_TargetStateCost):
+    """sum_i ((x_i - x*_i) / l_i)^2 over ``active_dims`` (Cost_function.py:39-63)."""
+
+    _saturate = False
+    _torch_cost = staticmethod(distance_from_target)
+
+
+class Expected_saturated_distance(_TargetStateCost):
+    """1 - exp(-sum_i ((x_i - x*_i) / l_i)^2) over ``active_dims`` (Cost_function.py:66-101)."""
+
+    _saturate = True
+    _torch_cost = staticmethod(saturated_distance_from_target)

@@ -398,7 +398,8 @@ class MC_PILCO(torch.nn.Module):
         use_graph = (bool(getattr(self, "capture_attempts", False)) and depth > 0 and adam is not None and dev.type == "cuda"
                      and type(self).apply_policy is MC_PILCO.apply_policy  # (the measurement-model rollout of MC_PILCO4PMS keeps the eager loop)
                      and isinstance(pol_, _Policy.Sum_of_gaussians) and getattr(pol_, "_unit_scale", False)
-                     and _has_fused_layout(self.model_learning) and isinstance(self.cost_function, _Cost._HipExpectedCost))
+                     and _has_fused_layout(self.model_learning) and isinstance(self.cost_function, _Cost._HipExpectedCost)
+                     and self.cost_function.runs_on_kernels())  # (a target-state cost with several target rows keeps its torch path)
         cap = dict(on=use_graph, graphs=[None, None], outs=[None, None], eager=0, rec=torch.zeros(2, abi.OPT_RECORD_DOUBLES, dtype=dt, device=dev),
                    one=torch.ones(1, dtype=dt, device=dev), last_flat=None)
         self.attempts_replayed = 0

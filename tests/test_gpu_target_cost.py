@@ -1,0 +1,293 @@
+"""GPU: the target-state expected costs (Expected_distance / Expected_saturated_distance, Cost_function.py:39-101) on the HIP cost kernels
+(MCP_COST_TARGET_QUAD / MCP_COST_TARGET): against the reference's fixture, against the CPU oracle at the shapes where the kernels' indexing
+can go wrong, the status word, the classes' choice of path, the recorded optimizer loop and the sharded (summable) form."""
+import contextlib
+import io
+
+import numpy as np
+import pytest
+import torch
+
+from mc_pilco_amd import synthetic as sy
+
+pytestmark = pytest.mark.gpu
+DT = torch.float64
+KINDS = (("dist", False), ("sat", True))
+
+
+def dev():
+    return torch.device("cuda", 0)
+
+
+def G(a):
+    return torch.tensor(np.asarray(a), dtype=DT, device=dev())
+
+
+def relerr(a, b):
+    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    b = b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else np.asarray(b)
+    return float(np.max(np.abs(a - b)) / max(1e-300, np.max(np.abs(b))))
+
+
+def packed(S, target, ls, used, saturate):
+    from mc_pilco_amd import ops
+
+    return ops.PackedCost("target", S, dev(), target_state=target, lengthscales=ls, active_dims=used, saturate=saturate)
+
+
+def cost_std_grad(pc, states):
+    from mc_pilco_amd import ops
+
+    st = G(states).requires_grad_(True)
+    c, s = ops.expected_cost(pc, st)
+    c.backward()
+    return c.detach(), s.detach(), st.grad
+
+
+# ---- 1: the reference's own numbers ------------------------------------------------------------------------------------------------------
+def test_packed_target_cost_matches_the_reference_fixture(golden):
+    """simple_costs.npz (T = 6, M = 10, S = 4, active [0, 1, 2], one target row; written by the reference's classes): cost, std and state
+    gradient of both kinds at 1e-12 relative, the bound test_gpu_dropin.py:509-511 holds these quantities to."""
+    fx = golden("simple_costs")
+    act = [int(i) for i in fx["active_dims"]]
+    assert fx["target"].shape == (1, 3)
+    for tag, sat in KINDS:
+        c, s, g = cost_std_grad(packed(4, fx["target"], fx["lengthscales"], act, sat), fx["states"])
+        ec = abs(float(c) - float(fx[tag + "_cost"])) / abs(float(fx[tag + "_cost"]))
+        es = abs(float(s) - float(fx[tag + "_std"])) / abs(float(fx[tag + "_std"]))
+        eg = relerr(g, fx[tag + "_grad"])
+        print("fixture %s: cost %.2e std %.2e grad %.2e" % (tag, ec, es, eg))
+        assert ec < 1e-12 and es < 1e-12 and eg < 1e-12
+
+
+# ---- 2: the oracle at the smallest shapes where the kernels can go wrong -----------------------------------------------------------------
+SHAPES = [(1, 2, 1, [0]),                          # one step, one state, the smallest swarm with a std
+          (3, 257, 4, [2, 0]),                     # M crosses the 256-thread stride by one; T M = 771 is no multiple of the backward's 256
+          (2, 64, 16, list(range(15, -1, -1)))]    # the state limit MCP_MAX_STATE, every index, reversed
+
+
+def draw(T, M, S, used, seed=7):
+    """States with |x_i - x*_i| / l_i <= 3 / sqrt(n_used) <= 3 on the used indices: d <= 9 for every n_used, so 1 - exp(-d) stays away from
+    the saturation where its own rounding (one ulp of 1) would decide the std; the other columns are arbitrary."""
+    rs = np.random.RandomState(seed)
+    n = len(used)
+    x = rs.randn(T, M, S)
+    ls = 0.5 + 1.5 * rs.rand(n)
+    tg = 2 * rs.rand(n) - 1
+    r = (2 * rs.rand(T, M, n) - 1) * 3 / np.sqrt(n)
+    for i, s in enumerate(used):
+        x[:, :, s] = tg[i] + ls[i] * r[:, :, i]
+    return x, tg, ls
+
+
+@pytest.fixture(scope="module")
+def oracle_cases():
+    """Per (shape, kind): the oracle's per-particle costs, cost, std and autograd gradient (CPU fp64), computed once."""
+    from oracle import mcpilco_oracle as orc
+
+    out = {}
+    for T, M, S, used in SHAPES:
+        x, tg, ls = draw(T, M, S, used)
+        for tag, sat in KINDS:
+            xs = torch.tensor(x, dtype=DT, requires_grad=True)
+            f = orc.saturated_distance_cost if sat else orc.distance_cost
+            c = f(xs, torch.tensor(tg, dtype=DT), torch.tensor(ls, dtype=DT), used)
+            cost = torch.sum(torch.mean(c, 1))
+            std = torch.sum(torch.std(c.detach(), 1))
+            cost.backward()
+            out[(T, M, S, tag)] = dict(x=x, tg=tg, ls=ls, used=used, costs=c.detach(), cost=cost.detach(), std=std, grad=xs.grad)
+    return out
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "T%dM%dS%d" % s[:3])
+@pytest.mark.parametrize("tag,sat", KINDS)
+def test_target_cost_matches_the_oracle(oracle_cases, shape, tag, sat):
+    """The oracle evaluates the reference's expanded form; for these inputs it is within 3e-15 (relative, max norm) of the difference form in
+    torch fp64 on the CPU in every quantity (measured: cost <= 3.0e-16, std <= 1.1e-15, gradient <= 2.7e-15, per-particle <= 1.1e-15), so the
+    project's 1e-12 for cost, std and gradient is a fair bound here as well and serves for the per-particle costs too."""
+    from mc_pilco_amd import ops
+
+    T, M, S, used = shape
+    o = oracle_cases[(T, M, S, tag)]
+    pc = packed(S, o["tg"], o["ls"], used, sat)
+    c, s, g = cost_std_grad(pc, o["x"])
+    mom, costs, _ = ops.cost_moments(pc, G(o["x"]))
+    ec = abs(float(c) - float(o["cost"])) / abs(float(o["cost"]))
+    es = abs(float(s) - float(o["std"])) / abs(float(o["std"]))
+    eg, ep = relerr(g, o["grad"]), relerr(costs, o["costs"])
+    print("oracle %s T=%d M=%d S=%d: cost %.2e std %.2e grad %.2e per-particle %.2e" % (tag, T, M, S, ec, es, eg, ep))
+    assert costs.shape == (T, M) and g.shape == (T, M, S)
+    assert ec < 1e-12 and es < 1e-12 and eg < 1e-12 and ep < 1e-12
+    unused = [i for i in range(S) if i not in used]
+    assert float(g[:, :, unused].abs().sum()) == 0.0 if unused else True  # exactly zero, not small
+    assert bool((g[:, :, used] != 0).any())
+
+
+def test_repeated_index_accumulates_like_torch_indexing():
+    """active_dims = [1, 1, 3]: the distance counts state 1 twice (two targets, two lengthscales) and its gradient is the sum of both terms."""
+    from mc_pilco_amd.policy_learning import Cost_function as CF
+
+    x, _, _ = draw(2, 5, 4, [1, 3], seed=3)
+    tg, ls, used = [0.2, -0.4, 0.1], [1.1, 0.6, 1.7], [1, 1, 3]
+    for tag, sat in KINDS:
+        c, s, g = cost_std_grad(packed(4, tg, ls, used, sat), x)
+        xt = torch.tensor(x, dtype=DT, requires_grad=True)
+        f = CF.saturated_distance_from_target if sat else CF.distance_from_target
+        ct = f(xt, None, 0, torch.tensor(tg, dtype=DT), torch.tensor(ls, dtype=DT), used)
+        ref = torch.sum(torch.mean(ct, 1))
+        ref.backward()
+        assert abs(float(c) - float(ref.detach())) < 1e-12 * abs(float(c)) and relerr(g, xt.grad) < 1e-12
+        assert float(g[:, :, [0, 2]].abs().sum()) == 0.0
+
+
+# ---- 3: the status word -----------------------------------------------------------------------------------------------------------------
+def test_nan_state_raises_the_status_flag():
+    from mc_pilco_amd import hipabi, ops
+
+    x, tg, ls = draw(3, 257, 4, [2, 0])
+    for _, sat in KINDS:
+        pc = packed(4, tg, ls, [2, 0], sat)
+        for col, flagged in ((2, True), (1, False)):  # (column 1 is not read by this cost: a NaN there is not the cost's business)
+            st = G(x)
+            st[1, 256, col] = float("nan")
+            status = torch.zeros(1, dtype=torch.int32, device=dev())
+            mom, costs, status = ops.cost_moments(pc, st, status=status)
+            assert bool(int(status.item()) & hipabi.STATUS_NAN) == flagged
+            assert bool(torch.isnan(costs[1, 256])) == flagged and bool(torch.isnan(mom[1, 0])) == flagged
+            assert bool(torch.isfinite(mom[[0, 2]]).all())
+
+
+# ---- 4: the classes pick their path --------------------------------------------------------------------------------------------------------
+def test_classes_run_on_the_kernels_with_one_target_row_and_in_torch_with_two(golden):
+    from mc_pilco_amd.policy_learning import Cost_function as CF
+
+    fx = golden("simple_costs")
+    act = [int(i) for i in fx["active_dims"]]
+    for (tag, sat), cls, f in zip(KINDS, (CF.Expected_distance, CF.Expected_saturated_distance),
+                                  (CF.distance_from_target, CF.saturated_distance_from_target)):
+        # one row on GPU states: the kernels, i.e. exactly what the packed descriptor gives
+        cf = cls(target_state=G(fx["target"]), lengthscales=G(fx["lengthscales"]), active_dims=act)
+        assert cf._packed is None and cf.runs_on_kernels()
+        st = G(fx["states"]).requires_grad_(True)
+        c, s = cf(st, None, 0)
+        c.backward()
+        assert cf._packed is not None and cf._packed.kind == "target" and cf.runs_on_kernels(st)
+        c0, s0, g0 = cost_std_grad(packed(4, fx["target"], fx["lengthscales"], act, sat), fx["states"])
+        assert torch.equal(c.detach(), c0) and torch.equal(s.detach(), s0) and torch.equal(st.grad, g0)
+        assert torch.allclose(cf.cost_function(st.detach(), None, 0), f(st.detach(), None, 0, G(fx["target"]), G(fx["lengthscales"]), act))
+        # two target rows (the torch formula pairs them with two particles): the plain torch formula, bit for bit, nothing packed
+        tg2 = G([[0.3, -0.2, 1.0], [0.1, 0.4, -0.6]])
+        cf2 = cls(target_state=tg2, lengthscales=G(fx["lengthscales"]), active_dims=act)
+        x2 = G(fx["states"][:, :2]).requires_grad_(True)
+        c2, s2 = cf2(x2, None, 0)
+        c2.backward()
+        y2 = G(fx["states"][:, :2]).requires_grad_(True)
+        ct = f(y2, None, 0, tg2, G(fx["lengthscales"]), act)
+        cr, sr = torch.sum(torch.mean(ct, 1)), torch.sum(torch.std(ct.detach(), 1))
+        cr.backward()
+        assert not cf2.runs_on_kernels() and cf2._packed is None
+        assert torch.equal(c2, cr) and torch.equal(s2, sr) and torch.equal(x2.grad, y2.grad)
+
+
+# ---- 5: the optimizer loop records its attempts with a target-state cost ---------------------------------------------------------------------
+def tiny_mcpilco():
+    """The `tiny` workload's model and policy (workloads.py: 48 training rows of the first synthetic cart-pole rollout, the launch-script
+    policy initialisation) on the drop-in classes, with Expected_saturated_distance on the pole angle and the cart position."""
+    from mc_pilco_amd.model_learning import Model_learning as ML
+    from mc_pilco_amd.policy_learning import MC_PILCO, Cost_function, Policy
+
+    c = sy.CARTPOLE
+    rbf = dict(active_dims=np.arange(6), lengthscales_init=np.asarray(c["lengthscales"], dtype=float), flg_train_lengthscales=True,
+               lambda_init=np.ones(1), flg_train_lambda=False, sigma_n_init=c["sigma_n"] * np.ones(1), sigma_n_num=None, flg_train_sigma_n=True,
+               dtype=DT, device=dev())
+    mlp = dict(num_gp=2, T_sampling=c["Ts"], angle_indeces=c["angle"], not_angle_indeces=c["not_angle"], vel_indeces=c["vel"],
+               not_vel_indeces=c["not_vel"], dtype=DT, device=dev(), init_dict_list=[rbf] * 2)
+    pi = sy.cartpole_policy_init(B=c["B"], seed=1)
+    ppar = dict(state_dim=4, input_dim=1, num_basis=c["B"], angle_indices=np.array([2]), non_angle_indices=np.array([0, 1, 3]),
+                lengthscales_init=pi["lengthscales"], centers_init=pi["centers"], weight_init=pi["weight"], flg_squash=True, u_max=c["u_max"],
+                flg_drop=True, dtype=DT, device=dev())
+    with contextlib.redirect_stdout(io.StringIO()):
+        obj = MC_PILCO.MC_PILCO(T_sampling=c["Ts"], state_dim=4, input_dim=1, f_sim=lambda y, t, u: None,
+                                f_model_learning=ML.Speed_Model_learning_RBF_angle_state, model_learning_par=mlp,
+                                f_rand_exploration_policy=Policy.Random_exploration,
+                                rand_exploration_policy_par=dict(state_dim=4, input_dim=1, u_max=10.0, dtype=DT),
+                                f_control_policy=Policy.Sum_of_gaussians_with_angles, control_policy_par=ppar,
+                                f_cost_function=Cost_function.Expected_saturated_distance,
+                                cost_function_par=dict(target_state=G([[np.pi, 0.0]]), lengthscales=G([3.0, 1.0]), active_dims=[2, 0]),
+                                log_path=None, dtype=DT, device=dev())
+        xs, us = sy.cartpole_rollouts(n_roll=1, seed=1)[0]
+        obj.model_learning.add_data(np.asarray(xs)[:49], np.asarray(us)[:49])
+        with torch.no_grad():
+            for g in range(2):
+                obj.model_learning.pretrain_gp(g)
+        obj.model_learning.set_eval_mode()
+    assert int(obj.model_learning.gp_inputs.shape[0]) == 48
+    return obj
+
+
+def test_loop_with_a_target_cost_replays_graphs_and_takes_the_eager_steps():
+    """4 steps of reinforce_policy (N = 48, M = 16, T = 6), attempts replayed from HIP graphs against eager launches: the same cost list and
+    policy parameters, bit for bit, and the recording run did replay (the first two attempts of a run are eager by design)."""
+    c = sy.CARTPOLE
+    out = []
+    for capture in (True, False):
+        obj = tiny_mcpilco()
+        obj.noise_mode = "philox"
+        obj.capture_attempts = capture
+        torch.manual_seed(1234)
+        buf = io.StringIO()
+        with contextlib.redirect_stdout(buf):
+            # (T_control 0.31 s: int(0.31 / 0.05) = 6 steps -- 0.3 / 0.05 rounds below 6)
+            res = obj.reinforce_policy(T_control=0.31, num_particles=16, trial_index=0, particles_initial_state_mean=G(c["x0_mean"]),
+                                       particles_initial_state_var=G(c["x0_var"]), flg_particles_init_uniform=False, particles_init_up_bound=None,
+                                       particles_init_low_bound=None, flg_particles_init_multi_gauss=False,
+                                       f_optimizer="lambda p, lr : torch.optim.Adam(p, lr)", opt_steps_list=[4], lr_list=[0.01],
+                                       p_dropout_list=[0.25], num_step_print=100)
+        cf = obj.cost_function
+        assert cf._packed is not None and cf._packed.kind == "target", "the loop's cost did not run on the kernels"
+        if capture:
+            assert "recording an attempt into a graph failed" not in buf.getvalue(), buf.getvalue()[-2000:]
+            assert obj.attempts_replayed > 0, buf.getvalue()[-2000:]
+        else:
+            assert obj.attempts_replayed == 0
+        pol = obj.control_policy
+        out.append((np.asarray(res[0]), [q.detach().cpu().numpy().copy() for q in (pol.log_lengthscales, pol.centers, pol.f_linear.weight)]))
+    (c1, p1), (c0, p0) = out
+    assert c0.shape == (4,) and np.isfinite(c0).all()
+    assert np.array_equal(c1, c0)
+    for a, b in zip(p1, p0):
+        assert np.array_equal(a, b)
+
+
+# ---- 6: the summable form of a sharded step, in one process ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("with_shift", [False, True])
+def test_sharded_sums_pool_to_the_whole_swarm(with_shift):
+    """M = 24 as shards of 16 and 8: local_moments into two sums buffers, added, then from_sums, against forward on the whole swarm.  The pooled
+    forms are compared at the bounds tests/test_gpu_sharding.py holds them to (cost 1e-13 relative, :95; std 1e-10 relative, :96 -- the sums
+    form takes the variance as a difference of sums); the shards' gradients are rows of the whole swarm's, bit for bit (each row is computed on
+    its own with the same 1 / m_total)."""
+    from mc_pilco_amd.policy_learning import Cost_function as CF
+
+    T, M, S, used = 6, 24, 4, [2, 0]
+    x, tg, ls = draw(T, M, S, used, seed=11)
+    for cls in (CF.Expected_saturated_distance, CF.Expected_distance):
+        cf = cls(target_state=G(tg.reshape(1, -1)), lengthscales=G(ls), active_dims=used)
+        whole = G(x).requires_grad_(True)
+        c, s = cf(whole, None, 0)
+        c.backward()
+        shift = torch.full((T,), float(c) / T, dtype=DT, device=dev()) if with_shift else None
+        sums, grads = [], []
+        for a, b in ((0, 16), (16, 24)):
+            part = G(x[:, a:b]).requires_grad_(True)
+            buf = torch.zeros(2 * T, dtype=DT, device=dev())
+            share, sm = cf.local_moments(part, None, 0, M, shift, sums_out=buf)
+            assert sm.data_ptr() == buf.data_ptr()
+            share.backward()
+            sums.append(sm)
+            grads.append(part.grad)
+        cp, sp = cf.from_sums(sums[0] + sums[1], M, shift)
+        ec, es = abs(float(cp) - float(c)) / abs(float(c)), abs(float(sp) - float(s)) / abs(float(s))
+        print("%s shift=%s: pooled cost %.2e std %.2e" % (cls.__name__, with_shift, ec, es))
+        assert cf._packed is not None
+        assert ec < 1e-13 and es < 1e-10
+        assert torch.equal(torch.cat(grads, 1), whole.grad)
