@@ -292,6 +292,23 @@ int mcp_rollout_fwd(const mcp_model* model, const mcp_policy* policy, const mcp_
  * every step (what get_next_state returns; rows beyond a length are not written).  status: MCP_STATUS_NAN | MCP_STATUS_NONPOS_VAR. */
 int mcp_rollout_open(const mcp_model* model, const mcp_noise* noise, int M, int T, int particle_pred, const double* x0, const double* u,
                      int Mu, const int32_t* lengths, double* states, double* mu, double* var, uint32_t* status, void* stream);
+/* The RECORDING form of mcp_rollout_open, for gradients through the open-loop rollout: the same arguments plus jac [T-1][M][G][D] =
+ * d delta_g / d z with the sampling folded in (layout and meaning of mcp_rollout_fwd's record), which mcp_rollout_open_bwd consumes.
+ * The states (and mu / var) carry the bits of mcp_rollout_open with the same arguments; jac is bitwise reproducible and independent of
+ * the launch's other trajectories and of particle_offset sharding in the same way.  Rows of jac from len - 1 on are never written and
+ * never read.  A sampled step whose variance is not positive raises MCP_STATUS_NONPOS_VAR and leaves inf / NaN in that trajectory's
+ * rows, as mcp_rollout_fwd does.  Stands in for what autograd records through the step loop of MC_PILCO.rollout
+ * (policy_learning/MC_PILCO.py:347-373) over Model_learning.get_next_state (model_learning/Model_learning.py:210-229, 471-494, 685-718). */
+int mcp_rollout_open_rec(const mcp_model* model, const mcp_noise* noise, int M, int T, int particle_pred, const double* x0, const double* u,
+                         int Mu, const int32_t* lengths, double* states, double* mu, double* var, double* jac, uint32_t* status, void* stream);
+/* Reverse-time sweep of the open-loop rollout: g_states [T][M][S] = dJ/dstates (required; rows beyond a trajectory's row len - 1 are
+ * ignored) -> g_x0 [M][S] = dJ/dx0 and g_u [T-1][M][U] = dJ/du per trajectory (each may be NULL; rows of g_u from len - 1 on are zeros;
+ * a shared input sequence's gradient is the caller's sum over M).  states, lengths, jac: what mcp_rollout_open_rec wrote / was given.
+ * Only the model's index maps and Ts are read (no GP array).  No atomics: bitwise reproducible, a trajectory's results do not depend
+ * on the others.  Replaces autograd's backward through the step loop of MC_PILCO.rollout (policy_learning/MC_PILCO.py:347-373) over
+ * get_next_state and the integrators (model_learning/Model_learning.py:210-229, 471-494, 685-718). */
+int mcp_rollout_open_bwd(const mcp_model* model, int M, int T, const double* states, const int32_t* lengths, const double* jac,
+                         const double* g_states, double* g_x0, double* g_u, void* stream);
 /* Reverse-time adjoint of the rollout: given dJ/dstates, dJ/dinputs (either may be NULL) returns
  * dJ/d{log_lengthscales [P], centers [B][P], f_linear.weight [U][B]} (overwritten, this rank's
  * particles only; with policy->bias also dJ/dbias into policy->g_bias) and optionally dJ/dx0 [M][S].  Replaces autograd's backward through

@@ -21,6 +21,20 @@
 // workgroup barriers per step.  With variances a workgroup owns a tile of 16 trajectories so that Kinv is streamed once per step for
 // all of them; the k panel ([Npad][16] doubles) must fit the LDS, so beyond ~1000 training points the tile shrinks to 4 (fits up to
 // MCP_MAX_TRAIN).  Phase K walks X^T once per group of 4 trajectories of the tile (register budget of the polynomial terms).
+//
+// The RECORDING form (template NEEDJAC, mcp_rollout_open_rec) also writes jac [T-1][M][G][D] = d delta_g / dz with the sampling folded
+// in -- layout and meaning of the closed-loop kernels' record (mcp_rollout_fwd) -- for the reverse-time sweep at the end of this file
+// (rollout_open_bwd_kernel, mcp_rollout_open_bwd).  Phases K, V and F are the same instructions in both forms (the library is built
+// without floating-point contraction), so the states carry the same bits; the recording form adds
+//   V'  v = Kinv k is KEPT: a second [Npad][pitch] panel next to k (where the two do not fit, the tile shrinks 16 -> 4 -> 1)
+//   J   R_c = [X^T; 1] W_c  on v_mfma_f64_16x16x4_f64, one column per trajectory of the tile:
+//         d delta/dz = sum_j beta_j dk_j/dz + w dk(z,z)/dz,   beta_j = alpha_j - 2 w v_j,   w = var_scale eps / (2 sigma)  (0: mean)
+//         W_0 = beta kse | W_1 = beta (degree >= 1) | W_2 = beta pb, W_3 = beta pa (degree 2);  lane (kk, n) recomputes kse / pa / pb of
+//         training row j0 + kk for trajectory n (phase K's arithmetic: a twentieth of phase V at the cart-pole size) instead of keeping
+//         three more panels; the 8 waves take interleaved 4-row steps, their partial R meet in LDS (over the k panel, dead after V)
+//   J'  thread (trajectory, d): adds the waves' parts in wave order, applies the kernel's factors, writes jac
+// A variance that is not positive follows the closed-loop phase F: w = eps / (2 sqrt(var)) is formed as it comes (inf / NaN rows of
+// jac for that trajectory alone) and MCP_STATUS_NONPOS_VAR is raised.  Rows of jac from len - 1 on are NEVER WRITTEN and never read.
 #include "rollout_fwd_shared.h"
 
 using namespace mcp;
@@ -33,6 +47,8 @@ struct OpenArgs {
   mcp_model model;
   mcp_noise nz;
   int M, T, sample, Mu, NpadMax;
+  int na;       // recording form: weight columns of phase J per trajectory (1 / 2 / 4 by the model's highest polynomial degree)
+  double* jac;  // recording form: [T-1][M][G][D]
   const double* x0;
   const double* u;
   const int32_t* lengths;
@@ -44,12 +60,13 @@ struct OpenArgs {
 
 struct OpenLayout {
   int xs, z, red, gpl, kpar, panel, xt, al, total;  // offsets in doubles
+  int vpan, redj, wj, redj_gp;                      // recording form: v panel | partial sums of phase J (stride per GP) | w per trajectory
   int xl;                                           // X^T and alpha of every GP staged in LDS (row pitch NpadMax)
 };
 
 #define RO_KR(PT) ((PT) == 16 ? 18 : (PT))  // row pitch of the k panel (16 particles: + 2 pad, bank spread of the phase-K stores)
 
-__host__ __device__ inline OpenLayout open_layout(int PT, bool needvar, int S, int D, int G, int NpadMax) {
+__host__ __device__ inline OpenLayout open_layout(int PT, bool needvar, int S, int D, int G, int NpadMax, bool needjac = false, int na = 0) {
   OpenLayout L;
   int o = 0;
   auto take = [&](int n) {
@@ -62,7 +79,14 @@ __host__ __device__ inline OpenLayout open_layout(int PT, bool needvar, int S, i
   L.red = take(2 * G * RF_NW * PT);  // per-wave partial sums: alpha^T k | k^T Kinv k
   L.gpl = take(G * GPL_DOUBLES);
   L.kpar = take(G * KP_STRIDE(D));
-  L.panel = needvar ? take(NpadMax * RO_KR(PT)) : 0;
+  // phase J's partial sums [wave][column][D + 1][PT]: with variances one GP at a time, over the k panel (dead once phase V is through);
+  // the mean chain runs J beside K for every GP before its one barrier, so each GP has its own
+  const int rj = needjac ? RF_NW * na * (D + 1) * PT : 0;
+  L.panel = needvar ? take(imax(NpadMax * RO_KR(PT), rj)) : 0;
+  L.vpan = (needvar && needjac) ? take(NpadMax * RO_KR(PT)) : 0;
+  L.wj = (needvar && needjac) ? take(PT) : 0;
+  L.redj_gp = needvar ? 0 : rj;
+  L.redj = needvar ? L.panel : (needjac ? take(G * rj) : 0);
   const int xneed = G * (D + 1) * NpadMax + 4;
   L.xl = (!needvar && o + xneed <= MCP_LDS_LIMIT / 8) ? 1 : 0;
   L.xt = L.xl ? take(G * D * NpadMax) : 0;
@@ -94,8 +118,8 @@ __device__ __forceinline__ void open_v_mfma(const v2d (&A)[RO_VU], const double 
     acc_o = __builtin_amdgcn_mfma_f64_16x16x4f64(A[u].y, B[u], acc_o, 0, 0, 0);
   }
 }
-template <int PT>
-__device__ __forceinline__ double open_v_block(const double* Kinv, int Npad, int I0, const double* panel, int lane) {
+template <int PT, bool STOREV>
+__device__ __forceinline__ double open_v_block(const double* Kinv, int Npad, int I0, const double* panel, double* vpan, int lane) {
   constexpr int KR = RO_KR(PT);
   const int m = lane & 15, kk = lane >> 4;
   const int nn = m < PT ? m : 0;
@@ -125,6 +149,10 @@ __device__ __forceinline__ double open_v_block(const double* Kinv, int Npad, int
     if (row < Npad) {  // (Npad is even: row + 1 is inside too)
       q = fma(acc_e[r], panel[row * KR + nn], q);
       q = fma(acc_o[r], panel[(row + 1) * KR + nn], q);
+      if (STOREV && m < PT) {  // recording form: every (row, trajectory) of v comes out of exactly one lane of one wave
+        vpan[row * KR + m] = acc_e[r];
+        vpan[(row + 1) * KR + m] = acc_o[r];
+      }
     }
   }
   return q;
@@ -195,20 +223,173 @@ __device__ __forceinline__ void open_phase_k(const GpL& gp, const double* kp, in
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// recording form.  w = var_scale eps / (2 sigma) of trajectory p of the tile at GP g (0 without sampling): the variance from the
+// same sums as phase F
+// ---------------------------------------------------------------------------------------
+template <int PT, int MAXDEG>
+__device__ __forceinline__ double open_wjs(const OpenArgs& a, const mcp_noise& nzl, const GpL& gp, const double* kp, int D, int G, int g, int t,
+                                           int om, const double* zp, const double* red, int p) {
+  if (!a.sample) return 0.0;
+  double ktv = 0.0;
+#pragma unroll
+  for (int w = 0; w < RF_NW; ++w) ktv += red[(G + g) * RF_NW * PT + w * PT + p];
+  double kzz = gp.lambda;
+  if (MAXDEG >= 1 && gp.deg >= 1) {
+    double p1 = kp[KP_W1(D) + D];
+    for (int d = 0; d < D; ++d) p1 = fma(kp[KP_W1(D) + d] * zp[d], zp[d], p1);
+    kzz += p1;
+    if (MAXDEG >= 2 && gp.deg >= 2) {
+      double Sa = 0.0, Sb = 0.0;
+      for (int d = 0; d < D; ++d) {
+        const double zz = zp[d] * zp[d];
+        Sa = fma(kp[KP_W20(D) + d], zz, Sa);
+        Sb = fma(kp[KP_W21(D) + d], zz, Sb);
+      }
+      kzz = fma(Sa, Sb, kzz);
+    }
+  }
+  const double var = (kzz - ktv) * gp.var_scale;
+  const double e = nzl.eps ? nzl.eps[((size_t)t * a.M + om) * G + g] : philox_normal(nzl, om, t, g);
+  return e / (2.0 * sqrt(var)) * gp.var_scale;
+}
+
+// phase J for one GP:  R_c[r][n] = sum_j [X^T; 1][r][j] W_c[j][n]  over this wave's 4-row steps of the training index
+//   A operand  lane (m = l&15, kk = l>>4) : [X^T; 1][16 db + m][j0 + kk]
+//   B operand  lane (kk = l>>4, n = l&15) : W_c[j0 + kk][n], formed in the lane
+//   acc[db][c][r] : R_c[16 db + (l>>4) + 4r][n = l&15]
+// Padding rows of the training index carry alpha = v = 0.  Lanes of trajectories the tile does not have repeat column 0, unused.
 template <int PT, int MAXDEG, bool NEEDVAR>
+__device__ __forceinline__ void open_phase_j(const GpL& gp, const double* kp, int D, const double* z, const double* vpan, double wjs, double* redj,
+                                             int na, int wv, int lane, const double* Xt, const double* al, int pitch) {
+  constexpr int KR = RO_KR(PT);
+  constexpr int NAX = MAXDEG == 0 ? 1 : 4;
+  const int m = lane & 15, kk = lane >> 4;
+  const int nn = m < PT ? m : 0;
+  const int Npad = gp.Npad, rows = D + 1, ndb = (rows + 15) >> 4;
+  const int deg = MAXDEG == 0 ? 0 : gp.deg;
+  const double lam = gp.lambda;
+  const double* zp = z + nn * D;
+  v4d acc[3][NAX];
+#pragma unroll
+  for (int db = 0; db < 3; ++db)
+#pragma unroll
+    for (int c = 0; c < NAX; ++c) acc[db][c] = (v4d){0.0, 0.0, 0.0, 0.0};
+  for (int j0 = 4 * wv; j0 < Npad; j0 += 4 * RF_NW) {
+    const int j = j0 + kk;
+    double se = 0.0, szz = 0.0, sxx = 0.0, pa = 0.0, pb = 0.0;
+    for (int d = 0; d < D; ++d) {
+      const double x = Xt[(size_t)d * pitch + j];
+      const double il = kp[KP_INVLS(D) + d];
+      const double zz = zp[d];
+      const double tx = il * x;
+      sxx = fma(tx, tx, sxx);
+      const double il2z = il * il * zz;
+      se = fma(-2.0 * il2z, x, se);
+      szz = fma(il2z, zz, szz);
+      if (MAXDEG >= 2) {
+        const double ab = zz * x;
+        pa = fma(kp[KP_W20(D) + d], ab, pa);
+        pb = fma(kp[KP_W21(D) + d], ab, pb);
+      }
+    }
+    const double kse = lam * exp(-((szz + sxx) + se));
+    double beta = al[j];
+    if (NEEDVAR) beta = fma(-2.0 * wjs, vpan[j * KR + nn], beta);
+    double B[NAX];
+    B[0] = beta * kse;
+    if (MAXDEG >= 1) {
+      B[1] = beta;
+      B[2] = beta * pb;
+      B[3] = beta * pa;
+    }
+#pragma unroll
+    for (int db = 0; db < 3; ++db) {
+      if (db < ndb) {
+        const int r = 16 * db + m;
+        const double A = r < D ? Xt[(size_t)r * pitch + j] : (r == D ? 1.0 : 0.0);
+#pragma unroll
+        for (int c = 0; c < NAX; ++c)
+          if (c == 0 || (c == 1 && deg >= 1) || (c >= 2 && deg >= 2)) acc[db][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(A, B[c], acc[db][c], 0, 0, 0);
+      }
+    }
+  }
+  if (m < PT) {
+#pragma unroll
+    for (int db = 0; db < 3; ++db)
+#pragma unroll
+      for (int c = 0; c < NAX; ++c)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = 16 * db + kk + 4 * r;
+          if (db < ndb && row < rows && c < na) redj[((wv * na + c) * rows + row) * PT + m] = acc[db][c][r];
+        }
+  }
+}
+
+// phase J': thread (trajectory p, feature d) of one GP: the waves' parts in wave order, the kernel's factors, the store
+//   d delta/dz_d = -2/l_d^2 (z_d R_0[D] - R_0[d]) + w1_d R_1[d] + w20_d R_2[d] + w21_d R_3[d] + w d k(z,z)/dz_d
+template <int PT, int MAXDEG, bool NEEDVAR>
+__device__ __forceinline__ void open_jac_store(const OpenArgs& a, const GpL& gp, const double* kp, int g, int t, int m0, const double* z,
+                                               const double* wjl, const double* redj, int na, int tid) {
+  const int D = a.model.D, G = a.model.G, rows = D + 1;
+  const int deg = MAXDEG == 0 ? 0 : gp.deg;
+  for (int it = tid; it < PT * D; it += RF_NT) {
+    const int p = it / D, d = it - p * D;
+    const int mm = m0 + p;
+    if (mm >= a.M) continue;
+    const int len = a.lengths ? imin(imax(a.lengths[mm], 1), a.T) : a.T;
+    if (t + 1 >= len) continue;
+    double R[4] = {0.0, 0.0, 0.0, 0.0}, R0D = 0.0;
+    for (int w = 0; w < RF_NW; ++w) {
+      R0D += redj[((w * na + 0) * rows + D) * PT + p];
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (c < na && (c == 0 || (c == 1 && deg >= 1) || (c >= 2 && deg >= 2))) R[c] += redj[((w * na + c) * rows + d) * PT + p];
+    }
+    const double* zp = z + p * D;
+    const double il = kp[KP_INVLS(D) + d];
+    const double wjs = NEEDVAR ? wjl[p] : 0.0;
+    double J = -2.0 * (il * il) * (zp[d] * R0D - R[0]);
+    if (MAXDEG >= 1 && deg >= 1) {
+      const double w1 = kp[KP_W1(D) + d];
+      J += w1 * R[1];
+      if (NEEDVAR) J += wjs * (2.0 * w1 * zp[d]);
+      if (MAXDEG >= 2 && deg >= 2) {
+        const double wa = kp[KP_W20(D) + d], wb = kp[KP_W21(D) + d];
+        J += wa * R[2] + wb * R[3];
+        if (NEEDVAR) {
+          double Sa = 0.0, Sb = 0.0;
+          for (int e = 0; e < D; ++e) {
+            const double zz = zp[e] * zp[e];
+            Sa = fma(kp[KP_W20(D) + e], zz, Sa);
+            Sb = fma(kp[KP_W21(D) + e], zz, Sb);
+          }
+          J += wjs * (2.0 * zp[d] * (wa * Sb + wb * Sa));
+        }
+      }
+    }
+    a.jac[(((size_t)t * a.M + mm) * G + g) * D + d] = J;
+  }
+}
+
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC>
 __global__ __launch_bounds__(RF_NT) void rollout_open_kernel(OpenArgs a) {
   extern __shared__ double smem[];
   const mcp_model& md = a.model;
   const int S = md.S, U = md.U, G = md.G, D = md.D, M = a.M, T = a.T;
   const int nna = md.n_not_angle, na = md.n_angle;
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const OpenLayout L = open_layout(PT, NEEDVAR, S, D, G, a.NpadMax);
+  const OpenLayout L = open_layout(PT, NEEDVAR, S, D, G, a.NpadMax, NEEDJAC, a.na);
   double* xs = smem + L.xs;
   double* z = smem + L.z;
   double* red = smem + L.red;  // [2][G][RF_NW][PT]
   GpL* gpl = reinterpret_cast<GpL*>(smem + L.gpl);
   double* kpar = smem + L.kpar;
   double* panel = smem + L.panel;
+  double* vpan = smem + L.vpan;  // (recording form)
+  double* wjl = smem + L.wj;
+  double* redj = smem + L.redj;
   const mcp_noise nzl = noise_of_launch(a.nz);
   const int m0 = blockIdx.x * PT;
 
@@ -292,17 +473,31 @@ __global__ __launch_bounds__(RF_NT) void rollout_open_kernel(OpenArgs a) {
       const double* al = L.xl ? smem + L.al + g * a.NpadMax : gp.alpha;
       open_phase_k<PT, MAXDEG, NEEDVAR>(gp, kpar + g * KP_STRIDE(D), D, z, panel, red + g * RF_NW * PT, tid, wv, lane, Xt, al,
                                         L.xl ? a.NpadMax : gp.Npad);
+      if (NEEDJAC && !NEEDVAR)  // the mean chain: beta = alpha, nothing of phase K is needed -- no barrier in between
+        open_phase_j<PT, MAXDEG, false>(gp, kpar + g * KP_STRIDE(D), D, z, nullptr, 0.0, redj + g * L.redj_gp, a.na, wv, lane, Xt, al,
+                                        L.xl ? a.NpadMax : gp.Npad);
       if (NEEDVAR) {
         lds_barrier();
         const int Npad = __builtin_amdgcn_readfirstlane(gp.Npad);
         double q = 0.0;
-        for (int I0 = 32 * wv; I0 < Npad; I0 += 32 * RF_NW) q += open_v_block<PT>(gp.Kinv, Npad, I0, panel, lane);
+        for (int I0 = 32 * wv; I0 < Npad; I0 += 32 * RF_NW) q += open_v_block<PT, NEEDJAC>(gp.Kinv, Npad, I0, panel, vpan, lane);
         q = fold_kk(q);
         if (lane < PT) red[(G + g) * RF_NW * PT + wv * PT + lane] = q;
-        lds_barrier();  // the panel is rewritten by the next GP
+        lds_barrier();  // the panel is rewritten by the next GP (recording form: by phase J's partial sums)
+        if (NEEDJAC) {
+          const int nn = (lane & 15) < PT ? (lane & 15) : 0;
+          const double wjs = open_wjs<PT, MAXDEG>(a, nzl, gp, kpar + g * KP_STRIDE(D), D, G, g, t, imin(m0 + nn, M - 1), z + nn * D, red, nn);
+          if (wv == 0 && lane < PT) wjl[lane] = wjs;
+          open_phase_j<PT, MAXDEG, true>(gp, kpar + g * KP_STRIDE(D), D, z, vpan, wjs, redj, a.na, wv, lane, Xt, al, gp.Npad);
+          lds_barrier();
+          open_jac_store<PT, MAXDEG, true>(a, gp, kpar + g * KP_STRIDE(D), g, t, m0, z, wjl, redj, a.na, tid);
+          lds_barrier();  // the next GP's phase K writes the panel again
+        }
       }
     }
     if (!NEEDVAR) lds_barrier();
+    if (NEEDJAC && !NEEDVAR)
+      for (int g = 0; g < G; ++g) open_jac_store<PT, MAXDEG, false>(a, gpl[g], kpar + g * KP_STRIDE(D), g, t, m0, z, nullptr, redj + g * L.redj_gp, a.na, tid);
     // ---- phase F: moments, sample, integrate   v' = v + delta ;  q' = q + Ts v + Ts/2 delta   (Model_learning.py:711-716) ----
     if (own) {
       const double* xc = xs + cur * PT * S + op * S;
@@ -351,29 +546,30 @@ __global__ __launch_bounds__(RF_NT) void rollout_open_kernel(OpenArgs a) {
       }
       xn = nx;
     }
-    if (NEEDVAR && MAXDEG >= 1) lds_barrier();  // k(z, z) above read z, which the next step's phase S rewrites
+    if ((NEEDVAR && MAXDEG >= 1) || NEEDJAC) lds_barrier();  // k(z, z) above (and phase J') read z, which the next step's phase S rewrites
     cur ^= 1;
   }
   if (bad) atomicOr(a.status, bad);
 }
 
-template <int PT, int MAXDEG, bool NEEDVAR>
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC>
 static int launch_open(const OpenArgs& a, hipStream_t st) {
-  const OpenLayout L = open_layout(PT, NEEDVAR, a.model.S, a.model.D, a.model.G, a.NpadMax);
+  const OpenLayout L = open_layout(PT, NEEDVAR, a.model.S, a.model.D, a.model.G, a.NpadMax, NEEDJAC, a.na);
   const size_t lds = (size_t)L.total * sizeof(double);
   if (lds > MCP_LDS_LIMIT) return MCP_ERR_LIMIT;
-  MCP_ENSURE_MAX_LDS(rollout_open_kernel<PT, MAXDEG, NEEDVAR>);
-  hipLaunchKernelGGL((rollout_open_kernel<PT, MAXDEG, NEEDVAR>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
+  MCP_ENSURE_MAX_LDS(rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC>);
+  hipLaunchKernelGGL((rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
 }
-template <int PT, bool NEEDVAR>
+template <int PT, bool NEEDVAR, bool NEEDJAC>
 static int launch_open_deg(const OpenArgs& a, int maxdeg, hipStream_t st) {
-  return maxdeg == 0 ? launch_open<PT, 0, NEEDVAR>(a, st) : launch_open<PT, 2, NEEDVAR>(a, st);
+  return maxdeg == 0 ? launch_open<PT, 0, NEEDVAR, NEEDJAC>(a, st) : launch_open<PT, 2, NEEDVAR, NEEDJAC>(a, st);
 }
 
-extern "C" int mcp_rollout_open(const mcp_model* model, const mcp_noise* noise, int M, int T, int particle_pred, const double* x0, const double* u,
-                                int Mu, const int32_t* lengths, double* states, double* mu, double* var, uint32_t* status, void* stream) {
+// what mcp_rollout_open and mcp_rollout_open_rec share: the checks, the arguments, the choice of the tile (jac: the recording form)
+static int open_dispatch(const mcp_model* model, const mcp_noise* noise, int M, int T, int particle_pred, const double* x0, const double* u, int Mu,
+                         const int32_t* lengths, double* states, double* mu, double* var, double* jac, uint32_t* status, void* stream) {
   if (!model || !noise || !x0 || !u || !states || !status) return MCP_ERR_ARG;
   if (M <= 0 || T < 2 || (Mu != 1 && Mu != M)) return MCP_ERR_ARG;
   if (model->S > MCP_MAX_STATE || model->U > MCP_MAX_INPUT || model->G > MCP_MAX_GP || model->D > MCP_MAX_GPDIM) return MCP_ERR_LIMIT;
@@ -393,6 +589,8 @@ extern "C" int mcp_rollout_open(const mcp_model* model, const mcp_noise* noise, 
     a.NpadMax = imax(a.NpadMax, model->gp[g].Npad);
     maxdeg = imax(maxdeg, model->gp[g].kern.poly_deg);
   }
+  a.na = jac ? (maxdeg == 0 ? 1 : maxdeg == 1 ? 2 : 4) : 0;
+  a.jac = jac;
   a.x0 = x0;
   a.u = u;
   a.lengths = lengths;
@@ -401,10 +599,261 @@ extern "C" int mcp_rollout_open(const mcp_model* model, const mcp_noise* noise, 
   a.var = var;
   a.status = status;
   hipStream_t st = (hipStream_t)stream;
-  if (!a.sample && !var) return launch_open_deg<1, false>(a, maxdeg, st);  // the mean chain: no Kinv
-  int rc = launch_open_deg<16, true>(a, maxdeg, st);
-  // the k panel of 16 trajectories does not fit the LDS: 4 per workgroup (at every compiled limit at once -- S = 16, D = 32, G = 8, Npad = 4096 --
-  // that layout takes 148 KB of the 160, so nothing within MCP_MAX_* is refused)
-  if (rc == MCP_ERR_LIMIT) rc = launch_open_deg<4, true>(a, maxdeg, st);
+  if (!jac) {
+    if (!a.sample && !var) return launch_open_deg<1, false, false>(a, maxdeg, st);  // the mean chain: no Kinv
+    int rc = launch_open_deg<16, true, false>(a, maxdeg, st);
+    // the k panel of 16 trajectories does not fit the LDS: 4 per workgroup (at every compiled limit at once -- S = 16, D = 32, G = 8, Npad = 4096 --
+    // that layout takes 148 KB of the 160, so nothing within MCP_MAX_* is refused)
+    if (rc == MCP_ERR_LIMIT) rc = launch_open_deg<4, true, false>(a, maxdeg, st);
+    return rc;
+  }
+  if (!a.sample && !var) return launch_open_deg<1, false, true>(a, maxdeg, st);  // (at every limit at once: 85 KB, X^T then stays in global memory)
+  // two panels: 16 trajectories up to Npad ~ 500, 4 up to ~ 2000, beyond that one (at every compiled limit at once: 2 x 32 KB of panels, 85 KB in all)
+  int rc = launch_open_deg<16, true, true>(a, maxdeg, st);
+  if (rc == MCP_ERR_LIMIT) rc = launch_open_deg<4, true, true>(a, maxdeg, st);
+  if (rc == MCP_ERR_LIMIT) rc = launch_open_deg<1, true, true>(a, maxdeg, st);
   return rc;
+}
+
+extern "C" int mcp_rollout_open(const mcp_model* model, const mcp_noise* noise, int M, int T, int particle_pred, const double* x0, const double* u,
+                                int Mu, const int32_t* lengths, double* states, double* mu, double* var, uint32_t* status, void* stream) {
+  return open_dispatch(model, noise, M, T, particle_pred, x0, u, Mu, lengths, states, mu, var, nullptr, status, stream);
+}
+
+// the recording form (same reference lines as mcp_rollout_open; the record is what autograd would keep of MC_PILCO.py:347-373)
+extern "C" int mcp_rollout_open_rec(const mcp_model* model, const mcp_noise* noise, int M, int T, int particle_pred, const double* x0, const double* u,
+                                    int Mu, const int32_t* lengths, double* states, double* mu, double* var, double* jac, uint32_t* status,
+                                    void* stream) {
+  if (!jac) return MCP_ERR_ARG;
+  return open_dispatch(model, noise, M, T, particle_pred, x0, u, Mu, lengths, states, mu, var, jac, status, stream);
+}
+
+// ---------------------------------------------------------------------------------------
+// Reverse-time sweep of the open-loop rollout: what autograd's backward does through the step loop of MC_PILCO.rollout
+// (MC_PILCO.py:347-373) over get_next_state (Model_learning.py:210-229, 471-494, 685-718), from the record alone.
+//   lambda_{len-1} = g_states[len-1];   g_u[t] = (dx_{t+1}/du_t)^T lambda_{t+1};   lambda_t = g_states[t] + (dx_{t+1}/dx_t)^T lambda_{t+1}
+// One step backwards, with gd_g the adjoint of GP g's increment and gz = sum_g gd_g jac[t][m][g][:] that of its input z:
+//   gd_g  = sum over the components s that integrate GP g of  lambda'[s]  (a velocity, or a delta-state component: not_vel == -1)
+//                                                          or  Ts/2 lambda'[s]  (the position not_vel[g])
+//   lambda[s] = g_states[t][s] + lambda'[s] (s is integrated at all) + Ts lambda'[not_vel[g]] (s = vel[g] of a position) + gz through
+//               z = [x_not_angle, sin, cos, u]: gz[i] | gz[sin_i] cos x - gz[cos_i] sin x;     g_u[t][k] = gz[nna + 2 na + k]
+// The same uniform test as rollout_bwd.hip separates the model families: not_vel[g] < 0 has no Ts term.
+// Trajectories are independent: a workgroup of two waves owns OB_PT of them, no atomics, no sums across trajectories.  Wave 1 is the
+// LOADER: while wave 0 runs the chain of row r it brings row r - 1 of the record (jac, the states for the angles, g_states) into the
+// other half of a double buffer, coalesced -- jac[t][m0 .. m0 + OB_PT) is one contiguous block.  Wave 0, lane (p = l & 15, q = l >> 4):
+// trajectory p, every fourth g / d / s; its three stages meet in LDS, ordered within the wave (no workgroup barrier on the chain).
+// Ragged lengths: row len - 1 starts the sweep, later rows of g_states are never read, g_u rows from len - 1 on are zeros.
+// ---------------------------------------------------------------------------------------
+#define OB_PT 16
+#define OB_NT 128
+
+struct OpenBwdArgs {
+  int S, U, G, D, nna, na, M, T;
+  int angle[MCP_MAX_STATE], not_angle[MCP_MAX_STATE], vel[MCP_MAX_GP], not_vel[MCP_MAX_GP];
+  double Ts;
+  const double* states;
+  const double* jac;
+  const double* g_states;
+  const int32_t* lengths;
+  double* g_x0;
+  double* g_u;
+};
+
+struct OpenBwdLayout {
+  int rec, xs, gs, lam, gd, gz, tab, total;  // offsets in doubles
+  int rp;                                    // pitch of a trajectory's record row (odd: bank spread)
+};
+__host__ __device__ inline OpenBwdLayout open_bwd_layout(int S, int G, int D) {
+  OpenBwdLayout L;
+  int o = 0;
+  auto take = [&](int n) {
+    int r = o;
+    o += (n + 1) & ~1;
+    return r;
+  };
+  L.rp = (G * D) | 1;
+  L.rec = take(2 * OB_PT * L.rp);
+  L.xs = take(2 * OB_PT * S);
+  L.gs = take(2 * OB_PT * S);
+  L.lam = take(2 * OB_PT * S);
+  L.gd = take(OB_PT * G);
+  L.gz = take(OB_PT * D);
+  L.tab = take((5 * MCP_MAX_STATE + OB_PT) / 2 + 2);  // ints: og | ispos | velof | zplain | zang (per state component), len (per trajectory)
+  L.total = o;
+  return L;
+}
+
+// orders this wave's LDS stores before its later LDS loads (the DS queue of a wave is in order; this drains it and stops the compiler)
+__device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+
+__global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(OpenBwdArgs a) {
+  extern __shared__ double smem[];
+  const int S = a.S, U = a.U, G = a.G, D = a.D, M = a.M, T = a.T, nna = a.nna, na = a.na;
+  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const OpenBwdLayout L = open_bwd_layout(S, G, D);
+  const int GD = G * D, RP = L.rp;
+  double* rec = smem + L.rec;
+  double* xsl = smem + L.xs;
+  double* gsl = smem + L.gs;
+  double* lam = smem + L.lam;
+  double* gdl = smem + L.gd;
+  double* gzl = smem + L.gz;
+  int* ogt = reinterpret_cast<int*>(smem + L.tab);
+  int* post = ogt + MCP_MAX_STATE;
+  int* velof = post + MCP_MAX_STATE;
+  int* zplain = velof + MCP_MAX_STATE;
+  int* zang = zplain + MCP_MAX_STATE;
+  int* lenl = zang + MCP_MAX_STATE;
+  const int m0 = blockIdx.x * OB_PT;
+
+  if (tid < S) {  // which GP a component integrates, as the forward kernel decides it
+    const int s = tid;
+    int g_vel = -1, g_pos = -1, zp = -1, za = -1;
+    for (int g = 0; g < G; ++g) {
+      if (a.vel[g] == s) g_vel = g;
+      if (a.not_vel[g] == s) g_pos = g;
+    }
+    for (int i = 0; i < nna; ++i)
+      if (a.not_angle[i] == s) zp = i;
+    for (int i = 0; i < na; ++i)
+      if (a.angle[i] == s) za = i;
+    ogt[s] = g_pos >= 0 ? g_pos : g_vel;
+    post[s] = g_pos >= 0 ? 1 : 0;
+    velof[s] = g_pos >= 0 ? a.vel[g_pos] : -1;
+    zplain[s] = zp;
+    zang[s] = za;
+  }
+  if (tid >= 64 && tid < 64 + OB_PT) {
+    const int p = tid - 64;
+    lenl[p] = m0 + p < M ? (a.lengths ? imin(imax(a.lengths[m0 + p], 1), T) : T) : 0;
+  }
+  for (int it = tid; it < 2 * OB_PT * S; it += OB_NT) lam[it] = 0.0;
+  __syncthreads();
+  int tl = 1;
+  for (int p = 0; p < OB_PT; ++p) tl = imax(tl, lenl[p]);
+  if (a.g_u) {  // rows from len - 1 on: zeros
+    for (int p = 0; p < OB_PT; ++p) {
+      const int len = lenl[p];
+      if (len == 0) continue;
+      for (int it = (len - 1) * U + tid; it < (T - 1) * U; it += OB_NT) {
+        const int t = it / U, k = it - t * U;
+        a.g_u[((size_t)t * M + m0 + p) * U + k] = 0.0;
+      }
+    }
+  }
+
+  // the loader's work for one row (64 lanes): g_states[r] where r <= len - 1; states[r] and jac[r] where r < len - 1
+  auto load_row = [&](int r, int b, int l) {
+    for (int it = l; it < OB_PT * S; it += 64) {
+      const int p = it / S, s = it - p * S;
+      const int len = lenl[p];
+      if (r <= len - 1) gsl[(b * OB_PT + p) * S + s] = a.g_states[((size_t)r * M + m0 + p) * S + s];
+      if (r < len - 1) xsl[(b * OB_PT + p) * S + s] = a.states[((size_t)r * M + m0 + p) * S + s];
+    }
+    for (int it = l; it < OB_PT * GD; it += 64) {
+      const int p = it / GD, e = it - p * GD;
+      if (r < lenl[p] - 1) rec[(b * OB_PT + p) * RP + e] = a.jac[((size_t)r * M + m0 + p) * GD + e];
+    }
+  };
+
+  int b = 0, lc = 0;
+  if (wv == 1) load_row(tl - 1, 0, lane);
+  __syncthreads();
+  for (int r = tl - 1; r >= 0; --r) {
+    if (wv == 1) {
+      if (r > 0) load_row(r - 1, b ^ 1, lane);
+    } else {
+      const int p = lane & 15, q = lane >> 4;
+      const int len = lenl[p];
+      const double* lamc = lam + (lc * OB_PT + p) * S;
+      double* lamn = lam + ((lc ^ 1) * OB_PT + p) * S;
+      const double* rc = rec + (b * OB_PT + p) * RP;
+      const double* xc = xsl + (b * OB_PT + p) * S;
+      const double* gc = gsl + (b * OB_PT + p) * S;
+      const bool active = r < len - 1;
+      // stage A: the adjoints of the increments
+      for (int g = q; g < G; g += 4) {
+        double acc = 0.0;
+        for (int s = 0; s < S; ++s)
+          if (ogt[s] == g) acc += post[s] ? 0.5 * a.Ts * lamc[s] : lamc[s];
+        gdl[p * G + g] = acc;
+      }
+      wave_lds_sync();
+      // stage B: through the record to the GP input
+      if (active) {
+        for (int d = q; d < D; d += 4) {
+          double acc = 0.0;
+          for (int g = 0; g < G; ++g) acc = fma(gdl[p * G + g], rc[g * D + d], acc);
+          gzl[p * D + d] = acc;
+        }
+      }
+      wave_lds_sync();
+      // stage C: the integrator and the feature map
+      for (int s = q; s < S; s += 4) {
+        double v = 0.0;
+        if (r == len - 1) {
+          v = gc[s];
+        } else if (active) {
+          v = gc[s];
+          if (ogt[s] >= 0) v += lamc[s];
+          for (int s2 = 0; s2 < S; ++s2)
+            if (velof[s2] == s) v = fma(a.Ts, lamc[s2], v);
+          if (zplain[s] >= 0) v += gzl[p * D + zplain[s]];
+          if (zang[s] >= 0) {
+            double sn, cs;
+            sincos_fast(xc[s], &sn, &cs);
+            v += gzl[p * D + nna + zang[s]] * cs - gzl[p * D + nna + na + zang[s]] * sn;
+          }
+        }
+        lamn[s] = v;
+      }
+      if (active && a.g_u)
+        for (int k = q; k < U; k += 4) a.g_u[((size_t)r * M + m0 + p) * U + k] = gzl[p * D + nna + 2 * na + k];
+      wave_lds_sync();
+      lc ^= 1;
+    }
+    __syncthreads();
+    b ^= 1;
+  }
+  if (wv == 0 && a.g_x0) {
+    const int p = lane & 15, q = lane >> 4;
+    if (lenl[p] > 0)
+      for (int s = q; s < S; s += 4) a.g_x0[(size_t)(m0 + p) * S + s] = lam[(lc * OB_PT + p) * S + s];
+  }
+}
+
+extern "C" int mcp_rollout_open_bwd(const mcp_model* model, int M, int T, const double* states, const int32_t* lengths, const double* jac,
+                                    const double* g_states, double* g_x0, double* g_u, void* stream) {
+  if (!model || !states || !jac || !g_states) return MCP_ERR_ARG;
+  if (M <= 0 || T < 2) return MCP_ERR_ARG;
+  if (model->S > MCP_MAX_STATE || model->U > MCP_MAX_INPUT || model->G > MCP_MAX_GP || model->D > MCP_MAX_GPDIM) return MCP_ERR_LIMIT;
+  if (model->S <= 0 || model->U <= 0 || model->G <= 0 || model->D <= 0 || model->n_angle < 0 || model->n_not_angle < 0 ||
+      model->n_not_angle + 2 * model->n_angle + model->U != model->D)
+    return MCP_ERR_ARG;
+  for (int i = 0; i < model->n_angle; ++i)
+    if (model->angle[i] < 0 || model->angle[i] >= model->S) return MCP_ERR_ARG;
+  for (int i = 0; i < model->n_not_angle; ++i)
+    if (model->not_angle[i] < 0 || model->not_angle[i] >= model->S) return MCP_ERR_ARG;
+  for (int g = 0; g < model->G; ++g)
+    if (model->vel[g] < 0 || model->vel[g] >= model->S || model->not_vel[g] < -1 || model->not_vel[g] >= model->S) return MCP_ERR_ARG;
+  if (!g_x0 && !g_u) return MCP_OK;  // nothing asked for
+  OpenBwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.S = model->S, a.U = model->U, a.G = model->G, a.D = model->D, a.nna = model->n_not_angle, a.na = model->n_angle, a.M = M, a.T = T;
+  for (int i = 0; i < MCP_MAX_STATE; ++i) a.angle[i] = model->angle[i], a.not_angle[i] = model->not_angle[i];
+  for (int g = 0; g < MCP_MAX_GP; ++g) a.vel[g] = model->vel[g], a.not_vel[g] = model->not_vel[g];
+  a.Ts = model->Ts;
+  a.states = states;
+  a.jac = jac;
+  a.g_states = g_states;
+  a.lengths = lengths;
+  a.g_x0 = g_x0;
+  a.g_u = g_u;
+  const OpenBwdLayout L = open_bwd_layout(a.S, a.G, a.D);  // (at every compiled limit at once: 72 KB)
+  const size_t lds = (size_t)L.total * sizeof(double);
+  if (lds > MCP_LDS_LIMIT) return MCP_ERR_LIMIT;
+  MCP_ENSURE_MAX_LDS(rollout_open_bwd_kernel);
+  hipLaunchKernelGGL(rollout_open_bwd_kernel, dim3((M + OB_PT - 1) / OB_PT), dim3(OB_NT), lds, (hipStream_t)stream, a);
+  MCP_LAUNCH_CHECK();
+  return MCP_OK;
 }

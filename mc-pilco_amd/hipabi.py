@@ -116,6 +116,9 @@ _SIGS = {
                                   dptr, dptr, dptr, C.c_size_t, dptr]),
     "mcp_rollout_open": (C.c_int, [C.POINTER(Model), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr, C.c_int, dptr, dptr, dptr, dptr,
                                    dptr, dptr]),
+    "mcp_rollout_open_rec": (C.c_int, [C.POINTER(Model), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr, C.c_int, dptr, dptr, dptr, dptr,
+                                       dptr, dptr, dptr]),
+    "mcp_rollout_open_bwd": (C.c_int, [C.POINTER(Model), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
     "mcp_rollout_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(Policy), C.POINTER(Noise), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr,
                                   dptr, dptr, dptr, dptr, dptr, C.c_size_t, dptr]),
     "mcp_rollout_fwd_ex": (C.c_int, [C.POINTER(Model), C.POINTER(Policy), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr, dptr,

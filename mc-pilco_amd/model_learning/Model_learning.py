@@ -261,14 +261,23 @@ class Model_learning(torch.nn.Module):
         return (all(getattr(cls, n) is getattr(own, n) for n in ("get_next_state", "get_next_state_from_gp_output", "get_one_step_gp_out"))
                 and cls.data_to_gp_input in known_inputs)
 
-    def open_loop_rollout(self, initial_states, inputs, particle_pred=False, lengths=None, noise=None, moments=False):
+    def open_loop_rollout(self, initial_states, inputs, particle_pred=False, lengths=None, noise=None, moments=False, differentiable=False):
         """Drives the model open loop by given inputs in ONE fused launch (ops.rollout_open): initial_states [M,S], inputs [T-1,M,U] or
         [T-1,U] (shared by all trajectories) -> states [T,M,S] (+ GP means and variances [T-1,M,G] with ``moments``) and the status word.
         Mean prediction unless ``particle_pred``; ``noise``: ops.NoiseSpec (eps buffer, or Philox seed / call).  The T-loop over
-        get_next_state of MC_PILCO.rollout (reference policy_learning/MC_PILCO.py:347-373) without its per-step launches."""
+        get_next_state of MC_PILCO.rollout (reference policy_learning/MC_PILCO.py:347-373) without its per-step launches.
+        ``differentiable``: the same states with gradients to ``initial_states`` and ``inputs`` (ops.rollout_open_diff: the recording
+        launch and, in backward, the reverse-time sweep); the model is frozen; only for models whose step is the packed one."""
         if not self.has_fused_layout():
             raise NotImplementedError("no fused-rollout layout for this model: roll it out step by step on get_next_state")
         t = lambda a: a if isinstance(a, torch.Tensor) else torch.as_tensor(a, dtype=self.dtype)
+        if differentiable:
+            if not self.steps_like_the_packed_model():
+                raise NotImplementedError("this model overrides the step the fused rollout implements: differentiate its own step loop on get_next_state")
+            if moments:
+                raise NotImplementedError("the differentiable open-loop rollout returns no moments")
+            return ops.rollout_open_diff(self.packed(), t(initial_states).to(self.device), t(inputs).to(self.device), lengths=lengths, noise=noise,
+                                         particle_pred=particle_pred)
         with torch.no_grad():
             return ops.rollout_open(self.packed(), t(initial_states).to(self.device), t(inputs).to(self.device), lengths=lengths, noise=noise,
                                     particle_pred=particle_pred, moments=moments)

@@ -516,6 +516,76 @@ def rollout_open(model: PackedModel, x0, u, *, lengths=None, noise: Optional[Noi
     return states, status
 
 
+class RolloutOpenFunction(torch.autograd.Function):
+    """(x0 [M,S], u [T-1,Mu,U]) -> states [T,M,S] through the recording form of the fused open-loop rollout (mcp_rollout_open_rec); backward is
+    the reverse-time sweep mcp_rollout_open_bwd over the record.  Gradients flow to x0 and u; the GP model is frozen.  In sampled mode the
+    draws are those of the NoiseSpec, and the backward differentiates the reparameterised sample."""
+
+    @staticmethod
+    def forward(ctx, x0, u, model, lengths, noise, particle_pred, status):
+        T, Mu, M = int(u.shape[0]) + 1, int(u.shape[1]), int(x0.shape[0])
+        dev = model.device
+        states = torch.empty(T, M, model.S, dtype=DT, device=dev)
+        jac = torch.empty(T - 1, M, model.G, model.D, dtype=DT, device=dev)  # (rows from len - 1 on: never written, never read)
+        nz = noise.to_c()
+        abi.check(abi.lib().mcp_rollout_open_rec(_mc(model), C.byref(nz), M, T, int(bool(particle_pred)), abi.ptr(x0), abi.ptr(u), Mu,
+                                                 abi.ptr(lengths), abi.ptr(states), None, None, abi.ptr(jac), abi.ptr(status), abi.stream()),
+                  "mcp_rollout_open_rec")
+        ctx.model, ctx.lengths, ctx.Mu = model, lengths, Mu
+        ctx.save_for_backward(states, jac)  # (saved tensors: autograd refuses a backward after an in-place change of either)
+        return states
+
+    @staticmethod
+    def backward(ctx, g_states):
+        states, jac = ctx.saved_tensors
+        model = ctx.model
+        T, M = int(states.shape[0]), int(states.shape[1])
+        want_x0, want_u = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gs = g_states.to(dtype=DT).contiguous()
+        g_x0 = torch.empty(M, model.S, dtype=DT, device=states.device) if want_x0 else None
+        g_u = torch.empty(T - 1, M, model.U, dtype=DT, device=states.device) if want_u else None
+        abi.check(abi.lib().mcp_rollout_open_bwd(_mc(model), M, T, abi.ptr(states), abi.ptr(ctx.lengths), abi.ptr(jac), abi.ptr(gs), abi.ptr(g_x0),
+                                                 abi.ptr(g_u), abi.stream()), "mcp_rollout_open_bwd")
+        if want_u and ctx.Mu == 1 and M > 1:
+            g_u = g_u.sum(dim=1, keepdim=True)  # a shared input sequence: the trajectories' gradients added in torch's fixed order
+        return g_x0, g_u, None, None, None, None, None
+
+
+def rollout_open_diff(model: PackedModel, x0, u, *, lengths=None, noise: Optional[NoiseSpec] = None, particle_pred=False, status=None):
+    """The differentiable open-loop rollout: arguments and states of ``rollout_open`` (bit for bit), with gradients to ``x0`` [M,S] and ``u``
+    ([T-1,M,U], or one shared sequence [T-1,U] / [T-1,1,U]: its gradient has u's own shape, the sum over the trajectories).  The model is
+    frozen.  When neither input requires grad nothing is recorded and the call IS ``rollout_open``.  Returns (states, status)."""
+    for name, t in (("x0", x0), ("u", u)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError("rollout_open_diff operates on GPU memory only (%s is not a GPU tensor); there is no CPU path" % name)
+    if not (torch.is_grad_enabled() and (x0.requires_grad or u.requires_grad)):
+        return rollout_open(model, x0.detach(), u.detach(), lengths=lengths, noise=noise, particle_pred=particle_pred, status=status)
+    dev = model.device
+    x0c = x0.to(device=dev, dtype=DT).contiguous()
+    if x0c.dim() != 2 or x0c.shape[1] != model.S:
+        raise RuntimeError("x0 must be [M,%d]" % model.S)
+    M = int(x0c.shape[0])
+    uc = u.to(device=dev, dtype=DT)
+    if uc.dim() == 2:
+        uc = uc.reshape(uc.shape[0], 1, uc.shape[1])  # (autograd hands the gradient back in u's own shape)
+    if uc.dim() != 3 or uc.shape[2] != model.U or uc.shape[1] not in (1, M) or uc.shape[0] < 1:
+        raise RuntimeError("u must be [T-1,M,%d] or [T-1,%d]" % (model.U, model.U))
+    uc = uc.contiguous()
+    T = int(uc.shape[0]) + 1
+    noise = NoiseSpec() if noise is None else noise
+    if particle_pred:
+        _check_noise(noise, T, M, model.G, 0, 0.0, True)
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths, dtype=torch.int32).to(dev).contiguous()
+        if tuple(lengths.shape) != (M,):
+            raise RuntimeError("lengths must have one entry per trajectory")
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    elif status.dtype != torch.int32 or status.numel() != 1 or status.device != x0c.device or not status.is_contiguous():
+        raise RuntimeError("status must be a one-element int32 tensor on the rollout's device")
+    return RolloutOpenFunction.apply(x0c, uc, model, lengths, noise, bool(particle_pred), status), status
+
+
 # measurement hook (bench.py): a pair of torch.cuda.Event recorded on the launch stream right around mcp_rollout_bwd -- the adjoint sweep
 # runs inside autograd's backward, where the caller cannot bracket it.  None (the default) = nothing is recorded.  ``fwd_events``: the same
 # around mcp_rollout_fwd (operand packing + hand-off buffer reset + the rollout kernel, without the host's tensor allocations).
