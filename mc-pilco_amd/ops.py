@@ -865,7 +865,7 @@ class PosteriorFunction(torch.autograd.Function):
     """Z [M,D] -> (mu [M,1], var [M]) = GP_prior.get_estimate_from_alpha on the packed GP."""
 
     @staticmethod
-    def forward(ctx, Z, gp: PackedGP):
+    def forward(ctx, Z, gp: PackedGP, status=None):
         Zc = Z.detach().to(dtype=DT).contiguous()
         M, D = Zc.shape
         need = ctx.needs_input_grad[0]
@@ -873,7 +873,10 @@ class PosteriorFunction(torch.autograd.Function):
         var = torch.empty(M, dtype=DT, device=Zc.device)
         Jm = torch.empty(M, D, dtype=DT, device=Zc.device) if need else None
         Jv = torch.empty(M, D, dtype=DT, device=Zc.device) if need else None
-        status = torch.zeros(1, dtype=torch.int32, device=Zc.device)
+        if status is None:  # (nobody asked: the flags go to a scratch word)
+            status = torch.zeros(1, dtype=torch.int32, device=Zc.device)
+        elif status.dtype != torch.int32 or status.numel() != 1 or status.device != Zc.device or not status.is_contiguous():
+            raise RuntimeError("status must be a one-element int32 tensor on the test points' device")
         g = gp.to_c()
         abi.check(abi.lib().mcp_posterior_fwd_ex(C.byref(g), M, abi.ptr(Zc), abi.ptr(mu), abi.ptr(var), abi.ptr(Jm), abi.ptr(Jv), abi.ptr(status),
                                                  abi.stream(), C.byref(abi.DISPATCH)), "mcp_posterior_fwd")
@@ -890,11 +893,13 @@ class PosteriorFunction(torch.autograd.Function):
         gv = (torch.zeros(M, dtype=DT, device=Jm.device) if g_var is None else g_var.reshape(-1)).contiguous()
         abi.check(abi.lib().mcp_posterior_bwd(M, D, abi.ptr(gm), abi.ptr(gv), abi.ptr(Jm), abi.ptr(Jv), abi.ptr(gz), abi.stream()),
                   "mcp_posterior_bwd")
-        return gz, None
+        return gz, None, None
 
 
-def posterior(gp: PackedGP, Z):
-    return PosteriorFunction.apply(Z, gp)
+def posterior(gp: PackedGP, Z, status=None):
+    """(mu [M,1], var [M]) at the test points Z [M,D], differentiable w.r.t. Z.  ``status``: an int32[1] on the device that the kernel ORs its
+    flags INTO (MCP_STATUS_NAN, MCP_STATUS_NONPOS_VAR; decode with ``status_flags``), as ``rollout_open`` takes it; None: the flags are dropped."""
+    return PosteriorFunction.apply(Z, gp, status)
 
 
 def status_flags(status):
