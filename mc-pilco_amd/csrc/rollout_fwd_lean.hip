@@ -30,8 +30,8 @@ using namespace mcp;
 //     row tiles, so v is complete inside a wave: no cross-wave partial sums, no phase "vsum", and the wave goes straight on to its
 //     share of phase J (4x4x4 MFMA as well, the rows it has just produced) without a workgroup barrier in between.
 //   * phase F, the hand-off, the integrator and the next step's phase S run back to back in wave 0 (wave-level ordering only; delta
-//     and its granules before the Jacobian columns; no trajectory store: the last wave writes states, Jacobians and inputs to global
-//     memory behind the next barrier); the other waves meanwhile draw the next step's dropout decisions and process noise (never
+//     and its granules before the Jacobian columns; no trajectory store there: wave 0 writes states, Jacobians and inputs to global
+//     memory behind its own phase J, where it waits for the slower waves anyway); the other waves meanwhile draw the next step's dropout decisions and process noise (never
 //     wave 4, which shares wave 0's SIMD).
 // Results do not depend on P (1, 2, 4): equal shards reproduce each other bit for bit, as before.  Covers SE-only models with
 // D <= 8 (<= 6 state-derived + <= 2 inputs), <= 6 policy features, 32 <= Npad <= 384; everything else runs the general kernel
@@ -55,7 +55,6 @@ using namespace mcp;
 #define RL_ZD (RL_DSM + RL_UM)
 #define RL_PFM 6  // policy features, zero padded
 #define RL_NSTAMP 64  // slots of the stamp buffer (tools/phase_stamps.py names them)
-#define RL_STORE_WAVE (RF_NW - 1)  // the wave that writes the trajectory to global memory
 #define RL_NRES 2  // register buffers kept resident: RL_NRES or RL_NRES + 1, whichever leaves an even number to stream
 
 // LDS plan: the regions whose size is bounded by compile-time limits come first, at compile-time offsets (no scalar register per
@@ -85,7 +84,7 @@ struct LatFixed {
 static_assert(LatFixed::pc % 2 == 0 && LatFixed::fz % 2 == 0 && LatFixed::gpl % 2 == 0, "16-byte alignment");
 static_assert(LatFixed::red % 2 == 0 && LatFixed::rt % 2 == 0 && LatFixed::zs % 2 == 0 && LatFixed::role % 2 == 0 && LatFixed::sro % 2 == 0 && LatFixed::end % 2 == 0, "16-byte alignment of the v2d regions");
 struct LatLayout {
-  int gs, kb, vb, xq, al, cen, wgt, mk, total;  // offsets in doubles
+  int gs, kb, vb, xq, al, cen, wgt, mk, ho, total;  // offsets in doubles
 };
 __host__ __device__ inline int lat_ng(int B) { return (B + 15) >> 4; }                 // groups of 16 basis functions
 __host__ __device__ inline int lat_ngp(int B) { return ((lat_ng(B) + 7) >> 3) << 3; }  // padded to whole chunks of 8 (zeros)
@@ -110,6 +109,9 @@ __host__ __device__ inline LatLayout lat_layout(int P, int B, int Npad, int maxd
   L.cen = take(RL_PFM * Bp);
   L.wgt = take(RL_UM * Bp);
   L.mk = take((P * ((B + 3) / 4) + 1) / 2);
+  // [2][64] what wave 0 parks for its own trajectory stores: Jacobian column of thread (p, c) | measurement of thread (p, s) (PMS).  The SE
+  // kernels never touch the `rt` region (its 192 doubles hold both); the polynomial kernels sum their tiles there and get words of their own
+  L.ho = maxdeg > 0 ? take(2 * 64) : LatFixed::rt;
   L.total = o;
   return L;
 }
@@ -509,10 +511,10 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
   double* epsb = smem + LatFixed::eps;
   double* red = smem + LatFixed::red;
   double* rtot = smem + LatFixed::rt;
-  // hand-over of wave 0's outputs to the storing wave, in tiles of `red` that are free from phase F of a step (wave 0 has read them) to
-  // phase J of the next: the Jacobian column of thread (p, c); the measurement of thread (p, s) (PMS)
-  double* jl = red;
-  double* xml = red + 64;
+  // what wave 0 parks for its own trajectory stores behind the next phase J (`red` is rewritten by that phase J, `rtot` by the polynomial
+  // kernels' phase F: lat_layout): the Jacobian column of thread (p, c); the measurement of thread (p, s) (PMS)
+  double* jl = smem + L.ho;
+  double* xml = jl + 64;
   double* pc = smem + LatFixed::pc;    // polynomial constants (MAXDEG > 0)
   double* fz = smem + LatFixed::fz;    // z-only polynomial terms of the step (MAXDEG > 0)
   double* pnz = smem + LatFixed::pn;   // position measurement noise (PMS)
@@ -792,6 +794,33 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
       if (r == NRES && nresb) kt_load(vres[r], vpb, 0);
     }
   }
+  // ---- the trajectory stores of step t, by wave 0 behind its own phase J.  From 16 row tiles on (Npad >= 256: all eight waves own rows)
+  // wave 0 owns the fewest rows of Kinv and reaches the barrier about 3 k cycles before the slowest wave: the stores have drained long
+  // before the hand-off poll, which waits for every store the wave has outstanding -- one counter for loads and stores on this target --
+  // and they sit in no barrier interval another wave bounds.  Below that the rows go to fewer waves (at Npad = 32 to wave 0 alone), the
+  // stores then stand directly in front of phase F and the poll waits for them: correct, and no slower than storing from the chain itself.
+  // Stored: x_t and its measurement, the inputs u_t (published in z by the u phase of this step), the Jacobian columns phase F of step
+  // t - 1 parked.  In the last step (no phase V) the same behind the u phase, without the inputs: the threads that form u_{T-1} store it
+  // themselves.  A step that ends in a hand-off abort (MCP_STATUS_SYNC) stores nothing more: the status word voids the whole rollout.
+  auto store_step = [&](int t, int lane, double xt, bool last) {
+    const int* ro = role + lane * 16;
+    const int2 r0 = *reinterpret_cast<const int2*>(ro), r3 = *reinterpret_cast<const int2*>(ro + 12);
+    if (writer && lane < P * S) {
+      const int op = r0.x, os = r0.y;
+      if (m0 + op < Mend) {
+        a.states[((size_t)t * M + m0 + op) * S + os] = xt;
+        if (PMS) pl.meas.meas[((size_t)t * M + m0 + op) * S + os] = xml[lane];
+      }
+    }
+    if (t > 0 && lane < P * (D + 1)) {
+      const int p = r3.x, c = r3.y;
+      if (c < D && a.jac && m0 + p < Mend) a.jac[(((size_t)(t - 1) * M + m0 + p) * G + myg) * D + c] = jl[lane];
+    }
+    if (!last && writer && lane < P * U) {  // U <= 2
+      const int ip = U == 1 ? lane : lane >> 1, ik = U == 1 ? 0 : lane & 1;
+      if (m0 + ip < Mend) a.inputs[((size_t)t * M + m0 + ip) * U + ik] = z[ip * D + DS + ik];
+    }
+  };
   unsigned long long last_stamp = STAMPS ? clock64() : 0, sub_stamp = last_stamp;
   double pm_prev_np = 0.0, pm_prev_nv = 0.0, pm_prev_mv = 0.0;  // PMS: previous noisy position / noisy velocity / filtered velocity of this lane's pair
 
@@ -841,7 +870,7 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
         const v2d sc0 = *reinterpret_cast<const v2d*>(srow + 4), sc1 = *reinterpret_cast<const v2d*>(srow + 6);
         double* xc = xs + cur * P * S;
         xc[op * S + os] = xn;
-        if (PMS) xml[lane] = xm;  // (for the wave that stores the trajectory)
+        if (PMS) xml[lane] = xm;  // (for the trajectory stores behind phase J)
         if (ovalid && (is_bad(xn) || (PMS && is_bad(xm)))) bad |= MCP_STATUS_NAN;
         double sn = 0.0, cs = 0.0;
         if (zi_ang >= 0 || pi_ang >= 0) sincos_fast(xn, &sn, &cs);
@@ -860,30 +889,6 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
     }
     if (wv == 0) RL_SUB(15);
     lds_barrier();  // B0
-    // ---- the trajectory stores of wave 0's serial section, by another wave: x_t (phase S above), and what phase F and the policy of step
-    // t - 1 left in LDS -- the Jacobian columns and the inputs.  Wave 0 issues no global store but its granules: its hand-off poll waits for
-    // every store it has outstanding (one counter for loads and stores on this target).  The last wave has the fewest phase-K items.
-    if (wv == RL_STORE_WAVE) {
-      const int* ro = role + lane * 16;
-      const int2 r0 = *reinterpret_cast<const int2*>(ro), r3 = *reinterpret_cast<const int2*>(ro + 12);
-      if (writer && lane < P * S) {
-        const int op = r0.x, os = r0.y;
-        if (m0 + op < Mend) {
-          a.states[((size_t)t * M + m0 + op) * S + os] = xs[cur * P * S + op * S + os];
-          if (PMS) pl.meas.meas[((size_t)t * M + m0 + op) * S + os] = xml[lane];
-        }
-      }
-      if (t > 0) {
-        if (lane < P * (D + 1)) {
-          const int p = r3.x, c = r3.y;
-          if (c < D && a.jac && m0 + p < Mend) a.jac[(((size_t)(t - 1) * M + m0 + p) * G + myg) * D + c] = jl[lane];
-        }
-        if (writer && lane < P * U) {  // U <= 2
-          const int ip = U == 1 ? lane : lane >> 1, ik = U == 1 ? 0 : lane & 1;
-          if (m0 + ip < Mend) a.inputs[((size_t)(t - 1) * M + m0 + ip) * U + ik] = z[ip * D + DS + ik];
-        }
-      }
-    }
     if (*abortw) {  // uniform: a partner never arrived (set by wave 0 in the previous step's hand-off)
       bad |= MCP_STATUS_SYNC;
       break;
@@ -1039,7 +1044,10 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
         }
       }
     }
-    if (t == T - 1) break;
+    if (t == T - 1) {
+      if (wv == 0) store_step(t, lane, xn, true);  // (x_{T-1}, and step T - 2's Jacobian columns)
+      break;
+    }
     RL_WSUB(40);
     v2d bufA[KT_NL], bufB[KT_NL];  // (phase V's stream buffers)
     // ---- phase K, second half: the input dimensions and the exp ----
@@ -1143,6 +1151,7 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
 #pragma unroll
       for (int g = 0; g < NCG; ++g) red[(wv * NCG + g) * 64 + lane] = 0.0;  // (a wave without rows)
     }
+    if (wv == 0) store_step(t, lane, xn, false);
     lds_barrier();  // B4
     RL_STAMP(6);
     if (wv == 0) {
@@ -1252,7 +1261,7 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
               Jvar += 2.0 * zc * (a_ * fz[p * 4 + 3] + b_ * fz[p * 4 + 2]) - 2.0 * lc * (a_ * Rp(crow, 2) + b_ * Rp(crow, 3));
             }
           }
-          jl[lane] = a.particle_pred ? fma(wj, Jvar * vscale, Jmu) : Jmu;  // (to global memory by the storing wave, behind B0)
+          jl[lane] = a.particle_pred ? fma(wj, Jvar * vscale, Jmu) : Jmu;  // (to global memory behind the next phase J)
         }
       }
       RL_SUB(13);
