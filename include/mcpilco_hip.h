@@ -168,6 +168,22 @@ typedef struct mcp_noise {
                                in the recorded kernel arguments (round 6: MC_PILCO.reinforce_policy replays its attempts) */
 } mcp_noise;
 
+/* PD law in closed loop -- Policy.PD_controller (policy_learning/Policy.py:406-449) with flg_trainable, evaluated inside the fused
+ * rollout:  e = target_traj[t] - x_t;  a_k = sqrt_kp[k]^2 e[pos[k]] + sqrt_kd[k]^2 e[vel[k]];  u_t[k] = u_max[k] tanh(a_k / u_max[k])
+ * (squash) or a_k.  The reference's layout is pos = 0..U-1, vel = S/2..S/2+U-1.  The entries of pos are distinct state components, and
+ * so are those of vel.  The gains and the target are DEVICE pointers: an optimizer updates the gains in place. */
+typedef struct mcp_pd_policy {
+  int32_t U;                    /* inputs, == model->U                                        */
+  int32_t squash;               /* flg_squash                                                 */
+  int32_t pos[MCP_MAX_INPUT];   /* state component whose error sqrt_kp[k]^2 multiplies        */
+  int32_t vel[MCP_MAX_INPUT];   /* state component whose error sqrt_kd[k]^2 multiplies        */
+  double u_max[MCP_MAX_INPUT];  /* > 0 with squash                                            */
+  const double* sqrt_kp;        /* [U]  sqrt_Kp_gains                                         */
+  const double* sqrt_kd;        /* [U]  sqrt_Kd_gains                                         */
+  const double* target_traj;    /* [target_rows][S]                                           */
+  int32_t target_rows;          /* >= T                                                       */
+} mcp_pd_policy;
+
 /* ---- library ------------------------------------------------------------------------ */
 int mcp_abi_version(void);
 const char* mcp_build_info(void);
@@ -309,6 +325,25 @@ int mcp_rollout_open_rec(const mcp_model* model, const mcp_noise* noise, int M, 
  * get_next_state and the integrators (model_learning/Model_learning.py:210-229, 471-494, 685-718). */
 int mcp_rollout_open_bwd(const mcp_model* model, int M, int T, const double* states, const int32_t* lengths, const double* jac,
                          const double* g_states, double* g_x0, double* g_u, void* stream);
+/* Closed-loop rollout under the PD law, ONE launch: mcp_rollout_open's step with the input of step t computed from x_t inside the
+ * kernel (mcp_pd_policy) instead of read from a buffer -- same phases, same noise addressing (eps [T-1][M][G] or Philox by seed, call,
+ * m + particle_offset), same status flags; a NaN input raises MCP_STATUS_NAN.  states [T][M][S]; inputs [T][M][U], row T - 1 included
+ * (no transition reads it; the reference stores it too and a cost may read it).  No ragged lengths.  jac NULL: nothing is recorded;
+ * else jac [T-1][M][G][D] as mcp_rollout_open_rec writes it, input columns included, for mcp_rollout_pd_bwd; states and inputs carry the
+ * same bits either way.  mu / var (optional, [T-1][M][G]) as in mcp_rollout_open.  T == 1 evaluates the policy only.
+ * MCP_ERR_ARG: an index out of range or repeated, pd->U != model->U, target_rows < T, T < 1, a u_max <= 0 with squash; MCP_ERR_LIMIT
+ * beyond MCP_MAX_*.  Replaces the loop of MC_PILCO.apply_policy (policy_learning/MC_PILCO.py:615-674) with PD_controller.forward
+ * (policy_learning/Policy.py:437-449) over Model_learning.get_next_state (model_learning/Model_learning.py:210-229, 471-494, 685-718). */
+int mcp_rollout_pd(const mcp_model* model, const mcp_pd_policy* pd, const mcp_noise* noise, int M, int T, int particle_pred, const double* x0,
+                   double* states, double* inputs, double* jac /* NULL: no record */, double* mu, double* var, uint32_t* status, void* stream);
+/* Reverse-time sweep of mcp_rollout_pd: g_states [T][M][S] (required) and g_inputs [T][M][U] (optional) -> g_gains [M][2][U] =
+ * dJ/d(sqrt_kp, sqrt_kd) PER TRAJECTORY (the sum over M is the caller's, in an order of its choosing) and g_x0 [M][S]; each may be
+ * NULL.  states, inputs, jac: what mcp_rollout_pd wrote (jac may be NULL when T == 1).  Row T - 1 contributes through g_inputs alone.
+ * No atomics: bitwise reproducible, a trajectory's results do not depend on the others.  Replaces autograd's backward (MC_PILCO.py:522)
+ * through MC_PILCO.apply_policy's loop (policy_learning/MC_PILCO.py:615-674), PD_controller.forward (policy_learning/Policy.py:437-449)
+ * and the integrators (model_learning/Model_learning.py:210-229, 471-494, 685-718). */
+int mcp_rollout_pd_bwd(const mcp_model* model, const mcp_pd_policy* pd, int M, int T, const double* states, const double* inputs,
+                       const double* jac, const double* g_states, const double* g_inputs, double* g_gains, double* g_x0, void* stream);
 /* Reverse-time adjoint of the rollout: given dJ/dstates, dJ/dinputs (either may be NULL) returns
  * dJ/d{log_lengthscales [P], centers [B][P], f_linear.weight [U][B]} (overwritten, this rank's
  * particles only; with policy->bias also dJ/dbias into policy->g_bias) and optionally dJ/dx0 [M][S].  Replaces autograd's backward through

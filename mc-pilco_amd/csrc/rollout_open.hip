@@ -58,6 +58,25 @@ struct OpenArgs {
   uint32_t* status;
 };
 
+// FEEDBACK form (template FB, mcp_rollout_pd): the input of step t is not read from a buffer, it is the PD law on the state the step
+// starts from (Policy.PD_controller.forward, policy_learning/Policy.py:437-449, inside MC_PILCO.apply_policy's loop, MC_PILCO.py:615-674):
+//   e = target_traj[t] - x_t;   a_k = sqrt_kp[k]^2 e[pos[k]] + sqrt_kd[k]^2 e[vel[k]];   u_t[k] = u_max[k] tanh(a_k / u_max[k])  (or a_k)
+// The threads that fetch the inputs in the open-loop form compute them from the xs row the state threads have just published -- one more
+// LDS barrier per step, in this form only -- and store them to inputs [T][M][U]; row T - 1 is computed and stored although no transition
+// reads it.  Everything after that (phases K, V, J, F, the noise addressing) is the open-loop step on the same operands.
+struct OpenArgsPd : OpenArgs {
+  mcp_pd_policy pd;
+  double* inputs;  // [T][M][U]
+};
+template <bool FB>
+struct OpenArgsOf {
+  typedef OpenArgs type;
+};
+template <>
+struct OpenArgsOf<true> {
+  typedef OpenArgsPd type;
+};
+
 struct OpenLayout {
   int xs, z, red, gpl, kpar, panel, xt, al, total;  // offsets in doubles
   int vpan, redj, wj, redj_gp;                      // recording form: v panel | partial sums of phase J (stride per GP) | w per trajectory
@@ -373,8 +392,8 @@ __device__ __forceinline__ void open_jac_store(const OpenArgs& a, const GpL& gp,
   }
 }
 
-template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC>
-__global__ __launch_bounds__(RF_NT) void rollout_open_kernel(OpenArgs a) {
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool FB = false>
+__global__ __launch_bounds__(RF_NT) void rollout_open_kernel(typename OpenArgsOf<FB>::type a) {
   extern __shared__ double smem[];
   const mcp_model& md = a.model;
   const int S = md.S, U = md.U, G = md.G, D = md.D, M = a.M, T = a.T;
@@ -437,6 +456,19 @@ __global__ __launch_bounds__(RF_NT) void rollout_open_kernel(OpenArgs a) {
   const double Ts = md.Ts;
   unsigned bad = 0;
   int cur = 0;
+  // feedback form: the gains (squared once, as the reference squares them in every evaluation), bound and state components of input uk
+  double kp2 = 0.0, kd2 = 0.0, umax = 1.0;
+  int ipos = 0, ivel = 0;
+  if constexpr (FB) {
+    if (isu) {
+      const double kp = a.pd.sqrt_kp[uk], kd = a.pd.sqrt_kd[uk];
+      kp2 = kp * kp;
+      kd2 = kd * kd;
+      umax = a.pd.u_max[uk];
+      ipos = a.pd.pos[uk];
+      ivel = a.pd.vel[uk];
+    }
+  }
   lds_barrier();
 
   for (int t = 0; t < T; ++t) {
@@ -446,6 +478,20 @@ __global__ __launch_bounds__(RF_NT) void rollout_open_kernel(OpenArgs a) {
       if (ovalid) {
         a.states[((size_t)t * M + m0 + op) * S + os] = t < len ? xn : 0.0;
         if (t < len && is_bad(xn)) bad |= MCP_STATUS_NAN;
+      }
+    }
+    double ufb = 0.0;
+    if constexpr (FB) {  // u_t from the row just published (every row, the last one included: it is stored, and a cost may read it)
+      lds_barrier();
+      if (isu) {
+        const double* xr = xs + cur * PT * S + up * S;
+        const double* tg = a.pd.target_traj + (size_t)t * S;
+        const double av = kp2 * (tg[ipos] - xr[ipos]) + kd2 * (tg[ivel] - xr[ivel]);
+        ufb = a.pd.squash ? umax * fast_tanh(av / umax) : av;
+        if (ovalid) {
+          a.inputs[((size_t)t * M + m0 + up) * U + uk] = ufb;
+          if (is_bad(ufb)) bad |= MCP_STATUS_NAN;
+        }
       }
     }
     if (t + 1 >= tl) continue;  // (uniform) nothing of this tile goes further: only the zero rows are left to write
@@ -459,7 +505,9 @@ __global__ __launch_bounds__(RF_NT) void rollout_open_kernel(OpenArgs a) {
         zp[nna + na + zi_ang] = cs;
       }
     }
-    if (isu) {  // inputs beyond a trajectory's last transition are never read
+    if constexpr (FB) {
+      if (isu) z[up * D + nna + 2 * na + uk] = ufb;
+    } else if (isu) {  // inputs beyond a trajectory's last transition are never read
       const double uv = (t + 1 < len) ? a.u[((size_t)t * a.Mu + (a.Mu == 1 ? 0 : om)) * U + uk] : 0.0;
       z[up * D + nna + 2 * na + uk] = uv;
       if (ovalid && t + 1 < len && is_bad(uv)) bad |= MCP_STATUS_NAN;
@@ -628,6 +676,90 @@ extern "C" int mcp_rollout_open_rec(const mcp_model* model, const mcp_noise* noi
   return open_dispatch(model, noise, M, T, particle_pred, x0, u, Mu, lengths, states, mu, var, jac, status, stream);
 }
 
+// ---- feedback form: launch, checks, entry ---------------------------------------------------------------------------------------
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC>
+static int launch_pd(const OpenArgsPd& a, hipStream_t st) {
+  const OpenLayout L = open_layout(PT, NEEDVAR, a.model.S, a.model.D, a.model.G, a.NpadMax, NEEDJAC, a.na);
+  const size_t lds = (size_t)L.total * sizeof(double);
+  if (lds > MCP_LDS_LIMIT) return MCP_ERR_LIMIT;
+  MCP_ENSURE_MAX_LDS(rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, true>);
+  hipLaunchKernelGGL((rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, true>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
+  MCP_LAUNCH_CHECK();
+  return MCP_OK;
+}
+template <int PT, bool NEEDVAR, bool NEEDJAC>
+static int launch_pd_deg(const OpenArgsPd& a, int maxdeg, hipStream_t st) {
+  return maxdeg == 0 ? launch_pd<PT, 0, NEEDVAR, NEEDJAC>(a, st) : launch_pd<PT, 2, NEEDVAR, NEEDJAC>(a, st);
+}
+
+// the descriptor against the model and the horizon (host fields only: the gains and the target are device memory).  pos / vel hold distinct
+// components each: the sweep keeps one input per state component and role
+static int pd_policy_check(const mcp_model* model, const mcp_pd_policy* pd, int T) {
+  if (pd->U < 1 || pd->U > MCP_MAX_INPUT) return pd->U > MCP_MAX_INPUT ? MCP_ERR_LIMIT : MCP_ERR_ARG;
+  if (pd->U != model->U || pd->target_rows < T || !pd->sqrt_kp || !pd->sqrt_kd || !pd->target_traj) return MCP_ERR_ARG;
+  for (int k = 0; k < pd->U; ++k) {
+    if (pd->pos[k] < 0 || pd->pos[k] >= model->S || pd->vel[k] < 0 || pd->vel[k] >= model->S) return MCP_ERR_ARG;
+    if (pd->squash && !(pd->u_max[k] > 0.0)) return MCP_ERR_ARG;
+    for (int j = 0; j < k; ++j)
+      if (pd->pos[j] == pd->pos[k] || pd->vel[j] == pd->vel[k]) return MCP_ERR_ARG;
+  }
+  return MCP_OK;
+}
+
+// Closed-loop rollout under the PD law: replaces the loop of MC_PILCO.apply_policy (policy_learning/MC_PILCO.py:615-674) with
+// Policy.PD_controller.forward (policy_learning/Policy.py:437-449) as the policy, over Model_learning.get_next_state
+// (model_learning/Model_learning.py:210-229, 471-494, 685-718).  jac != NULL: the recording form (what autograd would keep of that loop).
+extern "C" int mcp_rollout_pd(const mcp_model* model, const mcp_pd_policy* pd, const mcp_noise* noise, int M, int T, int particle_pred,
+                              const double* x0, double* states, double* inputs, double* jac, double* mu, double* var, uint32_t* status,
+                              void* stream) {
+  if (!model || !pd || !noise || !x0 || !states || !inputs || !status) return MCP_ERR_ARG;
+  if (M <= 0 || T < 1) return MCP_ERR_ARG;
+  if (model->S > MCP_MAX_STATE || model->U > MCP_MAX_INPUT || model->G > MCP_MAX_GP || model->D > MCP_MAX_GPDIM) return MCP_ERR_LIMIT;
+  for (int g = 0; g < model->G && g < MCP_MAX_GP; ++g)
+    if (model->gp[g].N > MCP_MAX_TRAIN) return MCP_ERR_LIMIT;
+  if (!model_ok(model)) return MCP_ERR_ARG;
+  const int prc = pd_policy_check(model, pd, T);
+  if (prc != MCP_OK) return prc;
+  OpenArgsPd a;
+  a.model = *model;
+  a.nz = *noise;
+  a.M = M;
+  a.T = T;
+  a.sample = particle_pred & 1;
+  a.Mu = M;
+  a.NpadMax = 0;
+  int maxdeg = 0;
+  for (int g = 0; g < model->G; ++g) {
+    a.NpadMax = imax(a.NpadMax, model->gp[g].Npad);
+    maxdeg = imax(maxdeg, model->gp[g].kern.poly_deg);
+  }
+  if (T == 1) jac = nullptr;  // the policy alone: no transition, nothing to record
+  a.na = jac ? (maxdeg == 0 ? 1 : maxdeg == 1 ? 2 : 4) : 0;
+  a.jac = jac;
+  a.x0 = x0;
+  a.u = nullptr;
+  a.lengths = nullptr;
+  a.states = states;
+  a.mu = mu;
+  a.var = var;
+  a.status = status;
+  a.pd = *pd;
+  a.inputs = inputs;
+  hipStream_t st = (hipStream_t)stream;
+  // the tiles of open_dispatch: the feedback adds nothing to the LDS layout
+  if (!jac) {
+    if (!a.sample && !var) return launch_pd_deg<1, false, false>(a, maxdeg, st);
+    int rc = launch_pd_deg<16, true, false>(a, maxdeg, st);
+    if (rc == MCP_ERR_LIMIT) rc = launch_pd_deg<4, true, false>(a, maxdeg, st);
+    return rc;
+  }
+  if (!a.sample && !var) return launch_pd_deg<1, false, true>(a, maxdeg, st);
+  int rc = launch_pd_deg<16, true, true>(a, maxdeg, st);
+  if (rc == MCP_ERR_LIMIT) rc = launch_pd_deg<4, true, true>(a, maxdeg, st);
+  if (rc == MCP_ERR_LIMIT) rc = launch_pd_deg<1, true, true>(a, maxdeg, st);
+  return rc;
+}
+
 // ---------------------------------------------------------------------------------------
 // Reverse-time sweep of the open-loop rollout: what autograd's backward does through the step loop of MC_PILCO.rollout
 // (MC_PILCO.py:347-373) over get_next_state (Model_learning.py:210-229, 471-494, 685-718), from the record alone.
@@ -658,12 +790,35 @@ struct OpenBwdArgs {
   double* g_x0;
   double* g_u;
 };
+// FEEDBACK form of the sweep (template FB, mcp_rollout_pd_bwd): u_t = pd(x_t) closes the loop, so the adjoint of the input goes back into
+// the state of the same row and into the gains.  Per row r, after stage B (row T - 1 has no record: only the upstream term):
+//   gu_k = gz[nna + 2 na + k] + g_inputs[r][k];     abar_k = gu_k (1 - (u_k / u_max_k)^2)  with squashing, gu_k without
+//   lambda[pos[k]] -= sqrt_kp[k]^2 abar_k;  lambda[vel[k]] -= sqrt_kd[k]^2 abar_k                      (stage C, tables kpos / kvel)
+//   g_sqrt_kp[k] += 2 sqrt_kp[k] e[pos[k]] abar_k;  g_sqrt_kd[k] += 2 sqrt_kd[k] e[vel[k]] abar_k,  e = target_traj[r] - x_r
+// Lane (p, q) keeps the sums of trajectory p's inputs q and q + 4 in registers and stores them once: g_gains [M][2][U], no atomics, no
+// sum across trajectories.  The loader also brings inputs[r], g_inputs[r], the state of EVERY row and target_traj[r].
+struct OpenBwdArgsPd : OpenBwdArgs {
+  mcp_pd_policy pd;
+  const double* inputs;    // [T][M][U]
+  const double* g_inputs;  // [T][M][U] or NULL
+  double* g_gains;         // [M][2][U] or NULL
+};
+template <bool FB>
+struct OpenBwdArgsOf {
+  typedef OpenBwdArgs type;
+};
+template <>
+struct OpenBwdArgsOf<true> {
+  typedef OpenBwdArgsPd type;
+};
+#define OB_KMAX ((MCP_MAX_INPUT + 3) / 4)  // inputs per lane of the chain wave
 
 struct OpenBwdLayout {
   int rec, xs, gs, lam, gd, gz, tab, total;  // offsets in doubles
   int rp;                                    // pitch of a trajectory's record row (odd: bank spread)
+  int ul, gul, tgl, abl, ktab, gnl;          // feedback form: inputs | g_inputs | target row (double buffers) | abar | kpos, kvel | gains^2
 };
-__host__ __device__ inline OpenBwdLayout open_bwd_layout(int S, int G, int D) {
+__host__ __device__ inline OpenBwdLayout open_bwd_layout(int S, int G, int D, bool fb = false, int U = 0) {
   OpenBwdLayout L;
   int o = 0;
   auto take = [&](int n) {
@@ -679,6 +834,12 @@ __host__ __device__ inline OpenBwdLayout open_bwd_layout(int S, int G, int D) {
   L.gd = take(OB_PT * G);
   L.gz = take(OB_PT * D);
   L.tab = take((5 * MCP_MAX_STATE + OB_PT) / 2 + 2);  // ints: og | ispos | velof | zplain | zang (per state component), len (per trajectory)
+  L.ul = fb ? take(2 * OB_PT * U) : 0;
+  L.gul = fb ? take(2 * OB_PT * U) : 0;
+  L.tgl = fb ? take(2 * S) : 0;
+  L.abl = fb ? take(OB_PT * U) : 0;
+  L.ktab = fb ? take(MCP_MAX_STATE) : 0;  // ints: kpos | kvel (per state component: the input that reads it as position / velocity, or -1)
+  L.gnl = fb ? take(2 * MCP_MAX_INPUT) : 0;  // sqrt_kp^2 | sqrt_kd^2
   L.total = o;
   return L;
 }
@@ -686,11 +847,12 @@ __host__ __device__ inline OpenBwdLayout open_bwd_layout(int S, int G, int D) {
 // orders this wave's LDS stores before its later LDS loads (the DS queue of a wave is in order; this drains it and stops the compiler)
 __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
-__global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(OpenBwdArgs a) {
+template <bool FB>
+__global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBwdArgsOf<FB>::type a) {
   extern __shared__ double smem[];
   const int S = a.S, U = a.U, G = a.G, D = a.D, M = a.M, T = a.T, nna = a.nna, na = a.na;
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const OpenBwdLayout L = open_bwd_layout(S, G, D);
+  const OpenBwdLayout L = open_bwd_layout(S, G, D, FB, U);
   const int GD = G * D, RP = L.rp;
   double* rec = smem + L.rec;
   double* xsl = smem + L.xs;
@@ -704,6 +866,13 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(OpenBwdArgs a) 
   int* zplain = velof + MCP_MAX_STATE;
   int* zang = zplain + MCP_MAX_STATE;
   int* lenl = zang + MCP_MAX_STATE;
+  double* ull = smem + L.ul;   // (feedback form)
+  double* gul = smem + L.gul;
+  double* tgl = smem + L.tgl;
+  double* abl = smem + L.abl;
+  int* kpos = reinterpret_cast<int*>(smem + L.ktab);
+  int* kvel = kpos + MCP_MAX_STATE;
+  double* gnl = smem + L.gnl;
   const int m0 = blockIdx.x * OB_PT;
 
   if (tid < S) {  // which GP a component integrates, as the forward kernel decides it
@@ -722,6 +891,23 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(OpenBwdArgs a) 
     velof[s] = g_pos >= 0 ? a.vel[g_pos] : -1;
     zplain[s] = zp;
     zang[s] = za;
+    if constexpr (FB) {
+      int kp = -1, kv = -1;
+      for (int k = 0; k < U; ++k) {
+        if (a.pd.pos[k] == s) kp = k;
+        if (a.pd.vel[k] == s) kv = k;
+      }
+      kpos[s] = kp;
+      kvel[s] = kv;
+    }
+  }
+  if constexpr (FB) {
+    if (tid >= 64 + OB_PT && tid < 64 + OB_PT + U) {
+      const int k = tid - 64 - OB_PT;
+      const double kp = a.pd.sqrt_kp[k], kd = a.pd.sqrt_kd[k];
+      gnl[k] = kp * kp;
+      gnl[MCP_MAX_INPUT + k] = kd * kd;
+    }
   }
   if (tid >= 64 && tid < 64 + OB_PT) {
     const int p = tid - 64;
@@ -748,7 +934,17 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(OpenBwdArgs a) 
       const int p = it / S, s = it - p * S;
       const int len = lenl[p];
       if (r <= len - 1) gsl[(b * OB_PT + p) * S + s] = a.g_states[((size_t)r * M + m0 + p) * S + s];
-      if (r < len - 1) xsl[(b * OB_PT + p) * S + s] = a.states[((size_t)r * M + m0 + p) * S + s];
+      if (r < len - (FB ? 0 : 1)) xsl[(b * OB_PT + p) * S + s] = a.states[((size_t)r * M + m0 + p) * S + s];
+    }
+    if constexpr (FB) {
+      for (int it = l; it < OB_PT * U; it += 64) {
+        const int p = it / U, k = it - p * U;
+        if (r <= lenl[p] - 1) {
+          ull[(b * OB_PT + p) * U + k] = a.inputs[((size_t)r * M + m0 + p) * U + k];
+          gul[(b * OB_PT + p) * U + k] = a.g_inputs ? a.g_inputs[((size_t)r * M + m0 + p) * U + k] : 0.0;
+        }
+      }
+      for (int s = l; s < S; s += 64) tgl[b * S + s] = a.pd.target_traj[(size_t)r * S + s];
     }
     for (int it = l; it < OB_PT * GD; it += 64) {
       const int p = it / GD, e = it - p * GD;
@@ -757,6 +953,21 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(OpenBwdArgs a) 
   };
 
   int b = 0, lc = 0;
+  // feedback form: this lane's inputs q, q + 4, ... of trajectory p and the running sums of their gain gradients
+  double fkp[OB_KMAX], fkd[OB_KMAX], fum[OB_KMAX], gkp[OB_KMAX], gkd[OB_KMAX];
+  int fpos[OB_KMAX], fvel[OB_KMAX];
+  if constexpr (FB) {
+#pragma unroll
+    for (int i = 0; i < OB_KMAX; ++i) {
+      const int k = (lane >> 4) + 4 * i;
+      fkp[i] = k < U ? a.pd.sqrt_kp[k] : 0.0;
+      fkd[i] = k < U ? a.pd.sqrt_kd[k] : 0.0;
+      fum[i] = k < U ? a.pd.u_max[k] : 1.0;
+      fpos[i] = k < U ? a.pd.pos[k] : 0;
+      fvel[i] = k < U ? a.pd.vel[k] : 0;
+      gkp[i] = gkd[i] = 0.0;
+    }
+  }
   if (wv == 1) load_row(tl - 1, 0, lane);
   __syncthreads();
   for (int r = tl - 1; r >= 0; --r) {
@@ -788,6 +999,28 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(OpenBwdArgs a) 
         }
       }
       wave_lds_sync();
+      if constexpr (FB) {  // stage B': through the squashing to the PD law's argument; the gains' sums
+        if (r <= len - 1) {
+          const double* tg = tgl + b * S;
+#pragma unroll
+          for (int i = 0; i < OB_KMAX; ++i) {
+            const int k = q + 4 * i;
+            if (k < U) {
+              double gu = gul[(b * OB_PT + p) * U + k];
+              if (active) gu += gzl[p * D + nna + 2 * na + k];
+              double ab = gu;
+              if (a.pd.squash) {
+                const double th = ull[(b * OB_PT + p) * U + k] / fum[i];
+                ab = gu * (1.0 - th * th);
+              }
+              abl[p * U + k] = ab;
+              gkp[i] += 2.0 * fkp[i] * (tg[fpos[i]] - xc[fpos[i]]) * ab;
+              gkd[i] += 2.0 * fkd[i] * (tg[fvel[i]] - xc[fvel[i]]) * ab;
+            }
+          }
+        }
+        wave_lds_sync();
+      }
       // stage C: the integrator and the feature map
       for (int s = q; s < S; s += 4) {
         double v = 0.0;
@@ -805,6 +1038,13 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(OpenBwdArgs a) 
             v += gzl[p * D + nna + zang[s]] * cs - gzl[p * D + nna + na + zang[s]] * sn;
           }
         }
+        if constexpr (FB) {
+          if (r <= len - 1) {
+            const int kp = kpos[s], kv = kvel[s];
+            if (kp >= 0) v -= gnl[kp] * abl[p * U + kp];
+            if (kv >= 0) v -= gnl[MCP_MAX_INPUT + kv] * abl[p * U + kv];
+          }
+        }
         lamn[s] = v;
       }
       if (active && a.g_u)
@@ -819,6 +1059,21 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(OpenBwdArgs a) 
     const int p = lane & 15, q = lane >> 4;
     if (lenl[p] > 0)
       for (int s = q; s < S; s += 4) a.g_x0[(size_t)(m0 + p) * S + s] = lam[(lc * OB_PT + p) * S + s];
+  }
+  if constexpr (FB) {
+    if (wv == 0 && a.g_gains) {
+      const int p = lane & 15, q = lane >> 4;
+      if (lenl[p] > 0) {
+#pragma unroll
+        for (int i = 0; i < OB_KMAX; ++i) {
+          const int k = q + 4 * i;
+          if (k < U) {
+            a.g_gains[((size_t)(m0 + p) * 2 + 0) * U + k] = gkp[i];
+            a.g_gains[((size_t)(m0 + p) * 2 + 1) * U + k] = gkd[i];
+          }
+        }
+      }
+    }
   }
 }
 
@@ -852,8 +1107,54 @@ extern "C" int mcp_rollout_open_bwd(const mcp_model* model, int M, int T, const 
   const OpenBwdLayout L = open_bwd_layout(a.S, a.G, a.D);  // (at every compiled limit at once: 72 KB)
   const size_t lds = (size_t)L.total * sizeof(double);
   if (lds > MCP_LDS_LIMIT) return MCP_ERR_LIMIT;
-  MCP_ENSURE_MAX_LDS(rollout_open_bwd_kernel);
-  hipLaunchKernelGGL(rollout_open_bwd_kernel, dim3((M + OB_PT - 1) / OB_PT), dim3(OB_NT), lds, (hipStream_t)stream, a);
+  MCP_ENSURE_MAX_LDS(rollout_open_bwd_kernel<false>);
+  hipLaunchKernelGGL(rollout_open_bwd_kernel<false>, dim3((M + OB_PT - 1) / OB_PT), dim3(OB_NT), lds, (hipStream_t)stream, a);
+  MCP_LAUNCH_CHECK();
+  return MCP_OK;
+}
+
+// Reverse-time sweep of the closed loop under the PD law: replaces autograd's backward (MC_PILCO.py:522) through the loop of
+// MC_PILCO.apply_policy (policy_learning/MC_PILCO.py:615-674), Policy.PD_controller.forward (policy_learning/Policy.py:437-449) and
+// get_next_state with its integrators (model_learning/Model_learning.py:210-229, 471-494, 685-718), from the record alone.
+extern "C" int mcp_rollout_pd_bwd(const mcp_model* model, const mcp_pd_policy* pd, int M, int T, const double* states, const double* inputs,
+                                  const double* jac, const double* g_states, const double* g_inputs, double* g_gains, double* g_x0,
+                                  void* stream) {
+  if (!model || !pd || !states || !inputs || !g_states || (!jac && T > 1)) return MCP_ERR_ARG;
+  if (M <= 0 || T < 1) return MCP_ERR_ARG;
+  if (model->S > MCP_MAX_STATE || model->U > MCP_MAX_INPUT || model->G > MCP_MAX_GP || model->D > MCP_MAX_GPDIM) return MCP_ERR_LIMIT;
+  if (model->S <= 0 || model->U <= 0 || model->G <= 0 || model->D <= 0 || model->n_angle < 0 || model->n_not_angle < 0 ||
+      model->n_not_angle + 2 * model->n_angle + model->U != model->D)
+    return MCP_ERR_ARG;
+  for (int i = 0; i < model->n_angle; ++i)
+    if (model->angle[i] < 0 || model->angle[i] >= model->S) return MCP_ERR_ARG;
+  for (int i = 0; i < model->n_not_angle; ++i)
+    if (model->not_angle[i] < 0 || model->not_angle[i] >= model->S) return MCP_ERR_ARG;
+  for (int g = 0; g < model->G; ++g)
+    if (model->vel[g] < 0 || model->vel[g] >= model->S || model->not_vel[g] < -1 || model->not_vel[g] >= model->S) return MCP_ERR_ARG;
+  const int prc = pd_policy_check(model, pd, T);
+  if (prc != MCP_OK) return prc;
+  if (!g_x0 && !g_gains) return MCP_OK;  // nothing asked for
+  OpenBwdArgsPd a;
+  memset(&a, 0, sizeof(a));
+  a.S = model->S, a.U = model->U, a.G = model->G, a.D = model->D, a.nna = model->n_not_angle, a.na = model->n_angle, a.M = M, a.T = T;
+  for (int i = 0; i < MCP_MAX_STATE; ++i) a.angle[i] = model->angle[i], a.not_angle[i] = model->not_angle[i];
+  for (int g = 0; g < MCP_MAX_GP; ++g) a.vel[g] = model->vel[g], a.not_vel[g] = model->not_vel[g];
+  a.Ts = model->Ts;
+  a.states = states;
+  a.jac = jac;
+  a.g_states = g_states;
+  a.lengths = nullptr;
+  a.g_x0 = g_x0;
+  a.g_u = nullptr;
+  a.pd = *pd;
+  a.inputs = inputs;
+  a.g_inputs = g_inputs;
+  a.g_gains = g_gains;
+  const OpenBwdLayout L = open_bwd_layout(a.S, a.G, a.D, true, a.U);  // (at every compiled limit at once: 89 KB)
+  const size_t lds = (size_t)L.total * sizeof(double);
+  if (lds > MCP_LDS_LIMIT) return MCP_ERR_LIMIT;
+  MCP_ENSURE_MAX_LDS(rollout_open_bwd_kernel<true>);
+  hipLaunchKernelGGL(rollout_open_bwd_kernel<true>, dim3((M + OB_PT - 1) / OB_PT), dim3(OB_NT), lds, (hipStream_t)stream, a);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
 }

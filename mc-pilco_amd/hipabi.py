@@ -60,6 +60,11 @@ class Noise(C.Structure):
     _fields_ = [("eps", dptr), ("masks", dptr), ("seed", C.c_uint64), ("call", C.c_uint64), ("particle_offset", C.c_int64), ("call_dev", dptr)]
 
 
+class PDPolicy(C.Structure):
+    _fields_ = [("U", C.c_int32), ("squash", C.c_int32), ("pos", C.c_int32 * MAX_INPUT), ("vel", C.c_int32 * MAX_INPUT),
+                ("u_max", C.c_double * MAX_INPUT), ("sqrt_kp", dptr), ("sqrt_kd", dptr), ("target_traj", dptr), ("target_rows", C.c_int32)]
+
+
 class OptState(C.Structure):
     _fields_ = [("step", C.c_int64), ("attempt", C.c_int64), ("pending", C.c_int64), ("adam_t", C.c_int64), ("total_attempts", C.c_int64),
                 ("es2", C.c_double), ("cost_prev", C.c_double)]
@@ -119,6 +124,9 @@ _SIGS = {
     "mcp_rollout_open_rec": (C.c_int, [C.POINTER(Model), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr, C.c_int, dptr, dptr, dptr, dptr,
                                        dptr, dptr, dptr]),
     "mcp_rollout_open_bwd": (C.c_int, [C.POINTER(Model), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
+    "mcp_rollout_pd": (C.c_int, [C.POINTER(Model), C.POINTER(PDPolicy), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr,
+                                 dptr, dptr, dptr]),
+    "mcp_rollout_pd_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(PDPolicy), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
     "mcp_rollout_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(Policy), C.POINTER(Noise), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr,
                                   dptr, dptr, dptr, dptr, dptr, C.c_size_t, dptr]),
     "mcp_rollout_fwd_ex": (C.c_int, [C.POINTER(Model), C.POINTER(Policy), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr, dptr,

@@ -586,6 +586,131 @@ def rollout_open_diff(model: PackedModel, x0, u, *, lengths=None, noise: Optiona
     return RolloutOpenFunction.apply(x0c, uc, model, lengths, noise, bool(particle_pred), status), status
 
 
+# --------------------------------------------------------------------------------------
+# fused closed loop under the PD law (autograd)
+# --------------------------------------------------------------------------------------
+class PackedPD:
+    """mcp_pd_policy of a ``Policy.PD_controller`` (reference policy_learning/Policy.py:406-449): the two gain parameters are kept as they
+    are -- every launch takes views of the LIVE tensors, so an optimizer's in-place updates are seen -- and the target trajectory is held
+    on the device.  The reference's index layout: input k reads the errors of position k and of velocity h + k, h = S / 2."""
+
+    def __init__(self, policy):
+        self.sqrt_kp, self.sqrt_kd = policy.sqrt_Kp_gains, policy.sqrt_Kd_gains
+        self.S, self.U = int(policy.state_dim), int(policy.input_dim)
+        dev = _dev(self.sqrt_kp.device)
+        if policy.target_traj is None:
+            raise RuntimeError("the PD controller has no target trajectory")
+        self.target_traj = _t(policy.target_traj, dev).reshape(-1, self.S).contiguous()
+        h = self.S // 2
+        self.pos, self.vel = list(range(self.U)), list(range(h, h + self.U))
+        self.squash = bool(policy.flg_squash)
+        self.u_max = np.full(self.U, float(policy.u_max)) if np.isscalar(policy.u_max) else np.asarray(policy.u_max, dtype=np.float64).reshape(-1)
+        if self.u_max.size != self.U or self.U > abi.MAX_INPUT:
+            raise RuntimeError("u_max must be a scalar or hold one bound per input (at most %d inputs)" % abi.MAX_INPUT)
+        self.device = dev
+
+    def gains(self):
+        """(sqrt_kp, sqrt_kd) as [U] tensors on the autograd graph of the parameters: views, or a scalar gain expanded to every input."""
+        out = []
+        for g in (self.sqrt_kp, self.sqrt_kd):
+            g = g.reshape(-1)
+            if g.numel() == 1 and self.U > 1:
+                g = g.expand(self.U)
+            if g.numel() != self.U:
+                raise RuntimeError("the PD gains must hold one value per input (or one for all)")
+            out.append(g)
+        return out
+
+    def to_c(self, kp, kd):
+        """The descriptor over the contiguous float64 GPU tensors ``kp`` / ``kd`` [U]."""
+        for t in (kp, kd):
+            if t.dtype != DT or not t.is_cuda or not t.is_contiguous() or t.numel() != self.U:
+                raise RuntimeError("the PD gains must be contiguous float64 GPU tensors with one value per input")
+        c = abi.PDPolicy()
+        c.U, c.squash = self.U, int(self.squash)
+        for k in range(self.U):
+            c.pos[k], c.vel[k], c.u_max[k] = self.pos[k], self.vel[k], float(self.u_max[k])
+        c.sqrt_kp, c.sqrt_kd = kp.data_ptr(), kd.data_ptr()
+        c.target_traj, c.target_rows = self.target_traj.data_ptr(), int(self.target_traj.shape[0])
+        return c
+
+
+def _rollout_pd_launch(model, pd, kp, kd, noise, x0, T, particle_pred, status, record):
+    M, dev = int(x0.shape[0]), model.device
+    states = torch.empty(T, M, model.S, dtype=DT, device=dev)
+    inputs = torch.empty(T, M, model.U, dtype=DT, device=dev)
+    jac = torch.empty(T - 1, M, model.G, model.D, dtype=DT, device=dev) if (record and T > 1) else None
+    pc, nz = pd.to_c(kp, kd), noise.to_c()
+    abi.check(abi.lib().mcp_rollout_pd(_mc(model), C.byref(pc), C.byref(nz), M, T, int(bool(particle_pred)), abi.ptr(x0), abi.ptr(states),
+                                       abi.ptr(inputs), abi.ptr(jac), None, None, abi.ptr(status), abi.stream()), "mcp_rollout_pd")
+    return states, inputs, jac
+
+
+class RolloutPDFunction(torch.autograd.Function):
+    """(x0 [M,S], sqrt_kp [U], sqrt_kd [U]) -> states [T,M,S], inputs [T,M,U] through the recording form of the fused closed loop under the
+    PD law (mcp_rollout_pd); backward is the reverse-time sweep mcp_rollout_pd_bwd over the record, with both upstream gradients.  The
+    per-trajectory gain gradients are added in torch's fixed order; the GP model is frozen."""
+
+    @staticmethod
+    def forward(ctx, x0, kp, kd, model, pd, noise, T, particle_pred, status):
+        states, inputs, jac = _rollout_pd_launch(model, pd, kp, kd, noise, x0, T, particle_pred, status, True)
+        ctx.model, ctx.pd, ctx.has_jac = model, pd, jac is not None
+        ctx.set_materialize_grads(False)
+        # (saved tensors: autograd refuses a backward after an in-place change of any of them -- the record, or a gain stepped too early)
+        ctx.save_for_backward(*((states, inputs, kp, kd) + ((jac,) if jac is not None else ())))
+        return states, inputs
+
+    @staticmethod
+    def backward(ctx, g_states, g_inputs):
+        saved = ctx.saved_tensors
+        states, inputs, kp, kd = saved[:4]
+        jac = saved[4] if ctx.has_jac else None
+        model, pd = ctx.model, ctx.pd
+        T, M = int(states.shape[0]), int(states.shape[1])
+        gs = torch.zeros_like(states) if g_states is None else g_states.to(dtype=DT).contiguous()
+        gi = None if g_inputs is None else g_inputs.to(dtype=DT).contiguous()
+        want_x0, want_g = ctx.needs_input_grad[0], ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        g_x0 = torch.empty(M, model.S, dtype=DT, device=states.device) if want_x0 else None
+        g_gains = torch.empty(M, 2, model.U, dtype=DT, device=states.device) if want_g else None
+        pc = pd.to_c(kp, kd)
+        abi.check(abi.lib().mcp_rollout_pd_bwd(_mc(model), C.byref(pc), M, T, abi.ptr(states), abi.ptr(inputs), abi.ptr(jac), abi.ptr(gs), abi.ptr(gi),
+                                               abi.ptr(g_gains), abi.ptr(g_x0), abi.stream()), "mcp_rollout_pd_bwd")
+        gg = g_gains.sum(0) if want_g else None  # the trajectories' gradients added in torch's fixed order
+        return (g_x0, gg[0] if ctx.needs_input_grad[1] else None, gg[1] if ctx.needs_input_grad[2] else None, None, None, None, None, None, None)
+
+
+def rollout_pd(model: PackedModel, pd: PackedPD, noise: Optional[NoiseSpec], x0, T, particle_pred=True, status=None):
+    """Closed-loop rollout under a PD controller in ONE launch: x0 [M,S] -> states [T,M,S], inputs [T,M,U] (row T - 1 included) and the
+    status word.  ``noise``: an eps buffer [T-1,M,G] or Philox by seed / call / particle_offset (``particle_pred``), as ``rollout_open``.
+    With gradients enabled and x0 or a gain requiring grad the recording launch runs and backward is the fused sweep (gradients to
+    ``sqrt_Kp_gains``, ``sqrt_Kd_gains`` and x0); otherwise nothing is recorded.  The same states and inputs, bit for bit, either way."""
+    if not isinstance(x0, torch.Tensor) or not x0.is_cuda or not pd.sqrt_kp.is_cuda or not pd.sqrt_kd.is_cuda:
+        raise RuntimeError("rollout_pd operates on GPU memory only (x0 and the gains must be GPU tensors); there is no CPU path")
+    dev, T = model.device, int(T)
+    if pd.S != model.S or pd.U != model.U:
+        raise RuntimeError("the PD controller is for %d states and %d inputs, the model has %d and %d" % (pd.S, pd.U, model.S, model.U))
+    if T < 1 or pd.target_traj.shape[0] < T:
+        raise RuntimeError("the target trajectory has %d rows, the rollout needs %d" % (pd.target_traj.shape[0], T))
+    x0c = x0.to(device=dev, dtype=DT).contiguous()
+    if x0c.dim() != 2 or x0c.shape[1] != model.S:
+        raise RuntimeError("x0 must be [M,%d]" % model.S)
+    M = int(x0c.shape[0])
+    noise = NoiseSpec() if noise is None else noise
+    if particle_pred:
+        _check_noise(noise, T, M, model.G, 0, 0.0, True)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    elif status.dtype != torch.int32 or status.numel() != 1 or status.device != x0c.device or not status.is_contiguous():
+        raise RuntimeError("status must be a one-element int32 tensor on the rollout's device")
+    kp, kd = pd.gains()
+    if torch.is_grad_enabled() and (x0c.requires_grad or kp.requires_grad or kd.requires_grad):
+        states, inputs = RolloutPDFunction.apply(x0c, kp.contiguous(), kd.contiguous(), model, pd, noise, T, bool(particle_pred), status)
+        return states, inputs, status
+    states, inputs, _ = _rollout_pd_launch(model, pd, kp.detach().contiguous(), kd.detach().contiguous(), noise, x0c.detach(), T, particle_pred,
+                                           status, False)
+    return states, inputs, status
+
+
 # measurement hook (bench.py): a pair of torch.cuda.Event recorded on the launch stream right around mcp_rollout_bwd -- the adjoint sweep
 # runs inside autograd's backward, where the caller cannot bracket it.  None (the default) = nothing is recorded.  ``fwd_events``: the same
 # around mcp_rollout_fwd (operand packing + hand-off buffer reset + the rollout kernel, without the host's tensor allocations).

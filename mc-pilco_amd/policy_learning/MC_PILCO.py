@@ -71,6 +71,8 @@ class MC_PILCO(torch.nn.Module):
         self._rollout_calls = 0
         self.fused_open_loop = True       # MC_PILCO.rollout's mean chain as one fused launch (False: the step loop on get_next_state)
         self.last_open_loop_fused = False  # what the last rollout() ran
+        self.fused_feedback = True        # apply_policy with a PD_controller as one fused launch (False: the step loop on get_next_state)
+        self.last_feedback_fused = False  # what the last apply_policy() ran for such a policy
         self.dist_group = None
         self.last_status = None
         self.gp_sharding = True    # cleared for good once a GP-sharded launch reports MCP_STATUS_SYNC (co-residency was not there)
@@ -154,6 +156,18 @@ class MC_PILCO(torch.nn.Module):
             return ops.NoiseSpec(eps=eps, masks=mk), p
         return self._philox_noise(), p
 
+    def _feedback_noise(self, T):
+        """``_rollout_noise`` for a policy without dropout: in "reference" mode eps_t for t = 1..T-1 in the reference's order, with no
+        mask draw in between; else Philox."""
+        G = self.model_learning.num_gp
+        self._rollout_calls += 1
+        if self.noise_mode == "reference":
+            Mt = self._m_total
+            eps = [torch.empty(Mt, G, dtype=self.dtype).normal_() for _ in range(1, T)]
+            eps = self._shard_slice(torch.stack(eps) if eps else torch.zeros(0, Mt, G, dtype=self.dtype), 1).to(self.device).contiguous()
+            return ops.NoiseSpec(eps=eps)
+        return self._philox_noise()
+
     def _philox_noise(self):
         """In-kernel noise keyed by (seed, rollout counter, global particle).  While an attempt is being recorded into a graph the counter is the
         device word the graph advances (by-value part 0); the host's ``_rollout_calls`` mirrors it either way."""
@@ -178,6 +192,14 @@ class MC_PILCO(torch.nn.Module):
             noise, p = self._rollout_noise(M, T, p_dropout)
             states, inputs, status = ops.rollout(ml.packed(), pol.packed(), noise, x0, T, p, gp_sharding=self.gp_sharding)
             self.last_status = status
+            return states, inputs
+        self.last_feedback_fused = False
+        if (self.fused_feedback and world == 1 and isinstance(pol, _Policy.PD_controller) and _has_fused_layout(ml)
+                and pol.fusable(ml.packed(), T)):
+            # the closed loop under the PD law, one launch (and one sweep in backward): the eps draws of _rollout_noise, no dropout masks
+            states, inputs, status = ops.rollout_pd(ml.packed(), pol.packed(), self._feedback_noise(T), x0, T)
+            self.last_status = status
+            self.last_feedback_fused = True
             return states, inputs
         # generic (unfused) path: any model / policy object with the reference's step interface
         self.last_status = None  # (no fused launch: the flags of an earlier fused rollout do not describe this one)

@@ -95,7 +95,10 @@ class Sum_of_sinusoids(Policy):
 
 class PD_controller(Policy):
     """u = squash(Kp e_q + Kd e_qdot) with e = target_traj[t] - state, gains = sqrt_*_gains^2 (Policy.py:406-449; the UR5 launch
-    script's exploration controller).  Host-side helper for the system simulator; not part of the fused rollout."""
+    script's tracking controller, and with ``flg_trainable`` the reference's second trainable policy).  ``forward`` is the reference's
+    torch expression: the system simulator calls it once per sample.  As ``MC_PILCO``'s control policy on a GPU model with a fused
+    layout it runs inside the fused closed-loop rollout (``packed()``, ``fusable()``; ops.rollout_pd: one launch, and the reverse-time
+    sweep for the gradients of the two gain parameters)."""
 
     def __init__(self, state_dim, input_dim, sqrt_Kp_gains, sqrt_Kd_gains, target_traj=None, flg_squash=True, u_max=1.0, flg_trainable=False,
                  dtype=torch.float64, device=torch.device("cpu")):
@@ -103,6 +106,34 @@ class PD_controller(Policy):
         self.target_traj = target_traj
         self.sqrt_Kp_gains = torch.nn.Parameter(torch.tensor(sqrt_Kp_gains, dtype=self.dtype, device=self.device), requires_grad=flg_trainable)
         self.sqrt_Kd_gains = torch.nn.Parameter(torch.tensor(sqrt_Kd_gains, dtype=self.dtype, device=self.device), requires_grad=flg_trainable)
+
+    def packed(self) -> "ops.PackedPD":
+        """mcp_pd_policy over the LIVE gain parameters (rebuilt if a tensor or the target was replaced)."""
+        key = (self.sqrt_Kp_gains.data_ptr(), self.sqrt_Kd_gains.data_ptr(), id(self.target_traj), self.flg_squash, id(self.u_max))
+        hit = self.__dict__.get("_packed_pd")
+        if hit is None or hit[0] != key:
+            hit = self.__dict__["_packed_pd"] = (key, ops.PackedPD(self))
+        return hit[1]
+
+    def fusable(self, model, T):
+        """Whether T steps of this controller on ``model`` (an ops.PackedModel, or anything with ``S`` and ``U``) can run as the fused
+        closed loop: the reference's index layout needs an even S with one input per position (input_dim == S / 2), each gain holds one
+        value per input (or one for all: expanded on the host), the target covers the horizon, and everything is float64 on a GPU."""
+        S = int(self.state_dim)
+        if S % 2 != 0 or int(self.input_dim) != S // 2 or int(self.input_dim) > ops.abi.MAX_INPUT:
+            return False
+        if int(getattr(model, "S", -1)) != S or int(getattr(model, "U", -1)) != int(self.input_dim):
+            return False
+        if any(int(g.numel()) not in (1, int(self.input_dim)) for g in (self.sqrt_Kp_gains, self.sqrt_Kd_gains)):
+            return False
+        tt = self.target_traj
+        if tt is None or np.ndim(tt) != 2 or int(np.shape(tt)[0]) < int(T) or int(np.shape(tt)[1]) != S:
+            return False
+        if not np.isscalar(self.u_max) and np.asarray(self.u_max).size != int(self.input_dim):
+            return False
+        if self.dtype != torch.float64 or any(g.dtype != torch.float64 or not g.is_cuda for g in (self.sqrt_Kp_gains, self.sqrt_Kd_gains)):
+            return False
+        return True
 
     def forward(self, states, t, p_dropout=0.0):
         states = states.reshape([-1, self.state_dim])
