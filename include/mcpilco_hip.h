@@ -55,6 +55,8 @@ extern "C" {
 #define MCP_MAX_GPDIM 32   /* D  : GP input dimension                                   */
 #define MCP_MAX_PFEAT 32   /* P  : policy feature dimension                             */
 #define MCP_MAX_BASIS 1024 /* B  : policy basis functions                               */
+#define MCP_MAX_BASIS_WIDE 512 /* B of a WIDE policy (P > 16 or U > 4): the adjoint sweep of those widths has one thread per basis function in
+                                * workgroups of at most 512, so mcp_rollout_fwd and mcp_rollout_bwd both refuse more (MCP_ERR_LIMIT) */
 #define MCP_MAX_TRAIN 4096 /* N  : training points kept per GP (fused rollout kernels; round 5: was 1024) */
 
 /* Kernel hyper-parameters of one GP: squared-exponential (+ Volterra polynomial of degree

@@ -1549,6 +1549,7 @@ static int rollout_bwd_impl(const mcp_model* model, const mcp_policy* policy, co
     return MCP_ERR_ARG;
   }
   if (!policy_ok(policy, model->S, model->U, T)) return MCP_ERR_ARG;
+  if (!policy_basis_ok(policy)) return MCP_ERR_LIMIT;
   if (workspace_bytes < mcp_rollout_workspace_bytes(model, policy, M, T)) return MCP_ERR_WORKSPACE;
   BwdArgs a;
   a.model = *model;

@@ -97,6 +97,10 @@ static inline mcp_model policy_only_model(const mcp_policy* p) {
   return m;
 }
 
+// the sweeps of the wide policy classes (<24,6>, <32,8>: P > 16 or U > 4) exist for up to 512 threads, one per basis function: the forward refuses
+// what the backward could not differentiate (MCP_ERR_LIMIT from both)
+static inline bool policy_basis_ok(const mcp_policy* p) { return !((p->P > 16 || p->U > 4) && p->B > MCP_MAX_BASIS_WIDE); }
+
 static inline bool policy_ok(const mcp_policy* p, int S, int U, int T) {
   if (!p || p->S != S || p->U != U) return false;
   if (p->B <= 0 || p->B > MCP_MAX_BASIS || p->P <= 0 || p->P > MCP_MAX_PFEAT) return false;

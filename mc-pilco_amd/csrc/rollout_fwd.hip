@@ -1288,6 +1288,7 @@ static int rollout_fwd_impl(const mcp_model* model, const mcp_policy* policy, co
     return MCP_ERR_ARG;
   }
   if (!policy_ok(policy, model->S, model->U, T)) return MCP_ERR_ARG;
+  if (!policy_basis_ok(policy)) return MCP_ERR_LIMIT;
   FwdArgs a;
   a.model = *model;
   a.pol = *policy;

@@ -280,6 +280,10 @@ class PackedPolicy:
         self.bias = bias  # [U] f_linear.bias (flg_bias) or None
         B, P = centers.shape
         U = weight.shape[0]
+        if (P > 16 or U > 4) and B > abi.MAX_BASIS_WIDE:
+            # (refused here, not at the first backward(): the adjoint sweep of these widths has one thread per basis function, 512 at the most)
+            raise ValueError("a policy with more than 16 features or more than 4 inputs (P = %d, U = %d) takes at most MCP_MAX_BASIS_WIDE = %d "
+                             "basis functions (%d given): the adjoint sweep of the wide classes has no larger form" % (P, U, abi.MAX_BASIS_WIDE, B))
         um = np.full(U, float(u_max)) if np.isscalar(u_max) else np.asarray(u_max, dtype=np.float64).reshape(-1)
         self.u_max = _t(um, dev)
         self.target_traj = None if target_traj is None else _t(target_traj, dev)

@@ -267,6 +267,33 @@ def next_state(m: SpeedModel, x, u, eps: Optional[torch.Tensor], particle_pred: 
     return nxt, dmu, dvar
 
 
+def mixed_next_state(m: SpeedModel, x, u, eps: Optional[torch.Tensor], particle_pred: bool = True, var_scale=None):
+    """``next_state`` for the layouts the packed model descriptor also takes (include/mcpilco_hip.h, mcp_model): ``m.not_vel[g] == -1``
+    means GP g integrates no position (x'[vel[g]] = x[vel[g]] + delta_g only, the delta-state rule of Model_learning.py:471-493), and
+    ``var_scale`` [G] multiplies the posterior variances before sampling (flg_norm: norm_list^2, Model_learning.py:220-221).  A state
+    that is neither a velocity nor an integrated position stays zero, as in ``next_state``.  With every position given and no scale this
+    is ``next_state``; with vel = all states and every not_vel -1 it is ``delta_next_state``."""
+    _, mus, vrs = one_step_gp_out(m, x, u)
+    dmu = torch.cat(mus, 1)
+    dvar = torch.cat(vrs, 1)
+    if var_scale is not None:
+        dvar = dvar * torch.as_tensor(var_scale, dtype=DT).reshape(1, -1)
+    if particle_pred:
+        if eps is None:
+            eps = torch.empty(dmu.shape, dtype=DT).normal_()
+        delta = dmu + torch.sqrt(dvar) * eps
+    else:
+        delta = dmu
+    vel, not_vel = list(m.vel), list(m.not_vel)
+    nxt = torch.zeros_like(x)
+    nxt[:, vel] = x[:, vel] + delta
+    gs = [g for g, q in enumerate(not_vel) if q >= 0]
+    if gs:
+        q, v = [not_vel[g] for g in gs], [vel[g] for g in gs]
+        nxt[:, q] = x[:, q] + m.Ts * x[:, v] + m.Ts / 2 * delta[:, gs]
+    return nxt, dmu, dvar
+
+
 # --------------------------------------------------------------------------------------
 # policy
 # --------------------------------------------------------------------------------------
@@ -368,8 +395,10 @@ def apply_policy(
     eps: Optional[torch.Tensor] = None,
     masks: Optional[torch.Tensor] = None,
     particle_pred: bool = True,
+    step=None,
 ):
     """policy_learning/MC_PILCO.py:615-674 (the T-loop after x0 has been sampled).
+    ``step``: the model's one-step function (m, x, u, eps, particle_pred) -> (x', mu, var); None = ``next_state``.
 
     eps [T-1,M,G] / masks [T,M,B] given -> injected;  None -> drawn from the torch CPU
     generator in the reference's order: mask_0, then for t=1..T-1: eps_t, mask_t.
@@ -379,7 +408,7 @@ def apply_policy(
     us = [policy_forward(pp, x0, 0, None if masks is None else masks[0], p_drop)]
     for t in range(1, T):
         e = None if eps is None else eps[t - 1]
-        x, _, _ = next_state(m, xs[-1], us[-1], e, particle_pred)
+        x, _, _ = (step or next_state)(m, xs[-1], us[-1], e, particle_pred)
         xs.append(x)
         us.append(policy_forward(pp, x, t, None if masks is None else masks[t], p_drop))
     return torch.stack(xs), torch.stack(us)
@@ -406,6 +435,7 @@ def apply_policy_pms(
     eps: Optional[torch.Tensor] = None,
     masks: Optional[torch.Tensor] = None,
     pos_noise: Optional[torch.Tensor] = None,
+    step=None,
 ):
     """policy_learning/MC_PILCO.py:808-906 (MC_PILCO4PMS.apply_policy, the T-loop after x0 has been sampled).
 
@@ -413,7 +443,7 @@ def apply_policy_pms(
     (:881-885), velocities by backward difference of the noisy positions (:888-891) passed through the first-order
     Butterworth filter (:895-899); at t=0 measured = true (:856).  eps [T-1,M,G], pos_noise [T-1,M,len(pos)] (standard
     normal, scaled here by std_pos) and masks [T,M,B] are injected; None draws from the torch CPU generator in the
-    reference's order (mask_0; per step: eps_t, position noise, mask_t).
+    reference's order (mask_0; per step: eps_t, position noise, mask_t).  ``step``: as in ``apply_policy``.
     """
     b, a = butter1(fc)
     Ts = m.Ts
@@ -424,7 +454,7 @@ def apply_policy_pms(
     us = [policy_forward(pp, meas_prev, 0, None if masks is None else masks[0], p_drop)]
     for t in range(1, T):
         e = None if eps is None else eps[t - 1]
-        x, _, _ = next_state(m, xs[-1], us[-1], e, True)
+        x, _, _ = (step or next_state)(m, xs[-1], us[-1], e, True)
         xs.append(x)
         n = torch.randn(x.shape[0], len(pos), dtype=DT) if pos_noise is None else pos_noise[t - 1]
         noisy = x.clone()
