@@ -68,24 +68,43 @@ struct OpenArgsPd : OpenArgs {
   mcp_pd_policy pd;
   double* inputs;  // [T][M][U]
 };
-template <bool FB>
+// MEASURED feedback form (template PMS with FB, mcp_rollout_pd_meas): the PD law reads a simulated measurement y_t of x_t instead of x_t
+// (MC_PILCO4PMS.apply_policy, policy_learning/MC_PILCO.py:856-899; mcp_meas in include/mcpilco_hip.h).  Per pair i, p = pos[i], v = vel[i]:
+//   row 0      np_0 = x_0[p],  nv_0 = mv_0 = x_0[v]                                   (the true state)
+//   row t >= 1 np_t = x_t[p] + std_i n_{t,i};  nv_t = (np_t - np_{t-1}) / Ts;  mv_t = (b0 nv_t + b1 nv_{t-1} - a1 mv_{t-1}) / a0
+//   y_t = x_t with y[p] = np_t, y[v] = mv_t;   e = target_traj[t] - y_t
+// The state thread of a measured position keeps np, nv, mv of its pair in registers (x_0[v] read once from x0) and writes y[p] and y[v]
+// into an LDS row beside xs; the threads of the components in no pair write their own value, the thread of a measured velocity writes
+// nothing; the input threads read that row behind the barrier the feedback form already has.  n_{t,i} is addressed as in the closed-loop
+// kernels (pos_noise[((t-1) M + m) n + i], or Philox stream MCP_STREAM_POS by global particle id): a particle sees the same measurement
+// noise whichever policy drives it.  meas.meas [T][M][S] is written for every row (the sweep reads it).
+struct OpenArgsPdMeas : OpenArgsPd {
+  mcp_meas ms;
+};
+template <bool FB, bool PMS = false>
 struct OpenArgsOf {
   typedef OpenArgs type;
 };
 template <>
-struct OpenArgsOf<true> {
+struct OpenArgsOf<true, false> {
   typedef OpenArgsPd type;
+};
+template <>
+struct OpenArgsOf<true, true> {
+  typedef OpenArgsPdMeas type;
 };
 
 struct OpenLayout {
   int xs, z, red, gpl, kpar, panel, xt, al, total;  // offsets in doubles
   int vpan, redj, wj, redj_gp;                      // recording form: v panel | partial sums of phase J (stride per GP) | w per trajectory
   int xl;                                           // X^T and alpha of every GP staged in LDS (row pitch NpadMax)
+  int ym;                                           // measured feedback form: the measurement row [PT][S]
 };
 
 #define RO_KR(PT) ((PT) == 16 ? 18 : (PT))  // row pitch of the k panel (16 particles: + 2 pad, bank spread of the phase-K stores)
 
-__host__ __device__ inline OpenLayout open_layout(int PT, bool needvar, int S, int D, int G, int NpadMax, bool needjac = false, int na = 0) {
+__host__ __device__ inline OpenLayout open_layout(int PT, bool needvar, int S, int D, int G, int NpadMax, bool needjac = false, int na = 0,
+                                                  bool pms = false) {
   OpenLayout L;
   int o = 0;
   auto take = [&](int n) {
@@ -106,6 +125,7 @@ __host__ __device__ inline OpenLayout open_layout(int PT, bool needvar, int S, i
   L.wj = (needvar && needjac) ? take(PT) : 0;
   L.redj_gp = needvar ? 0 : rj;
   L.redj = needvar ? L.panel : (needjac ? take(G * rj) : 0);
+  L.ym = pms ? take(PT * S) : 0;
   const int xneed = G * (D + 1) * NpadMax + 4;
   L.xl = (!needvar && o + xneed <= MCP_LDS_LIMIT / 8) ? 1 : 0;
   L.xt = L.xl ? take(G * D * NpadMax) : 0;
@@ -392,14 +412,15 @@ __device__ __forceinline__ void open_jac_store(const OpenArgs& a, const GpL& gp,
   }
 }
 
-template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool FB = false>
-__global__ __launch_bounds__(RF_NT) void rollout_open_kernel(typename OpenArgsOf<FB>::type a) {
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool FB = false, bool PMS = false>
+__global__ __launch_bounds__(RF_NT) void rollout_open_kernel(typename OpenArgsOf<FB, PMS>::type a) {
+  static_assert(FB || !PMS, "the measurement model belongs to the feedback form");
   extern __shared__ double smem[];
   const mcp_model& md = a.model;
   const int S = md.S, U = md.U, G = md.G, D = md.D, M = a.M, T = a.T;
   const int nna = md.n_not_angle, na = md.n_angle;
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const OpenLayout L = open_layout(PT, NEEDVAR, S, D, G, a.NpadMax, NEEDJAC, a.na);
+  const OpenLayout L = open_layout(PT, NEEDVAR, S, D, G, a.NpadMax, NEEDJAC, a.na, PMS);
   double* xs = smem + L.xs;
   double* z = smem + L.z;
   double* red = smem + L.red;  // [2][G][RF_NW][PT]
@@ -469,6 +490,23 @@ __global__ __launch_bounds__(RF_NT) void rollout_open_kernel(typename OpenArgsOf
       ivel = a.pd.vel[uk];
     }
   }
+  // measured feedback form: the pair of this state component (pm_pos: it is the pair's position and carries the filter; pm_vel: it is
+  // the pair's velocity and leaves its slot of the measurement row to the position's thread)
+  int pm_pos = -1, pm_vel = -1, pm_vc = 0;
+  double pm_std = 0.0, pm_np = 0.0, pm_nv = 0.0, pm_mv = 0.0;
+  if constexpr (PMS) {
+    if (own) {
+      for (int i = 0; i < a.ms.n; ++i) {
+        if (a.ms.vel[i] == os) pm_vel = i;
+        if (a.ms.pos[i] == os) {
+          pm_pos = i;
+          pm_vc = a.ms.vel[i];
+          pm_std = a.ms.std_pos[i];
+        }
+      }
+      if (pm_pos >= 0) pm_nv = pm_mv = a.x0[(size_t)om * S + pm_vc];
+    }
+  }
   lds_barrier();
 
   for (int t = 0; t < T; ++t) {
@@ -480,11 +518,39 @@ __global__ __launch_bounds__(RF_NT) void rollout_open_kernel(typename OpenArgsOf
         if (t < len && is_bad(xn)) bad |= MCP_STATUS_NAN;
       }
     }
+    if constexpr (PMS) {  // y_t: the measurement of the row just formed (MC_PILCO.py:856-899)
+      if (own && pm_vel < 0) {
+        double* yr = smem + L.ym + op * S;
+        double npos = xn, mv = 0.0;
+        if (pm_pos >= 0) {
+          if (t == 0) {
+            mv = pm_mv;  // (row 0: the true velocity, which also starts both histories)
+          } else {
+            const double nn = a.ms.pos_noise ? a.ms.pos_noise[((size_t)(t - 1) * M + om) * a.ms.n + pm_pos]
+                                             : philox_normal(nzl, om, t, pm_pos, MCP_STREAM_POS);
+            npos = fma(pm_std, nn, xn);
+            const double nv = (npos - pm_np) / Ts;
+            mv = (a.ms.b0 * nv + a.ms.b1 * pm_nv - a.ms.a1 * pm_mv) / a.ms.a0;
+            pm_nv = nv;
+            pm_mv = mv;
+          }
+          pm_np = npos;
+          yr[pm_vc] = mv;
+        }
+        yr[os] = npos;
+        if (ovalid) {
+          double* mr = a.ms.meas + ((size_t)t * M + m0 + op) * S;
+          mr[os] = npos;
+          if (pm_pos >= 0) mr[pm_vc] = mv;
+          if (is_bad(npos) || is_bad(mv)) bad |= MCP_STATUS_NAN;
+        }
+      }
+    }
     double ufb = 0.0;
     if constexpr (FB) {  // u_t from the row just published (every row, the last one included: it is stored, and a cost may read it)
       lds_barrier();
       if (isu) {
-        const double* xr = xs + cur * PT * S + up * S;
+        const double* xr = PMS ? smem + L.ym + up * S : xs + cur * PT * S + up * S;
         const double* tg = a.pd.target_traj + (size_t)t * S;
         const double av = kp2 * (tg[ipos] - xr[ipos]) + kd2 * (tg[ivel] - xr[ivel]);
         ufb = a.pd.squash ? umax * fast_tanh(av / umax) : av;
@@ -494,6 +560,8 @@ __global__ __launch_bounds__(RF_NT) void rollout_open_kernel(typename OpenArgsOf
         }
       }
     }
+    // (this path skips the barrier below, which is also what separates the input threads' read of the measurement row of step t from its
+    //  rewrite in step t + 1: harmless while the feedback form has no ragged lengths -- tl == T, the path is the last row's alone)
     if (t + 1 >= tl) continue;  // (uniform) nothing of this tile goes further: only the zero rows are left to write
     if (own) {
       double* zp = z + op * D;
@@ -677,19 +745,48 @@ extern "C" int mcp_rollout_open_rec(const mcp_model* model, const mcp_noise* noi
 }
 
 // ---- feedback form: launch, checks, entry ---------------------------------------------------------------------------------------
-template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC>
-static int launch_pd(const OpenArgsPd& a, hipStream_t st) {
-  const OpenLayout L = open_layout(PT, NEEDVAR, a.model.S, a.model.D, a.model.G, a.NpadMax, NEEDJAC, a.na);
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool PMS>
+static int launch_pd(const typename OpenArgsOf<true, PMS>::type& a, hipStream_t st) {
+  const OpenLayout L = open_layout(PT, NEEDVAR, a.model.S, a.model.D, a.model.G, a.NpadMax, NEEDJAC, a.na, PMS);
   const size_t lds = (size_t)L.total * sizeof(double);
   if (lds > MCP_LDS_LIMIT) return MCP_ERR_LIMIT;
-  MCP_ENSURE_MAX_LDS(rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, true>);
-  hipLaunchKernelGGL((rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, true>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
+  MCP_ENSURE_MAX_LDS(rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, true, PMS>);
+  hipLaunchKernelGGL((rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, true, PMS>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
 }
-template <int PT, bool NEEDVAR, bool NEEDJAC>
-static int launch_pd_deg(const OpenArgsPd& a, int maxdeg, hipStream_t st) {
-  return maxdeg == 0 ? launch_pd<PT, 0, NEEDVAR, NEEDJAC>(a, st) : launch_pd<PT, 2, NEEDVAR, NEEDJAC>(a, st);
+template <int PT, bool NEEDVAR, bool NEEDJAC, bool PMS>
+static int launch_pd_deg(const typename OpenArgsOf<true, PMS>::type& a, int maxdeg, hipStream_t st) {
+  return maxdeg == 0 ? launch_pd<PT, 0, NEEDVAR, NEEDJAC, PMS>(a, st) : launch_pd<PT, 2, NEEDVAR, NEEDJAC, PMS>(a, st);
+}
+// the tiles of open_dispatch: the feedback adds nothing to the LDS layout, the measurement one row [PT][S]
+template <bool PMS>
+static int launch_pd_tiles(const typename OpenArgsOf<true, PMS>::type& a, int maxdeg, bool wantvar, hipStream_t st) {
+  if (!a.jac) {
+    if (!a.sample && !wantvar) return launch_pd_deg<1, false, false, PMS>(a, maxdeg, st);
+    int rc = launch_pd_deg<16, true, false, PMS>(a, maxdeg, st);
+    if (rc == MCP_ERR_LIMIT) rc = launch_pd_deg<4, true, false, PMS>(a, maxdeg, st);
+    return rc;
+  }
+  if (!a.sample && !wantvar) return launch_pd_deg<1, false, true, PMS>(a, maxdeg, st);
+  int rc = launch_pd_deg<16, true, true, PMS>(a, maxdeg, st);
+  if (rc == MCP_ERR_LIMIT) rc = launch_pd_deg<4, true, true, PMS>(a, maxdeg, st);
+  if (rc == MCP_ERR_LIMIT) rc = launch_pd_deg<1, true, true, PMS>(a, maxdeg, st);
+  return rc;
+}
+
+// the measurement model against the model (host fields only).  Every component belongs to at most one pair, as position or as velocity:
+// the forward kernel gives a pair to the thread of its position, the sweep keeps one filter adjoint per position component
+static int pd_meas_check(const mcp_model* model, const mcp_meas* ms) {
+  if (ms->n < 0 || 2 * ms->n > model->S || ms->n > MCP_MAX_STATE) return MCP_ERR_ARG;
+  if (ms->n == 0) return MCP_OK;
+  if (!ms->meas || !(fabs(ms->a0) > 0.0) || !(model->Ts > 0.0)) return MCP_ERR_ARG;  // (a NaN a0 or Ts is refused too)
+  for (int i = 0; i < ms->n; ++i) {
+    if (ms->pos[i] < 0 || ms->pos[i] >= model->S || ms->vel[i] < 0 || ms->vel[i] >= model->S) return MCP_ERR_ARG;
+    for (int j = 0; j < ms->n; ++j)
+      if ((i != j && (ms->pos[i] == ms->pos[j] || ms->vel[i] == ms->vel[j])) || ms->pos[i] == ms->vel[j]) return MCP_ERR_ARG;
+  }
+  return MCP_OK;
 }
 
 // the descriptor against the model and the horizon (host fields only: the gains and the target are device memory).  pos / vel hold distinct
@@ -709,9 +806,8 @@ static int pd_policy_check(const mcp_model* model, const mcp_pd_policy* pd, int 
 // Closed-loop rollout under the PD law: replaces the loop of MC_PILCO.apply_policy (policy_learning/MC_PILCO.py:615-674) with
 // Policy.PD_controller.forward (policy_learning/Policy.py:437-449) as the policy, over Model_learning.get_next_state
 // (model_learning/Model_learning.py:210-229, 471-494, 685-718).  jac != NULL: the recording form (what autograd would keep of that loop).
-extern "C" int mcp_rollout_pd(const mcp_model* model, const mcp_pd_policy* pd, const mcp_noise* noise, int M, int T, int particle_pred,
-                              const double* x0, double* states, double* inputs, double* jac, double* mu, double* var, uint32_t* status,
-                              void* stream) {
+static int pd_dispatch(const mcp_model* model, const mcp_pd_policy* pd, const mcp_meas* ms, const mcp_noise* noise, int M, int T, int particle_pred,
+                       const double* x0, double* states, double* inputs, double* jac, double* mu, double* var, uint32_t* status, void* stream) {
   if (!model || !pd || !noise || !x0 || !states || !inputs || !status) return MCP_ERR_ARG;
   if (M <= 0 || T < 1) return MCP_ERR_ARG;
   if (model->S > MCP_MAX_STATE || model->U > MCP_MAX_INPUT || model->G > MCP_MAX_GP || model->D > MCP_MAX_GPDIM) return MCP_ERR_LIMIT;
@@ -720,7 +816,8 @@ extern "C" int mcp_rollout_pd(const mcp_model* model, const mcp_pd_policy* pd, c
   if (!model_ok(model)) return MCP_ERR_ARG;
   const int prc = pd_policy_check(model, pd, T);
   if (prc != MCP_OK) return prc;
-  OpenArgsPd a;
+  if (ms && pd_meas_check(model, ms) != MCP_OK) return MCP_ERR_ARG;
+  OpenArgsPdMeas a;
   a.model = *model;
   a.nz = *noise;
   a.M = M;
@@ -746,18 +843,26 @@ extern "C" int mcp_rollout_pd(const mcp_model* model, const mcp_pd_policy* pd, c
   a.pd = *pd;
   a.inputs = inputs;
   hipStream_t st = (hipStream_t)stream;
-  // the tiles of open_dispatch: the feedback adds nothing to the LDS layout
-  if (!jac) {
-    if (!a.sample && !var) return launch_pd_deg<1, false, false>(a, maxdeg, st);
-    int rc = launch_pd_deg<16, true, false>(a, maxdeg, st);
-    if (rc == MCP_ERR_LIMIT) rc = launch_pd_deg<4, true, false>(a, maxdeg, st);
-    return rc;
-  }
-  if (!a.sample && !var) return launch_pd_deg<1, false, true>(a, maxdeg, st);
-  int rc = launch_pd_deg<16, true, true>(a, maxdeg, st);
-  if (rc == MCP_ERR_LIMIT) rc = launch_pd_deg<4, true, true>(a, maxdeg, st);
-  if (rc == MCP_ERR_LIMIT) rc = launch_pd_deg<1, true, true>(a, maxdeg, st);
-  return rc;
+  if (!ms || ms->n == 0) return launch_pd_tiles<false>(a, maxdeg, var != nullptr, st);  // (the base part of `a`: mcp_rollout_pd's own kernels)
+  a.ms = *ms;
+  return launch_pd_tiles<true>(a, maxdeg, var != nullptr, st);
+}
+
+extern "C" int mcp_rollout_pd(const mcp_model* model, const mcp_pd_policy* pd, const mcp_noise* noise, int M, int T, int particle_pred,
+                              const double* x0, double* states, double* inputs, double* jac, double* mu, double* var, uint32_t* status,
+                              void* stream) {
+  return pd_dispatch(model, pd, nullptr, noise, M, T, particle_pred, x0, states, inputs, jac, mu, var, status, stream);
+}
+
+// Closed-loop rollout under the PD law evaluated on a simulated measurement: replaces the loop of MC_PILCO4PMS.apply_policy
+// (policy_learning/MC_PILCO.py:808-906: noisy positions, backward-difference velocities, the first-order filter) with
+// Policy.PD_controller.forward (policy_learning/Policy.py:437-449) as the policy, over Model_learning.get_next_state
+// (model_learning/Model_learning.py:210-229, 471-494, 685-718).  meas->n == 0: mcp_rollout_pd's kernels on the same arguments.
+extern "C" int mcp_rollout_pd_meas(const mcp_model* model, const mcp_pd_policy* pd, const mcp_meas* meas, const mcp_noise* noise, int M, int T,
+                                   int particle_pred, const double* x0, double* states, double* inputs, double* jac, double* mu, double* var,
+                                   uint32_t* status, void* stream) {
+  if (!meas) return MCP_ERR_ARG;
+  return pd_dispatch(model, pd, meas, noise, M, T, particle_pred, x0, states, inputs, jac, mu, var, status, stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -803,13 +908,29 @@ struct OpenBwdArgsPd : OpenBwdArgs {
   const double* g_inputs;  // [T][M][U] or NULL
   double* g_gains;         // [M][2][U] or NULL
 };
-template <bool FB>
+// MEASURED feedback form of the sweep (template PMS with FB, mcp_rollout_pd_meas_bwd): the PD law read y_r (ms.meas, brought by the loader),
+// so stage B' takes e = target_traj[r] - y_r and stage C receives the policy's pull ON THE MEASUREMENT,
+//   ybar_r[s] = - sqrt_kp[k]^2 abar_k (pos[k] == s) - sqrt_kd[k]^2 abar_k (vel[k] == s),
+// through the adjoint of the filter.  Per (trajectory, pair) two carries, both zero behind the last row, kept in LDS at the pair's position
+// component (the same lane writes and reads them, row after row):
+//   mvbar_r = ybar_r[v] - (a1/a0) mvbar_{r+1};   nvbar_r = (b0/a0) mvbar_r + (b1/a0) mvbar_{r+1};   npbar_r = ybar_r[p] + (nvbar_r - nvbar_{r+1}) / Ts
+//   r >= 1: lambda_r[p] += npbar_r (the true velocity gets nothing from the policy)
+//   r == 0: lambda_0[p] += ybar_0[p] - nvbar_1 / Ts;   lambda_0[v] += ybar_0[v] + ((b1 - a1)/a0) mvbar_1     (row 0 is measured true)
+// Components in no pair: lambda_r[s] += ybar_r[s], as in the plain feedback form.
+struct OpenBwdArgsPdMeas : OpenBwdArgsPd {
+  mcp_meas ms;
+};
+template <bool FB, bool PMS = false>
 struct OpenBwdArgsOf {
   typedef OpenBwdArgs type;
 };
 template <>
-struct OpenBwdArgsOf<true> {
+struct OpenBwdArgsOf<true, false> {
   typedef OpenBwdArgsPd type;
+};
+template <>
+struct OpenBwdArgsOf<true, true> {
+  typedef OpenBwdArgsPdMeas type;
 };
 #define OB_KMAX ((MCP_MAX_INPUT + 3) / 4)  // inputs per lane of the chain wave
 
@@ -817,8 +938,9 @@ struct OpenBwdLayout {
   int rec, xs, gs, lam, gd, gz, tab, total;  // offsets in doubles
   int rp;                                    // pitch of a trajectory's record row (odd: bank spread)
   int ul, gul, tgl, abl, ktab, gnl;          // feedback form: inputs | g_inputs | target row (double buffers) | abar | kpos, kvel | gains^2
+  int yml, car, mtab;                        // measured feedback form: measurement rows (double buffer) | the filter's carries | pvel, ppos
 };
-__host__ __device__ inline OpenBwdLayout open_bwd_layout(int S, int G, int D, bool fb = false, int U = 0) {
+__host__ __device__ inline OpenBwdLayout open_bwd_layout(int S, int G, int D, bool fb = false, int U = 0, bool pms = false) {
   OpenBwdLayout L;
   int o = 0;
   auto take = [&](int n) {
@@ -840,6 +962,9 @@ __host__ __device__ inline OpenBwdLayout open_bwd_layout(int S, int G, int D, bo
   L.abl = fb ? take(OB_PT * U) : 0;
   L.ktab = fb ? take(MCP_MAX_STATE) : 0;  // ints: kpos | kvel (per state component: the input that reads it as position / velocity, or -1)
   L.gnl = fb ? take(2 * MCP_MAX_INPUT) : 0;  // sqrt_kp^2 | sqrt_kd^2
+  L.yml = pms ? take(2 * OB_PT * S) : 0;
+  L.car = pms ? take(2 * OB_PT * S) : 0;     // [trajectory][position component]: mvbar | nvbar of the row behind
+  L.mtab = pms ? take(MCP_MAX_STATE) : 0;    // ints: pvel (per state component: the velocity of the pair it is the position of, or -1) | ppos (the converse)
   L.total = o;
   return L;
 }
@@ -847,12 +972,13 @@ __host__ __device__ inline OpenBwdLayout open_bwd_layout(int S, int G, int D, bo
 // orders this wave's LDS stores before its later LDS loads (the DS queue of a wave is in order; this drains it and stops the compiler)
 __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
-template <bool FB>
-__global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBwdArgsOf<FB>::type a) {
+template <bool FB, bool PMS = false>
+__global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBwdArgsOf<FB, PMS>::type a) {
+  static_assert(FB || !PMS, "the measurement model belongs to the feedback form");
   extern __shared__ double smem[];
   const int S = a.S, U = a.U, G = a.G, D = a.D, M = a.M, T = a.T, nna = a.nna, na = a.na;
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const OpenBwdLayout L = open_bwd_layout(S, G, D, FB, U);
+  const OpenBwdLayout L = open_bwd_layout(S, G, D, FB, U, PMS);
   const int GD = G * D, RP = L.rp;
   double* rec = smem + L.rec;
   double* xsl = smem + L.xs;
@@ -873,6 +999,10 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
   int* kpos = reinterpret_cast<int*>(smem + L.ktab);
   int* kvel = kpos + MCP_MAX_STATE;
   double* gnl = smem + L.gnl;
+  double* yml = smem + L.yml;  // (measured feedback form)
+  double* car = smem + L.car;
+  int* pvel = reinterpret_cast<int*>(smem + L.mtab);
+  int* ppos = pvel + MCP_MAX_STATE;
   const int m0 = blockIdx.x * OB_PT;
 
   if (tid < S) {  // which GP a component integrates, as the forward kernel decides it
@@ -900,6 +1030,15 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
       kpos[s] = kp;
       kvel[s] = kv;
     }
+    if constexpr (PMS) {
+      int pv = -1, pp = -1;
+      for (int i = 0; i < a.ms.n; ++i) {
+        if (a.ms.pos[i] == s) pv = a.ms.vel[i];
+        if (a.ms.vel[i] == s) pp = a.ms.pos[i];
+      }
+      pvel[s] = pv;
+      ppos[s] = pp;
+    }
   }
   if constexpr (FB) {
     if (tid >= 64 + OB_PT && tid < 64 + OB_PT + U) {
@@ -914,6 +1053,8 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
     lenl[p] = m0 + p < M ? (a.lengths ? imin(imax(a.lengths[m0 + p], 1), T) : T) : 0;
   }
   for (int it = tid; it < 2 * OB_PT * S; it += OB_NT) lam[it] = 0.0;
+  if constexpr (PMS)
+    for (int it = tid; it < 2 * OB_PT * S; it += OB_NT) car[it] = 0.0;
   __syncthreads();
   int tl = 1;
   for (int p = 0; p < OB_PT; ++p) tl = imax(tl, lenl[p]);
@@ -935,6 +1076,8 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
       const int len = lenl[p];
       if (r <= len - 1) gsl[(b * OB_PT + p) * S + s] = a.g_states[((size_t)r * M + m0 + p) * S + s];
       if (r < len - (FB ? 0 : 1)) xsl[(b * OB_PT + p) * S + s] = a.states[((size_t)r * M + m0 + p) * S + s];
+      if constexpr (PMS)
+        if (r <= len - 1) yml[(b * OB_PT + p) * S + s] = a.ms.meas[((size_t)r * M + m0 + p) * S + s];
     }
     if constexpr (FB) {
       for (int it = l; it < OB_PT * U; it += 64) {
@@ -982,6 +1125,8 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
       const double* xc = xsl + (b * OB_PT + p) * S;
       const double* gc = gsl + (b * OB_PT + p) * S;
       const bool active = r < len - 1;
+      const double* ec = PMS ? yml + (b * OB_PT + p) * S : xc;  // what the PD law read of row r
+      (void)ec;
       // stage A: the adjoints of the increments
       for (int g = q; g < G; g += 4) {
         double acc = 0.0;
@@ -1014,8 +1159,8 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
                 ab = gu * (1.0 - th * th);
               }
               abl[p * U + k] = ab;
-              gkp[i] += 2.0 * fkp[i] * (tg[fpos[i]] - xc[fpos[i]]) * ab;
-              gkd[i] += 2.0 * fkd[i] * (tg[fvel[i]] - xc[fvel[i]]) * ab;
+              gkp[i] += 2.0 * fkp[i] * (tg[fpos[i]] - ec[fpos[i]]) * ab;
+              gkd[i] += 2.0 * fkd[i] * (tg[fvel[i]] - ec[fvel[i]]) * ab;
             }
           }
         }
@@ -1038,11 +1183,40 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
             v += gzl[p * D + nna + zang[s]] * cs - gzl[p * D + nna + na + zang[s]] * sn;
           }
         }
-        if constexpr (FB) {
+        if constexpr (FB && !PMS) {
           if (r <= len - 1) {
             const int kp = kpos[s], kv = kvel[s];
             if (kp >= 0) v -= gnl[kp] * abl[p * U + kp];
             if (kv >= 0) v -= gnl[MCP_MAX_INPUT + kv] * abl[p * U + kv];
+          }
+        }
+        if constexpr (PMS) {
+          if (r <= len - 1) {
+            auto ybar = [&](int c) {  // the policy's pull on component c of the measurement
+              const int kp = kpos[c], kv = kvel[c];
+              double y = 0.0;
+              if (kp >= 0) y -= gnl[kp] * abl[p * U + kp];
+              if (kv >= 0) y -= gnl[MCP_MAX_INPUT + kv] * abl[p * U + kv];
+              return y;
+            };
+            const int pv = pvel[s], pp = ppos[s];
+            if (pv >= 0) {  // a measured position: the filter's adjoint of its pair
+              double* cr = car + (p * S + s) * 2;
+              const double mvn = cr[0], nvn = cr[1];
+              if (r >= 1) {
+                const double mvb = ybar(pv) - (a.ms.a1 / a.ms.a0) * mvn;
+                const double nvb = (a.ms.b0 / a.ms.a0) * mvb + (a.ms.b1 / a.ms.a0) * mvn;
+                v += ybar(s) + (nvb - nvn) / a.Ts;
+                cr[0] = mvb;
+                cr[1] = nvb;
+              } else {
+                v += ybar(s) - nvn / a.Ts;
+              }
+            } else if (pp >= 0) {  // a measured velocity: seen true in row 0 only, where it also started both histories
+              if (r == 0) v += ybar(s) + ((a.ms.b1 - a.ms.a1) / a.ms.a0) * car[(p * S + pp) * 2];
+            } else {
+              v += ybar(s);
+            }
           }
         }
         lamn[s] = v;
@@ -1116,9 +1290,9 @@ extern "C" int mcp_rollout_open_bwd(const mcp_model* model, int M, int T, const 
 // Reverse-time sweep of the closed loop under the PD law: replaces autograd's backward (MC_PILCO.py:522) through the loop of
 // MC_PILCO.apply_policy (policy_learning/MC_PILCO.py:615-674), Policy.PD_controller.forward (policy_learning/Policy.py:437-449) and
 // get_next_state with its integrators (model_learning/Model_learning.py:210-229, 471-494, 685-718), from the record alone.
-extern "C" int mcp_rollout_pd_bwd(const mcp_model* model, const mcp_pd_policy* pd, int M, int T, const double* states, const double* inputs,
-                                  const double* jac, const double* g_states, const double* g_inputs, double* g_gains, double* g_x0,
-                                  void* stream) {
+static int pd_bwd_dispatch(const mcp_model* model, const mcp_pd_policy* pd, const mcp_meas* ms, int M, int T, const double* states,
+                           const double* inputs, const double* jac, const double* g_states, const double* g_inputs, double* g_gains, double* g_x0,
+                           void* stream) {
   if (!model || !pd || !states || !inputs || !g_states || (!jac && T > 1)) return MCP_ERR_ARG;
   if (M <= 0 || T < 1) return MCP_ERR_ARG;
   if (model->S > MCP_MAX_STATE || model->U > MCP_MAX_INPUT || model->G > MCP_MAX_GP || model->D > MCP_MAX_GPDIM) return MCP_ERR_LIMIT;
@@ -1133,8 +1307,9 @@ extern "C" int mcp_rollout_pd_bwd(const mcp_model* model, const mcp_pd_policy* p
     if (model->vel[g] < 0 || model->vel[g] >= model->S || model->not_vel[g] < -1 || model->not_vel[g] >= model->S) return MCP_ERR_ARG;
   const int prc = pd_policy_check(model, pd, T);
   if (prc != MCP_OK) return prc;
+  if (ms && pd_meas_check(model, ms) != MCP_OK) return MCP_ERR_ARG;
   if (!g_x0 && !g_gains) return MCP_OK;  // nothing asked for
-  OpenBwdArgsPd a;
+  OpenBwdArgsPdMeas a;
   memset(&a, 0, sizeof(a));
   a.S = model->S, a.U = model->U, a.G = model->G, a.D = model->D, a.nna = model->n_not_angle, a.na = model->n_angle, a.M = M, a.T = T;
   for (int i = 0; i < MCP_MAX_STATE; ++i) a.angle[i] = model->angle[i], a.not_angle[i] = model->not_angle[i];
@@ -1150,11 +1325,36 @@ extern "C" int mcp_rollout_pd_bwd(const mcp_model* model, const mcp_pd_policy* p
   a.inputs = inputs;
   a.g_inputs = g_inputs;
   a.g_gains = g_gains;
-  const OpenBwdLayout L = open_bwd_layout(a.S, a.G, a.D, true, a.U);  // (at every compiled limit at once: 89 KB)
+  const bool pms = ms && ms->n > 0;
+  const OpenBwdLayout L = open_bwd_layout(a.S, a.G, a.D, true, a.U, pms);  // (at every compiled limit at once: 89 KB, measured form 98 KB)
   const size_t lds = (size_t)L.total * sizeof(double);
   if (lds > MCP_LDS_LIMIT) return MCP_ERR_LIMIT;
-  MCP_ENSURE_MAX_LDS(rollout_open_bwd_kernel<true>);
-  hipLaunchKernelGGL(rollout_open_bwd_kernel<true>, dim3((M + OB_PT - 1) / OB_PT), dim3(OB_NT), lds, (hipStream_t)stream, a);
+  if (pms) {
+    a.ms = *ms;
+    MCP_ENSURE_MAX_LDS((rollout_open_bwd_kernel<true, true>));
+    hipLaunchKernelGGL((rollout_open_bwd_kernel<true, true>), dim3((M + OB_PT - 1) / OB_PT), dim3(OB_NT), lds, (hipStream_t)stream, a);
+  } else {
+    const OpenBwdArgsPd& ab = a;  // (the base part: mcp_rollout_pd_bwd's own kernel)
+    MCP_ENSURE_MAX_LDS(rollout_open_bwd_kernel<true>);
+    hipLaunchKernelGGL(rollout_open_bwd_kernel<true>, dim3((M + OB_PT - 1) / OB_PT), dim3(OB_NT), lds, (hipStream_t)stream, ab);
+  }
   MCP_LAUNCH_CHECK();
   return MCP_OK;
+}
+
+extern "C" int mcp_rollout_pd_bwd(const mcp_model* model, const mcp_pd_policy* pd, int M, int T, const double* states, const double* inputs,
+                                  const double* jac, const double* g_states, const double* g_inputs, double* g_gains, double* g_x0,
+                                  void* stream) {
+  return pd_bwd_dispatch(model, pd, nullptr, M, T, states, inputs, jac, g_states, g_inputs, g_gains, g_x0, stream);
+}
+
+// Reverse-time sweep of the closed loop under the PD law on the simulated measurement: replaces autograd's backward (MC_PILCO.py:522)
+// through the loop of MC_PILCO4PMS.apply_policy (policy_learning/MC_PILCO.py:808-906, the filter recursion included),
+// Policy.PD_controller.forward (policy_learning/Policy.py:437-449) and get_next_state with its integrators
+// (model_learning/Model_learning.py:210-229, 471-494, 685-718), from the record and meas->meas alone.  meas->n == 0: mcp_rollout_pd_bwd's kernel.
+extern "C" int mcp_rollout_pd_meas_bwd(const mcp_model* model, const mcp_pd_policy* pd, const mcp_meas* meas, int M, int T, const double* states,
+                                       const double* inputs, const double* jac, const double* g_states, const double* g_inputs, double* g_gains,
+                                       double* g_x0, void* stream) {
+  if (!meas) return MCP_ERR_ARG;
+  return pd_bwd_dispatch(model, pd, meas, M, T, states, inputs, jac, g_states, g_inputs, g_gains, g_x0, stream);
 }

@@ -128,6 +128,10 @@ _SIGS = {
     "mcp_rollout_pd": (C.c_int, [C.POINTER(Model), C.POINTER(PDPolicy), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr,
                                  dptr, dptr, dptr]),
     "mcp_rollout_pd_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(PDPolicy), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
+    "mcp_rollout_pd_meas": (C.c_int, [C.POINTER(Model), C.POINTER(PDPolicy), C.POINTER(Meas), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr,
+                                      dptr, dptr, dptr, dptr, dptr, dptr]),
+    "mcp_rollout_pd_meas_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(PDPolicy), C.POINTER(Meas), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr,
+                                          dptr, dptr]),
     "mcp_rollout_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(Policy), C.POINTER(Noise), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr,
                                   dptr, dptr, dptr, dptr, dptr, C.c_size_t, dptr]),
     "mcp_rollout_fwd_ex": (C.c_int, [C.POINTER(Model), C.POINTER(Policy), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr, dptr,

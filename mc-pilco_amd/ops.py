@@ -351,7 +351,8 @@ class NoiseSpec:
 class MeasSpec:
     """Measurement model of ``MC_PILCO4PMS.apply_policy`` (MC_PILCO.py:808-906) for the fused rollout: the policy is fed
     noisy positions and backward-difference velocities smoothed by the first-order filter (b, a) = butter(1, fc).
-    ``pos_noise`` [T-1,M,n] standard normals on the GPU (parity mode) or None (in-kernel Philox)."""
+    ``pos_noise`` [T-1,M,n] standard normals on the GPU (parity mode) or None (in-kernel Philox).  ``measured``: an OUTPUT -- ``rollout_pd``
+    leaves the measured states [T,M,S] of its last launch with this spec there."""
 
     pos: Sequence[int]
     vel: Sequence[int]
@@ -359,6 +360,7 @@ class MeasSpec:
     b: Sequence[float]
     a: Sequence[float]
     pos_noise: Optional[torch.Tensor] = None
+    measured: Optional[torch.Tensor] = None
 
     def fill(self, m, T, M, meas_buf):
         n = len(self.pos)
@@ -639,29 +641,40 @@ class PackedPD:
         return c
 
 
-def _rollout_pd_launch(model, pd, kp, kd, noise, x0, T, particle_pred, status, record):
+def _rollout_pd_launch(model, pd, kp, kd, noise, x0, T, particle_pred, status, record, meas=None):
     M, dev = int(x0.shape[0]), model.device
     states = torch.empty(T, M, model.S, dtype=DT, device=dev)
     inputs = torch.empty(T, M, model.U, dtype=DT, device=dev)
     jac = torch.empty(T - 1, M, model.G, model.D, dtype=DT, device=dev) if (record and T > 1) else None
     pc, nz = pd.to_c(kp, kd), noise.to_c()
-    abi.check(abi.lib().mcp_rollout_pd(_mc(model), C.byref(pc), C.byref(nz), M, T, int(bool(particle_pred)), abi.ptr(x0), abi.ptr(states),
-                                       abi.ptr(inputs), abi.ptr(jac), None, None, abi.ptr(status), abi.stream()), "mcp_rollout_pd")
+    if meas is None:
+        abi.check(abi.lib().mcp_rollout_pd(_mc(model), C.byref(pc), C.byref(nz), M, T, int(bool(particle_pred)), abi.ptr(x0), abi.ptr(states),
+                                           abi.ptr(inputs), abi.ptr(jac), None, None, abi.ptr(status), abi.stream()), "mcp_rollout_pd")
+        return states, inputs, jac
+    meas_buf = meas.measured = torch.empty(T, M, model.S, dtype=DT, device=dev)  # (allocated as rollout_forward_raw allocates it)
+    mc = abi.Meas()
+    meas.fill(mc, T, M, meas_buf)
+    abi.check(abi.lib().mcp_rollout_pd_meas(_mc(model), C.byref(pc), C.byref(mc), C.byref(nz), M, T, int(bool(particle_pred)), abi.ptr(x0),
+                                            abi.ptr(states), abi.ptr(inputs), abi.ptr(jac), None, None, abi.ptr(status), abi.stream()),
+              "mcp_rollout_pd_meas")
     return states, inputs, jac
 
 
 class RolloutPDFunction(torch.autograd.Function):
     """(x0 [M,S], sqrt_kp [U], sqrt_kd [U]) -> states [T,M,S], inputs [T,M,U] through the recording form of the fused closed loop under the
     PD law (mcp_rollout_pd); backward is the reverse-time sweep mcp_rollout_pd_bwd over the record, with both upstream gradients.  The
-    per-trajectory gain gradients are added in torch's fixed order; the GP model is frozen."""
+    per-trajectory gain gradients are added in torch's fixed order; the GP model is frozen.  With a measurement model (``meas``) the two
+    launches are mcp_rollout_pd_meas / mcp_rollout_pd_meas_bwd; the measured states [T,M,S] the forward launch wrote (``meas.measured``) are
+    saved with the record and handed to the sweep."""
 
     @staticmethod
-    def forward(ctx, x0, kp, kd, model, pd, noise, T, particle_pred, status):
-        states, inputs, jac = _rollout_pd_launch(model, pd, kp, kd, noise, x0, T, particle_pred, status, True)
-        ctx.model, ctx.pd, ctx.has_jac = model, pd, jac is not None
+    def forward(ctx, x0, kp, kd, model, pd, noise, T, particle_pred, status, meas):
+        states, inputs, jac = _rollout_pd_launch(model, pd, kp, kd, noise, x0, T, particle_pred, status, True, meas)
+        meas_buf = None if meas is None else meas.measured
+        ctx.model, ctx.pd, ctx.has_jac, ctx.meas = model, pd, jac is not None, meas
         ctx.set_materialize_grads(False)
         # (saved tensors: autograd refuses a backward after an in-place change of any of them -- the record, or a gain stepped too early)
-        ctx.save_for_backward(*((states, inputs, kp, kd) + ((jac,) if jac is not None else ())))
+        ctx.save_for_backward(*((states, inputs, kp, kd) + ((jac,) if jac is not None else ()) + ((meas_buf,) if meas is not None else ())))
         return states, inputs
 
     @staticmethod
@@ -669,7 +682,7 @@ class RolloutPDFunction(torch.autograd.Function):
         saved = ctx.saved_tensors
         states, inputs, kp, kd = saved[:4]
         jac = saved[4] if ctx.has_jac else None
-        model, pd = ctx.model, ctx.pd
+        model, pd, meas = ctx.model, ctx.pd, ctx.meas
         T, M = int(states.shape[0]), int(states.shape[1])
         gs = torch.zeros_like(states) if g_states is None else g_states.to(dtype=DT).contiguous()
         gi = None if g_inputs is None else g_inputs.to(dtype=DT).contiguous()
@@ -677,17 +690,28 @@ class RolloutPDFunction(torch.autograd.Function):
         g_x0 = torch.empty(M, model.S, dtype=DT, device=states.device) if want_x0 else None
         g_gains = torch.empty(M, 2, model.U, dtype=DT, device=states.device) if want_g else None
         pc = pd.to_c(kp, kd)
-        abi.check(abi.lib().mcp_rollout_pd_bwd(_mc(model), C.byref(pc), M, T, abi.ptr(states), abi.ptr(inputs), abi.ptr(jac), abi.ptr(gs), abi.ptr(gi),
-                                               abi.ptr(g_gains), abi.ptr(g_x0), abi.stream()), "mcp_rollout_pd_bwd")
+        if meas is None:
+            abi.check(abi.lib().mcp_rollout_pd_bwd(_mc(model), C.byref(pc), M, T, abi.ptr(states), abi.ptr(inputs), abi.ptr(jac), abi.ptr(gs), abi.ptr(gi),
+                                                   abi.ptr(g_gains), abi.ptr(g_x0), abi.stream()), "mcp_rollout_pd_bwd")
+        else:
+            mc = abi.Meas()
+            meas.fill(mc, T, M, saved[-1])
+            abi.check(abi.lib().mcp_rollout_pd_meas_bwd(_mc(model), C.byref(pc), C.byref(mc), M, T, abi.ptr(states), abi.ptr(inputs), abi.ptr(jac),
+                                                        abi.ptr(gs), abi.ptr(gi), abi.ptr(g_gains), abi.ptr(g_x0), abi.stream()),
+                      "mcp_rollout_pd_meas_bwd")
         gg = g_gains.sum(0) if want_g else None  # the trajectories' gradients added in torch's fixed order
-        return (g_x0, gg[0] if ctx.needs_input_grad[1] else None, gg[1] if ctx.needs_input_grad[2] else None, None, None, None, None, None, None)
+        return (g_x0, gg[0] if ctx.needs_input_grad[1] else None, gg[1] if ctx.needs_input_grad[2] else None, None, None, None, None, None, None,
+                None)
 
 
-def rollout_pd(model: PackedModel, pd: PackedPD, noise: Optional[NoiseSpec], x0, T, particle_pred=True, status=None):
+def rollout_pd(model: PackedModel, pd: PackedPD, noise: Optional[NoiseSpec], x0, T, particle_pred=True, status=None, meas: Optional[MeasSpec] = None):
     """Closed-loop rollout under a PD controller in ONE launch: x0 [M,S] -> states [T,M,S], inputs [T,M,U] (row T - 1 included) and the
     status word.  ``noise``: an eps buffer [T-1,M,G] or Philox by seed / call / particle_offset (``particle_pred``), as ``rollout_open``.
     With gradients enabled and x0 or a gain requiring grad the recording launch runs and backward is the fused sweep (gradients to
-    ``sqrt_Kp_gains``, ``sqrt_Kd_gains`` and x0); otherwise nothing is recorded.  The same states and inputs, bit for bit, either way."""
+    ``sqrt_Kp_gains``, ``sqrt_Kd_gains`` and x0); otherwise nothing is recorded.  The same states and inputs, bit for bit, either way.
+    ``meas``: a measurement model between the particles and the PD law (partially measurable systems, as in ``rollout``); the measured
+    states [T,M,S] the law was evaluated on are left in ``meas.measured`` (not differentiable).  None: the law sees the true state, and
+    the calls made are the ones made without the argument.  The return has the same three elements either way."""
     if not isinstance(x0, torch.Tensor) or not x0.is_cuda or not pd.sqrt_kp.is_cuda or not pd.sqrt_kd.is_cuda:
         raise RuntimeError("rollout_pd operates on GPU memory only (x0 and the gains must be GPU tensors); there is no CPU path")
     dev, T = model.device, int(T)
@@ -708,10 +732,10 @@ def rollout_pd(model: PackedModel, pd: PackedPD, noise: Optional[NoiseSpec], x0,
         raise RuntimeError("status must be a one-element int32 tensor on the rollout's device")
     kp, kd = pd.gains()
     if torch.is_grad_enabled() and (x0c.requires_grad or kp.requires_grad or kd.requires_grad):
-        states, inputs = RolloutPDFunction.apply(x0c, kp.contiguous(), kd.contiguous(), model, pd, noise, T, bool(particle_pred), status)
+        states, inputs = RolloutPDFunction.apply(x0c, kp.contiguous(), kd.contiguous(), model, pd, noise, T, bool(particle_pred), status, meas)
         return states, inputs, status
     states, inputs, _ = _rollout_pd_launch(model, pd, kp.detach().contiguous(), kd.detach().contiguous(), noise, x0c.detach(), T, particle_pred,
-                                           status, False)
+                                           status, False, meas)
     return states, inputs, status
 
 

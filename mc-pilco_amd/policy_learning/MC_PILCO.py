@@ -188,15 +188,16 @@ class MC_PILCO(torch.nn.Module):
                                                              particles_init_up_bound, particles_init_low_bound, flg_particles_init_multi_gauss,
                                                              self._m_total), 0)
         pol, ml = self.control_policy, self.model_learning
+        self.last_feedback_fused = False  # (reset before every branch: a run under another policy must not leave an earlier True standing)
         if isinstance(pol, _Policy.Sum_of_gaussians) and _has_fused_layout(ml):
             noise, p = self._rollout_noise(M, T, p_dropout)
             states, inputs, status = ops.rollout(ml.packed(), pol.packed(), noise, x0, T, p, gp_sharding=self.gp_sharding)
             self.last_status = status
             return states, inputs
-        self.last_feedback_fused = False
-        if (self.fused_feedback and world == 1 and isinstance(pol, _Policy.PD_controller) and _has_fused_layout(ml)
-                and pol.fusable(ml.packed(), T)):
-            # the closed loop under the PD law, one launch (and one sweep in backward): the eps draws of _rollout_noise, no dropout masks
+        if self.fused_feedback and isinstance(pol, _Policy.PD_controller) and _has_fused_layout(ml) and pol.fusable(ml.packed(), T):
+            # the closed loop under the PD law, one launch (and one sweep in backward): the eps draws of _rollout_noise, no dropout masks.
+            # Sharded: the eps buffers are drawn for the whole swarm and sliced, Philox counts by global particle; the gains' gradients
+            # reach the step's all-reduce through their .grad (_cost_backward)
             states, inputs, status = ops.rollout_pd(ml.packed(), pol.packed(), self._feedback_noise(T), x0, T)
             self.last_status = status
             self.last_feedback_fused = True
@@ -206,7 +207,8 @@ class MC_PILCO(torch.nn.Module):
         if world > 1:
             # its noise (torch draws inside get_next_state / the policy's dropout) is per LOCAL particle: identically seeded ranks
             # would simulate correlated shards, not the particles one GPU would
-            raise NotImplementedError("particle sharding needs the fused rollout (Sum_of_gaussians policy + a model with a fused layout)")
+            raise NotImplementedError("particle sharding needs the fused rollout (Sum_of_gaussians or PD_controller policy + a model with a "
+                                      "fused layout)")
         xs = [x0]
         us = [pol(x0, t=0, p_dropout=p_dropout)]
         for t in range(1, T):
@@ -866,7 +868,8 @@ class MC_PILCO4PMS(MC_PILCO):
     noise, velocities by backward difference of the noisy positions, smoothed online by a first-order Butterworth filter
     (``filtering_dict["fc"]``).  With the speed-integration models and the RBF policies the rollout is the same single fused
     launch as ``MC_PILCO.apply_policy``: the kernels carry the filter's states per particle and the reverse sweep its adjoint
-    recursion (``mcp_meas``).  ``fused = False`` (or any other model / policy object) runs step by step on the posterior and
+    recursion (``mcp_meas``); a trainable ``PD_controller`` runs on its own fused launch and sweep with the same measurement model
+    (``mcp_rollout_pd_meas``; ``fused_feedback = False``: the step loop).  ``fused = False`` (or any other model / policy object) runs step by step on the posterior and
     policy operators with the filter as torch device ops.
     """
 
@@ -903,6 +906,7 @@ class MC_PILCO4PMS(MC_PILCO):
                                                             self._m_total), 0)
         b, a = signal.butter(1, self.filtering_dict["fc"])
         pos, vel = list(self.pos_indeces), list(self.vel_indeces)
+        self.last_feedback_fused = False  # (reset before every branch, as in MC_PILCO.apply_policy)
         if self.fused and isinstance(pol, _Policy.Sum_of_gaussians) and _has_fused_layout(ml):
             # one fused launch: the kernels carry the measurement filter's states per particle (mcp_meas)
             p = float(p_dropout) if getattr(pol, "flg_drop", True) else 0.0
@@ -932,9 +936,34 @@ class MC_PILCO4PMS(MC_PILCO):
             states, inputs, status = ops.rollout(model, pol.packed(), noise, x, T, p, meas=meas, gp_sharding=self.gp_sharding)
             self.last_status = status
             return states, inputs
+        if self.fused and self.fused_feedback and isinstance(pol, _Policy.PD_controller) and _has_fused_layout(ml):
+            model = ml.packed()
+            if getattr(model, "is_delta", False) and model.Ts != float(self.T_sampling):
+                model = ml.packed(T_sampling=self.T_sampling)  # (a delta-state model has no Ts: the measured velocities need one)
+            if pol.fusable(model, T):
+                # the closed loop under the PD law on the simulated measurement, one launch (and one sweep in backward)
+                G = ml.num_gp
+                self._rollout_calls += 1
+                if ref:  # the reference's draw order per step: eps_t, position noise; no mask (whole swarm, then this rank's slice)
+                    Mt = self._m_total
+                    eps, pn = [], []
+                    for _ in range(1, T):
+                        eps.append(torch.empty(Mt, G, dtype=self.dtype).normal_())
+                        pn.append(torch.randn(Mt, len(pos), dtype=self.dtype))
+                    stack = lambda l, w: self._shard_slice(torch.stack(l) if l else torch.zeros(0, Mt, w, dtype=self.dtype), 1).to(self.device).contiguous()
+                    noise, pos_noise = ops.NoiseSpec(eps=stack(eps, G)), stack(pn, len(pos))
+                else:
+                    noise, pos_noise = self._philox_noise(), None
+                meas = ops.MeasSpec(pos=pos, vel=vel, std_pos=[float(v) for v in np.asarray(self.std_meas_noise_sim)[pos]], b=b, a=a,
+                                    pos_noise=pos_noise)
+                states, inputs, status = ops.rollout_pd(model, pol.packed(), noise, x, T, meas=meas)
+                self.last_status = status
+                self.last_feedback_fused = True
+                return states, inputs
         self.last_status = None  # (no fused launch)
         if world > 1:  # (per-LOCAL-particle torch draws: identically seeded ranks would simulate correlated shards)
-            raise NotImplementedError("particle sharding needs the fused rollout (fused=True, Sum_of_gaussians policy, a model with a fused layout)")
+            raise NotImplementedError("particle sharding needs the fused rollout (fused=True, Sum_of_gaussians or PD_controller policy, a model "
+                                      "with a fused layout)")
         std_pos = torch.tensor(np.asarray(self.std_meas_noise_sim)[pos], dtype=self.dtype, device=self.device)
         saved_mode = getattr(pol, "noise_mode", None)
         if ref and saved_mode is not None:

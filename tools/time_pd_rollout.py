@@ -2,12 +2,17 @@
 backward -- fused (ops.rollout_pd: one launch, one sweep) and with ``fused_feedback = False`` (the step loop on get_next_state with autograd
 through it: the code before the fused form, line for line), in the same run.
 
-    python tools/time_pd_rollout.py [--blocks 5] [--reps 3] [--step-blocks 3]
+    python tools/time_pd_rollout.py [--blocks 5] [--reps 3] [--step-blocks 3] [--pms]
 
 Shapes: the UR5 script shape (6 GPs, D = 24, N = 400, M = 200, T = 200) and a two-joint arm (2 GPs, D = 8, N = 300, M = 400, T = 150).
 Events around the step, `reps` steps per block, median over the blocks; the step path runs one step per block.  Also
 counts the device launches of one step of either path (torch profiler), times the two fused launches alone, and -- for comparison --
 ``mcp_rollout_fwd`` with the shape's Sum_of_gaussians policy at the same M and T where the workload table has one.  One JSON line per shape.
+
+``--pms``: the same two steps through MC_PILCO4PMS.apply_policy (every joint's position measured with noise, velocities by backward
+differences through the first-order filter, fc = 0.3): the fused launch and sweep with the measurement model (ops.rollout_pd(meas=...))
+against ``fused_feedback = False`` -- the step loop with the filter as torch ops -- in the same run; the step and launch counts only, plus
+``fused_not_slower`` (the medians compared; the tool fails when it is false).
 """
 import argparse
 import contextlib
@@ -78,7 +83,7 @@ def arm2_data(n, Ts, seed=3):
     return x + 1e-3 * rs.randn(n + 1, 4), u
 
 
-def build_object(shape, dev):
+def build_object(shape, dev, pms=False):
     if shape == "ur5_script":
         c, N, M, T = sy.UR5, 400, 200, 200
         rolls = sy.ur5_rollouts(n_roll=2, seed=1)
@@ -109,14 +114,19 @@ def build_object(shape, dev):
         tg = torch.as_tensor(target, dtype=DT).to(dev).contiguous()
         ppar = dict(state_dim=S, input_dim=U, sqrt_Kp_gains=1.0 * np.ones(U), sqrt_Kd_gains=0.5 * np.ones(U), target_traj=tg, flg_squash=True,
                     u_max=u_max, flg_trainable=True, dtype=DT, device=dev)
-        obj = MC_PILCO.MC_PILCO(T_sampling=c["Ts"], state_dim=S, input_dim=U, f_sim=lambda y, t, u: None, f_model_learning=lambda **kw: ml,
-                                model_learning_par={}, f_rand_exploration_policy=Policy.Random_exploration,
-                                rand_exploration_policy_par=dict(state_dim=S, input_dim=U, u_max=1.0, dtype=DT),
-                                f_control_policy=Policy.PD_controller, control_policy_par=ppar,
-                                f_cost_function=Cost_function.Expected_saturated_distance,
-                                cost_function_par=dict(target_state=torch.zeros(S, dtype=DT, device=dev), lengthscales=torch.ones(S, dtype=DT, device=dev),
-                                                       active_dims=np.arange(S)),
-                                log_path=None, dtype=DT, device=dev)
+        common = dict(T_sampling=c["Ts"], state_dim=S, input_dim=U, f_sim=lambda y, t, u: None, f_model_learning=lambda **kw: ml,
+                      model_learning_par={}, f_rand_exploration_policy=Policy.Random_exploration,
+                      rand_exploration_policy_par=dict(state_dim=S, input_dim=U, u_max=1.0, dtype=DT),
+                      f_control_policy=Policy.PD_controller, control_policy_par=ppar,
+                      f_cost_function=Cost_function.Expected_saturated_distance,
+                      cost_function_par=dict(target_state=torch.zeros(S, dtype=DT, device=dev), lengthscales=torch.ones(S, dtype=DT, device=dev),
+                                             active_dims=np.arange(S)),
+                      log_path=None, dtype=DT, device=dev)
+        if pms:  # positions 0..U-1 measured with 1e-3 of noise, their velocities S/2.. derived
+            obj = MC_PILCO.MC_PILCO4PMS(pos_indeces=list(range(U)), vel_indeces=list(range(S // 2, S // 2 + U)), std_meas_noise=1e-3 * np.ones(S),
+                                        filtering_dict={"fc": 0.3}, **common)
+        else:
+            obj = MC_PILCO.MC_PILCO(**common)
     sim = dict(particles_initial_state_mean=tg[0].clone(), particles_initial_state_var=1e-4 * torch.ones(S, dtype=DT, device=dev),
                flg_particles_init_uniform=False, particles_init_up_bound=None, particles_init_low_bound=None, flg_particles_init_multi_gauss=False,
                num_particles=M, T_control=T)
@@ -129,10 +139,11 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--step-blocks", type=int, default=3)
     ap.add_argument("--shapes", default="ur5_script,arm2")
+    ap.add_argument("--pms", action="store_true", help="time MC_PILCO4PMS (the PD law on a simulated measurement) instead of MC_PILCO")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     for shape in args.shapes.split(","):
-        obj, sim, N, M, T = build_object(shape, dev)
+        obj, sim, N, M, T = build_object(shape, dev, pms=args.pms)
         pol, pm = obj.control_policy, obj.model_learning.packed()
         gen = torch.Generator(device=dev).manual_seed(1)
         w = torch.randn(T, M, pm.S, dtype=DT, device=dev, generator=gen)
@@ -150,6 +161,16 @@ def main():
         out["fused_step_ms"] = median_ms(step, args.blocks, args.reps)
         assert obj.last_feedback_fused and int(obj.last_status.item()) == 0
         out["fused_launches"] = launches(step)
+        if args.pms:
+            out["class"] = "MC_PILCO4PMS"
+            obj.fused_feedback = False
+            out["step_path_step_ms"] = median_ms(step, args.step_blocks, 1)
+            assert not obj.last_feedback_fused
+            out["step_path_launches"] = launches(step)
+            out["fused_not_slower"] = out["fused_step_ms"][0] <= out["step_path_step_ms"][0]  # medians of the same run
+            print(json.dumps(out), flush=True)
+            assert out["fused_not_slower"], "the fused step is slower than the step loop timed in the same run"
+            continue
         x0 = obj.sample_initial_particles(sim["particles_initial_state_mean"], sim["particles_initial_state_var"], False, None, None, False, M)
         with torch.no_grad():
             out["fused_fwd_plain_ms"] = median_ms(lambda: ops.rollout_pd(pm, pol.packed(), ops.NoiseSpec(seed=1, call=1), x0, T), args.blocks, args.reps)
