@@ -77,10 +77,20 @@ class Expected_cost(torch.nn.modules.loss._Loss):
 class _HipExpectedCost(Expected_cost):
     def __init__(self):
         super().__init__(None)
-        self._packed = None
+        self._packed = None   # the descriptor of the last evaluation
+        self._packs = {}      # every descriptor made so far, by what packed_for keys it with
 
-    def _pack(self, states):
+    def _pack(self, states, trial_index=None):
         raise NotImplementedError()
+
+    def packed_for(self, states, trial_index=None):
+        """The kernels' descriptor of this cost for these states: one per (trial, where the cost depends on it; state width; device), packed
+        when first needed and kept for the life of the object (nothing is evicted)."""
+        key = (int(trial_index) if getattr(self, "flg_var_lengthscales", False) else None, states.shape[2], states.device)
+        if key not in self._packs:
+            self._packs[key] = self._pack(states, trial_index)
+        self._packed = self._packs[key]
+        return self._packed
 
     def runs_on_kernels(self, states=None):
         """Whether this cost (for these states, when given) is evaluated by the HIP cost kernels: what makes an attempt recordable into a
@@ -88,14 +98,14 @@ class _HipExpectedCost(Expected_cost):
         return True
 
     def forward(self, states_sequence, inputs_sequence=None, trial_index=None, group=None, counts=None):
-        if self._packed is None or self._packed.device != states_sequence.device:
-            self._packed = self._pack(states_sequence)
-        return ops.expected_cost(self._packed, states_sequence, group, counts)
+        if not self.runs_on_kernels(states_sequence):
+            return Expected_cost.forward(self, states_sequence, inputs_sequence, trial_index, group, counts)
+        return ops.expected_cost(self.packed_for(states_sequence, trial_index), states_sequence, group, counts)
 
     def local_moments(self, states_sequence, inputs_sequence, trial_index, m_total, shift=None, sums_out=None):
-        if self._packed is None or self._packed.device != states_sequence.device:
-            self._packed = self._pack(states_sequence)
-        return ops.local_cost(self._packed, states_sequence, m_total, shift, sums_out)
+        if not self.runs_on_kernels(states_sequence):
+            return Expected_cost.local_moments(self, states_sequence, inputs_sequence, trial_index, m_total, shift, sums_out)
+        return ops.local_cost(self.packed_for(states_sequence, trial_index), states_sequence, m_total, shift, sums_out)
 
     @staticmethod
     def from_sums(sums, n_total, shift=None, mean_out=None):
@@ -111,7 +121,7 @@ class Cart_pole_cost(_HipExpectedCost):
         self.target_state, self.lengthscales = _np(target_state).reshape(-1), _np(lengthscales).reshape(-1)
         self.angle_index, self.pos_index = int(angle_index), int(pos_index)
 
-    def _pack(self, states):
+    def _pack(self, states, trial_index=None):
         return ops.PackedCost("cartpole", states.shape[2], states.device, target_state=self.target_state, lengthscales=self.lengthscales,
                               angle_index=self.angle_index, pos_index=self.pos_index)
 
@@ -122,31 +132,14 @@ class Expected_saturated_distance_from_trajectory(_HipExpectedCost):
 
     def __init__(self, target_traj, lengthscales, flg_var_lengthscales=False, used_indeces=None):
         super().__init__()
-        self.flg_var_lengthscales = bool(flg_var_lengthscales)
+        self.flg_var_lengthscales = bool(flg_var_lengthscales)  # (per-trial lengthscales: packed_for keeps one descriptor per trial index)
         self.target_traj = _np(target_traj)
         self.lengthscales = [_np(l).reshape(-1) for l in lengthscales] if self.flg_var_lengthscales else _np(lengthscales).reshape(-1)
         self.used_indeces = None if used_indeces is None else [int(i) for i in used_indeces]
-        self._packed_by_trial = {}
 
     def _pack(self, states, trial_index=None):
-        ls = self.lengthscales[trial_index] if self.flg_var_lengthscales else self.lengthscales
+        ls = self.lengthscales[int(trial_index)] if self.flg_var_lengthscales else self.lengthscales
         return ops.PackedCost("traj", states.shape[2], states.device, target_traj=self.target_traj, lengthscales=ls, used=self.used_indeces)
-
-    def _select(self, states, trial_index):
-        """Per-trial lengthscales: one packed descriptor per trial index, chosen before the base class evaluates."""
-        if self.flg_var_lengthscales:
-            key = (int(trial_index), str(states.device))
-            if key not in self._packed_by_trial:
-                self._packed_by_trial[key] = self._pack(states, int(trial_index))
-            self._packed = self._packed_by_trial[key]
-
-    def forward(self, states_sequence, inputs_sequence=None, trial_index=None, group=None, counts=None):
-        self._select(states_sequence, trial_index)
-        return super().forward(states_sequence, inputs_sequence, trial_index, group, counts)
-
-    def local_moments(self, states_sequence, inputs_sequence, trial_index, m_total, shift=None, sums_out=None):
-        self._select(states_sequence, trial_index)
-        return super().local_moments(states_sequence, inputs_sequence, trial_index, m_total, shift, sums_out)
 
 
 # ---- the two costs as plain functions (Cost_function.py:124-147, 170-182) -----------------------------------------------
@@ -228,26 +221,10 @@ class _TargetStateCost(_HipExpectedCost):
         return (states.is_cuda and states.dtype == torch.float64 and states.dim() == 3 and S <= ops.abi.MAX_STATE
                 and all(-S <= i < S for i in self._act))
 
-    def _pack(self, states):
+    def _pack(self, states, trial_index=None):
         S = states.shape[2]
         return ops.PackedCost("target", S, states.device, target_state=_np(self.target_state), lengthscales=_np(self.lengthscales),
                               active_dims=[i % S for i in self._act], saturate=self._saturate)
-
-    def _select(self, states, trial_index=None):
-        if self._packed is not None and self._packed.c.S != states.shape[2]:
-            self._packed = None
-
-    def forward(self, states_sequence, inputs_sequence=None, trial_index=None, group=None, counts=None):
-        if not self.runs_on_kernels(states_sequence):
-            return Expected_cost.forward(self, states_sequence, inputs_sequence, trial_index, group, counts)
-        self._select(states_sequence)
-        return super().forward(states_sequence, inputs_sequence, trial_index, group, counts)
-
-    def local_moments(self, states_sequence, inputs_sequence, trial_index, m_total, shift=None, sums_out=None):
-        if not self.runs_on_kernels(states_sequence):
-            return Expected_cost.local_moments(self, states_sequence, inputs_sequence, trial_index, m_total, shift, sums_out)
-        self._select(states_sequence)
-        return super().local_moments(states_sequence, inputs_sequence, trial_index, m_total, shift, sums_out)
 
     @staticmethod
     def from_sums(sums, n_total, shift=None, mean_out=None):

@@ -9,8 +9,8 @@
 Constructor injection is the plug-in mechanism, as in the reference: model / policy / cost classes and their kwargs.
 Additions (all optional): ``noise_mode`` -- "philox" (in-kernel generator, default) or "reference" (noise drawn on the
 CPU with the reference's torch calls in its order, for seed-for-seed parity); ``shard_particles(group)`` -- split the
-particles over the ranks of a torch.distributed group (one all-gather of cost moments and one all-reduce of the
-policy gradient per optimizer step; every rank then applies the identical update).
+particles over the ranks of a torch.distributed group (ONE all-reduce of [gradients | cost sums | flags] per optimizer
+step; every rank then applies the identical update).
 ``MC_PILCO4PMS`` (MC_PILCO.py:755-958, partially measurable systems): the measurement filter between particles and policy is
 part of the fused rollout kernels (``mcp_meas``); a step-wise path on the posterior / policy operators remains as fallback.
 Out of scope: MC_PILCO_Experiment, MuJoCo environments.
@@ -24,9 +24,10 @@ import torch
 from torch.distributions.multivariate_normal import MultivariateNormal
 from torch.distributions.uniform import Uniform
 
-from mc_pilco_amd import ops, sharding
+from mc_pilco_amd import hipabi, ops, sharding
 from mc_pilco_amd.policy_learning import Cost_function as _Cost
 from mc_pilco_amd.policy_learning import Policy as _Policy
+from mc_pilco_amd.policy_learning import opt_loop
 from mc_pilco_amd.simulation_class import model as _sim
 
 
@@ -35,6 +36,25 @@ def _has_fused_layout(ml):
     state.  A model object without ``has_fused_layout`` keeps the older test, a speed-integration interface."""
     f = getattr(ml, "has_fused_layout", None)
     return bool(f()) if callable(f) else hasattr(ml, "vel_indeces")
+
+
+def reference_draws(m_total, T, G, dtype, *, B=0, p_drop=0.0, n_pos=0):
+    """The noise of one rollout of the WHOLE swarm, drawn from the CPU generator with the reference's torch calls in the reference's order
+    (what seed-for-seed parity rests on): mask_0 if p_drop > 0, then for t = 1..T-1: eps_t, the position noise of a simulated
+    measurement if n_pos > 0 (MC_PILCO4PMS), mask_t if p_drop > 0.
+    Returns eps [T-1, Mt, G], masks [T, Mt, B] uint8 or None, pos_noise [T-1, Mt, n_pos] or None."""
+    Mt, p = int(m_total), float(p_drop)
+    mask = lambda: torch.empty(Mt, 1, B, dtype=dtype).bernoulli_(1 - p).reshape(Mt, B)
+    masks = [mask()] if p > 0 else None
+    eps, pos_noise = [], []
+    for _ in range(1, T):
+        eps.append(torch.empty(Mt, G, dtype=dtype).normal_())
+        if n_pos:
+            pos_noise.append(torch.randn(Mt, n_pos, dtype=dtype))
+        if p > 0:
+            masks.append(mask())
+    stack = lambda l, w: torch.stack(l) if l else torch.zeros(0, Mt, w, dtype=dtype)
+    return stack(eps, G), None if masks is None else torch.stack(masks).to(torch.uint8), stack(pos_noise, n_pos) if n_pos else None
 
 
 class MC_PILCO(torch.nn.Module):
@@ -136,75 +156,60 @@ class MC_PILCO(torch.nn.Module):
         off, cnt = self._shard
         return t if cnt == t.shape[dim] else t.narrow(dim, off, cnt).contiguous()
 
-    def _rollout_noise(self, M, T, p_dropout):
+    def _rollout_noise(self, T, p_dropout=None, n_pos=0):
+        """(NoiseSpec, position noise or None, the dropout probability the policy applies) of the next rollout; the one place that advances
+        the rollout counter.  ``p_dropout`` None: a policy without dropout.  "reference" mode: the reference's draws for the WHOLE swarm
+        (every rank draws the same numbers from the same seed), sliced to this rank's particles."""
         pol = self.control_policy
-        p = float(p_dropout) if getattr(pol, "flg_drop", True) else 0.0
-        G, B = self.model_learning.num_gp, pol.num_basis
+        p = float(p_dropout) if p_dropout is not None and getattr(pol, "flg_drop", True) else 0.0
         self._rollout_calls += 1
-        if self.noise_mode == "reference":
-            # the reference's draw order: mask_0, then for t = 1..T-1: eps_t, mask_t    -- drawn for the WHOLE swarm
-            # (every rank draws the same numbers from the same seed) and sliced to this rank's particles
-            Mt = self._m_total
-            masks = [torch.empty(Mt, 1, B, dtype=self.dtype).bernoulli_(1 - p).reshape(Mt, B)] if p > 0 else None
-            eps = []
-            for _ in range(1, T):
-                eps.append(torch.empty(Mt, G, dtype=self.dtype).normal_())
-                if p > 0:
-                    masks.append(torch.empty(Mt, 1, B, dtype=self.dtype).bernoulli_(1 - p).reshape(Mt, B))
-            eps = self._shard_slice(torch.stack(eps) if eps else torch.zeros(0, Mt, G, dtype=self.dtype), 1).to(self.device).contiguous()
-            mk = None if masks is None else self._shard_slice(torch.stack(masks).to(torch.uint8), 1).to(self.device).contiguous()
-            return ops.NoiseSpec(eps=eps, masks=mk), p
-        return self._philox_noise(), p
-
-    def _feedback_noise(self, T):
-        """``_rollout_noise`` for a policy without dropout: in "reference" mode eps_t for t = 1..T-1 in the reference's order, with no
-        mask draw in between; else Philox."""
-        G = self.model_learning.num_gp
-        self._rollout_calls += 1
-        if self.noise_mode == "reference":
-            Mt = self._m_total
-            eps = [torch.empty(Mt, G, dtype=self.dtype).normal_() for _ in range(1, T)]
-            eps = self._shard_slice(torch.stack(eps) if eps else torch.zeros(0, Mt, G, dtype=self.dtype), 1).to(self.device).contiguous()
-            return ops.NoiseSpec(eps=eps)
-        return self._philox_noise()
+        if self.noise_mode != "reference":
+            return self._philox_noise(), None, p
+        draws = reference_draws(self._m_total, T, self.model_learning.num_gp, self.dtype, B=getattr(pol, "num_basis", 0), p_drop=p, n_pos=n_pos)
+        eps, masks, pos_noise = (None if t is None else self._shard_slice(t, 1).to(self.device).contiguous() for t in draws)
+        return ops.NoiseSpec(eps=eps, masks=masks), pos_noise, p
 
     def _philox_noise(self):
         """In-kernel noise keyed by (seed, rollout counter, global particle).  While an attempt is being recorded into a graph the counter is the
         device word the graph advances (by-value part 0); the host's ``_rollout_calls`` mirrors it either way."""
-        if self._call_dev is not None:
-            return ops.NoiseSpec(seed=self.seed, call=0, particle_offset=self._shard[0], call_dev=self._call_dev)
-        return ops.NoiseSpec(seed=self.seed, call=self._rollout_calls, particle_offset=self._shard[0])
+        call = self._rollout_calls if self._call_dev is None else 0
+        return ops.NoiseSpec(seed=self.seed, call=call, particle_offset=self._shard[0], call_dev=self._call_dev)
+
+    def _begin_rollout(self, particles_initial_state_mean, particles_initial_state_var, flg_particles_init_uniform, particles_init_up_bound,
+                       particles_init_low_bound, flg_particles_init_multi_gauss, num_particles, T_control):
+        """The set-up every rollout starts with (the arguments of ``apply_policy``): this rank's range of the swarm (``_shard``, ``_m_total``) and
+        x0, drawn for the whole swarm and sliced.  Returns (M of this rank, T, x0)."""
+        world, rank = self._world()
+        self._shard = sharding.shard_range(int(num_particles), world, rank)
+        self._m_total = int(num_particles)
+        x0 = self.sample_initial_particles(particles_initial_state_mean, particles_initial_state_var, flg_particles_init_uniform, particles_init_up_bound,
+                                           particles_init_low_bound, flg_particles_init_multi_gauss, self._m_total)
+        return self._shard[1], int(T_control), self._shard_slice(x0, 0)
+
+    def _fused(self, states, inputs, status, feedback=False):
+        """Books a fused launch (its status word; whether it ran the PD law) and returns what ``apply_policy`` returns."""
+        self.last_status, self.last_feedback_fused = status, feedback
+        return states, inputs
 
     def apply_policy(self, particles_initial_state_mean, particles_initial_state_var, flg_particles_init_uniform, particles_init_up_bound,
                      particles_init_low_bound, flg_particles_init_multi_gauss, num_particles, T_control, p_dropout=0.0):
         """Simulates ``num_particles`` particles for ``T_control`` steps under the control policy.
         Returns states [T,M,S] and inputs [T,M,U] (differentiable w.r.t. the policy parameters)."""
-        world, rank = self._world()
-        self._shard = sharding.shard_range(int(num_particles), world, rank)
-        self._m_total = int(num_particles)
-        M = self._shard[1]
-        T = int(T_control)
-        x0 = self._shard_slice(self.sample_initial_particles(particles_initial_state_mean, particles_initial_state_var, flg_particles_init_uniform,
-                                                             particles_init_up_bound, particles_init_low_bound, flg_particles_init_multi_gauss,
-                                                             self._m_total), 0)
+        _, T, x0 = self._begin_rollout(particles_initial_state_mean, particles_initial_state_var, flg_particles_init_uniform, particles_init_up_bound,
+                                       particles_init_low_bound, flg_particles_init_multi_gauss, num_particles, T_control)
         pol, ml = self.control_policy, self.model_learning
         self.last_feedback_fused = False  # (reset before every branch: a run under another policy must not leave an earlier True standing)
         if isinstance(pol, _Policy.Sum_of_gaussians) and _has_fused_layout(ml):
-            noise, p = self._rollout_noise(M, T, p_dropout)
-            states, inputs, status = ops.rollout(ml.packed(), pol.packed(), noise, x0, T, p, gp_sharding=self.gp_sharding)
-            self.last_status = status
-            return states, inputs
+            noise, _, p = self._rollout_noise(T, p_dropout)
+            return self._fused(*ops.rollout(ml.packed(), pol.packed(), noise, x0, T, p, gp_sharding=self.gp_sharding))
         if self.fused_feedback and isinstance(pol, _Policy.PD_controller) and _has_fused_layout(ml) and pol.fusable(ml.packed(), T):
             # the closed loop under the PD law, one launch (and one sweep in backward): the eps draws of _rollout_noise, no dropout masks.
             # Sharded: the eps buffers are drawn for the whole swarm and sliced, Philox counts by global particle; the gains' gradients
             # reach the step's all-reduce through their .grad (_cost_backward)
-            states, inputs, status = ops.rollout_pd(ml.packed(), pol.packed(), self._feedback_noise(T), x0, T)
-            self.last_status = status
-            self.last_feedback_fused = True
-            return states, inputs
+            return self._fused(*ops.rollout_pd(ml.packed(), pol.packed(), self._rollout_noise(T)[0], x0, T), feedback=True)
         # generic (unfused) path: any model / policy object with the reference's step interface
         self.last_status = None  # (no fused launch: the flags of an earlier fused rollout do not describe this one)
-        if world > 1:
+        if self._world()[0] > 1:
             # its noise (torch draws inside get_next_state / the policy's dropout) is per LOCAL particle: identically seeded ranks
             # would simulate correlated shards, not the particles one GPU would
             raise NotImplementedError("particle sharding needs the fused rollout (Sum_of_gaussians or PD_controller policy + a model with a "
@@ -217,20 +222,9 @@ class MC_PILCO(torch.nn.Module):
             us.append(pol(x, t=t, p_dropout=p_dropout))
         return torch.stack(xs), torch.stack(us)
 
-    def _cost(self, states, inputs, trial_index):
-        """(cost, std) of the whole swarm WITHOUT running backward (warm-up of the cost monitors, user calls).  Sharded: one
-        all-reduce of the summable cost moments."""
-        if self.dist_group is None:
-            return self.cost_function(states, inputs, trial_index)
-        with torch.no_grad():
-            cost, std, _ = self._cost_backward(states, inputs, trial_index, backward=False)
-        return cost, std
-
     def _step_flags(self, cost):
         """Device vector [cost is NaN, a GP-sharded launch timed out (MCP_STATUS_SYNC), a predictive variance was <= 0
         (MCP_STATUS_NONPOS_VAR)] of the last fused rollout."""
-        from mc_pilco_amd import hipabi
-
         st = self.last_status
         if st is None or st.device != cost.device:
             sync = nonpos = torch.zeros((), dtype=torch.bool, device=cost.device)
@@ -344,17 +338,11 @@ class MC_PILCO(torch.nn.Module):
         optimizer and in a particle-sharded run).  A failed attempt needs nothing from the host (the next attempt is the retry);
         where the host must act -- ten failures in a row, the lr / exit condition, the last step -- the device ignores the attempts
         enqueued meanwhile and the host rewinds the noise counters past them: both depths take exactly the same steps."""
-        import ctypes as C
-
-        from mc_pilco_amd import hipabi as abi
-
-        dev, dt = self.device, self.dtype
-        horizon = int(T_control / self.T_sampling)
         n_steps = opt_steps_list[trial_index]
         sim = dict(particles_initial_state_mean=particles_initial_state_mean, particles_initial_state_var=particles_initial_state_var,
                    flg_particles_init_uniform=flg_particles_init_uniform, flg_particles_init_multi_gauss=flg_particles_init_multi_gauss,
                    particles_init_up_bound=particles_init_up_bound, particles_init_low_bound=particles_init_low_bound,
-                   num_particles=num_particles, T_control=horizon)
+                   num_particles=num_particles, T_control=int(T_control / self.T_sampling))
         p_drop0 = 0.0 if p_dropout_list is None else p_dropout_list[trial_index]
         if p_dropout_list is not None:
             print("\nDROPOUT ACTIVE:")
@@ -376,269 +364,140 @@ class MC_PILCO(torch.nn.Module):
                 print("\nSE filter initialization: Cost is NaN - reinit the policy")
                 self.control_policy.reinit(**policy_reinit_dict)
 
-        # ---- device-side loop state (mcp_opt_state + the monitors' arrays) ------------------------------------------------------------
-        lib = abi.lib()
-        if dt != torch.float64:
-            # the loop state, the cost lists and the Adam kernel are double precision on the device (mcp_opt_state, mcp_adam_step_guarded):
-            # another dtype would be read through double* -- refuse it here rather than take garbage decisions
-            raise RuntimeError("reinforce_policy on the HIP path works in torch.float64 (the kernels are fp64); got dtype %s" % dt)
-        st = torch.zeros(7, dtype=torch.int64, device=dev)  # mcp_opt_state: step, attempt, pending, adam_t, total_attempts | es2, cost_prev
-        st[5:].view(torch.float64)[1:2].copy_(cost0.detach().reshape(1))   # cost_tm1 = the warm-up cost (MC_PILCO.py:462)
-        cost_list = torch.zeros(n_steps, device=dev, dtype=dt)
-        std_list = torch.zeros(n_steps, device=dev, dtype=dt)
-        es1 = torch.zeros(n_steps + 1, device=dev, dtype=dt)
-        ratio = torch.zeros(n_steps + 1, device=dev, dtype=dt)
-        hs = dict(lr=lr_list[trial_index], p_drop=p_drop0, min_diff=min_diff_cost, min_step=min_step, prev_cost=0.0)  # what the host holds
-        params = [q for q in self.control_policy.parameters()]
-        opt = make_opt(p=self.control_policy.parameters(), lr=hs["lr"])
-        adam = self._plain_adam(opt)
-        depth = int(getattr(self, "pipeline_depth", 1))
-        if adam is None or self.noise_mode == "reference" or self.dist_group is not None:
-            depth = 0
-        ad = {}
-
-        def fresh_adam_state():
-            if adam is not None:
-                ps = [q for q in opt.param_groups[0]["params"] if q.requires_grad]
-                ad.update(ps=ps, m=[torch.zeros_like(q) for q in ps], v=[torch.zeros_like(q) for q in ps],
-                          numel=(C.c_int64 * len(ps))(*[q.numel() for q in ps]))
-                for k in ("m", "v", "ps"):
-                    ad["c_" + k] = (abi.dptr * len(ps))(*[t.data_ptr() for t in ad[k]])
-            st[3:4].zero_()
-
-        fresh_adam_state()
-        ring = [torch.empty(abi.OPT_RECORD_DOUBLES, dtype=dt).pin_memory() for _ in range(depth + 2)]
-        rec_dev = torch.zeros(depth + 2, abi.OPT_RECORD_DOUBLES, dtype=dt, device=dev)
-        seq = [0]
-
-        # ---- one attempt = rollout -> cost -> adjoint -> guarded Adam -> commit: ~15 launches and as many host calls.  In the pipelined loop it
-        # is recorded ONCE into a HIP graph and replayed (round 6): everything an attempt reads that changes from one attempt to the next lives in
-        # device memory -- the parameters, the loop state, torch's generator offset (graph-safe) and the rollout counter of the in-kernel noise
-        # (mcp_noise.call_dev, advanced by the graph itself) -- so a replay takes the same step the eager calls would, bit for bit.  Two graphs
-        # alternate (each with its own trajectories and record row: an attempt voided while the host decides must not overwrite the outputs of
-        # the one before it).  The first two attempts after every (re)start run eagerly (they warm the launch paths); a host decision that
-        # changes a recorded value -- lr, dropout, new Adam moments, re-initialised parameters -- drops the graphs.
-        pol_ = self.control_policy
-        use_graph = (bool(getattr(self, "capture_attempts", False)) and depth > 0 and adam is not None and dev.type == "cuda"
-                     and type(self).apply_policy is MC_PILCO.apply_policy  # (the measurement-model rollout of MC_PILCO4PMS keeps the eager loop)
-                     and isinstance(pol_, _Policy.Sum_of_gaussians) and getattr(pol_, "_unit_scale", False)
-                     and _has_fused_layout(self.model_learning) and isinstance(self.cost_function, _Cost._HipExpectedCost)
-                     and self.cost_function.runs_on_kernels())  # (a target-state cost with several target rows keeps its torch path)
-        cap = dict(on=use_graph, graphs=[None, None], outs=[None, None], eager=0, rec=torch.zeros(2, abi.OPT_RECORD_DOUBLES, dtype=dt, device=dev),
-                   one=torch.ones(1, dtype=dt, device=dev), last_flat=None)
+        sched = opt_loop.HostSchedule(lr_list[trial_index], p_drop0, min_diff_cost, min_step, lr_min, lr_reduction_ratio, p_drop_reduction,
+                                      num_min_diff_cost)
+        lp = opt_loop.PolicyLoop(self, make_opt, sched, n_steps, cost0, sim, trial_index, alpha_diff_cost)
         self.attempts_replayed = 0
+        last, done = self._run_attempts(lp, num_step_print, policy_reinit_dict)
+        if lp.graphs.last_flat is not None:  # (the last attempt was a replay: its gradients are where autograd would have left them)
+            for q in lp.params:
+                g_ = lp.graphs.last_flat.get(id(q))
+                q.grad = None if g_ is None else g_.reshape(q.shape)
+        lp.graphs.drop()  # (rollouts after this call count by value again; the host's mirror of the counter is current)
+        return (lp.state.cost_list[0:done].detach().cpu().numpy(), lp.state.std_list[0:done].detach().cpu().numpy(),
+                last.states.detach().cpu().numpy(), last.inputs.detach().cpu().numpy())
 
-        def drop_graphs():
-            cap["graphs"], cap["outs"], cap["eager"] = [None, None], [None, None], 0
-            self._call_dev = None
-
-        def commit(cost, std, flags, status, grads, rec_row):
-            cptr, sptr = abi.ptr(cost.detach().reshape(1)), abi.ptr(std.detach().reshape(1))
-            if adam is not None:
-                abi.check(lib.mcp_adam_step_guarded(len(ad["ps"]), ad["c_ps"], grads, ad["c_m"], ad["c_v"], ad["numel"], float(hs["lr"]), adam[1],
-                                                    adam[2], adam[3], abi.ptr(st), 0, n_steps, cptr, abi.ptr(flags), abi.ptr(status), abi.stream()),
-                          "mcp_adam_step_guarded")
-            abi.check(lib.mcp_policy_step_commit(abi.ptr(st), n_steps, cptr, sptr, abi.ptr(flags), abi.ptr(status), abi.ptr(cost_list),
-                                                 abi.ptr(std_list), abi.ptr(es1), abi.ptr(ratio), float(alpha_diff_cost),
-                                                 float(min(hs["min_step"], 1e300)), float(hs["min_diff"]), int(num_min_diff_cost),
-                                                 abi.ptr(rec_row), abi.stream()), "mcp_policy_step_commit")
-
-        def attempt_body(rec_row):
-            """The reference's lines (MC_PILCO.py:484-525) on the drop-in classes: apply_policy -> cost_function -> cost.backward() -> step."""
-            for q in params:
-                q.grad = None
-            states, inputs = self.apply_policy(p_dropout=hs["p_drop"], **sim)
-            cost, std, flags = self._cost_backward(states, inputs, trial_index, flags_as_vector=self.dist_group is not None)
-            status = None if (flags is not None or self.last_status is None) else self.last_status
-            grads = None if adam is None else (abi.dptr * len(ad["ps"]))(*[None if q.grad is None else q.grad.data_ptr() for q in ad["ps"]])
-            commit(cost, std, flags, status, grads, rec_row)
-            return states, inputs, cost, None
-
-        def attempt_body_raw(rec_row):
-            """The same attempt as the operators underneath make it, without the autograd engine (whose stream bookkeeping does not survive a
-            stream capture): x0 -> mcp_rollout_fwd -> mcp_cost_fwd / _finalize / _bwd -> mcp_rollout_bwd -> guarded Adam -> commit.  Identical
-            launches with identical arguments, hence identical bits; this is the form that is recorded and replayed."""
-            self._call_dev.add_(1)
-            world, rank = self._world()
-            self._shard = sharding.shard_range(int(sim["num_particles"]), world, rank)
-            self._m_total = int(sim["num_particles"])
-            M, T = self._shard[1], int(sim["T_control"])
-            x0 = self.sample_initial_particles(sim["particles_initial_state_mean"], sim["particles_initial_state_var"], sim["flg_particles_init_uniform"],
-                                               sim["particles_init_up_bound"], sim["particles_init_low_bound"], sim["flg_particles_init_multi_gauss"],
-                                               self._m_total)
-            noise, p = self._rollout_noise(M, T, hs["p_drop"])
-            model, pk = self.model_learning.packed(), pol_.packed()
-            states, inputs, jac, status = ops.rollout_forward_raw(model, pk, noise, x0, T, p, True, need_jac=True, gp_sharding=self.gp_sharding)
-            self.last_status = status
-            cf = self.cost_function
-            if hasattr(cf, "_select"):
-                cf._select(states, trial_index)
-            if cf._packed is None or cf._packed.device != states.device:
-                cf._packed = cf._pack(states)
-            cost, std, g_states = ops.expected_cost_raw(cf._packed, states, cap["one"])
-            g_ls, g_c, g_w, _, g_b = ops.rollout_backward_raw(model, pk, noise, states, inputs, jac, g_states, None, p)
-            by_param = {id(pol_.log_lengthscales): g_ls, id(pol_.centers): g_c, id(pol_.f_linear.weight): g_w}
-            if pol_.f_linear.bias is not None:
-                by_param[id(pol_.f_linear.bias)] = g_b
-            grads = (abi.dptr * len(ad["ps"]))(*[by_param[id(q)].data_ptr() for q in ad["ps"]])
-            commit(cost, std, None, status, grads, rec_row)
-            return states, inputs, cost, by_param
-
-        def enqueue():
-            """One attempt, start to finish, without a host sync."""
-            snap = (self._rollout_calls, torch.cuda.get_rng_state(dev) if depth > 0 else None)
-            slot = seq[0] % (depth + 2)
-            gi = seq[0] & 1
-            seq[0] += 1
-            rec_src = None
-            if cap["on"] and cap["eager"] >= 2:
-                if cap["graphs"][gi] is None:
-                    # record: the kernels are not run here; the replay below is this attempt
-                    if self._call_dev is None:
-                        self._call_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-                    self._call_dev.fill_(self._rollout_calls)
-                    torch.cuda.synchronize(dev)
-                    g = torch.cuda.CUDAGraph()
-                    try:
-                        with torch.cuda.graph(g):
-                            cap["outs"][gi] = attempt_body_raw(cap["rec"][gi])
-                        cap["graphs"][gi] = g
-                    except Exception as e:  # noqa: BLE001  (a runtime that cannot record this sequence: the eager loop is the same loop)
-                        print("\nreinforce_policy: recording an attempt into a graph failed (%r) -- continuing with eager launches" % (e,))
-                        cap["on"] = False
-                        self._rollout_calls = snap[0]
-                        if snap[1] is not None:
-                            torch.cuda.set_rng_state(snap[1], dev)
-                        drop_graphs()
-                else:
-                    self._rollout_calls += 1  # (the host's mirror of the counter the replay advances)
-                if cap["graphs"][gi] is not None:
-                    cap["graphs"][gi].replay()
-                    self.attempts_replayed += 1
-                    states, inputs, cost, cap["last_flat"] = cap["outs"][gi]
-                    rec_src = cap["rec"][gi]
-            if rec_src is None:
-                cap["eager"] += 1
-                states, inputs, cost, cap["last_flat"] = attempt_body(rec_dev[slot])
-                rec_src = rec_dev[slot]
-            ring[slot].copy_(rec_src, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            return dict(states=states, inputs=inputs, rec=ring[slot], ev=ev, snap=snap, cost=cost)
-
-        def read(h):
-            h["ev"].synchronize()
-            return h["rec"].tolist()
-
-        def step_print(k, cost_now, rabs):
-            print("\nOptimization step: ", k)
-            print("cost: ", cost_now)
-            print("cost improvement: ", hs["prev_cost"] - cost_now)
-            print("p_dropout_applied: ", hs["p_drop"])
-            print("current_min_diff_cost; ", hs["min_diff"])
-            print("current_min_step: ", hs["min_step"])
-            print("diff_cost_ratio: ", rabs)
-            print("time elapsed: ", time.time() - hs["t_mark"])
-            hs["prev_cost"] = cost_now
-            hs["t_mark"] = time.time()
-
-        def lr_or_exit(k):
-            """The condition of MC_PILCO.py:540-547 held at step k.  True: leave the loop."""
-            if hs["lr"] > lr_min:
-                print("Optimization_step:", k)
-                print("\nREDUCING THE LEARNING RATE:")
-                hs["lr"] = max(hs["lr"] * lr_reduction_ratio, lr_min)
-                print("lr: ", hs["lr"])
-                hs["min_diff"] = max(hs["min_diff"] / 2, 0.01)
-                hs["min_step"] = k + num_min_diff_cost
-                print("\nREDUCING THE DROPOUT:")
-                hs["p_drop"] = max(hs["p_drop"] - p_drop_reduction, 0.0)
-                print("p_dropout_applied: ", hs["p_drop"])
-                return False
-            print("\nEXIT FROM OPTIMIZATION: diff_cost_ratio < min_diff_cost for num_min_diff_cost steps")
-            return True
-
-        def discard(queue):
-            """The attempts enqueued while the device was waiting for the host: the device ignored them; the noise counters go back
-            to where the first of them found them, so the run continues exactly as one that never enqueued them."""
-            if queue:
-                for h in queue:
-                    r = read(h)
-                    assert r[1] == 1.0 and r[0] == 0.0, "an attempt enqueued past a host decision was not void"
-                self._rollout_calls = queue[0]["snap"][0]
-                if self._call_dev is not None:
-                    self._call_dev.fill_(self._rollout_calls)
-                if queue[0]["snap"][1] is not None:
-                    torch.cuda.set_rng_state(queue[0]["snap"][1], dev)
-                queue.clear()
-
-        hs["t_mark"] = time.time()
+    def _run_attempts(self, lp, num_step_print, policy_reinit_dict):
+        """Enqueues attempts and reads their records ``lp.depth`` attempts late until the steps are taken or the exit condition holds.
+        Returns (the last attempt read, the number of steps taken)."""
+        sched = lp.sched
+        sched.t_mark = time.time()
         queue, last, done, reinits, leave = [], None, 0, 0, False
         while not leave:
-            queue.append(enqueue())
-            while queue and (len(queue) > depth) and not leave:
+            queue.append(self._enqueue(lp))
+            while queue and (len(queue) > lp.depth) and not leave:
                 h = queue.pop(0)
-                counted, void, k, failed, pending, cost_now, _std, rabs, nan, sync, nonpos, _tot = read(h)
-                k = int(k)
-                assert void == 0.0, "the oldest attempt in flight cannot be void"
-                if counted == 0.0:
-                    self._judge_attempt(nan, sync, nonpos)  # (raises on a non-positive variance; switches GP sharding off after a time-out)
+                r = opt_loop.read(h)
+                k = int(r.step)
+                assert r.void == 0.0, "the oldest attempt in flight cannot be void"
+                if r.counted == 0.0:
+                    self._judge_attempt(r.nan, r.sync, r.nonpos)  # (raises on a non-positive variance; switches GP sharding off after a time-out)
                     print("\nCost is NaN: try sampling again")
                     last = h
-                    if failed >= abi.OPT_MAX_ATTEMPTS:
+                    if r.attempt >= hipabi.OPT_MAX_ATTEMPTS:
                         # ten failed attempts in a row (MC_PILCO.py:573-607): the reference takes the step on the failed cost (its monitors
                         # and messages included) and restarts from a re-initialised policy
-                        discard(queue)
+                        self._discard(queue)
                         if k % num_step_print == 0:
-                            step_print(k, cost_now, float("nan"))
-                        if k > hs["min_step"]:  # (its lr / exit test looks at the window BEFORE this step's ratio: it may still fire; only the
-                            win = torch.abs(ratio[max(k + 1 - num_min_diff_cost, 0):k + 1])  # messages matter, everything is reset below)
-                            if int(torch.sum(win < hs["min_diff"])) >= num_min_diff_cost and k + 1 >= num_min_diff_cost:
-                                lr_or_exit(k)
+                            sched.step_print(k, r.cost, float("nan"))
+                        if k > sched.min_step:  # (its lr / exit test looks at the window BEFORE this step's ratio: it may still fire; only the
+                            win = torch.abs(lp.state.ratio[max(k + 1 - sched.n_win, 0):k + 1])  # messages matter, everything is reset below)
+                            if int(torch.sum(win < sched.min_diff)) >= sched.n_win and k + 1 >= sched.n_win:
+                                sched.lr_or_exit(k)
                         reinits += 1
                         print("\nCost is NaN: re-initialize control policy [attempt #" + str(reinits) + "]")
                         self.control_policy.reinit(**policy_reinit_dict)
-                        st[0:5].zero_()  # (ES2 and cost_tm1 are NOT reset by the reference: they keep the failed step's values)
-                        for a in (cost_list, std_list, es1, ratio):
-                            a.zero_()
-                        hs.update(lr=lr_list[trial_index], p_drop=p_drop0, min_diff=min_diff_cost, min_step=min_step, prev_cost=0.0)
-                        opt = make_opt(p=self.control_policy.parameters(), lr=hs["lr"])
-                        adam = self._plain_adam(opt)
-                        params = [q for q in self.control_policy.parameters()]
-                        fresh_adam_state()
-                        drop_graphs()  # (new moments / learning rate / dropout / parameters: what the graphs recorded is gone)
+                        lp.state.reset_after_reinit()
+                        sched.reset()
+                        lp.new_optimizer(same_kind=False)  # (new moments / learning rate / dropout / parameters: what the graphs recorded is gone)
                         done = 0
                     continue
                 # the attempt counted: step k was taken
                 last, done = h, k + 1
-                if adam is None:
-                    opt.step()  # (depth 0: the host knows the attempt counted before it updates)
+                if lp.adam is None:
+                    lp.opt.step()  # (depth 0: the host knows the attempt counted before it updates)
                 if k % num_step_print == 0:
-                    step_print(k, cost_now, rabs)
-                if pending != 0.0:
-                    discard(queue)
-                    leave = lr_or_exit(k)
+                    sched.step_print(k, r.cost, r.abs_ratio)
+                if r.pending != 0.0:
+                    self._discard(queue)
+                    leave = sched.lr_or_exit(k)
                     if not leave:
-                        opt = make_opt(p=self.control_policy.parameters(), lr=hs["lr"])
-                        adam_now = self._plain_adam(opt)
-                        if (adam_now is None) != (adam is None):
-                            raise RuntimeError("f_optimizer must build the same kind of optimizer on every call")
-                        adam = adam_now
-                        fresh_adam_state()
-                        drop_graphs()  # (new moments / learning rate / dropout / parameters: what the graphs recorded is gone)
-                    st[2:3].zero_()
-                if done >= n_steps:
-                    discard(queue)
+                        lp.new_optimizer()  # (new moments / learning rate / dropout: what the graphs recorded is gone)
+                    lp.state.clear_pending()
+                if done >= lp.state.n_steps:
+                    self._discard(queue)
                     leave = True
-        discard(queue)
-        states, inputs = last["states"], last["inputs"]
-        if cap["last_flat"] is not None:  # (the last attempt was a replay: its gradients are where autograd would have left them)
-            for q in params:
-                g_ = cap["last_flat"].get(id(q))
-                q.grad = None if g_ is None else g_.reshape(q.shape)
-        drop_graphs()  # (rollouts after this call count by value again; the host's mirror of the counter is current)
-        return (cost_list[0:done].detach().cpu().numpy(), std_list[0:done].detach().cpu().numpy(), states.detach().cpu().numpy(),
-                inputs.detach().cpu().numpy())
+        self._discard(queue)
+        return last, done
+
+    def _recordable(self):
+        """An attempt of this object can be recorded into a HIP graph (``capture_attempts``; pipelined loop with the guarded Adam only)."""
+        pol = self.control_policy
+        return (bool(getattr(self, "capture_attempts", False)) and self.device.type == "cuda"
+                and type(self).apply_policy is MC_PILCO.apply_policy  # (the measurement-model rollout of MC_PILCO4PMS keeps the eager loop)
+                and isinstance(pol, _Policy.Sum_of_gaussians) and getattr(pol, "_unit_scale", False)
+                and _has_fused_layout(self.model_learning) and isinstance(self.cost_function, _Cost._HipExpectedCost)
+                and self.cost_function.runs_on_kernels())  # (a target-state cost with several target rows keeps its torch path)
+
+    def _attempt(self, lp, rec_row):
+        """The reference's lines (MC_PILCO.py:484-525) on the drop-in classes: apply_policy -> cost_function -> cost.backward() -> step."""
+        for q in lp.params:
+            q.grad = None
+        states, inputs = self.apply_policy(p_dropout=lp.sched.p_drop, **lp.sim)
+        cost, std, flags = self._cost_backward(states, inputs, lp.trial_index, flags_as_vector=self.dist_group is not None)
+        status = None if (flags is not None or self.last_status is None) else self.last_status
+        grads = None if lp.adam is None else lp.adam.pointers(None if q.grad is None else q.grad.data_ptr() for q in lp.adam.ps)
+        lp.commit(cost, std, flags, status, grads, rec_row)
+        return states, inputs, cost, None
+
+    def _attempt_raw(self, lp, rec_row):
+        """The same attempt as the operators underneath make it, without the autograd engine (whose stream bookkeeping does not survive a
+        stream capture): x0 -> mcp_rollout_fwd -> mcp_cost_fwd / _finalize / _bwd -> mcp_rollout_bwd -> guarded Adam -> commit.  Identical
+        launches with identical arguments, hence identical bits; this is the form that is recorded and replayed."""
+        pol = self.control_policy
+        self._call_dev.add_(1)
+        _, T, x0 = self._begin_rollout(**lp.sim)  # (a recorded attempt runs on one rank: the whole swarm)
+        noise, _, p = self._rollout_noise(T, lp.sched.p_drop)
+        model, pk = self.model_learning.packed(), pol.packed()
+        states, inputs, jac, status = ops.rollout_forward_raw(model, pk, noise, x0, T, p, True, need_jac=True, gp_sharding=self.gp_sharding)
+        self.last_status = status
+        cost, std, g_states = ops.expected_cost_raw(self.cost_function.packed_for(states, lp.trial_index), states, lp.graphs.one)
+        g_ls, g_c, g_w, _, g_b = ops.rollout_backward_raw(model, pk, noise, states, inputs, jac, g_states, None, p)
+        by_param = {id(pol.log_lengthscales): g_ls, id(pol.centers): g_c, id(pol.f_linear.weight): g_w}
+        if pol.f_linear.bias is not None:
+            by_param[id(pol.f_linear.bias)] = g_b
+        lp.commit(cost, std, None, status, lp.adam.pointers(by_param[id(q)].data_ptr() for q in lp.adam.ps), rec_row)
+        return states, inputs, cost, by_param
+
+    def _enqueue(self, lp):
+        """One attempt, start to finish, without a host sync: a graph replay where there is one, else the eager calls."""
+        state, graphs = lp.state, lp.graphs
+        snap = (self._rollout_calls, torch.cuda.get_rng_state(self.device) if lp.depth > 0 else None)
+        slot, gi = state.seq % state.slots, state.seq & 1  # (of the record ring; which of the two graphs)
+        state.seq += 1
+        ran = graphs.run(gi, lambda row: self._attempt_raw(lp, row), snap)
+        if ran is None:
+            graphs.eager += 1
+            ran = self._attempt(lp, state.rec_dev[slot]), state.rec_dev[slot]
+        (states, inputs, cost, graphs.last_flat), rec_src = ran
+        state.ring[slot].copy_(rec_src, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return opt_loop.Attempt(states, inputs, cost, state.ring[slot], ev, snap)
+
+    def _discard(self, queue):
+        """The attempts enqueued while the device was waiting for the host: the device ignored them; the noise counters go back
+        to where the first of them found them, so the run continues exactly as one that never enqueued them."""
+        if queue:
+            for h in queue:
+                r = opt_loop.read(h)
+                assert r.void == 1.0 and r.counted == 0.0, "an attempt enqueued past a host decision was not void"
+            self._rollout_calls, rng_state = queue[0].snap
+            if self._call_dev is not None:
+                self._call_dev.fill_(self._rollout_calls)
+            if rng_state is not None:
+                torch.cuda.set_rng_state(rng_state, self.device)
+            queue.clear()
 
     # ------------------------------------------------------------------------------------------------------------
     # trial loop
@@ -890,78 +749,45 @@ class MC_PILCO4PMS(MC_PILCO):
         self.std_meas_noise_sim = std_meas_noise if std_meas_noise_sim is None else std_meas_noise_sim
         self.fused = True  # False: step-by-step rollout on the posterior / policy operators (any model or policy object)
 
+    def _measured_model(self):
+        """The packed model a fused rollout on measurements launches."""
+        model = self.model_learning.packed()
+        if getattr(model, "is_delta", False) and model.Ts != float(self.T_sampling):
+            model = self.model_learning.packed(T_sampling=self.T_sampling)  # (a delta-state model has no Ts: the measured velocities need one)
+        return model
+
+    def _meas_spec(self, b, a, pos_noise):
+        pos = list(self.pos_indeces)
+        return ops.MeasSpec(pos=pos, vel=list(self.vel_indeces), std_pos=[float(v) for v in np.asarray(self.std_meas_noise_sim)[pos]], b=b, a=a,
+                            pos_noise=pos_noise)
+
     def apply_policy(self, particles_initial_state_mean, particles_initial_state_var, flg_particles_init_uniform, particles_init_up_bound,
                      particles_init_low_bound, flg_particles_init_multi_gauss, num_particles, T_control, p_dropout=0.0):
         from scipy import signal
 
-        world, rank = self._world()
-        self._shard = sharding.shard_range(int(num_particles), world, rank)
-        self._m_total = int(num_particles)
-        M, T = self._shard[1], int(T_control)
+        M, T, x = self._begin_rollout(particles_initial_state_mean, particles_initial_state_var, flg_particles_init_uniform, particles_init_up_bound,
+                                      particles_init_low_bound, flg_particles_init_multi_gauss, num_particles, T_control)
         pol, ml = self.control_policy, self.model_learning
         ref = self.noise_mode == "reference"  # draw on the CPU with the reference's calls, in its order
         ndev = torch.device("cpu") if ref else self.device
-        x = self._shard_slice(self.sample_initial_particles(particles_initial_state_mean, particles_initial_state_var, flg_particles_init_uniform,
-                                                            particles_init_up_bound, particles_init_low_bound, flg_particles_init_multi_gauss,
-                                                            self._m_total), 0)
         b, a = signal.butter(1, self.filtering_dict["fc"])
         pos, vel = list(self.pos_indeces), list(self.vel_indeces)
         self.last_feedback_fused = False  # (reset before every branch, as in MC_PILCO.apply_policy)
         if self.fused and isinstance(pol, _Policy.Sum_of_gaussians) and _has_fused_layout(ml):
-            # one fused launch: the kernels carry the measurement filter's states per particle (mcp_meas)
-            p = float(p_dropout) if getattr(pol, "flg_drop", True) else 0.0
-            G, B = ml.num_gp, pol.num_basis
-            self._rollout_calls += 1
-            if ref:  # the reference's draw order: mask_0; per step: eps_t, position noise, mask_t (whole swarm, then this rank's slice)
-                Mt = self._m_total
-                masks = [torch.empty(Mt, 1, B, dtype=self.dtype).bernoulli_(1 - p).reshape(Mt, B)] if p > 0 else None
-                eps, pn = [], []
-                for _ in range(1, T):
-                    eps.append(torch.empty(Mt, G, dtype=self.dtype).normal_())
-                    pn.append(torch.randn(Mt, len(pos), dtype=self.dtype))
-                    if p > 0:
-                        masks.append(torch.empty(Mt, 1, B, dtype=self.dtype).bernoulli_(1 - p).reshape(Mt, B))
-                stack = lambda l, w: self._shard_slice(torch.stack(l) if l else torch.zeros(0, Mt, w, dtype=self.dtype), 1).to(self.device).contiguous()
-                noise = ops.NoiseSpec(eps=stack(eps, G), masks=None if masks is None else
-                                      self._shard_slice(torch.stack(masks).to(torch.uint8), 1).to(self.device).contiguous())
-                pos_noise = stack(pn, len(pos))
-            else:
-                noise = self._philox_noise()
-                pos_noise = None
-            meas = ops.MeasSpec(pos=pos, vel=vel, std_pos=[float(v) for v in np.asarray(self.std_meas_noise_sim)[pos]], b=b, a=a,
-                                pos_noise=pos_noise)
-            model = ml.packed()
-            if getattr(model, "is_delta", False) and model.Ts != float(self.T_sampling):
-                model = ml.packed(T_sampling=self.T_sampling)  # (a delta-state model has no Ts: the measured velocities need one)
-            states, inputs, status = ops.rollout(model, pol.packed(), noise, x, T, p, meas=meas, gp_sharding=self.gp_sharding)
-            self.last_status = status
-            return states, inputs
+            # one fused launch: the kernels carry the measurement filter's states per particle (mcp_meas); the reference's draw order is
+            # mask_0; per step: eps_t, position noise, mask_t
+            noise, pos_noise, p = self._rollout_noise(T, p_dropout, n_pos=len(pos))
+            return self._fused(*ops.rollout(self._measured_model(), pol.packed(), noise, x, T, p, meas=self._meas_spec(b, a, pos_noise),
+                                            gp_sharding=self.gp_sharding))
         if self.fused and self.fused_feedback and isinstance(pol, _Policy.PD_controller) and _has_fused_layout(ml):
-            model = ml.packed()
-            if getattr(model, "is_delta", False) and model.Ts != float(self.T_sampling):
-                model = ml.packed(T_sampling=self.T_sampling)  # (a delta-state model has no Ts: the measured velocities need one)
+            model = self._measured_model()
             if pol.fusable(model, T):
-                # the closed loop under the PD law on the simulated measurement, one launch (and one sweep in backward)
-                G = ml.num_gp
-                self._rollout_calls += 1
-                if ref:  # the reference's draw order per step: eps_t, position noise; no mask (whole swarm, then this rank's slice)
-                    Mt = self._m_total
-                    eps, pn = [], []
-                    for _ in range(1, T):
-                        eps.append(torch.empty(Mt, G, dtype=self.dtype).normal_())
-                        pn.append(torch.randn(Mt, len(pos), dtype=self.dtype))
-                    stack = lambda l, w: self._shard_slice(torch.stack(l) if l else torch.zeros(0, Mt, w, dtype=self.dtype), 1).to(self.device).contiguous()
-                    noise, pos_noise = ops.NoiseSpec(eps=stack(eps, G)), stack(pn, len(pos))
-                else:
-                    noise, pos_noise = self._philox_noise(), None
-                meas = ops.MeasSpec(pos=pos, vel=vel, std_pos=[float(v) for v in np.asarray(self.std_meas_noise_sim)[pos]], b=b, a=a,
-                                    pos_noise=pos_noise)
-                states, inputs, status = ops.rollout_pd(model, pol.packed(), noise, x, T, meas=meas)
-                self.last_status = status
-                self.last_feedback_fused = True
-                return states, inputs
+                # the closed loop under the PD law on the simulated measurement, one launch (and one sweep in backward); the reference's draw
+                # order per step: eps_t, position noise; no mask
+                noise, pos_noise, _ = self._rollout_noise(T, n_pos=len(pos))
+                return self._fused(*ops.rollout_pd(model, pol.packed(), noise, x, T, meas=self._meas_spec(b, a, pos_noise)), feedback=True)
         self.last_status = None  # (no fused launch)
-        if world > 1:  # (per-LOCAL-particle torch draws: identically seeded ranks would simulate correlated shards)
+        if self._world()[0] > 1:  # (per-LOCAL-particle torch draws: identically seeded ranks would simulate correlated shards)
             raise NotImplementedError("particle sharding needs the fused rollout (fused=True, Sum_of_gaussians or PD_controller policy, a model "
                                       "with a fused layout)")
         std_pos = torch.tensor(np.asarray(self.std_meas_noise_sim)[pos], dtype=self.dtype, device=self.device)
