@@ -52,6 +52,44 @@ int mcp_rollout_bwd_ex(const mcp_model* model, const mcp_policy* policy, const m
 int mcp_posterior_fwd_ex(const mcp_gp* gp, int M, const double* Z, double* mu, double* var, double* Jmu, double* Jvar, uint32_t* status,
                          void* stream, mcp_dispatch* d);
 
+/*
+ * Plan queries: what mcp_rollout_fwd_ex / mcp_rollout_bwd_ex would decide for a call, without making it.  Same descriptors, M, T, flags
+ * (the particle_pred argument) and workspace size (0 = no workspace), the device's compute-unit count given explicitly, and a request
+ * (NULL = automatic).  They return what the real call returns from validating its descriptors and planning, read only the scalars of the
+ * descriptors (pointers are tested for NULL, never followed) and make no HIP call: they run on a machine without a GPU.  All fields int32.
+ */
+enum { MCP_FWD_SMALL_SHARDED = 1, MCP_FWD_LEAN = 2, MCP_FWD_TILE_SHARDED = 3, MCP_FWD_TILE = 4, MCP_FWD_SMALL = 5 };
+typedef struct mcp_fwd_plan {
+  int32_t family;               /* MCP_FWD_*: small-tile kernel GP-sharded, lean kernel, 16-particle kernel GP-sharded, 16-particle, small-tile */
+  int32_t particles;            /* particles per workgroup */
+  int32_t xlds, gb, ncmax;      /* small-tile kernels: operands staged in LDS, GPs per pass, column chunks per pass */
+  int32_t lds_bytes;            /* dynamic LDS of the small-tile and lean kernels (the 16-particle kernel sizes its own) */
+  int32_t npad_max, maxdeg;     /* of the model: largest padded training set, highest polynomial degree */
+  int32_t launches;             /* kernel launches of the rollout proper */
+  int32_t particles_per_launch;
+  int32_t gsh_cs, gsh_rs, gsh_map, policy_split; /* GP-sharded 16-particle launch: workgroups per tile, row parts, deal, policy split */
+  int32_t ws_xch, ws_xj, ws_kt, ws_uxch, ws_rxch, ws_total; /* the forward workspace map: byte offsets of its regions and their end (capped at INT32_MAX) */
+  int32_t use_xj, use_kt;       /* the caller's workspace reaches the packed phase-J operands / the lean kernel's Kinv tiles */
+  int32_t zero_xch, zero_uxch, zero_rxch;        /* granule regions zeroed on the stream before the launch */
+  int32_t pack_kt, pack_xj;     /* operand packs built on the stream before the launch */
+  int32_t ran_particles, ran_gp_sharded, ran_fwd_lean, ran_row_split; /* the report words the call writes */
+} mcp_fwd_plan;
+typedef struct mcp_bwd_plan {
+  int32_t lean;                 /* 1: the latency-lean sweep */
+  int32_t pfm, um;              /* sweep class <PFM, UM> */
+  int32_t maxnt;                /* thread class of the general sweep: 256 / 512 / 1024 (0: lean) */
+  int32_t particles;            /* particles per workgroup (lean: its two slots) */
+  int32_t threads;              /* threads per workgroup */
+  int32_t pipe;                 /* general sweep: the pipelined form */
+  int32_t launches;
+  int32_t slabs;                /* per-workgroup gradient slabs the reduction sums */
+  int32_t ran_bwd_lean, ran_bwd_pipe; /* the report words the call writes */
+} mcp_bwd_plan;
+int mcp_rollout_fwd_plan(const mcp_model* model, const mcp_policy* policy, int M, int T, int particle_pred, size_t workspace_bytes, int cus,
+                         const mcp_dispatch* request, mcp_fwd_plan* plan);
+int mcp_rollout_bwd_plan(const mcp_model* model, const mcp_policy* policy, int M, int T, int particle_pred, size_t workspace_bytes, int cus,
+                         const mcp_dispatch* request, mcp_bwd_plan* plan);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,8 +15,7 @@
 // Two kernels:  rollout_bwd_kernel<PFM, UM, MAXNT, WPE, PB, PMS>  -- the general sweep (any class, 1 / 2 / 4 (wide class: 8) particles per workgroup, measurement
 // models), and  rollout_bwd_lat_kernel<GM>  -- narrow plain / angle policies on swarms up to 3072 particles: one chain wave per particle working
 // from registers beside RBF waves that prepare their step ahead of the barrier.
-#include "rollout_common.h"
-#include "../../include/mcpilco_hip_debug.h"
+#include "rollout_plan.h"
 #include <type_traits>
 
 using namespace mcp;
@@ -94,6 +93,11 @@ __host__ __device__ inline BwdLayout bwd_layout(int S, int U, int D, int G, int 
   L.rtab = take(pms ? 0 : 64 * BW_RT);  // lane roles of the register chain (serial section without a measurement model)
   L.total = o;
   return L;
+}
+
+// the layout of the instantiation <PFM, ., MAXNT, ., PB> at NT threads (the wide classes keep the RBF centres in LDS)
+static inline BwdLayout bwd_sweep_layout(const mcp_model* md, const mcp_policy* pl, int PFM, int MAXNT, int PB, int NT) {
+  return bwd_layout(md->S, md->U, md->D, md->G, pl->P, NT / 64, PB, pl->meas.n > 0, PFM > 8 || MAXNT > 512);
 }
 
 #define BW_LAUNDER(PFM, PB) ((PFM) > 8 || (PB) > 1)  // (narrow class, one particle per workgroup -- the latency-bound small-swarm sweep: measured 7 % slower with it)
@@ -962,7 +966,6 @@ __global__ __launch_bounds__(MAXNT, WPE) void rollout_bwd_kernel(BwdArgs a) {
 //     (all of it depends on x_t only), so that behind it only the multiply-adds and the 8-value wave sum remain.
 // Same gradients as the general kernel up to summation order (tests/test_gpu_parity.py compares them on every policy kind it covers).
 #define BL_GM 4    // GPs
-#define BL_MAX_M 3072  // largest swarm the lean sweep takes (tools/sweep_bwd_particles.py on a 256-CU device: it wins up to ~3000 particles)
 #define BL_FL0 8   // first feature lane of wave 0
 #define BL_UL0 16  // first input lane of wave 0
 // (scalar members only: with arrays inside, part of the struct stayed a stack object -- two of its prefetched values went through
@@ -1476,9 +1479,10 @@ __global__ __launch_bounds__(64 * GR_NW) void grad_reduce_kernel(int nblk, int n
 // ---------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------
+namespace mcp {
 // what rollout_bwd_lat_kernel covers: the narrow class with its lane roles (states on lanes 0-7, features on 8-15, inputs on 16-17),
 // up to 256 basis functions, plain / angle policies on the true or (measurement model) the measured state, disjoint index lists
-static bool bwd_lean_applies(const mcp_model* md, const mcp_policy* pl, int T) {
+bool bwd_lean_applies(const mcp_model* md, const mcp_policy* pl, int T) {
   if (T < 2 || md->G < 1 || md->G > BL_GM || md->S > 8 || pl->P > 8 || pl->U > 2 || pl->B > 256 || md->U != pl->U) return false;
   if (pl->kind != MCP_POLICY_PLAIN && pl->kind != MCP_POLICY_ANGLES) return false;
   if (pl->meas.n > 4) return false;  // (measurement pairs cross lanes by uniform-index v_readlane: up to 4 pairs on 8 state lanes)
@@ -1501,159 +1505,105 @@ static bool bwd_lean_applies(const mcp_model* md, const mcp_policy* pl, int T) {
       if (md->vel[g] == md->vel[h]) return false;
   return true;
 }
-static int bwd_threads(int B) { return imax(64, ((B + 63) / 64) * 64); }
-static int bwd_blocks(int M) { return imin(M, 1024); }
+
+// the general sweep <PFM, ., MAXNT, ., PB> can launch NT threads for this shape: thread bounds, the prefetched record, the LDS
+bool bwd_sweep_fits(const mcp_model* md, const mcp_policy* pl, int PFM, int MAXNT, int PB, int NT) {
+  if (NT > MAXNT || NT < 64 * PB) return false;
+  const bool pms = pl->meas.n > 0;
+  if (PB * bwd_rec_len(md->S, md->U, md->D, md->G, pms) > BW_RPT * (NT / 64 > PB ? NT - 64 * PB : NT)) return false;
+  return sizeof(double) * (size_t)bwd_sweep_layout(md, pl, PFM, MAXNT, PB, NT).total <= MCP_LDS_LIMIT;
+}
+}  // namespace mcp
 
 extern "C" size_t mcp_rollout_workspace_bytes(const mcp_model* model, const mcp_policy* policy, int M, int T) {
   if (!policy || M <= 0 || T <= 0) return 0;
-  size_t nparam = (size_t)policy->P + (size_t)policy->B * policy->P + (size_t)policy->U * policy->B + (size_t)policy->U;  // (+ U: dJ/dbias)
-  const size_t bwd = sizeof(double) * nparam * (size_t)bwd_blocks(M);   // mcp_rollout_bwd: per-workgroup gradient slabs
-  const size_t fwd = model ? rollout_xch_bytes(M, model->G) + rollout_xj_bytes(model) + rollout_kt_bytes(model) + rollout_uxch_bytes(M, model->G, model->U) + rollout_rxch_bytes(model, M) : 0;  // mcp_rollout_fwd: hand-off granules (GP-sharded launch) + packed phase-J operand (wide classes)
-  return bwd > fwd ? bwd : fwd;
+  return rollout_workspace_bytes(model, policy, M);
 }
 
+// register budget: 3*PFM + 2*UM doubles of per-thread accumulators plus the prefetched record; the launch bound is the
+// tightest that fits the thread count, capped so that two 256-thread workgroups share a CU
 template <int PFM, int UM, int MAXNT, int WPE, int PB, bool PMS>
-static int launch_bwd_pms(const BwdArgs& a, int grid, int NT, size_t lds, hipStream_t st) {
+static int launch_bwd_pms(const BwdArgs& a, const BwdPlan& pl, size_t lds, hipStream_t st) {
   MCP_ENSURE_MAX_LDS(rollout_bwd_kernel<PFM, UM, MAXNT, WPE, PB, PMS>);
-  hipLaunchKernelGGL((rollout_bwd_kernel<PFM, UM, MAXNT, WPE, PB, PMS>), dim3(grid), dim3(NT), lds, st, a);
-  MCP_LAUNCH_CHECK();
-  return grid;
-}
-template <int PFM, int UM, int MAXNT, int WPE, int PB>
-static int launch_bwd(const BwdArgs& a, int NT, hipStream_t st) {
-  if (NT > MAXNT || NT < 64 * PB) return MCP_ERR_LIMIT;
-  const mcp_model& md = a.model;
-  const bool pms = a.pol.meas.n > 0;
-  if (PB * bwd_rec_len(md.S, md.U, md.D, md.G, pms) > BW_RPT * (NT / 64 > PB ? NT - 64 * PB : NT)) return MCP_ERR_LIMIT;
-  const int grid = imin((a.M + PB - 1) / PB, 1024);
-  BwdLayout L = bwd_layout(md.S, md.U, md.D, md.G, a.pol.P, NT / 64, PB, pms, PFM > 8 || MAXNT > 512);
-  const size_t lds = sizeof(double) * (size_t)L.total;
-  if (lds > MCP_LDS_LIMIT) return MCP_ERR_LIMIT;
-  return pms ? launch_bwd_pms<PFM, UM, MAXNT, WPE, PB, true>(a, grid, NT, lds, st) : launch_bwd_pms<PFM, UM, MAXNT, WPE, PB, false>(a, grid, NT, lds, st);
-}
-
-static int rollout_bwd_impl(const mcp_model* model, const mcp_policy* policy, const mcp_noise* noise, int M, int T,
-                               const double* states, const double* inputs, const double* jac, const double* g_states,
-                               const double* g_inputs, double* g_log_ls, double* g_centers, double* g_weight, double* g_x0,
-                               void* workspace, size_t workspace_bytes, void* stream, unsigned long long* g_bwd_stamps, int g_force_bwd_pb, int g_bwd_lean, int& g_last_bwd_lean,
-                               int g_bwd_pipe = -1, int* g_last_bwd_pipe = nullptr) {
-  if (!noise || !states || !inputs || !g_log_ls || !g_centers || !g_weight || !workspace || !policy || M <= 0 || T <= 0) return MCP_ERR_ARG;
-  if (T > 1 && !jac) return MCP_ERR_ARG;
-  if (policy->meas.n > 0 && !policy->meas.meas) return MCP_ERR_ARG;
-  mcp_model stub;
-  if (!model) {
-    if (T != 1) return MCP_ERR_ARG;
-    stub = policy_only_model(policy);
-    model = &stub;
-  } else if (!model_ok(model)) {
-    return MCP_ERR_ARG;
-  }
-  if (!policy_ok(policy, model->S, model->U, T)) return MCP_ERR_ARG;
-  if (!policy_basis_ok(policy)) return MCP_ERR_LIMIT;
-  if (workspace_bytes < mcp_rollout_workspace_bytes(model, policy, M, T)) return MCP_ERR_WORKSPACE;
-  BwdArgs a;
-  a.model = *model;
-  a.pol = *policy;
-  a.nz = *noise;
-  a.M = M;
-  a.T = T;
-  a.states = states;
-  a.inputs = inputs;
-  a.jac = jac;
-  a.g_states = g_states;
-  a.g_inputs = g_inputs;
-  a.slab = (double*)workspace;
-  a.g_x0 = g_x0;
-  a.stamps = g_bwd_stamps;
-  a.m_base = 0;
-  a.slab_accum = 0;
-  a.pipe = 0;
-  hipStream_t st = (hipStream_t)stream;
-  const int PF = policy->P, U = policy->U;
-  // particles per workgroup: large swarms are latency bound per workgroup, so several particles share one sweep; small
-  // swarms keep one particle per workgroup to spread over the CUs
-  // (two 256-thread workgroups per CU are resident: one particle per workgroup while M of them fit in one round, then 2, then 4;
-  //  measured, tools/sweep_bwd_particles.py: M=800 1.74 / 1.34 / 1.92 ms, M=2000 3.24 / 2.51 / 2.07 ms for 1 / 2 / 4)
-  int PB = g_force_bwd_pb ? g_force_bwd_pb : (M > 2816 ? 4 : (M > 512 ? 2 : 1));  // (round 3, after the RBF stage's diet: 2 particles win up to ~2800, tools/sweep_bwd_particles.py)
-  if (!g_force_bwd_pb && (PF > 16 || U > 4)) {
-    PB = M > 1024 ? 4 : 1;
-    // eight per sweep (round 4) where that saves resident rounds: a 512-thread workgroup of this class has a CU to itself (256 per round), and a
-    // step of eight particles costs 1.86 x a step of four (tools/phase_stamps.py c5: 64.7 k vs 34.7 k cycles -- the RBF stage is per particle) --
-    // M = 2000: one round instead of two, 8.74 -> 8.1 ms; M = 3072: two instead of three, slower (16.8 vs 13.6 ms)
-    const int r4 = (((M + 3) / 4) + 255) / 256, r8 = (((M + 7) / 8) + 255) / 256;
-    if (PB == 4 && bwd_threads(policy->B) > 256 && 1.86 * r8 < (double)r4) PB = 8;  // (the 512-thread instantiation: > 256 basis functions)
-  }  // wide policies: eight (round 4; four before) particles per sweep on large swarms where the
-                                                                      // instantiation exists (> 256 basis functions), else two
-                                                                      // (tools/time_bwd.py, UR5 shape, M = 2000, T = 300: 18.1 / 15.5 / 14.5 ms for 1 / 2 / 4)
-  if (PB != 1 && PB != 2 && PB != 4 && PB != 8) return MCP_ERR_ARG;
-  int NT = imax(bwd_threads(policy->B), 64 * PB);
-  int rc = MCP_ERR_LIMIT;
-  g_last_bwd_lean = 0;
-  if (g_bwd_lean != 0 && !g_force_bwd_pb && M <= BL_MAX_M && model != &stub && bwd_lean_applies(model, policy, T)) {
-    // small swarm, narrow class: the latency-lean sweep (wave 0 = the chain, the basis functions in the waves behind it)
-    const int nt = 2 * (64 + bwd_threads(policy->B));  // two particle slots per workgroup
-    for (int mb = 0; mb < M; mb += 512) {           // one launch per 512 particles = 256 workgroups: a resident round each
-      const int grid = (imin(M - mb, 512) + 1) / 2;
-      a.m_base = mb;
-      a.slab_accum = mb >= 1024;
-      if (policy->meas.n > 0) {
-        if (model->G <= 2)
-          hipLaunchKernelGGL((rollout_bwd_lat_kernel<2, true>), dim3(grid), dim3(nt), 0, st, a);
-        else
-          hipLaunchKernelGGL((rollout_bwd_lat_kernel<BL_GM, true>), dim3(grid), dim3(nt), 0, st, a);
-      } else if (model->G <= 2) {
-        hipLaunchKernelGGL((rollout_bwd_lat_kernel<2, false>), dim3(grid), dim3(nt), 0, st, a);
-      } else {
-        hipLaunchKernelGGL((rollout_bwd_lat_kernel<BL_GM, false>), dim3(grid), dim3(nt), 0, st, a);
-      }
-      MCP_LAUNCH_CHECK();
-    }
-    g_last_bwd_lean = 1;
-    rc = imin(M, 1024);  // slabs: one per particle, modulo the 1024 the workspace holds
-    PB = 0;
-  }
-  // register budget: 3*PFM + 2*UM doubles of per-thread accumulators plus the prefetched record; the launch bound is the
-  // tightest that fits the thread count, capped so that two 256-thread workgroups share a CU
-  for (; PB >= 1 && rc == MCP_ERR_LIMIT; PB >>= 1) {
-    // one particle per workgroup on the 512-thread wide instantiations, no measurement model, a wave to spare: the pipelined form (PIPEC)
-    a.pipe = (PB == 1 && g_bwd_pipe != 0 && !(PF <= 16 && U <= 4) && NT > 256 && NT + 64 <= 512 && policy->meas.n == 0) ? 1 : 0;
-    if (PF <= 8 && U <= 2) {
-      if (NT <= 256)
-        rc = PB == 4 ? launch_bwd<8, 2, 256, BW_WPE_A, 4>(a, NT, st) : PB == 2 ? launch_bwd<8, 2, 256, BW_WPE_A, 2>(a, NT, st) : launch_bwd<8, 2, 256, BW_WPE_A, 1>(a, NT, st);
-      else
-        rc = PB == 1 ? launch_bwd<8, 2, 1024, 4, 1>(a, NT, st) : MCP_ERR_LIMIT;
-    } else if (PF <= 16 && U <= 4) {
-      if (NT <= 256)
-        rc = PB == 2 ? launch_bwd<16, 4, 256, BW_WPE_A, 2>(a, NT, st) : PB == 1 ? launch_bwd<16, 4, 256, BW_WPE_A, 1>(a, NT, st) : MCP_ERR_LIMIT;
-      else
-        rc = PB == 1 ? launch_bwd<16, 4, 1024, 4, 1>(a, NT, st) : MCP_ERR_LIMIT;
-    } else if (PF <= 24 && U <= 6) {  // UR5 class
-      if (NT <= 256)
-        rc = PB == 2 ? launch_bwd<24, 6, 256, BW_WPE_A, 2>(a, NT, st) : PB == 1 ? launch_bwd<24, 6, 256, BW_WPE_A, 1>(a, NT, st) : MCP_ERR_LIMIT;
-      else
-        rc = PB == 8   ? launch_bwd<24, 6, 512, 2, 8>(a, NT, st)
-             : PB == 4 ? launch_bwd<24, 6, 512, 2, 4>(a, NT, st)
-             : PB == 2 ? launch_bwd<24, 6, 512, 2, 2>(a, NT, st)
-             : PB == 1 ? launch_bwd<24, 6, 512, 2, 1>(a, NT + 64 * a.pipe, st)
-                       : MCP_ERR_LIMIT;
-    } else {
-      if (NT <= 256)
-        rc = PB == 2 ? launch_bwd<MCP_MAX_PFEAT, MCP_MAX_INPUT, 256, BW_WPE_A, 2>(a, NT, st)
-                     : PB == 1 ? launch_bwd<MCP_MAX_PFEAT, MCP_MAX_INPUT, 256, BW_WPE_A, 1>(a, NT, st) : MCP_ERR_LIMIT;
-      else
-        rc = PB == 2 ? launch_bwd<MCP_MAX_PFEAT, MCP_MAX_INPUT, 512, 2, 2>(a, NT, st)
-                     : PB == 1 ? launch_bwd<MCP_MAX_PFEAT, MCP_MAX_INPUT, 512, 2, 1>(a, NT + 64 * a.pipe, st) : MCP_ERR_LIMIT;
-    }
-    if (rc == MCP_ERR_LIMIT && PB > 1) NT = imax(bwd_threads(policy->B), 64 * (PB >> 1));
-  }
-  if (rc < 0) return rc;
-  if (g_last_bwd_pipe) *g_last_bwd_pipe = a.pipe;  // (set by the launch that went out; 0 when the lean sweep ran)
-  const int grid = rc;
-  const int nparam = PF + policy->B * PF + U * policy->B + (policy->bias ? U : 0);
-  hipLaunchKernelGGL(grad_reduce_kernel, dim3((nparam + 63) / 64), dim3(64 * GR_NW), 0, st, grid, nparam, PF, policy->B * PF, U * policy->B, a.slab,
-                     g_log_ls, g_centers, g_weight, policy->bias ? policy->g_bias : nullptr);
+  hipLaunchKernelGGL((rollout_bwd_kernel<PFM, UM, MAXNT, WPE, PB, PMS>), dim3(pl.slabs), dim3(pl.threads), lds, st, a);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
+}
+template <int PFM, int UM, int MAXNT, int WPE, int PB>
+static int launch_bwd(const BwdArgs& a, const BwdPlan& pl, hipStream_t st) {
+  const size_t lds = sizeof(double) * (size_t)bwd_sweep_layout(&a.model, &a.pol, PFM, MAXNT, PB, pl.threads).total;
+  return a.pol.meas.n > 0 ? launch_bwd_pms<PFM, UM, MAXNT, WPE, PB, true>(a, pl, lds, st) : launch_bwd_pms<PFM, UM, MAXNT, WPE, PB, false>(a, pl, lds, st);
+}
+// the instantiation the plan names (rollout_plan.h, bwd_sweep_exists, lists the same ones)
+static int launch_bwd_sweep(const BwdArgs& a, const BwdPlan& pl, hipStream_t st) {
+#define BW_KEY(PFM, MAXNT, PB) (((PFM) * 2048 + (MAXNT)) * 16 + (PB))
+#define BW_CASE(PFM, UM, MAXNT, WPE, PB) \
+  case BW_KEY(PFM, MAXNT, PB): return launch_bwd<PFM, UM, MAXNT, WPE, PB>(a, pl, st)
+  switch (BW_KEY(pl.pfm, pl.maxnt, pl.particles)) {
+    BW_CASE(8, 2, 256, BW_WPE_A, 1);
+    BW_CASE(8, 2, 256, BW_WPE_A, 2);
+    BW_CASE(8, 2, 256, BW_WPE_A, 4);
+    BW_CASE(8, 2, 1024, 4, 1);
+    BW_CASE(16, 4, 256, BW_WPE_A, 1);
+    BW_CASE(16, 4, 256, BW_WPE_A, 2);
+    BW_CASE(16, 4, 1024, 4, 1);
+    BW_CASE(24, 6, 256, BW_WPE_A, 1);  // UR5 class
+    BW_CASE(24, 6, 256, BW_WPE_A, 2);
+    BW_CASE(24, 6, 512, 2, 1);
+    BW_CASE(24, 6, 512, 2, 2);
+    BW_CASE(24, 6, 512, 2, 4);
+    BW_CASE(24, 6, 512, 2, 8);
+    BW_CASE(MCP_MAX_PFEAT, MCP_MAX_INPUT, 256, BW_WPE_A, 1);
+    BW_CASE(MCP_MAX_PFEAT, MCP_MAX_INPUT, 256, BW_WPE_A, 2);
+    BW_CASE(MCP_MAX_PFEAT, MCP_MAX_INPUT, 512, 2, 1);
+    BW_CASE(MCP_MAX_PFEAT, MCP_MAX_INPUT, 512, 2, 2);
+    default: return MCP_ERR_LIMIT;
+  }
+#undef BW_CASE
+#undef BW_KEY
+}
+// the lean sweep: one launch per 512 particles = 256 workgroups of two particle slots, a resident round each
+static int launch_bwd_lean(BwdArgs& a, const BwdPlan& pl, hipStream_t st) {
+  for (int mb = 0; mb < a.M; mb += 512) {
+    const int grid = (imin(a.M - mb, 512) + 1) / 2;
+    a.m_base = mb;
+    a.slab_accum = mb >= 1024;
+    if (a.pol.meas.n > 0) {
+      if (a.model.G <= 2)
+        hipLaunchKernelGGL((rollout_bwd_lat_kernel<2, true>), dim3(grid), dim3(pl.threads), 0, st, a);
+      else
+        hipLaunchKernelGGL((rollout_bwd_lat_kernel<BL_GM, true>), dim3(grid), dim3(pl.threads), 0, st, a);
+    } else if (a.model.G <= 2) {
+      hipLaunchKernelGGL((rollout_bwd_lat_kernel<2, false>), dim3(grid), dim3(pl.threads), 0, st, a);
+    } else {
+      hipLaunchKernelGGL((rollout_bwd_lat_kernel<BL_GM, false>), dim3(grid), dim3(pl.threads), 0, st, a);
+    }
+    MCP_LAUNCH_CHECK();
+  }
+  return MCP_OK;
+}
+
+// the sweep the plan names, then the fixed-order sum of its slabs
+static int run_bwd_plan(BwdArgs& a, const BwdPlan& pl, double* g_log_ls, double* g_centers, double* g_weight, hipStream_t st) {
+  a.pipe = pl.pipe;
+  const int rc = pl.lean ? launch_bwd_lean(a, pl, st) : launch_bwd_sweep(a, pl, st);
+  if (rc != MCP_OK) return rc;
+  const mcp_policy& p = a.pol;
+  const int nparam = p.P + p.B * p.P + p.U * p.B + (p.bias ? p.U : 0);
+  hipLaunchKernelGGL(grad_reduce_kernel, dim3((nparam + 63) / 64), dim3(64 * GR_NW), 0, st, pl.slabs, nparam, p.P, p.B * p.P, p.U * p.B, a.slab,
+                     g_log_ls, g_centers, g_weight, p.bias ? p.g_bias : nullptr);
+  MCP_LAUNCH_CHECK();
+  return MCP_OK;
+}
+
+static const mcp_dispatch g_automatic = {};  // the request of the plain entry point
+
+extern "C" int mcp_rollout_bwd_plan(const mcp_model* model, const mcp_policy* policy, int M, int T, int particle_pred, size_t workspace_bytes, int cus,
+                                    const mcp_dispatch* request, mcp_bwd_plan* plan) {
+  (void)particle_pred;  // (the sweep does not depend on the flags or on the device's size: same signature as the forward query)
+  (void)cus;
+  if (!plan) return MCP_ERR_ARG;
+  return plan_bwd(model, policy, M, T, workspace_bytes > 0, workspace_bytes, request ? request : &g_automatic, plan);
 }
 
 extern "C" int mcp_rollout_bwd_ex(const mcp_model* model, const mcp_policy* policy, const mcp_noise* noise, int M, int T,
@@ -1661,11 +1611,34 @@ extern "C" int mcp_rollout_bwd_ex(const mcp_model* model, const mcp_policy* poli
                                const double* g_inputs, double* g_log_ls, double* g_centers, double* g_weight, double* g_x0,
                                void* workspace, size_t workspace_bytes, void* stream, mcp_dispatch* d) {
   // (the request travels with the call: include/mcpilco_hip_debug.h; d == NULL: automatic)
-  int last_lean = 0, last_pipe = 0;
-  const int rc = rollout_bwd_impl(model, policy, noise, M, T, states, inputs, jac, g_states, g_inputs, g_log_ls, g_centers, g_weight, g_x0, workspace, workspace_bytes, stream, d ? (unsigned long long*)d->bwd_stamps : nullptr, d ? d->bwd_particles : 0,
-                                  (d && d->bwd_lean == 1) ? 0 : -1, last_lean, (d && d->bwd_pipe == 1) ? 0 : -1, &last_pipe);
-  if (d) d->ran_bwd_lean = last_lean;
-  if (d) d->ran_bwd_pipe = last_pipe;
+  const mcp_dispatch* rq = d ? d : &g_automatic;
+  BwdPlan pl = {};
+  int rc = MCP_ERR_ARG;
+  if (noise && states && inputs && g_log_ls && g_centers && g_weight && !(T > 1 && !jac))
+    rc = plan_bwd(model, policy, M, T, workspace != nullptr, workspace_bytes, rq, &pl);
+  if (rc == MCP_OK) {
+    BwdArgs a;
+    a.model = model ? *model : policy_only_model(policy);
+    a.pol = *policy;
+    a.nz = *noise;
+    a.M = M;
+    a.T = T;
+    a.states = states;
+    a.inputs = inputs;
+    a.jac = jac;
+    a.g_states = g_states;
+    a.g_inputs = g_inputs;
+    a.slab = (double*)workspace;
+    a.g_x0 = g_x0;
+    a.stamps = (unsigned long long*)rq->bwd_stamps;
+    a.m_base = 0;
+    a.slab_accum = 0;
+    rc = run_bwd_plan(a, pl, g_log_ls, g_centers, g_weight, (hipStream_t)stream);
+  }
+  if (d) {
+    d->ran_bwd_lean = rc == MCP_OK ? pl.ran_bwd_lean : 0;
+    d->ran_bwd_pipe = rc == MCP_OK ? pl.ran_bwd_pipe : 0;
+  }
   return rc;
 }
 extern "C" int mcp_rollout_bwd(const mcp_model* model, const mcp_policy* policy, const mcp_noise* noise, int M, int T,

@@ -33,7 +33,6 @@
 using namespace mcp;
 
 #define RF_MAX_NA 7  // accumulators per Jacobian item: 2 (SE), 3 (SE+P1), 7 (SE+P2)
-#define RF_MAX_CHUNKS (MCP_MAX_GP * (MCP_MAX_TRAIN / 128))
 #define RF_GS 8  // rows of Kinv per register buffer (two buffers in flight per wave)
 #define RF_NRES 1  // register groups of Kinv a wave keeps resident for the whole rollout (GP-sharded 4-particle launch)
 
@@ -52,7 +51,6 @@ struct FwdLayout {
 #define TAB_SLO (TAB_WC0 + RF_NW)            // first / last partial-sum slot of a chunk (phase vsum)
 #define TAB_SHI (TAB_SLO + RF_MAX_CHUNKS)
 #define TAB_INTS (TAB_SHI + RF_MAX_CHUNKS)
-#define RF_CW 128  // rows of v per column chunk: 64 lanes x 2 rows (one 16-byte load per lane)
 
 // GX = number of GPs whose operands are staged in LDS (G, or 1 in a GP-sharded launch)
 __host__ __device__ inline FwdLayout fwd_layout(int P, int S, int U, int D, int G, int PF, int B, int NpadMax, int maxdeg, int GB,
@@ -1174,53 +1172,9 @@ __global__ void posterior_bwd_kernel(int M, int D, const double* __restrict__ gm
 // ---------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------
-static int pick_particles_per_wg(int M) {
-  // small swarms: spread over as many CUs as possible (every workgroup re-streams Kinv, so the
-  // per-CU L2->L1 rate is the bound); large swarms: amortise the Kinv stream over more particles
-  if (M <= 256) return 1;
-  if (M <= 1024) return 2;
-  return 16;  // falls back to 4 when the model does not fit the tile kernel
-}
-
-// What a call may be asked to do differently from the automatic dispatch, and what it reports back: carried by the call itself
-// (mcp_dispatch, include/mcpilco_hip_debug.h) -- the library holds no dispatch state.  The values below are the ones the dispatch code reads.
-// the automatic row split of the GP-sharded 16-particle kernel: parts and deal
-#define MCP_ROW_PARTS_DEFAULT 3
-#define MCP_ROW_PART_MAJOR_DEFAULT 1
-struct FwdHooks {
-  int force_ppw = 0;     // particles per workgroup (0 = automatic)
-  int force_xlds = -1;   // -1 automatic, 0 never stage small operands in LDS
-  int force_gb = 0;      // GPs per pass (0 = as many as fit)
-  int gp_sharding = -1;  // -1 automatic, 0 never, 1 whenever the grid fits the device
-  int policy_split = -1; // -1 automatic, 0 every member evaluates the whole policy, 1 the split whenever the shape allows it
-  int fwd_lean = -1;     // -1 / 1 the latency-lean kernel wherever it applies, 0 never
-  int row_split = -1;    // -1 automatic, 0 one workgroup per (tile, GP range), 2 / 3 that many (row parts of Kinv) whenever the shape allows it
-  int cluster_map = -1;  // -1 automatic, 0 the members of a tile on one XCD, 1 row part major (FwdArgs.gsh_map)
-  unsigned long long* stamps = nullptr;
-  unsigned stamp_block = 0;
-  int last_ppw = 0, last_sharded = 0, last_lean = 0, last_row_split = 0;  // report
-};
-static FwdHooks fwd_hooks(const mcp_dispatch* d) {
-  FwdHooks h;
-  if (d) {
-    h.force_ppw = d->fwd_particles;
-    h.force_xlds = d->fwd_no_xlds ? 0 : -1;
-    h.force_gb = d->fwd_gb;
-    h.gp_sharding = d->gp_sharding == 1 ? 0 : (d->gp_sharding == 2 ? 1 : -1);
-    h.policy_split = d->policy_split == 1 ? 0 : (d->policy_split == 2 ? 1 : -1);
-    h.fwd_lean = d->fwd_lean == 1 ? 0 : -1;
-    h.row_split = d->row_split == 1 ? 0 : ((d->row_split == 2 || d->row_split == 3) ? d->row_split : -1);
-    h.cluster_map = d->cluster_map == 1 ? 0 : (d->cluster_map == 2 ? 1 : -1);
-    h.stamps = (unsigned long long*)d->fwd_stamps;
-    h.stamp_block = d->stamp_block;
-  }
-  return h;
-}
-static const int g_gp_max_launches = 2;  // a swarm goes out GP-sharded when it fits this many resident grids (cart-pole shape, forward ms,
-                                         // tools/sweep_fwd_swarm.py: M=1024 two launches 4.9 vs 6.5 unsharded; M=1280 three launches 7.3 vs 6.9 on the tile kernel)
-static int gsh_grid(int nclusters, int G) { return ((nclusters + 7) / 8) * 8 * G; }
-// every workgroup of a GP-sharded grid waits for its partners, so the whole grid must be resident: one 512-thread
-// workgroup per CU (the LDS footprint allows no more)
+// What a call may be asked to do differently from the automatic dispatch, and what it reports back, is carried by the call itself
+// (mcp_dispatch, include/mcpilco_hip_debug.h) -- the library holds no dispatch state.  The call is validated, planned (rollout_plan.h: a pure
+// function of the descriptors' scalars, the request and the device's CU count) and the plan is run.
 static int device_cu_count() {
   static int cus[64];
   int dev = 0;
@@ -1233,26 +1187,11 @@ static int device_cu_count() {
   return cus[dev];
 }
 
-// Workgroups per tile with which the GP-sharded 16-particle kernel can take the whole swarm in one resident grid (0 = it cannot):
-// the largest divisor of G that fits, i.e. the fewest GPs per workgroup (rollout_fwd_tile.hip: cart-pole and UR5 register classes)
-static int tile_sharded_cluster(const mcp_model* m, const mcp_policy* p, int NpadMax, int M, int T) {
-  if (m->G < 2 || T <= 1 || NpadMax > 512) return 0;
-  if (!(m->D <= 24 && p->P <= 24 && m->U <= 6) || !fwd_tile_fits(m, p)) return 0;
-  const int cus = device_cu_count(), ncl = (M + 15) / 16;
-  for (int cs = m->G; cs >= 2; --cs)
-    if (m->G % cs == 0 && ((ncl + 7) / 8) * 8 * cs <= cus) return cs;
-  return 0;
+namespace mcp {
+size_t fwd_small_lds_bytes(const mcp_model* m, const mcp_policy* p, int P, int NpadMax, int maxdeg, int GB, int NCmax, bool xlds, bool sharded) {
+  return sizeof(double) * (size_t)fwd_layout(P, m->S, m->U, m->D, m->G, p->P, p->B, NpadMax, maxdeg, GB, NCmax, xlds, sharded ? 1 : -1).total;
 }
-
-static int chunks_in_pass(const mcp_model* m, int GB) {
-  int best = 0;
-  for (int g0 = 0; g0 < m->G; g0 += GB) {
-    int nc = 0;
-    for (int g = g0; g < m->G && g < g0 + GB; ++g) nc += (m->gp[g].Npad + RF_CW - 1) / RF_CW;
-    best = imax(best, nc);
-  }
-  return best;
-}
+}  // namespace mcp
 
 template <int P, bool XLDS, int MAXDEG, bool GSH>
 static int launch_fwd_deg(const FwdArgs& a, size_t lds, hipStream_t st) {
@@ -1271,218 +1210,86 @@ template <int P>
 static int launch_fwd_sharded(const FwdArgs& a, size_t lds, hipStream_t st) {
   return a.maxdeg == 0 ? launch_fwd_deg<P, true, 0, true>(a, lds, st) : launch_fwd_deg<P, true, 2, true>(a, lds, st);
 }
+static int launch_fwd_small(const FwdArgs& a, int P, bool xlds, size_t lds, hipStream_t st) {
+  if (P == 4) return xlds ? launch_fwd<4, true>(a, lds, st) : launch_fwd<4, false>(a, lds, st);
+  if (P == 2) return xlds ? launch_fwd<2, true>(a, lds, st) : launch_fwd<2, false>(a, lds, st);
+  return xlds ? launch_fwd<1, true>(a, lds, st) : launch_fwd<1, false>(a, lds, st);
+}
 
-static int rollout_fwd_impl(const mcp_model* model, const mcp_policy* policy, const mcp_noise* noise, int M, int T, int particle_pred,
-                            const double* x0, double* states, double* inputs, double* jac, uint32_t* status, void* workspace,
-                            size_t workspace_bytes, void* stream, FwdHooks& hk) {
-  if (!noise || !x0 || !states || !inputs || !status || !policy || M <= 0 || T <= 0) return MCP_ERR_ARG;
-  const bool no_gp_sharding = (particle_pred & MCP_FWD_NO_GP_SHARDING) != 0;  // (the recovery path after MCP_STATUS_SYNC keeps its workspace)
-  const int operands_packed = ((particle_pred & MCP_FWD_KT_PACKED) ? 1 : 0) | ((particle_pred & MCP_FWD_XJ_PACKED) ? 2 : 0);
-  particle_pred &= 1;
-  mcp_model stub;
-  if (!model) {
-    if (T != 1) return MCP_ERR_ARG;  // without a dynamics model only the policy can be evaluated
-    stub = policy_only_model(policy);
-    model = &stub;
-  } else if (!model_ok(model)) {
-    return MCP_ERR_ARG;
-  }
-  if (!policy_ok(policy, model->S, model->U, T)) return MCP_ERR_ARG;
-  if (!policy_basis_ok(policy)) return MCP_ERR_LIMIT;
+// the kernel argument of a planned call: the workspace regions the plan uses, at the offsets of fwd_workspace
+static FwdArgs fwd_args(const mcp_model* model, const mcp_policy* policy, const mcp_noise* noise, int M, int T, int flags, const double* x0,
+                        double* states, double* inputs, double* jac, uint32_t* status, void* workspace, const mcp_dispatch* rq, const FwdPlan& pl) {
+  const FwdWorkspace w = fwd_workspace(model, M);
+  char* ws = (char*)workspace;
+  const bool sharded = pl.zero_xch != 0;
   FwdArgs a;
   a.model = *model;
   a.pol = *policy;
   a.nz = *noise;
   a.M = M;
   a.T = T;
-  a.particle_pred = particle_pred;
-  a.operands_packed = operands_packed;
-  a.NpadMax = 0;
-  a.maxdeg = 0;
-  for (int g = 0; g < model->G; ++g) {
-    a.NpadMax = imax(a.NpadMax, model->gp[g].Npad);
-    a.maxdeg = imax(a.maxdeg, model->gp[g].kern.poly_deg);
-  }
+  a.particle_pred = flags & 1;
+  a.operands_packed = ((flags & MCP_FWD_KT_PACKED) ? 1 : 0) | ((flags & MCP_FWD_XJ_PACKED) ? 2 : 0);
+  a.NpadMax = pl.npad_max;
+  a.maxdeg = pl.maxdeg;
+  a.GB = pl.gb;
+  a.NCmax = pl.ncmax;
   a.x0 = x0;
   a.states = states;
   a.inputs = inputs;
   a.jac = jac;
   a.status = status;
-  a.stamps = hk.stamps;
-  a.stamp_block = hk.stamp_block;
-  a.xch = nullptr;
-  a.xj = nullptr;
-  a.xj_stride = 0;
-  {
-    const size_t xoff = rollout_xch_bytes(M, model->G), xb = rollout_xj_bytes(model);
-    if (xb && workspace && workspace_bytes >= xoff + xb) {
-      a.xj = (double*)((char*)workspace + xoff);
-      a.xj_stride = (int)(xb / sizeof(double) / (size_t)model->G);
-    }
-  }
-  a.kt = nullptr;
-  a.kt_stride = 0;
-  {
-    const size_t koff = rollout_xch_bytes(M, model->G) + rollout_xj_bytes(model), kb_ = rollout_kt_bytes(model);
-    if (kb_ && workspace && workspace_bytes >= koff + kb_) {
-      a.kt = (const double*)((char*)workspace + koff);
-      a.kt_stride = a.NpadMax * a.NpadMax;
-    }
-  }
-  a.nclusters = 0;
+  a.stamps = (unsigned long long*)rq->fwd_stamps;
+  a.stamp_block = rq->stamp_block;
+  a.xj = pl.use_xj ? (double*)(ws + w.xj) : nullptr;
+  a.xj_stride = pl.use_xj ? (int)((w.kt - w.xj) / sizeof(double) / (size_t)model->G) : 0;
+  a.kt = pl.use_kt ? (const double*)(ws + w.kt) : nullptr;
+  a.kt_stride = pl.use_kt ? pl.npad_max * pl.npad_max : 0;
+  a.xch = sharded ? (unsigned long long*)(ws + w.xch) : nullptr;
+  a.nclusters = pl.family == MCP_FWD_TILE_SHARDED ? (M + 15) / 16 : 0;
   a.m_off = 0;
   a.m_cnt = M;
-  a.gsh_cs = 0;
-  a.uxch = nullptr;
-  a.gsh_rs = 1;
-  a.gsh_map = 0;
-  a.rxch = nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  // configuration search: most particles per workgroup first, operands in LDS if they fit, all GPs per pass if they fit
-  int P0 = hk.force_ppw ? hk.force_ppw : pick_particles_per_wg(M);
-  if (P0 != 1 && P0 != 2 && P0 != 4 && P0 != 16) return MCP_ERR_ARG;
-  if (policy->meas.n > 0 && !policy->meas.meas) return MCP_ERR_ARG;
-  // small swarms: shard the GPs of a particle cluster over G workgroups (each streams one Kinv) when the whole grid is
-  // resident at one workgroup per CU; smallest cluster size first (most CUs busy)
-  hk.last_sharded = 0;
-  hk.last_lean = 0;
-  hk.last_row_split = 0;
-  if (hk.gp_sharding != 0 && !no_gp_sharding && model->G >= 2 && T > 1 && workspace && workspace_bytes >= rollout_xch_bytes(M, model->G) &&
-      (hk.force_ppw == 0 || (hk.gp_sharding == 1 && hk.force_ppw != 16))) {
-    const int cus = device_cu_count();
-    int NC1 = 0;
-    for (int g = 0; g < model->G; ++g) NC1 = imax(NC1, (model->gp[g].Npad + RF_CW - 1) / RF_CW);
-    const bool forced = hk.force_ppw == 1 || hk.force_ppw == 2 || hk.force_ppw == 4;
-    const bool tile_sh = tile_sharded_cluster(model, policy, a.NpadMax, M, T) > 0;
-    a.xch = (unsigned long long*)workspace;
-    a.GB = 1;
-    a.NCmax = NC1;
-    for (int P = forced ? hk.force_ppw : 1; P <= (forced ? hk.force_ppw : 4) && NC1 <= RF_MAX_CHUNKS; P <<= 1) {
-      // particles one resident grid takes at this cluster size (whole groups of 8 clusters, G workgroups each)
-      const int cap = (cus / (8 * model->G)) * 8 * P;
-      if (cap <= 0) break;
-      // up to g_gp_max_launches launches back to back (each resident on its own; they may overlap where one drains and the next
-      // starts, which only delays a partner)
-      const int nchunk = (M + cap - 1) / cap;
-      if (nchunk > 1 && (P < 4 || nchunk > g_gp_max_launches || (!forced && tile_sh))) continue;  // (the sharded 16-particle kernel is the faster form then)
-      FwdLayout L = fwd_layout(P, model->S, model->U, model->D, model->G, policy->P, policy->B, a.NpadMax, a.maxdeg, 1, NC1, true, 1);
-      size_t lds = sizeof(double) * (size_t)L.total;
-      bool lean = false;
-      if (hk.fwd_lean != 0 && a.kt) {
-        const size_t ll = fwd_lean_lds_bytes(model, policy, P, a.NpadMax, a.maxdeg);  // 0: the lean kernel does not take this shape
-        if (ll > 0 && ll <= MCP_LDS_LIMIT) {
-          lean = true;
-          lds = ll;
-        }
-      }
-      if (lds > MCP_LDS_LIMIT) break;
-      if (hipMemsetAsync(workspace, 0, rollout_xch_bytes(M, model->G), st) != hipSuccess) return MCP_ERR_LAUNCH;
-      if (lean && !(a.operands_packed & 1)) {  // Kinv of every GP as MFMA operand tiles, in each wave's streaming order (unless an earlier call left them)
-        const int rcp = launch_fwd_lean_pack(a, st);
-        if (rcp != MCP_OK) return rcp;
-      }
-      hk.last_ppw = P;
-      hk.last_sharded = nchunk;
-      hk.last_lean = lean ? 1 : 0;
-      const int per = (((M + nchunk - 1) / nchunk + P - 1) / P) * P;  // particles per launch, whole clusters
-      for (int off = 0; off < M; off += per) {
-        a.m_off = off;
-        a.m_cnt = imin(per, M - off);
-        a.nclusters = (a.m_cnt + P - 1) / P;
-        const int rc = lean ? launch_fwd_lean(a, P, lds, st)
-                            : (P == 4 ? launch_fwd_sharded<4>(a, lds, st) : (P == 2 ? launch_fwd_sharded<2>(a, lds, st) : launch_fwd_sharded<1>(a, lds, st)));
-        if (rc != MCP_OK) return rc;
-      }
-      return MCP_OK;
-    }
+  a.gsh_cs = pl.gsh_cs;
+  a.uxch = pl.policy_split ? (unsigned long long*)(ws + w.uxch) : nullptr;
+  a.gsh_rs = pl.gsh_rs > 1 ? pl.gsh_rs : 1;
+  a.gsh_map = pl.gsh_map;
+  a.rxch = pl.zero_rxch ? (unsigned long long*)(ws + w.rxch) : nullptr;
+  return a;
+}
+
+// memsets, operand packs and launches of a plan, in that order on the stream
+static int run_fwd_plan(FwdArgs& a, const FwdPlan& pl, hipStream_t st) {
+  const mcp_model& m = a.model;
+  if (pl.zero_xch && hipMemsetAsync(a.xch, 0, rollout_xch_bytes(a.M, m.G), st) != hipSuccess) return MCP_ERR_LAUNCH;
+  if (pl.zero_uxch) {  // (the granules this launch's clusters use, not the whole region)
+    const size_t ub = (size_t)a.nclusters * 2 * a.gsh_cs * 16 * m.U * 2 * sizeof(unsigned long long);
+    if (hipMemsetAsync(a.uxch, 0, ub, st) != hipSuccess) return MCP_ERR_LAUNCH;
   }
-  if ((P0 == 16 || hk.force_ppw == 0) && hk.gp_sharding != 0 && !no_gp_sharding && workspace && workspace_bytes >= rollout_xch_bytes(M, model->G) &&
-      tile_sharded_cluster(model, policy, a.NpadMax, M, T) > 0) {
-    // swarms beyond one resident grid of the small-tile kernel, up to 2048 particles at two GPs: the 16-particle kernel GP-sharded --
-    // twice the workgroups, each with one GP's contractions (tools/sweep_fwd_swarm.py, cart-pole shape, forward ms: M=1024 3.8 vs 4.9
-    // for two small-tile launches vs 6.4 unsharded; M=2048 3.9 vs 6.8 for the unsharded 16-particle kernel)
-    const int ncl = (M + 15) / 16;
-    {
-      a.xch = (unsigned long long*)workspace;
-      a.nclusters = ncl;
-      a.gsh_cs = tile_sharded_cluster(model, policy, a.NpadMax, M, T);
-      if (hipMemsetAsync(workspace, 0, rollout_xch_bytes(M, model->G), st) != hipSuccess) return MCP_ERR_LAUNCH;
-      {  // the policy split over the members of a cluster (every member needs a tile of 16 basis functions)
-        const size_t uoff = rollout_xch_bytes(M, model->G) + rollout_xj_bytes(model) + rollout_kt_bytes(model);
-        const size_t ub = (size_t)ncl * 2 * a.gsh_cs * 16 * model->U * 2 * sizeof(unsigned long long);
-        // automatic: clusters of three or more on small swarms (the UR5 launch script's M = 200: six members, the policy 1/6 of the step;
-        // ur5_script 11.2 -> 10.5 ms).  Not with two members -- the exchange costs what half a cart-pole policy does -- and not on large
-        // swarms, whose halves run another cluster size: they would no longer reproduce the whole bit for bit (tests: *_full_size_properties)
-        const bool want = hk.policy_split == 1 || (hk.policy_split < 0 && a.gsh_cs >= 3 && M <= 512);
-        if (want && (policy->B + 15) / 16 >= a.gsh_cs && workspace_bytes >= uoff + rollout_uxch_bytes(M, model->G, model->U)) {
-          a.uxch = (unsigned long long*)((char*)workspace + uoff);
-          if (hipMemsetAsync(a.uxch, 0, ub, st) != hipSuccess) return MCP_ERR_LAUNCH;
-        }
-      }
-      {  // Two workgroups per (tile, GP range), one per half of the rows of Kinv, when the grid is still resident at twice the size: the UR5
-         // launch script's M = 200 is 13 tiles x 6 GPs = 78 workgroups on 256 CUs, each bound by ONE GP's phase V on ONE CU
-         // (profiles/r04_ur5_script_stamps.txt: V 50 k of 112 k cycles per step).  Wide classes with the per-tile phase J only (degree <= 1).
-        const size_t roff = rollout_xch_bytes(M, model->G) + rollout_xj_bytes(model) + rollout_kt_bytes(model) + rollout_uxch_bytes(M, model->G, model->U);
-        const size_t rb = rollout_rxch_bytes(model, M);
-        // Round 6: THREE row parts where three times the grid is resident (13 x 6 x 3 = 234), and the workgroups dealt row part major
-        // (FwdArgs.gsh_map): one workgroup per CU, at most 32 per XCD -- the grid is rounded up to a multiple of 8, the XCDs take its blocks in turn.
-        const bool can = a.xj && a.maxdeg <= 1 && a.NpadMax >= 128 && rb > 0 && workspace_bytes >= roff + rb;
-        const int cus = device_cu_count();
-        const int map = hk.cluster_map < 0 ? MCP_ROW_PART_MAJOR_DEFAULT : hk.cluster_map;
-        auto resident = [&](int rs) { return map == 1 ? ((ncl * a.gsh_cs * rs + 7) / 8) * 8 <= cus : ((ncl + 7) / 8) * 8 * a.gsh_cs * rs <= cus && ((ncl + 7) / 8) * a.gsh_cs * rs <= cus / 8; };
-        if (can && hk.row_split != 0) {
-          const int want = hk.row_split < 0 ? MCP_ROW_PARTS_DEFAULT : hk.row_split;
-          const int rs = (want >= 3 && resident(3)) ? 3 : (resident(2) ? 2 : 1);
-          if (rs > 1) {
-            a.gsh_rs = rs;
-            a.gsh_map = map;
-            a.rxch = (unsigned long long*)((char*)workspace + roff);
-            if (hipMemsetAsync(a.rxch, 0, rb, st) != hipSuccess) return MCP_ERR_LAUNCH;
-          }
-        }
-      }
-      const int rc = launch_fwd_tile_sharded(a, st);
-      if (rc == MCP_OK) {
-        hk.last_ppw = 16;
-        hk.last_sharded = 1;
-        hk.last_row_split = a.gsh_rs > 1 ? a.gsh_rs : 0;
-        return MCP_OK;
-      }
-      if (rc != MCP_ERR_LIMIT) return rc;
-      a.xch = nullptr;
-      a.uxch = nullptr;
-      a.gsh_rs = 1;
-      a.gsh_map = 0;
-      a.rxch = nullptr;
-      a.nclusters = 0;
-    }
+  if (pl.zero_rxch && hipMemsetAsync(a.rxch, 0, rollout_rxch_bytes(&m, a.M), st) != hipSuccess) return MCP_ERR_LAUNCH;
+  if (pl.pack_kt) {  // Kinv of every GP as MFMA operand tiles, in each wave's streaming order
+    const int rc = launch_fwd_lean_pack(a, st);
+    if (rc != MCP_OK) return rc;
   }
-  if (P0 == 16) {
-    // large swarms: 16-particle tiles on the matrix cores (rollout_fwd_tile.hip) when the problem fits that kernel
-    if (model->G >= 1 && T > 1 && fwd_tile_fits(model, policy)) {
-      hk.last_ppw = 16;
-      return launch_fwd_tile(a, st);
-    }
-    P0 = 4;
+  // (the packed phase-J operand, pl.pack_xj, is built by the two tile launch functions themselves)
+  const int P = pl.particles;
+  const size_t lds = (size_t)pl.lds_bytes;
+  switch (pl.family) {
+    case MCP_FWD_TILE_SHARDED: return launch_fwd_tile_sharded(a, st);
+    case MCP_FWD_TILE: return launch_fwd_tile(a, st);
+    case MCP_FWD_SMALL: return launch_fwd_small(a, P, pl.xlds != 0, lds, st);
+    default: break;
   }
-  for (int P = P0; P >= 1; P >>= 1) {
-    for (int xl = (hk.force_xlds == 0 ? 0 : 1); xl >= 0; --xl) {
-      for (int GB = imax(1, (hk.force_gb > 0 ? imin(hk.force_gb, model->G) : model->G)); GB >= 1; --GB) {
-        int NCmax = chunks_in_pass(model, GB);
-        if (NCmax > RF_MAX_CHUNKS) continue;
-        FwdLayout L = fwd_layout(P, model->S, model->U, model->D, model->G, policy->P, policy->B, a.NpadMax, a.maxdeg, GB, NCmax, xl != 0);
-        size_t lds = sizeof(double) * (size_t)L.total;
-        if (lds > MCP_LDS_LIMIT) continue;
-        a.GB = GB;
-        a.NCmax = NCmax;
-        hk.last_ppw = P;
-        if (P == 4) return xl ? launch_fwd<4, true>(a, lds, st) : launch_fwd<4, false>(a, lds, st);
-        if (P == 2) return xl ? launch_fwd<2, true>(a, lds, st) : launch_fwd<2, false>(a, lds, st);
-        return xl ? launch_fwd<1, true>(a, lds, st) : launch_fwd<1, false>(a, lds, st);
-      }
-    }
+  // GP-sharded small-tile or lean kernel: a launch per resident grid, back to back (they may overlap where one drains and the next starts,
+  // which only delays a partner)
+  for (int off = 0; off < a.M; off += pl.particles_per_launch) {
+    a.m_off = off;
+    a.m_cnt = imin(pl.particles_per_launch, a.M - off);
+    a.nclusters = (a.m_cnt + P - 1) / P;
+    const int rc = pl.family == MCP_FWD_LEAN ? launch_fwd_lean(a, P, lds, st)
+                                            : (P == 4 ? launch_fwd_sharded<4>(a, lds, st) : (P == 2 ? launch_fwd_sharded<2>(a, lds, st) : launch_fwd_sharded<1>(a, lds, st)));
+    if (rc != MCP_OK) return rc;
   }
-  return MCP_ERR_LIMIT;
+  return MCP_OK;
 }
 
 template <int P>
@@ -1493,16 +1300,39 @@ static int launch_post(const PostArgs& a, size_t lds, hipStream_t st) {
   return MCP_OK;
 }
 
+static const mcp_dispatch g_automatic = {};  // the request of the plain entry points
+
+extern "C" int mcp_rollout_fwd_plan(const mcp_model* model, const mcp_policy* policy, int M, int T, int particle_pred, size_t workspace_bytes, int cus,
+                                    const mcp_dispatch* request, mcp_fwd_plan* plan) {
+  if (!plan) return MCP_ERR_ARG;
+  const FwdCall c = {M, T, particle_pred, workspace_bytes > 0, workspace_bytes, cus};
+  return plan_fwd(model, policy, c, request ? request : &g_automatic, plan);
+}
+
 extern "C" int mcp_rollout_fwd_ex(const mcp_model* model, const mcp_policy* policy, const mcp_noise* noise, int M, int T, int particle_pred,
                                   const double* x0, double* states, double* inputs, double* jac, uint32_t* status, void* workspace,
                                   size_t workspace_bytes, void* stream, mcp_dispatch* d) {
-  FwdHooks hk = fwd_hooks(d);
-  const int rc = rollout_fwd_impl(model, policy, noise, M, T, particle_pred, x0, states, inputs, jac, status, workspace, workspace_bytes, stream, hk);
+  const mcp_dispatch* rq = d ? d : &g_automatic;
+  FwdPlan pl = {};
+  int rc = MCP_ERR_ARG;
+  if (noise && x0 && states && inputs && status) {
+    const FwdCall c = {M, T, particle_pred, workspace != nullptr, workspace_bytes, device_cu_count()};
+    rc = plan_fwd(model, policy, c, rq, &pl);
+  }
+  if (rc == MCP_OK) {
+    mcp_model stub;
+    if (!model) {
+      stub = policy_only_model(policy);
+      model = &stub;
+    }
+    FwdArgs a = fwd_args(model, policy, noise, M, T, particle_pred, x0, states, inputs, jac, status, workspace, rq, pl);
+    rc = run_fwd_plan(a, pl, (hipStream_t)stream);
+  }
   if (d) {
-    d->ran_particles = hk.last_ppw;
-    d->ran_gp_sharded = hk.last_sharded;
-    d->ran_fwd_lean = hk.last_lean;
-    d->ran_row_split = hk.last_row_split;
+    d->ran_particles = pl.ran_particles;
+    d->ran_gp_sharded = pl.ran_gp_sharded;
+    d->ran_fwd_lean = pl.ran_fwd_lean;
+    d->ran_row_split = pl.ran_row_split;
   }
   return rc;
 }
@@ -1514,7 +1344,6 @@ extern "C" int mcp_rollout_fwd(const mcp_model* model, const mcp_policy* policy,
 
 extern "C" int mcp_posterior_fwd_ex(const mcp_gp* gp, int M, const double* Z, double* mu, double* var, double* Jmu, double* Jvar,
                                     uint32_t* status, void* stream, mcp_dispatch* d) {
-  FwdHooks hk = fwd_hooks(d);
   if (!gp || !Z || !mu || !var || M <= 0) return MCP_ERR_ARG;
   if ((Jmu == nullptr) != (Jvar == nullptr)) return MCP_ERR_ARG;
   if (gp->kern.D <= 0 || gp->kern.D > MCP_MAX_GPDIM || gp->N <= 0 || gp->Npad < gp->N || (gp->Npad % 16) != 0) return MCP_ERR_ARG;
@@ -1533,7 +1362,7 @@ extern "C" int mcp_posterior_fwd_ex(const mcp_gp* gp, int M, const double* Z, do
   a.Jmu = Jmu;
   a.Jvar = Jvar;
   a.status = status;
-  int P0 = hk.force_ppw ? hk.force_ppw : pick_particles_per_wg(M);
+  int P0 = (d && d->fwd_particles) ? d->fwd_particles : pick_particles_per_wg(M);
   if (P0 == 16) P0 = 4;  // (the single-step operator has no 16-particle form: more than 1024 test points run 4 per workgroup)
   if (P0 != 1 && P0 != 2 && P0 != 4) return MCP_ERR_ARG;
   for (int P = P0; P >= 1; P >>= 1) {

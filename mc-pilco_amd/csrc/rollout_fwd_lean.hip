@@ -1317,7 +1317,6 @@ __global__ __launch_bounds__(RF_NT) void rollout_fwd_lat_kernel(FwdArgs a) {
 
 
 // the latency-lean GP-sharded kernel: narrow SE-only models (cart-pole class); KR = phase-K items per thread
-static int gsh_grid(int nclusters, int G) { return ((nclusters + 7) / 8) * 8 * G; }  // (whole groups of 8 clusters: rollout_fwd.hip)
 template <int P, int KR, int MAXDEG, bool PMS, bool STAMPS>
 static int launch_fwd_lean_s(const FwdArgs& a, size_t lds, hipStream_t st) {
   MCP_ENSURE_MAX_LDS(rollout_fwd_lat_kernel<P, KR, MAXDEG, PMS, STAMPS>);

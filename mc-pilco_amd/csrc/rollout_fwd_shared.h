@@ -3,6 +3,7 @@
 // the GP descriptors, kernel hyper-parameter tables.
 #pragma once
 #include "rollout_common.h"
+#include "rollout_plan.h"
 
 #define RF_NT 512
 #define RF_NW (RF_NT / 64)
@@ -142,15 +143,16 @@ __device__ __forceinline__ double fold_kk(double v) {
   return sum_xor32(sum_xor16(v));
 }
 
+// grid of a GP-sharded launch of the 1 / 2 / 4-particle kernels (rollout_fwd.hip, rollout_fwd_lean.hip): whole groups of 8 clusters, G workgroups each
+static inline int gsh_grid(int nclusters, int G) { return ((nclusters + 7) / 8) * 8 * G; }
+
 // forward rollout with 16 particles per workgroup (rollout_fwd_tile.hip); MCP_ERR_LIMIT when the problem does not fit it
 int launch_fwd_tile(const FwdArgs& a, hipStream_t st);
 // the same kernel GP-sharded (G workgroups per 16-particle tile; a.xch / a.nclusters set by the caller); MCP_ERR_LIMIT when
-// the shape has no sharded instantiation
+// the shape has no sharded instantiation (fwd_tile_sharded_takes, rollout_plan.h: the plan asks before it chooses this form)
 int launch_fwd_tile_sharded(const FwdArgs& a, hipStream_t st);
-bool fwd_tile_fits(const mcp_model* model, const mcp_policy* policy);
-// the latency-lean GP-sharded kernel of small swarms (rollout_fwd_lean.hip): dynamic LDS it needs for this shape at P particles per
-// workgroup (0: it does not take the shape), the packing of Kinv into its operand tiles (a.kt), the launch itself
-size_t fwd_lean_lds_bytes(const mcp_model* model, const mcp_policy* policy, int P, int NpadMax, int maxdeg);
+// the latency-lean GP-sharded kernel of small swarms (rollout_fwd_lean.hip; fwd_lean_lds_bytes, rollout_plan.h, says whether it takes a
+// shape): the packing of Kinv into its operand tiles (a.kt), the launch itself
 int launch_fwd_lean_pack(const FwdArgs& a, hipStream_t st);
 int launch_fwd_lean(const FwdArgs& a, int P, size_t lds, hipStream_t st);
 

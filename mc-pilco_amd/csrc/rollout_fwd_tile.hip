@@ -1777,6 +1777,16 @@ bool fwd_tile_fits(const mcp_model* model, const mcp_policy* policy) {
   return sizeof(double) * (size_t)L.total <= MCP_LDS_LIMIT;
 }
 
+// register class of a shape: 0 the cart-pole widths (D + 1 <= 8 rows of [X^T; 1], phase J), 1 the UR5 widths, 2 anything wider or longer
+static int tile_class(const mcp_model* m, const mcp_policy* p, int NpadMax) {
+  if (NpadMax > 512) return 2;
+  return (m->D <= 7 && p->P <= 8 && m->U <= 2) ? 0 : ((m->D <= 24 && p->P <= 24 && m->U <= 6) ? 1 : 2);
+}
+// the GP-sharded launch exists for classes 0 and 1
+bool fwd_tile_sharded_takes(const mcp_model* model, const mcp_policy* policy, int NpadMax) {
+  return fwd_tile_fits(model, policy) && tile_class(model, policy, NpadMax) != 2;
+}
+
 template <int MAXDEG, int CLS, bool PMS, bool XL>
 static int launch_tile_pms(const FwdArgs& a, size_t lds, hipStream_t st) {
   MCP_ENSURE_MAX_LDS(rollout_fwd_tile_kernel<MAXDEG, CLS, PMS, false, XL>);
@@ -1825,8 +1835,7 @@ static int tile_xj_pack(const FwdArgs& a, hipStream_t st) {
 int launch_fwd_tile(const FwdArgs& a, hipStream_t st) {
   if (!fwd_tile_fits(&a.model, &a.pol)) return MCP_ERR_LIMIT;
   if (tile_xj_pack(a, st) != MCP_OK) return MCP_ERR_LAUNCH;
-  const int D = a.model.D, PF = a.pol.P, U = a.model.U;
-  const int cls = a.NpadMax > 512 ? 2 : ((D <= 7 && PF <= 8 && U <= 2) ? 0 : ((D <= 24 && PF <= 24 && U <= 6) ? 1 : 2));  // (class 0: D + 1 <= 8 rows of [X^T; 1], phase J)
+  const int cls = tile_class(&a.model, &a.pol, a.NpadMax);
   // one instantiation per (highest polynomial degree, class): no code or registers for kernel terms the model does not have
   switch (cls * 3 + a.maxdeg) {
     case 0: return launch_tile_deg<0, 0>(a, st);
@@ -1844,11 +1853,8 @@ int launch_fwd_tile(const FwdArgs& a, hipStream_t st) {
 // GP-sharded launch of the 16-particle kernel (a.gsh_cs workgroups per tile, a.xch, a.nclusters set by the caller): the cart-pole
 // and the UR5 register classes
 int launch_fwd_tile_sharded(const FwdArgs& a, hipStream_t st) {
-  if (!fwd_tile_fits(&a.model, &a.pol) || a.gsh_cs < 2 || a.gsh_cs > a.model.G || !a.xch) return MCP_ERR_LIMIT;
-  const int D = a.model.D, PF = a.pol.P, U = a.model.U;
-  if (a.NpadMax > 512) return MCP_ERR_LIMIT;
-  const int cls = (D <= 7 && PF <= 8 && U <= 2) ? 0 : ((D <= 24 && PF <= 24 && U <= 6) ? 1 : 2);
-  if (cls == 2) return MCP_ERR_LIMIT;
+  if (!fwd_tile_sharded_takes(&a.model, &a.pol, a.NpadMax) || a.gsh_cs < 2 || a.gsh_cs > a.model.G || !a.xch) return MCP_ERR_LIMIT;
+  const int D = a.model.D, cls = tile_class(&a.model, &a.pol, a.NpadMax);
   if (a.gsh_map == 1 && (a.gsh_rs < 2 || cls == 0 || a.maxdeg > 1)) return MCP_ERR_ARG;  // (the row-part-major deal exists where the row split does)
   if (a.gsh_rs > 1 && (a.gsh_rs > 3 || cls == 0 || a.maxdeg > 1 || !a.xj || !a.rxch || TL_PT * (D + 1) > RF_NT)) return MCP_ERR_ARG;  // (the row split exists in the per-tile form of phase J only)
   if (tile_xj_pack(a, st) != MCP_OK) return MCP_ERR_LAUNCH;

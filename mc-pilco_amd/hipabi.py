@@ -95,6 +95,20 @@ class Dispatch(C.Structure):
                 ("ran_bwd_lean", C.c_int32), ("ran_row_split", C.c_int32), ("ran_bwd_pipe", C.c_int32)]
 
 
+class FwdPlan(C.Structure):
+    """include/mcpilco_hip_debug.h: struct mcp_fwd_plan -- what mcp_rollout_fwd_plan answers (the launch plan of a forward call)."""
+    _fields_ = [(k, C.c_int32) for k in ("family", "particles", "xlds", "gb", "ncmax", "lds_bytes", "npad_max", "maxdeg", "launches", "particles_per_launch",
+                                         "gsh_cs", "gsh_rs", "gsh_map", "policy_split", "ws_xch", "ws_xj", "ws_kt", "ws_uxch", "ws_rxch", "ws_total", "use_xj", "use_kt", "zero_xch", "zero_uxch", "zero_rxch", "pack_kt",
+                                         "pack_xj", "ran_particles", "ran_gp_sharded", "ran_fwd_lean", "ran_row_split")]
+
+
+class BwdPlan(C.Structure):
+    """include/mcpilco_hip_debug.h: struct mcp_bwd_plan -- what mcp_rollout_bwd_plan answers."""
+    _fields_ = [(k, C.c_int32) for k in ("lean", "pfm", "um", "maxnt", "particles", "threads", "pipe", "launches", "slabs", "ran_bwd_lean", "ran_bwd_pipe")]
+
+
+FWD_SMALL_SHARDED, FWD_LEAN, FWD_TILE_SHARDED, FWD_TILE, FWD_SMALL = 1, 2, 3, 4, 5  # mcp_fwd_plan.family
+
 # The dispatch request of THIS PROCESS's calls through `ops` (all zero: automatic).  It lives here, in the host layer -- the library keeps no
 # dispatch state; tests and tools set its fields through the `mcp_debug_*` methods of `lib()` (the names the library itself exported until
 # round 4), every `ops` call passes it along and finds in it what ran.
@@ -138,6 +152,10 @@ _SIGS = {
                                      dptr, dptr, dptr, C.c_size_t, dptr, C.POINTER(Dispatch)]),
     "mcp_rollout_bwd_ex": (C.c_int, [C.POINTER(Model), C.POINTER(Policy), C.POINTER(Noise), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr,
                                      dptr, dptr, dptr, dptr, dptr, C.c_size_t, dptr, C.POINTER(Dispatch)]),
+    "mcp_rollout_fwd_plan": (C.c_int, [C.POINTER(Model), C.POINTER(Policy), C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.POINTER(Dispatch),
+                                       C.POINTER(FwdPlan)]),
+    "mcp_rollout_bwd_plan": (C.c_int, [C.POINTER(Model), C.POINTER(Policy), C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.POINTER(Dispatch),
+                                       C.POINTER(BwdPlan)]),
     "mcp_cost_fwd": (C.c_int, [C.POINTER(Cost), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr]),
     "mcp_cost_finalize": (C.c_int, [C.c_int, C.c_int, dptr, C.POINTER(C.c_int64), dptr, dptr]),
     "mcp_cost_bwd": (C.c_int, [C.POINTER(Cost), C.c_int, C.c_int, dptr, dptr, C.c_double, dptr, dptr]),
@@ -155,8 +173,9 @@ _SIGS = {
     "mcp_allreduce_grad": (C.c_int, [dptr, C.c_size_t, dptr]),
     "mcp_comm_destroy": (C.c_int, []),
 }
-EXPORTED = [k for k in _SIGS if not k.endswith("_ex")]        # include/mcpilco_hip.h
-EXPORTED_DEBUG = [k for k in _SIGS if k.endswith("_ex")]      # include/mcpilco_hip_debug.h
+PLAN_QUERIES = ("mcp_rollout_fwd_plan", "mcp_rollout_bwd_plan")
+EXPORTED_DEBUG = [k for k in _SIGS if k.endswith("_ex") or k in PLAN_QUERIES]  # include/mcpilco_hip_debug.h
+EXPORTED = [k for k in _SIGS if k not in EXPORTED_DEBUG]                       # include/mcpilco_hip.h
 
 _lib = None
 

@@ -32,9 +32,12 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, n), "libmcpilco_hip.so does not export %s" % n
     assert set(hipabi.EXPORTED) == set(names)
     # the test / diagnostic entry points live in their own header, outside the boundary, and the binding knows exactly those: each is its plain
-    # namesake plus a per-call mcp_dispatch (round 5: the library exports no setter and keeps no dispatch state)
+    # namesake plus a per-call mcp_dispatch (round 5: the library exports no setter and keeps no dispatch state), or one of the two plan queries,
+    # whose stem is the boundary call it plans
     dbg = declared_symbols(DEBUG_HEADER)
-    assert dbg and all(n.endswith("_ex") and n[:-3] in names for n in dbg)
+    plan_queries = ("mcp_rollout_fwd_plan", "mcp_rollout_bwd_plan")
+    assert dbg and all((n.endswith("_ex") and n[:-3] in names) or (n in plan_queries and n[:-len("_plan")] in names) for n in dbg)
+    assert all(dbg.count(n) == 1 for n in plan_queries)
     for n in dbg:
         assert hasattr(lib, n)
     assert set(hipabi.EXPORTED_DEBUG) == set(dbg)
@@ -95,6 +98,29 @@ def test_dispatch_struct_layout_matches_the_debug_header_and_every_object_depend
     got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
     assert got == [C.sizeof(hipabi.Dispatch)] + [getattr(hipabi.Dispatch, n).offset for n in names]
     assert any(h.endswith("mcpilco_hip_debug.h") for h in build.HEADERS) and any(h.endswith("mcpilco_hip.h") for h in build.HEADERS)
+
+
+@pytest.mark.parametrize("struct,mirror", [("mcp_fwd_plan", "FwdPlan"), ("mcp_bwd_plan", "BwdPlan")])
+def test_plan_struct_layouts_match_the_debug_header(tmp_path, struct, mirror):
+    """`mcp_fwd_plan` / `mcp_bwd_plan` (include/mcpilco_hip_debug.h), what the plan queries fill: int32 fields only, and the ctypes mirrors lay out
+    every field where the header does (offset by offset, as for `mcp_dispatch`)."""
+    from mc_pilco_amd import hipabi
+
+    cls = getattr(hipabi, mirror)
+    hdr = open(DEBUG_HEADER).read()
+    body = hdr[hdr.index("typedef struct %s {" % struct):hdr.index("} %s;" % struct)]
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    decls = re.findall(r"^\s*(\w+)\s+([\w\s,]+);", body, re.M)
+    assert decls and all(t == "int32_t" for t, _ in decls)
+    names = [n.strip() for _, group in decls for n in group.split(",")]
+    assert names == [f[0] for f in cls._fields_]
+    src = tmp_path / "pz.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mcpilco_hip_debug.h"\nint main(){printf("%%zu", sizeof(%s));' % struct
+                   + "".join('printf(" %%zu", offsetof(%s, %s));' % (struct, n) for n in names) + "return 0;}\n")
+    exe = tmp_path / "pz"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
+    assert got == [C.sizeof(cls)] + [getattr(cls, n).offset for n in names]
 
 
 def test_argument_validation_without_gpu():

@@ -69,7 +69,7 @@ class Case:
 
 def classes(c):
     """What the dispatch rules of rollout_fwd_tile.hip / rollout_bwd.hip give for the widths of ``c`` (restated here from the rules in the module
-    docstring, not read from the library): tile class (None: no tile kernel), row tiles, sweep <PFM,UM>, its thread class, GP-sharded tile launch."""
+    docstring, not read from the library: tests/test_dispatch_plan_cpu.py compares the two): tile class (None: no tile kernel), row tiles, sweep <PFM,UM>, its thread class, GP-sharded tile launch."""
     D, P, U = c.D, c.P, c.U
     tile = None if D + 1 > 32 else (0 if (D <= 7 and P <= 8 and U <= 2) else (1 if (D <= 24 and P <= 24 and U <= 6) else 2))
     sweep = (8, 2) if (P <= 8 and U <= 2) else ((16, 4) if (P <= 16 and U <= 4) else ((24, 6) if (P <= 24 and U <= 6) else (32, 8)))
@@ -80,18 +80,20 @@ def classes(c):
 
 
 def sweep_widths(c):
-    """Particles per workgroup the general sweep can launch for ``c``, restated from rollout_bwd_impl / launch_bwd: the instantiations that exist
+    """Particles per workgroup the general sweep can launch for ``c``, restated from plan_bwd (csrc/rollout_plan.h): the instantiations that exist
     for (sweep class, thread class) and, of those, the ones whose prefetched record fits (PB x record <= 5 per chain-free thread, the record being
-    2 S + 2 U + G D (+ S with the measurement model)).  A forced width that is not among them is halved by the library until one is; the dispatch
-    report has no field for the width that ran, so the tests request only these."""
+    2 S + 2 U + G D (+ S with the measurement model)).  A forced width that is not among them is halved by the library until one is.  The dispatch
+    report has no field for the width that ran, but the plan query has (mcp_bwd_plan.particles): tests/test_dispatch_plan_cpu.py holds this
+    restatement against it for every case and every forced width; the GPU tests request only these."""
     k = classes(c)
     have = {((8, 2), 256): (1, 2, 4), ((16, 4), 256): (1, 2), ((24, 6), 256): (1, 2), ((32, 8), 256): (1, 2), ((8, 2), 1024): (1,),
-            ((16, 4), 1024): (1,), ((24, 6), 512): (1, 2, 4, 8), ((32, 8), 512): (1, 2)}[(k["sweep"], k["maxnt"])]
+            ((16, 4), 1024): (1,), ((24, 6), 512): (1, 2, 4, 8), ((32, 8), 512): (1, 2)}
     rec = 2 * c.S + 2 * c.U + c.G * c.D + (c.S if c.pms is not None else 0)
     out = []
-    for pb in have:
-        nt = max(k["nt"], 64 * pb)
-        if nt <= k["maxnt"] and pb * rec <= 5 * (nt - 64 * pb if nt // 64 > pb else nt):
+    for pb in (1, 2, 4, 8):
+        nt = max(k["nt"], 64 * pb)  # a wave per particle at least: a wide request lifts the thread class (eight particles: 512 threads)
+        maxnt = 256 if nt <= 256 else (1024 if k["sweep"][0] <= 16 else 512)
+        if pb in have[(k["sweep"], maxnt)] and nt <= maxnt and pb * rec <= 5 * (nt - 64 * pb if nt // 64 > pb else nt):
             out.append(pb)
     return out
 
