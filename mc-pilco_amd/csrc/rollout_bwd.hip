@@ -1486,9 +1486,7 @@ bool bwd_lean_applies(const mcp_model* md, const mcp_policy* pl, int T) {
   if (T < 2 || md->G < 1 || md->G > BL_GM || md->S > 8 || pl->P > 8 || pl->U > 2 || pl->B > 256 || md->U != pl->U) return false;
   if (pl->kind != MCP_POLICY_PLAIN && pl->kind != MCP_POLICY_ANGLES) return false;
   if (pl->meas.n > 4) return false;  // (measurement pairs cross lanes by uniform-index v_readlane: up to 4 pairs on 8 state lanes)
-  for (int i = 0; i < pl->meas.n; ++i)
-    for (int j = 0; j < pl->meas.n; ++j)
-      if ((i != j && (pl->meas.pos[i] == pl->meas.pos[j] || pl->meas.vel[i] == pl->meas.vel[j])) || pl->meas.pos[i] == pl->meas.vel[j]) return false;
+  if (!meas_pairs_disjoint(&pl->meas)) return false;
   if (pl->kind == MCP_POLICY_PLAIN && pl->P != md->S) return false;
   if (md->n_not_angle + 2 * md->n_angle + md->U != md->D) return false;
   for (int i = 0; i < md->n_angle; ++i)

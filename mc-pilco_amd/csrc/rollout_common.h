@@ -1,5 +1,5 @@
-// Shared by rollout_fwd.hip and rollout_bwd.hip: feature maps of the dynamics model and of the
-// policy, descriptor validation, small integer helpers.
+// Shared by the rollout sources (rollout_fwd*.hip, rollout_bwd.hip, rollout_open.hip): feature maps of the dynamics model and of the
+// policy, descriptor validation (model_within_limits, model_lists_ok, model_ok, meas_pairs_disjoint, policy_ok), small integer helpers.
 #pragma once
 #include <string.h>
 
@@ -63,7 +63,19 @@ static inline size_t rollout_rxch_bytes(const mcp_model* m, int M) {
   return (size_t)((M + 15) / 16) * 2 * (size_t)m->G * 2 * 16 * (size_t)(m->D + 1) * 4 * sizeof(unsigned long long);  // (two senders: gsh_rs = 3)
 }
 
-static inline bool model_ok(const mcp_model* m) {
+// ---- descriptor checks: one home each.  The order every entry point keeps: NULL pointers and sizes (MCP_ERR_ARG), model_within_limits
+// (MCP_ERR_LIMIT), model_ok or model_lists_ok (MCP_ERR_ARG), then its own descriptors ----
+// the compiled limits of the model's dimensions and, unless `train` is false, of the training-set sizes (the sweeps of rollout_open.hip run
+// from the record and never read a GP descriptor)
+static inline bool model_within_limits(const mcp_model* m, bool train = true) {
+  if (m->S > MCP_MAX_STATE || m->U > MCP_MAX_INPUT || m->G > MCP_MAX_GP || m->D > MCP_MAX_GPDIM) return false;
+  for (int g = 0; train && g < m->G; ++g)
+    if (m->gp[g].N > MCP_MAX_TRAIN) return false;
+  return true;
+}
+
+// the model's scalars and index lists: ranges, D = n_not_angle + 2 n_angle + U, every index inside the state.  No GP operand is looked at.
+static inline bool model_lists_ok(const mcp_model* m) {
   if (!m) return false;
   if (m->S <= 0 || m->S > MCP_MAX_STATE || m->U <= 0 || m->U > MCP_MAX_INPUT || m->G <= 0 || m->G > MCP_MAX_GP) return false;
   if (m->D <= 0 || m->D > MCP_MAX_GPDIM) return false;
@@ -72,6 +84,15 @@ static inline bool model_ok(const mcp_model* m) {
     if (m->angle[i] < 0 || m->angle[i] >= m->S) return false;
   for (int i = 0; i < m->n_not_angle; ++i)
     if (m->not_angle[i] < 0 || m->not_angle[i] >= m->S) return false;
+  // not_vel[g] == -1: GP g has no integrated position (delta-state model, x'[vel] = x[vel] + delta)
+  for (int g = 0; g < m->G; ++g)
+    if (m->vel[g] < 0 || m->vel[g] >= m->S || m->not_vel[g] < -1 || m->not_vel[g] >= m->S) return false;
+  return true;
+}
+
+// model_lists_ok plus the operands of every GP
+static inline bool model_ok(const mcp_model* m) {
+  if (!model_lists_ok(m)) return false;
   for (int g = 0; g < m->G; ++g) {
     const mcp_gp& gp = m->gp[g];
     if (gp.kern.D != m->D || gp.N <= 0 || gp.Npad < gp.N || (gp.Npad % 16) != 0 || gp.N > MCP_MAX_TRAIN) return false;
@@ -79,9 +100,15 @@ static inline bool model_ok(const mcp_model* m) {
     if (gp.kern.poly_deg < 0 || gp.kern.poly_deg > 2) return false;
     if (gp.kern.poly_deg >= 1 && (!gp.kern.w1 || !gp.aX)) return false;
     if (gp.kern.poly_deg >= 2 && (!gp.kern.w20 || !gp.kern.w21)) return false;
-    // not_vel[g] == -1: GP g has no integrated position (delta-state model, x'[vel] = x[vel] + delta)
-    if (m->vel[g] < 0 || m->vel[g] >= m->S || m->not_vel[g] < -1 || m->not_vel[g] >= m->S) return false;
   }
+  return true;
+}
+
+// every state component in at most one measurement pair, as position or as velocity (indices in range and n <= MCP_MAX_STATE: the caller's)
+static inline bool meas_pairs_disjoint(const mcp_meas* ms) {
+  for (int i = 0; i < ms->n; ++i)
+    for (int j = 0; j < ms->n; ++j)
+      if ((i != j && (ms->pos[i] == ms->pos[j] || ms->vel[i] == ms->vel[j])) || ms->pos[i] == ms->vel[j]) return false;
   return true;
 }
 

@@ -1,10 +1,18 @@
-// Fused OPEN-LOOP rollout for gfx950 (MI355X): M trajectories are advanced T steps through an mcp_model, the input of step t
-// is read from a buffer (the inputs recorded on the system) instead of coming out of a policy.
+// Fused rollouts for gfx950 (MI355X) whose inputs do not come out of the RBF policy, and their reverse-time sweeps.  M trajectories are
+// advanced T steps through an mcp_model in ONE launch; the forms differ in where the input of step t comes from and in what is kept:
+//   open loop          mcp_rollout_open         u_t is read from a buffer (the inputs recorded on the system)
+//   recording          mcp_rollout_open_rec     the same, and the Jacobians of the increments are recorded for mcp_rollout_open_bwd
+//   feedback           mcp_rollout_pd           u_t is the PD law on x_t (struct OpenArgsPd); with jac the record for mcp_rollout_pd_bwd
+//   measured feedback  mcp_rollout_pd_meas      the PD law on a simulated measurement of x_t (struct OpenArgsPdMeas); mcp_rollout_pd_meas_bwd
+// All forward forms are one kernel template, rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, FB, PMS>, the three sweeps one,
+// rollout_open_bwd_kernel<FB, PMS>.  The host path is the same for every entry point: checks (rollout_common.h: model_within_limits,
+// model_ok / model_lists_ok, meas_pairs_disjoint; here: pd_policy_check, pd_meas_check), one fill of the arguments' base part per direction
+// (open_fill, open_bwd_fill), one ladder of tiles (launch_open_tiles) -- a refused call makes no HIP call.
 //
-// Replaces the step loop of MC_PILCO.rollout (policy_learning/MC_PILCO.py:347-373) over Model_learning.get_next_state
+// The open-loop form replaces the step loop of MC_PILCO.rollout (policy_learning/MC_PILCO.py:347-373) over Model_learning.get_next_state
 // (model_learning/Model_learning.py:210-229, 685-718; GP_prior.get_estimate_from_alpha, GP_prior.py:137-155): per step G posterior
-// launches plus indexing, concatenation and a Normal(...).rsample() -- here ONE launch, no workspace, no hand-off between
-// workgroups.  There is no policy and no Jacobian (nothing is differentiated), so a step is three phases:
+// launches plus indexing, concatenation and a Normal(...).rsample() -- here no workspace, no hand-off between workgroups.  Without a
+// record a step is three phases:
 //
 //   K   k[j][p] = k(z_p, X_j)          thread j, all particles of the tile; the weighted distance in the reference's own expanded form
 //                                      |z/l|^2 + |X_j/l|^2 - 2 sum_d (z_d/l_d^2) X_jd (Stationary_GP.py:65-109), as in the closed-loop
@@ -668,31 +676,48 @@ __global__ __launch_bounds__(RF_NT) void rollout_open_kernel(typename OpenArgsOf
   if (bad) atomicOr(a.status, bad);
 }
 
-template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC>
-static int launch_open(const OpenArgs& a, hipStream_t st) {
-  const OpenLayout L = open_layout(PT, NEEDVAR, a.model.S, a.model.D, a.model.G, a.NpadMax, NEEDJAC, a.na);
+// ---- host path of the forward entry points: checks -> fill -> ladder -----------------------------------------------------------------
+// (an entry checks its own pointers and sizes, then the limits, the model, its descriptors -- every refusal before any HIP call --, fills
+// the base part of the arguments with open_fill, adds what is its own and hands them to the one ladder of tiles, launch_open_tiles)
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool FB, bool PMS>
+static int launch_open(const typename OpenArgsOf<FB, PMS>::type& a, hipStream_t st) {
+  const OpenLayout L = open_layout(PT, NEEDVAR, a.model.S, a.model.D, a.model.G, a.NpadMax, NEEDJAC, a.na, PMS);
   const size_t lds = (size_t)L.total * sizeof(double);
   if (lds > MCP_LDS_LIMIT) return MCP_ERR_LIMIT;
-  MCP_ENSURE_MAX_LDS(rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC>);
-  hipLaunchKernelGGL((rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
+  MCP_ENSURE_MAX_LDS((rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, FB, PMS>));
+  hipLaunchKernelGGL((rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, FB, PMS>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
 }
-template <int PT, bool NEEDVAR, bool NEEDJAC>
-static int launch_open_deg(const OpenArgs& a, int maxdeg, hipStream_t st) {
-  return maxdeg == 0 ? launch_open<PT, 0, NEEDVAR, NEEDJAC>(a, st) : launch_open<PT, 2, NEEDVAR, NEEDJAC>(a, st);
+template <int PT, bool NEEDVAR, bool NEEDJAC, bool FB, bool PMS>
+static int launch_open_deg(const typename OpenArgsOf<FB, PMS>::type& a, int maxdeg, hipStream_t st) {
+  return maxdeg == 0 ? launch_open<PT, 0, NEEDVAR, NEEDJAC, FB, PMS>(a, st) : launch_open<PT, 2, NEEDVAR, NEEDJAC, FB, PMS>(a, st);
+}
+// The ladder of tiles, the same for every form (the feedback adds nothing to the LDS layout, the measurement one row [PT][S]); a.jac: the
+// recording form.  The mean chain (no sampling, no variance asked for) touches no Kinv: one trajectory per workgroup.  With a variance:
+//   no record  16 trajectories per workgroup, 4 where the k panel of 16 does not fit (at every compiled limit at once -- S = 16, D = 32, G = 8,
+//              Npad = 4096 -- that layout takes 148 KB of the 160, so nothing within MCP_MAX_* is refused)
+//   record     two panels: 16 up to Npad ~ 500, 4 up to ~ 2000, beyond that one (at every compiled limit at once: 2 x 32 KB of panels, 85 KB
+//              in all; the recording mean chain: 85 KB, X^T then stays in global memory)
+template <bool FB, bool PMS>
+static int launch_open_tiles(const typename OpenArgsOf<FB, PMS>::type& a, int maxdeg, bool wantvar, hipStream_t st) {
+  if (!a.jac) {
+    if (!a.sample && !wantvar) return launch_open_deg<1, false, false, FB, PMS>(a, maxdeg, st);
+    int rc = launch_open_deg<16, true, false, FB, PMS>(a, maxdeg, st);
+    if (rc == MCP_ERR_LIMIT) rc = launch_open_deg<4, true, false, FB, PMS>(a, maxdeg, st);
+    return rc;
+  }
+  if (!a.sample && !wantvar) return launch_open_deg<1, false, true, FB, PMS>(a, maxdeg, st);
+  int rc = launch_open_deg<16, true, true, FB, PMS>(a, maxdeg, st);
+  if (rc == MCP_ERR_LIMIT) rc = launch_open_deg<4, true, true, FB, PMS>(a, maxdeg, st);
+  if (rc == MCP_ERR_LIMIT) rc = launch_open_deg<1, true, true, FB, PMS>(a, maxdeg, st);
+  return rc;
 }
 
-// what mcp_rollout_open and mcp_rollout_open_rec share: the checks, the arguments, the choice of the tile (jac: the recording form)
-static int open_dispatch(const mcp_model* model, const mcp_noise* noise, int M, int T, int particle_pred, const double* x0, const double* u, int Mu,
-                         const int32_t* lengths, double* states, double* mu, double* var, double* jac, uint32_t* status, void* stream) {
-  if (!model || !noise || !x0 || !u || !states || !status) return MCP_ERR_ARG;
-  if (M <= 0 || T < 2 || (Mu != 1 && Mu != M)) return MCP_ERR_ARG;
-  if (model->S > MCP_MAX_STATE || model->U > MCP_MAX_INPUT || model->G > MCP_MAX_GP || model->D > MCP_MAX_GPDIM) return MCP_ERR_LIMIT;
-  for (int g = 0; g < model->G && g < MCP_MAX_GP; ++g)
-    if (model->gp[g].N > MCP_MAX_TRAIN) return MCP_ERR_LIMIT;
-  if (!model_ok(model)) return MCP_ERR_ARG;
-  OpenArgs a;
+// the base part of the arguments, for every form (u, Mu, lengths: the open-loop form's own; jac != NULL: the recording form); returns the
+// highest polynomial degree of the model's kernels
+static int open_fill(OpenArgs& a, const mcp_model* model, const mcp_noise* noise, int M, int T, int particle_pred, const double* x0, const double* u,
+                     int Mu, const int32_t* lengths, double* states, double* mu, double* var, double* jac, uint32_t* status) {
   a.model = *model;
   a.nz = *noise;
   a.M = M;
@@ -714,21 +739,19 @@ static int open_dispatch(const mcp_model* model, const mcp_noise* noise, int M, 
   a.mu = mu;
   a.var = var;
   a.status = status;
-  hipStream_t st = (hipStream_t)stream;
-  if (!jac) {
-    if (!a.sample && !var) return launch_open_deg<1, false, false>(a, maxdeg, st);  // the mean chain: no Kinv
-    int rc = launch_open_deg<16, true, false>(a, maxdeg, st);
-    // the k panel of 16 trajectories does not fit the LDS: 4 per workgroup (at every compiled limit at once -- S = 16, D = 32, G = 8, Npad = 4096 --
-    // that layout takes 148 KB of the 160, so nothing within MCP_MAX_* is refused)
-    if (rc == MCP_ERR_LIMIT) rc = launch_open_deg<4, true, false>(a, maxdeg, st);
-    return rc;
-  }
-  if (!a.sample && !var) return launch_open_deg<1, false, true>(a, maxdeg, st);  // (at every limit at once: 85 KB, X^T then stays in global memory)
-  // two panels: 16 trajectories up to Npad ~ 500, 4 up to ~ 2000, beyond that one (at every compiled limit at once: 2 x 32 KB of panels, 85 KB in all)
-  int rc = launch_open_deg<16, true, true>(a, maxdeg, st);
-  if (rc == MCP_ERR_LIMIT) rc = launch_open_deg<4, true, true>(a, maxdeg, st);
-  if (rc == MCP_ERR_LIMIT) rc = launch_open_deg<1, true, true>(a, maxdeg, st);
-  return rc;
+  return maxdeg;
+}
+
+// what mcp_rollout_open and mcp_rollout_open_rec share (jac: the recording form)
+static int open_dispatch(const mcp_model* model, const mcp_noise* noise, int M, int T, int particle_pred, const double* x0, const double* u, int Mu,
+                         const int32_t* lengths, double* states, double* mu, double* var, double* jac, uint32_t* status, void* stream) {
+  if (!model || !noise || !x0 || !u || !states || !status) return MCP_ERR_ARG;
+  if (M <= 0 || T < 2 || (Mu != 1 && Mu != M)) return MCP_ERR_ARG;
+  if (!model_within_limits(model)) return MCP_ERR_LIMIT;
+  if (!model_ok(model)) return MCP_ERR_ARG;
+  OpenArgs a;
+  const int maxdeg = open_fill(a, model, noise, M, T, particle_pred, x0, u, Mu, lengths, states, mu, var, jac, status);
+  return launch_open_tiles<false, false>(a, maxdeg, var != nullptr, (hipStream_t)stream);
 }
 
 extern "C" int mcp_rollout_open(const mcp_model* model, const mcp_noise* noise, int M, int T, int particle_pred, const double* x0, const double* u,
@@ -744,49 +767,16 @@ extern "C" int mcp_rollout_open_rec(const mcp_model* model, const mcp_noise* noi
   return open_dispatch(model, noise, M, T, particle_pred, x0, u, Mu, lengths, states, mu, var, jac, status, stream);
 }
 
-// ---- feedback form: launch, checks, entry ---------------------------------------------------------------------------------------
-template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool PMS>
-static int launch_pd(const typename OpenArgsOf<true, PMS>::type& a, hipStream_t st) {
-  const OpenLayout L = open_layout(PT, NEEDVAR, a.model.S, a.model.D, a.model.G, a.NpadMax, NEEDJAC, a.na, PMS);
-  const size_t lds = (size_t)L.total * sizeof(double);
-  if (lds > MCP_LDS_LIMIT) return MCP_ERR_LIMIT;
-  MCP_ENSURE_MAX_LDS(rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, true, PMS>);
-  hipLaunchKernelGGL((rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, true, PMS>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
-  MCP_LAUNCH_CHECK();
-  return MCP_OK;
-}
-template <int PT, bool NEEDVAR, bool NEEDJAC, bool PMS>
-static int launch_pd_deg(const typename OpenArgsOf<true, PMS>::type& a, int maxdeg, hipStream_t st) {
-  return maxdeg == 0 ? launch_pd<PT, 0, NEEDVAR, NEEDJAC, PMS>(a, st) : launch_pd<PT, 2, NEEDVAR, NEEDJAC, PMS>(a, st);
-}
-// the tiles of open_dispatch: the feedback adds nothing to the LDS layout, the measurement one row [PT][S]
-template <bool PMS>
-static int launch_pd_tiles(const typename OpenArgsOf<true, PMS>::type& a, int maxdeg, bool wantvar, hipStream_t st) {
-  if (!a.jac) {
-    if (!a.sample && !wantvar) return launch_pd_deg<1, false, false, PMS>(a, maxdeg, st);
-    int rc = launch_pd_deg<16, true, false, PMS>(a, maxdeg, st);
-    if (rc == MCP_ERR_LIMIT) rc = launch_pd_deg<4, true, false, PMS>(a, maxdeg, st);
-    return rc;
-  }
-  if (!a.sample && !wantvar) return launch_pd_deg<1, false, true, PMS>(a, maxdeg, st);
-  int rc = launch_pd_deg<16, true, true, PMS>(a, maxdeg, st);
-  if (rc == MCP_ERR_LIMIT) rc = launch_pd_deg<4, true, true, PMS>(a, maxdeg, st);
-  if (rc == MCP_ERR_LIMIT) rc = launch_pd_deg<1, true, true, PMS>(a, maxdeg, st);
-  return rc;
-}
-
+// ---- feedback form: checks, entry -------------------------------------------------------------------------------------------------------
 // the measurement model against the model (host fields only).  Every component belongs to at most one pair, as position or as velocity:
 // the forward kernel gives a pair to the thread of its position, the sweep keeps one filter adjoint per position component
 static int pd_meas_check(const mcp_model* model, const mcp_meas* ms) {
   if (ms->n < 0 || 2 * ms->n > model->S || ms->n > MCP_MAX_STATE) return MCP_ERR_ARG;
   if (ms->n == 0) return MCP_OK;
   if (!ms->meas || !(fabs(ms->a0) > 0.0) || !(model->Ts > 0.0)) return MCP_ERR_ARG;  // (a NaN a0 or Ts is refused too)
-  for (int i = 0; i < ms->n; ++i) {
+  for (int i = 0; i < ms->n; ++i)
     if (ms->pos[i] < 0 || ms->pos[i] >= model->S || ms->vel[i] < 0 || ms->vel[i] >= model->S) return MCP_ERR_ARG;
-    for (int j = 0; j < ms->n; ++j)
-      if ((i != j && (ms->pos[i] == ms->pos[j] || ms->vel[i] == ms->vel[j])) || ms->pos[i] == ms->vel[j]) return MCP_ERR_ARG;
-  }
-  return MCP_OK;
+  return meas_pairs_disjoint(ms) ? MCP_OK : MCP_ERR_ARG;
 }
 
 // the descriptor against the model and the horizon (host fields only: the gains and the target are device memory).  pos / vel hold distinct
@@ -802,6 +792,12 @@ static int pd_policy_check(const mcp_model* model, const mcp_pd_policy* pd, int 
   }
   return MCP_OK;
 }
+// the PD descriptor, then the measurement (ms NULL: none), for both directions
+static int pd_checks(const mcp_model* model, const mcp_pd_policy* pd, const mcp_meas* ms, int T) {
+  const int prc = pd_policy_check(model, pd, T);
+  if (prc != MCP_OK) return prc;
+  return ms ? pd_meas_check(model, ms) : MCP_OK;
+}
 
 // Closed-loop rollout under the PD law: replaces the loop of MC_PILCO.apply_policy (policy_learning/MC_PILCO.py:615-674) with
 // Policy.PD_controller.forward (policy_learning/Policy.py:437-449) as the policy, over Model_learning.get_next_state
@@ -810,42 +806,19 @@ static int pd_dispatch(const mcp_model* model, const mcp_pd_policy* pd, const mc
                        const double* x0, double* states, double* inputs, double* jac, double* mu, double* var, uint32_t* status, void* stream) {
   if (!model || !pd || !noise || !x0 || !states || !inputs || !status) return MCP_ERR_ARG;
   if (M <= 0 || T < 1) return MCP_ERR_ARG;
-  if (model->S > MCP_MAX_STATE || model->U > MCP_MAX_INPUT || model->G > MCP_MAX_GP || model->D > MCP_MAX_GPDIM) return MCP_ERR_LIMIT;
-  for (int g = 0; g < model->G && g < MCP_MAX_GP; ++g)
-    if (model->gp[g].N > MCP_MAX_TRAIN) return MCP_ERR_LIMIT;
+  if (!model_within_limits(model)) return MCP_ERR_LIMIT;
   if (!model_ok(model)) return MCP_ERR_ARG;
-  const int prc = pd_policy_check(model, pd, T);
-  if (prc != MCP_OK) return prc;
-  if (ms && pd_meas_check(model, ms) != MCP_OK) return MCP_ERR_ARG;
+  const int crc = pd_checks(model, pd, ms, T);
+  if (crc != MCP_OK) return crc;
   OpenArgsPdMeas a;
-  a.model = *model;
-  a.nz = *noise;
-  a.M = M;
-  a.T = T;
-  a.sample = particle_pred & 1;
-  a.Mu = M;
-  a.NpadMax = 0;
-  int maxdeg = 0;
-  for (int g = 0; g < model->G; ++g) {
-    a.NpadMax = imax(a.NpadMax, model->gp[g].Npad);
-    maxdeg = imax(maxdeg, model->gp[g].kern.poly_deg);
-  }
   if (T == 1) jac = nullptr;  // the policy alone: no transition, nothing to record
-  a.na = jac ? (maxdeg == 0 ? 1 : maxdeg == 1 ? 2 : 4) : 0;
-  a.jac = jac;
-  a.x0 = x0;
-  a.u = nullptr;
-  a.lengths = nullptr;
-  a.states = states;
-  a.mu = mu;
-  a.var = var;
-  a.status = status;
+  const int maxdeg = open_fill(a, model, noise, M, T, particle_pred, x0, nullptr, M, nullptr, states, mu, var, jac, status);
   a.pd = *pd;
   a.inputs = inputs;
   hipStream_t st = (hipStream_t)stream;
-  if (!ms || ms->n == 0) return launch_pd_tiles<false>(a, maxdeg, var != nullptr, st);  // (the base part of `a`: mcp_rollout_pd's own kernels)
+  if (!ms || ms->n == 0) return launch_open_tiles<true, false>(a, maxdeg, var != nullptr, st);  // (the base part of `a`: mcp_rollout_pd's own kernels)
   a.ms = *ms;
-  return launch_pd_tiles<true>(a, maxdeg, var != nullptr, st);
+  return launch_open_tiles<true, true>(a, maxdeg, var != nullptr, st);
 }
 
 extern "C" int mcp_rollout_pd(const mcp_model* model, const mcp_pd_policy* pd, const mcp_noise* noise, int M, int T, int particle_pred,
@@ -1251,23 +1224,10 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
   }
 }
 
-extern "C" int mcp_rollout_open_bwd(const mcp_model* model, int M, int T, const double* states, const int32_t* lengths, const double* jac,
-                                    const double* g_states, double* g_x0, double* g_u, void* stream) {
-  if (!model || !states || !jac || !g_states) return MCP_ERR_ARG;
-  if (M <= 0 || T < 2) return MCP_ERR_ARG;
-  if (model->S > MCP_MAX_STATE || model->U > MCP_MAX_INPUT || model->G > MCP_MAX_GP || model->D > MCP_MAX_GPDIM) return MCP_ERR_LIMIT;
-  if (model->S <= 0 || model->U <= 0 || model->G <= 0 || model->D <= 0 || model->n_angle < 0 || model->n_not_angle < 0 ||
-      model->n_not_angle + 2 * model->n_angle + model->U != model->D)
-    return MCP_ERR_ARG;
-  for (int i = 0; i < model->n_angle; ++i)
-    if (model->angle[i] < 0 || model->angle[i] >= model->S) return MCP_ERR_ARG;
-  for (int i = 0; i < model->n_not_angle; ++i)
-    if (model->not_angle[i] < 0 || model->not_angle[i] >= model->S) return MCP_ERR_ARG;
-  for (int g = 0; g < model->G; ++g)
-    if (model->vel[g] < 0 || model->vel[g] >= model->S || model->not_vel[g] < -1 || model->not_vel[g] >= model->S) return MCP_ERR_ARG;
-  if (!g_x0 && !g_u) return MCP_OK;  // nothing asked for
-  OpenBwdArgs a;
-  memset(&a, 0, sizeof(a));
+// ---- host path of the sweeps: checks -> fill -> launch ---------------------------------------------------------------------------------
+// (the sweeps run from the record: they check the model's scalars and index lists, model_lists_ok, and never look at a GP descriptor)
+static void open_bwd_fill(OpenBwdArgs& a, const mcp_model* model, int M, int T, const double* states, const int32_t* lengths, const double* jac,
+                          const double* g_states, double* g_x0, double* g_u) {
   a.S = model->S, a.U = model->U, a.G = model->G, a.D = model->D, a.nna = model->n_not_angle, a.na = model->n_angle, a.M = M, a.T = T;
   for (int i = 0; i < MCP_MAX_STATE; ++i) a.angle[i] = model->angle[i], a.not_angle[i] = model->not_angle[i];
   for (int g = 0; g < MCP_MAX_GP; ++g) a.vel[g] = model->vel[g], a.not_vel[g] = model->not_vel[g];
@@ -1278,13 +1238,30 @@ extern "C" int mcp_rollout_open_bwd(const mcp_model* model, int M, int T, const 
   a.lengths = lengths;
   a.g_x0 = g_x0;
   a.g_u = g_u;
-  const OpenBwdLayout L = open_bwd_layout(a.S, a.G, a.D);  // (at every compiled limit at once: 72 KB)
+}
+// (at every compiled limit at once the layout takes 72 KB, the feedback form 89 KB, the measured form 98 KB)
+template <bool FB, bool PMS>
+static int launch_open_bwd(const typename OpenBwdArgsOf<FB, PMS>::type& a, hipStream_t st) {
+  const OpenBwdLayout L = open_bwd_layout(a.S, a.G, a.D, FB, a.U, PMS);
   const size_t lds = (size_t)L.total * sizeof(double);
   if (lds > MCP_LDS_LIMIT) return MCP_ERR_LIMIT;
-  MCP_ENSURE_MAX_LDS(rollout_open_bwd_kernel<false>);
-  hipLaunchKernelGGL(rollout_open_bwd_kernel<false>, dim3((M + OB_PT - 1) / OB_PT), dim3(OB_NT), lds, (hipStream_t)stream, a);
+  MCP_ENSURE_MAX_LDS((rollout_open_bwd_kernel<FB, PMS>));
+  hipLaunchKernelGGL((rollout_open_bwd_kernel<FB, PMS>), dim3((a.M + OB_PT - 1) / OB_PT), dim3(OB_NT), lds, st, a);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
+}
+
+extern "C" int mcp_rollout_open_bwd(const mcp_model* model, int M, int T, const double* states, const int32_t* lengths, const double* jac,
+                                    const double* g_states, double* g_x0, double* g_u, void* stream) {
+  if (!model || !states || !jac || !g_states) return MCP_ERR_ARG;
+  if (M <= 0 || T < 2) return MCP_ERR_ARG;
+  if (!model_within_limits(model, false)) return MCP_ERR_LIMIT;
+  if (!model_lists_ok(model)) return MCP_ERR_ARG;
+  if (!g_x0 && !g_u) return MCP_OK;  // nothing asked for
+  OpenBwdArgs a;
+  memset(&a, 0, sizeof(a));
+  open_bwd_fill(a, model, M, T, states, lengths, jac, g_states, g_x0, g_u);
+  return launch_open_bwd<false, false>(a, (hipStream_t)stream);
 }
 
 // Reverse-time sweep of the closed loop under the PD law: replaces autograd's backward (MC_PILCO.py:522) through the loop of
@@ -1295,51 +1272,24 @@ static int pd_bwd_dispatch(const mcp_model* model, const mcp_pd_policy* pd, cons
                            void* stream) {
   if (!model || !pd || !states || !inputs || !g_states || (!jac && T > 1)) return MCP_ERR_ARG;
   if (M <= 0 || T < 1) return MCP_ERR_ARG;
-  if (model->S > MCP_MAX_STATE || model->U > MCP_MAX_INPUT || model->G > MCP_MAX_GP || model->D > MCP_MAX_GPDIM) return MCP_ERR_LIMIT;
-  if (model->S <= 0 || model->U <= 0 || model->G <= 0 || model->D <= 0 || model->n_angle < 0 || model->n_not_angle < 0 ||
-      model->n_not_angle + 2 * model->n_angle + model->U != model->D)
-    return MCP_ERR_ARG;
-  for (int i = 0; i < model->n_angle; ++i)
-    if (model->angle[i] < 0 || model->angle[i] >= model->S) return MCP_ERR_ARG;
-  for (int i = 0; i < model->n_not_angle; ++i)
-    if (model->not_angle[i] < 0 || model->not_angle[i] >= model->S) return MCP_ERR_ARG;
-  for (int g = 0; g < model->G; ++g)
-    if (model->vel[g] < 0 || model->vel[g] >= model->S || model->not_vel[g] < -1 || model->not_vel[g] >= model->S) return MCP_ERR_ARG;
-  const int prc = pd_policy_check(model, pd, T);
-  if (prc != MCP_OK) return prc;
-  if (ms && pd_meas_check(model, ms) != MCP_OK) return MCP_ERR_ARG;
+  if (!model_within_limits(model, false)) return MCP_ERR_LIMIT;
+  if (!model_lists_ok(model)) return MCP_ERR_ARG;
+  const int crc = pd_checks(model, pd, ms, T);
+  if (crc != MCP_OK) return crc;
   if (!g_x0 && !g_gains) return MCP_OK;  // nothing asked for
   OpenBwdArgsPdMeas a;
   memset(&a, 0, sizeof(a));
-  a.S = model->S, a.U = model->U, a.G = model->G, a.D = model->D, a.nna = model->n_not_angle, a.na = model->n_angle, a.M = M, a.T = T;
-  for (int i = 0; i < MCP_MAX_STATE; ++i) a.angle[i] = model->angle[i], a.not_angle[i] = model->not_angle[i];
-  for (int g = 0; g < MCP_MAX_GP; ++g) a.vel[g] = model->vel[g], a.not_vel[g] = model->not_vel[g];
-  a.Ts = model->Ts;
-  a.states = states;
-  a.jac = jac;
-  a.g_states = g_states;
-  a.lengths = nullptr;
-  a.g_x0 = g_x0;
-  a.g_u = nullptr;
+  open_bwd_fill(a, model, M, T, states, nullptr, jac, g_states, g_x0, nullptr);
   a.pd = *pd;
   a.inputs = inputs;
   a.g_inputs = g_inputs;
   a.g_gains = g_gains;
-  const bool pms = ms && ms->n > 0;
-  const OpenBwdLayout L = open_bwd_layout(a.S, a.G, a.D, true, a.U, pms);  // (at every compiled limit at once: 89 KB, measured form 98 KB)
-  const size_t lds = (size_t)L.total * sizeof(double);
-  if (lds > MCP_LDS_LIMIT) return MCP_ERR_LIMIT;
-  if (pms) {
+  hipStream_t st = (hipStream_t)stream;
+  if (ms && ms->n > 0) {
     a.ms = *ms;
-    MCP_ENSURE_MAX_LDS((rollout_open_bwd_kernel<true, true>));
-    hipLaunchKernelGGL((rollout_open_bwd_kernel<true, true>), dim3((M + OB_PT - 1) / OB_PT), dim3(OB_NT), lds, (hipStream_t)stream, a);
-  } else {
-    const OpenBwdArgsPd& ab = a;  // (the base part: mcp_rollout_pd_bwd's own kernel)
-    MCP_ENSURE_MAX_LDS(rollout_open_bwd_kernel<true>);
-    hipLaunchKernelGGL(rollout_open_bwd_kernel<true>, dim3((M + OB_PT - 1) / OB_PT), dim3(OB_NT), lds, (hipStream_t)stream, ab);
+    return launch_open_bwd<true, true>(a, st);
   }
-  MCP_LAUNCH_CHECK();
-  return MCP_OK;
+  return launch_open_bwd<true, false>(a, st);  // (the base part of `a`: mcp_rollout_pd_bwd's own kernel)
 }
 
 extern "C" int mcp_rollout_pd_bwd(const mcp_model* model, const mcp_pd_policy* pd, int M, int T, const double* states, const double* inputs,

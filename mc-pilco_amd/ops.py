@@ -391,7 +391,7 @@ def _set_meas(policy, meas, T, M, buf):
 # --------------------------------------------------------------------------------------
 # fused rollout (autograd)
 # --------------------------------------------------------------------------------------
-def _check_noise(noise, T, M, G, B, p_drop, particle_pred):
+def _check_noise(noise, T, M, G, B):
     if noise.eps is not None:
         e = noise.eps
         if e.dtype != DT or not e.is_cuda or not e.is_contiguous() or tuple(e.shape) != (max(T - 1, 0), M, G):
@@ -400,6 +400,48 @@ def _check_noise(noise, T, M, G, B, p_drop, particle_pred):
         k = noise.masks
         if k.dtype != torch.uint8 or not k.is_cuda or not k.is_contiguous() or tuple(k.shape) != (T, M, B):
             raise RuntimeError("masks must be a contiguous uint8 GPU tensor of shape [T,M,B]")
+
+
+def _status_word(status, dev, where):
+    """The caller's status word (an int32[1] on ``dev`` that the kernels OR their flags into) after its check, or a fresh zeroed one."""
+    if status is None:
+        return torch.zeros(1, dtype=torch.int32, device=dev)
+    if status.dtype != torch.int32 or status.numel() != 1 or status.device != dev or not status.is_contiguous():
+        raise RuntimeError("status must be a one-element int32 tensor on " + where)
+    return status
+
+
+def _record_buffers(dev, T, M, S, U, G, D, jac):
+    """(states [T,M,S], inputs [T,M,U] -- None for U None --, jac [T-1,M,G,D] -- None unless ``jac``) of a rollout, uninitialised.  (The
+    max(): a policy-only call, T == 1 without a model, has G == 0.)"""
+    return (torch.empty(T, M, S, dtype=DT, device=dev), None if U is None else torch.empty(T, M, U, dtype=DT, device=dev),
+            torch.empty(max(T - 1, 1), M, max(G, 1), D, dtype=DT, device=dev) if jac else None)
+
+
+def _open_operands(model, x0, u, T, lengths, noise, particle_pred, status):
+    """The operands of the open-loop and PD rollouts as the library takes them: x0 [M,S] and u [T-1,Mu,U] (a 2-D u is one shared sequence;
+    u None: the PD forms, ``T`` given) contiguous float64 on the model's device, ``lengths`` int32 [M], a NoiseSpec (checked under
+    ``particle_pred``) and the status word.  Returns (x0, u, T, lengths, noise, status)."""
+    dev = model.device
+    x0 = x0.to(device=dev, dtype=DT).contiguous()
+    if x0.dim() != 2 or x0.shape[1] != model.S:
+        raise RuntimeError("x0 must be [M,%d]" % model.S)
+    M = int(x0.shape[0])
+    if u is not None:
+        u = u.to(device=dev, dtype=DT)
+        if u.dim() == 2:
+            u = u.reshape(u.shape[0], 1, u.shape[1])  # (under autograd the gradient comes back in u's own shape)
+        if u.dim() != 3 or u.shape[2] != model.U or u.shape[1] not in (1, M) or u.shape[0] < 1:
+            raise RuntimeError("u must be [T-1,M,%d] or [T-1,%d]" % (model.U, model.U))
+        u, T = u.contiguous(), int(u.shape[0]) + 1
+    noise = NoiseSpec() if noise is None else noise
+    if particle_pred:
+        _check_noise(noise, T, M, model.G, 0)
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths, dtype=torch.int32).to(dev).contiguous()
+        if tuple(lengths.shape) != (M,):
+            raise RuntimeError("lengths must have one entry per trajectory")
+    return x0, u, T, lengths, noise, _status_word(status, dev, "the rollout's device")
 
 
 def _mc(model):
@@ -435,14 +477,9 @@ def rollout_forward_raw(model: Optional[PackedModel], policy: PackedPolicy, nois
     x0 = x0.detach().to(device=dev, dtype=DT).contiguous()
     M = x0.shape[0]
     G, D = (0, policy.U) if model is None else (model.G, model.D)
-    _check_noise(noise, T, M, G, policy.B, p_drop, particle_pred)
-    states = torch.empty(T, M, policy.S, dtype=DT, device=dev)
-    inputs = torch.empty(T, M, policy.U, dtype=DT, device=dev)
-    jac = torch.empty(max(T - 1, 1), M, max(G, 1), D, dtype=DT, device=dev) if (need_jac and T > 1) else None
-    if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-    elif status.dtype != torch.int32 or status.numel() != 1 or status.device != x0.device or not status.is_contiguous():
-        raise RuntimeError("status must be a one-element int32 tensor on the rollout's device")
+    _check_noise(noise, T, M, G, policy.B)
+    states, inputs, jac = _record_buffers(dev, T, M, policy.S, policy.U, G, D, need_jac and T > 1)
+    status = _status_word(status, x0.device, "the rollout's device")
     pc = policy.bind(p_drop)
     nz = noise.to_c()
     meas_buf = torch.empty(T, M, policy.S, dtype=DT, device=dev) if meas is not None else None
@@ -489,31 +526,11 @@ def rollout_open(model: PackedModel, x0, u, *, lengths=None, noise: Optional[Noi
             raise RuntimeError("rollout_open operates on GPU memory only (%s is not a GPU tensor); there is no CPU path" % name)
         if t.requires_grad:
             raise RuntimeError("rollout_open has no gradient: %s requires grad (detach it; the closed-loop ops.rollout is the differentiable one)" % name)
-    dev = model.device
-    x0 = x0.to(device=dev, dtype=DT).contiguous()
-    u = u.to(device=dev, dtype=DT).contiguous()
-    if x0.dim() != 2 or x0.shape[1] != model.S:
-        raise RuntimeError("x0 must be [M,%d]" % model.S)
-    M = int(x0.shape[0])
-    if u.dim() == 2:
-        u = u.reshape(u.shape[0], 1, u.shape[1])
-    if u.dim() != 3 or u.shape[2] != model.U or u.shape[1] not in (1, M) or u.shape[0] < 1:
-        raise RuntimeError("u must be [T-1,M,%d] or [T-1,%d]" % (model.U, model.U))
-    T, Mu = int(u.shape[0]) + 1, int(u.shape[1])
-    noise = NoiseSpec() if noise is None else noise
-    if particle_pred:
-        _check_noise(noise, T, M, model.G, 0, 0.0, True)
-    if lengths is not None:
-        lengths = torch.as_tensor(lengths, dtype=torch.int32).to(dev).contiguous()
-        if tuple(lengths.shape) != (M,):
-            raise RuntimeError("lengths must have one entry per trajectory")
+    x0, u, T, lengths, noise, status = _open_operands(model, x0, u, None, lengths, noise, particle_pred, status)
+    dev, M, Mu = model.device, int(x0.shape[0]), int(u.shape[1])
     states = torch.empty(T, M, model.S, dtype=DT, device=dev)
     mu = torch.zeros(T - 1, M, model.G, dtype=DT, device=dev) if moments else None
     var = torch.zeros(T - 1, M, model.G, dtype=DT, device=dev) if moments else None
-    if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-    elif status.dtype != torch.int32 or status.numel() != 1 or status.device != x0.device or not status.is_contiguous():
-        raise RuntimeError("status must be a one-element int32 tensor on the rollout's device")
     nz = noise.to_c()
     abi.check(abi.lib().mcp_rollout_open(_mc(model), C.byref(nz), M, T, int(bool(particle_pred)), abi.ptr(x0), abi.ptr(u), Mu, abi.ptr(lengths),
                                          abi.ptr(states), abi.ptr(mu), abi.ptr(var), abi.ptr(status), abi.stream()), "mcp_rollout_open")
@@ -530,9 +547,7 @@ class RolloutOpenFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, u, model, lengths, noise, particle_pred, status):
         T, Mu, M = int(u.shape[0]) + 1, int(u.shape[1]), int(x0.shape[0])
-        dev = model.device
-        states = torch.empty(T, M, model.S, dtype=DT, device=dev)
-        jac = torch.empty(T - 1, M, model.G, model.D, dtype=DT, device=dev)  # (rows from len - 1 on: never written, never read)
+        states, _, jac = _record_buffers(model.device, T, M, model.S, None, model.G, model.D, True)  # (jac rows from len - 1 on: never written, never read)
         nz = noise.to_c()
         abi.check(abi.lib().mcp_rollout_open_rec(_mc(model), C.byref(nz), M, T, int(bool(particle_pred)), abi.ptr(x0), abi.ptr(u), Mu,
                                                  abi.ptr(lengths), abi.ptr(states), None, None, abi.ptr(jac), abi.ptr(status), abi.stream()),
@@ -566,29 +581,7 @@ def rollout_open_diff(model: PackedModel, x0, u, *, lengths=None, noise: Optiona
             raise RuntimeError("rollout_open_diff operates on GPU memory only (%s is not a GPU tensor); there is no CPU path" % name)
     if not (torch.is_grad_enabled() and (x0.requires_grad or u.requires_grad)):
         return rollout_open(model, x0.detach(), u.detach(), lengths=lengths, noise=noise, particle_pred=particle_pred, status=status)
-    dev = model.device
-    x0c = x0.to(device=dev, dtype=DT).contiguous()
-    if x0c.dim() != 2 or x0c.shape[1] != model.S:
-        raise RuntimeError("x0 must be [M,%d]" % model.S)
-    M = int(x0c.shape[0])
-    uc = u.to(device=dev, dtype=DT)
-    if uc.dim() == 2:
-        uc = uc.reshape(uc.shape[0], 1, uc.shape[1])  # (autograd hands the gradient back in u's own shape)
-    if uc.dim() != 3 or uc.shape[2] != model.U or uc.shape[1] not in (1, M) or uc.shape[0] < 1:
-        raise RuntimeError("u must be [T-1,M,%d] or [T-1,%d]" % (model.U, model.U))
-    uc = uc.contiguous()
-    T = int(uc.shape[0]) + 1
-    noise = NoiseSpec() if noise is None else noise
-    if particle_pred:
-        _check_noise(noise, T, M, model.G, 0, 0.0, True)
-    if lengths is not None:
-        lengths = torch.as_tensor(lengths, dtype=torch.int32).to(dev).contiguous()
-        if tuple(lengths.shape) != (M,):
-            raise RuntimeError("lengths must have one entry per trajectory")
-    if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-    elif status.dtype != torch.int32 or status.numel() != 1 or status.device != x0c.device or not status.is_contiguous():
-        raise RuntimeError("status must be a one-element int32 tensor on the rollout's device")
+    x0c, uc, _, lengths, noise, status = _open_operands(model, x0, u, None, lengths, noise, particle_pred, status)
     return RolloutOpenFunction.apply(x0c, uc, model, lengths, noise, bool(particle_pred), status), status
 
 
@@ -643,9 +636,7 @@ class PackedPD:
 
 def _rollout_pd_launch(model, pd, kp, kd, noise, x0, T, particle_pred, status, record, meas=None):
     M, dev = int(x0.shape[0]), model.device
-    states = torch.empty(T, M, model.S, dtype=DT, device=dev)
-    inputs = torch.empty(T, M, model.U, dtype=DT, device=dev)
-    jac = torch.empty(T - 1, M, model.G, model.D, dtype=DT, device=dev) if (record and T > 1) else None
+    states, inputs, jac = _record_buffers(dev, T, M, model.S, model.U, model.G, model.D, record and T > 1)
     pc, nz = pd.to_c(kp, kd), noise.to_c()
     if meas is None:
         abi.check(abi.lib().mcp_rollout_pd(_mc(model), C.byref(pc), C.byref(nz), M, T, int(bool(particle_pred)), abi.ptr(x0), abi.ptr(states),
@@ -714,22 +705,12 @@ def rollout_pd(model: PackedModel, pd: PackedPD, noise: Optional[NoiseSpec], x0,
     the calls made are the ones made without the argument.  The return has the same three elements either way."""
     if not isinstance(x0, torch.Tensor) or not x0.is_cuda or not pd.sqrt_kp.is_cuda or not pd.sqrt_kd.is_cuda:
         raise RuntimeError("rollout_pd operates on GPU memory only (x0 and the gains must be GPU tensors); there is no CPU path")
-    dev, T = model.device, int(T)
+    T = int(T)
     if pd.S != model.S or pd.U != model.U:
         raise RuntimeError("the PD controller is for %d states and %d inputs, the model has %d and %d" % (pd.S, pd.U, model.S, model.U))
     if T < 1 or pd.target_traj.shape[0] < T:
         raise RuntimeError("the target trajectory has %d rows, the rollout needs %d" % (pd.target_traj.shape[0], T))
-    x0c = x0.to(device=dev, dtype=DT).contiguous()
-    if x0c.dim() != 2 or x0c.shape[1] != model.S:
-        raise RuntimeError("x0 must be [M,%d]" % model.S)
-    M = int(x0c.shape[0])
-    noise = NoiseSpec() if noise is None else noise
-    if particle_pred:
-        _check_noise(noise, T, M, model.G, 0, 0.0, True)
-    if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-    elif status.dtype != torch.int32 or status.numel() != 1 or status.device != x0c.device or not status.is_contiguous():
-        raise RuntimeError("status must be a one-element int32 tensor on the rollout's device")
+    x0c, _, _, _, noise, status = _open_operands(model, x0, None, T, None, noise, particle_pred, status)
     kp, kd = pd.gains()
     if torch.is_grad_enabled() and (x0c.requires_grad or kp.requires_grad or kd.requires_grad):
         states, inputs = RolloutPDFunction.apply(x0c, kp.contiguous(), kd.contiguous(), model, pd, noise, T, bool(particle_pred), status, meas)
@@ -1026,10 +1007,7 @@ class PosteriorFunction(torch.autograd.Function):
         var = torch.empty(M, dtype=DT, device=Zc.device)
         Jm = torch.empty(M, D, dtype=DT, device=Zc.device) if need else None
         Jv = torch.empty(M, D, dtype=DT, device=Zc.device) if need else None
-        if status is None:  # (nobody asked: the flags go to a scratch word)
-            status = torch.zeros(1, dtype=torch.int32, device=Zc.device)
-        elif status.dtype != torch.int32 or status.numel() != 1 or status.device != Zc.device or not status.is_contiguous():
-            raise RuntimeError("status must be a one-element int32 tensor on the test points' device")
+        status = _status_word(status, Zc.device, "the test points' device")  # (None, nobody asked: the flags go to a scratch word)
         g = gp.to_c()
         abi.check(abi.lib().mcp_posterior_fwd_ex(C.byref(g), M, abi.ptr(Zc), abi.ptr(mu), abi.ptr(var), abi.ptr(Jm), abi.ptr(Jv), abi.ptr(status),
                                                  abi.stream(), C.byref(abi.DISPATCH)), "mcp_posterior_fwd")

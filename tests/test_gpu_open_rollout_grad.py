@@ -3,7 +3,11 @@ Model_learning.open_loop_rollout(differentiable=True)) against torch autograd th
 bitwise contracts of the recording form.
 
 Bounds (the ones tests/test_gpu_parity.py holds the closed-loop adjoint to on the oracle's own Kinv / alpha): states 1e-9
-absolute, gradients 1e-9 relative to the gradient's largest magnitude."""
+absolute, gradients 1e-9 relative to the gradient's largest magnitude.
+
+The tiles of the recording form: its two panels (k and v = Kinv k, [Npad][pitch] each) fit the LDS with 16 trajectories per workgroup up to
+Npad ~ 540 and with 4 up to ~ 2450, beyond that one trajectory.  CASES stops at N = 300, so test_the_smaller_tiles_of_the_recording_form
+launches the 4- and the 1-trajectory kernels (N = 640, Npad 640; N = 2600, Npad 2608) at degree classes 0 and 2."""
 import functools
 
 import numpy as np
@@ -101,6 +105,32 @@ def test_states_carry_the_bits_of_the_plain_call(noise):
     # nothing requires grad: nothing is recorded, the call is rollout_open
     s0, _ = ops.rollout_open_diff(pm, G(x0), G(u), lengths=lens)
     assert not s0.requires_grad and torch.equal(s0, ops.rollout_open(pm, G(x0), G(u), lengths=lens)[0])
+
+
+# The rungs below are held to the bounds of the N = 300 cases of CASES (STATE_TOL, GRAD_TOL): the library of the commit before the host path
+# was unified measured below them on an MI355X at every rung (states / g_x0 / g_u; a case measuring above would have been given four times
+# its measurement, the headroom the N = 1100 / 1500 bounds of tests/test_gpu_open_rollout.py carry):
+#   N 640  degree 0  5.7e-12 / 1.3e-12 / 1.4e-11      N 640  degree 2  6.3e-12 / 1.6e-12 / 1.3e-11
+#   N 2600 degree 0  5.8e-11 / 1.2e-11 / 4.6e-11      N 2600 degree 2  6.8e-11 / 1.7e-11 / 7.2e-11
+@pytest.mark.parametrize("N,deg", [(640, 0), (640, 2), (2600, 0), (2600, 2)])
+def test_the_smaller_tiles_of_the_recording_form(N, deg):
+    """Sampled, M = 5, T = 3 on the base shape: the recording launch runs 4 trajectories per workgroup at N = 640 and one at N = 2600 (the
+    plain launch 16 and 4).  Status 0; the states carry the bits of the plain call; states and both gradients against the oracle."""
+    from mc_pilco_amd import ops
+
+    c, m, pm = pair("speed", N, deg)
+    M, T = 5, 3
+    x0, u, eps, w = inputs_for(c, M, T, seed=T * 100 + M)
+    torch.set_num_threads(1)
+    ost, ogx, ogu, vmin = oracle_truth("speed", m, x0, u, eps, w, True)
+    assert vmin > 0.0
+    st, gx, gu, status = gpu_grads(pm, x0, u, eps, w, True)
+    sp, status_p = ops.rollout_open(pm, G(x0), G(u), noise=ops.NoiseSpec(eps=G(eps)), particle_pred=True)
+    es, ex, eu = float((st.cpu() - ost).abs().max()), relmax(gx, ogx), relmax(gu, ogu)
+    print("rung N %d deg %d: states %.3e g_x0 %.3e g_u %.3e (min var %.3e)" % (N, deg, es, ex, eu, vmin))
+    assert status == 0 and int(status_p.item()) == 0
+    assert torch.equal(st, sp)
+    assert es < STATE_TOL and ex < GRAD_TOL and eu < GRAD_TOL
 
 
 def test_philox_mode_against_central_differences():

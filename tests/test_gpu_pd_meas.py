@@ -4,7 +4,11 @@ through the oracle's step with the measurement and the policy written out (tests
 tests/test_pd_meas_cpu.py), and the bitwise contracts it shares with mcp_rollout_pd and the open-loop kernels.
 
 Bounds: those of tests/test_gpu_pd_rollout.py, unchanged -- states 1e-9 absolute, inputs 2e-9 absolute, gradients 1e-9 relative to the
-gradient's largest magnitude; the measured states are held to the states' bound."""
+gradient's largest magnitude; the measured states are held to the states' bound.
+
+The tiles: as in tests/test_gpu_pd_rollout.py, CASES stops at N = 300 (16 trajectories per workgroup).  The measured form's recording
+kernels with 4 and 1 trajectories (N = 640, N = 2600) and its 4-trajectory kernel without a record (N = 1200) are launched by the two rung
+tests below, at degree class 0; degree class 2 at those sizes is left out on purpose (see tests/test_gpu_pd_rollout.py)."""
 import contextlib
 import ctypes as C
 import functools
@@ -134,6 +138,63 @@ def test_plain_launch_recording_launch_and_open_loop_launch_carry_the_same_bits(
     assert sr.requires_grad and int(status_r.item()) == 0
     assert torch.equal(sr.detach(), st) and torch.equal(ir.detach(), inp) and torch.equal(yr, ym)
     assert float((ym[1:, :, :2] - st[1:, :, :2]).abs().min()) > 0 and torch.equal(ym[0], st[0])  # a measurement was simulated; row 0 is true
+
+
+# The rungs are held to the bounds of the N = 300 case of CASES (STATE_TOL for states and measurements, INPUT_TOL, GRAD_TOL): the library of
+# the commit before the host path was unified measured below them on an MI355X at every rung (states / inputs / meas / g_sqrt_kp /
+# g_sqrt_kd / g_x0; a case measuring above would have been given four times its measurement, as in tests/test_gpu_pd_rollout.py):
+#   N 640   5.4e-13 / 5.3e-14 / 9.1e-14 / 2.1e-13 / 5.8e-13 / 4.9e-13      N 2600  1.1e-11 / 2.0e-12 / 2.2e-12 / 1.7e-12 / 8.5e-12 / 3.1e-12
+#   N 1200, no record  3.2e-12 / 6.8e-13 / 9.5e-13
+def _rung_case(N):
+    c, m, pm = pair("arm2", N, 0)
+    M, T = 5, 3
+    x0, kp, kd, target, eps, w, wu = inputs_for(c, M, T, seed=T * 100 + M)
+    ms = meas_model("arm2")
+    pn = pos_noise_for(T, M, 2, seed=T * 100 + M)
+    torch.set_num_threads(1)
+    truth = pd_meas_truth("arm2", m, x0, kp, kd, target, eps, pn, w, wu, True, ms)
+    assert truth[-1] > 0.0
+    return c, pm, M, T, x0, kp, kd, target, eps, w, wu, ms, pn, truth
+
+
+@pytest.mark.parametrize("N", [640, 2600])
+def test_the_smaller_tiles_of_the_recording_form(N):
+    """Sampled, degree 0, M = 5, T = 3 on arm2, every joint measured: the recording launch runs 4 trajectories per workgroup at N = 640 and
+    one at N = 2600.  Status 0; states, inputs and measurements carry the bits of the launch without a record, whose states carry the bits of
+    the open-loop launch on its inputs; states, inputs, measurements and the three gradients against the truth."""
+    from mc_pilco_amd import ops
+
+    c, pm, M, T, x0, kp, kd, target, eps, w, wu, ms, pn, (ost, oin, oym, ogp, ogd, ogx, vmin) = _rung_case(N)
+    pol = controller(c, kp, kd, target)
+    st, inp, ym, gp_, gd_, gx, status = gpu_run(pm, pol, x0, eps, pn, w, wu, True, T, ms)
+    s0 = spec(ms, pn)
+    with torch.no_grad():
+        st0, i0, status0 = ops.rollout_pd(pm, pol.packed(), ops.NoiseSpec(eps=G(eps)), G(x0), T, particle_pred=True, meas=s0)
+    so, status_o = ops.rollout_open(pm, G(x0), i0[:T - 1].contiguous(), noise=ops.NoiseSpec(eps=G(eps)), particle_pred=True)
+    es, ei, em = float((st.cpu() - ost).abs().max()), float((inp.cpu() - oin).abs().max()), float((ym.cpu() - oym).abs().max())
+    ep, ed, ex = relmax(gp_, ogp), relmax(gd_, ogd), relmax(gx, ogx)
+    print("rung N %d: states %.3e inputs %.3e meas %.3e g_sqrt_kp %.3e g_sqrt_kd %.3e g_x0 %.3e (min var %.3e)" % (N, es, ei, em, ep, ed, ex, vmin))
+    assert status == 0 and int(status0.item()) == 0 and int(status_o.item()) == 0
+    assert torch.equal(st, st0) and torch.equal(inp, i0) and torch.equal(ym, s0.measured) and torch.equal(st0, so)
+    assert es < STATE_TOL and ei < INPUT_TOL and em < STATE_TOL
+    assert ep < GRAD_TOL and ed < GRAD_TOL and ex < GRAD_TOL
+
+
+def test_the_four_trajectory_tile_without_a_record():
+    """Sampled, degree 0, N = 1200 (the k panel of 16 trajectories does not fit), nothing requires grad: status 0, the states carry the bits
+    of the open-loop launch on the inputs, states, inputs and measurements against the truth.  (No record, so no gradient to compare.)"""
+    from mc_pilco_amd import ops
+
+    c, pm, M, T, x0, kp, kd, target, eps, w, wu, ms, pn, (ost, oin, oym, _, _, _, vmin) = _rung_case(1200)
+    pd = controller(c, kp, kd, target, trainable=False).packed()
+    sp = spec(ms, pn)
+    st, inp, status = ops.rollout_pd(pm, pd, ops.NoiseSpec(eps=G(eps)), G(x0), T, particle_pred=True, meas=sp)
+    so, status_o = ops.rollout_open(pm, G(x0), inp[:T - 1].contiguous(), noise=ops.NoiseSpec(eps=G(eps)), particle_pred=True)
+    es, ei, em = float((st.cpu() - ost).abs().max()), float((inp.cpu() - oin).abs().max()), float((sp.measured.cpu() - oym).abs().max())
+    print("rung N 1200 deg 0, no record: states %.3e inputs %.3e meas %.3e (min var %.3e)" % (es, ei, em, vmin))
+    assert int(status.item()) == 0 and int(status_o.item()) == 0 and not st.requires_grad
+    assert torch.equal(st, so)
+    assert es < STATE_TOL and ei < INPUT_TOL and em < STATE_TOL
 
 
 def raw_run(pm, pd, kpg, kdg, ms, nz, x0, T, w, wu, sample=True, entry="meas"):

@@ -3,7 +3,13 @@ PD_controller) against torch autograd through the oracle's step with the policy 
 reference by tests/test_pd_rollout_cpu.py), and the bitwise contracts with the open-loop kernels it shares its phases with.
 
 Bounds (on the oracle's own Kinv / alpha): states 1e-9 absolute, inputs 2e-9 absolute, gradients 1e-9 relative to the
-gradient's largest magnitude."""
+gradient's largest magnitude.
+
+The tiles (the ladder the feedback form shares with the open-loop form): CASES stops at N = 300, where every launch with a variance runs
+16 trajectories per workgroup.  test_the_smaller_tiles_of_the_recording_form launches the recording form's 4- and 1-trajectory kernels
+(N = 640, N = 2600) and test_the_four_trajectory_tile_without_a_record the plain launch's 4-trajectory kernel (N = 1200).  The recording
+kernels of degree class 2 at those sizes are left out on purpose: four more long training-set builds for kernels that differ from the ones
+launched here by the degree template argument of the same ladder code, which the open-loop module's rungs exercise at both classes."""
 import contextlib
 import functools
 import io
@@ -114,6 +120,60 @@ def test_states_carry_the_bits_of_the_open_loop_launch(noise):
     sr, ir, status_r = ops.rollout_pd(pm, pol.packed(), nz(), G(x0), T, particle_pred=sample)  # the gains require grad: the recording launch
     assert sr.requires_grad and int(status_r.item()) == 0
     assert torch.equal(sr.detach(), st) and torch.equal(ir.detach(), inp)
+
+
+# ---- 2b. the ladder's smaller tiles ---------------------------------------------------------------------------------------------------------
+# The rungs are held to the bounds of the N = 300 cases of CASES (STATE_TOL, INPUT_TOL, GRAD_TOL): the library of the commit before the host
+# path was unified measured below them on an MI355X at every rung (states / inputs / g_sqrt_kp / g_sqrt_kd / g_x0; a case measuring above
+# would have been given four times its measurement, the headroom the N = 1100 / 1500 bounds of tests/test_gpu_open_rollout.py carry):
+#   N 640   6.2e-13 / 1.9e-13 / 5.6e-13 / 5.6e-13 / 2.9e-13      N 2600  7.4e-12 / 4.2e-12 / 8.5e-12 / 1.1e-11 / 2.8e-12
+#   N 1200, degree 2, no record  3.2e-12 / 1.2e-12
+@pytest.mark.parametrize("N", [640, 2600])
+def test_the_smaller_tiles_of_the_recording_form(N):
+    """Sampled, degree 0, M = 5, T = 3 on arm2: the recording launch runs 4 trajectories per workgroup at N = 640 and one at N = 2600.
+    Status 0; states and inputs carry the bits of the launch without a record, whose states carry the bits of the open-loop launch on its
+    inputs; states, inputs and the three gradients against the truth."""
+    from mc_pilco_amd import ops
+
+    c, m, pm = pair("arm2", N, 0)
+    M, T = 5, 3
+    x0, kp, kd, target, eps, w, wu = inputs_for(c, M, T, seed=T * 100 + M)
+    torch.set_num_threads(1)
+    ost, oin, ogp, ogd, ogx, vmin = pd_truth("arm2", m, x0, kp, kd, target, eps, w, wu, True)
+    assert vmin > 0.0
+    pol = controller(c, kp, kd, target)
+    st, inp, gp_, gd_, gx, status = gpu_run(pm, pol, x0, eps, w, wu, True, T)
+    with torch.no_grad():
+        s0, i0, status0 = ops.rollout_pd(pm, pol.packed(), ops.NoiseSpec(eps=G(eps)), G(x0), T, particle_pred=True)
+    so, status_o = ops.rollout_open(pm, G(x0), i0[:T - 1].contiguous(), noise=ops.NoiseSpec(eps=G(eps)), particle_pred=True)
+    es, ei = float((st.cpu() - ost).abs().max()), float((inp.cpu() - oin).abs().max())
+    ep, ed, ex = relmax(gp_, ogp), relmax(gd_, ogd), relmax(gx, ogx)
+    print("rung N %d: states %.3e inputs %.3e g_sqrt_kp %.3e g_sqrt_kd %.3e g_x0 %.3e (min var %.3e)" % (N, es, ei, ep, ed, ex, vmin))
+    assert status == 0 and int(status0.item()) == 0 and int(status_o.item()) == 0
+    assert torch.equal(st, s0) and torch.equal(inp, i0) and torch.equal(s0, so)
+    assert es < STATE_TOL and ei < INPUT_TOL
+    assert ep < GRAD_TOL and ed < GRAD_TOL and ex < GRAD_TOL
+
+
+def test_the_four_trajectory_tile_without_a_record():
+    """Sampled, degree 2, N = 1200 (the k panel of 16 trajectories does not fit), nothing requires grad: status 0, the states carry the bits
+    of the open-loop launch on the inputs, states and inputs against the truth.  (No record, so no gradient to compare.)"""
+    from mc_pilco_amd import ops
+
+    c, m, pm = pair("arm2", 1200, 2)
+    M, T = 5, 3
+    x0, kp, kd, target, eps, w, wu = inputs_for(c, M, T, seed=T * 100 + M)
+    torch.set_num_threads(1)
+    ost, oin, _, _, _, vmin = pd_truth("arm2", m, x0, kp, kd, target, eps, w, wu, True)
+    assert vmin > 0.0
+    pd = controller(c, kp, kd, target, trainable=False).packed()
+    st, inp, status = ops.rollout_pd(pm, pd, ops.NoiseSpec(eps=G(eps)), G(x0), T, particle_pred=True)
+    so, status_o = ops.rollout_open(pm, G(x0), inp[:T - 1].contiguous(), noise=ops.NoiseSpec(eps=G(eps)), particle_pred=True)
+    es, ei = float((st.cpu() - ost).abs().max()), float((inp.cpu() - oin).abs().max())
+    print("rung N 1200 deg 2, no record: states %.3e inputs %.3e (min var %.3e)" % (es, ei, vmin))
+    assert int(status.item()) == 0 and int(status_o.item()) == 0 and not st.requires_grad
+    assert torch.equal(st, so)
+    assert es < STATE_TOL and ei < INPUT_TOL
 
 
 # ---- 3. Philox mode: central differences of the op ------------------------------------------------------------------------------------------
