@@ -1,5 +1,5 @@
-// Device-side helpers shared by the gfx950 kernels: wave64 DPP reductions, Philox4x32-10,
-// and the covariance function of include/mcpilco_hip.h's mcp_kernel.
+// Device-side helpers shared by the gfx950 kernels: the launch macros, imin / imax, the v4d accumulator type, the LDS-only barrier,
+// wave64 DPP reductions, Philox4x32-10, and the covariance function of include/mcpilco_hip.h's mcp_kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -28,7 +28,16 @@
     }                                                                                                                       \
   } while (0)
 
+__host__ __device__ inline int imax(int a, int b) { return a > b ? a : b; }
+__host__ __device__ inline int imin(int a, int b) { return a < b ? a : b; }
+
 namespace mcp {
+
+typedef double v4d __attribute__((ext_vector_type(4)));  // an accumulator of v_mfma_f64_16x16x4_f64
+
+// workgroup barrier that orders LDS traffic only: global loads in flight and global stores issued earlier (fire-and-forget in the rollout
+// kernels: nobody in the kernel reads them back) are not drained at every barrier, as __syncthreads would
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // ---------------------------------------------------------------------------------------
 // wave64 sum of a double via DPP (gfx9 row_shr / row_bcast controls); result broadcast to

@@ -1,14 +1,11 @@
 // Shared by the rollout sources (rollout_fwd*.hip, rollout_bwd.hip, rollout_open.hip): feature maps of the dynamics model and of the
-// policy, descriptor validation (model_within_limits, model_lists_ok, model_ok, meas_pairs_disjoint, policy_ok), small integer helpers.
+// policy, descriptor validation (model_within_limits, model_lists_ok, model_ok, meas_pairs_disjoint, policy_ok).
 #pragma once
 #include <string.h>
 
 #include "mcp_device.h"
 
 #define MCP_LDS_LIMIT (160 * 1024)
-
-__host__ __device__ inline int imax(int a, int b) { return a > b ? a : b; }
-__host__ __device__ inline int imin(int a, int b) { return a < b ? a : b; }
 
 // GP input z = [x[not_angle], sin x[angle], cos x[angle], u]   (Model_learning.py:670-683)
 // policy feature s = [x_nonangle, COS, SIN] (Policy.py:326-333) or [x, x*_t - x] (:397-399)
@@ -25,10 +22,6 @@ __device__ __forceinline__ double policy_feature(const mcp_policy& pl, const dou
   }
   return x[q];
 }
-
-// workgroup barrier that orders LDS traffic only: global stores issued earlier are fire-and-forget in
-// the rollout kernels (nobody in the kernel reads them back), so they are not drained at every barrier
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // hand-off buffer of the GP-sharded forward launch (rollout_fwd.hip): [clusters][2][G][P][2] granules of 8 bytes, clusters * P < M + 16 (a launch per chunk, each rounded up to whole clusters)
 static inline size_t rollout_xch_bytes(int M, int G) { return ((size_t)(M + 16) * 2 * G * 2 * sizeof(unsigned long long) + 15) & ~(size_t)15; }

@@ -486,7 +486,6 @@ __device__ __forceinline__ void vsum_range(const GpL& gp, int ggl, int gl, const
 // (three LDS reads and a multiply), accumulator  D[row = (l>>4) + 4r][col = l&15].  The 8 waves split N; their partial tiles
 // meet in LDS (redw) and the finalize phase adds the 8 partials.  The centred sums the Jacobians need follow from
 //     sum_j w_j (z_c - X_jc) = z_c * R[D][n] - R[c][n].
-typedef double v4d __attribute__((ext_vector_type(4)));
 #define RF_NAX(deg) ((deg) == 0 ? 2 : ((deg) == 1 ? 5 : 9))
 
 template <int P, bool XLDS, int DEG, bool WPRE>

@@ -137,7 +137,6 @@ __device__ __forceinline__ size_t xch_slot(int cluster, int t, int G, int g, int
 // form that drops the line from the XCD's L2 was measured and dropped: profiles/NOTES.md part A.)
 __device__ __forceinline__ void store_output(double* p, double v) { *p = v; }
 
-typedef double v4d_t __attribute__((ext_vector_type(4)));
 // sum over the 4 lanes l, l^16, l^32, l^48 (the 4 feature groups of an MFMA operand column)
 __device__ __forceinline__ double fold_kk(double v) {
   return sum_xor32(sum_xor16(v));

@@ -28,8 +28,6 @@
 
 using namespace mcp;
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-
 #define TL_PT 16       // particles per workgroup
 #define TL_KR 18       // row pitch (doubles) of the k / v panels: 16 particles + 2 pad (bank spread of the phase-K stores)
 #define TL_MAXTASK 4   // 32-row blocks of Kinv per wave (N <= 1024)

@@ -47,8 +47,6 @@
 
 using namespace mcp;
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-
 #define RO_VU 4  // 4-row MFMA steps per register batch of phase V
 
 struct OpenArgs {

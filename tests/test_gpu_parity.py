@@ -130,12 +130,9 @@ def test_sod_indices_exact(golden):
     assert ops.sod_select(sp, X, float(fx["thr_abs"])) == [int(i) for i in fx["idx_abs"]]
 
 
-@pytest.mark.parametrize("N", [600, 601, 729, 1000, 1153, 1500, 2048, 4096])
-def test_blocked_cholesky_across_workgroups(N):
-    """Round 5: from 600 rows on `mcp_chol_factor` factorises by panels of 128 rows across the chip (the diagonal block by the one-workgroup
-    kernel, U_kj = W^T A_kj and the trailing update A_ij -= U_ki^T U_kj as MFMA products of one wave per tile; scratch in the lower triangle,
-    which comes back zero) -- sizes around the panel edges, beyond the old 1152-row limit, up to 4096: U^T U = K to 1e-13, upper
-    triangular, logdet against numpy to 1e-10; and the not-positive-definite flag from a pivot in a late panel."""
+def _factor_and_inverse_hold(N):
+    """U^T U = K to 1e-13, U and U^-1 upper triangular, logdet against numpy to 1e-10, U^-1 U = I to 1e-11, K^-1 against numpy to 1e-10;
+    returns K."""
     from gpu_helpers import G
     from mc_pilco_amd import ops
 
@@ -154,9 +151,38 @@ def test_blocked_cholesky_across_workgroups(N):
     assert float(torch.tril(Ui, -1).abs().max()) == 0.0
     assert float((Ui @ U - torch.eye(N, dtype=U.dtype, device=U.device)).abs().max()) < 1e-11
     assert relerr(Kinv, np.linalg.inv(K)) < 1e-10
+    return K
+
+
+@pytest.mark.parametrize("N", [600, 601, 729, 1000, 1153, 1500, 2048, 4096])
+def test_blocked_cholesky_across_workgroups(N):
+    """Round 5: from 600 rows on `mcp_chol_factor` factorises by panels of 128 rows across the chip (the diagonal block by the one-workgroup
+    kernel, U_kj = W^T A_kj and the trailing update A_ij -= U_ki^T U_kj as MFMA products of one wave per tile; scratch in the lower triangle,
+    which comes back zero) -- sizes around the panel edges, beyond the old 1152-row limit, up to 4096: U^T U = K to 1e-13, upper
+    triangular, logdet against numpy to 1e-10; and the not-positive-definite flag from a pivot in a late panel."""
+    from gpu_helpers import G
+    from mc_pilco_amd import ops
+
+    K = _factor_and_inverse_hold(N)
     if N == 729:
         K2 = K.copy()
         K2[700, 700] = -5.0  # a pivot of the last panel
+        assert ops.status_flags(ops.chol_factor(G(K2))[2])["not_spd"]
+
+
+@pytest.mark.parametrize("N", [599, 656, 657, 1281])
+def test_cholesky_and_inverse_at_the_seams_of_the_launch_helpers(N):
+    """The same assertions and bounds where the host's launch helpers change hands: 599, the last size of the one-workgroup kernel; 656 and
+    657, panels whose last one has 16 rows (the LDS kernel on a tail) and 17 rows (the left-looking kernel on a tail; 1153 above has a 1-row
+    tail); 1281, the blocked inverse with ten full diagonal blocks in one batched launch pair and a 1-row last block through the same
+    helper.  And the not-positive-definite flag from a pivot of a 16-row tail panel."""
+    from gpu_helpers import G
+    from mc_pilco_amd import ops
+
+    K = _factor_and_inverse_hold(N)
+    if N == 656:
+        K2 = K.copy()
+        K2[650, 650] = -5.0
         assert ops.status_flags(ops.chol_factor(G(K2))[2])["not_spd"]
 
 

@@ -1,4 +1,4 @@
-"""Host replay of the control flow of tri_inverse_cols4_kernel (csrc/gp_pretrain.hip): four waves share a block column of U^-1, meet at two
+"""Host replay of the control flow of tri_inverse_cols4_kernel (csrc/gp_linalg.hip): four waves share a block column of U^-1, meet at two
 LDS-only barriers per step and each walks its own stream of prefetched items.  A wave that took one barrier more or less than the others would
 hang the workgroup on the device, and a product issued before its block's barrier would read an unfinished block -- both are properties of the
 scalar bookkeeping alone, so they are checked here, on the CPU, for every column length the kernel can meet (N <= 1152: J <= 71).
