@@ -327,6 +327,26 @@ int mcp_rollout_open_rec(const mcp_model* model, const mcp_noise* noise, int M, 
  * get_next_state and the integrators (model_learning/Model_learning.py:210-229, 471-494, 685-718). */
 int mcp_rollout_open_bwd(const mcp_model* model, int M, int T, const double* states, const int32_t* lengths, const double* jac,
                          const double* g_states, double* g_x0, double* g_u, void* stream);
+/* ONE time step of the model, for a closed loop whose policy the caller evaluates itself (any torch module): x [M][S], u [M][U] ->
+ * x_next [M][S] in one launch, one workgroup per (tile of particles, GP), no workspace.  Replaces one Model_learning.get_next_state
+ * (model_learning/Model_learning.py:210-229, 471-494, 685-718).  The arithmetic of a (particle, GP) is mcp_rollout_open's: a chain of
+ * steps t = 0, 1, ... fed the inputs of a rollout carries the bits of that rollout's states (and of its mu / var).
+ * noise->eps is THIS step's row [M][G]; NULL: Philox addressed as mcp_rollout_open addresses step t of a rollout (seed, call, call_dev,
+ * m + particle_offset), so particles [a, b) launched with particle_offset = a carry the bits of rows [a, b) of one launch.
+ * particle_pred bit 0 clear: the step is the posterior mean and reads no Kinv unless `var` is asked for.  mean / var (optional, [M][G]):
+ * what get_next_state returns, var_scale applied.  jac (optional, [M][G][D]): the record d delta_g / dz with the sampling folded in, one
+ * row of mcp_rollout_open_rec's, for mcp_model_step_bwd; x_next carries the same bits with and without it.  OUTPUTS NOT DIFFERENTIATED:
+ * the record describes x_next alone -- no gradient is provided through mean and var.  status: MCP_STATUS_NAN (x, u, a moment or x_next is
+ * not finite) | MCP_STATUS_NONPOS_VAR.  MCP_ERR_ARG: a NULL among model / noise / x / u / x_next / status, M <= 0, t < 0, a model
+ * model_ok refuses; MCP_ERR_LIMIT: a dimension beyond MCP_MAX_*.  A refused call makes no HIP call. */
+int mcp_model_step(const mcp_model* model, const mcp_noise* noise, int M, int t, int particle_pred, const double* x, const double* u,
+                   double* x_next, double* mean, double* var, double* jac, uint32_t* status, void* stream);
+/* The reverse of mcp_model_step: g_next [M][S] = dJ/dx_next -> g_x [M][S] = dJ/dx and g_u [M][U] = dJ/du (each may be NULL; both NULL:
+ * MCP_OK without a launch) from x and the record jac of the forward call.  Only the model's index maps and Ts are read (no GP array).  No
+ * atomics: bitwise reproducible, a particle's results do not depend on the others.  One row of mcp_rollout_open_bwd, the same order of
+ * operations. */
+int mcp_model_step_bwd(const mcp_model* model, int M, const double* x, const double* jac, const double* g_next, double* g_x, double* g_u,
+                       void* stream);
 /* Closed-loop rollout under the PD law, ONE launch: mcp_rollout_open's step with the input of step t computed from x_t inside the
  * kernel (mcp_pd_policy) instead of read from a buffer -- same phases, same noise addressing (eps [T-1][M][G] or Philox by seed, call,
  * m + particle_offset), same status flags; a NaN input raises MCP_STATUS_NAN.  states [T][M][S]; inputs [T][M][U], row T - 1 included

@@ -139,6 +139,8 @@ _SIGS = {
     "mcp_rollout_open_rec": (C.c_int, [C.POINTER(Model), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr, C.c_int, dptr, dptr, dptr, dptr,
                                        dptr, dptr, dptr]),
     "mcp_rollout_open_bwd": (C.c_int, [C.POINTER(Model), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
+    "mcp_model_step": (C.c_int, [C.POINTER(Model), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
+    "mcp_model_step_bwd": (C.c_int, [C.POINTER(Model), C.c_int, dptr, dptr, dptr, dptr, dptr, dptr]),
     "mcp_rollout_pd": (C.c_int, [C.POINTER(Model), C.POINTER(PDPolicy), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr,
                                  dptr, dptr, dptr]),
     "mcp_rollout_pd_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(PDPolicy), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr, dptr, dptr]),

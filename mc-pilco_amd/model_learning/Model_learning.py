@@ -283,6 +283,18 @@ class Model_learning(torch.nn.Module):
                                     particle_pred=particle_pred, moments=moments)
 
     # ---- one-step prediction ------------------------------------------------------------------------------------------
+    def fused_next_state(self, current_state, current_input, t=0, noise=None, particle_pred=True, status=None):
+        """``get_next_state`` as ONE launch (ops.model_step), and one more in backward: the tuple (next state [M,S], GP means [M,G], scaled
+        variances [M,G]), the next state differentiable in the state and the input (the moments are not differentiated), the model frozen.
+        ``t`` and ``noise`` (ops.NoiseSpec: this step's eps row [M,G], or Philox seed / call) say where the sample comes from -- nothing is
+        drawn from the torch generator; ``status``: an int32[1] the kernels OR their flags into.  Only for models whose step is the packed
+        one (``steps_like_the_packed_model``)."""
+        if not self.steps_like_the_packed_model():
+            raise NotImplementedError("this model has no fused layout, or overrides the step that layout describes: step it with get_next_state")
+        nxt, mean, var, _ = ops.model_step(self.packed(), current_state, current_input, t, noise=noise, particle_pred=particle_pred, moments=True,
+                                           status=status)
+        return nxt, mean, var
+
     def get_next_state(self, current_state, current_input, particle_pred=True):
         """x_{t+1} samples (or means) with the mean and variance of the GP outputs."""
         _, _, mean_list, var_list = self.get_one_step_gp_out(states=current_state, inputs=current_input)

@@ -586,6 +586,71 @@ def rollout_open_diff(model: PackedModel, x0, u, *, lengths=None, noise: Optiona
 
 
 # --------------------------------------------------------------------------------------
+# one fused model step (autograd): closed loops under a policy the fused rollouts do not know
+# --------------------------------------------------------------------------------------
+class ModelStepFunction(torch.autograd.Function):
+    """(x [M,S], u [M,U]) -> x_next [M,S], mean [M,G], var [M,G] in one launch (mcp_model_step); the recording launch when an input requires grad,
+    and then backward is the one launch of mcp_model_step_bwd over the record.  Gradients flow to x and u through x_next; the GP model is
+    frozen and ``mean`` / ``var`` are not differentiated."""
+
+    @staticmethod
+    def forward(ctx, x, u, model, t, noise, particle_pred, moments, status):
+        M, dev = int(x.shape[0]), model.device
+        rec = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        x_next = torch.empty(M, model.S, dtype=DT, device=dev)
+        mu = torch.empty(M, model.G, dtype=DT, device=dev) if moments else None
+        var = torch.empty(M, model.G, dtype=DT, device=dev) if moments else None
+        jac = torch.empty(M, model.G, model.D, dtype=DT, device=dev) if rec else None
+        nz = noise.to_c()
+        abi.check(abi.lib().mcp_model_step(_mc(model), C.byref(nz), M, int(t), int(bool(particle_pred)), abi.ptr(x), abi.ptr(u), abi.ptr(x_next),
+                                           abi.ptr(mu), abi.ptr(var), abi.ptr(jac), abi.ptr(status), abi.stream()), "mcp_model_step")
+        ctx.model = model
+        if rec:
+            ctx.save_for_backward(x, jac)
+        if not moments:
+            return x_next
+        ctx.mark_non_differentiable(mu, var)
+        return x_next, mu, var
+
+    @staticmethod
+    def backward(ctx, g_next, *_):
+        x, jac = ctx.saved_tensors
+        model, M = ctx.model, int(x.shape[0])
+        g_x = torch.empty(M, model.S, dtype=DT, device=x.device) if ctx.needs_input_grad[0] else None
+        g_u = torch.empty(M, model.U, dtype=DT, device=x.device) if ctx.needs_input_grad[1] else None
+        gn = g_next.to(dtype=DT).contiguous()
+        abi.check(abi.lib().mcp_model_step_bwd(_mc(model), M, abi.ptr(x), abi.ptr(jac), abi.ptr(gn), abi.ptr(g_x), abi.ptr(g_u), abi.stream()),
+                  "mcp_model_step_bwd")
+        return g_x, g_u, None, None, None, None, None, None
+
+
+def model_step(model: PackedModel, x, u, t, noise: Optional[NoiseSpec] = None, particle_pred=True, moments=False, status=None):
+    """One time step of the model in ONE launch: x [M,S], u [M,U] -> x_next [M,S], differentiable in x and u (the model is frozen), for a
+    closed loop whose policy is evaluated in torch between the steps.  ``t``: the step's index in its rollout.  ``noise``: a NoiseSpec whose
+    ``eps`` is THIS step's row [M,G], or Philox by seed / call / particle_offset and ``t`` -- a chain of steps carries the bits of
+    ``rollout_open`` fed the same inputs.  ``particle_pred`` False: the posterior mean.  ``moments``: also the GP means and scaled variances
+    [M,G] (what get_next_state returns; not differentiated).  ``status``: an int32[1] the kernels OR their flags into.
+    Returns (x_next, status) or (x_next, mean, var, status)."""
+    for name, a in (("x", x), ("u", u)):
+        if not isinstance(a, torch.Tensor) or not a.is_cuda:
+            raise RuntimeError("model_step operates on GPU memory only (%s is not a GPU tensor); there is no CPU path" % name)
+    dev = model.device
+    x, u = x.to(device=dev, dtype=DT).contiguous(), u.to(device=dev, dtype=DT).contiguous()
+    if x.dim() != 2 or x.shape[1] != model.S or u.dim() != 2 or tuple(u.shape) != (x.shape[0], model.U) or x.shape[0] < 1:
+        raise RuntimeError("model_step takes x [M,%d] and u [M,%d]" % (model.S, model.U))
+    if int(t) < 0:
+        raise RuntimeError("model_step: the step index must not be negative")
+    noise = NoiseSpec() if noise is None else noise
+    if particle_pred and noise.eps is not None:
+        e = noise.eps
+        if e.dtype != DT or not e.is_cuda or not e.is_contiguous() or tuple(e.shape) != (x.shape[0], model.G):
+            raise RuntimeError("eps must be this step's row: a contiguous float64 GPU tensor of shape [M,G]")
+    status = _status_word(status, dev, "the model's device")
+    out = ModelStepFunction.apply(x, u, model, t, noise, bool(particle_pred), bool(moments), status)
+    return (out[0], out[1], out[2], status) if moments else (out, status)
+
+
+# --------------------------------------------------------------------------------------
 # fused closed loop under the PD law (autograd)
 # --------------------------------------------------------------------------------------
 class PackedPD:

@@ -93,6 +93,8 @@ class MC_PILCO(torch.nn.Module):
         self.last_open_loop_fused = False  # what the last rollout() ran
         self.fused_feedback = True        # apply_policy with a PD_controller as one fused launch (False: the step loop on get_next_state)
         self.last_feedback_fused = False  # what the last apply_policy() ran for such a policy
+        self.fused_step = False           # the generic loop of apply_policy steps the model with ONE launch per step (see _step_fused); False: get_next_state
+        self.last_step_fused = False      # what the last apply_policy() ran in its generic loop
         self.dist_group = None
         self.last_status = None
         self.gp_sharding = True    # cleared for good once a GP-sharded launch reports MCP_STATUS_SYNC (co-residency was not there)
@@ -199,6 +201,7 @@ class MC_PILCO(torch.nn.Module):
                                        particles_init_low_bound, flg_particles_init_multi_gauss, num_particles, T_control)
         pol, ml = self.control_policy, self.model_learning
         self.last_feedback_fused = False  # (reset before every branch: a run under another policy must not leave an earlier True standing)
+        self.last_step_fused = False
         if isinstance(pol, _Policy.Sum_of_gaussians) and _has_fused_layout(ml):
             noise, _, p = self._rollout_noise(T, p_dropout)
             return self._fused(*ops.rollout(ml.packed(), pol.packed(), noise, x0, T, p, gp_sharding=self.gp_sharding))
@@ -214,13 +217,36 @@ class MC_PILCO(torch.nn.Module):
             # would simulate correlated shards, not the particles one GPU would
             raise NotImplementedError("particle sharding needs the fused rollout (Sum_of_gaussians or PD_controller policy + a model with a "
                                       "fused layout)")
+        step = self._step_fused(T)
         xs = [x0]
         us = [pol(x0, t=0, p_dropout=p_dropout)]
         for t in range(1, T):
-            x, _, _ = ml.get_next_state(current_state=xs[-1], current_input=us[-1])
+            x, _, _ = step(xs[-1], us[-1], t - 1) if step else ml.get_next_state(current_state=xs[-1], current_input=us[-1])
             xs.append(x)
             us.append(pol(x, t=t, p_dropout=p_dropout))
         return torch.stack(xs), torch.stack(us)
+
+    def _step_fused(self, T, n_pos=0):
+        """The generic loop's model step as one launch per time step (Model_learning.fused_next_state) when ``fused_step`` is on and the
+        model's step is the one its fused layout describes, else None: the loop then calls get_next_state as ever.  The policy is called
+        exactly as in the unfused loop.  The noise is the fused rollouts': ``_rollout_noise`` -- Philox by (seed, call, t, particle), or in
+        "reference" mode row t of the eps buffer of ``reference_draws`` -- and nothing is drawn from the torch generator for the model.  The
+        steps OR their flags into one word, ``last_status``.  Returns step(x, u, t) -> get_next_state's tuple; ``step.pos_noise``: the
+        position noise [T-1,M,n_pos] drawn with the eps ("reference" mode with ``n_pos``), else None."""
+        f = getattr(self.model_learning, "steps_like_the_packed_model", None)
+        if not (self.fused_step and callable(f) and f() and T > 1):
+            return None
+        noise, pos_noise, _ = self._rollout_noise(T, n_pos=n_pos)
+        status = self.last_status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.last_step_fused = True
+        ml, eps = self.model_learning, noise.eps
+
+        def step(x, u, t):
+            nz = noise if eps is None else ops.NoiseSpec(eps=eps[t])
+            return ml.fused_next_state(current_state=x, current_input=u, t=t, noise=nz, status=status)
+
+        step.pos_noise = pos_noise
+        return step
 
     def _step_flags(self, cost):
         """Device vector [cost is NaN, a GP-sharded launch timed out (MCP_STATUS_SYNC), a predictive variance was <= 0
@@ -773,6 +799,7 @@ class MC_PILCO4PMS(MC_PILCO):
         b, a = signal.butter(1, self.filtering_dict["fc"])
         pos, vel = list(self.pos_indeces), list(self.vel_indeces)
         self.last_feedback_fused = False  # (reset before every branch, as in MC_PILCO.apply_policy)
+        self.last_step_fused = False
         if self.fused and isinstance(pol, _Policy.Sum_of_gaussians) and _has_fused_layout(ml):
             # one fused launch: the kernels carry the measurement filter's states per particle (mcp_meas); the reference's draw order is
             # mask_0; per step: eps_t, position noise, mask_t
@@ -791,6 +818,7 @@ class MC_PILCO4PMS(MC_PILCO):
             raise NotImplementedError("particle sharding needs the fused rollout (fused=True, Sum_of_gaussians or PD_controller policy, a model "
                                       "with a fused layout)")
         std_pos = torch.tensor(np.asarray(self.std_meas_noise_sim)[pos], dtype=self.dtype, device=self.device)
+        step = self._step_fused(T, n_pos=len(pos))
         saved_mode = getattr(pol, "noise_mode", None)
         if ref and saved_mode is not None:
             pol.noise_mode = "torch_cpu"
@@ -799,16 +827,21 @@ class MC_PILCO4PMS(MC_PILCO):
             noisy_prev, meas_prev = x, x
             us = [pol(x, t=0, p_dropout=p_dropout)]
             for t in range(1, T):
-                _, _, mean_list, var_list = ml.get_one_step_gp_out(states=xs[-1], inputs=us[-1])
-                var_list = [v * ml.norm_list[i] ** 2 for i, v in enumerate(var_list)]
-                mean, var = torch.cat(mean_list, 1), torch.cat(var_list, 1)
-                eps = torch.empty(M, ml.num_gp, dtype=self.dtype, device=ndev).normal_().to(self.device)
-                delta = mean + torch.sqrt(var) * eps
-                x, _, _ = ml.get_next_state_from_gp_output(current_state=xs[-1], current_input=us[-1],
-                                                           gp_output_mean_list=[delta[:, g:g + 1] for g in range(ml.num_gp)],
-                                                           gp_output_var_list=var_list, particle_pred=False)
-                xs.append(x)
-                n = torch.randn(M, len(pos), dtype=self.dtype, device=ndev).to(self.device)
+                if step:  # one launch; its eps (and in "reference" mode the position noise below) are _rollout_noise's, in the reference's order
+                    x, _, _ = step(xs[-1], us[-1], t - 1)
+                    xs.append(x)
+                    n = step.pos_noise[t - 1] if step.pos_noise is not None else torch.randn(M, len(pos), dtype=self.dtype, device=self.device)
+                else:
+                    _, _, mean_list, var_list = ml.get_one_step_gp_out(states=xs[-1], inputs=us[-1])
+                    var_list = [v * ml.norm_list[i] ** 2 for i, v in enumerate(var_list)]
+                    mean, var = torch.cat(mean_list, 1), torch.cat(var_list, 1)
+                    eps = torch.empty(M, ml.num_gp, dtype=self.dtype, device=ndev).normal_().to(self.device)
+                    delta = mean + torch.sqrt(var) * eps
+                    x, _, _ = ml.get_next_state_from_gp_output(current_state=xs[-1], current_input=us[-1],
+                                                               gp_output_mean_list=[delta[:, g:g + 1] for g in range(ml.num_gp)],
+                                                               gp_output_var_list=var_list, particle_pred=False)
+                    xs.append(x)
+                    n = torch.randn(M, len(pos), dtype=self.dtype, device=ndev).to(self.device)
                 noisy = x.clone()
                 noisy[:, pos] = noisy[:, pos] + std_pos * n
                 noisy[:, vel] = (noisy[:, pos] - noisy_prev[:, pos]) / self.T_sampling
