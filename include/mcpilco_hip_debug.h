@@ -90,6 +90,23 @@ int mcp_rollout_fwd_plan(const mcp_model* model, const mcp_policy* policy, int M
 int mcp_rollout_bwd_plan(const mcp_model* model, const mcp_policy* policy, int M, int T, int particle_pred, size_t workspace_bytes, int cus,
                          const mcp_dispatch* request, mcp_bwd_plan* plan);
 
+/*
+ * The training epoch's plan: where mcp_nll_epoch keeps what it makes inside its workspace and which gradient form it launches for
+ * (G, N, D).  Returns what mcp_nll_epoch returns from validating the three sizes; no HIP call.  All fields int64.  Offsets in doubles:
+ * `first_gp` from the start of the workspace (the G mcp_kernel descriptors come first), GP g's block at first_gp + g per_gp, the others
+ * inside a GP's block, in the order K -> U | Uinv | Kinv | alpha | r | slab | grad | inv_ls | w1 | w20 | w21 | scal | logdet.
+ */
+enum { MCP_NLL_GRAD_ROWS = 1, MCP_NLL_GRAD_ROW_PER_WG = 2 };
+typedef struct mcp_nll_plan {
+  int64_t first_gp, per_gp, total; /* total: the whole workspace = mcp_nll_epoch_workspace_bytes / 8 */
+  int64_t K, Uinv, Kinv, alpha, r, slab, grad, inv_ls, w1, w20, w21, scal, logdet;
+  int64_t grad_form;   /* MCP_NLL_GRAD_ROWS: inputs in LDS, rows_per_wg rows per workgroup; MCP_NLL_GRAD_ROW_PER_WG: one workgroup per row of K */
+  int64_t rows_per_wg; /* rows of K per workgroup of the gradient launch */
+  int64_t slab_rows;   /* rows of the slab the finish kernel adds: workgroups of the gradient launch per GP */
+  int64_t lds_bytes;   /* dynamic LDS of the gradient launch */
+} mcp_nll_plan;
+int mcp_nll_epoch_plan(int G, int N, int D, mcp_nll_plan* plan);
+
 #ifdef __cplusplus
 }
 #endif

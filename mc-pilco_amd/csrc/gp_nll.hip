@@ -1,10 +1,12 @@
 // Marginal-likelihood gradient and the batched training epoch for gfx950 (mcp_nll_workspace_bytes, mcp_nll_grad,
-// mcp_nll_epoch_workspace_bytes, mcp_nll_epoch).  Replaces the objective of GP_prior.fit_model and its autograd pass in the reference
+// mcp_nll_epoch_workspace_bytes, mcp_nll_epoch, and the epoch's plan query mcp_nll_epoch_plan).  Replaces the objective of
+// GP_prior.fit_model and its autograd pass in the reference
 // (gpr_lib/GP_prior/GP_prior.py:91-115,179-230; Gaussian_likelihood.py:15-24; Model_learning.train_gp_likelihood,
 // model_learning/Model_learning.py:398-421): once per EPOCH of the hyper-parameter training.  The epoch factorises and inverts its G Gram
 // matrices with gp_linalg.hip's one-workgroup launchers in their batched form (gp_launch.h).
 #include <type_traits>
 
+#include "../../include/mcpilco_hip_debug.h"
 #include "gp_launch.h"
 #include "mcp_device.h"
 
@@ -577,12 +579,58 @@ extern "C" size_t mcp_nll_epoch_workspace_bytes(int G, int N, int D) {
   return sizeof(double) * nll_ws_layout(G, N, D).total;
 }
 
+// The epoch's plan for (G, N, D), on the host: the workspace map and the gradient form.  mcp_nll_epoch runs what this returns and
+// mcp_nll_epoch_plan (include/mcpilco_hip_debug.h) reports it, so the plan returned is the plan run.
+static int nll_epoch_plan(int G, int N, int D, NllWs* L, mcp_nll_plan* pl) {
+  if (G <= 0 || N <= 0 || D <= 0) return MCP_ERR_ARG;
+  if (G > MCP_MAX_GP || D > MCP_MAX_GPDIM || N > 1152 || N <= 16) return MCP_ERR_LIMIT;  // (the MFMA-blocked factorisations: 16 < N, row panel in LDS)
+  *L = nll_ws_layout(G, N, D);
+  pl->first_gp = (int64_t)(L->total - (size_t)G * L->per_gp);
+  pl->per_gp = (int64_t)L->per_gp;
+  pl->total = (int64_t)L->total;
+  pl->K = (int64_t)L->K;
+  pl->Uinv = (int64_t)L->Ui;
+  pl->Kinv = (int64_t)L->Kinv;
+  pl->alpha = (int64_t)L->alpha;
+  pl->r = (int64_t)L->r;
+  pl->slab = (int64_t)L->slab;
+  pl->grad = (int64_t)L->grad;
+  pl->inv_ls = (int64_t)L->invls;
+  pl->w1 = (int64_t)L->w1;
+  pl->w20 = (int64_t)L->w20;
+  pl->w21 = (int64_t)L->w21;
+  pl->scal = (int64_t)L->scal;
+  pl->logdet = (int64_t)L->logdet;
+  if (nll_grad_rows_lds(N, D) <= 150 * 1024) {
+    pl->grad_form = MCP_NLL_GRAD_ROWS;
+    pl->rows_per_wg = nll_grad_rows_per_wg(N);
+    pl->slab_rows = (N + pl->rows_per_wg - 1) / pl->rows_per_wg;
+    pl->lds_bytes = (int64_t)nll_grad_rows_lds(N, D);
+  } else {
+    pl->grad_form = MCP_NLL_GRAD_ROW_PER_WG;
+    pl->rows_per_wg = 1;
+    pl->slab_rows = N;
+    pl->lds_bytes = (int64_t)(sizeof(double) * (4 * (size_t)N + 256));
+  }
+  return MCP_OK;
+}
+
+extern "C" int mcp_nll_epoch_plan(int G, int N, int D, mcp_nll_plan* plan) {
+  if (!plan) return MCP_ERR_ARG;
+  NllWs L;
+  return nll_epoch_plan(G, N, D, &L, plan);
+}
+
 extern "C" int mcp_nll_epoch(int G, const mcp_nll_gp* gps, int N, int D, int poly_deg, int ard, const double* X, uint32_t* status,
                              void* workspace, size_t workspace_bytes, void* stream) {
-  if (!gps || !X || !status || !workspace || G <= 0 || N <= 0 || D <= 0) return MCP_ERR_ARG;
-  if (G > MCP_MAX_GP || D > MCP_MAX_GPDIM || N > 1152 || N <= 16) return MCP_ERR_LIMIT;  // (the MFMA-blocked factorisations: 16 < N, row panel in LDS)
+  if (!gps || !X || !status || !workspace) return MCP_ERR_ARG;
+  NllWs L;
+  mcp_nll_plan pl;
+  {
+    const int rc = nll_epoch_plan(G, N, D, &L, &pl);
+    if (rc != MCP_OK) return rc;
+  }
   if (poly_deg < 0 || poly_deg > 2) return MCP_ERR_ARG;
-  const NllWs L = nll_ws_layout(G, N, D);
   if (workspace_bytes < sizeof(double) * L.total) return MCP_ERR_WORKSPACE;
   NllBatch b;
   for (int g = 0; g < MCP_MAX_GP; ++g) b.gp[g] = gps[g < G ? g : 0];
@@ -619,20 +667,19 @@ extern "C" int mcp_nll_epoch(int G, const mcp_nll_gp* gps, int N, int D, int pol
   }
   hipLaunchKernelGGL(nll_alpha_batch_kernel, dim3((N + 3) / 4, G), dim3(256), 0, st, b, G, N, ws, L);
   MCP_LAUNCH_CHECK();
-  int slab_rows = N;
-  if (nll_grad_rows_lds(N, D) <= 150 * 1024) {
-    const int rows = nll_grad_rows_per_wg(N);
-    slab_rows = (N + rows - 1) / rows;
+  const int slab_rows = (int)pl.slab_rows;
+  if (pl.grad_form == MCP_NLL_GRAD_ROWS) {
+    const int rows = (int)pl.rows_per_wg;
     const int rc = with_degree(poly_deg, [&](auto deg_c) -> int {
       constexpr int DEG = decltype(deg_c)::value;
       MCP_ENSURE_MAX_LDS(nll_grad_rows_kernel<DEG>);
-      hipLaunchKernelGGL(nll_grad_rows_kernel<DEG>, dim3(slab_rows, G), dim3(NG_NT), nll_grad_rows_lds(N, D), st, kns, N, X, ws, G, L, rows);
+      hipLaunchKernelGGL(nll_grad_rows_kernel<DEG>, dim3(slab_rows, G), dim3(NG_NT), (size_t)pl.lds_bytes, st, kns, N, X, ws, G, L, rows);
       return MCP_OK;
     });
     if (rc != MCP_OK) return rc;
   } else {
     MCP_ENSURE_MAX_LDS(nll_grad_batch_kernel);
-    hipLaunchKernelGGL(nll_grad_batch_kernel, dim3(N, G), dim3(256), sizeof(double) * (4 * (size_t)N + 256), st, kns, N, X, ws, G, L);
+    hipLaunchKernelGGL(nll_grad_batch_kernel, dim3(slab_rows, G), dim3(256), (size_t)pl.lds_bytes, st, kns, N, X, ws, G, L);
   }
   MCP_LAUNCH_CHECK();
   hipLaunchKernelGGL(nll_finish_kernel, dim3(G), dim3(256), 0, st, b, G, N, D, poly_deg, ard, ws, L, slab_rows);

@@ -107,6 +107,13 @@ class BwdPlan(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("lean", "pfm", "um", "maxnt", "particles", "threads", "pipe", "launches", "slabs", "ran_bwd_lean", "ran_bwd_pipe")]
 
 
+class NllPlan(C.Structure):
+    """include/mcpilco_hip_debug.h: struct mcp_nll_plan -- what mcp_nll_epoch_plan answers (workspace map in doubles, gradient form)."""
+    _fields_ = [(k, C.c_int64) for k in ("first_gp", "per_gp", "total", "K", "Uinv", "Kinv", "alpha", "r", "slab", "grad", "inv_ls", "w1", "w20", "w21",
+                                         "scal", "logdet", "grad_form", "rows_per_wg", "slab_rows", "lds_bytes")]
+
+
+NLL_GRAD_ROWS, NLL_GRAD_ROW_PER_WG = 1, 2  # mcp_nll_plan.grad_form
 FWD_SMALL_SHARDED, FWD_LEAN, FWD_TILE_SHARDED, FWD_TILE, FWD_SMALL = 1, 2, 3, 4, 5  # mcp_fwd_plan.family
 
 # The dispatch request of THIS PROCESS's calls through `ops` (all zero: automatic).  It lives here, in the host layer -- the library keeps no
@@ -167,6 +174,7 @@ _SIGS = {
                                         C.c_double, C.c_double, C.c_double, dptr, C.c_int64, C.c_int, dptr, dptr, dptr, dptr]),
     "mcp_nll_epoch_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "mcp_nll_epoch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, dptr, dptr, dptr, C.c_size_t, dptr]),
+    "mcp_nll_epoch_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(NllPlan)]),
     "mcp_policy_step_commit": (C.c_int, [dptr, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr, dptr, dptr, C.c_double, C.c_double, C.c_double, C.c_int,
                                          dptr, dptr]),
     "mcp_comm_unique_id": (C.c_int, [C.c_char_p]),
@@ -175,7 +183,7 @@ _SIGS = {
     "mcp_allreduce_grad": (C.c_int, [dptr, C.c_size_t, dptr]),
     "mcp_comm_destroy": (C.c_int, []),
 }
-PLAN_QUERIES = ("mcp_rollout_fwd_plan", "mcp_rollout_bwd_plan")
+PLAN_QUERIES = ("mcp_rollout_fwd_plan", "mcp_rollout_bwd_plan", "mcp_nll_epoch_plan")
 EXPORTED_DEBUG = [k for k in _SIGS if k.endswith("_ex") or k in PLAN_QUERIES]  # include/mcpilco_hip_debug.h
 EXPORTED = [k for k in _SIGS if k not in EXPORTED_DEBUG]                       # include/mcpilco_hip.h
 

@@ -1,4 +1,5 @@
-"""Extended-precision reference of the GP operators (helper of tests/test_gp_truth_cpu.py and tests/test_gpu_gp_operators.py; no tests here).
+"""Extended-precision reference of the GP operators (helper of tests/test_gp_truth_cpu.py, tests/test_gpu_gp_operators.py and
+tests/test_gpu_nll_grad.py; no tests here).
 
 The truth is the exact value of the library's OWN formula (header comment of ``mcp_kernel``, include/mcpilco_hip.h) on the float64
 operands exactly as the kernel receives them -- X, alpha, the symmetrised Kinv, 1/l, lambda, mean, w1, w20, w21, Z --, evaluated in
@@ -10,6 +11,8 @@ good Kinv is as an inverse.
   Jmu_d  = sum_j alpha_j dk_j/dz_d                                     S = sum_j |alpha_j dk_j/dz_d|
   Jvar_d = dk(z,z)/dz_d - 2 sum_ij dk_i/dz_d Kinv_ij k_j               S = |dk(z,z)/dz_d| + 2 sum_ij |dk_i/dz_d Kinv_ij k_j|
   A G A                                                                S = |A| |G| |A|  (entrywise)
+  g_p    = 1/2 sum_ij (W_ij - alpha_i alpha_j) dK_ij/dtheta_p          S = 1/2 sum_ij (|W_ij| + |alpha_i alpha_j|) |dK_ij/dtheta_p|
+           (the marginal-likelihood gradient operator, mcp_nll_grad's 4D + 3 log-parameters; W = Kinv, or any matrix)
 
 Errors are reported as r = |got - truth| / (2^-53 S): the a-priori form of a float64 sum's rounding error (Higham, Accuracy and
 Stability of Numerical Algorithms, 2nd ed., section 4.2), independent of the order of summation and finite where mu cancels.
@@ -18,7 +21,8 @@ The bounds C (below) are NOT chosen from what the kernels give: C = 16 x r_orc r
 worst r of the float64 CPU oracle (oracle/mcpilco_oracle.py, torch autograd for the Jacobians) against this truth over every case
 of ``POSTERIOR_CASES`` -- the reference's own noise floor, measured by tests/test_gp_truth_cpu.py.  The factor 16 covers what differs
 between two correct float64 evaluations: the kernels add the N terms in another tree, contract with fma, use their own exp and the
-centred distance form (the oracle expands the square).
+centred distance form (the oracle expands the square).  For the gradient operator the floor is ``nll_grad_float64``, a float64 torch
+evaluation of the same formula on the same operands, over ``ALL_GRAD_CASES``.
 """
 import functools
 import math
@@ -31,7 +35,7 @@ U53 = 2.0 ** -53
 # ----------------------------------------------------------------------------------------------------------------------------------
 # recorded floor of the float64 oracle (worst r over all cases; tests/test_gp_truth_cpu.py re-measures and prints it) and the bounds
 # ----------------------------------------------------------------------------------------------------------------------------------
-R_ORC = {"mu": 1.889, "var": 1.145, "Jmu": 1.899, "Jvar": 1.799, "sandwich": 8.986}
+R_ORC = {"mu": 1.889, "var": 1.145, "Jmu": 1.899, "Jvar": 1.799, "sandwich": 8.986, "nll_grad": 2.445}
 
 
 def pow2_ceil(x):
@@ -296,3 +300,179 @@ def nll_truth(X, Y, log_ls, log_lambda, log_sigma_n, mean=0.0, sigma_n_num=0.0, 
     g_sn = np.trace(W) * 2 * sn * sn
     g_mean = -a.sum()
     return loss, g_ls, g_lam, g_sn, g_mean
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# the marginal-likelihood gradient operator (mcp_nll_grad and the gradient stage of mcp_nll_epoch), at operand level
+# ----------------------------------------------------------------------------------------------------------------------------------
+# (N, D, degree).  mcp_nll_grad directly: N below the segment count of nll_grad_row (256 / NPpad segments of NPpad >= 4D + 3 lanes), every
+# NPpad boundary (32 | 64 at D = 7 | 8, 64 | 128 at 15 | 16, 128 | 256 at 31 | 32) at N = 257, the 256-stride of stage 1 and the tails of
+# nll_colsum_kernel's four-way unroll (N mod 4 = 3, 0, 2, 3, 1), and the limit N = 4096 (133 KB of LDS)
+GRAD_SMALL_CASES = [(1, 1, 0), (3, 2, 2), (7, 7, 2)]
+GRAD_NPPAD_CASES = [(257, D, 2) for D in (7, 8, 15, 16, 31, 32)]
+GRAD_STRIDE_CASES = [(255, 6, 0), (256, 6, 1), (258, 6, 2), (259, 6, 1), (1153, 6, 2)]
+GRAD_LIMIT_CASE = (4096, 2, 1)
+GRAD_VARIANT_CASE = (65, 8, 2)  # ldk > N, kern->scal, non-symmetric W with alpha = 0
+GRAD_CASES = GRAD_SMALL_CASES + GRAD_NPPAD_CASES + GRAD_STRIDE_CASES + [GRAD_LIMIT_CASE, GRAD_VARIANT_CASE]
+# mcp_nll_epoch, the LDS-rows form: nll_grad_rows_per_wg = 2 at N = 129; (257, 8): 3 rows per workgroup, the last one has 2; (1025, 6): a
+# second pass of one thread over j; the last shapes before the form flips at D = 24 and at N = 1152
+EPOCH_ROWS_CASES = [(129, 6, 0), (129, 6, 1), (129, 6, 2), (257, 8, 2), (1025, 6, 2), (681, 24, 1), (1152, 12, 2)]
+# ... the row-per-workgroup form (nll_grad_batch_kernel): (N, D, degree, ard)
+EPOCH_FALLBACK_CASES = [(530, 32, 2, True), (682, 24, 1, True), (682, 24, 0, False), (1152, 13, 0, True), (1152, 15, 2, True)]
+EPOCH_BATCH_CASE = (530, 32, 1)  # G = 3, each GP with its own hyper-parameters and targets
+ALL_GRAD_CASES = sorted(set(GRAD_CASES + EPOCH_ROWS_CASES + [c[:3] for c in EPOCH_FALLBACK_CASES] + [EPOCH_BATCH_CASE]))
+
+
+def nll_grad_live(N, D, deg):
+    """Which of the 4D + 3 entries have a term that is not identically zero: the slots of the degree, and the lengthscale entries from
+    N = 2 on (dK_ii/d log l = 0: at N = 1 their only term vanishes, truth and S are exactly 0).  Every other entry must be exactly 0.0."""
+    live = np.zeros(4 * D + 3, dtype=bool)
+    live[:D] = N > 1
+    live[D:D + 2] = True
+    if deg >= 1:
+        live[D + 2:2 * D + 3] = True
+    if deg >= 2:
+        live[2 * D + 3:] = True
+    return live
+
+
+def _row_block(N, D):
+    return max(1, min(N, (1 << 20) // max(1, N * D)))
+
+
+def nll_grad_truth(X, W, alpha, inv_ls, lam, w1, w20, w21, deg, be=None):
+    """g_p = 1/2 sum_ij (W_ij - alpha_i alpha_j) dK_ij/dtheta_p for the 4D + 3 log-parameters of mcp_nll_grad (layout: its comment in
+    include/mcpilco_hip.h; p = D + 1 is 1/2 tr(W - alpha alpha^T)), and S_p = 1/2 sum_ij (|W_ij| + |alpha_i alpha_j|) |dK_ij/dtheta_p|, from the
+    float64 operands as the kernel receives them (W [N,N] general, NOT assumed symmetric).  Row blocks of W: nothing larger than about
+    2^20 extended numbers lives at a time.  Every sum over j is a pairwise one along the contiguous axis and the rows are added the same
+    way, so the truth's own error stays at a few 2^-64 S whatever N is (a running sum over N^2 = 2^24 terms would not)."""
+    be = backend() if be is None else be
+    up = be.up
+    X, W, alpha, u = up(_np(X)), up(_np(W)), up(_np(alpha)).reshape(-1), up(_np(inv_ls)).reshape(-1)
+    N, D = X.shape
+    NP = 4 * D + 3
+    lam, deg = up(float(lam)), int(deg)
+    XT = np.ascontiguousarray(X.T)  # [D,N]
+    u2 = (u * u)[None, :, None]
+    if deg >= 1:
+        w1 = up(_np(w1)).reshape(-1)
+    if deg >= 2:
+        w20, w21 = up(_np(w20)).reshape(-1), up(_np(w21)).reshape(-1)
+    rows_g, rows_S = be.zeros((NP, N)), be.zeros((NP, N))  # [p][i]: the sums over j of row i
+    b = _row_block(N, D)
+    for i0 in range(0, N, b):
+        I = slice(i0, min(N, i0 + b))
+        Xi = X[I]  # [b,D]
+        diff = Xi[:, :, None] - XT[None, :, :]  # [b,D,N]
+        sq = diff * diff * u2  # ((x_ip - x_jp) / l_p)^2
+        su = diff * u[None, :, None]
+        kse = lam * be.exp(-(su * su).sum(1))  # [b,N]
+        aa = alpha[I][:, None] * alpha[None, :]
+        Wm, aWm = W[I] - aa, abs(W[I]) + abs(aa)
+
+        def put(p, dK):  # dK [b,N] or [b,n,N] -> entries p, p + 1, ...
+            dK = dK if dK.ndim == 3 else dK[:, None, :]
+            n = dK.shape[1]
+            rows_g[p:p + n, I] = (Wm[:, None, :] * dK).sum(2).T
+            rows_S[p:p + n, I] = (aWm[:, None, :] * abs(dK)).sum(2).T
+
+        put(0, 2 * sq * kse[:, None, :])
+        put(D, kse)
+        ii = np.arange(I.start, I.stop)
+        rows_g[D + 1, I], rows_S[D + 1, I] = Wm[ii - i0, ii], aWm[ii - i0, ii]
+        if deg >= 1:
+            xx = Xi[:, :, None] * XT[None, :, :]  # [b,D,N]
+            put(D + 2, 2 * w1[None, :D, None] * xx)
+            put(2 * D + 2, 2 * w1[D] + 0 * kse)
+        if deg >= 2:
+            A, B = (xx * w20[None, :, None]).sum(1), (xx * w21[None, :, None]).sum(1)  # [b,N]
+            put(2 * D + 3, 2 * w20[None, :, None] * xx * B[:, None, :])
+            put(3 * D + 3, 2 * w21[None, :, None] * xx * A[:, None, :])
+    return rows_g.sum(1) / 2, rows_S.sum(1) / 2
+
+
+def nll_grad_float64(X, W, alpha, inv_ls, lam, w1, w20, w21, deg):
+    """The same formula in float64 torch on one thread, vectorised the obvious way (row blocks, torch's own sums): a correct float64
+    evaluation that shares nothing with the kernels.  Its worst r against nll_grad_truth is the floor R_ORC["nll_grad"]."""
+    T = lambda a: torch.as_tensor(_np(a))
+    X, W, alpha, u = T(X), T(W), T(alpha).reshape(-1), T(inv_ls).reshape(-1)
+    N, D = X.shape
+    lam, deg = float(lam), int(deg)
+    g = torch.zeros(4 * D + 3, dtype=torch.float64)
+    n = torch.get_num_threads()
+    torch.set_num_threads(1)  # (the floor is a recorded number: one summation order)
+    try:
+        b = _row_block(N, D)
+        for i0 in range(0, N, b):
+            Xi = X[i0:i0 + b]
+            diff = Xi[:, None, :] - X[None, :, :]  # [b,N,D]
+            sq = (diff * u) ** 2
+            kse = lam * torch.exp(-sq.sum(2))
+            Wm = W[i0:i0 + b] - alpha[i0:i0 + b, None] * alpha[None, :]
+            Wk = Wm * kse
+            g[:D] += (Wk[:, :, None] * (2.0 * sq)).sum((0, 1))
+            g[D] += Wk.sum()
+            g[D + 1] += torch.diagonal(Wm, offset=i0).sum()
+            if deg >= 1:
+                w1t = T(w1).reshape(-1)
+                xx = Xi[:, None, :] * X[None, :, :]
+                g[D + 2:2 * D + 2] += (Wm[:, :, None] * (2.0 * w1t[:D] * xx)).sum((0, 1))
+                g[2 * D + 2] += (Wm * (2.0 * w1t[D])).sum()
+            if deg >= 2:
+                w20t, w21t = T(w20).reshape(-1), T(w21).reshape(-1)
+                A, B = (xx * w20t).sum(2), (xx * w21t).sum(2)
+                g[2 * D + 3:3 * D + 3] += ((Wm * B)[:, :, None] * (2.0 * w20t * xx)).sum((0, 1))
+                g[3 * D + 3:] += ((Wm * A)[:, :, None] * (2.0 * w21t * xx)).sum((0, 1))
+    finally:
+        torch.set_num_threads(n)
+    return 0.5 * g
+
+
+def nll_kernel_operands(D, deg, ls, pw, lam=1.3):
+    """float64 kernel operands of the model (lengthscales ls, lambda, raw polynomial weights pw): 1 / l, lambda and the MPK weights
+    ((k - d) exp(log pw))^2 as the library's host layer forms them."""
+    op = dict(D=D, deg=deg, lam=float(lam), inv_ls=1.0 / np.asarray(ls, dtype=np.float64), w1=None, w20=None, w21=None)
+    if deg >= 1:
+        op["w1"] = np.exp(np.log(pw[0])) ** 2
+    if deg >= 2:
+        lp = np.log(pw[1])
+        op["w20"], op["w21"] = (2.0 * np.exp(lp[:D])) ** 2, np.exp(lp[D:]) ** 2
+    return op
+
+
+@functools.lru_cache(maxsize=None)
+def nll_grad_case(N, D, deg, seed=0):
+    """Seeded operands of one case: nll_data's inputs, targets and lengthscales, nll_poly_weights' polynomial weights, lambda 1.3,
+    sigma_n 0.1; Kinv = numpy's inverse of the case's own K, symmetrised; alpha = Kinv Y.  Everything float64 numpy, made once."""
+    X, Y, ls = nll_data(N, D, seed)
+    op = nll_kernel_operands(D, deg, ls, nll_poly_weights(D, deg, seed))
+    K = np.empty((N, N))
+    b = _row_block(N, D)
+    for i0 in range(0, N, b):  # (row blocks: no N x N x D array at N = 4096)
+        su = (X[i0:i0 + b, None, :] - X[None, :, :]) * op["inv_ls"]
+        K[i0:i0 + b] = op["lam"] * np.exp(-(su * su).sum(2))
+    if deg >= 1:
+        K += (X * op["w1"][:-1]) @ X.T + op["w1"][-1]
+    if deg >= 2:
+        K += ((X * op["w20"]) @ X.T) * ((X * op["w21"]) @ X.T)
+    K += 0.1 ** 2 * np.eye(N)
+    Kinv = np.linalg.inv(K)
+    Kinv = np.ascontiguousarray((Kinv + Kinv.T) / 2)
+    op.update(N=N, X=X, Y=Y, ls=ls, W=Kinv, alpha=(Kinv @ Y).reshape(-1))
+    return op
+
+
+def nll_grad_args(op):
+    return (op["X"], op["W"], op["alpha"], op["inv_ls"], op["lam"], op["w1"], op["w20"], op["w21"], op["deg"])
+
+
+@functools.lru_cache(maxsize=None)
+def nll_grad_case_truth(case):
+    return nll_grad_truth(*nll_grad_args(nll_grad_case(*case)))
+
+
+def r_entries(got, truth, S, live, be=None):
+    """r = |got - truth| / (2^-53 S) of the live entries (float64 array)."""
+    be = backend() if be is None else be
+    g = be.up(_np(got)).reshape(np.shape(truth))
+    return be.down(abs(g - truth)[live] / (be.up(U53) * S[live]))

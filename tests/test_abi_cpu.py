@@ -32,10 +32,10 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, n), "libmcpilco_hip.so does not export %s" % n
     assert set(hipabi.EXPORTED) == set(names)
     # the test / diagnostic entry points live in their own header, outside the boundary, and the binding knows exactly those: each is its plain
-    # namesake plus a per-call mcp_dispatch (round 5: the library exports no setter and keeps no dispatch state), or one of the two plan queries,
+    # namesake plus a per-call mcp_dispatch (round 5: the library exports no setter and keeps no dispatch state), or one of the three plan queries,
     # whose stem is the boundary call it plans
     dbg = declared_symbols(DEBUG_HEADER)
-    plan_queries = ("mcp_rollout_fwd_plan", "mcp_rollout_bwd_plan")
+    plan_queries = ("mcp_rollout_fwd_plan", "mcp_rollout_bwd_plan", "mcp_nll_epoch_plan")
     assert dbg and all((n.endswith("_ex") and n[:-3] in names) or (n in plan_queries and n[:-len("_plan")] in names) for n in dbg)
     assert all(dbg.count(n) == 1 for n in plan_queries)
     for n in dbg:

@@ -10,7 +10,9 @@
     exchanged where they act asymmetrically) sits at r > 100 C from the right one, so the bound would catch such a kernel;
   - the mpmath back end (used where long double is no wider than double) gives the long-double truth on a small case;
   - the marginal likelihood: orc.marginal_nll + autograd against the extended-precision loss and gradient at the two smallest N of the
-    training-epoch cases.
+    training-epoch cases;
+  - the marginal-likelihood gradient OPERATOR (tests/test_gpu_nll_grad.py): the floor of a float64 torch evaluation of the library's formula
+    over every case of gt.ALL_GRAD_CASES against gt.nll_grad_truth, the conditions on S, and three subtly wrong models the bound tells apart.
 """
 import numpy as np
 import pytest
@@ -137,3 +139,79 @@ def test_oracle_marginal_likelihood_against_the_extended_precision_loss(N):
     e_grad = float(np.abs(got - want).max()) / max(1.0, float(np.abs(want).max()))
     print("N = %d: oracle loss rel %.2e, worst gradient error %.2e" % (N, e_loss, e_grad))
     assert e_loss < 1e-11 and e_grad < 1e-9
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# the marginal-likelihood gradient operator
+# ----------------------------------------------------------------------------------------------------------------------------------
+GRAD_IDS = lambda c: "N%d-D%d-deg%d" % c
+
+
+def test_float64_floor_of_the_nll_gradient_supports_the_recorded_bound():
+    """r_orc: gt.nll_grad_float64 (float64 torch, one thread, the same formula on the same operands) against the truth, every case."""
+    worst, where = 0.0, None
+    for case in gt.ALL_GRAD_CASES:
+        op = gt.nll_grad_case(*case)
+        g, S = gt.nll_grad_case_truth(case)
+        got = gt.nll_grad_float64(*gt.nll_grad_args(op)).numpy()
+        live = gt.nll_grad_live(*case)
+        assert np.all(got[~live] == 0.0), case
+        r = float(gt.r_entries(got, g, S, live).max())
+        print("r_orc[nll_grad] (N, D, deg) = %s: %.3f" % (case, r))
+        if r > worst:
+            worst, where = r, case
+    print("r_orc[nll_grad] = %.3f at %s; recorded %.3f, C = %g" % (worst, where, gt.R_ORC["nll_grad"], gt.C["nll_grad"]))
+    assert gt.C["nll_grad"] == gt.pow2_ceil(16.0 * gt.R_ORC["nll_grad"])
+    assert worst <= gt.C["nll_grad"] / 8.0
+
+
+@pytest.mark.parametrize("case", gt.ALL_GRAD_CASES, ids=GRAD_IDS)
+def test_conditions_on_the_nll_gradient_cases(case):
+    N, D, deg = case
+    op = gt.nll_grad_case(*case)
+    g, S = gt.nll_grad_case_truth(case)
+    down, live = gt.backend().down, gt.nll_grad_live(*case)
+    g, S = down(g), down(S)
+    assert g.shape == S.shape == (4 * D + 3,) and live.sum() == (D if N > 1 else 0) + 2 + (D + 1) * (deg >= 1) + 2 * D * (deg >= 2)
+    assert np.all(np.isfinite(S[live])) and np.all(S[live] > 0)
+    assert np.all(np.isfinite(g[live])) and np.all(np.abs(g[live]) <= S[live])
+    assert np.all(g[~live] == 0.0) and np.all(S[~live] == 0.0)
+    assert np.array_equal(op["W"], op["W"].T) and op["W"].shape == (N, N) and op["alpha"].shape == (N,)
+
+
+def test_the_nll_gradient_bound_tells_a_subtly_different_model_apart():
+    case = gt.GRAD_VARIANT_CASE
+    N, D, deg = case
+    assert deg == 2
+    op = gt.nll_grad_case(*case)
+    g, S = gt.nll_grad_case_truth(case)
+    be = gt.backend()
+    bound = 100.0 * gt.C["nll_grad"]
+    entries = lambda a, b: np.arange(a, b)
+
+    def r_on(wrong, idx):
+        mask = np.zeros(4 * D + 3, dtype=bool)
+        mask[idx] = True
+        return gt.r_entries(be.down(wrong), g, S, mask)
+
+    # one alpha_i alpha_j term dropped from Wm (an off-diagonal one: it enters every sum but the trace)
+    i, j = N - 1, 0
+    W = op["W"].copy()
+    W[i, j] += op["alpha"][i] * op["alpha"][j]  # (W_ij - a_i a_j + a_i a_j: the float64 rounding of this sum is far below the effect)
+    args = list(gt.nll_grad_args(op))
+    args[1] = W
+    r = r_on(gt.nll_grad_truth(*args)[0], np.r_[entries(0, D + 1), entries(D + 2, 4 * D + 3)])
+    print("alpha_i alpha_j dropped at (%d, %d): r >= %.3g" % (i, j, r.min()))
+    assert r.min() > bound
+    # a MPK_2 factor-0 entry formed with A instead of B:  2 w20_e x_ie x_je A_ij  (the truth of the model whose second factor reads w20)
+    args = list(gt.nll_grad_args(op))
+    args[7] = op["w20"]
+    r = r_on(gt.nll_grad_truth(*args)[0], entries(2 * D + 3, 3 * D + 3))
+    print("factor 0 with A for B: r >= %.3g" % r.min())
+    assert r.min() > bound
+    # inv_ls where inv_ls^2 belongs:  2 dx^2 / l  in the lengthscale entries
+    wrong = g.copy()
+    wrong[:D] = g[:D] / be.up(op["inv_ls"])
+    r = r_on(wrong, entries(0, D))
+    print("inv_ls for inv_ls^2: r >= %.3g" % r.min())
+    assert r.min() > bound
