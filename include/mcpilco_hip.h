@@ -186,6 +186,26 @@ typedef struct mcp_pd_policy {
   int32_t target_rows;          /* >= T                                                       */
 } mcp_pd_policy;
 
+/* Tanh multilayer perceptron in closed loop -- Policy.MLP_policy (this project's own class; the reference has none), evaluated inside the
+ * fused rollout on the features of Sum_of_gaussians_with_angles in the order f = [x[non_angle], sin x[angle], cos x[angle]] (both lists
+ * empty: f = x, P = S):
+ *   h1 = tanh(W[0] f + b[0]);  h2 = tanh(W[1] h1 + b[1]) (n_hidden == 2);  a = W[2] h + b[2];  u[k] = u_max[k] tanh(a[k] / u_max[k]) (squash) or a[k]
+ * Layer i is row-major [out][in]; W[2] / b[2] are ALWAYS the output layer, W[1] / b[1] are NULL with one hidden layer.  The weights are
+ * DEVICE pointers: an optimizer updates them in place.  An index appears at most once in angle and non_angle together. */
+#define MCP_MAX_HIDDEN 64 /* units of a hidden layer of mcp_mlp_policy */
+typedef struct mcp_mlp_policy {
+  int32_t S, U, P;                  /* == model->S, == model->U, n_non_angle + 2 n_angle (or S)    */
+  int32_t n_hidden;                 /* 1 or 2                                                     */
+  int32_t h[2];                     /* widths, 1 .. MCP_MAX_HIDDEN (h[1] ignored with one layer)  */
+  int32_t n_angle, n_non_angle;     /* both 0: f = x                                              */
+  int32_t angle[MCP_MAX_STATE];
+  int32_t non_angle[MCP_MAX_STATE];
+  int32_t squash;                   /* flg_squash                                                 */
+  double u_max[MCP_MAX_INPUT];      /* > 0 with squash                                            */
+  const double* W[3];               /* [h0][P] | [h1][h0] or NULL | [U][h_last]                   */
+  const double* b[3];               /* [h0]    | [h1] or NULL     | [U]                           */
+} mcp_mlp_policy;
+
 /* ---- library ------------------------------------------------------------------------ */
 int mcp_abi_version(void);
 const char* mcp_build_info(void);
@@ -366,6 +386,26 @@ int mcp_rollout_pd(const mcp_model* model, const mcp_pd_policy* pd, const mcp_no
  * and the integrators (model_learning/Model_learning.py:210-229, 471-494, 685-718). */
 int mcp_rollout_pd_bwd(const mcp_model* model, const mcp_pd_policy* pd, int M, int T, const double* states, const double* inputs,
                        const double* jac, const double* g_states, const double* g_inputs, double* g_gains, double* g_x0, void* stream);
+/* Closed-loop rollout under the tanh MLP (mcp_mlp_policy), ONE launch: mcp_rollout_pd with the descriptor exchanged -- the same step,
+ * noise addressing, status flags (a NaN input raises MCP_STATUS_NAN; MCP_STATUS_NONPOS_VAR as there), T == 1 evaluates the policy only.
+ * states [T][M][S]; inputs [T][M][U], row T - 1 included.  jac NULL: the plain launch; else the record [T-1][M][G][D] for
+ * mcp_rollout_mlp_bwd.  The states carry the bits of mcp_rollout_open fed with the launch's own inputs[:T-1], and the plain launch those
+ * of the recording launch.  The weights are copied to LDS (rows padded to an odd pitch) where they fit beside the step's layout, else read
+ * from global memory.  MCP_ERR_ARG: a NULL pointer, M <= 0, T < 1, mlp->U != model->U, mlp->S != model->S, n_hidden outside 1..2, a
+ * width < 1, an index out of range or listed twice, P != n_non_angle + 2 n_angle (P != S without lists), a missing layer pointer, a
+ * u_max <= 0 with squash; MCP_ERR_LIMIT beyond MCP_MAX_* (P > MCP_MAX_PFEAT included) or MCP_MAX_HIDDEN; limits first, as for the PD law. */
+int mcp_rollout_mlp(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_noise* noise, int M, int T, int particle_pred, const double* x0,
+                    double* states, double* inputs, double* mu, double* var, double* jac /* NULL: no record */, uint32_t* status, void* stream);
+/* Reverse-time sweep of mcp_rollout_mlp: g_states [T][M][S] (required) and g_inputs [T][M][U] (may be NULL) -> g_x0 [M][S] and
+ * g_params [ceil(M/16)][n_param]: ONE PARTIAL SLAB PER WORKGROUP of 16 trajectories, laid out W0 | b0 | [W1 | b1] | Wout | bout (each
+ * row-major as in the descriptor); the sum over the slabs is the caller's, in an order of its choosing.  No atomics, a fixed order of
+ * sums: bitwise reproducible, and a slab depends on its own 16 trajectories alone.  Either output may be NULL; with both NULL the call
+ * returns MCP_OK without a launch.  states, inputs, jac: what mcp_rollout_mlp wrote (jac may be NULL when T == 1).  Row T - 1 contributes
+ * through g_inputs alone.  The activations are recomputed from states with the forward's own order of operations.  The argument checks of
+ * the forward entry. */
+int mcp_rollout_mlp_bwd(const mcp_model* model, const mcp_mlp_policy* mlp, int M, int T, const double* states, const double* inputs,
+                        const double* jac, const double* g_states, const double* g_inputs /* may be NULL */, double* g_params, double* g_x0,
+                        void* stream);
 /* mcp_rollout_pd with the PD law evaluated on a SIMULATED MEASUREMENT of the state (mcp_meas: noisy positions, backward-difference
  * velocities through the first-order filter; row 0 is measured true), ONE launch: the particles evolve on their true states,
  * e = target_traj[t] - y_t.  Per pair i (p = pos[i], v = vel[i]) and row t >= 1: np_t = x_t[p] + std_pos[i] n_{t,i}, nv_t = (np_t - np_{t-1}) / Ts,

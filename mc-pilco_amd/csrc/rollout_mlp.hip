@@ -1,0 +1,868 @@
+// Fused closed loop under a tanh multilayer perceptron for gfx950 (MI355X), and its reverse-time sweep: Policy.MLP_policy as MC_PILCO's
+// control policy.  The policy is this project's own (the reference has no such class); the loop it closes is MC_PILCO.apply_policy's
+// (policy_learning/MC_PILCO.py:615-674) over Model_learning.get_next_state (model_learning/Model_learning.py:210-229, 471-494, 685-718).
+//   mcp_rollout_mlp      M trajectories, T steps, ONE launch: u_t = mlp(x_t) computed in the kernel; with jac the record for the sweep
+//   mcp_rollout_mlp_bwd  the sweep: g_x0 and one partial slab of parameter gradients per workgroup of 16 trajectories
+// The forward kernel is the step loop of rollout_open.hip's feedback form with the PD law exchanged for the network: phases S, K, V, J, J', F
+// and the noise addressing are the same functions (rollout_open_phases.h) and the same statements on the same operands, and the library is
+// built without floating-point contraction, so the states carry the bits of mcp_rollout_open fed with the launch's own inputs.  Per step
+// and tile of PT trajectories the network adds, behind the barrier that publishes x_t:
+//   features   thread (trajectory, feature source): x[non_angle] as it is, one sincos_fast per angle          [PT][P]  in LDS
+//   layer l    thread (trajectory, unit), PT * width dot products dealt over the 512 threads, fast_tanh        [PT][h_l] in LDS
+//   output     the threads that fetch the inputs in the open-loop form: dot product, squashing, inputs[t], z
+// one LDS barrier behind each.  The weights are launch constants: copied to LDS once (rows at an odd pitch: a wave reads one column of
+// a layer without bank conflicts) where they fit beside the step's layout, else read from global memory (L2) in every step.
+#include "rollout_open_phases.h"
+
+using namespace mcp;
+
+// ---- the network's geometry: layers in order (the output layer is the descriptor's slot 2), parameter offsets of g_params, LDS copy ----
+struct MlpGeom {
+  int nl;                   // layers, hidden + 1
+  int in[3], out[3];        // widths
+  int woff[3], boff[3];     // offsets in the parameter order W0 | b0 | [W1 | b1] | Wout | bout
+  int pitch[3], wl[3], bl[3];  // LDS copy: row pitch (in | 1), offsets of the weights and biases
+  int nparam, lds;
+};
+__host__ __device__ inline MlpGeom mlp_geom(const mcp_mlp_policy& p) {
+  MlpGeom g;
+  g.nl = p.n_hidden + 1;
+  int o = 0, lo = 0, in = p.P;
+#pragma unroll
+  for (int l = 0; l < 3; ++l) {
+    const int out = l >= g.nl ? 0 : (l < p.n_hidden ? p.h[l] : p.U);
+    g.in[l] = l >= g.nl ? 0 : in;
+    g.out[l] = out;
+    g.woff[l] = o;
+    o += out * g.in[l];
+    g.boff[l] = o;
+    o += out;
+    g.pitch[l] = g.in[l] | 1;
+    g.wl[l] = lo;
+    lo += out * g.pitch[l];
+    g.bl[l] = lo;
+    lo += out;
+    in = out;
+  }
+  g.nparam = o;
+  g.lds = (lo + 1) & ~1;
+  return g;
+}
+__host__ __device__ inline int mlp_slot(const mcp_mlp_policy& p, int l) { return l < p.n_hidden ? l : 2; }  // layer l in the descriptor
+
+// copies the weights to LDS at the padded pitch (every thread of the workgroup; the caller's barrier follows)
+__device__ __forceinline__ void mlp_stage_weights(const mcp_mlp_policy& p, const MlpGeom& g, double* wl, int tid, int nt) {
+#pragma unroll
+  for (int l = 0; l < 3; ++l) {
+    if (l >= g.nl) break;
+    const double* W = p.W[mlp_slot(p, l)];
+    const double* b = p.b[mlp_slot(p, l)];
+    const int in = g.in[l], n = g.out[l] * in;
+    for (int it = tid; it < n; it += nt) {
+      const int j = it / in, i = it - j * in;
+      wl[g.wl[l] + j * g.pitch[l] + i] = W[it];
+    }
+    for (int j = tid; j < g.out[l]; j += nt) wl[g.bl[l] + j] = b[j];
+  }
+}
+
+// pre-activation of unit j on the input row x: the bias first, then the row's products in order -- the ONE order of operations of the
+// forward kernel and of the sweep's recomputation
+__device__ __forceinline__ double mlp_unit(const double* wr, double bias, const double* x, int in) {
+  double acc = bias;
+  for (int i = 0; i < in; ++i) acc = fma(wr[i], x[i], acc);
+  return acc;
+}
+
+// ---- forward (template WLDS: the weights have an LDS copy; a form keeps only the addresses of the copy it reads) ----------------------------
+struct OpenArgsMlp : OpenArgs {
+  mcp_mlp_policy mlp;  // (the index lists normalised by the host: without lists non_angle = 0 .. S - 1)
+  double* inputs;      // [T][M][U]
+};
+struct MlpActs {
+  int fp, hp[2];       // row pitches of the features and of the hidden layers (odd)
+  int f, h[2], w, total;  // offsets inside the form's region of the layout
+};
+__host__ __device__ inline MlpActs mlp_acts(int PT, const mcp_mlp_policy& p, const MlpGeom& g, bool wlds) {
+  MlpActs A;
+  int o = 0;
+  A.fp = p.P | 1;
+  A.f = o, o += PT * A.fp;
+#pragma unroll
+  for (int l = 0; l < 2; ++l) {
+    A.hp[l] = (l < p.n_hidden ? p.h[l] : 0) | 1;
+    A.h[l] = o;
+    o += l < p.n_hidden ? PT * A.hp[l] : 0;
+  }
+  o = (o + 1) & ~1;
+  A.w = o;
+  A.total = o + (wlds ? g.lds : 6);  // (no copy: the six addresses of the weights, read from LDS in the loop -- they then cost no scalar registers)
+  return A;
+}
+
+template <int PT>
+__device__ __forceinline__ void mlp_layer_fwd(const double* W, const double* b, int pitch, int in, int out, const double* x, int xp, double* y, int yp,
+                                              int tid) {
+  for (int it = tid; it < PT * out; it += RF_NT) {
+    const int p = it / out, j = it - p * out;
+    y[p * yp + j] = fast_tanh(mlp_unit(W + j * pitch, b[j], x + p * xp, in));
+  }
+}
+
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool WLDS>
+__global__ __launch_bounds__(RF_NT) void rollout_mlp_kernel(OpenArgsMlp a) {
+  extern __shared__ double smem[];
+  const mcp_model& md = a.model;
+  const mcp_mlp_policy& pl = a.mlp;
+  const int S = md.S, U = md.U, G = md.G, D = md.D, M = a.M, T = a.T;
+  const int nna = md.n_not_angle, na = md.n_angle;
+  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const MlpGeom mg = mlp_geom(pl);
+  const MlpActs A = mlp_acts(PT, pl, mg, WLDS);
+  const OpenLayout L = open_layout(PT, NEEDVAR, S, D, G, a.NpadMax, NEEDJAC, a.na, false, A.total);
+  double* xs = smem + L.xs;
+  double* z = smem + L.z;
+  double* red = smem + L.red;  // [2][G][RF_NW][PT]
+  GpL* gpl = reinterpret_cast<GpL*>(smem + L.gpl);
+  double* kpar = smem + L.kpar;
+  double* panel = smem + L.panel;
+  double* vpan = smem + L.vpan;  // (recording form)
+  double* wjl = smem + L.wj;
+  double* redj = smem + L.redj;
+  double* fl = smem + L.ext + A.f;       // features [PT][fp]
+  double* hl0 = smem + L.ext + A.h[0];   // hidden layers [PT][hp]
+  double* hl1 = smem + L.ext + A.h[1];
+  double* wlc = smem + L.ext + A.w;      // the weights' LDS copy
+  const mcp_noise nzl = noise_of_launch(a.nz);
+  const int m0 = blockIdx.x * PT;
+
+  stage_gp_tables(md.gp, md.var_scale, G, D, gpl, kpar, tid);
+  if (WLDS) mlp_stage_weights(pl, mg, wlc, tid, RF_NT);
+  const double** wtab = reinterpret_cast<const double**>(wlc);  // (WLDS false) W[0..2] | b[0..2]
+  if (!WLDS && tid < 6) wtab[tid] = tid < 3 ? pl.W[tid] : pl.b[tid - 3];
+  if (L.xl) {  // mean mode: the small operands of phase K come from LDS for the whole launch
+    const int NP = a.NpadMax;
+    for (int g = 0; g < G; ++g) {
+      const mcp_gp& gp = md.gp[g];
+      for (int it = tid; it < D * NP; it += RF_NT) {
+        const int d = it / NP, j = it - d * NP;
+        smem[L.xt + (g * D + d) * NP + j] = j < gp.Npad ? gp.Xt[(size_t)d * gp.Npad + j] : 0.0;
+      }
+      for (int j = tid; j < NP; j += RF_NT) smem[L.al + g * NP + j] = j < gp.Npad ? gp.alpha[j] : 0.0;
+    }
+  }
+  __syncthreads();
+  // thread (p, s) owns state component s of trajectory p of the tile; the next PT * U threads compute the inputs
+  const bool own = tid < PT * S;
+  const int op = own ? tid / S : 0, os = own ? tid - op * S : 0;
+  const int ut = tid - PT * S;
+  const bool isu = ut >= 0 && ut < PT * U;
+  const int up = isu ? ut / U : 0, uk = isu ? ut - up * U : 0;
+  const int tp = own ? op : up;
+  const int om = imin(m0 + tp, M - 1);
+  const bool ovalid = m0 + tp < M;
+  double xn = own ? a.x0[(size_t)om * S + os] : 0.0;
+  int zi_plain = -1, zi_ang = -1, g_vel = -1, g_pos = -1, vel_of_pos = 0;
+  if (own) {
+    for (int i = 0; i < nna; ++i)
+      if (md.not_angle[i] == os) zi_plain = i;
+    for (int i = 0; i < na; ++i)
+      if (md.angle[i] == os) zi_ang = i;
+    for (int g = 0; g < G; ++g) {
+      if (md.vel[g] == os) g_vel = g;
+      if (md.not_vel[g] == os) {
+        g_pos = g;
+        vel_of_pos = md.vel[g];
+      }
+    }
+  }
+  const int og = g_pos >= 0 ? g_pos : g_vel;  // the GP whose increment this component integrates
+  const double Ts = md.Ts;
+  unsigned bad = 0;
+  int cur = 0;
+  // the network: thread (trajectory fq, feature source fi) of the feature stage; the output threads' bound
+  const int nnp = pl.n_non_angle, nap = pl.n_angle, nsrc = nnp + nap;
+  const bool isf = tid < PT * nsrc;
+  const int fq = isf ? tid / nsrc : 0, fi = isf ? tid - fq * nsrc : 0;
+  const int fsrc = fi < nnp ? pl.non_angle[fi] : pl.angle[fi - nnp];
+  const double umax = isu ? pl.u_max[uk] : 1.0;
+  const int nh = pl.n_hidden, H0 = pl.h[0], H1 = nh > 1 ? pl.h[1] : 0;
+  const int HL = nh > 1 ? H1 : H0;                // the last hidden layer: its width, row pitch and rows
+  const int hpL = nh > 1 ? A.hp[1] : A.hp[0];
+  const double* hlL = nh > 1 ? hl1 : hl0;
+  // (the output layer's place in the LDS copy, picked here: no table is indexed by a run-time layer number inside the loop)
+  const int wlo = nh > 1 ? mg.wl[2] : mg.wl[1], blo = nh > 1 ? mg.bl[2] : mg.bl[1], pto = nh > 1 ? mg.pitch[2] : mg.pitch[1];
+  lds_barrier();
+
+  for (int t = 0; t < T; ++t) {
+    // ---- phase S: publish x_t ----------------------------------------------------------------------------------------
+    if (own) {
+      xs[cur * PT * S + op * S + os] = xn;
+      if (ovalid) {
+        a.states[((size_t)t * M + m0 + op) * S + os] = xn;
+        if (is_bad(xn)) bad |= MCP_STATUS_NAN;
+      }
+    }
+    // ---- u_t = mlp(x_t) from the row just published (every row, the last one included: it is stored, and a cost may read it) ----
+    lds_barrier();
+    if (isf) {
+      const double xv = xs[cur * PT * S + fq * S + fsrc];
+      double* fr = fl + fq * A.fp;
+      if (fi < nnp) {
+        fr[fi] = xv;
+      } else {
+        double sn, cs;
+        sincos_fast(xv, &sn, &cs);
+        fr[fi] = sn;
+        fr[fi + nap] = cs;
+      }
+    }
+    lds_barrier();
+    if (WLDS) {
+      mlp_layer_fwd<PT>(wlc + mg.wl[0], wlc + mg.bl[0], mg.pitch[0], pl.P, H0, fl, A.fp, hl0, A.hp[0], tid);
+    } else {
+      mlp_layer_fwd<PT>(wtab[0], wtab[3], pl.P, pl.P, H0, fl, A.fp, hl0, A.hp[0], tid);
+    }
+    lds_barrier();
+    if (nh > 1) {
+      if (WLDS) {
+        mlp_layer_fwd<PT>(wlc + mg.wl[1], wlc + mg.bl[1], mg.pitch[1], H0, H1, hl0, A.hp[0], hl1, A.hp[1], tid);
+      } else {
+        mlp_layer_fwd<PT>(wtab[1], wtab[4], H0, H0, H1, hl0, A.hp[0], hl1, A.hp[1], tid);
+      }
+      lds_barrier();
+    }
+    double ufb = 0.0;
+    if (isu) {
+      const double* hr = hlL + up * hpL;
+      const double av = WLDS ? mlp_unit(wlc + wlo + uk * pto, wlc[blo + uk], hr, HL)
+                               : mlp_unit(wtab[2] + uk * HL, wtab[5][uk], hr, HL);
+      ufb = pl.squash ? umax * fast_tanh(av / umax) : av;
+      if (ovalid) {
+        a.inputs[((size_t)t * M + m0 + up) * U + uk] = ufb;
+        if (is_bad(ufb)) bad |= MCP_STATUS_NAN;
+      }
+    }
+    if (t + 1 >= T) continue;  // (uniform) the last row: no transition
+    if (own) {
+      double* zp = z + op * D;
+      if (zi_plain >= 0) zp[zi_plain] = xn;
+      if (zi_ang >= 0) {
+        double sn, cs;
+        sincos_fast(xn, &sn, &cs);
+        zp[nna + zi_ang] = sn;
+        zp[nna + na + zi_ang] = cs;
+      }
+    }
+    if (isu) z[up * D + nna + 2 * na + uk] = ufb;
+    lds_barrier();
+    // ---- phases K (and V) per GP ---------------------------------------------------------------------------------------
+    for (int g = 0; g < G; ++g) {
+      const GpL gp = gpl[g];
+      // X^T and alpha of GP g: their LDS copies (row pitch NpadMax) where the launch staged them, else global memory (the GP's own Npad)
+      const double* Xt = L.xl ? smem + L.xt + g * D * a.NpadMax : gp.Xt;
+      const double* al = L.xl ? smem + L.al + g * a.NpadMax : gp.alpha;
+      open_phase_k<PT, MAXDEG, NEEDVAR>(gp, kpar + g * KP_STRIDE(D), D, z, panel, red + g * RF_NW * PT, tid, wv, lane, Xt, al,
+                                        L.xl ? a.NpadMax : gp.Npad);
+      if (NEEDJAC && !NEEDVAR)  // the mean chain: beta = alpha, nothing of phase K is needed -- no barrier in between
+        open_phase_j<PT, MAXDEG, false>(gp, kpar + g * KP_STRIDE(D), D, z, nullptr, 0.0, redj + g * L.redj_gp, a.na, wv, lane, Xt, al,
+                                        L.xl ? a.NpadMax : gp.Npad);
+      if (NEEDVAR) {
+        lds_barrier();
+        const int Npad = __builtin_amdgcn_readfirstlane(gp.Npad);
+        double q = 0.0;
+        for (int I0 = 32 * wv; I0 < Npad; I0 += 32 * RF_NW) q += open_v_block<PT, NEEDJAC>(gp.Kinv, Npad, I0, panel, vpan, lane);
+        q = fold_kk(q);
+        if (lane < PT) red[(G + g) * RF_NW * PT + wv * PT + lane] = q;
+        lds_barrier();  // the panel is rewritten by the next GP (recording form: by phase J's partial sums)
+        if (NEEDJAC) {
+          const int nn = (lane & 15) < PT ? (lane & 15) : 0;
+          const double wjs = open_wjs<PT, MAXDEG>(a, nzl, gp, kpar + g * KP_STRIDE(D), D, G, g, t, imin(m0 + nn, M - 1), z + nn * D, red, nn);
+          if (wv == 0 && lane < PT) wjl[lane] = wjs;
+          open_phase_j<PT, MAXDEG, true>(gp, kpar + g * KP_STRIDE(D), D, z, vpan, wjs, redj, a.na, wv, lane, Xt, al, gp.Npad);
+          lds_barrier();
+          open_jac_store<PT, MAXDEG, true>(a, gp, kpar + g * KP_STRIDE(D), g, t, m0, z, wjl, redj, a.na, tid);
+          lds_barrier();  // the next GP's phase K writes the panel again
+        }
+      }
+    }
+    if (!NEEDVAR) lds_barrier();
+    if (NEEDJAC && !NEEDVAR)
+      for (int g = 0; g < G; ++g) open_jac_store<PT, MAXDEG, false>(a, gpl[g], kpar + g * KP_STRIDE(D), g, t, m0, z, nullptr, redj + g * L.redj_gp, a.na, tid);
+    // ---- phase F: moments, sample, integrate   v' = v + delta ;  q' = q + Ts v + Ts/2 delta   (Model_learning.py:711-716) ----
+    if (own) {
+      const double* xc = xs + cur * PT * S + op * S;
+      double nx = 0.0;
+      if (og >= 0) {
+        const GpL& gp = gpl[og];
+        const double* kp = kpar + og * KP_STRIDE(D);
+        const double* zp = z + op * D;
+        double mu = gp.mean;
+#pragma unroll
+        for (int w = 0; w < RF_NW; ++w) mu += red[og * RF_NW * PT + w * PT + op];
+        double var = 0.0, dv = mu;
+        if (NEEDVAR) {
+          double ktv = 0.0;
+#pragma unroll
+          for (int w = 0; w < RF_NW; ++w) ktv += red[(G + og) * RF_NW * PT + w * PT + op];
+          double kzz = gp.lambda;
+          if (MAXDEG >= 1 && gp.deg >= 1) {
+            double p1 = kp[KP_W1(D) + D];
+            for (int d = 0; d < D; ++d) p1 = fma(kp[KP_W1(D) + d] * zp[d], zp[d], p1);
+            kzz += p1;
+            if (MAXDEG >= 2 && gp.deg >= 2) {
+              double Sa = 0.0, Sb = 0.0;
+              for (int d = 0; d < D; ++d) {
+                const double zz = zp[d] * zp[d];
+                Sa = fma(kp[KP_W20(D) + d], zz, Sa);
+                Sb = fma(kp[KP_W21(D) + d], zz, Sb);
+              }
+              kzz = fma(Sa, Sb, kzz);
+            }
+          }
+          var = (kzz - ktv) * gp.var_scale;
+          if (a.sample) {
+            const double e = nzl.eps ? nzl.eps[((size_t)t * M + om) * G + og] : philox_normal(nzl, om, t, og);
+            dv = fma(sqrt(var), e, mu);
+          }
+        }
+        if (og == g_vel && ovalid) {  // every GP has exactly one velocity component: its thread reports
+          const size_t o = ((size_t)t * M + m0 + op) * G + og;
+          if (a.mu) a.mu[o] = mu;
+          if (NEEDVAR && a.var) a.var[o] = var;
+          if (a.sample && var <= 0.0) bad |= MCP_STATUS_NONPOS_VAR;  // (finite and not positive: a NaN variance is MCP_STATUS_NAN)
+          if (is_bad(mu) || is_bad(var)) bad |= MCP_STATUS_NAN;
+        }
+        nx = og == g_pos ? xc[os] + Ts * xc[vel_of_pos] + 0.5 * Ts * dv : xc[os] + dv;
+      }
+      xn = nx;
+    }
+    if ((NEEDVAR && MAXDEG >= 1) || NEEDJAC) lds_barrier();  // k(z, z) above (and phase J') read z, which the next step's phase S rewrites
+    cur ^= 1;
+  }
+  if (bad) atomicOr(a.status, bad);
+}
+
+// ---- descriptor checks (host fields only: the weights are device memory) ------------------------------------------------------------------
+// The precedence of pd_policy_check: a compiled limit first (MCP_ERR_LIMIT), then everything else (MCP_ERR_ARG).  n_hidden is looked at
+// before the widths it counts.
+static int mlp_policy_check(const mcp_model* model, const mcp_mlp_policy* p) {
+  if (p->U > MCP_MAX_INPUT || p->S > MCP_MAX_STATE || p->P > MCP_MAX_PFEAT) return MCP_ERR_LIMIT;
+  if (p->n_hidden < 1 || p->n_hidden > 2) return MCP_ERR_ARG;
+  for (int l = 0; l < p->n_hidden; ++l)
+    if (p->h[l] > MCP_MAX_HIDDEN) return MCP_ERR_LIMIT;
+  if (p->n_angle > MCP_MAX_STATE || p->n_non_angle > MCP_MAX_STATE) return MCP_ERR_LIMIT;
+  if (p->U < 1 || p->U != model->U || p->S != model->S || p->n_angle < 0 || p->n_non_angle < 0) return MCP_ERR_ARG;
+  for (int l = 0; l < p->n_hidden; ++l)
+    if (p->h[l] < 1) return MCP_ERR_ARG;
+  const bool lists = p->n_angle > 0 || p->n_non_angle > 0;
+  if (p->P != (lists ? p->n_non_angle + 2 * p->n_angle : p->S)) return MCP_ERR_ARG;
+  unsigned seen = 0;  // an index at most once in the two lists together
+  for (int i = 0; i < p->n_angle + p->n_non_angle; ++i) {
+    const int s = i < p->n_angle ? p->angle[i] : p->non_angle[i - p->n_angle];
+    if (s < 0 || s >= p->S || (seen >> s & 1u)) return MCP_ERR_ARG;
+    seen |= 1u << s;
+  }
+  for (int l = 0; l <= p->n_hidden; ++l) {
+    const int sl = l < p->n_hidden ? l : 2;
+    if (!p->W[sl] || !p->b[sl]) return MCP_ERR_ARG;
+  }
+  for (int k = 0; p->squash && k < p->U; ++k)
+    if (!(p->u_max[k] > 0.0)) return MCP_ERR_ARG;
+  return MCP_OK;
+}
+// the descriptor the kernels see: without lists the features are the state
+static mcp_mlp_policy mlp_normalised(const mcp_mlp_policy* p) {
+  mcp_mlp_policy q = *p;
+  if (q.n_angle == 0 && q.n_non_angle == 0) {
+    q.n_non_angle = q.S;
+    for (int s = 0; s < q.S; ++s) q.non_angle[s] = s;
+  }
+  if (q.n_hidden == 1) q.h[1] = 0, q.W[1] = q.b[1] = nullptr;
+  return q;
+}
+
+// ---- host path of the forward entry: checks -> fill -> ladder -----------------------------------------------------------------------------
+// one rung: the weights in LDS where the layout then fits, else in global memory; MCP_ERR_LIMIT where the rung does not fit at all
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool WLDS>
+static int launch_mlp_w(const OpenArgsMlp& a, hipStream_t st) {
+  const MlpActs A = mlp_acts(PT, a.mlp, mlp_geom(a.mlp), WLDS);
+  const OpenLayout L = open_layout(PT, NEEDVAR, a.model.S, a.model.D, a.model.G, a.NpadMax, NEEDJAC, a.na, false, A.total);
+  const size_t lds = (size_t)L.total * sizeof(double);
+  if (lds > MCP_LDS_LIMIT) return MCP_ERR_LIMIT;
+  MCP_ENSURE_MAX_LDS((rollout_mlp_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, WLDS>));
+  hipLaunchKernelGGL((rollout_mlp_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, WLDS>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
+  MCP_LAUNCH_CHECK();
+  return MCP_OK;
+}
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC>
+static int launch_mlp(const OpenArgsMlp& a, hipStream_t st) {
+  const int rc = launch_mlp_w<PT, MAXDEG, NEEDVAR, NEEDJAC, true>(a, st);
+  return rc == MCP_ERR_LIMIT ? launch_mlp_w<PT, MAXDEG, NEEDVAR, NEEDJAC, false>(a, st) : rc;
+}
+template <int PT, bool NEEDVAR, bool NEEDJAC>
+static int launch_mlp_deg(const OpenArgsMlp& a, int maxdeg, hipStream_t st) {
+  return maxdeg == 0 ? launch_mlp<PT, 0, NEEDVAR, NEEDJAC>(a, st) : launch_mlp<PT, 2, NEEDVAR, NEEDJAC>(a, st);
+}
+// The ladder of tiles of rollout_open.hip's launch_open_tiles (at every compiled limit at once the one-trajectory recording rung takes
+// 85 KB + 1.3 KB of activations: nothing within the limits is refused), entered one rung lower by SMALL SWARMS: up to MLP_SMALL_SWARM
+// trajectories start at 4 per workgroup.  Measured (profiles/NOTES.md part T): the time of a launch is the time of ONE tile's T steps for as
+// long as every tile has a compute unit of its own, whatever M, and a tile of 4 takes 0.82x (UR5 shape) / 0.86x (arm shape) the time of a
+// tile of 16 -- the Kinv stream and the MFMAs of phases V and J do not depend on the width, phase K does.  Tiles of 4 have a compute unit
+// each up to M = 4 x 256 = 1024; at M = 1536 they take two rounds and twice the time, and tiles of 16 (96 workgroups) win again.  The tile
+// width changes no bit of a trajectory (a column of phases K, V, J is computed the same way in every width: the identities with
+// mcp_rollout_open hold across the rungs).
+#define MLP_SMALL_SWARM 1024  // 4 trajectories x the 256 compute units of the MI355X
+static int launch_mlp_tiles(const OpenArgsMlp& a, int maxdeg, bool wantvar, hipStream_t st) {
+  const bool small = a.M <= MLP_SMALL_SWARM;
+  if (!a.jac) {
+    if (!a.sample && !wantvar) return launch_mlp_deg<1, false, false>(a, maxdeg, st);
+    int rc = small ? MCP_ERR_LIMIT : launch_mlp_deg<16, true, false>(a, maxdeg, st);
+    if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<4, true, false>(a, maxdeg, st);
+    return rc;
+  }
+  if (!a.sample && !wantvar) return launch_mlp_deg<1, false, true>(a, maxdeg, st);
+  int rc = small ? MCP_ERR_LIMIT : launch_mlp_deg<16, true, true>(a, maxdeg, st);
+  if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<4, true, true>(a, maxdeg, st);
+  if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<1, true, true>(a, maxdeg, st);
+  return rc;
+}
+
+extern "C" int mcp_rollout_mlp(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_noise* noise, int M, int T, int particle_pred,
+                               const double* x0, double* states, double* inputs, double* mu, double* var, double* jac, uint32_t* status,
+                               void* stream) {
+  if (!model || !mlp || !noise || !x0 || !states || !inputs || !status) return MCP_ERR_ARG;
+  if (M <= 0 || T < 1) return MCP_ERR_ARG;
+  if (!model_within_limits(model)) return MCP_ERR_LIMIT;
+  if (!model_ok(model)) return MCP_ERR_ARG;
+  const int crc = mlp_policy_check(model, mlp);
+  if (crc != MCP_OK) return crc;
+  OpenArgsMlp a;
+  if (T == 1) jac = nullptr;  // the policy alone: no transition, nothing to record
+  const int maxdeg = open_fill(a, model, noise, M, T, particle_pred, x0, nullptr, M, nullptr, states, mu, var, jac, status);
+  a.mlp = mlp_normalised(mlp);
+  a.inputs = inputs;
+  return launch_mlp_tiles(a, maxdeg, var != nullptr, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------
+// Reverse-time sweep of the closed loop under the network: the open-loop sweep (rollout_open.hip: stages A, B, C, the loader wave) with
+// the policy's stage between B and C.  Per row r and trajectory, with gu = gz[input slots] + g_inputs[r] (row T - 1: g_inputs alone):
+//   abar = gu (1 - (u / u_max)^2)  (squash) or gu;   delta_out = abar;   delta_l = (W_{l+1}^T delta_{l+1}) (1 - h_l^2);   fbar = W_0^T delta_1
+//   lambda[s] += fbar[i]  (s = non_angle[i])  |  cos x fbar[sin_i] - sin x fbar[cos_i]  (s = angle[i])                       (stage C)
+//   g_W_l += delta_l h_{l-1}^T,  g_b_l += delta_l   summed over the rows and the tile's trajectories
+// A workgroup of 8 waves owns 16 trajectories.  Wave 0 is the CHAIN (lane (p = l & 15, q = l >> 4): trajectory p, every fourth index) and
+// carries only the delta back-propagation; wave 1 is the LOADER of the open-loop sweep.  Waves 2..7 are the WORKERS, off the chain:
+//   activations  of row r - 1 while the chain runs row r: a wave per trajectory (lane = feature source, then lane = unit), recomputed from
+//                states[r - 1] with the forward's order of operations (mlp_unit, fast_tanh, sincos_fast): the forward's bits
+//   outer sums   of row r + 1, whose deltas the chain left in LDS one barrier ago: the n_param entries are dealt over the 384 worker
+//                threads, at most MB_NACC each, held in registers across the whole sweep; a thread adds its entries' products over the
+//                trajectories in order, row after row, and stores them once: the workgroup's slab
+// Three rows of activations are alive at once (r + 1 read by the outer sums, r by the chain, r - 1 being written): three buffers, two of
+// deltas, one workgroup barrier per row.  Where 16 trajectories of that do not fit the LDS the workgroup sweeps its 16 trajectories in
+// parts of 8 / 4 / 2 / 1, one after the other, the sums staying in the registers: a slab is still one workgroup's.  No atomics; the order
+// of every sum is fixed by the shape alone.
+// ---------------------------------------------------------------------------------------
+#define MB_PT 16
+#define MB_NT 512
+#define MB_NWORK (MB_NT - 128)  // worker threads
+#define MB_NACC 18              // parameter entries per worker thread
+static_assert(MCP_MAX_HIDDEN * (MCP_MAX_PFEAT + 1) + MCP_MAX_HIDDEN * (MCP_MAX_HIDDEN + 1) + MCP_MAX_INPUT * (MCP_MAX_HIDDEN + 1) <= MB_NACC * MB_NWORK,
+              "a worker thread's share of the parameters");
+#define MB_CMAX (MCP_MAX_HIDDEN / 4)  // columns per lane of the chain wave
+
+struct MlpBwdArgs {
+  int S, U, G, D, nna, na, M, T;
+  int angle[MCP_MAX_STATE], not_angle[MCP_MAX_STATE], vel[MCP_MAX_GP], not_vel[MCP_MAX_GP];
+  double Ts;
+  const double* states;
+  const double* inputs;
+  const double* jac;
+  const double* g_states;
+  const double* g_inputs;  // or NULL
+  double* g_x0;            // or NULL
+  double* g_params;        // [ceil(M / 16)][n_param] or NULL
+  mcp_mlp_policy mlp;      // (normalised)
+  int pts;                 // trajectories per part: 16 / 8 / 4 / 2 / 1
+  int wlds;
+};
+
+struct MlpBwdLayout {
+  int rec, xs, gs, lam, gd, gz, tab, ul, gul, fbar, act, del, w, total;  // offsets in doubles
+  int rp, fp, ap, dp;          // pitches: record row | fbar row | activation row | delta row (odd)
+  int aoff[3], one, doff[3];   // inside an activation row: the input of layer l, the constant 1; inside a delta row: the output of layer l
+};
+__host__ __device__ inline MlpBwdLayout mlp_bwd_layout(int pts, int S, int U, int G, int D, const mcp_mlp_policy& p, const MlpGeom& g, bool wlds) {
+  MlpBwdLayout L;
+  int o = 0;
+  auto take = [&](int n) {
+    int r = o;
+    o += (n + 1) & ~1;
+    return r;
+  };
+  L.rp = (G * D) | 1;
+  L.fp = p.P | 1;
+  int ao = 0, dd = 0;
+#pragma unroll
+  for (int l = 0; l < 3; ++l) {
+    L.aoff[l] = ao;
+    ao += g.in[l];
+    L.doff[l] = dd;
+    dd += g.out[l];
+  }
+  L.one = ao;
+  L.ap = (ao + 1) | 1;
+  L.dp = dd | 1;
+  L.rec = take(2 * pts * L.rp);
+  L.xs = take(2 * pts * S);
+  L.gs = take(2 * pts * S);
+  L.lam = take(2 * pts * S);
+  L.gd = take(pts * G);
+  L.gz = take(pts * D);
+  L.tab = take((7 * MCP_MAX_STATE + MB_PT) / 2 + 2);  // ints: og | ispos | velof | zplain | zang | fplain | fang (per state component), len (per trajectory)
+  L.ul = take(2 * pts * U);
+  L.gul = take(2 * pts * U);
+  L.fbar = take(pts * L.fp);
+  L.act = take(3 * pts * L.ap);
+  L.del = take(2 * pts * L.dp);
+  L.w = o;
+  L.total = o + (wlds ? g.lds : 0);
+  return L;
+}
+
+// chain wave: acc[i] = sum_k W[k][c_i] d[k] for this lane's columns c_i = q + 4 i < nin (W: nout rows at `pitch`)
+__device__ __forceinline__ void mlp_back(const double* W, int pitch, int nin, int nout, const double* d, int q, double (&acc)[MB_CMAX]) {
+  const int nc = (nin + 3) >> 2;
+#pragma unroll
+  for (int i = 0; i < MB_CMAX; ++i) acc[i] = 0.0;
+  for (int k = 0; k < nout; ++k) {
+    const double dk = d[k];
+    const double* wr = W + k * pitch + q;
+#pragma unroll
+    for (int i = 0; i < MB_CMAX; ++i)
+      if (i < nc) acc[i] = fma(q + 4 * i < nin ? wr[4 * i] : 0.0, dk, acc[i]);
+  }
+}
+
+template <bool WLDS>
+__global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(MlpBwdArgs a) {
+  extern __shared__ double smem[];
+  const mcp_mlp_policy& pl = a.mlp;
+  const int S = a.S, U = a.U, G = a.G, D = a.D, M = a.M, T = a.T, nna = a.nna, na = a.na, pts = a.pts;
+  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const MlpGeom mg = mlp_geom(pl);
+  const MlpBwdLayout L = mlp_bwd_layout(pts, S, U, G, D, pl, mg, WLDS);
+  const int GD = G * D, RP = L.rp;
+  double* rec = smem + L.rec;
+  double* xsl = smem + L.xs;
+  double* gsl = smem + L.gs;
+  double* lam = smem + L.lam;
+  double* gdl = smem + L.gd;
+  double* gzl = smem + L.gz;
+  int* ogt = reinterpret_cast<int*>(smem + L.tab);
+  int* post = ogt + MCP_MAX_STATE;
+  int* velof = post + MCP_MAX_STATE;
+  int* zplain = velof + MCP_MAX_STATE;
+  int* zang = zplain + MCP_MAX_STATE;
+  int* fplain = zang + MCP_MAX_STATE;
+  int* fang = fplain + MCP_MAX_STATE;
+  int* lenl = fang + MCP_MAX_STATE;
+  double* ull = smem + L.ul;
+  double* gul = smem + L.gul;
+  double* fbar = smem + L.fbar;
+  double* act = smem + L.act;
+  double* del = smem + L.del;
+  double* wlc = smem + L.w;
+  const int nnp = pl.n_non_angle, nap = pl.n_angle, nl = mg.nl;
+  // the weights as this kernel reads them (WLDS: the LDS copy, else global memory); the layer loops below are unrolled over the three
+  // slots, so every index into these tables is a constant
+  const double* Wl[3];
+  const double* bl[3];
+  int wp[3];
+#pragma unroll
+  for (int l = 0; l < 3; ++l) {
+    const int sl = mlp_slot(pl, l);
+    Wl[l] = WLDS ? wlc + mg.wl[l] : pl.W[sl];
+    bl[l] = WLDS ? wlc + mg.bl[l] : pl.b[sl];
+    wp[l] = WLDS ? mg.pitch[l] : mg.in[l];
+  }
+  const int dlast = nl == 3 ? L.doff[2] : L.doff[1];  // the output layer's deltas
+
+  if (WLDS) mlp_stage_weights(pl, mg, wlc, tid, MB_NT);
+  if (tid < S) {  // which GP a component integrates, as the forward kernel decides it; where it enters the two feature maps
+    const int s = tid;
+    int g_vel = -1, g_pos = -1, zp = -1, za = -1, fpl = -1, fan = -1;
+    for (int g = 0; g < G; ++g) {
+      if (a.vel[g] == s) g_vel = g;
+      if (a.not_vel[g] == s) g_pos = g;
+    }
+    for (int i = 0; i < nna; ++i)
+      if (a.not_angle[i] == s) zp = i;
+    for (int i = 0; i < na; ++i)
+      if (a.angle[i] == s) za = i;
+    for (int i = 0; i < nnp; ++i)
+      if (pl.non_angle[i] == s) fpl = i;
+    for (int i = 0; i < nap; ++i)
+      if (pl.angle[i] == s) fan = i;
+    ogt[s] = g_pos >= 0 ? g_pos : g_vel;
+    post[s] = g_pos >= 0 ? 1 : 0;
+    velof[s] = g_pos >= 0 ? a.vel[g_pos] : -1;
+    zplain[s] = zp;
+    zang[s] = za;
+    fplain[s] = fpl;
+    fang[s] = fan;
+  }
+  // a worker thread's entries of the parameter vector: where their delta and their activation sit in a row; the running sums
+  const int wt = tid - 128;
+  const int nused = (mg.nparam + MB_NWORK - 1) / MB_NWORK;  // (uniform)
+  int dof[MB_NACC], aof[MB_NACC];
+  double gacc[MB_NACC];
+#pragma unroll
+  for (int i = 0; i < MB_NACC; ++i) {
+    dof[i] = aof[i] = 0;
+    gacc[i] = 0.0;
+    const int e = wt + MB_NWORK * i;
+    if (wt >= 0 && e < mg.nparam) {
+#pragma unroll
+      for (int l = 0; l < 3; ++l) {
+        if (l >= nl) continue;
+        if (e >= mg.woff[l] && e < mg.boff[l]) {
+          const int j = (e - mg.woff[l]) / mg.in[l];
+          dof[i] = L.doff[l] + j;
+          aof[i] = L.aoff[l] + (e - mg.woff[l] - j * mg.in[l]);
+        } else if (e >= mg.boff[l] && e < mg.boff[l] + mg.out[l]) {
+          dof[i] = L.doff[l] + e - mg.boff[l];
+          aof[i] = L.one;
+        }
+      }
+    }
+  }
+  const int ww = wv - 2;  // worker wave 0..5
+
+  // the activations of row r of this part's trajectories, worker wave `ww`: a trajectory per wave and turn
+  auto activations = [&](int r, int mp0) {
+    double* ab = act + (r % 3) * pts * L.ap;
+    for (int p = ww; p < pts; p += 6) {
+      const double* xr = a.states + ((size_t)r * M + imin(mp0 + p, M - 1)) * S;
+      double* A = ab + p * L.ap;
+      if (lane < nnp + nap) {
+        if (lane < nnp) {
+          A[lane] = xr[pl.non_angle[lane]];
+        } else {
+          double sn, cs;
+          sincos_fast(xr[pl.angle[lane - nnp]], &sn, &cs);
+          A[lane] = sn;
+          A[lane + nap] = cs;
+        }
+      }
+      if (lane == 0) A[L.one] = 1.0;
+      wave_lds_sync();
+#pragma unroll
+      for (int l = 0; l < 2; ++l) {
+        if (l + 1 >= nl) continue;  // (uniform)
+        if (lane < mg.out[l]) A[L.aoff[l + 1] + lane] = fast_tanh(mlp_unit(Wl[l] + lane * wp[l], bl[l][lane], A + L.aoff[l], mg.in[l]));
+        wave_lds_sync();
+      }
+    }
+  };
+  // this worker thread's entries: the products of row r added over the part's trajectories in order
+  auto outer_sums = [&](int r) {
+    const double* db = del + (r & 1) * pts * L.dp;
+    const double* ab = act + (r % 3) * pts * L.ap;
+#pragma unroll
+    for (int i = 0; i < MB_NACC; ++i) {
+      if (i < nused) {
+        for (int p = 0; p < pts; ++p) gacc[i] = fma(db[p * L.dp + dof[i]], ab[p * L.ap + aof[i]], gacc[i]);
+      }
+    }
+  };
+  // the loader's work for one row (64 lanes): g_states, the state, the inputs and their upstream gradient of row r; jac[r] where r < T - 1
+  auto load_row = [&](int r, int b, int l, int mp0) {
+    for (int it = l; it < pts * S; it += 64) {
+      const int p = it / S, s = it - p * S;
+      if (lenl[p] > 0) {
+        gsl[(b * pts + p) * S + s] = a.g_states[((size_t)r * M + mp0 + p) * S + s];
+        xsl[(b * pts + p) * S + s] = a.states[((size_t)r * M + mp0 + p) * S + s];
+      }
+    }
+    for (int it = l; it < pts * U; it += 64) {
+      const int p = it / U, k = it - p * U;
+      if (lenl[p] > 0) {
+        ull[(b * pts + p) * U + k] = a.inputs[((size_t)r * M + mp0 + p) * U + k];
+        gul[(b * pts + p) * U + k] = a.g_inputs ? a.g_inputs[((size_t)r * M + mp0 + p) * U + k] : 0.0;
+      }
+    }
+    if (r < T - 1)
+      for (int it = l; it < pts * GD; it += 64) {
+        const int p = it / GD, e = it - p * GD;
+        if (lenl[p] > 0) rec[(b * pts + p) * RP + e] = a.jac[((size_t)r * M + mp0 + p) * GD + e];
+      }
+  };
+
+  for (int part = 0; part * pts < MB_PT; ++part) {
+    const int mp0 = blockIdx.x * MB_PT + part * pts;
+    if (mp0 >= M) break;  // (uniform) the ragged last tile: nothing of it is left
+    if (part > 0) __syncthreads();
+    if (tid >= 64 && tid < 64 + pts) lenl[tid - 64] = mp0 + tid - 64 < M ? T : 0;
+    for (int it = tid; it < 2 * pts * S; it += MB_NT) lam[it] = 0.0;
+    __syncthreads();
+    int b = 0, lc = 0;
+    if (wv == 1) load_row(T - 1, 0, lane, mp0);
+    if (wv >= 2) activations(T - 1, mp0);
+    __syncthreads();
+    for (int r = T - 1; r >= 0; --r) {
+      if (wv == 1) {
+        if (r > 0) load_row(r - 1, b ^ 1, lane, mp0);
+      } else if (wv >= 2) {
+        if (a.g_params && r + 1 <= T - 1) outer_sums(r + 1);
+        if (r > 0) activations(r - 1, mp0);
+      } else if ((lane & 15) < pts) {
+        const int p = lane & 15, q = lane >> 4;
+        const int len = lenl[p];
+        const double* lamc = lam + (lc * pts + p) * S;
+        double* lamn = lam + ((lc ^ 1) * pts + p) * S;
+        const double* rc = rec + (b * pts + p) * RP;
+        const double* xc = xsl + (b * pts + p) * S;
+        const double* gc = gsl + (b * pts + p) * S;
+        const double* Ar = act + ((r % 3) * pts + p) * L.ap;
+        double* dr = del + ((r & 1) * pts + p) * L.dp;
+        double* fb = fbar + p * L.fp;
+        const bool active = r < len - 1;
+        // stage A: the adjoints of the increments
+        for (int g = q; g < G; g += 4) {
+          double acc = 0.0;
+          for (int s = 0; s < S; ++s)
+            if (ogt[s] == g) acc += post[s] ? 0.5 * a.Ts * lamc[s] : lamc[s];
+          gdl[p * G + g] = acc;
+        }
+        wave_lds_sync();
+        // stage B: through the record to the GP input
+        if (active) {
+          for (int d = q; d < D; d += 4) {
+            double acc = 0.0;
+            for (int g = 0; g < G; ++g) acc = fma(gdl[p * G + g], rc[g * D + d], acc);
+            gzl[p * D + d] = acc;
+          }
+        }
+        wave_lds_sync();
+        // stage M: through the squashing and the layers, last to first; the deltas stay in LDS for the workers' outer sums
+        for (int k = q; k < U; k += 4) {
+          double ab = 0.0;
+          if (r <= len - 1) {
+            double gu = gul[(b * pts + p) * U + k];
+            if (active) gu += gzl[p * D + nna + 2 * na + k];
+            ab = gu;
+            if (pl.squash) {
+              const double th = ull[(b * pts + p) * U + k] / pl.u_max[k];
+              ab = gu * (1.0 - th * th);
+            }
+          }
+          dr[dlast + k] = ab;
+        }
+        wave_lds_sync();
+        double acc[MB_CMAX];
+#pragma unroll
+        for (int l = 2; l >= 1; --l) {  // delta of layer l - 1 from that of layer l
+          if (l >= nl) continue;  // (uniform)
+          mlp_back(Wl[l], wp[l], mg.in[l], mg.out[l], dr + L.doff[l], q, acc);
+#pragma unroll
+          for (int i = 0; i < MB_CMAX; ++i) {
+            const int j = q + 4 * i;
+            if (j < mg.in[l]) {
+              const double h = Ar[L.aoff[l] + j];
+              dr[L.doff[l - 1] + j] = acc[i] * (1.0 - h * h);
+            }
+          }
+          wave_lds_sync();
+        }
+        mlp_back(Wl[0], wp[0], mg.in[0], mg.out[0], dr + L.doff[0], q, acc);
+#pragma unroll
+        for (int i = 0; i < MB_CMAX; ++i)
+          if (q + 4 * i < mg.in[0]) fb[q + 4 * i] = acc[i];
+        wave_lds_sync();
+        // stage C: the integrator and the two feature maps
+        for (int s = q; s < S; s += 4) {
+          double v = 0.0;
+          if (r == len - 1) {
+            v = gc[s];
+          } else if (active) {
+            v = gc[s];
+            if (ogt[s] >= 0) v += lamc[s];
+            for (int s2 = 0; s2 < S; ++s2)
+              if (velof[s2] == s) v = fma(a.Ts, lamc[s2], v);
+            if (zplain[s] >= 0) v += gzl[p * D + zplain[s]];
+            if (zang[s] >= 0) {
+              double sn, cs;
+              sincos_fast(xc[s], &sn, &cs);
+              v += gzl[p * D + nna + zang[s]] * cs - gzl[p * D + nna + na + zang[s]] * sn;
+            }
+          }
+          if (r <= len - 1) {
+            if (fplain[s] >= 0) v += fb[fplain[s]];
+            if (fang[s] >= 0) v += fb[nnp + fang[s]] * Ar[nnp + nap + fang[s]] - fb[nnp + nap + fang[s]] * Ar[nnp + fang[s]];
+          }
+          lamn[s] = v;
+        }
+        wave_lds_sync();
+        lc ^= 1;
+      }
+      __syncthreads();
+      b ^= 1;
+    }
+    // (T is the same for every lane: the chain wave flipped lc T times)
+    lc = T & 1;
+    if (wv >= 2 && a.g_params) outer_sums(0);
+    if (wv == 0 && a.g_x0) {
+      const int p = lane & 15, q = lane >> 4;
+      if (p < pts && lenl[p] > 0)
+        for (int s = q; s < S; s += 4) a.g_x0[(size_t)(mp0 + p) * S + s] = lam[(lc * pts + p) * S + s];
+    }
+  }
+  if (wt >= 0 && a.g_params) {
+#pragma unroll
+    for (int i = 0; i < MB_NACC; ++i) {
+      const int e = wt + MB_NWORK * i;
+      if (e < mg.nparam) a.g_params[(size_t)blockIdx.x * mg.nparam + e] = gacc[i];
+    }
+  }
+}
+
+extern "C" int mcp_rollout_mlp_bwd(const mcp_model* model, const mcp_mlp_policy* mlp, int M, int T, const double* states, const double* inputs,
+                                   const double* jac, const double* g_states, const double* g_inputs, double* g_params, double* g_x0,
+                                   void* stream) {
+  if (!model || !mlp || !states || !inputs || !g_states || (!jac && T > 1)) return MCP_ERR_ARG;
+  if (M <= 0 || T < 1) return MCP_ERR_ARG;
+  if (!model_within_limits(model, false)) return MCP_ERR_LIMIT;
+  if (!model_lists_ok(model)) return MCP_ERR_ARG;
+  const int crc = mlp_policy_check(model, mlp);
+  if (crc != MCP_OK) return crc;
+  if (!g_x0 && !g_params) return MCP_OK;  // nothing asked for
+  MlpBwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.S = model->S, a.U = model->U, a.G = model->G, a.D = model->D, a.nna = model->n_not_angle, a.na = model->n_angle, a.M = M, a.T = T;
+  for (int i = 0; i < MCP_MAX_STATE; ++i) a.angle[i] = model->angle[i], a.not_angle[i] = model->not_angle[i];
+  for (int g = 0; g < MCP_MAX_GP; ++g) a.vel[g] = model->vel[g], a.not_vel[g] = model->not_vel[g];
+  a.Ts = model->Ts;
+  a.states = states, a.inputs = inputs, a.jac = jac, a.g_states = g_states, a.g_inputs = g_inputs, a.g_x0 = g_x0, a.g_params = g_params;
+  a.mlp = mlp_normalised(mlp);
+  // the part of the tile swept at once: the largest whose layout fits, the weights in LDS where they then fit too
+  const MlpGeom mg = mlp_geom(a.mlp);
+  size_t lds = 0;
+  for (int pts = MB_PT; pts >= 1 && !a.pts; pts >>= 1)
+    for (int wl = 1; wl >= 0 && !a.pts; --wl) {
+      const MlpBwdLayout L = mlp_bwd_layout(pts, a.S, a.U, a.G, a.D, a.mlp, mg, wl != 0);
+      lds = (size_t)L.total * sizeof(double);
+      if (lds <= MCP_LDS_LIMIT) a.pts = pts, a.wlds = wl;
+    }
+  if (!a.pts) return MCP_ERR_LIMIT;  // (not reached within the compiled limits: one trajectory takes 22 KB at all of them at once)
+  const dim3 grid((M + MB_PT - 1) / MB_PT);
+  if (a.wlds) {
+    MCP_ENSURE_MAX_LDS((rollout_mlp_bwd_kernel<true>));
+    hipLaunchKernelGGL((rollout_mlp_bwd_kernel<true>), grid, dim3(MB_NT), lds, (hipStream_t)stream, a);
+  } else {
+    MCP_ENSURE_MAX_LDS((rollout_mlp_bwd_kernel<false>));
+    hipLaunchKernelGGL((rollout_mlp_bwd_kernel<false>), grid, dim3(MB_NT), lds, (hipStream_t)stream, a);
+  }
+  MCP_LAUNCH_CHECK();
+  return MCP_OK;
+}

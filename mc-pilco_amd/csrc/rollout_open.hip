@@ -43,7 +43,8 @@
 //   J'  thread (trajectory, d): adds the waves' parts in wave order, applies the kernel's factors, writes jac
 // A variance that is not positive follows the closed-loop phase F: w = eps / (2 sqrt(var)) is formed as it comes (inf / NaN rows of
 // jac for that trajectory alone) and MCP_STATUS_NONPOS_VAR is raised.  Rows of jac from len - 1 on are NEVER WRITTEN and never read.
-// The arguments' base part (OpenArgs, open_fill) and phases K, V, J, J' are in rollout_open_phases.h: model_step.hip runs the same step, one per launch.
+// The arguments' base part (OpenArgs, open_fill), the LDS layout (open_layout) and phases K, V, J, J' are in rollout_open_phases.h: model_step.hip
+// runs the same step, one per launch, and rollout_mlp.hip the same loop under the tanh-MLP policy.
 #include "rollout_open_phases.h"
 
 using namespace mcp;
@@ -83,44 +84,6 @@ template <>
 struct OpenArgsOf<true, true> {
   typedef OpenArgsPdMeas type;
 };
-
-struct OpenLayout {
-  int xs, z, red, gpl, kpar, panel, xt, al, total;  // offsets in doubles
-  int vpan, redj, wj, redj_gp;                      // recording form: v panel | partial sums of phase J (stride per GP) | w per trajectory
-  int xl;                                           // X^T and alpha of every GP staged in LDS (row pitch NpadMax)
-  int ym;                                           // measured feedback form: the measurement row [PT][S]
-};
-
-__host__ __device__ inline OpenLayout open_layout(int PT, bool needvar, int S, int D, int G, int NpadMax, bool needjac = false, int na = 0,
-                                                  bool pms = false) {
-  OpenLayout L;
-  int o = 0;
-  auto take = [&](int n) {
-    int r = o;
-    o += (n + 1) & ~1;
-    return r;
-  };
-  L.xs = take(2 * PT * S);
-  L.z = take(PT * D);
-  L.red = take(2 * G * RF_NW * PT);  // per-wave partial sums: alpha^T k | k^T Kinv k
-  L.gpl = take(G * GPL_DOUBLES);
-  L.kpar = take(G * KP_STRIDE(D));
-  // phase J's partial sums [wave][column][D + 1][PT]: with variances one GP at a time, over the k panel (dead once phase V is through);
-  // the mean chain runs J beside K for every GP before its one barrier, so each GP has its own
-  const int rj = needjac ? RF_NW * na * (D + 1) * PT : 0;
-  L.panel = needvar ? take(imax(NpadMax * RO_KR(PT), rj)) : 0;
-  L.vpan = (needvar && needjac) ? take(NpadMax * RO_KR(PT)) : 0;
-  L.wj = (needvar && needjac) ? take(PT) : 0;
-  L.redj_gp = needvar ? 0 : rj;
-  L.redj = needvar ? L.panel : (needjac ? take(G * rj) : 0);
-  L.ym = pms ? take(PT * S) : 0;
-  const int xneed = G * (D + 1) * NpadMax + 4;
-  L.xl = (!needvar && o + xneed <= MCP_LDS_LIMIT / 8) ? 1 : 0;
-  L.xt = L.xl ? take(G * D * NpadMax) : 0;
-  L.al = L.xl ? take(G * NpadMax) : 0;
-  L.total = o;
-  return L;
-}
 
 template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool FB = false, bool PMS = false>
 __global__ __launch_bounds__(RF_NT) void rollout_open_kernel(typename OpenArgsOf<FB, PMS>::type a) {
@@ -615,9 +578,6 @@ __host__ __device__ inline OpenBwdLayout open_bwd_layout(int S, int G, int D, bo
   L.total = o;
   return L;
 }
-
-// orders this wave's LDS stores before its later LDS loads (the DS queue of a wave is in order; this drains it and stops the compiler)
-__device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 template <bool FB, bool PMS = false>
 __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBwdArgsOf<FB, PMS>::type a) {

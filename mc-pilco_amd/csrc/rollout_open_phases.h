@@ -1,5 +1,6 @@
 // The step of the open-loop rollouts, shared by rollout_open.hip (T steps of a tile in one launch, the GPs one after the other) and
-// model_step.hip (one step per launch, one workgroup per (tile, GP)): the arguments' base part and its fill, phases K, V, J and J'.  Both
+// model_step.hip (one step per launch, one workgroup per (tile, GP)) and rollout_mlp.hip (the loop under the tanh-MLP policy): the arguments'
+// base part and its fill, the loop's LDS layout, phases K, V, J and J'.  All
 // sources instantiate the same functions and the library is built without floating-point contraction, so a (particle, GP) carries the
 // same bits whichever of them runs it.
 #pragma once
@@ -25,6 +26,51 @@ struct OpenArgs {
 };
 
 #define RO_KR(PT) ((PT) == 16 ? 18 : (PT))  // row pitch of the k panel (16 particles: + 2 pad, bank spread of the phase-K stores)
+
+// the LDS layout of a tile's step loop (rollout_open.hip, rollout_mlp.hip)
+struct OpenLayout {
+  int xs, z, red, gpl, kpar, panel, xt, al, total;  // offsets in doubles
+  int vpan, redj, wj, redj_gp;                      // recording form: v panel | partial sums of phase J (stride per GP) | w per trajectory
+  int xl;                                           // X^T and alpha of every GP staged in LDS (row pitch NpadMax)
+  int ym;                                           // measured feedback form: the measurement row [PT][S]
+  int ext;                                          // a form's own region of `extra` doubles (rollout_mlp.hip: features, activations, weights)
+};
+
+__host__ __device__ inline OpenLayout open_layout(int PT, bool needvar, int S, int D, int G, int NpadMax, bool needjac = false, int na = 0,
+                                                  bool pms = false, int extra = 0) {
+  OpenLayout L;
+  int o = 0;
+  auto take = [&](int n) {
+    int r = o;
+    o += (n + 1) & ~1;
+    return r;
+  };
+  L.xs = take(2 * PT * S);
+  L.z = take(PT * D);
+  L.red = take(2 * G * RF_NW * PT);  // per-wave partial sums: alpha^T k | k^T Kinv k
+  L.gpl = take(G * GPL_DOUBLES);
+  L.kpar = take(G * KP_STRIDE(D));
+  // phase J's partial sums [wave][column][D + 1][PT]: with variances one GP at a time, over the k panel (dead once phase V is through);
+  // the mean chain runs J beside K for every GP before its one barrier, so each GP has its own
+  const int rj = needjac ? RF_NW * na * (D + 1) * PT : 0;
+  L.panel = needvar ? take(imax(NpadMax * RO_KR(PT), rj)) : 0;
+  L.vpan = (needvar && needjac) ? take(NpadMax * RO_KR(PT)) : 0;
+  L.wj = (needvar && needjac) ? take(PT) : 0;
+  L.redj_gp = needvar ? 0 : rj;
+  L.redj = needvar ? L.panel : (needjac ? take(G * rj) : 0);
+  L.ym = pms ? take(PT * S) : 0;
+  L.ext = extra > 0 ? take(extra) : 0;
+  const int xneed = G * (D + 1) * NpadMax + 4;
+  L.xl = (!needvar && o + xneed <= MCP_LDS_LIMIT / 8) ? 1 : 0;
+  L.xt = L.xl ? take(G * D * NpadMax) : 0;
+  L.al = L.xl ? take(G * NpadMax) : 0;
+  L.total = o;
+  return L;
+}
+
+// orders this wave's LDS stores before its later LDS loads (the DS queue of a wave is in order; this drains it and stops the compiler)
+__device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+
 
 // ---------------------------------------------------------------------------------------
 // phase V: this wave's share of  q[n] = sum_i k[i][n] (Kinv k)[i][n]  over one 32-row block of Kinv

@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(HERE, "libmcpilco_hip.so")
 
 MAX_GP, MAX_STATE, MAX_INPUT, MAX_GPDIM, MAX_PFEAT, MAX_BASIS, MAX_TRAIN = 8, 16, 8, 32, 32, 1024, 4096
 MAX_BASIS_WIDE = 512  # B of a wide policy (P > 16 or U > 4): MCP_MAX_BASIS_WIDE
+MAX_HIDDEN = 64  # units of a hidden layer of mcp_mlp_policy: MCP_MAX_HIDDEN
 OK = 0
 ERRORS = {-1: "MCP_ERR_ARG", -2: "MCP_ERR_LIMIT", -3: "MCP_ERR_WORKSPACE", -4: "MCP_ERR_LAUNCH", -5: "MCP_ERR_COMM"}
 ABI_VERSION = 7
@@ -64,6 +65,12 @@ class Noise(C.Structure):
 class PDPolicy(C.Structure):
     _fields_ = [("U", C.c_int32), ("squash", C.c_int32), ("pos", C.c_int32 * MAX_INPUT), ("vel", C.c_int32 * MAX_INPUT),
                 ("u_max", C.c_double * MAX_INPUT), ("sqrt_kp", dptr), ("sqrt_kd", dptr), ("target_traj", dptr), ("target_rows", C.c_int32)]
+
+
+class MLPPolicy(C.Structure):
+    _fields_ = [("S", C.c_int32), ("U", C.c_int32), ("P", C.c_int32), ("n_hidden", C.c_int32), ("h", C.c_int32 * 2), ("n_angle", C.c_int32),
+                ("n_non_angle", C.c_int32), ("angle", C.c_int32 * MAX_STATE), ("non_angle", C.c_int32 * MAX_STATE), ("squash", C.c_int32),
+                ("u_max", C.c_double * MAX_INPUT), ("W", dptr * 3), ("b", dptr * 3)]
 
 
 class OptState(C.Structure):
@@ -151,6 +158,9 @@ _SIGS = {
     "mcp_rollout_pd": (C.c_int, [C.POINTER(Model), C.POINTER(PDPolicy), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr,
                                  dptr, dptr, dptr]),
     "mcp_rollout_pd_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(PDPolicy), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
+    "mcp_rollout_mlp": (C.c_int, [C.POINTER(Model), C.POINTER(MLPPolicy), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr,
+                                  dptr, dptr, dptr]),
+    "mcp_rollout_mlp_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(MLPPolicy), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
     "mcp_rollout_pd_meas": (C.c_int, [C.POINTER(Model), C.POINTER(PDPolicy), C.POINTER(Meas), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr,
                                       dptr, dptr, dptr, dptr, dptr, dptr]),
     "mcp_rollout_pd_meas_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(PDPolicy), C.POINTER(Meas), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr,

@@ -785,6 +785,132 @@ def rollout_pd(model: PackedModel, pd: PackedPD, noise: Optional[NoiseSpec], x0,
     return states, inputs, status
 
 
+# --------------------------------------------------------------------------------------
+# fused closed loop under the tanh MLP (autograd)
+# --------------------------------------------------------------------------------------
+class PackedMLP:
+    """mcp_mlp_policy of a ``Policy.MLP_policy``: the parameter tensors (W0, b0, [W1, b1], Wout, bout) are kept as they are -- every
+    launch takes the LIVE tensors, so an optimizer's in-place updates are seen.  Features f = [x[non_angle], sin x[angle], cos x[angle]]
+    (both lists empty: f = x)."""
+
+    def __init__(self, policy):
+        self.params = list(policy.mlp_parameters())
+        self.S, self.U = int(policy.state_dim), int(policy.input_dim)
+        self.hidden = [int(h) for h in policy.hidden_sizes]
+        self.angle, self.non_angle = [int(i) for i in policy.angle_indices], [int(i) for i in policy.non_angle_indices]
+        self.P = len(self.non_angle) + 2 * len(self.angle) if (self.angle or self.non_angle) else self.S
+        self.squash = bool(policy.flg_squash)
+        um = policy._u_max_values() or ()  # (floats, wherever the bounds are kept)
+        self.u_max = np.full(self.U, um[0]) if len(um) == 1 else np.asarray(um, dtype=np.float64)
+        if self.u_max.size != self.U or self.U > abi.MAX_INPUT:
+            raise RuntimeError("u_max must be a scalar or hold one bound per input (at most %d inputs)" % abi.MAX_INPUT)
+        if len(self.hidden) not in (1, 2) or len(self.params) != 2 * len(self.hidden) + 2:
+            raise RuntimeError("the MLP policy has one or two hidden layers")
+        if len(self.angle) > abi.MAX_STATE or len(self.non_angle) > abi.MAX_STATE:
+            raise RuntimeError("at most %d indices per feature list" % abi.MAX_STATE)
+        self.shapes = [tuple(q.shape) for q in self.params]
+        self.n_param = sum(int(q.numel()) for q in self.params)
+        self.device = self.params[0].device
+
+    def to_c(self, tensors):
+        """The descriptor over ``tensors``: contiguous float64 GPU tensors in the parameter order, of the parameters' shapes."""
+        for t, shp in zip(tensors, self.shapes):
+            if t.dtype != DT or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shp:
+                raise RuntimeError("the MLP parameters must be contiguous float64 GPU tensors of their declared shapes")
+        c = abi.MLPPolicy()
+        c.S, c.U, c.P, c.n_hidden, c.squash = self.S, self.U, self.P, len(self.hidden), int(self.squash)
+        for l, h in enumerate(self.hidden):
+            c.h[l] = h
+        c.n_angle, c.n_non_angle = len(self.angle), len(self.non_angle)
+        for i, v in enumerate(self.angle):
+            c.angle[i] = v
+        for i, v in enumerate(self.non_angle):
+            c.non_angle[i] = v
+        for k in range(self.U):
+            c.u_max[k] = float(self.u_max[k])
+        slots = (0, 2) if len(self.hidden) == 1 else (0, 1, 2)  # (the output layer is always slot 2)
+        for l, sl in enumerate(slots):
+            c.W[sl], c.b[sl] = tensors[2 * l].data_ptr(), tensors[2 * l + 1].data_ptr()
+        return c
+
+
+def _rollout_mlp_launch(model, mlp, tensors, noise, x0, T, particle_pred, status, record):
+    M, dev = int(x0.shape[0]), model.device
+    states, inputs, jac = _record_buffers(dev, T, M, model.S, model.U, model.G, model.D, record and T > 1)
+    pc, nz = mlp.to_c(tensors), noise.to_c()
+    abi.check(abi.lib().mcp_rollout_mlp(_mc(model), C.byref(pc), C.byref(nz), M, T, int(bool(particle_pred)), abi.ptr(x0), abi.ptr(states),
+                                        abi.ptr(inputs), None, None, abi.ptr(jac), abi.ptr(status), abi.stream()), "mcp_rollout_mlp")
+    return states, inputs, jac
+
+
+def _rollout_mlp_sweep(model, mlp, tensors, states, inputs, jac, g_states, g_inputs, want_params, want_x0):
+    """(g_params slabs [ceil(M/16), n_param] or None, g_x0 [M,S] or None) of mcp_rollout_mlp_bwd."""
+    T, M, dev = int(states.shape[0]), int(states.shape[1]), states.device
+    g_x0 = torch.empty(M, model.S, dtype=DT, device=dev) if want_x0 else None
+    slabs = torch.empty((M + 15) // 16, mlp.n_param, dtype=DT, device=dev) if want_params else None
+    pc = mlp.to_c(tensors)
+    abi.check(abi.lib().mcp_rollout_mlp_bwd(_mc(model), C.byref(pc), M, T, abi.ptr(states), abi.ptr(inputs), abi.ptr(jac), abi.ptr(g_states),
+                                            abi.ptr(g_inputs), abi.ptr(slabs), abi.ptr(g_x0), abi.stream()), "mcp_rollout_mlp_bwd")
+    return slabs, g_x0
+
+
+class RolloutMLPFunction(torch.autograd.Function):
+    """(x0 [M,S], W0, b0, [W1, b1], Wout, bout) -> states [T,M,S], inputs [T,M,U] through the recording form of the fused closed loop under
+    the tanh MLP (mcp_rollout_mlp); backward is the reverse-time sweep mcp_rollout_mlp_bwd over the record, with both upstream gradients.
+    The workgroups' partial slabs are added in torch's fixed order (``sum(0)``); the GP model is frozen."""
+
+    @staticmethod
+    def forward(ctx, model, mlp, noise, T, particle_pred, status, x0, *tensors):
+        states, inputs, jac = _rollout_mlp_launch(model, mlp, tensors, noise, x0, T, particle_pred, status, True)
+        ctx.model, ctx.mlp, ctx.has_jac = model, mlp, jac is not None
+        ctx.set_materialize_grads(False)
+        # (saved tensors: autograd refuses a backward after an in-place change of any of them -- the record, or a weight stepped too early)
+        ctx.save_for_backward(*((states, inputs) + ((jac,) if jac is not None else ()) + tuple(tensors)))
+        return states, inputs
+
+    @staticmethod
+    def backward(ctx, g_states, g_inputs):
+        saved = ctx.saved_tensors
+        states, inputs = saved[:2]
+        jac = saved[2] if ctx.has_jac else None
+        tensors = saved[3 if ctx.has_jac else 2:]
+        gs = torch.zeros_like(states) if g_states is None else g_states.to(dtype=DT).contiguous()
+        gi = None if g_inputs is None else g_inputs.to(dtype=DT).contiguous()
+        want_x0, want_p = ctx.needs_input_grad[6], any(ctx.needs_input_grad[7:])
+        slabs, g_x0 = _rollout_mlp_sweep(ctx.model, ctx.mlp, tensors, states, inputs, jac, gs, gi, want_p, want_x0)
+        grads = [None] * len(tensors)
+        if want_p:
+            flat = slabs.sum(0)  # the workgroups' slabs added in torch's fixed order
+            o = 0
+            for i, shp in enumerate(ctx.mlp.shapes):
+                n = int(np.prod(shp))
+                if ctx.needs_input_grad[7 + i]:
+                    grads[i] = flat[o:o + n].reshape(shp)
+                o += n
+        return (None, None, None, None, None, None, g_x0) + tuple(grads)
+
+
+def rollout_mlp(model: PackedModel, mlp: PackedMLP, noise: Optional[NoiseSpec], x0, T, particle_pred=True, status=None):
+    """Closed-loop rollout under a tanh-MLP policy in ONE launch: x0 [M,S] -> states [T,M,S], inputs [T,M,U] (row T - 1 included) and the
+    status word.  ``noise``: an eps buffer [T-1,M,G] or Philox by seed / call / particle_offset (``particle_pred``), as ``rollout_pd``.
+    With gradients enabled and x0 or a parameter requiring grad the recording launch runs and backward is the fused sweep (gradients to
+    the parameters that require them and to x0); otherwise nothing is recorded.  The same states and inputs, bit for bit, either way."""
+    if not isinstance(x0, torch.Tensor) or not x0.is_cuda or any(not q.is_cuda for q in mlp.params):
+        raise RuntimeError("rollout_mlp operates on GPU memory only (x0 and the parameters must be GPU tensors); there is no CPU path")
+    T = int(T)
+    if mlp.S != model.S or mlp.U != model.U:
+        raise RuntimeError("the MLP policy is for %d states and %d inputs, the model has %d and %d" % (mlp.S, mlp.U, model.S, model.U))
+    if T < 1:
+        raise RuntimeError("the rollout needs at least one row")
+    x0c, _, _, _, noise, status = _open_operands(model, x0, None, T, None, noise, particle_pred, status)
+    tensors = [q.contiguous() for q in mlp.params]
+    if torch.is_grad_enabled() and (x0c.requires_grad or any(q.requires_grad for q in tensors)):
+        states, inputs = RolloutMLPFunction.apply(model, mlp, noise, T, bool(particle_pred), status, x0c, *tensors)
+        return states, inputs, status
+    states, inputs, _ = _rollout_mlp_launch(model, mlp, [q.detach() for q in tensors], noise, x0c.detach(), T, particle_pred, status, False)
+    return states, inputs, status
+
+
 # measurement hook (bench.py): a pair of torch.cuda.Event recorded on the launch stream right around mcp_rollout_bwd -- the adjoint sweep
 # runs inside autograd's backward, where the caller cannot bracket it.  None (the default) = nothing is recorded.  ``fwd_events``: the same
 # around mcp_rollout_fwd (operand packing + hand-off buffer reset + the rollout kernel, without the host's tensor allocations).

@@ -91,7 +91,7 @@ class MC_PILCO(torch.nn.Module):
         self._rollout_calls = 0
         self.fused_open_loop = True       # MC_PILCO.rollout's mean chain as one fused launch (False: the step loop on get_next_state)
         self.last_open_loop_fused = False  # what the last rollout() ran
-        self.fused_feedback = True        # apply_policy with a PD_controller as one fused launch (False: the step loop on get_next_state)
+        self.fused_feedback = True        # apply_policy with a PD_controller or an MLP_policy as one fused launch (False: the step loop on get_next_state)
         self.last_feedback_fused = False  # what the last apply_policy() ran for such a policy
         self.fused_step = False           # the generic loop of apply_policy steps the model with ONE launch per step (see _step_fused); False: get_next_state
         self.last_step_fused = False      # what the last apply_policy() ran in its generic loop
@@ -210,6 +210,11 @@ class MC_PILCO(torch.nn.Module):
             # Sharded: the eps buffers are drawn for the whole swarm and sliced, Philox counts by global particle; the gains' gradients
             # reach the step's all-reduce through their .grad (_cost_backward)
             return self._fused(*ops.rollout_pd(ml.packed(), pol.packed(), self._rollout_noise(T)[0], x0, T), feedback=True)
+        if (self.fused_feedback and isinstance(pol, _Policy.MLP_policy) and _has_fused_layout(ml) and pol.fusable(ml.packed(), T)
+                and self._world()[0] == 1):
+            # the closed loop under the tanh MLP, one launch (and one sweep in backward): the eps draws of _rollout_noise.  Single process
+            # only: a sharded run falls through to the refusal below
+            return self._fused(*ops.rollout_mlp(ml.packed(), pol.packed(), self._rollout_noise(T)[0], x0, T), feedback=True)
         # generic (unfused) path: any model / policy object with the reference's step interface
         self.last_status = None  # (no fused launch: the flags of an earlier fused rollout do not describe this one)
         if self._world()[0] > 1:

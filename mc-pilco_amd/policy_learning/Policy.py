@@ -11,6 +11,7 @@ Dropout noise: ``noise_mode = "philox"`` (in-kernel counter-based generator, def
 drawn exactly like ``torch.nn.functional.dropout`` draws it on the CPU -- parity with the reference).
 ``scale_factor`` (plain ``Sum_of_gaussians`` only, as in the reference) is folded into the operands handed to the kernels.
 ``flg_bias`` adds ``f_linear.bias`` (not dropped out) to the linear layer inside the kernels; its gradient comes out of the adjoint sweep.
+``MLP_policy`` (this project's own: a tanh multilayer perceptron on the same features) runs inside the fused closed loop, mcp_rollout_mlp.
 Exploration policies (Random_exploration, Sum_of_sinusoids :94-150, PD_controller :406-449) drive the simulated system once per
 trial (61-201 samples): host-side, their ``np.random`` draws in the reference's order so that a seeded launch script collects the
 same data.
@@ -140,6 +141,105 @@ class PD_controller(Policy):
         err = self.target_traj[t, :].reshape(1, -1) - states
         h = int(self.state_dim / 2)
         return self.f_squash(self.sqrt_Kp_gains ** 2 * err[:, 0:h] + self.sqrt_Kd_gains ** 2 * err[:, h:])
+
+
+class MLP_policy(Policy):
+    """Tanh multilayer perceptron (this project's own policy class; the reference has none).  Features as in
+    ``Sum_of_gaussians_with_angles``, in the order f = [x[non_angle], sin x[angle], cos x[angle]] (both lists None: f = x); then
+    h1 = tanh(W0 f + b0), optionally h2 = tanh(W1 h1 + b1), a = Wout h + bout and u = u_max tanh(a / u_max) (``flg_squash``) or u = a.
+    ``hidden_sizes``: one or two widths, each 1..64.  The parameters are separate contiguous float64 tensors in the order W0, b0, [W1, b1],
+    Wout, bout; by default the weights are randn / sqrt(fan_in) and the biases zero (``weight_init``: the tensors' values in that order).
+    ``forward`` is the torch formula.  As ``MC_PILCO``'s control policy on a GPU model with a fused layout it runs inside the fused closed
+    loop (``packed()``, ``fusable()``; ops.rollout_mlp: one launch, and the reverse-time sweep for the parameters' gradients); with
+    ``MC_PILCO.fused_feedback = False`` the same object runs the step loop.  No dropout: ``p_dropout`` is accepted and ignored."""
+
+    def __init__(self, state_dim, input_dim, hidden_sizes, angle_indices=None, non_angle_indices=None, u_max=1.0, flg_squash=True, weight_init=None,
+                 dtype=torch.float64, device=torch.device("cuda")):
+        super().__init__(state_dim=state_dim, input_dim=input_dim, flg_squash=flg_squash, u_max=u_max, dtype=dtype, device=device)
+        self.hidden_sizes = [int(h) for h in np.atleast_1d(hidden_sizes)]
+        if len(self.hidden_sizes) not in (1, 2) or any(h < 1 for h in self.hidden_sizes):
+            raise ValueError("hidden_sizes holds one or two positive widths")
+        self.angle_indices = [] if angle_indices is None else [int(i) for i in np.atleast_1d(angle_indices)]
+        self.non_angle_indices = [] if non_angle_indices is None else [int(i) for i in np.atleast_1d(non_angle_indices)]
+        self._lists = bool(self.angle_indices or self.non_angle_indices)
+        self.feature_dim = len(self.non_angle_indices) + 2 * len(self.angle_indices) if self._lists else int(state_dim)
+        widths = [self.feature_dim] + self.hidden_sizes + [int(input_dim)]
+        names = ["0", "1", "out"] if len(self.hidden_sizes) == 2 else ["0", "out"]
+        self._names = []
+        for l, n in enumerate(names):
+            self.register_parameter("W" + n, torch.nn.Parameter(torch.zeros(widths[l + 1], widths[l], dtype=dtype, device=self.device)))
+            self.register_parameter("b" + n, torch.nn.Parameter(torch.zeros(widths[l + 1], dtype=dtype, device=self.device)))
+            self._names += ["W" + n, "b" + n]
+        if weight_init is None:
+            self.reinit()
+        else:
+            if len(weight_init) != len(self._names):
+                raise ValueError("weight_init holds %d arrays: %s" % (len(self._names), ", ".join(self._names)))
+            for q, v in zip(self.mlp_parameters(), weight_init):
+                q.data.copy_(torch.as_tensor(np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v), dtype=dtype).reshape(q.shape))
+
+    def mlp_parameters(self):
+        """The parameter tensors in the order W0, b0, [W1, b1], Wout, bout (the order of mcp_rollout_mlp_bwd's slabs)."""
+        return [getattr(self, n) for n in self._names]
+
+    def reinit(self, scaling=1):
+        """Weights redrawn as scaling * randn / sqrt(fan_in), biases zero; ``draw_device`` (set by MC_PILCO in "reference" noise mode): where
+        the draws are made."""
+        ddev = getattr(self, "draw_device", None) or self.device
+        for q in self.mlp_parameters():
+            if q.dim() == 2:
+                q.data.copy_(scaling * torch.randn(q.shape, dtype=self.dtype, device=ddev).to(self.device) / np.sqrt(q.shape[1]))
+            else:
+                q.data.zero_()
+
+    def features(self, states):
+        x = states.reshape([-1, self.state_dim])
+        if not self._lists:
+            return x
+        return torch.cat([x[:, self.non_angle_indices], torch.sin(x[:, self.angle_indices]), torch.cos(x[:, self.angle_indices])], dim=1)
+
+    def forward(self, states, t=None, p_dropout=0.0):
+        h = self.features(states)
+        ps = self.mlp_parameters()
+        for l in range(len(self.hidden_sizes)):
+            h = torch.tanh(h @ ps[2 * l].t() + ps[2 * l + 1])
+        return self.f_squash(h @ ps[-2].t() + ps[-1])
+
+    def _u_max_values(self):
+        """The bounds as a tuple of floats (a scalar: one entry), or None where ``u_max`` is nothing of the kind."""
+        try:
+            u = self.u_max.detach().cpu().numpy() if isinstance(self.u_max, torch.Tensor) else self.u_max
+            return tuple(float(v) for v in np.asarray(u, dtype=np.float64).reshape(-1))
+        except (TypeError, ValueError):
+            return None
+
+    def packed(self) -> "ops.PackedMLP":
+        """mcp_mlp_policy over the LIVE parameters (rebuilt if a tensor was replaced or a setting changed)."""
+        key = tuple(q.data_ptr() for q in self.mlp_parameters()) + (self.flg_squash, self._u_max_values())
+        hit = self.__dict__.get("_packed_mlp")
+        if hit is None or hit[0] != key:
+            hit = self.__dict__["_packed_mlp"] = (key, ops.PackedMLP(self))
+        return hit[1]
+
+    def fusable(self, model, T):
+        """Whether T steps of this policy on ``model`` (an ops.PackedModel, or anything with ``S`` and ``U``) can run as the fused closed loop:
+        float64 parameters on a GPU, S and U those of the model, the index lists in range and disjoint, every width within the kernels' limits."""
+        S, U = int(self.state_dim), int(self.input_dim)
+        if int(getattr(model, "S", -1)) != S or int(getattr(model, "U", -1)) != U or U > ops.abi.MAX_INPUT or S > ops.abi.MAX_STATE or int(T) < 1:
+            return False
+        if self.dtype != torch.float64 or any(q.dtype != torch.float64 or not q.is_cuda for q in self.mlp_parameters()):
+            return False
+        idx = self.angle_indices + self.non_angle_indices
+        if any(i < 0 or i >= S for i in idx) or len(set(idx)) != len(idx):
+            return False
+        if self.feature_dim < 1 or self.feature_dim > ops.abi.MAX_PFEAT or any(h < 1 or h > ops.abi.MAX_HIDDEN for h in self.hidden_sizes):
+            return False
+        um = self._u_max_values()  # (by value: a list of bounds changed in place gives a new descriptor, a tensor on any device is read)
+        if um is None or len(um) not in (1, U) or (len(um) == 1 and not np.isscalar(self.u_max) and U != 1):
+            return False
+        if self.flg_squash and not all(v > 0 for v in um):
+            return False
+        return True
 
 
 class Sum_of_gaussians(Policy):
