@@ -431,6 +431,32 @@ int mcp_rollout_pd_meas(const mcp_model* model, const mcp_pd_policy* pd, const m
 int mcp_rollout_pd_meas_bwd(const mcp_model* model, const mcp_pd_policy* pd, const mcp_meas* meas, int M, int T, const double* states,
                             const double* inputs, const double* jac, const double* g_states, const double* g_inputs, double* g_gains,
                             double* g_x0, void* stream);
+/* mcp_rollout_mlp with the network evaluated on a SIMULATED MEASUREMENT of the state (mcp_meas, as mcp_rollout_pd_meas has it for the PD
+ * law: noisy positions, backward-difference velocities through the first-order filter; row 0 is measured true), ONE launch: the particles
+ * evolve on their true states, u_t = mlp(y_t).  Per pair i (p = pos[i], v = vel[i]) and row t >= 1: np_t = x_t[p] + std_pos[i] n_{t,i},
+ * nv_t = (np_t - np_{t-1}) / Ts, y_t[v] = (b0 nv_t + b1 nv_{t-1} - a1 y_{t-1}[v]) / a0, y_t[p] = np_t; components in no pair are seen true.
+ * n_{t,i} is meas->pos_noise [T-1][M][n] (step t at row t - 1) or Philox by (seed, call, m + particle_offset) on the stream of
+ * mcp_rollout_fwd's measurement model: a particle sees the same measurement noise whichever policy drives it.  meas->meas [T][M][S] receives
+ * y (every row; a NaN in it raises MCP_STATUS_NAN) and is what mcp_rollout_mlp_meas_bwd reads.  Ts is the model's.  Everything else --
+ * states, inputs, jac, mu / var, eps addressing, status flags, T == 1, the weights' LDS copy -- as mcp_rollout_mlp; the states carry the bits
+ * of mcp_rollout_open fed with the launch's own inputs[:T-1], and the plain launch those of the recording launch, meas->meas included.
+ * meas->n == 0: mcp_rollout_mlp itself (same kernels, same bits).  Checks in this order: a NULL pointer (meas NULL included), M <= 0,
+ * T < 1 -> MCP_ERR_ARG; MCP_MAX_* of the model -> MCP_ERR_LIMIT; the model; the descriptor as for mcp_rollout_mlp (its limits first); then
+ * MCP_ERR_ARG for a pair index out of range, pos or vel with a repeated entry, a component listed as both, n > 0 with meas->meas NULL,
+ * a0 == 0 (or NaN) or the model's Ts <= 0.  Replaces the loop of MC_PILCO4PMS.apply_policy (policy_learning/MC_PILCO.py:808-906; the
+ * measurement :856-899) with Policy.MLP_policy over Model_learning.get_next_state (model_learning/Model_learning.py:210-229, 471-494, 685-718). */
+int mcp_rollout_mlp_meas(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_meas* meas, const mcp_noise* noise, int M, int T,
+                         int particle_pred, const double* x0, double* states, double* inputs, double* mu, double* var,
+                         double* jac /* NULL: no record */, uint32_t* status, void* stream);
+/* Reverse-time sweep of mcp_rollout_mlp_meas: mcp_rollout_mlp_bwd with the activations recomputed from the measurement (meas->meas, as the
+ * forward launch wrote it), the policy's adjoint taken on the measurement and passed through the adjoint recursion of the filter -- two
+ * carries per (trajectory, pair), no atomics; g_params [ceil(M/16)][n_param] slabs and g_x0 [M][S] as there, bitwise reproducible, a slab
+ * depending on its own 16 trajectories alone.  meas->n == 0: mcp_rollout_mlp_bwd itself.  The same argument checks as the forward entry
+ * (the sweep looks at no GP operand).  Replaces autograd's backward (MC_PILCO.py:522) through MC_PILCO4PMS.apply_policy's loop
+ * (policy_learning/MC_PILCO.py:808-906), Policy.MLP_policy and the integrators (model_learning/Model_learning.py:210-229, 471-494, 685-718). */
+int mcp_rollout_mlp_meas_bwd(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_meas* meas, int M, int T, const double* states,
+                             const double* inputs, const double* jac, const double* g_states, const double* g_inputs /* may be NULL */,
+                             double* g_params, double* g_x0, void* stream);
 /* Reverse-time adjoint of the rollout: given dJ/dstates, dJ/dinputs (either may be NULL) returns
  * dJ/d{log_lengthscales [P], centers [B][P], f_linear.weight [U][B]} (overwritten, this rank's
  * particles only; with policy->bias also dJ/dbias into policy->g_bias) and optionally dJ/dx0 [M][S].  Replaces autograd's backward through

@@ -1,5 +1,5 @@
 // Shared by the rollout sources (rollout_fwd*.hip, rollout_bwd.hip, rollout_open.hip): feature maps of the dynamics model and of the
-// policy, descriptor validation (model_within_limits, model_lists_ok, model_ok, meas_pairs_disjoint, policy_ok).
+// policy, descriptor validation (model_within_limits, model_lists_ok, model_ok, meas_pairs_disjoint, meas_model_check, policy_ok).
 #pragma once
 #include <string.h>
 
@@ -103,6 +103,18 @@ static inline bool meas_pairs_disjoint(const mcp_meas* ms) {
     for (int j = 0; j < ms->n; ++j)
       if ((i != j && (ms->pos[i] == ms->pos[j] || ms->vel[i] == ms->vel[j])) || ms->pos[i] == ms->vel[j]) return false;
   return true;
+}
+
+// the measurement model of a measured feedback form (mcp_rollout_pd_meas, mcp_rollout_mlp_meas) against the model (host fields only).
+// Every component belongs to at most one pair, as position or as velocity: the forward kernels give a pair to the thread of its position,
+// the sweeps keep one filter adjoint per position component
+static inline int meas_model_check(const mcp_model* model, const mcp_meas* ms) {
+  if (ms->n < 0 || 2 * ms->n > model->S || ms->n > MCP_MAX_STATE) return MCP_ERR_ARG;
+  if (ms->n == 0) return MCP_OK;
+  if (!ms->meas || !(fabs(ms->a0) > 0.0) || !(model->Ts > 0.0)) return MCP_ERR_ARG;  // (a NaN a0 or Ts is refused too)
+  for (int i = 0; i < ms->n; ++i)
+    if (ms->pos[i] < 0 || ms->pos[i] >= model->S || ms->vel[i] < 0 || ms->vel[i] >= model->S) return MCP_ERR_ARG;
+  return meas_pairs_disjoint(ms) ? MCP_OK : MCP_ERR_ARG;
 }
 
 // policy-only evaluation (T == 1, no dynamics model): a stub model with no GPs

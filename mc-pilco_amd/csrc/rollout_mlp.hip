@@ -3,6 +3,8 @@
 // (policy_learning/MC_PILCO.py:615-674) over Model_learning.get_next_state (model_learning/Model_learning.py:210-229, 471-494, 685-718).
 //   mcp_rollout_mlp      M trajectories, T steps, ONE launch: u_t = mlp(x_t) computed in the kernel; with jac the record for the sweep
 //   mcp_rollout_mlp_bwd  the sweep: g_x0 and one partial slab of parameter gradients per workgroup of 16 trajectories
+//   mcp_rollout_mlp_meas, mcp_rollout_mlp_meas_bwd   the same pair with the network fed a simulated measurement of x_t (template PMS:
+//                        MC_PILCO4PMS.apply_policy, policy_learning/MC_PILCO.py:808-906, as mcp_rollout_pd_meas has it for the PD law)
 // The forward kernel is the step loop of rollout_open.hip's feedback form with the PD law exchanged for the network: phases S, K, V, J, J', F
 // and the noise addressing are the same functions (rollout_open_phases.h) and the same statements on the same operands, and the library is
 // built without floating-point contraction, so the states carry the bits of mcp_rollout_open fed with the launch's own inputs.  Per step
@@ -79,6 +81,23 @@ struct OpenArgsMlp : OpenArgs {
   mcp_mlp_policy mlp;  // (the index lists normalised by the host: without lists non_angle = 0 .. S - 1)
   double* inputs;      // [T][M][U]
 };
+// MEASURED form (template PMS, mcp_rollout_mlp_meas): the network reads a simulated measurement y_t of x_t -- rollout_open.hip's measured
+// feedback form with the PD law exchanged for the network.  The measurement is that form's statements, the same operations in the same order
+// (stated here a second time: as a function shared through rollout_open_phases.h they moved the register figures of rollout_open.hip's own
+// measured forms): the state thread of a measured position keeps np, nv, mv of its pair in registers and writes y[p],
+// y[v] into the row [PT][S] at L.ym; the noise addressing is the closed-loop kernels'.  The feature threads read that row instead of xs behind
+// the barrier that already publishes x_t: no barrier is added, and phases K, V, J, F see the operands they see without a measurement.
+struct OpenArgsMlpMeas : OpenArgsMlp {
+  mcp_meas ms;
+};
+template <bool PMS>
+struct MlpArgsOf {
+  typedef OpenArgsMlp type;
+};
+template <>
+struct MlpArgsOf<true> {
+  typedef OpenArgsMlpMeas type;
+};
 struct MlpActs {
   int fp, hp[2];       // row pitches of the features and of the hidden layers (odd)
   int f, h[2], w, total;  // offsets inside the form's region of the layout
@@ -109,8 +128,8 @@ __device__ __forceinline__ void mlp_layer_fwd(const double* W, const double* b, 
   }
 }
 
-template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool WLDS>
-__global__ __launch_bounds__(RF_NT) void rollout_mlp_kernel(OpenArgsMlp a) {
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool WLDS, bool PMS = false>
+__global__ __launch_bounds__(RF_NT) void rollout_mlp_kernel(typename MlpArgsOf<PMS>::type a) {
   extern __shared__ double smem[];
   const mcp_model& md = a.model;
   const mcp_mlp_policy& pl = a.mlp;
@@ -119,7 +138,7 @@ __global__ __launch_bounds__(RF_NT) void rollout_mlp_kernel(OpenArgsMlp a) {
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const MlpGeom mg = mlp_geom(pl);
   const MlpActs A = mlp_acts(PT, pl, mg, WLDS);
-  const OpenLayout L = open_layout(PT, NEEDVAR, S, D, G, a.NpadMax, NEEDJAC, a.na, false, A.total);
+  const OpenLayout L = open_layout(PT, NEEDVAR, S, D, G, a.NpadMax, NEEDJAC, a.na, PMS, A.total);
   double* xs = smem + L.xs;
   double* z = smem + L.z;
   double* red = smem + L.red;  // [2][G][RF_NW][PT]
@@ -192,6 +211,22 @@ __global__ __launch_bounds__(RF_NT) void rollout_mlp_kernel(OpenArgsMlp a) {
   const double* hlL = nh > 1 ? hl1 : hl0;
   // (the output layer's place in the LDS copy, picked here: no table is indexed by a run-time layer number inside the loop)
   const int wlo = nh > 1 ? mg.wl[2] : mg.wl[1], blo = nh > 1 ? mg.bl[2] : mg.bl[1], pto = nh > 1 ? mg.pitch[2] : mg.pitch[1];
+  // measured form: the pair of this state component (as in rollout_open_kernel)
+  int pm_pos = -1, pm_vel = -1, pm_vc = 0;
+  double pm_std = 0.0, pm_np = 0.0, pm_nv = 0.0, pm_mv = 0.0;
+  if constexpr (PMS) {
+    if (own) {
+      for (int i = 0; i < a.ms.n; ++i) {
+        if (a.ms.vel[i] == os) pm_vel = i;
+        if (a.ms.pos[i] == os) {
+          pm_pos = i;
+          pm_vc = a.ms.vel[i];
+          pm_std = a.ms.std_pos[i];
+        }
+      }
+      if (pm_pos >= 0) pm_nv = pm_mv = a.x0[(size_t)om * S + pm_vc];
+    }
+  }
   lds_barrier();
 
   for (int t = 0; t < T; ++t) {
@@ -203,10 +238,39 @@ __global__ __launch_bounds__(RF_NT) void rollout_mlp_kernel(OpenArgsMlp a) {
         if (is_bad(xn)) bad |= MCP_STATUS_NAN;
       }
     }
-    // ---- u_t = mlp(x_t) from the row just published (every row, the last one included: it is stored, and a cost may read it) ----
+    if constexpr (PMS) {  // y_t: the measurement of the row just formed (MC_PILCO.py:856-899)
+      if (own && pm_vel < 0) {
+        double* yr = smem + L.ym + op * S;
+        double npos = xn, mv = 0.0;
+        if (pm_pos >= 0) {
+          if (t == 0) {
+            mv = pm_mv;  // (row 0: the true velocity, which also starts both histories)
+          } else {
+            const double nn = a.ms.pos_noise ? a.ms.pos_noise[((size_t)(t - 1) * M + om) * a.ms.n + pm_pos]
+                                             : philox_normal(nzl, om, t, pm_pos, MCP_STREAM_POS);
+            npos = fma(pm_std, nn, xn);
+            const double nv = (npos - pm_np) / Ts;
+            mv = (a.ms.b0 * nv + a.ms.b1 * pm_nv - a.ms.a1 * pm_mv) / a.ms.a0;
+            pm_nv = nv;
+            pm_mv = mv;
+          }
+          pm_np = npos;
+          yr[pm_vc] = mv;
+        }
+        yr[os] = npos;
+        if (ovalid) {
+          double* mr = a.ms.meas + ((size_t)t * M + m0 + op) * S;
+          mr[os] = npos;
+          if (pm_pos >= 0) mr[pm_vc] = mv;
+          if (is_bad(npos) || is_bad(mv)) bad |= MCP_STATUS_NAN;
+        }
+      }
+    }
+    // ---- u_t = mlp(x_t) -- measured form: mlp(y_t) -- from the row just published (every row, the last one included: it is stored, and a
+    // cost may read it).  The measurement row has one buffer: the feature threads read it here, its next writers are behind the barriers below
     lds_barrier();
     if (isf) {
-      const double xv = xs[cur * PT * S + fq * S + fsrc];
+      const double xv = PMS ? smem[L.ym + fq * S + fsrc] : xs[cur * PT * S + fq * S + fsrc];
       double* fr = fl + fq * A.fp;
       if (fi < nnp) {
         fr[fi] = xv;
@@ -384,65 +448,88 @@ static mcp_mlp_policy mlp_normalised(const mcp_mlp_policy* p) {
 
 // ---- host path of the forward entry: checks -> fill -> ladder -----------------------------------------------------------------------------
 // one rung: the weights in LDS where the layout then fits, else in global memory; MCP_ERR_LIMIT where the rung does not fit at all
-template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool WLDS>
-static int launch_mlp_w(const OpenArgsMlp& a, hipStream_t st) {
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool WLDS, bool PMS>
+static int launch_mlp_w(const typename MlpArgsOf<PMS>::type& a, hipStream_t st) {
   const MlpActs A = mlp_acts(PT, a.mlp, mlp_geom(a.mlp), WLDS);
-  const OpenLayout L = open_layout(PT, NEEDVAR, a.model.S, a.model.D, a.model.G, a.NpadMax, NEEDJAC, a.na, false, A.total);
+  const OpenLayout L = open_layout(PT, NEEDVAR, a.model.S, a.model.D, a.model.G, a.NpadMax, NEEDJAC, a.na, PMS, A.total);
   const size_t lds = (size_t)L.total * sizeof(double);
   if (lds > MCP_LDS_LIMIT) return MCP_ERR_LIMIT;
-  MCP_ENSURE_MAX_LDS((rollout_mlp_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, WLDS>));
-  hipLaunchKernelGGL((rollout_mlp_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, WLDS>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
+  MCP_ENSURE_MAX_LDS((rollout_mlp_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, WLDS, PMS>));
+  hipLaunchKernelGGL((rollout_mlp_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, WLDS, PMS>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
 }
-template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC>
-static int launch_mlp(const OpenArgsMlp& a, hipStream_t st) {
-  const int rc = launch_mlp_w<PT, MAXDEG, NEEDVAR, NEEDJAC, true>(a, st);
-  return rc == MCP_ERR_LIMIT ? launch_mlp_w<PT, MAXDEG, NEEDVAR, NEEDJAC, false>(a, st) : rc;
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool PMS>
+static int launch_mlp(const typename MlpArgsOf<PMS>::type& a, hipStream_t st) {
+  const int rc = launch_mlp_w<PT, MAXDEG, NEEDVAR, NEEDJAC, true, PMS>(a, st);
+  return rc == MCP_ERR_LIMIT ? launch_mlp_w<PT, MAXDEG, NEEDVAR, NEEDJAC, false, PMS>(a, st) : rc;
 }
-template <int PT, bool NEEDVAR, bool NEEDJAC>
-static int launch_mlp_deg(const OpenArgsMlp& a, int maxdeg, hipStream_t st) {
-  return maxdeg == 0 ? launch_mlp<PT, 0, NEEDVAR, NEEDJAC>(a, st) : launch_mlp<PT, 2, NEEDVAR, NEEDJAC>(a, st);
+template <int PT, bool NEEDVAR, bool NEEDJAC, bool PMS>
+static int launch_mlp_deg(const typename MlpArgsOf<PMS>::type& a, int maxdeg, hipStream_t st) {
+  return maxdeg == 0 ? launch_mlp<PT, 0, NEEDVAR, NEEDJAC, PMS>(a, st) : launch_mlp<PT, 2, NEEDVAR, NEEDJAC, PMS>(a, st);
 }
 // The ladder of tiles of rollout_open.hip's launch_open_tiles (at every compiled limit at once the one-trajectory recording rung takes
-// 85 KB + 1.3 KB of activations: nothing within the limits is refused), entered one rung lower by SMALL SWARMS: up to MLP_SMALL_SWARM
-// trajectories start at 4 per workgroup.  Measured (profiles/NOTES.md part T): the time of a launch is the time of ONE tile's T steps for as
+// 85 KB + 1.3 KB of activations, the measured form one row [PT][S] more: nothing within the limits is refused), entered one rung lower
+// by SMALL SWARMS: up to MLP_SMALL_SWARM trajectories start at 4 per workgroup.  Measured (profiles/NOTES.md part T): the time of a launch is the time of ONE tile's T steps for as
 // long as every tile has a compute unit of its own, whatever M, and a tile of 4 takes 0.82x (UR5 shape) / 0.86x (arm shape) the time of a
 // tile of 16 -- the Kinv stream and the MFMAs of phases V and J do not depend on the width, phase K does.  Tiles of 4 have a compute unit
 // each up to M = 4 x 256 = 1024; at M = 1536 they take two rounds and twice the time, and tiles of 16 (96 workgroups) win again.  The tile
 // width changes no bit of a trajectory (a column of phases K, V, J is computed the same way in every width: the identities with
 // mcp_rollout_open hold across the rungs).
 #define MLP_SMALL_SWARM 1024  // 4 trajectories x the 256 compute units of the MI355X
-static int launch_mlp_tiles(const OpenArgsMlp& a, int maxdeg, bool wantvar, hipStream_t st) {
+template <bool PMS>
+static int launch_mlp_tiles(const typename MlpArgsOf<PMS>::type& a, int maxdeg, bool wantvar, hipStream_t st) {
   const bool small = a.M <= MLP_SMALL_SWARM;
   if (!a.jac) {
-    if (!a.sample && !wantvar) return launch_mlp_deg<1, false, false>(a, maxdeg, st);
-    int rc = small ? MCP_ERR_LIMIT : launch_mlp_deg<16, true, false>(a, maxdeg, st);
-    if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<4, true, false>(a, maxdeg, st);
+    if (!a.sample && !wantvar) return launch_mlp_deg<1, false, false, PMS>(a, maxdeg, st);
+    int rc = small ? MCP_ERR_LIMIT : launch_mlp_deg<16, true, false, PMS>(a, maxdeg, st);
+    if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<4, true, false, PMS>(a, maxdeg, st);
     return rc;
   }
-  if (!a.sample && !wantvar) return launch_mlp_deg<1, false, true>(a, maxdeg, st);
-  int rc = small ? MCP_ERR_LIMIT : launch_mlp_deg<16, true, true>(a, maxdeg, st);
-  if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<4, true, true>(a, maxdeg, st);
-  if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<1, true, true>(a, maxdeg, st);
+  if (!a.sample && !wantvar) return launch_mlp_deg<1, false, true, PMS>(a, maxdeg, st);
+  int rc = small ? MCP_ERR_LIMIT : launch_mlp_deg<16, true, true, PMS>(a, maxdeg, st);
+  if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<4, true, true, PMS>(a, maxdeg, st);
+  if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<1, true, true, PMS>(a, maxdeg, st);
   return rc;
 }
 
-extern "C" int mcp_rollout_mlp(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_noise* noise, int M, int T, int particle_pred,
-                               const double* x0, double* states, double* inputs, double* mu, double* var, double* jac, uint32_t* status,
-                               void* stream) {
+// what mcp_rollout_mlp and mcp_rollout_mlp_meas share (ms NULL: no measurement)
+static int mlp_dispatch(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_meas* ms, const mcp_noise* noise, int M, int T, int particle_pred,
+                        const double* x0, double* states, double* inputs, double* mu, double* var, double* jac, uint32_t* status, void* stream) {
   if (!model || !mlp || !noise || !x0 || !states || !inputs || !status) return MCP_ERR_ARG;
   if (M <= 0 || T < 1) return MCP_ERR_ARG;
   if (!model_within_limits(model)) return MCP_ERR_LIMIT;
   if (!model_ok(model)) return MCP_ERR_ARG;
   const int crc = mlp_policy_check(model, mlp);
   if (crc != MCP_OK) return crc;
-  OpenArgsMlp a;
+  const int mrc = ms ? meas_model_check(model, ms) : MCP_OK;
+  if (mrc != MCP_OK) return mrc;
+  OpenArgsMlpMeas a;
   if (T == 1) jac = nullptr;  // the policy alone: no transition, nothing to record
   const int maxdeg = open_fill(a, model, noise, M, T, particle_pred, x0, nullptr, M, nullptr, states, mu, var, jac, status);
   a.mlp = mlp_normalised(mlp);
   a.inputs = inputs;
-  return launch_mlp_tiles(a, maxdeg, var != nullptr, (hipStream_t)stream);
+  hipStream_t st = (hipStream_t)stream;
+  if (!ms || ms->n == 0) return launch_mlp_tiles<false>(a, maxdeg, var != nullptr, st);  // (the base part of `a`: mcp_rollout_mlp's own kernels)
+  a.ms = *ms;
+  return launch_mlp_tiles<true>(a, maxdeg, var != nullptr, st);
+}
+
+extern "C" int mcp_rollout_mlp(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_noise* noise, int M, int T, int particle_pred,
+                               const double* x0, double* states, double* inputs, double* mu, double* var, double* jac, uint32_t* status,
+                               void* stream) {
+  return mlp_dispatch(model, mlp, nullptr, noise, M, T, particle_pred, x0, states, inputs, mu, var, jac, status, stream);
+}
+
+// Closed-loop rollout under the network evaluated on a simulated measurement: replaces the loop of MC_PILCO4PMS.apply_policy
+// (policy_learning/MC_PILCO.py:808-906: noisy positions, backward-difference velocities, the first-order filter) with Policy.MLP_policy as
+// the policy, over Model_learning.get_next_state (model_learning/Model_learning.py:210-229, 471-494, 685-718).  meas->n == 0:
+// mcp_rollout_mlp's kernels on the same arguments.
+extern "C" int mcp_rollout_mlp_meas(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_meas* meas, const mcp_noise* noise, int M, int T,
+                                    int particle_pred, const double* x0, double* states, double* inputs, double* mu, double* var, double* jac,
+                                    uint32_t* status, void* stream) {
+  if (!meas) return MCP_ERR_ARG;
+  return mlp_dispatch(model, mlp, meas, noise, M, T, particle_pred, x0, states, inputs, mu, var, jac, status, stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -462,6 +549,16 @@ extern "C" int mcp_rollout_mlp(const mcp_model* model, const mcp_mlp_policy* mlp
 // deltas, one workgroup barrier per row.  Where 16 trajectories of that do not fit the LDS the workgroup sweeps its 16 trajectories in
 // parts of 8 / 4 / 2 / 1, one after the other, the sums staying in the registers: a slab is still one workgroup's.  No atomics; the order
 // of every sum is fixed by the shape alone.
+// MEASURED form (template PMS, mcp_rollout_mlp_meas_bwd): the forward's network read y_r (ms.meas), so the workers recompute the activations
+// from ms.meas[r - 1] -- the forward's operands, the forward's bits -- and stage C takes fbar through the feature map at y_r: the policy's pull ON
+// THE MEASUREMENT,   ybar_r[s] = fbar[i] (s = non_angle[i])  |  cos y fbar[sin_i] - sin y fbar[cos_i]  (s = angle[i]; sin y, cos y are the
+// activation row's own entries, so no row of the measurement is held in LDS).  It reaches lambda through the adjoint of the filter exactly
+// as in rollout_open_bwd_kernel<true, true> (rollout_open.hip): two carries per (trajectory, pair), zero behind the last row, kept in LDS at
+// the pair's position component and zeroed at the start of every part (the same lane writes and reads them, row after row):
+//   mvbar_r = ybar_r[v] - (a1/a0) mvbar_{r+1};   nvbar_r = (b0/a0) mvbar_r + (b1/a0) mvbar_{r+1}
+//   r >= 1: lambda_r[p] += ybar_r[p] + (nvbar_r - nvbar_{r+1}) / Ts           (the true velocity of a later row gets nothing from the policy)
+//   r == 0: lambda_0[p] += ybar_0[p] - nvbar_1 / Ts;   lambda_0[v] += ybar_0[v] + ((b1 - a1)/a0) mvbar_1         (row 0 is measured true)
+// A component in no pair gets ybar_r[s] directly.  The slabs, the order of every sum and the parts are those of the plain form.
 // ---------------------------------------------------------------------------------------
 #define MB_PT 16
 #define MB_NT 512
@@ -487,12 +584,26 @@ struct MlpBwdArgs {
   int wlds;
 };
 
+struct MlpBwdArgsMeas : MlpBwdArgs {
+  mcp_meas ms;
+};
+template <bool PMS>
+struct MlpBwdArgsOf {
+  typedef MlpBwdArgs type;
+};
+template <>
+struct MlpBwdArgsOf<true> {
+  typedef MlpBwdArgsMeas type;
+};
+
 struct MlpBwdLayout {
   int rec, xs, gs, lam, gd, gz, tab, ul, gul, fbar, act, del, w, total;  // offsets in doubles
+  int car, mtab;               // measured form: the filter's carries | pvel, ppos
   int rp, fp, ap, dp;          // pitches: record row | fbar row | activation row | delta row (odd)
   int aoff[3], one, doff[3];   // inside an activation row: the input of layer l, the constant 1; inside a delta row: the output of layer l
 };
-__host__ __device__ inline MlpBwdLayout mlp_bwd_layout(int pts, int S, int U, int G, int D, const mcp_mlp_policy& p, const MlpGeom& g, bool wlds) {
+__host__ __device__ inline MlpBwdLayout mlp_bwd_layout(int pts, int S, int U, int G, int D, const mcp_mlp_policy& p, const MlpGeom& g, bool wlds,
+                                                       bool pms = false) {
   MlpBwdLayout L;
   int o = 0;
   auto take = [&](int n) {
@@ -525,6 +636,8 @@ __host__ __device__ inline MlpBwdLayout mlp_bwd_layout(int pts, int S, int U, in
   L.fbar = take(pts * L.fp);
   L.act = take(3 * pts * L.ap);
   L.del = take(2 * pts * L.dp);
+  L.car = pms ? take(2 * pts * S) : 0;     // [trajectory][position component]: mvbar | nvbar of the row behind
+  L.mtab = pms ? take(MCP_MAX_STATE) : 0;  // ints: pvel (per state component: the velocity of the pair it is the position of, or -1) | ppos (the converse)
   L.w = o;
   L.total = o + (wlds ? g.lds : 0);
   return L;
@@ -544,14 +657,24 @@ __device__ __forceinline__ void mlp_back(const double* W, int pitch, int nin, in
   }
 }
 
-template <bool WLDS>
-__global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(MlpBwdArgs a) {
+// the rows the forward's network read: the states, in the measured form the measurements
+template <bool PMS>
+__device__ __forceinline__ const double* mlp_policy_rows(const typename MlpBwdArgsOf<PMS>::type& a) {
+  if constexpr (PMS) {
+    return a.ms.meas;
+  } else {
+    return a.states;
+  }
+}
+
+template <bool WLDS, bool PMS = false>
+__global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdArgsOf<PMS>::type a) {
   extern __shared__ double smem[];
   const mcp_mlp_policy& pl = a.mlp;
   const int S = a.S, U = a.U, G = a.G, D = a.D, M = a.M, T = a.T, nna = a.nna, na = a.na, pts = a.pts;
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const MlpGeom mg = mlp_geom(pl);
-  const MlpBwdLayout L = mlp_bwd_layout(pts, S, U, G, D, pl, mg, WLDS);
+  const MlpBwdLayout L = mlp_bwd_layout(pts, S, U, G, D, pl, mg, WLDS, PMS);
   const int GD = G * D, RP = L.rp;
   double* rec = smem + L.rec;
   double* xsl = smem + L.xs;
@@ -572,6 +695,9 @@ __global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(MlpBwdArgs a) {
   double* fbar = smem + L.fbar;
   double* act = smem + L.act;
   double* del = smem + L.del;
+  double* car = smem + L.car;  // (measured form)
+  int* pvel = reinterpret_cast<int*>(smem + L.mtab);
+  int* ppos = pvel + MCP_MAX_STATE;
   double* wlc = smem + L.w;
   const int nnp = pl.n_non_angle, nap = pl.n_angle, nl = mg.nl;
   // the weights as this kernel reads them (WLDS: the LDS copy, else global memory); the layer loops below are unrolled over the three
@@ -611,6 +737,15 @@ __global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(MlpBwdArgs a) {
     zang[s] = za;
     fplain[s] = fpl;
     fang[s] = fan;
+    if constexpr (PMS) {
+      int pv = -1, pp = -1;
+      for (int i = 0; i < a.ms.n; ++i) {
+        if (a.ms.pos[i] == s) pv = a.ms.vel[i];
+        if (a.ms.vel[i] == s) pp = a.ms.pos[i];
+      }
+      pvel[s] = pv;
+      ppos[s] = pp;
+    }
   }
   // a worker thread's entries of the parameter vector: where their delta and their activation sit in a row; the running sums
   const int wt = tid - 128;
@@ -639,11 +774,12 @@ __global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(MlpBwdArgs a) {
   }
   const int ww = wv - 2;  // worker wave 0..5
 
-  // the activations of row r of this part's trajectories, worker wave `ww`: a trajectory per wave and turn
+  // the activations of row r of this part's trajectories, worker wave `ww`: a trajectory per wave and turn (from what the forward's network
+  // read: the state, in the measured form the measurement)
   auto activations = [&](int r, int mp0) {
     double* ab = act + (r % 3) * pts * L.ap;
     for (int p = ww; p < pts; p += 6) {
-      const double* xr = a.states + ((size_t)r * M + imin(mp0 + p, M - 1)) * S;
+      const double* xr = mlp_policy_rows<PMS>(a) + ((size_t)r * M + imin(mp0 + p, M - 1)) * S;
       double* A = ab + p * L.ap;
       if (lane < nnp + nap) {
         if (lane < nnp) {
@@ -705,6 +841,8 @@ __global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(MlpBwdArgs a) {
     if (part > 0) __syncthreads();
     if (tid >= 64 && tid < 64 + pts) lenl[tid - 64] = mp0 + tid - 64 < M ? T : 0;
     for (int it = tid; it < 2 * pts * S; it += MB_NT) lam[it] = 0.0;
+    if constexpr (PMS)
+      for (int it = tid; it < 2 * pts * S; it += MB_NT) car[it] = 0.0;
     __syncthreads();
     int b = 0, lc = 0;
     if (wv == 1) load_row(T - 1, 0, lane, mp0);
@@ -797,9 +935,36 @@ __global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(MlpBwdArgs a) {
               v += gzl[p * D + nna + zang[s]] * cs - gzl[p * D + nna + na + zang[s]] * sn;
             }
           }
-          if (r <= len - 1) {
-            if (fplain[s] >= 0) v += fb[fplain[s]];
-            if (fang[s] >= 0) v += fb[nnp + fang[s]] * Ar[nnp + nap + fang[s]] - fb[nnp + nap + fang[s]] * Ar[nnp + fang[s]];
+          if constexpr (!PMS) {
+            if (r <= len - 1) {
+              if (fplain[s] >= 0) v += fb[fplain[s]];
+              if (fang[s] >= 0) v += fb[nnp + fang[s]] * Ar[nnp + nap + fang[s]] - fb[nnp + nap + fang[s]] * Ar[nnp + fang[s]];
+            }
+          } else if (r <= len - 1) {
+            auto ybar = [&](int c) {  // the policy's pull on component c of the measurement
+              double y = 0.0;
+              if (fplain[c] >= 0) y += fb[fplain[c]];
+              if (fang[c] >= 0) y += fb[nnp + fang[c]] * Ar[nnp + nap + fang[c]] - fb[nnp + nap + fang[c]] * Ar[nnp + fang[c]];
+              return y;
+            };
+            const int pv = pvel[s], pp = ppos[s];
+            if (pv >= 0) {  // a measured position: the filter's adjoint of its pair
+              double* cr = car + (p * S + s) * 2;
+              const double mvn = cr[0], nvn = cr[1];
+              if (r >= 1) {
+                const double mvb = ybar(pv) - (a.ms.a1 / a.ms.a0) * mvn;
+                const double nvb = (a.ms.b0 / a.ms.a0) * mvb + (a.ms.b1 / a.ms.a0) * mvn;
+                v += ybar(s) + (nvb - nvn) / a.Ts;
+                cr[0] = mvb;
+                cr[1] = nvb;
+              } else {
+                v += ybar(s) - nvn / a.Ts;
+              }
+            } else if (pp >= 0) {  // a measured velocity: seen true in row 0 only, where it also started both histories
+              if (r == 0) v += ybar(s) + ((a.ms.b1 - a.ms.a1) / a.ms.a0) * car[(p * S + pp) * 2];
+            } else {
+              v += ybar(s);
+            }
           }
           lamn[s] = v;
         }
@@ -827,17 +992,28 @@ __global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(MlpBwdArgs a) {
   }
 }
 
-extern "C" int mcp_rollout_mlp_bwd(const mcp_model* model, const mcp_mlp_policy* mlp, int M, int T, const double* states, const double* inputs,
-                                   const double* jac, const double* g_states, const double* g_inputs, double* g_params, double* g_x0,
-                                   void* stream) {
+// what mcp_rollout_mlp_bwd and mcp_rollout_mlp_meas_bwd share (ms NULL: no measurement)
+template <bool WLDS, bool PMS>
+static int launch_mlp_bwd(const typename MlpBwdArgsOf<PMS>::type& a, size_t lds, hipStream_t st) {
+  MCP_ENSURE_MAX_LDS((rollout_mlp_bwd_kernel<WLDS, PMS>));
+  hipLaunchKernelGGL((rollout_mlp_bwd_kernel<WLDS, PMS>), dim3((a.M + MB_PT - 1) / MB_PT), dim3(MB_NT), lds, st, a);
+  MCP_LAUNCH_CHECK();
+  return MCP_OK;
+}
+static int mlp_bwd_dispatch(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_meas* ms, int M, int T, const double* states,
+                            const double* inputs, const double* jac, const double* g_states, const double* g_inputs, double* g_params, double* g_x0,
+                            void* stream) {
   if (!model || !mlp || !states || !inputs || !g_states || (!jac && T > 1)) return MCP_ERR_ARG;
   if (M <= 0 || T < 1) return MCP_ERR_ARG;
   if (!model_within_limits(model, false)) return MCP_ERR_LIMIT;
   if (!model_lists_ok(model)) return MCP_ERR_ARG;
   const int crc = mlp_policy_check(model, mlp);
   if (crc != MCP_OK) return crc;
+  const int mrc = ms ? meas_model_check(model, ms) : MCP_OK;
+  if (mrc != MCP_OK) return mrc;
   if (!g_x0 && !g_params) return MCP_OK;  // nothing asked for
-  MlpBwdArgs a;
+  const bool pms = ms && ms->n > 0;
+  MlpBwdArgsMeas a;
   memset(&a, 0, sizeof(a));
   a.S = model->S, a.U = model->U, a.G = model->G, a.D = model->D, a.nna = model->n_not_angle, a.na = model->n_angle, a.M = M, a.T = T;
   for (int i = 0; i < MCP_MAX_STATE; ++i) a.angle[i] = model->angle[i], a.not_angle[i] = model->not_angle[i];
@@ -845,24 +1021,35 @@ extern "C" int mcp_rollout_mlp_bwd(const mcp_model* model, const mcp_mlp_policy*
   a.Ts = model->Ts;
   a.states = states, a.inputs = inputs, a.jac = jac, a.g_states = g_states, a.g_inputs = g_inputs, a.g_x0 = g_x0, a.g_params = g_params;
   a.mlp = mlp_normalised(mlp);
+  if (pms) a.ms = *ms;
   // the part of the tile swept at once: the largest whose layout fits, the weights in LDS where they then fit too
   const MlpGeom mg = mlp_geom(a.mlp);
   size_t lds = 0;
   for (int pts = MB_PT; pts >= 1 && !a.pts; pts >>= 1)
     for (int wl = 1; wl >= 0 && !a.pts; --wl) {
-      const MlpBwdLayout L = mlp_bwd_layout(pts, a.S, a.U, a.G, a.D, a.mlp, mg, wl != 0);
+      const MlpBwdLayout L = mlp_bwd_layout(pts, a.S, a.U, a.G, a.D, a.mlp, mg, wl != 0, pms);
       lds = (size_t)L.total * sizeof(double);
       if (lds <= MCP_LDS_LIMIT) a.pts = pts, a.wlds = wl;
     }
   if (!a.pts) return MCP_ERR_LIMIT;  // (not reached within the compiled limits: one trajectory takes 22 KB at all of them at once)
-  const dim3 grid((M + MB_PT - 1) / MB_PT);
-  if (a.wlds) {
-    MCP_ENSURE_MAX_LDS((rollout_mlp_bwd_kernel<true>));
-    hipLaunchKernelGGL((rollout_mlp_bwd_kernel<true>), grid, dim3(MB_NT), lds, (hipStream_t)stream, a);
-  } else {
-    MCP_ENSURE_MAX_LDS((rollout_mlp_bwd_kernel<false>));
-    hipLaunchKernelGGL((rollout_mlp_bwd_kernel<false>), grid, dim3(MB_NT), lds, (hipStream_t)stream, a);
-  }
-  MCP_LAUNCH_CHECK();
-  return MCP_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (pms) return a.wlds ? launch_mlp_bwd<true, true>(a, lds, st) : launch_mlp_bwd<false, true>(a, lds, st);
+  return a.wlds ? launch_mlp_bwd<true, false>(a, lds, st) : launch_mlp_bwd<false, false>(a, lds, st);  // (the base part of `a`: mcp_rollout_mlp_bwd's own kernels)
+}
+
+extern "C" int mcp_rollout_mlp_bwd(const mcp_model* model, const mcp_mlp_policy* mlp, int M, int T, const double* states, const double* inputs,
+                                   const double* jac, const double* g_states, const double* g_inputs, double* g_params, double* g_x0,
+                                   void* stream) {
+  return mlp_bwd_dispatch(model, mlp, nullptr, M, T, states, inputs, jac, g_states, g_inputs, g_params, g_x0, stream);
+}
+
+// Reverse-time sweep of the closed loop under the network on the simulated measurement: replaces autograd's backward (MC_PILCO.py:522)
+// through the loop of MC_PILCO4PMS.apply_policy (policy_learning/MC_PILCO.py:808-906, the filter recursion included), Policy.MLP_policy and
+// get_next_state with its integrators (model_learning/Model_learning.py:210-229, 471-494, 685-718), from the record and meas->meas alone.
+// meas->n == 0: mcp_rollout_mlp_bwd's kernels.
+extern "C" int mcp_rollout_mlp_meas_bwd(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_meas* meas, int M, int T, const double* states,
+                                        const double* inputs, const double* jac, const double* g_states, const double* g_inputs, double* g_params,
+                                        double* g_x0, void* stream) {
+  if (!meas) return MCP_ERR_ARG;
+  return mlp_bwd_dispatch(model, mlp, meas, M, T, states, inputs, jac, g_states, g_inputs, g_params, g_x0, stream);
 }

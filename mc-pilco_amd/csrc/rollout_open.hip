@@ -6,7 +6,7 @@
 //   measured feedback  mcp_rollout_pd_meas      the PD law on a simulated measurement of x_t (struct OpenArgsPdMeas); mcp_rollout_pd_meas_bwd
 // All forward forms are one kernel template, rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, FB, PMS>, the three sweeps one,
 // rollout_open_bwd_kernel<FB, PMS>.  The host path is the same for every entry point: checks (rollout_common.h: model_within_limits,
-// model_ok / model_lists_ok, meas_pairs_disjoint; here: pd_policy_check, pd_meas_check), one fill of the arguments' base part per direction
+// model_ok / model_lists_ok, meas_model_check; here: pd_policy_check), one fill of the arguments' base part per direction
 // (open_fill, open_bwd_fill), one ladder of tiles (launch_open_tiles) -- a refused call makes no HIP call.
 //
 // The open-loop form replaces the step loop of MC_PILCO.rollout (policy_learning/MC_PILCO.py:347-373) over Model_learning.get_next_state
@@ -405,17 +405,6 @@ extern "C" int mcp_rollout_open_rec(const mcp_model* model, const mcp_noise* noi
 }
 
 // ---- feedback form: checks, entry -------------------------------------------------------------------------------------------------------
-// the measurement model against the model (host fields only).  Every component belongs to at most one pair, as position or as velocity:
-// the forward kernel gives a pair to the thread of its position, the sweep keeps one filter adjoint per position component
-static int pd_meas_check(const mcp_model* model, const mcp_meas* ms) {
-  if (ms->n < 0 || 2 * ms->n > model->S || ms->n > MCP_MAX_STATE) return MCP_ERR_ARG;
-  if (ms->n == 0) return MCP_OK;
-  if (!ms->meas || !(fabs(ms->a0) > 0.0) || !(model->Ts > 0.0)) return MCP_ERR_ARG;  // (a NaN a0 or Ts is refused too)
-  for (int i = 0; i < ms->n; ++i)
-    if (ms->pos[i] < 0 || ms->pos[i] >= model->S || ms->vel[i] < 0 || ms->vel[i] >= model->S) return MCP_ERR_ARG;
-  return meas_pairs_disjoint(ms) ? MCP_OK : MCP_ERR_ARG;
-}
-
 // the descriptor against the model and the horizon (host fields only: the gains and the target are device memory).  pos / vel hold distinct
 // components each: the sweep keeps one input per state component and role
 static int pd_policy_check(const mcp_model* model, const mcp_pd_policy* pd, int T) {
@@ -433,7 +422,7 @@ static int pd_policy_check(const mcp_model* model, const mcp_pd_policy* pd, int 
 static int pd_checks(const mcp_model* model, const mcp_pd_policy* pd, const mcp_meas* ms, int T) {
   const int prc = pd_policy_check(model, pd, T);
   if (prc != MCP_OK) return prc;
-  return ms ? pd_meas_check(model, ms) : MCP_OK;
+  return ms ? meas_model_check(model, ms) : MCP_OK;
 }
 
 // Closed-loop rollout under the PD law: replaces the loop of MC_PILCO.apply_policy (policy_learning/MC_PILCO.py:615-674) with

@@ -834,38 +834,57 @@ class PackedMLP:
         return c
 
 
-def _rollout_mlp_launch(model, mlp, tensors, noise, x0, T, particle_pred, status, record):
+def _rollout_mlp_launch(model, mlp, tensors, noise, x0, T, particle_pred, status, record, meas=None):
     M, dev = int(x0.shape[0]), model.device
     states, inputs, jac = _record_buffers(dev, T, M, model.S, model.U, model.G, model.D, record and T > 1)
     pc, nz = mlp.to_c(tensors), noise.to_c()
-    abi.check(abi.lib().mcp_rollout_mlp(_mc(model), C.byref(pc), C.byref(nz), M, T, int(bool(particle_pred)), abi.ptr(x0), abi.ptr(states),
-                                        abi.ptr(inputs), None, None, abi.ptr(jac), abi.ptr(status), abi.stream()), "mcp_rollout_mlp")
+    if meas is None:
+        abi.check(abi.lib().mcp_rollout_mlp(_mc(model), C.byref(pc), C.byref(nz), M, T, int(bool(particle_pred)), abi.ptr(x0), abi.ptr(states),
+                                            abi.ptr(inputs), None, None, abi.ptr(jac), abi.ptr(status), abi.stream()), "mcp_rollout_mlp")
+        return states, inputs, jac
+    meas_buf = meas.measured = torch.empty(T, M, model.S, dtype=DT, device=dev)  # (allocated as _rollout_pd_launch allocates it)
+    mc = abi.Meas()
+    meas.fill(mc, T, M, meas_buf)
+    abi.check(abi.lib().mcp_rollout_mlp_meas(_mc(model), C.byref(pc), C.byref(mc), C.byref(nz), M, T, int(bool(particle_pred)), abi.ptr(x0),
+                                             abi.ptr(states), abi.ptr(inputs), None, None, abi.ptr(jac), abi.ptr(status), abi.stream()),
+              "mcp_rollout_mlp_meas")
     return states, inputs, jac
 
 
-def _rollout_mlp_sweep(model, mlp, tensors, states, inputs, jac, g_states, g_inputs, want_params, want_x0):
-    """(g_params slabs [ceil(M/16), n_param] or None, g_x0 [M,S] or None) of mcp_rollout_mlp_bwd."""
+def _rollout_mlp_sweep(model, mlp, tensors, states, inputs, jac, g_states, g_inputs, want_params, want_x0, meas=None, meas_buf=None):
+    """(g_params slabs [ceil(M/16), n_param] or None, g_x0 [M,S] or None) of mcp_rollout_mlp_bwd; with ``meas`` (and the measured states
+    ``meas_buf`` its forward launch wrote) of mcp_rollout_mlp_meas_bwd."""
     T, M, dev = int(states.shape[0]), int(states.shape[1]), states.device
     g_x0 = torch.empty(M, model.S, dtype=DT, device=dev) if want_x0 else None
     slabs = torch.empty((M + 15) // 16, mlp.n_param, dtype=DT, device=dev) if want_params else None
     pc = mlp.to_c(tensors)
-    abi.check(abi.lib().mcp_rollout_mlp_bwd(_mc(model), C.byref(pc), M, T, abi.ptr(states), abi.ptr(inputs), abi.ptr(jac), abi.ptr(g_states),
-                                            abi.ptr(g_inputs), abi.ptr(slabs), abi.ptr(g_x0), abi.stream()), "mcp_rollout_mlp_bwd")
+    if meas is None:
+        abi.check(abi.lib().mcp_rollout_mlp_bwd(_mc(model), C.byref(pc), M, T, abi.ptr(states), abi.ptr(inputs), abi.ptr(jac), abi.ptr(g_states),
+                                                abi.ptr(g_inputs), abi.ptr(slabs), abi.ptr(g_x0), abi.stream()), "mcp_rollout_mlp_bwd")
+        return slabs, g_x0
+    mc = abi.Meas()
+    meas.fill(mc, T, M, meas_buf)
+    abi.check(abi.lib().mcp_rollout_mlp_meas_bwd(_mc(model), C.byref(pc), C.byref(mc), M, T, abi.ptr(states), abi.ptr(inputs), abi.ptr(jac),
+                                                 abi.ptr(g_states), abi.ptr(g_inputs), abi.ptr(slabs), abi.ptr(g_x0), abi.stream()),
+              "mcp_rollout_mlp_meas_bwd")
     return slabs, g_x0
 
 
 class RolloutMLPFunction(torch.autograd.Function):
     """(x0 [M,S], W0, b0, [W1, b1], Wout, bout) -> states [T,M,S], inputs [T,M,U] through the recording form of the fused closed loop under
     the tanh MLP (mcp_rollout_mlp); backward is the reverse-time sweep mcp_rollout_mlp_bwd over the record, with both upstream gradients.
-    The workgroups' partial slabs are added in torch's fixed order (``sum(0)``); the GP model is frozen."""
+    The workgroups' partial slabs are added in torch's fixed order (``sum(0)``); the GP model is frozen.  With a measurement model
+    (``meas``) the two launches are mcp_rollout_mlp_meas / mcp_rollout_mlp_meas_bwd; the measured states [T,M,S] the forward launch wrote
+    (``meas.measured``) are saved with the record and handed to the sweep."""
 
     @staticmethod
-    def forward(ctx, model, mlp, noise, T, particle_pred, status, x0, *tensors):
-        states, inputs, jac = _rollout_mlp_launch(model, mlp, tensors, noise, x0, T, particle_pred, status, True)
-        ctx.model, ctx.mlp, ctx.has_jac = model, mlp, jac is not None
+    def forward(ctx, model, mlp, noise, T, particle_pred, status, meas, x0, *tensors):
+        states, inputs, jac = _rollout_mlp_launch(model, mlp, tensors, noise, x0, T, particle_pred, status, True, meas)
+        ctx.model, ctx.mlp, ctx.has_jac, ctx.meas = model, mlp, jac is not None, meas
         ctx.set_materialize_grads(False)
         # (saved tensors: autograd refuses a backward after an in-place change of any of them -- the record, or a weight stepped too early)
-        ctx.save_for_backward(*((states, inputs) + ((jac,) if jac is not None else ()) + tuple(tensors)))
+        ctx.save_for_backward(*((states, inputs) + ((jac,) if jac is not None else ()) + ((meas.measured,) if meas is not None else ())
+                                + tuple(tensors)))
         return states, inputs
 
     @staticmethod
@@ -873,28 +892,34 @@ class RolloutMLPFunction(torch.autograd.Function):
         saved = ctx.saved_tensors
         states, inputs = saved[:2]
         jac = saved[2] if ctx.has_jac else None
-        tensors = saved[3 if ctx.has_jac else 2:]
+        n0 = 3 if ctx.has_jac else 2
+        meas_buf = saved[n0] if ctx.meas is not None else None
+        tensors = saved[n0 + (1 if ctx.meas is not None else 0):]
         gs = torch.zeros_like(states) if g_states is None else g_states.to(dtype=DT).contiguous()
         gi = None if g_inputs is None else g_inputs.to(dtype=DT).contiguous()
-        want_x0, want_p = ctx.needs_input_grad[6], any(ctx.needs_input_grad[7:])
-        slabs, g_x0 = _rollout_mlp_sweep(ctx.model, ctx.mlp, tensors, states, inputs, jac, gs, gi, want_p, want_x0)
+        want_x0, want_p = ctx.needs_input_grad[7], any(ctx.needs_input_grad[8:])
+        slabs, g_x0 = _rollout_mlp_sweep(ctx.model, ctx.mlp, tensors, states, inputs, jac, gs, gi, want_p, want_x0, ctx.meas, meas_buf)
         grads = [None] * len(tensors)
         if want_p:
             flat = slabs.sum(0)  # the workgroups' slabs added in torch's fixed order
             o = 0
             for i, shp in enumerate(ctx.mlp.shapes):
                 n = int(np.prod(shp))
-                if ctx.needs_input_grad[7 + i]:
+                if ctx.needs_input_grad[8 + i]:
                     grads[i] = flat[o:o + n].reshape(shp)
                 o += n
-        return (None, None, None, None, None, None, g_x0) + tuple(grads)
+        return (None, None, None, None, None, None, None, g_x0) + tuple(grads)
 
 
-def rollout_mlp(model: PackedModel, mlp: PackedMLP, noise: Optional[NoiseSpec], x0, T, particle_pred=True, status=None):
+def rollout_mlp(model: PackedModel, mlp: PackedMLP, noise: Optional[NoiseSpec], x0, T, particle_pred=True, status=None,
+                meas: Optional[MeasSpec] = None):
     """Closed-loop rollout under a tanh-MLP policy in ONE launch: x0 [M,S] -> states [T,M,S], inputs [T,M,U] (row T - 1 included) and the
     status word.  ``noise``: an eps buffer [T-1,M,G] or Philox by seed / call / particle_offset (``particle_pred``), as ``rollout_pd``.
     With gradients enabled and x0 or a parameter requiring grad the recording launch runs and backward is the fused sweep (gradients to
-    the parameters that require them and to x0); otherwise nothing is recorded.  The same states and inputs, bit for bit, either way."""
+    the parameters that require them and to x0); otherwise nothing is recorded.  The same states and inputs, bit for bit, either way.
+    ``meas``: a measurement model between the particles and the network (partially measurable systems, as in ``rollout_pd``); the measured
+    states [T,M,S] the network was evaluated on are left in ``meas.measured`` (not differentiable).  None: the network sees the true state,
+    and the calls made are the ones made without the argument.  The return has the same three elements either way."""
     if not isinstance(x0, torch.Tensor) or not x0.is_cuda or any(not q.is_cuda for q in mlp.params):
         raise RuntimeError("rollout_mlp operates on GPU memory only (x0 and the parameters must be GPU tensors); there is no CPU path")
     T = int(T)
@@ -905,9 +930,9 @@ def rollout_mlp(model: PackedModel, mlp: PackedMLP, noise: Optional[NoiseSpec], 
     x0c, _, _, _, noise, status = _open_operands(model, x0, None, T, None, noise, particle_pred, status)
     tensors = [q.contiguous() for q in mlp.params]
     if torch.is_grad_enabled() and (x0c.requires_grad or any(q.requires_grad for q in tensors)):
-        states, inputs = RolloutMLPFunction.apply(model, mlp, noise, T, bool(particle_pred), status, x0c, *tensors)
+        states, inputs = RolloutMLPFunction.apply(model, mlp, noise, T, bool(particle_pred), status, meas, x0c, *tensors)
         return states, inputs, status
-    states, inputs, _ = _rollout_mlp_launch(model, mlp, [q.detach() for q in tensors], noise, x0c.detach(), T, particle_pred, status, False)
+    states, inputs, _ = _rollout_mlp_launch(model, mlp, [q.detach() for q in tensors], noise, x0c.detach(), T, particle_pred, status, False, meas)
     return states, inputs, status
 
 

@@ -210,18 +210,18 @@ class MC_PILCO(torch.nn.Module):
             # Sharded: the eps buffers are drawn for the whole swarm and sliced, Philox counts by global particle; the gains' gradients
             # reach the step's all-reduce through their .grad (_cost_backward)
             return self._fused(*ops.rollout_pd(ml.packed(), pol.packed(), self._rollout_noise(T)[0], x0, T), feedback=True)
-        if (self.fused_feedback and isinstance(pol, _Policy.MLP_policy) and _has_fused_layout(ml) and pol.fusable(ml.packed(), T)
-                and self._world()[0] == 1):
-            # the closed loop under the tanh MLP, one launch (and one sweep in backward): the eps draws of _rollout_noise.  Single process
-            # only: a sharded run falls through to the refusal below
+        if self.fused_feedback and isinstance(pol, _Policy.MLP_policy) and _has_fused_layout(ml) and pol.fusable(ml.packed(), T):
+            # the closed loop under the tanh MLP, one launch (and one sweep in backward): the eps draws of _rollout_noise.  Sharded as the
+            # PD law is: x0 and the eps buffers are drawn for the whole swarm and sliced, Philox counts by global particle (_shard[0]); the
+            # parameters' gradients reach the step's all-reduce through their .grad (_cost_backward)
             return self._fused(*ops.rollout_mlp(ml.packed(), pol.packed(), self._rollout_noise(T)[0], x0, T), feedback=True)
         # generic (unfused) path: any model / policy object with the reference's step interface
         self.last_status = None  # (no fused launch: the flags of an earlier fused rollout do not describe this one)
         if self._world()[0] > 1:
             # its noise (torch draws inside get_next_state / the policy's dropout) is per LOCAL particle: identically seeded ranks
             # would simulate correlated shards, not the particles one GPU would
-            raise NotImplementedError("particle sharding needs the fused rollout (Sum_of_gaussians or PD_controller policy + a model with a "
-                                      "fused layout)")
+            raise NotImplementedError("particle sharding needs the fused rollout (Sum_of_gaussians, PD_controller or MLP_policy policy + a model "
+                                      "with a fused layout)")
         step = self._step_fused(T)
         xs = [x0]
         us = [pol(x0, t=0, p_dropout=p_dropout)]
@@ -304,7 +304,10 @@ class MC_PILCO(torch.nn.Module):
                 if q.requires_grad and q.grad is None:
                     q.grad = torch.zeros_like(q)
         # one all-reduce; pooled cost / std; a NaN rollout neither poisons the next steps' shift nor goes unnoticed on the other ranks
-        cost, std, flags, self._cost_shift = sharding.finish_step(cf, self._reducer, params if backward else [], sums, self._step_flags(share),
+        # (the message holds the parameters that require grad -- n_grad above --: a frozen tensor, e.g. some of an MLP's six, takes no part even
+        # where an earlier step left it a .grad)
+        cost, std, flags, self._cost_shift = sharding.finish_step(cf, self._reducer, [q for q in params if q.requires_grad] if backward else [], sums,
+                                                                  self._step_flags(share),
                                                                   self._m_total, self._cost_shift, msg=msg)
         return cost, std, flags
 
@@ -759,7 +762,8 @@ class MC_PILCO4PMS(MC_PILCO):
     (``filtering_dict["fc"]``).  With the speed-integration models and the RBF policies the rollout is the same single fused
     launch as ``MC_PILCO.apply_policy``: the kernels carry the filter's states per particle and the reverse sweep its adjoint
     recursion (``mcp_meas``); a trainable ``PD_controller`` runs on its own fused launch and sweep with the same measurement model
-    (``mcp_rollout_pd_meas``; ``fused_feedback = False``: the step loop).  ``fused = False`` (or any other model / policy object) runs step by step on the posterior and
+    (``mcp_rollout_pd_meas``), and so does an ``MLP_policy`` (``mcp_rollout_mlp_meas``; ``fused_feedback = False``: the step loop for
+    both).  ``fused = False`` (or any other model / policy object) runs step by step on the posterior and
     policy operators with the filter as torch device ops.
     """
 
@@ -818,10 +822,17 @@ class MC_PILCO4PMS(MC_PILCO):
                 # order per step: eps_t, position noise; no mask
                 noise, pos_noise, _ = self._rollout_noise(T, n_pos=len(pos))
                 return self._fused(*ops.rollout_pd(model, pol.packed(), noise, x, T, meas=self._meas_spec(b, a, pos_noise)), feedback=True)
+        if self.fused and self.fused_feedback and isinstance(pol, _Policy.MLP_policy) and _has_fused_layout(ml):
+            model = self._measured_model()
+            if pol.fusable(model, T):
+                # the closed loop under the tanh MLP on the simulated measurement, one launch (and one sweep in backward); the reference's
+                # draw order per step: eps_t, position noise; no mask
+                noise, pos_noise, _ = self._rollout_noise(T, n_pos=len(pos))
+                return self._fused(*ops.rollout_mlp(model, pol.packed(), noise, x, T, meas=self._meas_spec(b, a, pos_noise)), feedback=True)
         self.last_status = None  # (no fused launch)
         if self._world()[0] > 1:  # (per-LOCAL-particle torch draws: identically seeded ranks would simulate correlated shards)
-            raise NotImplementedError("particle sharding needs the fused rollout (fused=True, Sum_of_gaussians or PD_controller policy, a model "
-                                      "with a fused layout)")
+            raise NotImplementedError("particle sharding needs the fused rollout (fused=True, Sum_of_gaussians, PD_controller or MLP_policy "
+                                      "policy, a model with a fused layout)")
         std_pos = torch.tensor(np.asarray(self.std_meas_noise_sim)[pos], dtype=self.dtype, device=self.device)
         step = self._step_fused(T, n_pos=len(pos))
         saved_mode = getattr(pol, "noise_mode", None)
