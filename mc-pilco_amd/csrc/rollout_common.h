@@ -116,6 +116,32 @@ static inline int meas_model_check(const mcp_model* model, const mcp_meas* ms) {
     if (ms->pos[i] < 0 || ms->pos[i] >= model->S || ms->vel[i] < 0 || ms->vel[i] >= model->S) return MCP_ERR_ARG;
   return meas_pairs_disjoint(ms) ? MCP_OK : MCP_ERR_ARG;
 }
+// whether a measured entry runs its measured kernels (ms NULL: a plain entry; n == 0: the plain kernels on the same arguments)
+static inline bool meas_active(const mcp_meas* ms) { return ms && ms->n > 0; }
+
+// The refusals of a closed-loop entry (PD law, tanh MLP; rollout and sweep), in the order they all keep -- every one before any HIP call:
+// `ptrs` (the entry's required pointers, the model among them) and the sizes (MCP_ERR_ARG), the compiled limits (MCP_ERR_LIMIT), the model
+// (MCP_ERR_ARG), the policy's descriptor by `policy_check()` (its limit code first, then MCP_ERR_ARG), the measurement (ms NULL: none).
+// `sweep`: the sweeps run from the record -- no training-set limits, model_lists_ok in model_ok's place -- and afterwards return MCP_OK
+// themselves where no gradient is asked for.
+template <class PolicyCheck>
+static inline int closed_loop_checks(bool ptrs, int M, int T, const mcp_model* model, const mcp_meas* ms, bool sweep, PolicyCheck policy_check) {
+  if (!ptrs || M <= 0 || T < 1) return MCP_ERR_ARG;
+  if (!model_within_limits(model, !sweep)) return MCP_ERR_LIMIT;
+  if (!(sweep ? model_lists_ok(model) : model_ok(model))) return MCP_ERR_ARG;
+  const int prc = policy_check();
+  if (prc != MCP_OK) return prc;
+  return ms ? meas_model_check(model, ms) : MCP_OK;
+}
+
+// the model's part of a sweep's arguments (OpenBwdArgs, MlpBwdArgs: separate types, the same leading fields S .. T, index lists, Ts)
+template <class Args>
+static inline void sweep_fill_model(Args& a, const mcp_model* model, int M, int T) {
+  a.S = model->S, a.U = model->U, a.G = model->G, a.D = model->D, a.nna = model->n_not_angle, a.na = model->n_angle, a.M = M, a.T = T;
+  for (int i = 0; i < MCP_MAX_STATE; ++i) a.angle[i] = model->angle[i], a.not_angle[i] = model->not_angle[i];
+  for (int g = 0; g < MCP_MAX_GP; ++g) a.vel[g] = model->vel[g], a.not_vel[g] = model->not_vel[g];
+  a.Ts = model->Ts;
+}
 
 // policy-only evaluation (T == 1, no dynamics model): a stub model with no GPs
 static inline mcp_model policy_only_model(const mcp_policy* p) {

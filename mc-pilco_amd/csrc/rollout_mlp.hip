@@ -496,21 +496,16 @@ static int launch_mlp_tiles(const typename MlpArgsOf<PMS>::type& a, int maxdeg, 
 // what mcp_rollout_mlp and mcp_rollout_mlp_meas share (ms NULL: no measurement)
 static int mlp_dispatch(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_meas* ms, const mcp_noise* noise, int M, int T, int particle_pred,
                         const double* x0, double* states, double* inputs, double* mu, double* var, double* jac, uint32_t* status, void* stream) {
-  if (!model || !mlp || !noise || !x0 || !states || !inputs || !status) return MCP_ERR_ARG;
-  if (M <= 0 || T < 1) return MCP_ERR_ARG;
-  if (!model_within_limits(model)) return MCP_ERR_LIMIT;
-  if (!model_ok(model)) return MCP_ERR_ARG;
-  const int crc = mlp_policy_check(model, mlp);
+  const int crc = closed_loop_checks(model && mlp && noise && x0 && states && inputs && status, M, T, model, ms, false,
+                                     [&] { return mlp_policy_check(model, mlp); });
   if (crc != MCP_OK) return crc;
-  const int mrc = ms ? meas_model_check(model, ms) : MCP_OK;
-  if (mrc != MCP_OK) return mrc;
   OpenArgsMlpMeas a;
-  if (T == 1) jac = nullptr;  // the policy alone: no transition, nothing to record
-  const int maxdeg = open_fill(a, model, noise, M, T, particle_pred, x0, nullptr, M, nullptr, states, mu, var, jac, status);
+  // (T == 1: the policy alone -- no transition, nothing to record)
+  const int maxdeg = open_fill(a, model, noise, M, T, particle_pred, x0, nullptr, M, nullptr, states, mu, var, T == 1 ? nullptr : jac, status);
   a.mlp = mlp_normalised(mlp);
   a.inputs = inputs;
   hipStream_t st = (hipStream_t)stream;
-  if (!ms || ms->n == 0) return launch_mlp_tiles<false>(a, maxdeg, var != nullptr, st);  // (the base part of `a`: mcp_rollout_mlp's own kernels)
+  if (!meas_active(ms)) return launch_mlp_tiles<false>(a, maxdeg, var != nullptr, st);  // (the base part of `a`: mcp_rollout_mlp's own kernels)
   a.ms = *ms;
   return launch_mlp_tiles<true>(a, maxdeg, var != nullptr, st);
 }
@@ -1003,22 +998,14 @@ static int launch_mlp_bwd(const typename MlpBwdArgsOf<PMS>::type& a, size_t lds,
 static int mlp_bwd_dispatch(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_meas* ms, int M, int T, const double* states,
                             const double* inputs, const double* jac, const double* g_states, const double* g_inputs, double* g_params, double* g_x0,
                             void* stream) {
-  if (!model || !mlp || !states || !inputs || !g_states || (!jac && T > 1)) return MCP_ERR_ARG;
-  if (M <= 0 || T < 1) return MCP_ERR_ARG;
-  if (!model_within_limits(model, false)) return MCP_ERR_LIMIT;
-  if (!model_lists_ok(model)) return MCP_ERR_ARG;
-  const int crc = mlp_policy_check(model, mlp);
+  const int crc = closed_loop_checks(model && mlp && states && inputs && g_states && (jac || T <= 1), M, T, model, ms, true,
+                                     [&] { return mlp_policy_check(model, mlp); });
   if (crc != MCP_OK) return crc;
-  const int mrc = ms ? meas_model_check(model, ms) : MCP_OK;
-  if (mrc != MCP_OK) return mrc;
   if (!g_x0 && !g_params) return MCP_OK;  // nothing asked for
-  const bool pms = ms && ms->n > 0;
+  const bool pms = meas_active(ms);
   MlpBwdArgsMeas a;
   memset(&a, 0, sizeof(a));
-  a.S = model->S, a.U = model->U, a.G = model->G, a.D = model->D, a.nna = model->n_not_angle, a.na = model->n_angle, a.M = M, a.T = T;
-  for (int i = 0; i < MCP_MAX_STATE; ++i) a.angle[i] = model->angle[i], a.not_angle[i] = model->not_angle[i];
-  for (int g = 0; g < MCP_MAX_GP; ++g) a.vel[g] = model->vel[g], a.not_vel[g] = model->not_vel[g];
-  a.Ts = model->Ts;
+  sweep_fill_model(a, model, M, T);
   a.states = states, a.inputs = inputs, a.jac = jac, a.g_states = g_states, a.g_inputs = g_inputs, a.g_x0 = g_x0, a.g_params = g_params;
   a.mlp = mlp_normalised(mlp);
   if (pms) a.ms = *ms;

@@ -6,8 +6,8 @@
 //   measured feedback  mcp_rollout_pd_meas      the PD law on a simulated measurement of x_t (struct OpenArgsPdMeas); mcp_rollout_pd_meas_bwd
 // All forward forms are one kernel template, rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, FB, PMS>, the three sweeps one,
 // rollout_open_bwd_kernel<FB, PMS>.  The host path is the same for every entry point: checks (rollout_common.h: model_within_limits,
-// model_ok / model_lists_ok, meas_model_check; here: pd_policy_check), one fill of the arguments' base part per direction
-// (open_fill, open_bwd_fill), one ladder of tiles (launch_open_tiles) -- a refused call makes no HIP call.
+// model_ok / model_lists_ok, meas_model_check -- for the closed loops in closed_loop_checks' one order; here: pd_policy_check), one fill of
+// the arguments' base part per direction (open_fill, open_bwd_fill over sweep_fill_model), one ladder of tiles (launch_open_tiles) -- a refused call makes no HIP call.
 //
 // The open-loop form replaces the step loop of MC_PILCO.rollout (policy_learning/MC_PILCO.py:347-373) over Model_learning.get_next_state
 // (model_learning/Model_learning.py:210-229, 685-718; GP_prior.get_estimate_from_alpha, GP_prior.py:137-155): per step G posterior
@@ -418,31 +418,22 @@ static int pd_policy_check(const mcp_model* model, const mcp_pd_policy* pd, int 
   }
   return MCP_OK;
 }
-// the PD descriptor, then the measurement (ms NULL: none), for both directions
-static int pd_checks(const mcp_model* model, const mcp_pd_policy* pd, const mcp_meas* ms, int T) {
-  const int prc = pd_policy_check(model, pd, T);
-  if (prc != MCP_OK) return prc;
-  return ms ? meas_model_check(model, ms) : MCP_OK;
-}
 
 // Closed-loop rollout under the PD law: replaces the loop of MC_PILCO.apply_policy (policy_learning/MC_PILCO.py:615-674) with
 // Policy.PD_controller.forward (policy_learning/Policy.py:437-449) as the policy, over Model_learning.get_next_state
 // (model_learning/Model_learning.py:210-229, 471-494, 685-718).  jac != NULL: the recording form (what autograd would keep of that loop).
 static int pd_dispatch(const mcp_model* model, const mcp_pd_policy* pd, const mcp_meas* ms, const mcp_noise* noise, int M, int T, int particle_pred,
                        const double* x0, double* states, double* inputs, double* jac, double* mu, double* var, uint32_t* status, void* stream) {
-  if (!model || !pd || !noise || !x0 || !states || !inputs || !status) return MCP_ERR_ARG;
-  if (M <= 0 || T < 1) return MCP_ERR_ARG;
-  if (!model_within_limits(model)) return MCP_ERR_LIMIT;
-  if (!model_ok(model)) return MCP_ERR_ARG;
-  const int crc = pd_checks(model, pd, ms, T);
+  const int crc = closed_loop_checks(model && pd && noise && x0 && states && inputs && status, M, T, model, ms, false,
+                                     [&] { return pd_policy_check(model, pd, T); });
   if (crc != MCP_OK) return crc;
   OpenArgsPdMeas a;
-  if (T == 1) jac = nullptr;  // the policy alone: no transition, nothing to record
-  const int maxdeg = open_fill(a, model, noise, M, T, particle_pred, x0, nullptr, M, nullptr, states, mu, var, jac, status);
+  // (T == 1: the policy alone -- no transition, nothing to record)
+  const int maxdeg = open_fill(a, model, noise, M, T, particle_pred, x0, nullptr, M, nullptr, states, mu, var, T == 1 ? nullptr : jac, status);
   a.pd = *pd;
   a.inputs = inputs;
   hipStream_t st = (hipStream_t)stream;
-  if (!ms || ms->n == 0) return launch_open_tiles<true, false>(a, maxdeg, var != nullptr, st);  // (the base part of `a`: mcp_rollout_pd's own kernels)
+  if (!meas_active(ms)) return launch_open_tiles<true, false>(a, maxdeg, var != nullptr, st);  // (the base part of `a`: mcp_rollout_pd's own kernels)
   a.ms = *ms;
   return launch_open_tiles<true, true>(a, maxdeg, var != nullptr, st);
 }
@@ -851,10 +842,7 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
 // (the sweeps run from the record: they check the model's scalars and index lists, model_lists_ok, and never look at a GP descriptor)
 static void open_bwd_fill(OpenBwdArgs& a, const mcp_model* model, int M, int T, const double* states, const int32_t* lengths, const double* jac,
                           const double* g_states, double* g_x0, double* g_u) {
-  a.S = model->S, a.U = model->U, a.G = model->G, a.D = model->D, a.nna = model->n_not_angle, a.na = model->n_angle, a.M = M, a.T = T;
-  for (int i = 0; i < MCP_MAX_STATE; ++i) a.angle[i] = model->angle[i], a.not_angle[i] = model->not_angle[i];
-  for (int g = 0; g < MCP_MAX_GP; ++g) a.vel[g] = model->vel[g], a.not_vel[g] = model->not_vel[g];
-  a.Ts = model->Ts;
+  sweep_fill_model(a, model, M, T);
   a.states = states;
   a.jac = jac;
   a.g_states = g_states;
@@ -893,11 +881,8 @@ extern "C" int mcp_rollout_open_bwd(const mcp_model* model, int M, int T, const 
 static int pd_bwd_dispatch(const mcp_model* model, const mcp_pd_policy* pd, const mcp_meas* ms, int M, int T, const double* states,
                            const double* inputs, const double* jac, const double* g_states, const double* g_inputs, double* g_gains, double* g_x0,
                            void* stream) {
-  if (!model || !pd || !states || !inputs || !g_states || (!jac && T > 1)) return MCP_ERR_ARG;
-  if (M <= 0 || T < 1) return MCP_ERR_ARG;
-  if (!model_within_limits(model, false)) return MCP_ERR_LIMIT;
-  if (!model_lists_ok(model)) return MCP_ERR_ARG;
-  const int crc = pd_checks(model, pd, ms, T);
+  const int crc = closed_loop_checks(model && pd && states && inputs && g_states && (jac || T <= 1), M, T, model, ms, true,
+                                     [&] { return pd_policy_check(model, pd, T); });
   if (crc != MCP_OK) return crc;
   if (!g_x0 && !g_gains) return MCP_OK;  // nothing asked for
   OpenBwdArgsPdMeas a;
@@ -908,7 +893,7 @@ static int pd_bwd_dispatch(const mcp_model* model, const mcp_pd_policy* pd, cons
   a.g_inputs = g_inputs;
   a.g_gains = g_gains;
   hipStream_t st = (hipStream_t)stream;
-  if (ms && ms->n > 0) {
+  if (meas_active(ms)) {
     a.ms = *ms;
     return launch_open_bwd<true, true>(a, st);
   }

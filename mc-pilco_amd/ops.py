@@ -651,16 +651,29 @@ def model_step(model: PackedModel, x, u, t, noise: Optional[NoiseSpec] = None, p
 
 
 # --------------------------------------------------------------------------------------
-# fused closed loop under the PD law (autograd)
+# fused closed loop under a feedback policy (autograd): the PD law, the tanh MLP
 # --------------------------------------------------------------------------------------
+# What the one host path below (_closed_launch, _closed_sweep, RolloutClosedFunction, _rollout_closed) reads of a packed policy:
+#   params         the policy's own parameter tensors (where they live is checked); tensors(): the LIVE tensors one launch takes, to_c(*tensors)
+#                  its descriptor over them, shapes: their shapes -- a sweep's raw gradient buffer, summed over its rows, is cut in this order
+#   fwd, bwd       the C entries (plain, measured) of the rollout and of the sweep; fwd_outputs: the order of the forward entry's output
+#                  pointers between ``inputs`` and ``status`` -- the two policies' entries differ there, and only there
+#   grad_tile, grad_shape   the raw parameter-gradient buffer of a sweep is [ceil(M / grad_tile)] + grad_shape
+#   check(model, T)   the policy's own refusals
 class PackedPD:
     """mcp_pd_policy of a ``Policy.PD_controller`` (reference policy_learning/Policy.py:406-449): the two gain parameters are kept as they
     are -- every launch takes views of the LIVE tensors, so an optimizer's in-place updates are seen -- and the target trajectory is held
     on the device.  The reference's index layout: input k reads the errors of position k and of velocity h + k, h = S / 2."""
 
+    fwd, bwd = ("mcp_rollout_pd", "mcp_rollout_pd_meas"), ("mcp_rollout_pd_bwd", "mcp_rollout_pd_meas_bwd")
+    fwd_outputs = ("jac", "mu", "var")
+    grad_tile = 1  # one row of gain gradients per trajectory
+
     def __init__(self, policy):
         self.sqrt_kp, self.sqrt_kd = policy.sqrt_Kp_gains, policy.sqrt_Kd_gains
+        self.params = [self.sqrt_kp, self.sqrt_kd]
         self.S, self.U = int(policy.state_dim), int(policy.input_dim)
+        self.shapes, self.grad_shape = [(self.U,), (self.U,)], (2, self.U)
         dev = _dev(self.sqrt_kp.device)
         if policy.target_traj is None:
             raise RuntimeError("the PD controller has no target trajectory")
@@ -685,8 +698,16 @@ class PackedPD:
             out.append(g)
         return out
 
+    tensors = gains
+
+    def check(self, model, T):
+        if self.S != model.S or self.U != model.U:
+            raise RuntimeError("the PD controller is for %d states and %d inputs, the model has %d and %d" % (self.S, self.U, model.S, model.U))
+        if T < 1 or self.target_traj.shape[0] < T:
+            raise RuntimeError("the target trajectory has %d rows, the rollout needs %d" % (self.target_traj.shape[0], T))
+
     def to_c(self, kp, kd):
-        """The descriptor over the contiguous float64 GPU tensors ``kp`` / ``kd`` [U]."""
+        """The descriptor over the gains (kp, kd): contiguous float64 GPU tensors [U]."""
         for t in (kp, kd):
             if t.dtype != DT or not t.is_cuda or not t.is_contiguous() or t.numel() != self.U:
                 raise RuntimeError("the PD gains must be contiguous float64 GPU tensors with one value per input")
@@ -699,99 +720,14 @@ class PackedPD:
         return c
 
 
-def _rollout_pd_launch(model, pd, kp, kd, noise, x0, T, particle_pred, status, record, meas=None):
-    M, dev = int(x0.shape[0]), model.device
-    states, inputs, jac = _record_buffers(dev, T, M, model.S, model.U, model.G, model.D, record and T > 1)
-    pc, nz = pd.to_c(kp, kd), noise.to_c()
-    if meas is None:
-        abi.check(abi.lib().mcp_rollout_pd(_mc(model), C.byref(pc), C.byref(nz), M, T, int(bool(particle_pred)), abi.ptr(x0), abi.ptr(states),
-                                           abi.ptr(inputs), abi.ptr(jac), None, None, abi.ptr(status), abi.stream()), "mcp_rollout_pd")
-        return states, inputs, jac
-    meas_buf = meas.measured = torch.empty(T, M, model.S, dtype=DT, device=dev)  # (allocated as rollout_forward_raw allocates it)
-    mc = abi.Meas()
-    meas.fill(mc, T, M, meas_buf)
-    abi.check(abi.lib().mcp_rollout_pd_meas(_mc(model), C.byref(pc), C.byref(mc), C.byref(nz), M, T, int(bool(particle_pred)), abi.ptr(x0),
-                                            abi.ptr(states), abi.ptr(inputs), abi.ptr(jac), None, None, abi.ptr(status), abi.stream()),
-              "mcp_rollout_pd_meas")
-    return states, inputs, jac
-
-
-class RolloutPDFunction(torch.autograd.Function):
-    """(x0 [M,S], sqrt_kp [U], sqrt_kd [U]) -> states [T,M,S], inputs [T,M,U] through the recording form of the fused closed loop under the
-    PD law (mcp_rollout_pd); backward is the reverse-time sweep mcp_rollout_pd_bwd over the record, with both upstream gradients.  The
-    per-trajectory gain gradients are added in torch's fixed order; the GP model is frozen.  With a measurement model (``meas``) the two
-    launches are mcp_rollout_pd_meas / mcp_rollout_pd_meas_bwd; the measured states [T,M,S] the forward launch wrote (``meas.measured``) are
-    saved with the record and handed to the sweep."""
-
-    @staticmethod
-    def forward(ctx, x0, kp, kd, model, pd, noise, T, particle_pred, status, meas):
-        states, inputs, jac = _rollout_pd_launch(model, pd, kp, kd, noise, x0, T, particle_pred, status, True, meas)
-        meas_buf = None if meas is None else meas.measured
-        ctx.model, ctx.pd, ctx.has_jac, ctx.meas = model, pd, jac is not None, meas
-        ctx.set_materialize_grads(False)
-        # (saved tensors: autograd refuses a backward after an in-place change of any of them -- the record, or a gain stepped too early)
-        ctx.save_for_backward(*((states, inputs, kp, kd) + ((jac,) if jac is not None else ()) + ((meas_buf,) if meas is not None else ())))
-        return states, inputs
-
-    @staticmethod
-    def backward(ctx, g_states, g_inputs):
-        saved = ctx.saved_tensors
-        states, inputs, kp, kd = saved[:4]
-        jac = saved[4] if ctx.has_jac else None
-        model, pd, meas = ctx.model, ctx.pd, ctx.meas
-        T, M = int(states.shape[0]), int(states.shape[1])
-        gs = torch.zeros_like(states) if g_states is None else g_states.to(dtype=DT).contiguous()
-        gi = None if g_inputs is None else g_inputs.to(dtype=DT).contiguous()
-        want_x0, want_g = ctx.needs_input_grad[0], ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        g_x0 = torch.empty(M, model.S, dtype=DT, device=states.device) if want_x0 else None
-        g_gains = torch.empty(M, 2, model.U, dtype=DT, device=states.device) if want_g else None
-        pc = pd.to_c(kp, kd)
-        if meas is None:
-            abi.check(abi.lib().mcp_rollout_pd_bwd(_mc(model), C.byref(pc), M, T, abi.ptr(states), abi.ptr(inputs), abi.ptr(jac), abi.ptr(gs), abi.ptr(gi),
-                                                   abi.ptr(g_gains), abi.ptr(g_x0), abi.stream()), "mcp_rollout_pd_bwd")
-        else:
-            mc = abi.Meas()
-            meas.fill(mc, T, M, saved[-1])
-            abi.check(abi.lib().mcp_rollout_pd_meas_bwd(_mc(model), C.byref(pc), C.byref(mc), M, T, abi.ptr(states), abi.ptr(inputs), abi.ptr(jac),
-                                                        abi.ptr(gs), abi.ptr(gi), abi.ptr(g_gains), abi.ptr(g_x0), abi.stream()),
-                      "mcp_rollout_pd_meas_bwd")
-        gg = g_gains.sum(0) if want_g else None  # the trajectories' gradients added in torch's fixed order
-        return (g_x0, gg[0] if ctx.needs_input_grad[1] else None, gg[1] if ctx.needs_input_grad[2] else None, None, None, None, None, None, None,
-                None)
-
-
-def rollout_pd(model: PackedModel, pd: PackedPD, noise: Optional[NoiseSpec], x0, T, particle_pred=True, status=None, meas: Optional[MeasSpec] = None):
-    """Closed-loop rollout under a PD controller in ONE launch: x0 [M,S] -> states [T,M,S], inputs [T,M,U] (row T - 1 included) and the
-    status word.  ``noise``: an eps buffer [T-1,M,G] or Philox by seed / call / particle_offset (``particle_pred``), as ``rollout_open``.
-    With gradients enabled and x0 or a gain requiring grad the recording launch runs and backward is the fused sweep (gradients to
-    ``sqrt_Kp_gains``, ``sqrt_Kd_gains`` and x0); otherwise nothing is recorded.  The same states and inputs, bit for bit, either way.
-    ``meas``: a measurement model between the particles and the PD law (partially measurable systems, as in ``rollout``); the measured
-    states [T,M,S] the law was evaluated on are left in ``meas.measured`` (not differentiable).  None: the law sees the true state, and
-    the calls made are the ones made without the argument.  The return has the same three elements either way."""
-    if not isinstance(x0, torch.Tensor) or not x0.is_cuda or not pd.sqrt_kp.is_cuda or not pd.sqrt_kd.is_cuda:
-        raise RuntimeError("rollout_pd operates on GPU memory only (x0 and the gains must be GPU tensors); there is no CPU path")
-    T = int(T)
-    if pd.S != model.S or pd.U != model.U:
-        raise RuntimeError("the PD controller is for %d states and %d inputs, the model has %d and %d" % (pd.S, pd.U, model.S, model.U))
-    if T < 1 or pd.target_traj.shape[0] < T:
-        raise RuntimeError("the target trajectory has %d rows, the rollout needs %d" % (pd.target_traj.shape[0], T))
-    x0c, _, _, _, noise, status = _open_operands(model, x0, None, T, None, noise, particle_pred, status)
-    kp, kd = pd.gains()
-    if torch.is_grad_enabled() and (x0c.requires_grad or kp.requires_grad or kd.requires_grad):
-        states, inputs = RolloutPDFunction.apply(x0c, kp.contiguous(), kd.contiguous(), model, pd, noise, T, bool(particle_pred), status, meas)
-        return states, inputs, status
-    states, inputs, _ = _rollout_pd_launch(model, pd, kp.detach().contiguous(), kd.detach().contiguous(), noise, x0c.detach(), T, particle_pred,
-                                           status, False, meas)
-    return states, inputs, status
-
-
-# --------------------------------------------------------------------------------------
-# fused closed loop under the tanh MLP (autograd)
-# --------------------------------------------------------------------------------------
 class PackedMLP:
     """mcp_mlp_policy of a ``Policy.MLP_policy``: the parameter tensors (W0, b0, [W1, b1], Wout, bout) are kept as they are -- every
     launch takes the LIVE tensors, so an optimizer's in-place updates are seen.  Features f = [x[non_angle], sin x[angle], cos x[angle]]
     (both lists empty: f = x)."""
+
+    fwd, bwd = ("mcp_rollout_mlp", "mcp_rollout_mlp_meas"), ("mcp_rollout_mlp_bwd", "mcp_rollout_mlp_meas_bwd")
+    fwd_outputs = ("mu", "var", "jac")
+    grad_tile = 16  # one slab of parameter gradients per workgroup of the sweep
 
     def __init__(self, policy):
         self.params = list(policy.mlp_parameters())
@@ -810,9 +746,19 @@ class PackedMLP:
             raise RuntimeError("at most %d indices per feature list" % abi.MAX_STATE)
         self.shapes = [tuple(q.shape) for q in self.params]
         self.n_param = sum(int(q.numel()) for q in self.params)
+        self.grad_shape = (self.n_param,)
         self.device = self.params[0].device
 
-    def to_c(self, tensors):
+    def tensors(self):
+        return self.params
+
+    def check(self, model, T):
+        if self.S != model.S or self.U != model.U:
+            raise RuntimeError("the MLP policy is for %d states and %d inputs, the model has %d and %d" % (self.S, self.U, model.S, model.U))
+        if T < 1:
+            raise RuntimeError("the rollout needs at least one row")
+
+    def to_c(self, *tensors):
         """The descriptor over ``tensors``: contiguous float64 GPU tensors in the parameter order, of the parameters' shapes."""
         for t, shp in zip(tensors, self.shapes):
             if t.dtype != DT or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shp:
@@ -834,106 +780,115 @@ class PackedMLP:
         return c
 
 
-def _rollout_mlp_launch(model, mlp, tensors, noise, x0, T, particle_pred, status, record, meas=None):
-    M, dev = int(x0.shape[0]), model.device
-    states, inputs, jac = _record_buffers(dev, T, M, model.S, model.U, model.G, model.D, record and T > 1)
-    pc, nz = mlp.to_c(tensors), noise.to_c()
+def _meas_arg(meas, T, M, meas_buf):
+    """The measured entries' extra argument, the mcp_meas of ``meas`` over ``meas_buf`` [T,M,S] (a list, to splice in); empty without one."""
     if meas is None:
-        abi.check(abi.lib().mcp_rollout_mlp(_mc(model), C.byref(pc), C.byref(nz), M, T, int(bool(particle_pred)), abi.ptr(x0), abi.ptr(states),
-                                            abi.ptr(inputs), None, None, abi.ptr(jac), abi.ptr(status), abi.stream()), "mcp_rollout_mlp")
-        return states, inputs, jac
-    meas_buf = meas.measured = torch.empty(T, M, model.S, dtype=DT, device=dev)  # (allocated as _rollout_pd_launch allocates it)
+        return []
     mc = abi.Meas()
     meas.fill(mc, T, M, meas_buf)
-    abi.check(abi.lib().mcp_rollout_mlp_meas(_mc(model), C.byref(pc), C.byref(mc), C.byref(nz), M, T, int(bool(particle_pred)), abi.ptr(x0),
-                                             abi.ptr(states), abi.ptr(inputs), None, None, abi.ptr(jac), abi.ptr(status), abi.stream()),
-              "mcp_rollout_mlp_meas")
+    return [C.byref(mc)]
+
+
+def _closed_launch(model, packed, tensors, noise, x0, T, particle_pred, status, record, meas=None):
+    """(states [T,M,S], inputs [T,M,U], jac or None) of ONE launch of the closed loop under ``packed`` over its parameter ``tensors``
+    (packed.fwd); ``record`` and T > 1: the recording form.  With ``meas`` the measured entry, which writes ``meas.measured`` [T,M,S]."""
+    M, dev = int(x0.shape[0]), model.device
+    states, inputs, jac = _record_buffers(dev, T, M, model.S, model.U, model.G, model.D, record and T > 1)
+    pc, nz = packed.to_c(*tensors), noise.to_c()
+    meas_buf = None
+    if meas is not None:
+        meas_buf = meas.measured = torch.empty(T, M, model.S, dtype=DT, device=dev)  # (allocated as rollout_forward_raw allocates it)
+    outputs = {"jac": jac, "mu": None, "var": None}
+    name = packed.fwd[meas is not None]
+    abi.check(getattr(abi.lib(), name)(_mc(model), C.byref(pc), *_meas_arg(meas, T, M, meas_buf), C.byref(nz), M, T,
+                                       int(bool(particle_pred)), abi.ptr(x0), abi.ptr(states), abi.ptr(inputs),
+                                       *[abi.ptr(outputs[k]) for k in packed.fwd_outputs], abi.ptr(status), abi.stream()), name)
     return states, inputs, jac
 
 
-def _rollout_mlp_sweep(model, mlp, tensors, states, inputs, jac, g_states, g_inputs, want_params, want_x0, meas=None, meas_buf=None):
-    """(g_params slabs [ceil(M/16), n_param] or None, g_x0 [M,S] or None) of mcp_rollout_mlp_bwd; with ``meas`` (and the measured states
-    ``meas_buf`` its forward launch wrote) of mcp_rollout_mlp_meas_bwd."""
+def _closed_sweep(model, packed, tensors, states, inputs, jac, g_states, g_inputs, want_params, want_x0, meas=None, meas_buf=None):
+    """(raw parameter gradients [ceil(M / grad_tile)] + grad_shape or None, g_x0 [M,S] or None) of ONE reverse-time sweep over the record
+    (packed.bwd); with ``meas`` (and the measured states ``meas_buf`` its forward launch wrote) the measured entry."""
     T, M, dev = int(states.shape[0]), int(states.shape[1]), states.device
     g_x0 = torch.empty(M, model.S, dtype=DT, device=dev) if want_x0 else None
-    slabs = torch.empty((M + 15) // 16, mlp.n_param, dtype=DT, device=dev) if want_params else None
-    pc = mlp.to_c(tensors)
-    if meas is None:
-        abi.check(abi.lib().mcp_rollout_mlp_bwd(_mc(model), C.byref(pc), M, T, abi.ptr(states), abi.ptr(inputs), abi.ptr(jac), abi.ptr(g_states),
-                                                abi.ptr(g_inputs), abi.ptr(slabs), abi.ptr(g_x0), abi.stream()), "mcp_rollout_mlp_bwd")
-        return slabs, g_x0
-    mc = abi.Meas()
-    meas.fill(mc, T, M, meas_buf)
-    abi.check(abi.lib().mcp_rollout_mlp_meas_bwd(_mc(model), C.byref(pc), C.byref(mc), M, T, abi.ptr(states), abi.ptr(inputs), abi.ptr(jac),
-                                                 abi.ptr(g_states), abi.ptr(g_inputs), abi.ptr(slabs), abi.ptr(g_x0), abi.stream()),
-              "mcp_rollout_mlp_meas_bwd")
-    return slabs, g_x0
+    raw = torch.empty(((M + packed.grad_tile - 1) // packed.grad_tile,) + packed.grad_shape, dtype=DT, device=dev) if want_params else None
+    pc = packed.to_c(*tensors)
+    name = packed.bwd[meas is not None]
+    abi.check(getattr(abi.lib(), name)(_mc(model), C.byref(pc), *_meas_arg(meas, T, M, meas_buf), M, T, abi.ptr(states), abi.ptr(inputs),
+                                       abi.ptr(jac), abi.ptr(g_states), abi.ptr(g_inputs), abi.ptr(raw), abi.ptr(g_x0), abi.stream()), name)
+    return raw, g_x0
 
 
-class RolloutMLPFunction(torch.autograd.Function):
-    """(x0 [M,S], W0, b0, [W1, b1], Wout, bout) -> states [T,M,S], inputs [T,M,U] through the recording form of the fused closed loop under
-    the tanh MLP (mcp_rollout_mlp); backward is the reverse-time sweep mcp_rollout_mlp_bwd over the record, with both upstream gradients.
-    The workgroups' partial slabs are added in torch's fixed order (``sum(0)``); the GP model is frozen.  With a measurement model
-    (``meas``) the two launches are mcp_rollout_mlp_meas / mcp_rollout_mlp_meas_bwd; the measured states [T,M,S] the forward launch wrote
-    (``meas.measured``) are saved with the record and handed to the sweep."""
+class RolloutClosedFunction(torch.autograd.Function):
+    """(x0 [M,S], the policy's parameter tensors) -> states [T,M,S], inputs [T,M,U] through the recording form of the fused closed loop
+    under ``packed`` (a PackedPD or a PackedMLP); backward is the reverse-time sweep over the record, with both upstream gradients.  The
+    sweep's raw parameter gradients (per trajectory, or per workgroup) are added in torch's fixed order (``sum(0)``); the GP model is
+    frozen.  With a measurement model (``meas``) the two launches are the measured entries; the measured states [T,M,S] the forward launch
+    wrote (``meas.measured``) are saved with the record and handed to the sweep."""
 
     @staticmethod
-    def forward(ctx, model, mlp, noise, T, particle_pred, status, meas, x0, *tensors):
-        states, inputs, jac = _rollout_mlp_launch(model, mlp, tensors, noise, x0, T, particle_pred, status, True, meas)
-        ctx.model, ctx.mlp, ctx.has_jac, ctx.meas = model, mlp, jac is not None, meas
+    def forward(ctx, model, packed, noise, T, particle_pred, status, meas, x0, *tensors):
+        states, inputs, jac = _closed_launch(model, packed, tensors, noise, x0, T, particle_pred, status, True, meas)
+        ctx.model, ctx.packed, ctx.has_jac, ctx.meas = model, packed, jac is not None, meas
         ctx.set_materialize_grads(False)
-        # (saved tensors: autograd refuses a backward after an in-place change of any of them -- the record, or a weight stepped too early)
-        ctx.save_for_backward(*((states, inputs) + ((jac,) if jac is not None else ()) + ((meas.measured,) if meas is not None else ())
-                                + tuple(tensors)))
+        # (saved tensors: autograd refuses a backward after an in-place change of any of them -- the record, or a parameter stepped too early)
+        ctx.save_for_backward(states, inputs, *tensors, *((jac,) if jac is not None else ()), *((meas.measured,) if meas is not None else ()))
         return states, inputs
 
     @staticmethod
     def backward(ctx, g_states, g_inputs):
-        saved = ctx.saved_tensors
-        states, inputs = saved[:2]
-        jac = saved[2] if ctx.has_jac else None
-        n0 = 3 if ctx.has_jac else 2
-        meas_buf = saved[n0] if ctx.meas is not None else None
-        tensors = saved[n0 + (1 if ctx.meas is not None else 0):]
+        packed, n = ctx.packed, len(ctx.packed.shapes)
+        states, inputs, tensors, rest = ctx.saved_tensors[0], ctx.saved_tensors[1], ctx.saved_tensors[2:2 + n], list(ctx.saved_tensors[2 + n:])
+        jac = rest.pop(0) if ctx.has_jac else None
+        meas_buf = rest.pop(0) if ctx.meas is not None else None
         gs = torch.zeros_like(states) if g_states is None else g_states.to(dtype=DT).contiguous()
         gi = None if g_inputs is None else g_inputs.to(dtype=DT).contiguous()
-        want_x0, want_p = ctx.needs_input_grad[7], any(ctx.needs_input_grad[8:])
-        slabs, g_x0 = _rollout_mlp_sweep(ctx.model, ctx.mlp, tensors, states, inputs, jac, gs, gi, want_p, want_x0, ctx.meas, meas_buf)
-        grads = [None] * len(tensors)
-        if want_p:
-            flat = slabs.sum(0)  # the workgroups' slabs added in torch's fixed order
-            o = 0
-            for i, shp in enumerate(ctx.mlp.shapes):
-                n = int(np.prod(shp))
-                if ctx.needs_input_grad[8 + i]:
-                    grads[i] = flat[o:o + n].reshape(shp)
-                o += n
+        want_x0, want = ctx.needs_input_grad[7], ctx.needs_input_grad[8:]
+        raw, g_x0 = _closed_sweep(ctx.model, packed, tensors, states, inputs, jac, gs, gi, any(want), want_x0, ctx.meas, meas_buf)
+        grads = [None] * n
+        if raw is not None:
+            flat, o = raw.sum(0).reshape(-1), 0  # the trajectories' / workgroups' rows added in torch's fixed order
+            for i, shp in enumerate(packed.shapes):  # (only the parameters that need one get a gradient)
+                k = int(np.prod(shp))
+                if want[i]:
+                    grads[i] = flat[o:o + k].reshape(shp)
+                o += k
         return (None, None, None, None, None, None, None, g_x0) + tuple(grads)
+
+
+def _rollout_closed(op, noun, model, packed, noise, x0, T, particle_pred, status, meas):
+    """What ``rollout_pd`` and ``rollout_mlp`` do (``op``: which, ``noun``: what its message calls the parameters -- the device refusal comes
+    first and is raised whatever ``packed`` is, so the two words are not read from it): the checks, then the recording Function or, with
+    nothing to differentiate, one launch on detached tensors."""
+    if not isinstance(x0, torch.Tensor) or not x0.is_cuda or any(not q.is_cuda for q in packed.params):
+        raise RuntimeError("%s operates on GPU memory only (x0 and %s must be GPU tensors); there is no CPU path" % (op, noun))
+    T = int(T)
+    packed.check(model, T)
+    x0c, _, _, _, noise, status = _open_operands(model, x0, None, T, None, noise, particle_pred, status)
+    tensors = [q.contiguous() for q in packed.tensors()]
+    if torch.is_grad_enabled() and (x0c.requires_grad or any(q.requires_grad for q in tensors)):
+        states, inputs = RolloutClosedFunction.apply(model, packed, noise, T, bool(particle_pred), status, meas, x0c, *tensors)
+    else:
+        states, inputs, _ = _closed_launch(model, packed, [q.detach() for q in tensors], noise, x0c.detach(), T, particle_pred, status, False, meas)
+    return states, inputs, status
+
+
+def rollout_pd(model: PackedModel, pd: PackedPD, noise: Optional[NoiseSpec], x0, T, particle_pred=True, status=None, meas: Optional[MeasSpec] = None):
+    """Closed-loop rollout under a PD controller in ONE launch: x0 [M,S] -> states [T,M,S], inputs [T,M,U] (row T - 1 included) and the
+    status word.  ``noise``: an eps buffer [T-1,M,G] or Philox by seed / call / particle_offset (``particle_pred``), as ``rollout_open``.
+    With gradients enabled and x0 or a gain requiring grad the recording launch runs and backward is the fused sweep (gradients to
+    ``sqrt_Kp_gains``, ``sqrt_Kd_gains`` and x0); otherwise nothing is recorded.  The same states and inputs, bit for bit, either way.
+    ``meas``: a measurement model between the particles and the PD law (partially measurable systems, as in ``rollout``); the measured
+    states [T,M,S] the law was evaluated on are left in ``meas.measured`` (not differentiable).  None: the law sees the true state, and
+    the calls made are the ones made without the argument.  The return has the same three elements either way."""
+    return _rollout_closed("rollout_pd", "the gains", model, pd, noise, x0, T, particle_pred, status, meas)
 
 
 def rollout_mlp(model: PackedModel, mlp: PackedMLP, noise: Optional[NoiseSpec], x0, T, particle_pred=True, status=None,
                 meas: Optional[MeasSpec] = None):
-    """Closed-loop rollout under a tanh-MLP policy in ONE launch: x0 [M,S] -> states [T,M,S], inputs [T,M,U] (row T - 1 included) and the
-    status word.  ``noise``: an eps buffer [T-1,M,G] or Philox by seed / call / particle_offset (``particle_pred``), as ``rollout_pd``.
-    With gradients enabled and x0 or a parameter requiring grad the recording launch runs and backward is the fused sweep (gradients to
-    the parameters that require them and to x0); otherwise nothing is recorded.  The same states and inputs, bit for bit, either way.
-    ``meas``: a measurement model between the particles and the network (partially measurable systems, as in ``rollout_pd``); the measured
-    states [T,M,S] the network was evaluated on are left in ``meas.measured`` (not differentiable).  None: the network sees the true state,
-    and the calls made are the ones made without the argument.  The return has the same three elements either way."""
-    if not isinstance(x0, torch.Tensor) or not x0.is_cuda or any(not q.is_cuda for q in mlp.params):
-        raise RuntimeError("rollout_mlp operates on GPU memory only (x0 and the parameters must be GPU tensors); there is no CPU path")
-    T = int(T)
-    if mlp.S != model.S or mlp.U != model.U:
-        raise RuntimeError("the MLP policy is for %d states and %d inputs, the model has %d and %d" % (mlp.S, mlp.U, model.S, model.U))
-    if T < 1:
-        raise RuntimeError("the rollout needs at least one row")
-    x0c, _, _, _, noise, status = _open_operands(model, x0, None, T, None, noise, particle_pred, status)
-    tensors = [q.contiguous() for q in mlp.params]
-    if torch.is_grad_enabled() and (x0c.requires_grad or any(q.requires_grad for q in tensors)):
-        states, inputs = RolloutMLPFunction.apply(model, mlp, noise, T, bool(particle_pred), status, meas, x0c, *tensors)
-        return states, inputs, status
-    states, inputs, _ = _rollout_mlp_launch(model, mlp, [q.detach() for q in tensors], noise, x0c.detach(), T, particle_pred, status, False, meas)
-    return states, inputs, status
+    """Closed-loop rollout under a tanh-MLP policy in ONE launch: arguments, return and recording rule of ``rollout_pd``, with the network in
+    the PD law's place; the gradients go to the parameters that require them and to x0."""
+    return _rollout_closed("rollout_mlp", "the parameters", model, mlp, noise, x0, T, particle_pred, status, meas)
 
 
 # measurement hook (bench.py): a pair of torch.cuda.Event recorded on the launch stream right around mcp_rollout_bwd -- the adjoint sweep

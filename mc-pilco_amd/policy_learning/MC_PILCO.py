@@ -18,6 +18,7 @@ Out of scope: MC_PILCO_Experiment, MuJoCo environments.
 import copy
 import pickle as pkl
 import time
+from functools import partial
 
 import numpy as np
 import torch
@@ -193,6 +194,28 @@ class MC_PILCO(torch.nn.Module):
         self.last_status, self.last_feedback_fused = status, feedback
         return states, inputs
 
+    def _fused_rollout(self, x0, T, p_dropout, model_of=None, meas_of=None, n_pos=0):
+        """The one place that picks the fused rollout of the control policy: what ``apply_policy`` returns, or None when nothing fuses (then
+        nothing was drawn; a feedback policy's ``fusable`` is asked about the packed model, so that may have been packed).  ``model_of()``:
+        the packed model to launch on (default: ``packed`` of a model with a fused layout); ``meas_of(pos_noise)``: the MeasSpec of a rollout
+        on simulated measurements of ``n_pos`` positions (MC_PILCO4PMS).  ``_rollout_noise`` is called once, on the branch that launches --
+        the reference's draw order: (mask_0;) per step eps_t, (position noise,) (mask_t).  Sharded: x0 and the eps buffers are drawn for the
+        whole swarm and sliced, Philox counts by global particle; the gradients reach the all-reduce through the parameters' .grad."""
+        pol, ml = self.control_policy, self.model_learning
+        if not _has_fused_layout(ml):
+            return None
+        model_of, meas_of = model_of or ml.packed, meas_of or (lambda pos_noise: None)
+        if isinstance(pol, _Policy.Sum_of_gaussians):  # (on measurements the kernels carry the filter's states per particle, mcp_meas)
+            noise, pos_noise, p = self._rollout_noise(T, p_dropout, n_pos=n_pos)
+            return self._fused(*ops.rollout(model_of(), pol.packed(), noise, x0, T, p, meas=meas_of(pos_noise), gp_sharding=self.gp_sharding))
+        # the closed loop under the PD law or the tanh MLP: one launch (and one sweep in backward), the eps draws and no dropout masks
+        op = ops.rollout_pd if isinstance(pol, _Policy.PD_controller) else ops.rollout_mlp if isinstance(pol, _Policy.MLP_policy) else None
+        model = model_of() if op is not None and self.fused_feedback else None
+        if model is None or not pol.fusable(model, T):
+            return None
+        noise, pos_noise, _ = self._rollout_noise(T, n_pos=n_pos)
+        return self._fused(*op(model, pol.packed(), noise, x0, T, meas=meas_of(pos_noise)), feedback=True)
+
     def apply_policy(self, particles_initial_state_mean, particles_initial_state_var, flg_particles_init_uniform, particles_init_up_bound,
                      particles_init_low_bound, flg_particles_init_multi_gauss, num_particles, T_control, p_dropout=0.0):
         """Simulates ``num_particles`` particles for ``T_control`` steps under the control policy.
@@ -202,19 +225,9 @@ class MC_PILCO(torch.nn.Module):
         pol, ml = self.control_policy, self.model_learning
         self.last_feedback_fused = False  # (reset before every branch: a run under another policy must not leave an earlier True standing)
         self.last_step_fused = False
-        if isinstance(pol, _Policy.Sum_of_gaussians) and _has_fused_layout(ml):
-            noise, _, p = self._rollout_noise(T, p_dropout)
-            return self._fused(*ops.rollout(ml.packed(), pol.packed(), noise, x0, T, p, gp_sharding=self.gp_sharding))
-        if self.fused_feedback and isinstance(pol, _Policy.PD_controller) and _has_fused_layout(ml) and pol.fusable(ml.packed(), T):
-            # the closed loop under the PD law, one launch (and one sweep in backward): the eps draws of _rollout_noise, no dropout masks.
-            # Sharded: the eps buffers are drawn for the whole swarm and sliced, Philox counts by global particle; the gains' gradients
-            # reach the step's all-reduce through their .grad (_cost_backward)
-            return self._fused(*ops.rollout_pd(ml.packed(), pol.packed(), self._rollout_noise(T)[0], x0, T), feedback=True)
-        if self.fused_feedback and isinstance(pol, _Policy.MLP_policy) and _has_fused_layout(ml) and pol.fusable(ml.packed(), T):
-            # the closed loop under the tanh MLP, one launch (and one sweep in backward): the eps draws of _rollout_noise.  Sharded as the
-            # PD law is: x0 and the eps buffers are drawn for the whole swarm and sliced, Philox counts by global particle (_shard[0]); the
-            # parameters' gradients reach the step's all-reduce through their .grad (_cost_backward)
-            return self._fused(*ops.rollout_mlp(ml.packed(), pol.packed(), self._rollout_noise(T)[0], x0, T), feedback=True)
+        out = self._fused_rollout(x0, T, p_dropout)
+        if out is not None:
+            return out
         # generic (unfused) path: any model / policy object with the reference's step interface
         self.last_status = None  # (no fused launch: the flags of an earlier fused rollout do not describe this one)
         if self._world()[0] > 1:
@@ -809,26 +822,10 @@ class MC_PILCO4PMS(MC_PILCO):
         pos, vel = list(self.pos_indeces), list(self.vel_indeces)
         self.last_feedback_fused = False  # (reset before every branch, as in MC_PILCO.apply_policy)
         self.last_step_fused = False
-        if self.fused and isinstance(pol, _Policy.Sum_of_gaussians) and _has_fused_layout(ml):
-            # one fused launch: the kernels carry the measurement filter's states per particle (mcp_meas); the reference's draw order is
-            # mask_0; per step: eps_t, position noise, mask_t
-            noise, pos_noise, p = self._rollout_noise(T, p_dropout, n_pos=len(pos))
-            return self._fused(*ops.rollout(self._measured_model(), pol.packed(), noise, x, T, p, meas=self._meas_spec(b, a, pos_noise),
-                                            gp_sharding=self.gp_sharding))
-        if self.fused and self.fused_feedback and isinstance(pol, _Policy.PD_controller) and _has_fused_layout(ml):
-            model = self._measured_model()
-            if pol.fusable(model, T):
-                # the closed loop under the PD law on the simulated measurement, one launch (and one sweep in backward); the reference's draw
-                # order per step: eps_t, position noise; no mask
-                noise, pos_noise, _ = self._rollout_noise(T, n_pos=len(pos))
-                return self._fused(*ops.rollout_pd(model, pol.packed(), noise, x, T, meas=self._meas_spec(b, a, pos_noise)), feedback=True)
-        if self.fused and self.fused_feedback and isinstance(pol, _Policy.MLP_policy) and _has_fused_layout(ml):
-            model = self._measured_model()
-            if pol.fusable(model, T):
-                # the closed loop under the tanh MLP on the simulated measurement, one launch (and one sweep in backward); the reference's
-                # draw order per step: eps_t, position noise; no mask
-                noise, pos_noise, _ = self._rollout_noise(T, n_pos=len(pos))
-                return self._fused(*ops.rollout_mlp(model, pol.packed(), noise, x, T, meas=self._meas_spec(b, a, pos_noise)), feedback=True)
+        # the fused rollouts of MC_PILCO.apply_policy, launched on the measured model with the measurement filter between particles and policy
+        out = self._fused_rollout(x, T, p_dropout, self._measured_model, partial(self._meas_spec, b, a), len(pos)) if self.fused else None
+        if out is not None:
+            return out
         self.last_status = None  # (no fused launch)
         if self._world()[0] > 1:  # (per-LOCAL-particle torch draws: identically seeded ranks would simulate correlated shards)
             raise NotImplementedError("particle sharding needs the fused rollout (fused=True, Sum_of_gaussians, PD_controller or MLP_policy "

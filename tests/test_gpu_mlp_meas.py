@@ -271,8 +271,8 @@ def test_shard_invariance(noise):
         else:
             nz, sp = ops.NoiseSpec(seed=4, call=2, particle_offset=a), spec(ms)
         status = torch.zeros(1, dtype=torch.int32, device=dev())
-        st, inp, jac = ops._rollout_mlp_launch(pm, mlp, tensors, nz, G(x0[a:b]), T, True, status, True, sp)
-        slabs, gx = ops._rollout_mlp_sweep(pm, mlp, tensors, st, inp, jac, G(w[:, a:b]), G(wu[:, a:b]), True, True, sp, sp.measured)
+        st, inp, jac = ops._closed_launch(pm, mlp, tensors, nz, G(x0[a:b]), T, True, status, True, sp)
+        slabs, gx = ops._closed_sweep(pm, mlp, tensors, st, inp, jac, G(w[:, a:b]), G(wu[:, a:b]), True, True, sp, sp.measured)
         torch.cuda.synchronize()
         assert int(status.item()) == 0
         return st, inp, sp.measured, slabs, gx

@@ -182,9 +182,9 @@ def test_determinism_and_shard_invariance():
 
     def run(a, b):
         x = G(x0[a:b])
-        st, inp, jac = ops._rollout_mlp_launch(pm, mlp, tensors, ops.NoiseSpec(seed=4, call=2, particle_offset=a), x, T, True,
-                                               torch.zeros(1, dtype=torch.int32, device=dev()), True)
-        slabs, gx = ops._rollout_mlp_sweep(pm, mlp, tensors, st, inp, jac, G(w[:, a:b]), G(wu[:, a:b]), True, True)
+        st, inp, jac = ops._closed_launch(pm, mlp, tensors, ops.NoiseSpec(seed=4, call=2, particle_offset=a), x, T, True,
+                                          torch.zeros(1, dtype=torch.int32, device=dev()), True)
+        slabs, gx = ops._closed_sweep(pm, mlp, tensors, st, inp, jac, G(w[:, a:b]), G(wu[:, a:b]), True, True)
         torch.cuda.synchronize()
         return st, inp, slabs, gx
 

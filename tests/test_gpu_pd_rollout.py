@@ -227,8 +227,8 @@ def test_shard_invariance():
 
     def run(a, b):
         x = G(x0[a:b])
-        st, inp, jac = ops._rollout_pd_launch(pm, pd, kpg, kdg, ops.NoiseSpec(seed=4, call=2, particle_offset=a), x, T, True,
-                                              torch.zeros(1, dtype=torch.int32, device=dev()), True)
+        st, inp, jac = ops._closed_launch(pm, pd, (kpg, kdg), ops.NoiseSpec(seed=4, call=2, particle_offset=a), x, T, True,
+                                          torch.zeros(1, dtype=torch.int32, device=dev()), True)
         gg = torch.empty(b - a, 2, c["U"], dtype=DT, device=dev())
         gx = torch.empty(b - a, c["S"], dtype=DT, device=dev())
         pc = pd.to_c(kpg, kdg)
