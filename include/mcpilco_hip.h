@@ -161,7 +161,7 @@ typedef struct mcp_policy {
  * id (m + particle_offset), so a sharded run draws the same numbers as a single-GPU run. */
 typedef struct mcp_noise {
   const double* eps;      /* [T-1][M][G] standard normals, or NULL                     */
-  const uint8_t* masks;   /* [T][M][B]   dropout keep-masks {0,1}, or NULL             */
+  const uint8_t* masks;   /* [T][M][B]   dropout keep-masks {0,1}, or NULL (mcp_rollout_mlp_drop: [T][M][H], the hidden units) */
   uint64_t seed;
   uint64_t call;          /* increments once per rollout so draws never repeat         */
   int64_t particle_offset;
@@ -457,6 +457,29 @@ int mcp_rollout_mlp_meas(const mcp_model* model, const mcp_mlp_policy* mlp, cons
 int mcp_rollout_mlp_meas_bwd(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_meas* meas, int M, int T, const double* states,
                              const double* inputs, const double* jac, const double* g_states, const double* g_inputs /* may be NULL */,
                              double* g_params, double* g_x0, void* stream);
+/* mcp_rollout_mlp / mcp_rollout_mlp_meas with INVERTED DROPOUT on the hidden units, behind the activation (MC-PILCO's regulariser, which
+ * the RBF policies have on their basis functions: mcp_policy.p_drop).  With s = 1 / (1 - p_drop):
+ *   h_l[j] = keep[t][m][off_l + j] ? s tanh(pre_l[j]) : 0,   off_0 = 0, off_1 = h[0],   H = h[0] (+ h[1])
+ * Features, the output layer and the squashing are never dropped.  One row of H decisions per policy evaluation: T rows, row T - 1
+ * included.  noise->masks non-NULL: [T][M][H] keep-masks {0,1}, layer 0's units first; NULL: Philox by (seed, call, m + particle_offset, t)
+ * on the stream of the RBF kernels' masks with the unit's index off_l + j in the basis function's place (a block of four may serve units of
+ * both layers), kept where the word is >= p_drop 2^32: shard-invariant.  call_dev and particle_offset as everywhere.  meas NULL or
+ * meas->n == 0: the network sees the true state.  Everything else -- outputs, status flags, T == 1, the tile ladder, the weights' LDS
+ * copy -- as mcp_rollout_mlp_meas; the bit identities of mcp_rollout_mlp (mcp_rollout_open on the launch's own inputs; plain against
+ * recording launch) hold.  p_drop == 0: the kernels of the entries without dropout on the same arguments, the same bits.  The argument
+ * checks of mcp_rollout_mlp_meas in their order (a NULL meas allowed); p_drop outside [0, 1) or NaN is MCP_ERR_ARG, looked at with the
+ * sizes -- before the limits. */
+int mcp_rollout_mlp_drop(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_meas* meas /* NULL or n == 0: the true state */,
+                         const mcp_noise* noise, double p_drop, int M, int T, int particle_pred, const double* x0, double* states, double* inputs,
+                         double* mu, double* var, double* jac /* NULL: no record */, uint32_t* status, void* stream);
+/* Reverse-time sweep of mcp_rollout_mlp_drop: mcp_rollout_mlp_meas_bwd with the forward's keep decisions, recomputed beside the
+ * activations from the SAME noise descriptor (the mask buffer, or seed / call / particle_offset / call_dev) and p_drop: a dropped unit
+ * passes no gradient, a kept one s (1 - tanh^2), to the parameter slabs and along the chain to g_x0 and the earlier rows alike.  g_params,
+ * g_x0, the slab layout, reproducibility and the argument checks as there (a NULL meas allowed; p_drop as in the forward entry); noise may
+ * be NULL only when p_drop == 0, which runs the kernels of the sweeps without dropout: the same bits. */
+int mcp_rollout_mlp_drop_bwd(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_meas* meas, const mcp_noise* noise, double p_drop, int M,
+                             int T, const double* states, const double* inputs, const double* jac, const double* g_states,
+                             const double* g_inputs /* may be NULL */, double* g_params, double* g_x0, void* stream);
 /* Reverse-time adjoint of the rollout: given dJ/dstates, dJ/dinputs (either may be NULL) returns
  * dJ/d{log_lengthscales [P], centers [B][P], f_linear.weight [U][B]} (overwritten, this rank's
  * particles only; with policy->bias also dJ/dbias into policy->g_bias) and optionally dJ/dx0 [M][S].  Replaces autograd's backward through

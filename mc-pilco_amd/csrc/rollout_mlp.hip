@@ -5,6 +5,8 @@
 //   mcp_rollout_mlp_bwd  the sweep: g_x0 and one partial slab of parameter gradients per workgroup of 16 trajectories
 //   mcp_rollout_mlp_meas, mcp_rollout_mlp_meas_bwd   the same pair with the network fed a simulated measurement of x_t (template PMS:
 //                        MC_PILCO4PMS.apply_policy, policy_learning/MC_PILCO.py:808-906, as mcp_rollout_pd_meas has it for the PD law)
+//   mcp_rollout_mlp_drop, mcp_rollout_mlp_drop_bwd   either pair with inverted dropout on the hidden units (template DROP; masks from the
+//                        launch's mcp_noise: a buffer, or Philox on the RBF masks' stream); p_drop == 0: the kernels without DROP
 // The forward kernel is the step loop of rollout_open.hip's feedback form with the PD law exchanged for the network: phases S, K, V, J, J', F
 // and the noise addressing are the same functions (rollout_open_phases.h) and the same statements on the same operands, and the library is
 // built without floating-point contraction, so the states carry the bits of mcp_rollout_open fed with the launch's own inputs.  Per step
@@ -128,8 +130,45 @@ __device__ __forceinline__ void mlp_layer_fwd(const double* W, const double* b, 
   }
 }
 
-template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool WLDS, bool PMS = false>
-__global__ __launch_bounds__(RF_NT) void rollout_mlp_kernel(typename MlpArgsOf<PMS>::type a) {
+// DROPOUT form (template DROP, mcp_rollout_mlp_drop): inverted dropout on the hidden units, behind the activation --
+//   h_l[j] = keep[t][m][off_l + j] ? tanh(pre_l[j]) / (1 - p) : 0,   off_0 = 0, off_1 = h[0],   H = h[0] (+ h[1])
+// one row of H keep decisions per policy evaluation (row T - 1 included), as the RBF policy has one of B: the launch's mask buffer
+// [T][M][H] where it has one, else philox_keep -- the RBF kernels' function and stream -- with the unit's index off_l + j in the basis
+// function's place (a Philox block of four may so serve units of both layers).  The decision is made by the thread that owns
+// (trajectory, unit); features, the output layer and the squashing are never dropped.  The forms without DROP take no part in any of it.
+struct MlpDropArgs {
+  uint32_t thr;          // drop_threshold(p)
+  double scale, keep_p;  // 1 / (1 - p), 1 - p
+};
+template <bool PMS>
+struct OpenArgsMlpDrop : MlpArgsOf<PMS>::type {
+  MlpDropArgs drop;
+};
+template <bool PMS, bool DROP>
+struct MlpKernelArgs {
+  typedef typename MlpArgsOf<PMS>::type type;
+};
+template <bool PMS>
+struct MlpKernelArgs<PMS, true> {
+  typedef OpenArgsMlpDrop<PMS> type;
+};
+// whether unit `unit` of trajectory m (of this launch's M; the descriptor adds particle_offset) is kept in row t
+__device__ __forceinline__ bool mlp_keep(const mcp_noise& nzl, uint32_t thr, int H, int M, int m, int t, int unit) {
+  return nzl.masks ? nzl.masks[((size_t)t * M + m) * H + unit] != 0 : philox_keep(nzl, m, t, unit, thr);
+}
+template <int PT>
+__device__ __forceinline__ void mlp_layer_fwd_drop(const double* W, const double* b, int pitch, int in, int out, const double* x, int xp, double* y,
+                                                   int yp, int tid, const mcp_noise& nzl, const MlpDropArgs& dr, int H, int off, int M, int m0, int t) {
+  for (int it = tid; it < PT * out; it += RF_NT) {
+    const int p = it / out, j = it - p * out;
+    const bool keep = mlp_keep(nzl, dr.thr, H, M, imin(m0 + p, M - 1), t, off + j);
+    const double h = fast_tanh(mlp_unit(W + j * pitch, b[j], x + p * xp, in));
+    y[p * yp + j] = keep ? dr.scale * h : 0.0;
+  }
+}
+
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool WLDS, bool PMS = false, bool DROP = false>
+__global__ __launch_bounds__(RF_NT) void rollout_mlp_kernel(typename MlpKernelArgs<PMS, DROP>::type a) {
   extern __shared__ double smem[];
   const mcp_model& md = a.model;
   const mcp_mlp_policy& pl = a.mlp;
@@ -282,14 +321,20 @@ __global__ __launch_bounds__(RF_NT) void rollout_mlp_kernel(typename MlpArgsOf<P
       }
     }
     lds_barrier();
-    if (WLDS) {
+    if constexpr (DROP) {
+      mlp_layer_fwd_drop<PT>(WLDS ? wlc + mg.wl[0] : wtab[0], WLDS ? wlc + mg.bl[0] : wtab[3], WLDS ? mg.pitch[0] : pl.P, pl.P, H0, fl, A.fp, hl0,
+                             A.hp[0], tid, nzl, a.drop, H0 + H1, 0, M, m0, t);
+    } else if (WLDS) {
       mlp_layer_fwd<PT>(wlc + mg.wl[0], wlc + mg.bl[0], mg.pitch[0], pl.P, H0, fl, A.fp, hl0, A.hp[0], tid);
     } else {
       mlp_layer_fwd<PT>(wtab[0], wtab[3], pl.P, pl.P, H0, fl, A.fp, hl0, A.hp[0], tid);
     }
     lds_barrier();
     if (nh > 1) {
-      if (WLDS) {
+      if constexpr (DROP) {
+        mlp_layer_fwd_drop<PT>(WLDS ? wlc + mg.wl[1] : wtab[1], WLDS ? wlc + mg.bl[1] : wtab[4], WLDS ? mg.pitch[1] : H0, H0, H1, hl0, A.hp[0], hl1,
+                               A.hp[1], tid, nzl, a.drop, H0 + H1, H0, M, m0, t);
+      } else if (WLDS) {
         mlp_layer_fwd<PT>(wlc + mg.wl[1], wlc + mg.bl[1], mg.pitch[1], H0, H1, hl0, A.hp[0], hl1, A.hp[1], tid);
       } else {
         mlp_layer_fwd<PT>(wtab[1], wtab[4], H0, H0, H1, hl0, A.hp[0], hl1, A.hp[1], tid);
@@ -448,25 +493,25 @@ static mcp_mlp_policy mlp_normalised(const mcp_mlp_policy* p) {
 
 // ---- host path of the forward entry: checks -> fill -> ladder -----------------------------------------------------------------------------
 // one rung: the weights in LDS where the layout then fits, else in global memory; MCP_ERR_LIMIT where the rung does not fit at all
-template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool WLDS, bool PMS>
-static int launch_mlp_w(const typename MlpArgsOf<PMS>::type& a, hipStream_t st) {
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool WLDS, bool PMS, bool DROP>
+static int launch_mlp_w(const typename MlpKernelArgs<PMS, DROP>::type& a, hipStream_t st) {
   const MlpActs A = mlp_acts(PT, a.mlp, mlp_geom(a.mlp), WLDS);
   const OpenLayout L = open_layout(PT, NEEDVAR, a.model.S, a.model.D, a.model.G, a.NpadMax, NEEDJAC, a.na, PMS, A.total);
   const size_t lds = (size_t)L.total * sizeof(double);
   if (lds > MCP_LDS_LIMIT) return MCP_ERR_LIMIT;
-  MCP_ENSURE_MAX_LDS((rollout_mlp_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, WLDS, PMS>));
-  hipLaunchKernelGGL((rollout_mlp_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, WLDS, PMS>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
+  MCP_ENSURE_MAX_LDS((rollout_mlp_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, WLDS, PMS, DROP>));
+  hipLaunchKernelGGL((rollout_mlp_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, WLDS, PMS, DROP>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
 }
-template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool PMS>
-static int launch_mlp(const typename MlpArgsOf<PMS>::type& a, hipStream_t st) {
-  const int rc = launch_mlp_w<PT, MAXDEG, NEEDVAR, NEEDJAC, true, PMS>(a, st);
-  return rc == MCP_ERR_LIMIT ? launch_mlp_w<PT, MAXDEG, NEEDVAR, NEEDJAC, false, PMS>(a, st) : rc;
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool PMS, bool DROP>
+static int launch_mlp(const typename MlpKernelArgs<PMS, DROP>::type& a, hipStream_t st) {
+  const int rc = launch_mlp_w<PT, MAXDEG, NEEDVAR, NEEDJAC, true, PMS, DROP>(a, st);
+  return rc == MCP_ERR_LIMIT ? launch_mlp_w<PT, MAXDEG, NEEDVAR, NEEDJAC, false, PMS, DROP>(a, st) : rc;
 }
-template <int PT, bool NEEDVAR, bool NEEDJAC, bool PMS>
-static int launch_mlp_deg(const typename MlpArgsOf<PMS>::type& a, int maxdeg, hipStream_t st) {
-  return maxdeg == 0 ? launch_mlp<PT, 0, NEEDVAR, NEEDJAC, PMS>(a, st) : launch_mlp<PT, 2, NEEDVAR, NEEDJAC, PMS>(a, st);
+template <int PT, bool NEEDVAR, bool NEEDJAC, bool PMS, bool DROP>
+static int launch_mlp_deg(const typename MlpKernelArgs<PMS, DROP>::type& a, int maxdeg, hipStream_t st) {
+  return maxdeg == 0 ? launch_mlp<PT, 0, NEEDVAR, NEEDJAC, PMS, DROP>(a, st) : launch_mlp<PT, 2, NEEDVAR, NEEDJAC, PMS, DROP>(a, st);
 }
 // The ladder of tiles of rollout_open.hip's launch_open_tiles (at every compiled limit at once the one-trajectory recording rung takes
 // 85 KB + 1.3 KB of activations, the measured form one row [PT][S] more: nothing within the limits is refused), entered one rung lower
@@ -477,26 +522,39 @@ static int launch_mlp_deg(const typename MlpArgsOf<PMS>::type& a, int maxdeg, hi
 // width changes no bit of a trajectory (a column of phases K, V, J is computed the same way in every width: the identities with
 // mcp_rollout_open hold across the rungs).
 #define MLP_SMALL_SWARM 1024  // 4 trajectories x the 256 compute units of the MI355X
-template <bool PMS>
-static int launch_mlp_tiles(const typename MlpArgsOf<PMS>::type& a, int maxdeg, bool wantvar, hipStream_t st) {
+template <bool PMS, bool DROP = false>
+static int launch_mlp_tiles(const typename MlpKernelArgs<PMS, DROP>::type& a, int maxdeg, bool wantvar, hipStream_t st) {
   const bool small = a.M <= MLP_SMALL_SWARM;
   if (!a.jac) {
-    if (!a.sample && !wantvar) return launch_mlp_deg<1, false, false, PMS>(a, maxdeg, st);
-    int rc = small ? MCP_ERR_LIMIT : launch_mlp_deg<16, true, false, PMS>(a, maxdeg, st);
-    if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<4, true, false, PMS>(a, maxdeg, st);
+    if (!a.sample && !wantvar) return launch_mlp_deg<1, false, false, PMS, DROP>(a, maxdeg, st);
+    int rc = small ? MCP_ERR_LIMIT : launch_mlp_deg<16, true, false, PMS, DROP>(a, maxdeg, st);
+    if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<4, true, false, PMS, DROP>(a, maxdeg, st);
     return rc;
   }
-  if (!a.sample && !wantvar) return launch_mlp_deg<1, false, true, PMS>(a, maxdeg, st);
-  int rc = small ? MCP_ERR_LIMIT : launch_mlp_deg<16, true, true, PMS>(a, maxdeg, st);
-  if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<4, true, true, PMS>(a, maxdeg, st);
-  if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<1, true, true, PMS>(a, maxdeg, st);
+  if (!a.sample && !wantvar) return launch_mlp_deg<1, false, true, PMS, DROP>(a, maxdeg, st);
+  int rc = small ? MCP_ERR_LIMIT : launch_mlp_deg<16, true, true, PMS, DROP>(a, maxdeg, st);
+  if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<4, true, true, PMS, DROP>(a, maxdeg, st);
+  if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<1, true, true, PMS, DROP>(a, maxdeg, st);
   return rc;
 }
 
-// what mcp_rollout_mlp and mcp_rollout_mlp_meas share (ms NULL: no measurement)
-static int mlp_dispatch(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_meas* ms, const mcp_noise* noise, int M, int T, int particle_pred,
-                        const double* x0, double* states, double* inputs, double* mu, double* var, double* jac, uint32_t* status, void* stream) {
-  const int crc = closed_loop_checks(model && mlp && noise && x0 && states && inputs && status, M, T, model, ms, false,
+// the dropout probability of the _drop entries: looked at with the sizes (a NaN is refused)
+static inline bool mlp_drop_ok(double p) { return p >= 0.0 && p < 1.0; }
+static inline MlpDropArgs mlp_drop_args(double p) { return MlpDropArgs{drop_threshold(p), 1.0 / (1.0 - p), 1.0 - p}; }
+// the arguments of a dropout form: those of the form without, and the probability's three numbers
+template <class DropArgs, class Args>
+static DropArgs mlp_with_drop(const Args& a, double p_drop) {
+  DropArgs d;
+  static_cast<Args&>(d) = a;
+  d.drop = mlp_drop_args(p_drop);
+  return d;
+}
+
+// what mcp_rollout_mlp, mcp_rollout_mlp_meas and mcp_rollout_mlp_drop share (ms NULL: no measurement; p_drop 0: the kernels without dropout)
+static int mlp_dispatch(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_meas* ms, const mcp_noise* noise, double p_drop, int M, int T,
+                        int particle_pred, const double* x0, double* states, double* inputs, double* mu, double* var, double* jac,
+                        uint32_t* status, void* stream) {
+  const int crc = closed_loop_checks(model && mlp && noise && x0 && states && inputs && status && mlp_drop_ok(p_drop), M, T, model, ms, false,
                                      [&] { return mlp_policy_check(model, mlp); });
   if (crc != MCP_OK) return crc;
   OpenArgsMlpMeas a;
@@ -505,15 +563,20 @@ static int mlp_dispatch(const mcp_model* model, const mcp_mlp_policy* mlp, const
   a.mlp = mlp_normalised(mlp);
   a.inputs = inputs;
   hipStream_t st = (hipStream_t)stream;
-  if (!meas_active(ms)) return launch_mlp_tiles<false>(a, maxdeg, var != nullptr, st);  // (the base part of `a`: mcp_rollout_mlp's own kernels)
+  const bool drop = p_drop > 0.0;
+  if (!meas_active(ms)) {
+    if (drop) return launch_mlp_tiles<false, true>(mlp_with_drop<OpenArgsMlpDrop<false>, OpenArgsMlp>(a, p_drop), maxdeg, var != nullptr, st);
+    return launch_mlp_tiles<false>(a, maxdeg, var != nullptr, st);  // (the base part of `a`: mcp_rollout_mlp's own kernels)
+  }
   a.ms = *ms;
+  if (drop) return launch_mlp_tiles<true, true>(mlp_with_drop<OpenArgsMlpDrop<true>, OpenArgsMlpMeas>(a, p_drop), maxdeg, var != nullptr, st);
   return launch_mlp_tiles<true>(a, maxdeg, var != nullptr, st);
 }
 
 extern "C" int mcp_rollout_mlp(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_noise* noise, int M, int T, int particle_pred,
                                const double* x0, double* states, double* inputs, double* mu, double* var, double* jac, uint32_t* status,
                                void* stream) {
-  return mlp_dispatch(model, mlp, nullptr, noise, M, T, particle_pred, x0, states, inputs, mu, var, jac, status, stream);
+  return mlp_dispatch(model, mlp, nullptr, noise, 0.0, M, T, particle_pred, x0, states, inputs, mu, var, jac, status, stream);
 }
 
 // Closed-loop rollout under the network evaluated on a simulated measurement: replaces the loop of MC_PILCO4PMS.apply_policy
@@ -524,7 +587,16 @@ extern "C" int mcp_rollout_mlp_meas(const mcp_model* model, const mcp_mlp_policy
                                     int particle_pred, const double* x0, double* states, double* inputs, double* mu, double* var, double* jac,
                                     uint32_t* status, void* stream) {
   if (!meas) return MCP_ERR_ARG;
-  return mlp_dispatch(model, mlp, meas, noise, M, T, particle_pred, x0, states, inputs, mu, var, jac, status, stream);
+  return mlp_dispatch(model, mlp, meas, noise, 0.0, M, T, particle_pred, x0, states, inputs, mu, var, jac, status, stream);
+}
+
+// mcp_rollout_mlp / mcp_rollout_mlp_meas with inverted dropout on the hidden units (MC-PILCO's regulariser, as policy_learning/Policy.py:223-225, 261
+// has it for the RBF policies' basis functions): the DROP forms above.  meas NULL or meas->n == 0: the network sees the true state.  p_drop == 0: the kernels of the
+// entries without dropout on the same arguments, the same bits.
+extern "C" int mcp_rollout_mlp_drop(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_meas* meas, const mcp_noise* noise, double p_drop,
+                                    int M, int T, int particle_pred, const double* x0, double* states, double* inputs, double* mu, double* var,
+                                    double* jac, uint32_t* status, void* stream) {
+  return mlp_dispatch(model, mlp, meas, noise, p_drop, M, T, particle_pred, x0, states, inputs, mu, var, jac, status, stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -591,14 +663,33 @@ struct MlpBwdArgsOf<true> {
   typedef MlpBwdArgsMeas type;
 };
 
+// DROPOUT form (template DROP, mcp_rollout_mlp_drop_bwd): the workers recompute the forward's keep decisions with the forward's function
+// (mlp_keep, from the launch's noise descriptor) beside the activations -- a row holds the forward's h_l, zeros and scale included, so the
+// outer sums need nothing more -- and leave the decisions of a row and trajectory as one ballot word per hidden layer; the chain tests its
+// unit's bit: a dropped unit passes nothing, a kept one (1 - tanh^2) / (1 - p) with tanh = (1 - p) h.  Three rows of 2 words per trajectory.
+template <bool PMS>
+struct MlpBwdArgsDrop : MlpBwdArgsOf<PMS>::type {
+  mcp_noise nz;
+  MlpDropArgs drop;
+};
+template <bool PMS, bool DROP>
+struct MlpBwdKernelArgs {
+  typedef typename MlpBwdArgsOf<PMS>::type type;
+};
+template <bool PMS>
+struct MlpBwdKernelArgs<PMS, true> {
+  typedef MlpBwdArgsDrop<PMS> type;
+};
+
 struct MlpBwdLayout {
   int rec, xs, gs, lam, gd, gz, tab, ul, gul, fbar, act, del, w, total;  // offsets in doubles
   int car, mtab;               // measured form: the filter's carries | pvel, ppos
+  int keep;                    // dropout form: the keep words [3][pts][2]
   int rp, fp, ap, dp;          // pitches: record row | fbar row | activation row | delta row (odd)
   int aoff[3], one, doff[3];   // inside an activation row: the input of layer l, the constant 1; inside a delta row: the output of layer l
 };
 __host__ __device__ inline MlpBwdLayout mlp_bwd_layout(int pts, int S, int U, int G, int D, const mcp_mlp_policy& p, const MlpGeom& g, bool wlds,
-                                                       bool pms = false) {
+                                                       bool pms = false, bool drop = false) {
   MlpBwdLayout L;
   int o = 0;
   auto take = [&](int n) {
@@ -633,6 +724,7 @@ __host__ __device__ inline MlpBwdLayout mlp_bwd_layout(int pts, int S, int U, in
   L.del = take(2 * pts * L.dp);
   L.car = pms ? take(2 * pts * S) : 0;     // [trajectory][position component]: mvbar | nvbar of the row behind
   L.mtab = pms ? take(MCP_MAX_STATE) : 0;  // ints: pvel (per state component: the velocity of the pair it is the position of, or -1) | ppos (the converse)
+  L.keep = drop ? take(3 * pts * 2) : 0;   // 64-bit words: bit j = unit j of hidden layer l of the row's trajectory is kept
   L.w = o;
   L.total = o + (wlds ? g.lds : 0);
   return L;
@@ -662,14 +754,24 @@ __device__ __forceinline__ const double* mlp_policy_rows(const typename MlpBwdAr
   }
 }
 
-template <bool WLDS, bool PMS = false>
-__global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdArgsOf<PMS>::type a) {
+// the launch's noise descriptor of a dropout form (read once, as in the forward kernel); the other forms have none
+template <bool PMS>
+__device__ __forceinline__ mcp_noise mlp_bwd_noise(const MlpBwdArgsDrop<PMS>& a) {
+  return noise_of_launch(a.nz);
+}
+template <class Args>
+__device__ __forceinline__ mcp_noise mlp_bwd_noise(const Args&) {
+  return mcp_noise{};
+}
+
+template <bool WLDS, bool PMS = false, bool DROP = false>
+__global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdKernelArgs<PMS, DROP>::type a) {
   extern __shared__ double smem[];
   const mcp_mlp_policy& pl = a.mlp;
   const int S = a.S, U = a.U, G = a.G, D = a.D, M = a.M, T = a.T, nna = a.nna, na = a.na, pts = a.pts;
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const MlpGeom mg = mlp_geom(pl);
-  const MlpBwdLayout L = mlp_bwd_layout(pts, S, U, G, D, pl, mg, WLDS, PMS);
+  const MlpBwdLayout L = mlp_bwd_layout(pts, S, U, G, D, pl, mg, WLDS, PMS, DROP);
   const int GD = G * D, RP = L.rp;
   double* rec = smem + L.rec;
   double* xsl = smem + L.xs;
@@ -694,6 +796,9 @@ __global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdA
   int* pvel = reinterpret_cast<int*>(smem + L.mtab);
   int* ppos = pvel + MCP_MAX_STATE;
   double* wlc = smem + L.w;
+  unsigned long long* kwl = reinterpret_cast<unsigned long long*>(smem + L.keep);  // (dropout form; so are the next two)
+  const mcp_noise nzl = mlp_bwd_noise(a);
+  const int Hd = pl.h[0] + pl.h[1];  // the width of a mask row (one hidden layer: h[1] = 0)
   const int nnp = pl.n_non_angle, nap = pl.n_angle, nl = mg.nl;
   // the weights as this kernel reads them (WLDS: the LDS copy, else global memory); the layer loops below are unrolled over the three
   // slots, so every index into these tables is a constant
@@ -791,7 +896,18 @@ __global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdA
 #pragma unroll
       for (int l = 0; l < 2; ++l) {
         if (l + 1 >= nl) continue;  // (uniform)
-        if (lane < mg.out[l]) A[L.aoff[l + 1] + lane] = fast_tanh(mlp_unit(Wl[l] + lane * wp[l], bl[l][lane], A + L.aoff[l], mg.in[l]));
+        if constexpr (DROP) {  // (every lane of the wave is here: the ballot is the layer's row of decisions)
+          const bool unit = lane < mg.out[l];
+          const bool keep = unit && mlp_keep(nzl, a.drop.thr, Hd, M, imin(mp0 + p, M - 1), r, L.doff[l] + lane);
+          const unsigned long long kw = __ballot(keep);
+          if (unit) {
+            const double h = fast_tanh(mlp_unit(Wl[l] + lane * wp[l], bl[l][lane], A + L.aoff[l], mg.in[l]));
+            A[L.aoff[l + 1] + lane] = keep ? a.drop.scale * h : 0.0;
+          }
+          if (lane == 0) kwl[((r % 3) * pts + p) * 2 + l] = kw;
+        } else if (lane < mg.out[l]) {
+          A[L.aoff[l + 1] + lane] = fast_tanh(mlp_unit(Wl[l] + lane * wp[l], bl[l][lane], A + L.aoff[l], mg.in[l]));
+        }
         wave_lds_sync();
       }
     }
@@ -903,7 +1019,12 @@ __global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdA
             const int j = q + 4 * i;
             if (j < mg.in[l]) {
               const double h = Ar[L.aoff[l] + j];
-              dr[L.doff[l - 1] + j] = acc[i] * (1.0 - h * h);
+              if constexpr (DROP) {
+                const double th = a.drop.keep_p * h;
+                dr[L.doff[l - 1] + j] = (kwl[((r % 3) * pts + p) * 2 + l - 1] >> j & 1ull) ? acc[i] * (a.drop.scale * (1.0 - th * th)) : 0.0;
+              } else {
+                dr[L.doff[l - 1] + j] = acc[i] * (1.0 - h * h);
+              }
             }
           }
           wave_lds_sync();
@@ -987,19 +1108,27 @@ __global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdA
   }
 }
 
-// what mcp_rollout_mlp_bwd and mcp_rollout_mlp_meas_bwd share (ms NULL: no measurement)
-template <bool WLDS, bool PMS>
-static int launch_mlp_bwd(const typename MlpBwdArgsOf<PMS>::type& a, size_t lds, hipStream_t st) {
-  MCP_ENSURE_MAX_LDS((rollout_mlp_bwd_kernel<WLDS, PMS>));
-  hipLaunchKernelGGL((rollout_mlp_bwd_kernel<WLDS, PMS>), dim3((a.M + MB_PT - 1) / MB_PT), dim3(MB_NT), lds, st, a);
+// what mcp_rollout_mlp_bwd, mcp_rollout_mlp_meas_bwd and mcp_rollout_mlp_drop_bwd share (ms NULL: no measurement; p_drop 0: the kernels
+// without dropout, and `noise` is not looked at)
+template <bool WLDS, bool PMS, bool DROP = false>
+static int launch_mlp_bwd(const typename MlpBwdKernelArgs<PMS, DROP>::type& a, size_t lds, hipStream_t st) {
+  MCP_ENSURE_MAX_LDS((rollout_mlp_bwd_kernel<WLDS, PMS, DROP>));
+  hipLaunchKernelGGL((rollout_mlp_bwd_kernel<WLDS, PMS, DROP>), dim3((a.M + MB_PT - 1) / MB_PT), dim3(MB_NT), lds, st, a);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
 }
-static int mlp_bwd_dispatch(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_meas* ms, int M, int T, const double* states,
-                            const double* inputs, const double* jac, const double* g_states, const double* g_inputs, double* g_params, double* g_x0,
-                            void* stream) {
-  const int crc = closed_loop_checks(model && mlp && states && inputs && g_states && (jac || T <= 1), M, T, model, ms, true,
-                                     [&] { return mlp_policy_check(model, mlp); });
+template <bool PMS, class Args>
+static int launch_mlp_bwd_drop(const Args& a, const mcp_noise* noise, double p_drop, size_t lds, hipStream_t st) {
+  MlpBwdArgsDrop<PMS> d = mlp_with_drop<MlpBwdArgsDrop<PMS>, Args>(a, p_drop);
+  d.nz = *noise;
+  return a.wlds ? launch_mlp_bwd<true, PMS, true>(d, lds, st) : launch_mlp_bwd<false, PMS, true>(d, lds, st);
+}
+static int mlp_bwd_dispatch(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_meas* ms, const mcp_noise* noise, double p_drop, int M, int T,
+                            const double* states, const double* inputs, const double* jac, const double* g_states, const double* g_inputs,
+                            double* g_params, double* g_x0, void* stream) {
+  const bool drop = p_drop > 0.0;
+  const int crc = closed_loop_checks(model && mlp && states && inputs && g_states && (jac || T <= 1) && mlp_drop_ok(p_drop) && (noise || !drop), M, T,
+                                     model, ms, true, [&] { return mlp_policy_check(model, mlp); });
   if (crc != MCP_OK) return crc;
   if (!g_x0 && !g_params) return MCP_OK;  // nothing asked for
   const bool pms = meas_active(ms);
@@ -1014,12 +1143,13 @@ static int mlp_bwd_dispatch(const mcp_model* model, const mcp_mlp_policy* mlp, c
   size_t lds = 0;
   for (int pts = MB_PT; pts >= 1 && !a.pts; pts >>= 1)
     for (int wl = 1; wl >= 0 && !a.pts; --wl) {
-      const MlpBwdLayout L = mlp_bwd_layout(pts, a.S, a.U, a.G, a.D, a.mlp, mg, wl != 0, pms);
+      const MlpBwdLayout L = mlp_bwd_layout(pts, a.S, a.U, a.G, a.D, a.mlp, mg, wl != 0, pms, drop);
       lds = (size_t)L.total * sizeof(double);
       if (lds <= MCP_LDS_LIMIT) a.pts = pts, a.wlds = wl;
     }
   if (!a.pts) return MCP_ERR_LIMIT;  // (not reached within the compiled limits: one trajectory takes 22 KB at all of them at once)
   hipStream_t st = (hipStream_t)stream;
+  if (drop) return pms ? launch_mlp_bwd_drop<true, MlpBwdArgsMeas>(a, noise, p_drop, lds, st) : launch_mlp_bwd_drop<false, MlpBwdArgs>(a, noise, p_drop, lds, st);
   if (pms) return a.wlds ? launch_mlp_bwd<true, true>(a, lds, st) : launch_mlp_bwd<false, true>(a, lds, st);
   return a.wlds ? launch_mlp_bwd<true, false>(a, lds, st) : launch_mlp_bwd<false, false>(a, lds, st);  // (the base part of `a`: mcp_rollout_mlp_bwd's own kernels)
 }
@@ -1027,7 +1157,7 @@ static int mlp_bwd_dispatch(const mcp_model* model, const mcp_mlp_policy* mlp, c
 extern "C" int mcp_rollout_mlp_bwd(const mcp_model* model, const mcp_mlp_policy* mlp, int M, int T, const double* states, const double* inputs,
                                    const double* jac, const double* g_states, const double* g_inputs, double* g_params, double* g_x0,
                                    void* stream) {
-  return mlp_bwd_dispatch(model, mlp, nullptr, M, T, states, inputs, jac, g_states, g_inputs, g_params, g_x0, stream);
+  return mlp_bwd_dispatch(model, mlp, nullptr, nullptr, 0.0, M, T, states, inputs, jac, g_states, g_inputs, g_params, g_x0, stream);
 }
 
 // Reverse-time sweep of the closed loop under the network on the simulated measurement: replaces autograd's backward (MC_PILCO.py:522)
@@ -1038,5 +1168,14 @@ extern "C" int mcp_rollout_mlp_meas_bwd(const mcp_model* model, const mcp_mlp_po
                                         const double* inputs, const double* jac, const double* g_states, const double* g_inputs, double* g_params,
                                         double* g_x0, void* stream) {
   if (!meas) return MCP_ERR_ARG;
-  return mlp_bwd_dispatch(model, mlp, meas, M, T, states, inputs, jac, g_states, g_inputs, g_params, g_x0, stream);
+  return mlp_bwd_dispatch(model, mlp, meas, nullptr, 0.0, M, T, states, inputs, jac, g_states, g_inputs, g_params, g_x0, stream);
+}
+
+// Reverse-time sweep of mcp_rollout_mlp_drop: the keep decisions are the forward's, recomputed from the same noise descriptor (the mask
+// buffer, or seed / call / particle_offset / call_dev), which is required when p_drop > 0.  p_drop == 0: the kernels of the sweeps without
+// dropout, the same bits.
+extern "C" int mcp_rollout_mlp_drop_bwd(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_meas* meas, const mcp_noise* noise, double p_drop,
+                                        int M, int T, const double* states, const double* inputs, const double* jac, const double* g_states,
+                                        const double* g_inputs, double* g_params, double* g_x0, void* stream) {
+  return mlp_bwd_dispatch(model, mlp, meas, noise, p_drop, M, T, states, inputs, jac, g_states, g_inputs, g_params, g_x0, stream);
 }

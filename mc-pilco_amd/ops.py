@@ -418,10 +418,11 @@ def _record_buffers(dev, T, M, S, U, G, D, jac):
             torch.empty(max(T - 1, 1), M, max(G, 1), D, dtype=DT, device=dev) if jac else None)
 
 
-def _open_operands(model, x0, u, T, lengths, noise, particle_pred, status):
+def _open_operands(model, x0, u, T, lengths, noise, particle_pred, status, mask_width=0):
     """The operands of the open-loop and PD rollouts as the library takes them: x0 [M,S] and u [T-1,Mu,U] (a 2-D u is one shared sequence;
     u None: the PD forms, ``T`` given) contiguous float64 on the model's device, ``lengths`` int32 [M], a NoiseSpec (checked under
-    ``particle_pred``) and the status word.  Returns (x0, u, T, lengths, noise, status)."""
+    ``particle_pred``; ``mask_width``: the width of a mask row of a policy with dropout, whose masks are checked either way) and the
+    status word.  Returns (x0, u, T, lengths, noise, status)."""
     dev = model.device
     x0 = x0.to(device=dev, dtype=DT).contiguous()
     if x0.dim() != 2 or x0.shape[1] != model.S:
@@ -436,7 +437,9 @@ def _open_operands(model, x0, u, T, lengths, noise, particle_pred, status):
         u, T = u.contiguous(), int(u.shape[0]) + 1
     noise = NoiseSpec() if noise is None else noise
     if particle_pred:
-        _check_noise(noise, T, M, model.G, 0)
+        _check_noise(noise, T, M, model.G, mask_width)
+    elif mask_width:
+        _check_noise(NoiseSpec(masks=noise.masks), T, M, model.G, mask_width)
     if lengths is not None:
         lengths = torch.as_tensor(lengths, dtype=torch.int32).to(dev).contiguous()
         if tuple(lengths.shape) != (M,):
@@ -659,6 +662,8 @@ def model_step(model: PackedModel, x, u, t, noise: Optional[NoiseSpec] = None, p
 #   fwd, bwd       the C entries (plain, measured) of the rollout and of the sweep; fwd_outputs: the order of the forward entry's output
 #                  pointers between ``inputs`` and ``status`` -- the two policies' entries differ there, and only there
 #   grad_tile, grad_shape   the raw parameter-gradient buffer of a sweep is [ceil(M / grad_tile)] + grad_shape
+#   fwd_drop, bwd_drop, drop_width   (a policy with dropout) the entries that take the probability -- and a measurement model or NULL, and
+#                  in the sweep the noise -- and the width of a row of its masks
 #   check(model, T)   the policy's own refusals
 class PackedPD:
     """mcp_pd_policy of a ``Policy.PD_controller`` (reference policy_learning/Policy.py:406-449): the two gain parameters are kept as they
@@ -726,6 +731,7 @@ class PackedMLP:
     (both lists empty: f = x)."""
 
     fwd, bwd = ("mcp_rollout_mlp", "mcp_rollout_mlp_meas"), ("mcp_rollout_mlp_bwd", "mcp_rollout_mlp_meas_bwd")
+    fwd_drop, bwd_drop = "mcp_rollout_mlp_drop", "mcp_rollout_mlp_drop_bwd"
     fwd_outputs = ("mu", "var", "jac")
     grad_tile = 16  # one slab of parameter gradients per workgroup of the sweep
 
@@ -747,6 +753,7 @@ class PackedMLP:
         self.shapes = [tuple(q.shape) for q in self.params]
         self.n_param = sum(int(q.numel()) for q in self.params)
         self.grad_shape = (self.n_param,)
+        self.drop_width = sum(self.hidden)  # a row of keep-masks: the hidden units, layer 0's first
         self.device = self.params[0].device
 
     def tensors(self):
@@ -789,9 +796,15 @@ def _meas_arg(meas, T, M, meas_buf):
     return [C.byref(mc)]
 
 
-def _closed_launch(model, packed, tensors, noise, x0, T, particle_pred, status, record, meas=None):
+def _drop_args(meas_arg, nz, p_drop):
+    """What a dropout entry takes between the policy and the sizes: the measurement model or NULL, the noise, the probability."""
+    return [meas_arg[0] if meas_arg else None, C.byref(nz), float(p_drop)]
+
+
+def _closed_launch(model, packed, tensors, noise, x0, T, particle_pred, status, record, meas=None, p_drop=0.0):
     """(states [T,M,S], inputs [T,M,U], jac or None) of ONE launch of the closed loop under ``packed`` over its parameter ``tensors``
-    (packed.fwd); ``record`` and T > 1: the recording form.  With ``meas`` the measured entry, which writes ``meas.measured`` [T,M,S]."""
+    (packed.fwd); ``record`` and T > 1: the recording form.  With ``meas`` the measured entry, which writes ``meas.measured`` [T,M,S].
+    ``p_drop`` > 0: the policy's dropout entry (packed.fwd_drop), whatever ``meas`` is."""
     M, dev = int(x0.shape[0]), model.device
     states, inputs, jac = _record_buffers(dev, T, M, model.S, model.U, model.G, model.D, record and T > 1)
     pc, nz = packed.to_c(*tensors), noise.to_c()
@@ -799,22 +812,26 @@ def _closed_launch(model, packed, tensors, noise, x0, T, particle_pred, status, 
     if meas is not None:
         meas_buf = meas.measured = torch.empty(T, M, model.S, dtype=DT, device=dev)  # (allocated as rollout_forward_raw allocates it)
     outputs = {"jac": jac, "mu": None, "var": None}
-    name = packed.fwd[meas is not None]
-    abi.check(getattr(abi.lib(), name)(_mc(model), C.byref(pc), *_meas_arg(meas, T, M, meas_buf), C.byref(nz), M, T,
+    marg = _meas_arg(meas, T, M, meas_buf)
+    name, head = (packed.fwd_drop, _drop_args(marg, nz, p_drop)) if p_drop > 0.0 else (packed.fwd[meas is not None], marg + [C.byref(nz)])
+    abi.check(getattr(abi.lib(), name)(_mc(model), C.byref(pc), *head, M, T,
                                        int(bool(particle_pred)), abi.ptr(x0), abi.ptr(states), abi.ptr(inputs),
                                        *[abi.ptr(outputs[k]) for k in packed.fwd_outputs], abi.ptr(status), abi.stream()), name)
     return states, inputs, jac
 
 
-def _closed_sweep(model, packed, tensors, states, inputs, jac, g_states, g_inputs, want_params, want_x0, meas=None, meas_buf=None):
+def _closed_sweep(model, packed, tensors, states, inputs, jac, g_states, g_inputs, want_params, want_x0, meas=None, meas_buf=None, noise=None,
+                  p_drop=0.0):
     """(raw parameter gradients [ceil(M / grad_tile)] + grad_shape or None, g_x0 [M,S] or None) of ONE reverse-time sweep over the record
-    (packed.bwd); with ``meas`` (and the measured states ``meas_buf`` its forward launch wrote) the measured entry."""
+    (packed.bwd); with ``meas`` (and the measured states ``meas_buf`` its forward launch wrote) the measured entry.  ``p_drop`` > 0: the
+    policy's dropout entry (packed.bwd_drop) with the forward launch's ``noise``, from which it recomputes the keep decisions."""
     T, M, dev = int(states.shape[0]), int(states.shape[1]), states.device
     g_x0 = torch.empty(M, model.S, dtype=DT, device=dev) if want_x0 else None
     raw = torch.empty(((M + packed.grad_tile - 1) // packed.grad_tile,) + packed.grad_shape, dtype=DT, device=dev) if want_params else None
     pc = packed.to_c(*tensors)
-    name = packed.bwd[meas is not None]
-    abi.check(getattr(abi.lib(), name)(_mc(model), C.byref(pc), *_meas_arg(meas, T, M, meas_buf), M, T, abi.ptr(states), abi.ptr(inputs),
+    marg = _meas_arg(meas, T, M, meas_buf)
+    name, head = (packed.bwd_drop, _drop_args(marg, noise.to_c(), p_drop)) if p_drop > 0.0 else (packed.bwd[meas is not None], marg)
+    abi.check(getattr(abi.lib(), name)(_mc(model), C.byref(pc), *head, M, T, abi.ptr(states), abi.ptr(inputs),
                                        abi.ptr(jac), abi.ptr(g_states), abi.ptr(g_inputs), abi.ptr(raw), abi.ptr(g_x0), abi.stream()), name)
     return raw, g_x0
 
@@ -824,12 +841,14 @@ class RolloutClosedFunction(torch.autograd.Function):
     under ``packed`` (a PackedPD or a PackedMLP); backward is the reverse-time sweep over the record, with both upstream gradients.  The
     sweep's raw parameter gradients (per trajectory, or per workgroup) are added in torch's fixed order (``sum(0)``); the GP model is
     frozen.  With a measurement model (``meas``) the two launches are the measured entries; the measured states [T,M,S] the forward launch
-    wrote (``meas.measured``) are saved with the record and handed to the sweep."""
+    wrote (``meas.measured``) are saved with the record and handed to the sweep.  With dropout (``p_drop`` > 0) the launch's noise goes to
+    the sweep as well: the keep decisions are not recorded, the sweep draws them again."""
 
     @staticmethod
-    def forward(ctx, model, packed, noise, T, particle_pred, status, meas, x0, *tensors):
-        states, inputs, jac = _closed_launch(model, packed, tensors, noise, x0, T, particle_pred, status, True, meas)
+    def forward(ctx, model, packed, noise, T, particle_pred, status, meas, p_drop, x0, *tensors):
+        states, inputs, jac = _closed_launch(model, packed, tensors, noise, x0, T, particle_pred, status, True, meas, p_drop)
         ctx.model, ctx.packed, ctx.has_jac, ctx.meas = model, packed, jac is not None, meas
+        ctx.noise, ctx.p_drop = noise, p_drop
         ctx.set_materialize_grads(False)
         # (saved tensors: autograd refuses a backward after an in-place change of any of them -- the record, or a parameter stepped too early)
         ctx.save_for_backward(states, inputs, *tensors, *((jac,) if jac is not None else ()), *((meas.measured,) if meas is not None else ()))
@@ -843,8 +862,8 @@ class RolloutClosedFunction(torch.autograd.Function):
         meas_buf = rest.pop(0) if ctx.meas is not None else None
         gs = torch.zeros_like(states) if g_states is None else g_states.to(dtype=DT).contiguous()
         gi = None if g_inputs is None else g_inputs.to(dtype=DT).contiguous()
-        want_x0, want = ctx.needs_input_grad[7], ctx.needs_input_grad[8:]
-        raw, g_x0 = _closed_sweep(ctx.model, packed, tensors, states, inputs, jac, gs, gi, any(want), want_x0, ctx.meas, meas_buf)
+        want_x0, want = ctx.needs_input_grad[8], ctx.needs_input_grad[9:]
+        raw, g_x0 = _closed_sweep(ctx.model, packed, tensors, states, inputs, jac, gs, gi, any(want), want_x0, ctx.meas, meas_buf, ctx.noise, ctx.p_drop)
         grads = [None] * n
         if raw is not None:
             flat, o = raw.sum(0).reshape(-1), 0  # the trajectories' / workgroups' rows added in torch's fixed order
@@ -853,23 +872,28 @@ class RolloutClosedFunction(torch.autograd.Function):
                 if want[i]:
                     grads[i] = flat[o:o + k].reshape(shp)
                 o += k
-        return (None, None, None, None, None, None, None, g_x0) + tuple(grads)
+        return (None, None, None, None, None, None, None, None, g_x0) + tuple(grads)
 
 
-def _rollout_closed(op, noun, model, packed, noise, x0, T, particle_pred, status, meas):
+def _rollout_closed(op, noun, model, packed, noise, x0, T, particle_pred, status, meas, p_drop=0.0):
     """What ``rollout_pd`` and ``rollout_mlp`` do (``op``: which, ``noun``: what its message calls the parameters -- the device refusal comes
     first and is raised whatever ``packed`` is, so the two words are not read from it): the checks, then the recording Function or, with
-    nothing to differentiate, one launch on detached tensors."""
+    nothing to differentiate, one launch on detached tensors.  ``p_drop``: the dropout probability of a policy that has dropout entries
+    (0: the calls made without it); its masks, [T,M,packed.drop_width] uint8, are checked here."""
     if not isinstance(x0, torch.Tensor) or not x0.is_cuda or any(not q.is_cuda for q in packed.params):
         raise RuntimeError("%s operates on GPU memory only (x0 and %s must be GPU tensors); there is no CPU path" % (op, noun))
     T = int(T)
     packed.check(model, T)
-    x0c, _, _, _, noise, status = _open_operands(model, x0, None, T, None, noise, particle_pred, status)
+    p_drop = float(p_drop)
+    if not 0.0 <= p_drop < 1.0:
+        raise RuntimeError("%s: p_drop must be in [0, 1)" % op)
+    x0c, _, _, _, noise, status = _open_operands(model, x0, None, T, None, noise, particle_pred, status, packed.drop_width if p_drop > 0.0 else 0)
     tensors = [q.contiguous() for q in packed.tensors()]
     if torch.is_grad_enabled() and (x0c.requires_grad or any(q.requires_grad for q in tensors)):
-        states, inputs = RolloutClosedFunction.apply(model, packed, noise, T, bool(particle_pred), status, meas, x0c, *tensors)
+        states, inputs = RolloutClosedFunction.apply(model, packed, noise, T, bool(particle_pred), status, meas, p_drop, x0c, *tensors)
     else:
-        states, inputs, _ = _closed_launch(model, packed, [q.detach() for q in tensors], noise, x0c.detach(), T, particle_pred, status, False, meas)
+        states, inputs, _ = _closed_launch(model, packed, [q.detach() for q in tensors], noise, x0c.detach(), T, particle_pred, status, False, meas,
+                                           p_drop)
     return states, inputs, status
 
 
@@ -885,10 +909,13 @@ def rollout_pd(model: PackedModel, pd: PackedPD, noise: Optional[NoiseSpec], x0,
 
 
 def rollout_mlp(model: PackedModel, mlp: PackedMLP, noise: Optional[NoiseSpec], x0, T, particle_pred=True, status=None,
-                meas: Optional[MeasSpec] = None):
+                meas: Optional[MeasSpec] = None, p_drop=0.0):
     """Closed-loop rollout under a tanh-MLP policy in ONE launch: arguments, return and recording rule of ``rollout_pd``, with the network in
-    the PD law's place; the gradients go to the parameters that require them and to x0."""
-    return _rollout_closed("rollout_mlp", "the parameters", model, mlp, noise, x0, T, particle_pred, status, meas)
+    the PD law's place; the gradients go to the parameters that require them and to x0.  ``p_drop`` > 0: inverted dropout on the hidden
+    units, h = keep ? tanh(.) / (1 - p_drop) : 0, one row of decisions per policy evaluation -- ``noise.masks`` [T,M,H] uint8 (H: the
+    hidden widths added, layer 0's units first) or, without a buffer, Philox by seed / call / global particle, shard-invariant; the sweep
+    draws the same decisions again.  0 (the default): the calls made without the argument."""
+    return _rollout_closed("rollout_mlp", "the parameters", model, mlp, noise, x0, T, particle_pred, status, meas, p_drop)
 
 
 # measurement hook (bench.py): a pair of torch.cuda.Event recorded on the launch stream right around mcp_rollout_bwd -- the adjoint sweep

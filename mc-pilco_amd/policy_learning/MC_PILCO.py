@@ -168,7 +168,8 @@ class MC_PILCO(torch.nn.Module):
         self._rollout_calls += 1
         if self.noise_mode != "reference":
             return self._philox_noise(), None, p
-        draws = reference_draws(self._m_total, T, self.model_learning.num_gp, self.dtype, B=getattr(pol, "num_basis", 0), p_drop=p, n_pos=n_pos)
+        B = getattr(pol, "num_basis", None) or getattr(pol, "drop_width", 0)  # a mask row: the basis functions, or an MLP's hidden units
+        draws = reference_draws(self._m_total, T, self.model_learning.num_gp, self.dtype, B=B, p_drop=p, n_pos=n_pos)
         eps, masks, pos_noise = (None if t is None else self._shard_slice(t, 1).to(self.device).contiguous() for t in draws)
         return ops.NoiseSpec(eps=eps, masks=masks), pos_noise, p
 
@@ -208,13 +209,16 @@ class MC_PILCO(torch.nn.Module):
         if isinstance(pol, _Policy.Sum_of_gaussians):  # (on measurements the kernels carry the filter's states per particle, mcp_meas)
             noise, pos_noise, p = self._rollout_noise(T, p_dropout, n_pos=n_pos)
             return self._fused(*ops.rollout(model_of(), pol.packed(), noise, x0, T, p, meas=meas_of(pos_noise), gp_sharding=self.gp_sharding))
-        # the closed loop under the PD law or the tanh MLP: one launch (and one sweep in backward), the eps draws and no dropout masks
-        op = ops.rollout_pd if isinstance(pol, _Policy.PD_controller) else ops.rollout_mlp if isinstance(pol, _Policy.MLP_policy) else None
+        # the closed loop under the PD law or the tanh MLP: one launch (and one sweep in backward); the eps draws, and for an MLP with
+        # dropout (flg_drop) the masks of its hidden units -- the PD law has none
+        mlp = isinstance(pol, _Policy.MLP_policy)
+        op = ops.rollout_pd if isinstance(pol, _Policy.PD_controller) else ops.rollout_mlp if mlp else None
         model = model_of() if op is not None and self.fused_feedback else None
         if model is None or not pol.fusable(model, T):
             return None
-        noise, pos_noise, _ = self._rollout_noise(T, n_pos=n_pos)
-        return self._fused(*op(model, pol.packed(), noise, x0, T, meas=meas_of(pos_noise)), feedback=True)
+        noise, pos_noise, p = self._rollout_noise(T, p_dropout if mlp and pol.flg_drop else None, n_pos=n_pos)
+        drop = dict(p_drop=p) if p > 0.0 else {}
+        return self._fused(*op(model, pol.packed(), noise, x0, T, meas=meas_of(pos_noise), **drop), feedback=True)
 
     def apply_policy(self, particles_initial_state_mean, particles_initial_state_var, flg_particles_init_uniform, particles_init_up_bound,
                      particles_init_low_bound, flg_particles_init_multi_gauss, num_particles, T_control, p_dropout=0.0):

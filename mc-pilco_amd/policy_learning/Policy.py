@@ -151,11 +151,19 @@ class MLP_policy(Policy):
     Wout, bout; by default the weights are randn / sqrt(fan_in) and the biases zero (``weight_init``: the tensors' values in that order).
     ``forward`` is the torch formula.  As ``MC_PILCO``'s control policy on a GPU model with a fused layout it runs inside the fused closed
     loop (``packed()``, ``fusable()``; ops.rollout_mlp: one launch, and the reverse-time sweep for the parameters' gradients); with
-    ``MC_PILCO.fused_feedback = False`` the same object runs the step loop.  No dropout: ``p_dropout`` is accepted and ignored."""
+    ``MC_PILCO.fused_feedback = False`` the same object runs the step loop.
+    Dropout (``flg_drop=True``; MC-PILCO's regulariser, which the RBF policies have on their basis functions): inverted dropout on the hidden
+    units behind the activation, h_l = keep_l * tanh(.) / (1 - p_dropout) with one row ``keep`` of ``drop_width`` = sum(hidden_sizes)
+    decisions per call and particle, layer 0's units first; features, the output layer and the squashing are never dropped.  ``forward``
+    draws the row with ONE ``bernoulli_(1 - p)`` call, ``MC_PILCO.reference_draws``' own (on ``draw_device``, set by MC_PILCO in "reference"
+    noise mode, else on the policy's device), so the step loop and the fused launch see the same masks from the same seed; the fused
+    launch takes them as a buffer or draws them in the kernel (ops.rollout_mlp, ``p_drop``).  ``flg_drop=False`` (the default):
+    ``p_dropout`` is accepted and ignored."""
 
     def __init__(self, state_dim, input_dim, hidden_sizes, angle_indices=None, non_angle_indices=None, u_max=1.0, flg_squash=True, weight_init=None,
-                 dtype=torch.float64, device=torch.device("cuda")):
+                 dtype=torch.float64, device=torch.device("cuda"), flg_drop=False):
         super().__init__(state_dim=state_dim, input_dim=input_dim, flg_squash=flg_squash, u_max=u_max, dtype=dtype, device=device)
+        self.flg_drop = bool(flg_drop)
         self.hidden_sizes = [int(h) for h in np.atleast_1d(hidden_sizes)]
         if len(self.hidden_sizes) not in (1, 2) or any(h < 1 for h in self.hidden_sizes):
             raise ValueError("hidden_sizes holds one or two positive widths")
@@ -163,6 +171,7 @@ class MLP_policy(Policy):
         self.non_angle_indices = [] if non_angle_indices is None else [int(i) for i in np.atleast_1d(non_angle_indices)]
         self._lists = bool(self.angle_indices or self.non_angle_indices)
         self.feature_dim = len(self.non_angle_indices) + 2 * len(self.angle_indices) if self._lists else int(state_dim)
+        self.drop_width = sum(self.hidden_sizes)  # a row of dropout decisions: the hidden units, layer 0's first
         widths = [self.feature_dim] + self.hidden_sizes + [int(input_dim)]
         names = ["0", "1", "out"] if len(self.hidden_sizes) == 2 else ["0", "out"]
         self._names = []
@@ -201,8 +210,18 @@ class MLP_policy(Policy):
     def forward(self, states, t=None, p_dropout=0.0):
         h = self.features(states)
         ps = self.mlp_parameters()
-        for l in range(len(self.hidden_sizes)):
+        p = float(p_dropout) if self.flg_drop else 0.0
+        keep = None
+        if p > 0.0:
+            M, H = h.shape[0], self.drop_width
+            ddev = getattr(self, "draw_device", None) or self.device
+            keep = torch.empty(M, 1, H, dtype=self.dtype, device=ddev).bernoulli_(1 - p).reshape(M, H).to(self.device)
+        off = 0
+        for l, width in enumerate(self.hidden_sizes):
             h = torch.tanh(h @ ps[2 * l].t() + ps[2 * l + 1])
+            if keep is not None:
+                h = keep[:, off:off + width] * h * (1.0 / (1.0 - p))
+                off += width
         return self.f_squash(h @ ps[-2].t() + ps[-1])
 
     def _u_max_values(self):
