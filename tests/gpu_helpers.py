@@ -16,6 +16,23 @@ def G(a):
     return torch.as_tensor(np.asarray(a), dtype=DT).to(dev()).contiguous()
 
 
+def relmax(a, b):
+    """max |a - b| relative to max |b|."""
+    a, b = a.detach().cpu(), b.detach().cpu()
+    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-300))
+
+
+def rbf_dict(D, ls, sigma_n):
+    """The init dict of a gpr_lib RBF GP, as tests/golden/make_golden.py gave the reference's."""
+    return dict(active_dims=np.arange(D), lengthscales_init=np.asarray(ls, dtype=float), flg_train_lengthscales=True, lambda_init=np.ones(1),
+                flg_train_lambda=False, sigma_n_init=sigma_n * np.ones(1), sigma_n_num=None, flg_train_sigma_n=True, dtype=DT, device=dev())
+
+
+def mpk_dict(D, deg, weights):
+    return dict(active_dims=np.arange(D), poly_deg=deg, Sigma_pos_par_init_list=weights, flg_train_Sigma_pos_par_list=[True] * deg, dtype=DT,
+                device=dev())
+
+
 def spec_from(ls, sigma_n, lam=1.0, poly_w=None):
     """poly_w: list of raw (positive) weight vectors as given to the reference's
     Sigma_pos_par_init_list (their log is the parameter)."""

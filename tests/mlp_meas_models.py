@@ -18,19 +18,8 @@ DT = torch.float64
 
 
 def meas_model(shape, variant="all", std=0.1):
-    """pd_meas_models.meas_model for the shapes of mlp_models (``limits`` included): every joint measured, one pair only, or the pairs listed
-    in reverse order; one std per pair."""
-    c = mm.SHAPES[shape]
-    h = c["S"] // 2
-    pos, vel = list(range(h)), list(range(h, 2 * h))
-    if variant == "one":
-        pos, vel = pos[:1], vel[:1]
-    elif variant == "reversed":
-        pos, vel = pos[::-1], vel[::-1]
-    elif variant != "all":
-        raise ValueError(variant)
-    stds = [std * (1.0 + 0.5 * i) for i in range(len(pos))] if std else [0.0] * len(pos)
-    return dict(pos=pos, vel=vel, std=stds, b=list(pm.FILTER["b"]), a=list(pm.FILTER["a"]), Ts=c["Ts"])
+    """pd_meas_models.meas_model for the shapes of mlp_models (``limits`` included)."""
+    return pm.meas_model(shape, variant, std, shapes=mm.SHAPES)
 
 
 def mlp_meas_truth(shape, m, x0, params, eps, pos_noise, w, wu, sample, angle, non_angle, ms, u_max=1.0, squash=True, var_scale=None, defect=None):

@@ -15,9 +15,10 @@ DT = torch.float64
 FILTER = dict(b=[0.42, 0.31], a=[1.25, -0.38])
 
 
-def meas_model(shape, variant="all", std=0.1):
-    """{pos, vel, std, b, a, Ts} of a case: every joint measured, one pair only, or the pairs listed in reverse order."""
-    c = SHAPES[shape]
+def meas_model(shape, variant="all", std=0.1, shapes=SHAPES):
+    """{pos, vel, std, b, a, Ts} of a case on a shape of the table ``shapes``: every joint measured, one pair only, or the pairs listed in
+    reverse order."""
+    c = shapes[shape]
     h = c["S"] // 2
     pos, vel = list(range(h)), list(range(h, 2 * h))
     if variant == "one":

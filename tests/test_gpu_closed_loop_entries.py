@@ -6,12 +6,14 @@ M = 5, T = 3; T = 1 (no transition: nothing to record) once per policy."""
 import pytest
 import torch
 
+from closed_loop_family import PD, controller
+from closed_loop_family import policy as mlp_policy
+from gpu_helpers import G
 from mlp_models import network
 from pd_models import inputs_for
-from test_gpu_mlp_rollout import policy as mlp_policy
-from test_gpu_pd_rollout import G, controller, pair
 
 pytestmark = pytest.mark.gpu
+pair = PD.pair
 
 # (policy kind, measured) -> (the mcp_rollout_* entries of forward, of backward)
 ENTRIES = {

@@ -4,16 +4,14 @@ reference's golden rollouts (tests/golden/make_golden_delta.py) on every kernel 
 teacher-forced at the real size, and particle-sharded over two ranks."""
 import contextlib
 import io
-import os
-import socket
 
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
 
 import conftest  # noqa: F401  (registers the package, also in spawned workers)
-from gpu_helpers import VARIANTS
+from gpu_helpers import VARIANTS, mpk_dict, rbf_dict
+from rank_harness import rank_group, run_ranks
 
 pytestmark = pytest.mark.gpu
 DT = torch.float64
@@ -153,16 +151,6 @@ def test_delta_backward_forms(golden, name, lean, bwd):
 
 
 # ---- (b) drop-in: the project's own MC_PILCO with a delta model -----------------------------------------------------------------------
-def rbf_dict(D, ls, sigma_n):
-    return dict(active_dims=np.arange(D), lengthscales_init=np.asarray(ls, dtype=float), flg_train_lengthscales=True, lambda_init=np.ones(1),
-                flg_train_lambda=False, sigma_n_init=sigma_n * np.ones(1), sigma_n_num=None, flg_train_sigma_n=True, dtype=DT, device=dev())
-
-
-def mpk_dict(D, deg, weights):
-    return dict(active_dims=np.arange(D), poly_deg=deg, Sigma_pos_par_init_list=weights, flg_train_Sigma_pos_par_list=[True] * deg, dtype=DT,
-                device=dev())
-
-
 def build_delta_model(fx, states_tr=None, inputs_tr=None):
     from mc_pilco_amd.model_learning import Model_learning as ML
 
@@ -330,61 +318,32 @@ def test_delta_reinforce_policy_loops_agree(golden):
 
 
 # ---- (e) particle sharding over two ranks -----------------------------------------------------------------------------------------------
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _shard_run(rank, world, port, out_q, fx):
-    import torch.distributed as dist
-
     import mcp_boot  # noqa: F401
 
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
     torch.cuda.set_device(dev())
-    if world > 1:
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-    ml = build_delta_model(fx)
-    obj = build_mcpilco(fx, ml)
-    obj.noise_mode = "philox"
-    if world > 1:
-        obj.shard_particles(dist.group.WORLD)
-    M, Tn = 48, 10
-    torch.manual_seed(3)
-    st, inp = _apply(obj, fx, M=M, Tn=Tn)
-    cost, std, flags = obj._cost_backward(st, inp, 0)
-    torch.cuda.synchronize()
-    pol = obj.control_policy
-    res = (float(cost), float(std), [q.grad.cpu().numpy().copy() for q in (pol.log_lengthscales, pol.centers, pol.f_linear.weight)],
-           st.detach().cpu().numpy(), obj._shard[0], obj._shard[1])
-    if rank == 0:
-        out_q.put(res)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    with rank_group(rank, world, port) as group:
+        ml = build_delta_model(fx)
+        obj = build_mcpilco(fx, ml)
+        obj.noise_mode = "philox"
+        if world > 1:
+            obj.shard_particles(group)
+        M, Tn = 48, 10
+        torch.manual_seed(3)
+        st, inp = _apply(obj, fx, M=M, Tn=Tn)
+        cost, std, flags = obj._cost_backward(st, inp, 0)
+        torch.cuda.synchronize()
+        pol = obj.control_policy
+        res = (float(cost), float(std), [q.grad.cpu().numpy().copy() for q in (pol.log_lengthscales, pol.centers, pol.f_linear.weight)],
+               st.detach().cpu().numpy(), obj._shard[0], obj._shard[1])
+        if rank == 0:
+            out_q.put(res)
 
 
 def test_delta_two_rank_sharding_matches_single_process(golden):
     fx = dict(golden("rollout_delta"))
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    p1 = ctx.Process(target=_shard_run, args=(0, 1, 0, q, fx))
-    p1.start()
-    c1, s1, g1, st1, _, _ = q.get(timeout=300)
-    p1.join(timeout=60)
-    assert p1.exitcode == 0
-    port = _free_port()
-    procs = [ctx.Process(target=_shard_run, args=(r, 2, port, q, fx)) for r in range(2)]
-    for p in procs:
-        p.start()
-    c2, s2, g2, st2, off, cnt = q.get(timeout=300)
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    c1, s1, g1, st1, _, _ = run_ranks(_shard_run, 1, args=(fx,))[0]
+    c2, s2, g2, st2, off, cnt = run_ranks(_shard_run, 2, args=(fx,), expect=1)[0]
     assert cnt < st1.shape[1]
     assert np.array_equal(st2, st1[:, off:off + cnt])  # same noise per GLOBAL particle
     assert abs(c2 - c1) < 1e-13 * abs(c1)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import mpk_dict, rbf_dict  # noqa: F401  (other modules take them from here)
 from mc_pilco_amd import synthetic as sy
 
 pytestmark = pytest.mark.gpu
@@ -22,16 +23,6 @@ def dev():
 
 def T(a):
     return torch.tensor(np.asarray(a), dtype=dtype, device=dev())
-
-
-def rbf_dict(D, ls, sigma_n):
-    return dict(active_dims=np.arange(D), lengthscales_init=np.asarray(ls, dtype=float), flg_train_lengthscales=True, lambda_init=np.ones(1),
-                flg_train_lambda=False, sigma_n_init=sigma_n * np.ones(1), sigma_n_num=None, flg_train_sigma_n=True, dtype=dtype, device=dev())
-
-
-def mpk_dict(D, deg, weights):
-    return dict(active_dims=np.arange(D), poly_deg=deg, Sigma_pos_par_init_list=weights, flg_train_Sigma_pos_par_list=[True] * deg, dtype=dtype,
-                device=dev())
 
 
 def relerr(a, b):

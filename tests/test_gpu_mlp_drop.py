@@ -3,78 +3,44 @@ MC_PILCO / MC_PILCO4PMS.apply_policy with a Policy.MLP_policy(flg_drop=True), an
 through the oracle's step with the network and its keep-masks written out (tests/mlp_drop_models.drop_truth; conditioning checked by
 tests/test_mlp_drop_cpu.py), the Philox masks against the buffer masks bit for bit, and the bitwise contracts that survive dropout.
 
-Bounds (tests/test_gpu_mlp_rollout.py:19, on the oracle's own Kinv / alpha; 1 / (1 - p) <= 2 does not change the scale):
+Bounds (tests/test_gpu_mlp_rollout.py, on the oracle's own Kinv / alpha; 1 / (1 - p) <= 2 does not change the scale):
 states and measurements 1e-9 absolute, inputs 2e-9 absolute, every parameter gradient and g_x0 1e-9 relative to that tensor's largest magnitude."""
 import contextlib
 import ctypes as C
 import io
-import os
 
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
 
-import conftest  # noqa: F401  (registers the package, also in spawned workers)
+import closed_loop_family as clf
+from closed_loop_family import MLP, policy
+from closed_loop_family import meas_spec as spec
+from gpu_helpers import DT, G, dev, relmax
 from mlp_drop_models import CASES, case_id, case_truth, truth_of
 from mlp_meas_models import meas_model
 from mlp_models import SHAPES, inputs_for, network
 from pd_meas_models import pos_noise_for
+from rank_harness import rank_group, run_ranks
 
 pytestmark = pytest.mark.gpu
-DT = torch.float64
 STATE_TOL, INPUT_TOL, GRAD_TOL = 1e-9, 2e-9, 1e-9
-
-
-def dev():
-    return torch.device("cuda", 0)
-
-
-def G(a):
-    return torch.as_tensor(np.asarray(a), dtype=DT).to(dev()).contiguous()
+TOLS = (STATE_TOL, INPUT_TOL, GRAD_TOL)
 
 
 def K(masks):
     return masks.to(torch.uint8).to(dev()).contiguous()
 
 
-def relmax(a, b):
-    a, b = a.detach().cpu(), b.detach().cpu()
-    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-300))
-
-
 def pair(shape, N, deg):
     """(cfg, oracle model, PackedModel) of tests/test_gpu_mlp_meas.py: shared with that module, with the sampling time a measurement needs."""
-    from test_gpu_mlp_meas import pair as base
-
-    return base(shape, N, deg)
-
-
-def policy(*a, **kw):
-    from test_gpu_mlp_rollout import policy as base
-
-    return base(*a, **kw)
-
-
-def spec(ms, pos_noise=None):
-    from test_gpu_mlp_meas import spec as base
-
-    return None if ms is None else base(ms, pos_noise)
+    return MLP.pair(shape, N, deg, measured=True)
 
 
 def gpu_run(pm, pol, ins, T, noise, p, x0_grad=True, **edit):
-    """(states, inputs, [parameter gradients or None], g_x0, status) of the op with L = sum w states + sum wu inputs on a case's inputs."""
-    from mc_pilco_amd import ops
-
+    """The Run of the op with L = sum w states + sum wu inputs on a case's inputs."""
     q = dict(ins, **edit)
-    for t in pol.parameters():
-        t.grad = None
-    xg = G(q["x0"]).requires_grad_(x0_grad)
-    kw = {} if p is None else dict(p_drop=p)
-    st, inp, status = ops.rollout_mlp(pm, pol.packed(), noise, xg, T, particle_pred=q["sample"], meas=spec(q["ms"], q["pos_noise"]), **kw)
-    L = (G(q["w"]) * st).sum() + (0.0 if q["wu"] is None else (G(q["wu"]) * inp).sum())
-    L.backward()
-    return st.detach(), inp.detach(), [None if t.grad is None else t.grad.clone() for t in pol.mlp_parameters()], xg.grad, int(status.item())
+    return MLP.run(pm, pol, q["x0"], T, noise, q["w"], q["wu"], q["sample"], meas=spec(q["ms"], q["pos_noise"]), p_drop=p, x0_grad=x0_grad)
 
 
 def buffers(ins, masks=None):
@@ -84,18 +50,8 @@ def buffers(ins, masks=None):
 
 
 def check_against(truth, got, only=None, what=""):
-    ost, oin, ograds, ogx, vmin = truth
-    st, inp, grads, gx, status = got
-    es, ei = float((st.cpu() - ost).abs().max()), float((inp.cpu() - oin).abs().max())
-    if only is None:
-        eg, ex = [relmax(g, o) for g, o in zip(grads, ograds)], relmax(gx, ogx)
-    else:
-        assert gx is None and all((g is None) == (i != only) for i, g in enumerate(grads))
-        eg, ex = [relmax(grads[only], ograds[only])], 0.0
-    print("%s: states %.3e inputs %.3e g_params %s g_x0 %.3e (min var %.3e)" % (what, es, ei, " ".join("%.3e" % e for e in eg), ex, vmin))
-    assert status == 0
-    assert es < STATE_TOL and ei < INPUT_TOL
-    assert max(eg) < GRAD_TOL and ex < GRAD_TOL
+    """The states, inputs and gradients of a Run against drop_truth's tuple.  (The measurements are not part of that truth.)"""
+    clf.check_against(MLP, what, clf.mlp_truth_of(truth), got, TOLS, only)
 
 
 # ---- 1. parity with the truth, buffer mode ------------------------------------------------------------------------------------------------------
@@ -332,32 +288,13 @@ def test_mask_buffers_are_checked():
 def test_philox_mode_against_central_differences():
     """Step 1e-6, bound 1e-5 relative with floor 1e-3, as tests/test_gpu_mlp_rollout.py::test_philox_mode_against_central_differences; two
     entries of every parameter tensor and of x0.  (The keep decisions do not depend on the operands: the loss is smooth in them.)"""
-    from mc_pilco_amd import ops
-
     c, m, pm = pair("arm2", 37, 2)
     M, T, hidden, p = 3, 6, (7, 3), 0.25
     x0, _, _, _, _, w, wu = inputs_for(c, M, T, seed=5)
     params = network(c, hidden, c["angle"], c["not_angle"], 5)
-    nz = lambda: ops.NoiseSpec(seed=77, call=5)
-    ins = dict(x0=x0, w=w, wu=wu, sample=True, ms=None, pos_noise=None)
-    _, _, grads, gx, status = gpu_run(pm, policy(c, params, hidden), ins, T, nz(), p)
-    assert status == 0
-
-    def loss(params_, x0_):
-        st, inp, s = ops.rollout_mlp(pm, policy(c, params_, hidden, trainable=False).packed(), nz(), G(x0_), T, particle_pred=True, p_drop=p)
-        assert int(s.item()) == 0
-        return float((G(w) * st).sum() + (G(wu) * inp).sum())
-
-    h = 1e-6
-    for i, q in enumerate(params + [x0]):
-        g = (grads + [gx])[i].cpu().reshape(-1)
-        for e in (0, q.numel() - 1):
-            plus, minus = [t.clone() for t in params + [x0]], [t.clone() for t in params + [x0]]
-            plus[i].reshape(-1)[e] += h
-            minus[i].reshape(-1)[e] -= h
-            fd = (loss(plus[:-1], plus[-1]) - loss(minus[:-1], minus[-1])) / (2 * h)
-            print("tensor %d entry %d: fd %.9e adjoint %.9e" % (i, e, fd, float(g[e])))
-            assert abs(fd - float(g[e])) < 1e-5 * max(abs(float(g[e])), 1e-3)
+    policy_of = lambda tensors, trainable: policy(c, tensors, hidden, trainable=trainable)
+    clf.central_differences(MLP, pm, policy_of, params, x0, w, wu, T, clf.first_and_last_entries(params + [x0]), step=1e-6,
+                            bound=(1e-5, 1e-3), p_drop=p)
 
 
 # ---- 6. class path, "reference" noise mode ------------------------------------------------------------------------------------------------------
@@ -365,28 +302,18 @@ def _object(cls_name, params, hidden, M, flg_drop=True):
     """The MC_PILCO / MC_PILCO4PMS objects of tests/test_gpu_mlp_rollout.py and tests/test_gpu_mlp_meas.py with a policy built with ``flg_drop``;
     its masks are drawn where "reference" mode draws everything: on the CPU."""
     from mc_pilco_amd.policy_learning import Policy
-    from test_gpu_mlp_meas import _pms_object
-    from test_gpu_mlp_rollout import _arm_object
 
-    obj = (_arm_object if cls_name == "MC_PILCO" else _pms_object)(params, hidden, M)
-    c = SHAPES["arm2"]
-    kw = dict(flg_drop=True) if flg_drop else {}
-    obj.control_policy = Policy.MLP_policy(state_dim=4, input_dim=2, hidden_sizes=list(hidden), angle_indices=c["angle"], non_angle_indices=c["not_angle"],
-                                           u_max=1.5, flg_squash=True, weight_init=params, dtype=DT, device=dev(), **kw)
+    obj = clf.arm_object(Policy.MLP_policy, clf.arm_mlp_par(params, hidden), clf.ARM_PMS if cls_name == "MC_PILCO4PMS" else None)
+    obj.control_policy = Policy.MLP_policy(**clf.arm_mlp_par(params, hidden, **(dict(flg_drop=True) if flg_drop else {})))
     obj.control_policy.draw_device = torch.device("cpu")
     return obj
 
 
-def _sim(M, T):
-    from test_gpu_mlp_meas import _sim as base
-
-    return base(M, T)
+_sim = clf.sim_args
 
 
 @pytest.mark.parametrize("cls_name", ["MC_PILCO", "MC_PILCO4PMS"])
 def test_class_path(cls_name):
-    from test_gpu_pd_rollout import _normal_draws_on_the_cpu
-
     M, T, c, hidden = 16, 8, SHAPES["arm2"], (7, 3)
     sim = _sim(M, T)
     net = network(c, hidden, c["angle"], c["not_angle"], 40)
@@ -395,7 +322,7 @@ def test_class_path(cls_name):
         obj = _object(cls_name, net, hidden, M, flg_drop)
         obj.fused_feedback = fused
         torch.manual_seed(5)
-        with _normal_draws_on_the_cpu():
+        with clf.normal_draws_on_the_cpu():
             st, inp = obj.apply_policy(p_dropout=p, **sim)
         assert obj.last_feedback_fused is fused and (obj.last_status is not None) is fused
         if fused:
@@ -418,12 +345,8 @@ def test_class_path(cls_name):
     obj = _object(cls_name, net, hidden, M)
     before = [q.detach().clone() for q in obj.control_policy.mlp_parameters()]
     torch.manual_seed(6)
-    with _normal_draws_on_the_cpu(), contextlib.redirect_stdout(io.StringIO()):
-        out = obj.reinforce_policy(T_control=0.05 * T, num_particles=M, trial_index=0, particles_initial_state_mean=sim["particles_initial_state_mean"],
-                                   particles_initial_state_var=sim["particles_initial_state_var"], flg_particles_init_uniform=False,
-                                   particles_init_up_bound=None, particles_init_low_bound=None, flg_particles_init_multi_gauss=False,
-                                   opt_steps_list=[3], lr_list=[0.01], f_optimizer="lambda p, lr : torch.optim.Adam(p, lr)", num_step_print=10,
-                                   policy_reinit_dict=None, p_dropout_list=[0.25])
+    with clf.normal_draws_on_the_cpu(), contextlib.redirect_stdout(io.StringIO()):
+        out = obj.reinforce_policy(**clf.reinforce_args(sim, T, 3, p_dropout_list=[0.25]))
     assert obj.last_feedback_fused is True
     costs = np.asarray(out[0], dtype=float).reshape(-1)
     assert costs.shape == (3,) and np.isfinite(costs).all()
@@ -432,73 +355,29 @@ def test_class_path(cls_name):
 
 # ---- 7. two ranks on one device, Philox mode ----------------------------------------------------------------------------------------------------
 def _rank(rank, world, port, out_q):
-    import torch.distributed as dist
-
     import mcp_boot  # noqa: F401
 
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
     torch.cuda.set_device(dev())
-    if world > 1:
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-    M, T, hidden, c = 17, 6, (7, 3), SHAPES["arm2"]
-    res = {}
-    for cls_name in ("MC_PILCO", "MC_PILCO4PMS"):
-        obj = _object(cls_name, network(c, hidden, c["angle"], c["not_angle"], 40), hidden, M)
-        obj.noise_mode = "philox"
-        obj.seed = 17
-        if world > 1:
-            obj.shard_particles()
-        torch.manual_seed(23)  # (every rank alike: x0 is drawn for the whole swarm and sliced)
-        st, inp = obj.apply_policy(p_dropout=0.25, **_sim(M, T))
-        assert obj.last_feedback_fused is True
-        cost, std, flags = obj._cost_backward(st, inp, 0)
-        torch.cuda.synchronize()
-        res[cls_name] = (float(cost.detach()), float(std.detach()), [float(v) for v in flags.tolist()],
-                         [q.grad.cpu().numpy().copy() for q in obj.control_policy.mlp_parameters()], st.detach().cpu().numpy(), obj._shard)
-        if world == 1:  # (once: the run without dropout differs)
-            torch.manual_seed(23)
-            obj._rollout_calls = 0
-            res[cls_name] += (obj.apply_policy(p_dropout=0.0, **_sim(M, T))[0].detach().cpu().numpy(),)
-    out_q.put((rank, res))
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    with rank_group(rank, world, port):
+        M, T, hidden, c = 17, 6, (7, 3), SHAPES["arm2"]
+        res = {}
+        for cls_name in ("MC_PILCO", "MC_PILCO4PMS"):
+            obj = _object(cls_name, network(c, hidden, c["angle"], c["not_angle"], 40), hidden, M)
+            obj.noise_mode = "philox"
+            res[cls_name] = clf.sharded_step(MLP, obj, world, _sim(M, T), p_dropout=0.25)
+            if world == 1:  # (once: the run without dropout differs)
+                torch.manual_seed(23)
+                obj._rollout_calls = 0
+                res[cls_name] += (obj.apply_policy(p_dropout=0.0, **_sim(M, T))[0].detach().cpu().numpy(),)
+        out_q.put((rank, res))
 
 
 def test_two_rank_particle_sharding_matches_single_process():
     """MC_PILCO and MC_PILCO4PMS with the dropout policy under shard_particles (M = 17, T = 6, Philox, p = 0.25): each rank's states are the
-    matching slice of the one-process run bit for bit; the pooled cost, its std and the six parameter gradients agree to the bounds (another
-    order of the sums)."""
-    from test_gpu_mlp_meas import _free_port
-
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    p1 = ctx.Process(target=_rank, args=(0, 1, 0, q))
-    p1.start()
-    _, one = q.get(timeout=300)
-    p1.join(timeout=60)
-    assert p1.exitcode == 0
-    port = _free_port()
-    procs = [ctx.Process(target=_rank, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    two = dict(q.get(timeout=300) for _ in procs)
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    matching slice of the one-process run bit for bit (the same noise, the same masks per global particle); the pooled cost, its std and the
+    six parameter gradients agree to the bounds (another order of the sums)."""
+    one = run_ranks(_rank, 1)
+    two = run_ranks(_rank, 2)
+    one = clf.two_ranks_match_one_process(MLP, one, two, GRAD_TOL, n_grads=6)
     for cls_name in ("MC_PILCO", "MC_PILCO4PMS"):
-        c1, s1, f1, g1, st1, _, plain = one[cls_name]
-        assert f1 == [0.0, 0.0, 0.0] and len(g1) == 6 and all(float(np.abs(g).max()) > 0 for g in g1)
-        assert np.abs(plain - st1).max() > 1e-3  # (dropout was applied)
-        seen = 0
-        for r in range(2):
-            c2, s2, f2, g2, st2, (off, cnt) = two[r][cls_name]
-            assert np.array_equal(st2, st1[:, off:off + cnt])  # same noise, same masks per GLOBAL particle
-            seen += cnt
-            eg = [float(np.abs(a - b).max() / np.abs(b).max()) for a, b in zip(g2, g1)]
-            print("%s rank %d: cost %.3e std %.3e g_params %s" % (cls_name, r, abs(c2 - c1), abs(s2 - s1), " ".join("%.3e" % e for e in eg)))
-            assert f2 == [0.0, 0.0, 0.0]
-            assert abs(c2 - c1) < GRAD_TOL * abs(c1) and abs(s2 - s1) < GRAD_TOL * abs(s1)
-            assert len(g2) == 6 and max(eg) < GRAD_TOL
-        assert seen == 17
+        assert np.abs(one[cls_name][6] - one[cls_name][4]).max() > 1e-3  # (dropout was applied)

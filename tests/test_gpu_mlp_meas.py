@@ -3,82 +3,33 @@ ops.rollout_mlp(meas=...), MC_PILCO4PMS.apply_policy with a Policy.MLP_policy, a
 autograd through the oracle's step with the measurement and the network written out (tests/mlp_meas_models.mlp_meas_truth; conditioning and
 sensitivity checked by tests/test_mlp_meas_cpu.py), and the bitwise contracts it shares with mcp_rollout_mlp and the open-loop kernels.
 
-Bounds (tests/test_gpu_mlp_rollout.py:19, on the oracle's own Kinv / alpha): states and measurements 1e-9 absolute, inputs
+Bounds (tests/test_gpu_mlp_rollout.py, on the oracle's own Kinv / alpha): states and measurements 1e-9 absolute, inputs
 2e-9 absolute, every parameter gradient and g_x0 1e-9 relative to that tensor's largest magnitude."""
 import contextlib
-import functools
 import io
-import os
 
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
 
-import conftest  # noqa: F401  (registers the package, also in spawned workers)
+import closed_loop_family as clf
+from closed_loop_family import MLP, controller, policy
+from closed_loop_family import meas_spec as spec
+from closed_loop_family import noise_of as _noise
+from gpu_helpers import G, dev, relmax
 from mlp_meas_models import CASES, case_id, case_truth, meas_model, mlp_meas_truth
-from mlp_models import PAIR_SEED, SHAPES, build_pair, family, inputs_for, network
+from mlp_models import SHAPES, inputs_for, network
 from pd_meas_models import pos_noise_for
+from rank_harness import rank_group, run_ranks
 
 pytestmark = pytest.mark.gpu
-DT = torch.float64
 STATE_TOL, INPUT_TOL, GRAD_TOL = 1e-9, 2e-9, 1e-9
+TOLS = (STATE_TOL, INPUT_TOL, GRAD_TOL)
 
 
-def dev():
-    return torch.device("cuda", 0)
-
-
-def G(a):
-    return torch.as_tensor(np.asarray(a), dtype=DT).to(dev()).contiguous()
-
-
-def relmax(a, b):
-    a, b = a.detach().cpu(), b.detach().cpu()
-    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-300))
-
-
-@functools.lru_cache(maxsize=None)
 def pair(shape, N, deg, vs=None):
-    """(cfg, oracle model, PackedModel on the oracle's own Kinv / alpha), with the sampling time a measurement model needs on the delta-state
-    layout too; built once per process and shared, never modified."""
-    from mc_pilco_amd import ops
-    from test_gpu_mlp_rollout import packed_model
-
-    c, m, specs = build_pair(shape, N, deg, seed=PAIR_SEED)
-    pm = packed_model(c, m, specs, shape, vs)
-    if family(shape) == "delta":
-        pm = ops.PackedModel.delta(pm.gps, c["S"], c["U"], c["angle"], c["not_angle"], Ts=c["Ts"], var_scale=None if vs is None else list(vs))
-    return c, m, pm
-
-
-def policy(*a, **kw):
-    from test_gpu_mlp_rollout import policy as base
-
-    return base(*a, **kw)
-
-
-def spec(ms, pos_noise=None):
-    from mc_pilco_amd import ops
-
-    return ops.MeasSpec(pos=ms["pos"], vel=ms["vel"], std_pos=ms["std"], b=ms["b"], a=ms["a"], pos_noise=None if pos_noise is None else G(pos_noise))
-
-
-def gpu_run(pm, pol, x0, eps, pn, w, wu, sample, T, ms, noise=None, x0_grad=True):
-    """(states, inputs, meas, [parameter gradients or None], g_x0, status) of the op with L = sum w states + sum wu inputs."""
-    from mc_pilco_amd import ops
-
-    for q in pol.parameters():
-        q.grad = None
-    xg = G(x0).requires_grad_(x0_grad)
-    nz = noise if noise is not None else (ops.NoiseSpec(eps=G(eps)) if sample else None)
-    sp = spec(ms, pn)
-    st, inp, status = ops.rollout_mlp(pm, pol.packed(), nz, xg, T, particle_pred=sample, meas=sp)
-    ym = sp.measured
-    assert not ym.requires_grad and tuple(ym.shape) == tuple(st.shape)
-    L = (G(w) * st).sum() + (0.0 if wu is None else (G(wu) * inp).sum())
-    L.backward()
-    return st.detach(), inp.detach(), ym, [None if q.grad is None else q.grad.clone() for q in pol.mlp_parameters()], xg.grad, int(status.item())
+    """MLP.pair with the sampling time a measurement model needs on the delta-state layout too."""
+    return MLP.pair(shape, N, deg, vs, measured=True)
 
 
 # ---- 1. parity with the truth ---------------------------------------------------------------------------------------------------------
@@ -88,64 +39,31 @@ def test_parity_with_the_truth(case):
     mode, shape, deg, N, T, M, hidden, variant, opt = case
     sample = mode == "sampled"
     vs = opt.get("var_scale")
-    c, m, ins, (ost, oin, oym, ograds, ogx, vmin) = case_truth(case)
+    c, m, ins, truth = case_truth(case)
+    truth = clf.mlp_truth_of(truth)
     _, _, pm = pair(shape, N, deg, None if vs is None else tuple(vs))
     if sample and T > 1:
-        assert vmin > 0.0
+        assert truth.vmin > 0.0
     pol = policy(c, ins["params"], hidden, ins["angle"], ins["non_angle"], u_max=ins["u_max"], squash=ins["squash"])
     only = opt.get("only_grad")
     if only is not None:  # requires_grad on one tensor alone: neither x0 nor the other parameters get a gradient
         for i, q in enumerate(pol.mlp_parameters()):
             q.requires_grad_(i == only)
-    st, inp, ym, grads, gx, status = gpu_run(pm, pol, ins["x0"], ins["eps"], ins["pos_noise"], ins["w"], ins["wu"], sample, T, ins["ms"],
-                                             x0_grad=only is None)
-    es, ei, em = float((st.cpu() - ost).abs().max()), float((inp.cpu() - oin).abs().max()), float((ym.cpu() - oym).abs().max())
-    if only is None:
-        eg, ex = [relmax(g, o) for g, o in zip(grads, ograds)], relmax(gx, ogx)
-    else:
-        assert gx is None and all((g is None) == (i != only) for i, g in enumerate(grads))
-        eg, ex = [relmax(grads[only], ograds[only])], 0.0
-    print("%s: states %.3e inputs %.3e meas %.3e g_params %s g_x0 %.3e (min var %.3e)" % (case_id(case), es, ei, em, " ".join("%.3e" % e for e in eg),
-                                                                                          ex, vmin))
-    assert status == 0
-    assert es < STATE_TOL and ei < INPUT_TOL and em < STATE_TOL
-    assert max(eg) < GRAD_TOL and ex < GRAD_TOL
+    got = MLP.run(pm, pol, ins["x0"], T, clf.noise_buffer(ins["eps"]) if sample else None, ins["w"], ins["wu"], sample,
+                  meas=spec(ins["ms"], ins["pos_noise"]), x0_grad=only is None)
+    clf.check_against(MLP, case_id(case), truth, got, TOLS, only)
 
 
 # ---- 2. bit identities ------------------------------------------------------------------------------------------------------------------
-def _noise(kind, eps, **kw):
-    from mc_pilco_amd import ops
-
-    return None if kind == "mean" else (ops.NoiseSpec(eps=G(eps)) if kind == "eps" else ops.NoiseSpec(seed=11, call=3, **kw))
-
-
 @pytest.mark.parametrize("noise", ["mean", "eps", "philox"])
 def test_plain_launch_recording_launch_and_open_loop_launch_carry_the_same_bits(noise):
-    from mc_pilco_amd import ops
-
     c, m, pm = pair("arm2", 37, 1)
     M, T, hidden = 17, 6, (7, 3)
     x0, _, _, _, eps, w, wu = inputs_for(c, M, T, seed=21)
     ms = meas_model("arm2")
     pn = pos_noise_for(T, M, 2, seed=21)
     pol = policy(c, network(c, hidden, c["angle"], c["not_angle"], 21), hidden)
-    sample = noise != "mean"
-    sp = lambda: spec(ms, None if noise == "philox" else pn)
-    s1, s2 = sp(), sp()
-    with torch.no_grad():
-        st, inp, status = ops.rollout_mlp(pm, pol.packed(), _noise(noise, eps), G(x0), T, particle_pred=sample, meas=s1)
-    ym = s1.measured
-    assert int(status.item()) == 0 and not st.requires_grad
-    so, status_o = ops.rollout_open(pm, G(x0), inp[:T - 1].contiguous(), noise=_noise(noise, eps), particle_pred=sample)
-    assert int(status_o.item()) == 0
-    assert torch.equal(st, so)  # the same phases on the same operands
-    sr, ir, status_r = ops.rollout_mlp(pm, pol.packed(), _noise(noise, eps), G(x0), T, particle_pred=sample, meas=s2)  # the parameters require grad: recording
-    yr = s2.measured
-    assert sr.requires_grad and int(status_r.item()) == 0
-    assert torch.equal(sr.detach(), st) and torch.equal(ir.detach(), inp) and torch.equal(yr, ym)
-    assert float((ym[1:, :, :2] - st[1:, :, :2]).abs().min()) > 0 and torch.equal(ym[0], st[0])  # a measurement was simulated; row 0 is true
-    ((G(w) * sr).sum() + (G(wu) * ir).sum()).backward()  # the sweep over that record runs and leaves finite gradients
-    assert all(q.grad is not None and bool(torch.isfinite(q.grad).all()) and float(q.grad.abs().max()) > 0 for q in pol.mlp_parameters())
+    clf.three_way_bit_identity(MLP, pm, pol, x0, eps, T, noise, meas=lambda: spec(ms, None if noise == "philox" else pn), sweep=(w, wu))
 
 
 @pytest.mark.parametrize("noise", ["mean", "eps", "philox"])
@@ -204,48 +122,24 @@ def _rung_case(N):
     pn = pos_noise_for(T, M, 2, seed=seed)
     params = network(c, hidden, c["angle"], c["not_angle"], seed)
     torch.set_num_threads(1)
-    truth = mlp_meas_truth("arm2", m, x0, params, eps, pn, w, wu, True, c["angle"], c["not_angle"], ms)
-    assert truth[-1] > 0.0
-    return c, pm, M, T, hidden, x0, params, eps, w, wu, ms, pn, truth
+    truth = clf.mlp_truth_of(mlp_meas_truth("arm2", m, x0, params, eps, pn, w, wu, True, c["angle"], c["not_angle"], ms))
+    assert truth.vmin > 0.0
+    return pm, lambda **kw: policy(c, params, hidden, **kw), x0, eps, T, w, wu, truth, lambda: spec(ms, pn)
 
 
 @pytest.mark.parametrize("N", [640, 2600])
 def test_the_smaller_tiles_of_the_recording_form(N):
     """Sampled, degree 0, M = 5, T = 3 on arm2, every joint measured.  Status 0; states, inputs and measurements carry the bits of the launch
     without a record, whose states carry the bits of the open-loop launch on its inputs; everything against the truth."""
-    from mc_pilco_amd import ops
-
-    c, pm, M, T, hidden, x0, params, eps, w, wu, ms, pn, (ost, oin, oym, ograds, ogx, vmin) = _rung_case(N)
-    pol = policy(c, params, hidden)
-    st, inp, ym, grads, gx, status = gpu_run(pm, pol, x0, eps, pn, w, wu, True, T, ms)
-    s0 = spec(ms, pn)
-    with torch.no_grad():
-        st0, i0, status0 = ops.rollout_mlp(pm, pol.packed(), ops.NoiseSpec(eps=G(eps)), G(x0), T, particle_pred=True, meas=s0)
-    so, status_o = ops.rollout_open(pm, G(x0), i0[:T - 1].contiguous(), noise=ops.NoiseSpec(eps=G(eps)), particle_pred=True)
-    es, ei, em = float((st.cpu() - ost).abs().max()), float((inp.cpu() - oin).abs().max()), float((ym.cpu() - oym).abs().max())
-    eg, ex = [relmax(g, o) for g, o in zip(grads, ograds)], relmax(gx, ogx)
-    print("rung N %d: states %.3e inputs %.3e meas %.3e g_params %s g_x0 %.3e (min var %.3e)" % (N, es, ei, em, " ".join("%.3e" % e for e in eg), ex, vmin))
-    assert status == 0 and int(status0.item()) == 0 and int(status_o.item()) == 0
-    assert torch.equal(st, st0) and torch.equal(inp, i0) and torch.equal(ym, s0.measured) and torch.equal(st0, so)
-    assert es < STATE_TOL and ei < INPUT_TOL and em < STATE_TOL
-    assert max(eg) < GRAD_TOL and ex < GRAD_TOL
+    pm, pol, x0, eps, T, w, wu, truth, meas = _rung_case(N)
+    clf.rung_of_the_recording_form(MLP, "rung N %d" % N, pm, pol(), x0, eps, T, w, wu, truth, TOLS, meas)
 
 
 def test_the_four_trajectory_tile_without_a_record():
     """Nothing requires grad: status 0, the states carry the bits of the open-loop launch on the inputs; states, inputs and measurements
     against the truth.  (No record, so no gradient to compare.)"""
-    from mc_pilco_amd import ops
-
-    c, pm, M, T, hidden, x0, params, eps, w, wu, ms, pn, (ost, oin, oym, _, _, vmin) = _rung_case(640)
-    sp = spec(ms, pn)
-    st, inp, status = ops.rollout_mlp(pm, policy(c, params, hidden, trainable=False).packed(), ops.NoiseSpec(eps=G(eps)), G(x0), T, particle_pred=True,
-                                      meas=sp)
-    so, status_o = ops.rollout_open(pm, G(x0), inp[:T - 1].contiguous(), noise=ops.NoiseSpec(eps=G(eps)), particle_pred=True)
-    es, ei, em = float((st.cpu() - ost).abs().max()), float((inp.cpu() - oin).abs().max()), float((sp.measured.cpu() - oym).abs().max())
-    print("rung N 640, no record: states %.3e inputs %.3e meas %.3e (min var %.3e)" % (es, ei, em, vmin))
-    assert int(status.item()) == 0 and int(status_o.item()) == 0 and not st.requires_grad
-    assert torch.equal(st, so)
-    assert es < STATE_TOL and ei < INPUT_TOL and em < STATE_TOL
+    pm, pol, x0, eps, T, w, wu, truth, meas = _rung_case(640)
+    clf.four_trajectory_tile_without_a_record(MLP, "rung N 640", pm, pol(trainable=False), x0, eps, T, truth, TOLS, meas)
 
 
 # ---- 4. shard invariance of the op ----------------------------------------------------------------------------------------------------------
@@ -294,7 +188,6 @@ def test_philox_position_noise_is_the_pd_forms():
     recovery is within ulp(1) / 2 / std = 1.12e-15 of the draw while |y[p]| < 1 (one rounding of x + std n, the subtraction and the division
     adding less than a tenth of that): the two agree to 2.3e-15."""
     from mc_pilco_amd import ops
-    from test_gpu_pd_rollout import controller
 
     c, m, pm = pair("arm2", 37, 0)
     M, T, off, hidden, std = 5, 6, 3, (7, 3), 0.1
@@ -326,37 +219,22 @@ def test_philox_position_noise_is_the_pd_forms():
 
 
 # ---- 6. class path, one process -----------------------------------------------------------------------------------------------------------
-def _pms_object(params, hidden, M):
-    """MC_PILCO4PMS over the model and with the MLP policy of tests/test_gpu_mlp_rollout._arm_object: both joints measured, a first-order
-    filter with memory (fc = 0.3), position noise on both."""
-    from mc_pilco_amd.policy_learning import MC_PILCO
-    from test_gpu_mlp_rollout import _arm_object
-
-    base = _arm_object(params, hidden, M)
-    ml, pol, cf = base.model_learning, base.control_policy, base.cost_function
-    c = SHAPES["arm2"]
+def _object(cls_name, params, hidden):
+    """MC_PILCO, or MC_PILCO4PMS (both joints measured, a first-order filter with memory, fc = 0.3, position noise on both), over the model
+    and with the MLP policy of tests/test_gpu_mlp_rollout.py's class path."""
     from mc_pilco_amd.policy_learning import Policy
 
-    with contextlib.redirect_stdout(io.StringIO()):
-        obj = MC_PILCO.MC_PILCO4PMS(T_sampling=c["Ts"], state_dim=4, input_dim=2, f_sim=lambda y, t, u: None, f_model_learning=lambda **kw: ml,
-                                    model_learning_par={}, f_rand_exploration_policy=Policy.Random_exploration,
-                                    rand_exploration_policy_par=dict(state_dim=4, input_dim=2, u_max=1.0, dtype=DT),
-                                    f_control_policy=lambda **kw: pol, control_policy_par={}, f_cost_function=lambda **kw: cf, cost_function_par={},
-                                    pos_indeces=[0, 1], vel_indeces=[2, 3], std_meas_noise=np.array([0.02, 0.03, 0.0, 0.0]),
-                                    filtering_dict={"fc": 0.3}, log_path=None, dtype=DT, device=dev())
-    obj.noise_mode = "reference"
-    return obj
+    return clf.arm_object(Policy.MLP_policy, clf.arm_mlp_par(params, hidden), clf.ARM_PMS if cls_name == "MC_PILCO4PMS" else None)
 
 
-def _sim(M, T):
-    return dict(particles_initial_state_mean=G([0.1, -0.1, 0.0, 0.05]), particles_initial_state_var=G([1e-2, 1e-2, 2e-2, 2e-2]),
-                flg_particles_init_uniform=False, particles_init_up_bound=None, particles_init_low_bound=None, flg_particles_init_multi_gauss=False,
-                num_particles=M, T_control=T)
+def _pms_object(params, hidden, M):
+    return _object("MC_PILCO4PMS", params, hidden)
+
+
+_sim = clf.sim_args
 
 
 def test_class_path():
-    from test_gpu_pd_rollout import _normal_draws_on_the_cpu
-
     M, T, c = 16, 8, SHAPES["arm2"]
     sim = _sim(M, T)
     net = lambda hidden: network(c, hidden, c["angle"], c["not_angle"], 40)
@@ -367,7 +245,7 @@ def test_class_path():
         if edit:
             edit(obj)
         torch.manual_seed(5)
-        with _normal_draws_on_the_cpu():
+        with clf.normal_draws_on_the_cpu():
             st, inp = obj.apply_policy(**sim)
         expect = fused if expect is None else expect
         assert obj.last_feedback_fused is expect and (obj.last_status is not None) is expect
@@ -397,12 +275,8 @@ def test_class_path():
     obj = _pms_object(net((7, 3)), (7, 3), M)
     before = [q.detach().clone() for q in obj.control_policy.mlp_parameters()]
     torch.manual_seed(6)
-    with _normal_draws_on_the_cpu(), contextlib.redirect_stdout(io.StringIO()):
-        out = obj.reinforce_policy(T_control=0.05 * T, num_particles=M, trial_index=0, particles_initial_state_mean=sim["particles_initial_state_mean"],
-                                   particles_initial_state_var=sim["particles_initial_state_var"], flg_particles_init_uniform=False,
-                                   particles_init_up_bound=None, particles_init_low_bound=None, flg_particles_init_multi_gauss=False,
-                                   opt_steps_list=[3], lr_list=[0.01], f_optimizer="lambda p, lr : torch.optim.Adam(p, lr)", num_step_print=10,
-                                   policy_reinit_dict=None)
+    with clf.normal_draws_on_the_cpu(), contextlib.redirect_stdout(io.StringIO()):
+        out = obj.reinforce_policy(**clf.reinforce_args(sim, T, 3))
     assert obj.last_feedback_fused is True
     costs = np.asarray(out[0], dtype=float).reshape(-1)
     assert costs.shape == (3,) and np.isfinite(costs).all()
@@ -410,96 +284,34 @@ def test_class_path():
 
 
 # ---- 7. class path, two ranks on one device -------------------------------------------------------------------------------------------------
-def _free_port():
-    import socket
-
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _rank(rank, world, port, out_q):
-    import torch.distributed as dist
-
     import mcp_boot  # noqa: F401
-    from test_gpu_mlp_rollout import _arm_object
 
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
     torch.cuda.set_device(dev())
-    if world > 1:
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-    M, T, hidden, c = 17, 6, (7, 3), SHAPES["arm2"]
-    res = {}
-    for cls_name, make in (("MC_PILCO", _arm_object), ("MC_PILCO4PMS", _pms_object)):
-        obj = make(network(c, hidden, c["angle"], c["not_angle"], 40), hidden, M)
-        obj.noise_mode = "philox"
-        obj.seed = 17
-        if world > 1:
-            obj.shard_particles()
-        torch.manual_seed(23)  # (every rank alike: x0 is drawn for the whole swarm and sliced)
-        st, inp = obj.apply_policy(**_sim(M, T))
-        assert obj.last_feedback_fused is True
-        cost, std, flags = obj._cost_backward(st, inp, 0)
-        torch.cuda.synchronize()
-        res[cls_name] = (float(cost.detach()), float(std.detach()), [float(v) for v in flags.tolist()],
-                         [q.grad.cpu().numpy().copy() for q in obj.control_policy.mlp_parameters()], st.detach().cpu().numpy(), obj._shard)
-    out_q.put((rank, res))
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    with rank_group(rank, world, port):
+        M, T, hidden, c = 17, 6, (7, 3), SHAPES["arm2"]
+        res = {}
+        for cls_name in ("MC_PILCO", "MC_PILCO4PMS"):
+            obj = _object(cls_name, network(c, hidden, c["angle"], c["not_angle"], 40), hidden)
+            obj.noise_mode = "philox"
+            res[cls_name] = clf.sharded_step(MLP, obj, world, _sim(M, T))
+        out_q.put((rank, res))
 
 
 def test_two_rank_particle_sharding_matches_single_process():
     """MC_PILCO and MC_PILCO4PMS with the MLP policy under shard_particles (M = 17, T = 6, Philox): each rank's states are the matching slice
     of the one-process run bit for bit; the pooled cost, its std and the six parameter gradients agree to the bounds (another order of the
     sums)."""
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    p1 = ctx.Process(target=_rank, args=(0, 1, 0, q))
-    p1.start()
-    _, one = q.get(timeout=300)
-    p1.join(timeout=60)
-    assert p1.exitcode == 0
-    port = _free_port()
-    procs = [ctx.Process(target=_rank, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    two = dict(q.get(timeout=300) for _ in procs)
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    for cls_name in ("MC_PILCO", "MC_PILCO4PMS"):
-        c1, s1, f1, g1, st1, _ = one[cls_name]
-        assert f1 == [0.0, 0.0, 0.0] and len(g1) == 6 and all(float(np.abs(g).max()) > 0 for g in g1)
-        seen = 0
-        for r in range(2):
-            c2, s2, f2, g2, st2, (off, cnt) = two[r][cls_name]
-            assert np.array_equal(st2, st1[:, off:off + cnt])  # same noise per GLOBAL particle
-            seen += cnt
-            eg = [float(np.abs(a - b).max() / np.abs(b).max()) for a, b in zip(g2, g1)]
-            print("%s rank %d: cost %.3e std %.3e g_params %s" % (cls_name, r, abs(c2 - c1), abs(s2 - s1), " ".join("%.3e" % e for e in eg)))
-            assert f2 == [0.0, 0.0, 0.0]
-            assert abs(c2 - c1) < GRAD_TOL * abs(c1) and abs(s2 - s1) < GRAD_TOL * abs(s1)
-            assert len(g2) == 6 and max(eg) < GRAD_TOL
-        assert seen == 17
+    one = run_ranks(_rank, 1)
+    two = run_ranks(_rank, 2)
+    clf.two_ranks_match_one_process(MLP, one, two, GRAD_TOL, n_grads=6)
 
 
 # ---- 8. saved record -------------------------------------------------------------------------------------------------------------------------
 def test_saved_record_refuses_in_place_changes():
-    from mc_pilco_amd import ops
-
     c, m, pm = pair("arm2", 37, 0)
     x0, _, _, _, _, w, wu = inputs_for(c, 2, 4, seed=3)
     ms = meas_model("arm2")
     pn = pos_noise_for(4, 2, 2, seed=3)
     pol = policy(c, network(c, (5,), c["angle"], c["not_angle"], 3), (5,))
-    for which in (0, 1, 2):
-        sp = spec(ms, pn)
-        out = ops.rollout_mlp(pm, pol.packed(), None, G(x0), 4, particle_pred=False, meas=sp)
-        with torch.no_grad():
-            (sp.measured if which == 2 else out[which]).mul_(2.0)
-        with pytest.raises(RuntimeError, match="modified by an inplace operation"):
-            ((G(w) * out[0]).sum() + (G(wu) * out[1]).sum()).backward()
+    clf.saved_record_refuses_in_place_changes(MLP, pm, pol, x0, 4, meas=lambda: spec(ms, pn), weights=(w, wu))

@@ -16,6 +16,8 @@ import pytest
 import torch
 
 import width_models as wm
+from closed_loop_family import open_pair, zero_variance_model
+from gpu_helpers import G, dev, relmax
 from oracle import mcpilco_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -41,19 +43,6 @@ CASES = {
     # the wide class: D = 24, G = 6, degree 1 (two row blocks of [X^T; 1] in phase J)
     "wide": _case("wide", 12, 6, range(6), range(6, 12), range(6, 12), range(6), (33, 17, 48, 33, 48, 17), deg=1),
 }
-
-
-def dev():
-    return torch.device("cuda", 0)
-
-
-def G(a):
-    return torch.as_tensor(np.asarray(a), dtype=DT).to(dev()).contiguous()
-
-
-def relmax(a, b):
-    a, b = a.detach().cpu(), b.detach().cpu()
-    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-300))
 
 
 @functools.lru_cache(maxsize=None)
@@ -227,14 +216,9 @@ def test_policy_gradients_of_a_closed_loop_against_autograd_on_the_oracle_step(n
 def test_the_status_word_is_the_rollouts():
     """A known non-positive variance, by the recipe of tests/test_gpu_dropin.py::test_zero_predictive_variance_raises_like_the_reference_normal:
     one training point exactly at the GP input of x = 0, u = 0, no noise, Kinv = I -> var = 1 - 1 = 0.  And a NaN state."""
-    from gpu_helpers import spec_from
     from mc_pilco_amd import hipabi, ops
 
-    X = np.zeros((16, 6))
-    X[:, 4] = 1.0  # z = [x0, x1, x3, sin x2, cos x2, u] at x = 0, u = 0
-    X[1:, 0] = 50.0 + np.arange(15)  # the other rows far away (k = 0 there)
-    gp = ops.PackedGP(spec_from(np.ones(6), 0.0), G(X), G(np.zeros(16)), G(np.eye(16)))
-    pm = ops.PackedModel([gp, gp], 4, 1, 0.05, [2], [0, 1, 3], [1, 3], [0, 2])
+    pm = zero_variance_model(6, 4, 4, 1, 0.05, [2], [0, 1, 3], [1, 3], [0, 2])  # z = [x0, x1, x3, sin x2, cos x2, u] at x = 0, u = 0
     nan = np.zeros((8, 4))
     nan[3, 1] = float("nan")
     for x, flag, other in ((np.zeros((8, 4)), hipabi.STATUS_NONPOS_VAR, hipabi.STATUS_NAN), (nan + 1.0, hipabi.STATUS_NAN, hipabi.STATUS_NONPOS_VAR)):
@@ -311,9 +295,8 @@ def test_the_smaller_tiles(N, deg):
     recording chains carry the bits of the rollout; states and both gradients against the oracle."""
     from mc_pilco_amd import ops
     from open_grad_models import inputs_for, oracle_truth
-    from test_gpu_open_rollout_grad import pair
 
-    c, m, pm = pair("speed", N, deg)
+    c, m, pm = open_pair("speed", N, deg)
     M, Tn = 5, 3
     x0, u, eps, w = inputs_for(c, M, Tn, seed=Tn * 100 + M)
     torch.set_num_threads(1)

@@ -8,47 +8,17 @@ absolute, gradients 1e-9 relative to the gradient's largest magnitude.
 The tiles of the recording form: its two panels (k and v = Kinv k, [Npad][pitch] each) fit the LDS with 16 trajectories per workgroup up to
 Npad ~ 540 and with 4 up to ~ 2450, beyond that one trajectory.  CASES stops at N = 300, so test_the_smaller_tiles_of_the_recording_form
 launches the 4- and the 1-trajectory kernels (N = 640, Npad 640; N = 2600, Npad 2608) at degree classes 0 and 2."""
-import functools
-
 import numpy as np
 import pytest
 import torch
 
-from open_grad_models import CASES, SHAPES, build_pair, inputs_for, oracle_truth
+from closed_loop_family import open_pair as pair
+from gpu_helpers import DT, G, dev, rbf_dict, relmax
+from open_grad_models import CASES, inputs_for, oracle_truth
 
 pytestmark = pytest.mark.gpu
-DT = torch.float64
 STATE_TOL = 1e-9  # absolute, states
 GRAD_TOL = 1e-9   # relative to max |gradient|
-
-
-def dev():
-    return torch.device("cuda", 0)
-
-
-def G(a):
-    return torch.as_tensor(np.asarray(a), dtype=DT).to(dev()).contiguous()
-
-
-def relmax(a, b):
-    a, b = a.detach().cpu(), b.detach().cpu()
-    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-300))
-
-
-@functools.lru_cache(maxsize=None)
-def pair(shape, N, deg, vs=None):
-    """(cfg, oracle model, PackedModel on the oracle's own Kinv / alpha); built once per process and shared, never modified."""
-    from gpu_helpers import spec_from
-    from mc_pilco_amd import ops
-
-    c, m, specs = build_pair(shape, N, deg, seed=N + deg)
-    gps = [ops.PackedGP(spec_from(*specs[g]), G(m.cache[g].X), G(m.cache[g].alpha), G(m.cache[g].Kinv)) for g in range(c["G"])]
-    scale = None if vs is None else list(vs)
-    if shape == "delta":
-        pm = ops.PackedModel.delta(gps, c["S"], c["U"], c["angle"], c["not_angle"], var_scale=scale)
-    else:
-        pm = ops.PackedModel(gps, c["S"], c["U"], c["Ts"], c["angle"], c["not_angle"], c["vel"], c["not_vel"], var_scale=scale)
-    return c, m, pm
 
 
 def gpu_grads(pm, x0, u, eps, w, sample, lengths=None, noise=None):
@@ -226,7 +196,7 @@ def test_class_path(golden, family):
 
     from mc_pilco_amd import ops
     from mc_pilco_amd.model_learning import Model_learning as ML
-    from test_gpu_dropin import build_cartpole, rbf_dict
+    from test_gpu_dropin import build_cartpole
 
     fx = golden("mean_rollout")
     with contextlib.redirect_stdout(io.StringIO()):

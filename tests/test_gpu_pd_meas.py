@@ -9,78 +9,35 @@ gradient's largest magnitude; the measured states are held to the states' bound.
 The tiles: as in tests/test_gpu_pd_rollout.py, CASES stops at N = 300 (16 trajectories per workgroup).  The measured form's recording
 kernels with 4 and 1 trajectories (N = 640, N = 2600) and its 4-trajectory kernel without a record (N = 1200) are launched by the two rung
 tests below, at degree class 0; degree class 2 at those sizes is left out on purpose (see tests/test_gpu_pd_rollout.py)."""
-import contextlib
 import ctypes as C
-import functools
-import io
-import os
 
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
 
-import conftest  # noqa: F401  (registers the package, also in spawned workers)
+import closed_loop_family as clf
+import conftest
+from closed_loop_family import PD, controller
+from closed_loop_family import meas_spec as spec
+from gpu_helpers import DT, G, dev, rbf_dict, relmax
 from pd_meas_models import CASES, FILTER, case_id, meas_model, pd_meas_truth, pos_noise_for
-from pd_models import family, inputs_for
+from pd_models import inputs_for
+from rank_harness import rank_group, run_ranks
 
 pytestmark = pytest.mark.gpu
-DT = torch.float64
 STATE_TOL, INPUT_TOL, GRAD_TOL = 1e-9, 2e-9, 1e-9
+TOLS = (STATE_TOL, INPUT_TOL, GRAD_TOL)
 
 
-def dev():
-    return torch.device("cuda", 0)
-
-
-def G(a):
-    return torch.as_tensor(np.asarray(a), dtype=DT).to(dev()).contiguous()
-
-
-def relmax(a, b):
-    a, b = a.detach().cpu(), b.detach().cpu()
-    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-300))
-
-
-@functools.lru_cache(maxsize=None)
 def pair(shape, N, deg, vs=None):
-    """test_gpu_pd_rollout.pair with the sampling time a measurement model needs on the delta-state layout too; built once, never modified."""
-    from mc_pilco_amd import ops
-    from test_gpu_pd_rollout import pair as base
-
-    c, m, pm = base(shape, N, deg, vs)
-    if family(shape) == "delta":
-        pm = ops.PackedModel.delta(pm.gps, c["S"], c["U"], c["angle"], c["not_angle"], Ts=c["Ts"], var_scale=None if vs is None else list(vs))
-    return c, m, pm
-
-
-def controller(*a, **kw):
-    from test_gpu_pd_rollout import controller as base
-
-    return base(*a, **kw)
-
-
-def spec(ms, pos_noise=None):
-    from mc_pilco_amd import ops
-
-    return ops.MeasSpec(pos=ms["pos"], vel=ms["vel"], std_pos=ms["std"], b=ms["b"], a=ms["a"], pos_noise=None if pos_noise is None else G(pos_noise))
+    """PD.pair with the sampling time a measurement model needs on the delta-state layout too."""
+    return PD.pair(shape, N, deg, vs, measured=True)
 
 
 def gpu_run(pm, pol, x0, eps, pn, w, wu, sample, T, ms, noise=None):
-    """(states, inputs, meas, g_sqrt_kp, g_sqrt_kd, g_x0, status) of the op with L = sum w states + sum wu inputs."""
-    from mc_pilco_amd import ops
-
-    for q in pol.parameters():
-        q.grad = None
-    xg = G(x0).requires_grad_(True)
-    nz = noise if noise is not None else (ops.NoiseSpec(eps=G(eps)) if sample else None)
-    sp = spec(ms, pn)
-    st, inp, status = ops.rollout_pd(pm, pol.packed(), nz, xg, T, particle_pred=sample, meas=sp)
-    ym = sp.measured
-    assert not ym.requires_grad and tuple(ym.shape) == tuple(st.shape)
-    L = (G(w) * st).sum() + (0.0 if wu is None else (G(wu) * inp).sum())
-    L.backward()
-    return st.detach(), inp.detach(), ym, pol.sqrt_Kp_gains.grad.clone(), pol.sqrt_Kd_gains.grad.clone(), xg.grad, int(status.item())
+    """The Run of the op with L = sum w states + sum wu inputs."""
+    nz = noise if noise is not None else (clf.noise_buffer(eps) if sample else None)
+    return PD.run(pm, pol, x0, T, nz, w, wu, sample, meas=spec(ms, pn))
 
 
 # ---- 1. parity with the truth ---------------------------------------------------------------------------------------------------------
@@ -97,47 +54,22 @@ def test_parity_with_the_truth(case):
     pn = pos_noise_for(T, M, len(ms["pos"]), seed=T * 100 + M)
     u_max, squash = opt.get("u_max", 1.0), opt.get("squash", True)
     torch.set_num_threads(1)
-    ost, oin, oym, ogp, ogd, ogx, vmin = pd_meas_truth(shape, m, x0, kp, kd, target, eps, pn, w, wu, sample, ms, u_max=u_max, squash=squash,
-                                                       var_scale=vs)
+    truth = clf.pd_truth_of(pd_meas_truth(shape, m, x0, kp, kd, target, eps, pn, w, wu, sample, ms, u_max=u_max, squash=squash, var_scale=vs))
     if sample and T > 1:
-        assert vmin > 0.0  # the oracle alone keeps every step's variance positive on this seed
+        assert truth.vmin > 0.0  # the oracle alone keeps every step's variance positive on this seed
     pol = controller(c, kp, kd, target, u_max=u_max, squash=squash)
-    st, inp, ym, gp_, gd_, gx, status = gpu_run(pm, pol, x0, eps, pn, w, wu, sample, T, ms)
-    es, ei, em = float((st.cpu() - ost).abs().max()), float((inp.cpu() - oin).abs().max()), float((ym.cpu() - oym).abs().max())
-    ep, ed, ex = relmax(gp_, ogp), relmax(gd_, ogd), relmax(gx, ogx)
-    print("%s: states %.3e inputs %.3e meas %.3e g_sqrt_kp %.3e g_sqrt_kd %.3e g_x0 %.3e (min var %.3e)" % (case_id(case), es, ei, em, ep, ed, ex, vmin))
-    assert status == 0
-    assert es < STATE_TOL and ei < INPUT_TOL and em < STATE_TOL
-    assert ep < GRAD_TOL and ed < GRAD_TOL and ex < GRAD_TOL
+    clf.check_against(PD, case_id(case), truth, gpu_run(pm, pol, x0, eps, pn, w, wu, sample, T, ms), TOLS)
 
 
 # ---- 2. bit identities ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("noise", ["mean", "eps", "philox"])
 def test_plain_launch_recording_launch_and_open_loop_launch_carry_the_same_bits(noise):
-    from mc_pilco_amd import ops
-
     c, m, pm = pair("arm2", 37, 1)
     M, T = 17, 6
     x0, kp, kd, target, eps, w, wu = inputs_for(c, M, T, seed=21)
     ms = meas_model("arm2")
     pn = pos_noise_for(T, M, 2, seed=21)
-    pol = controller(c, kp, kd, target)
-    sample = noise != "mean"
-    nz = lambda: None if not sample else (ops.NoiseSpec(eps=G(eps)) if noise == "eps" else ops.NoiseSpec(seed=11, call=3))
-    sp = lambda: spec(ms, None if noise == "philox" else pn)
-    s1, s2 = sp(), sp()
-    with torch.no_grad():
-        st, inp, status = ops.rollout_pd(pm, pol.packed(), nz(), G(x0), T, particle_pred=sample, meas=s1)
-    ym = s1.measured
-    assert int(status.item()) == 0 and not st.requires_grad
-    so, status_o = ops.rollout_open(pm, G(x0), inp[:T - 1].contiguous(), noise=nz(), particle_pred=sample)
-    assert int(status_o.item()) == 0
-    assert torch.equal(st, so)  # the same phases on the same operands
-    sr, ir, status_r = ops.rollout_pd(pm, pol.packed(), nz(), G(x0), T, particle_pred=sample, meas=s2)  # the gains require grad: recording
-    yr = s2.measured
-    assert sr.requires_grad and int(status_r.item()) == 0
-    assert torch.equal(sr.detach(), st) and torch.equal(ir.detach(), inp) and torch.equal(yr, ym)
-    assert float((ym[1:, :, :2] - st[1:, :, :2]).abs().min()) > 0 and torch.equal(ym[0], st[0])  # a measurement was simulated; row 0 is true
+    clf.three_way_bit_identity(PD, pm, controller(c, kp, kd, target), x0, eps, T, noise, meas=lambda: spec(ms, None if noise == "philox" else pn))
 
 
 # The rungs are held to the bounds of the N = 300 case of CASES (STATE_TOL for states and measurements, INPUT_TOL, GRAD_TOL): the library of
@@ -152,9 +84,9 @@ def _rung_case(N):
     ms = meas_model("arm2")
     pn = pos_noise_for(T, M, 2, seed=T * 100 + M)
     torch.set_num_threads(1)
-    truth = pd_meas_truth("arm2", m, x0, kp, kd, target, eps, pn, w, wu, True, ms)
-    assert truth[-1] > 0.0
-    return c, pm, M, T, x0, kp, kd, target, eps, w, wu, ms, pn, truth
+    truth = clf.pd_truth_of(pd_meas_truth("arm2", m, x0, kp, kd, target, eps, pn, w, wu, True, ms))
+    assert truth.vmin > 0.0
+    return c, pm, (kp, kd, target), x0, eps, T, w, wu, truth, lambda: spec(ms, pn)
 
 
 @pytest.mark.parametrize("N", [640, 2600])
@@ -162,39 +94,15 @@ def test_the_smaller_tiles_of_the_recording_form(N):
     """Sampled, degree 0, M = 5, T = 3 on arm2, every joint measured: the recording launch runs 4 trajectories per workgroup at N = 640 and
     one at N = 2600.  Status 0; states, inputs and measurements carry the bits of the launch without a record, whose states carry the bits of
     the open-loop launch on its inputs; states, inputs, measurements and the three gradients against the truth."""
-    from mc_pilco_amd import ops
-
-    c, pm, M, T, x0, kp, kd, target, eps, w, wu, ms, pn, (ost, oin, oym, ogp, ogd, ogx, vmin) = _rung_case(N)
-    pol = controller(c, kp, kd, target)
-    st, inp, ym, gp_, gd_, gx, status = gpu_run(pm, pol, x0, eps, pn, w, wu, True, T, ms)
-    s0 = spec(ms, pn)
-    with torch.no_grad():
-        st0, i0, status0 = ops.rollout_pd(pm, pol.packed(), ops.NoiseSpec(eps=G(eps)), G(x0), T, particle_pred=True, meas=s0)
-    so, status_o = ops.rollout_open(pm, G(x0), i0[:T - 1].contiguous(), noise=ops.NoiseSpec(eps=G(eps)), particle_pred=True)
-    es, ei, em = float((st.cpu() - ost).abs().max()), float((inp.cpu() - oin).abs().max()), float((ym.cpu() - oym).abs().max())
-    ep, ed, ex = relmax(gp_, ogp), relmax(gd_, ogd), relmax(gx, ogx)
-    print("rung N %d: states %.3e inputs %.3e meas %.3e g_sqrt_kp %.3e g_sqrt_kd %.3e g_x0 %.3e (min var %.3e)" % (N, es, ei, em, ep, ed, ex, vmin))
-    assert status == 0 and int(status0.item()) == 0 and int(status_o.item()) == 0
-    assert torch.equal(st, st0) and torch.equal(inp, i0) and torch.equal(ym, s0.measured) and torch.equal(st0, so)
-    assert es < STATE_TOL and ei < INPUT_TOL and em < STATE_TOL
-    assert ep < GRAD_TOL and ed < GRAD_TOL and ex < GRAD_TOL
+    c, pm, gains, x0, eps, T, w, wu, truth, meas = _rung_case(N)
+    clf.rung_of_the_recording_form(PD, "rung N %d" % N, pm, controller(c, *gains), x0, eps, T, w, wu, truth, TOLS, meas)
 
 
 def test_the_four_trajectory_tile_without_a_record():
     """Sampled, degree 0, N = 1200 (the k panel of 16 trajectories does not fit), nothing requires grad: status 0, the states carry the bits
     of the open-loop launch on the inputs, states, inputs and measurements against the truth.  (No record, so no gradient to compare.)"""
-    from mc_pilco_amd import ops
-
-    c, pm, M, T, x0, kp, kd, target, eps, w, wu, ms, pn, (ost, oin, oym, _, _, _, vmin) = _rung_case(1200)
-    pd = controller(c, kp, kd, target, trainable=False).packed()
-    sp = spec(ms, pn)
-    st, inp, status = ops.rollout_pd(pm, pd, ops.NoiseSpec(eps=G(eps)), G(x0), T, particle_pred=True, meas=sp)
-    so, status_o = ops.rollout_open(pm, G(x0), inp[:T - 1].contiguous(), noise=ops.NoiseSpec(eps=G(eps)), particle_pred=True)
-    es, ei, em = float((st.cpu() - ost).abs().max()), float((inp.cpu() - oin).abs().max()), float((sp.measured.cpu() - oym).abs().max())
-    print("rung N 1200 deg 0, no record: states %.3e inputs %.3e meas %.3e (min var %.3e)" % (es, ei, em, vmin))
-    assert int(status.item()) == 0 and int(status_o.item()) == 0 and not st.requires_grad
-    assert torch.equal(st, so)
-    assert es < STATE_TOL and ei < INPUT_TOL and em < STATE_TOL
+    c, pm, gains, x0, eps, T, w, wu, truth, meas = _rung_case(1200)
+    clf.four_trajectory_tile_without_a_record(PD, "rung N 1200 deg 0", pm, controller(c, *gains, trainable=False), x0, eps, T, truth, TOLS, meas)
 
 
 def raw_run(pm, pd, kpg, kdg, ms, nz, x0, T, w, wu, sample=True, entry="meas"):
@@ -289,7 +197,7 @@ def test_philox_position_noise_is_the_closed_loop_kernels():
     ms["std"] = [0.1, 0.1]
     pol = controller(c, kp, kd, target)
     nz = lambda: ops.NoiseSpec(seed=21, call=7, particle_offset=off)
-    st, inp, ym, gkp, gkd, gx, status = gpu_run(pm, pol, x0, None, None, w, wu, True, T, ms, noise=nz())
+    st, inp, ym, (gkp, gkd), gx, status = gpu_run(pm, pol, x0, None, None, w, wu, True, T, ms, noise=nz())
     assert status == 0 and float(st[:, :, :2].abs().max()) < 1.0  # (the measured components: the positions)
     rec = (ym[1:, :, :2] - st[1:, :, :2]) / 0.1
     B = 8
@@ -304,7 +212,7 @@ def test_philox_position_noise_is_the_closed_loop_kernels():
     vel = c["vel"]
     eps = (st[1:, :, vel] - st[:-1, :, vel] - mu) / torch.sqrt(var)
     pol2 = controller(c, kp, kd, target)
-    st2, inp2, ym2, gkp2, gkd2, gx2, status2 = gpu_run(pm, pol2, x0, eps.cpu(), rec.cpu(), w, wu, True, T, ms)
+    st2, inp2, ym2, (gkp2, gkd2), gx2, status2 = gpu_run(pm, pol2, x0, eps.cpu(), rec.cpu(), w, wu, True, T, ms)
     es, ei, em = float((st2 - st).abs().max()), float((inp2 - inp).abs().max()), float((ym2 - ym).abs().max())
     ep, ed, ex = relmax(gkp2, gkp), relmax(gkd2, gkd), relmax(gx2, gx)
     print("buffers of the recovered noise vs Philox: states %.3e inputs %.3e meas %.3e grads %.3e %.3e %.3e" % (es, ei, em, ep, ed, ex))
@@ -375,13 +283,12 @@ def _fixture_object(fx, kind, cls_name="MC_PILCO4PMS", num_particles=None):
     """MC_PILCO4PMS (or MC_PILCO) over the model of a rollout_pd_pms.npz fixture -- trained here, on the fixture's recorded trajectory -- with the
     fixture's trainable PD controller and measurement model."""
     from mc_pilco_amd.model_learning import Model_learning as ML
-    from mc_pilco_amd.policy_learning import MC_PILCO, Cost_function, Policy
-    from test_gpu_dropin import rbf_dict
+    from mc_pilco_amd.policy_learning import Policy
 
     k = lambda n: fx[kind + "_" + n]
     Ts = float(k("Ts"))
     angle, not_angle = [int(i) for i in k("angle")], [int(i) for i in k("not_angle")]
-    with contextlib.redirect_stdout(io.StringIO()):
+    with clf.quiet():
         if kind == "speed":
             ml = ML.Speed_Model_learning_RBF_angle_state(num_gp=2, init_dict_list=[rbf_dict(8, k("lengthscales"), float(k("sigma_n")))] * 2, T_sampling=Ts,
                                                          angle_indeces=angle, not_angle_indeces=not_angle, vel_indeces=[int(i) for i in k("vel")],
@@ -389,31 +296,15 @@ def _fixture_object(fx, kind, cls_name="MC_PILCO4PMS", num_particles=None):
         else:
             ml = ML.Model_learning_RBF_angle_state(num_gp=4, init_dict_list=[rbf_dict(8, k("lengthscales"), float(k("sigma_n")))] * 4,
                                                    angle_indeces=angle, not_angle_indeces=not_angle, dtype=DT, device=dev())
-        ml.add_data(k("states_tr"), k("inputs_tr"))
-        with torch.no_grad():
-            for g in range(ml.num_gp):
-                ml.pretrain_gp(g)
-        ml.set_eval_mode()
-        ppar = dict(state_dim=4, input_dim=2, sqrt_Kp_gains=np.asarray(k("sqrt_kp")), sqrt_Kd_gains=np.asarray(k("sqrt_kd")), target_traj=G(k("target")),
-                    flg_squash=True, u_max=float(k("u_max")), flg_trainable=True, dtype=DT, device=dev())
-        common = dict(T_sampling=Ts, state_dim=4, input_dim=2, f_sim=lambda y, t, u: None, f_model_learning=lambda **kw: ml, model_learning_par={},
-                      f_rand_exploration_policy=Policy.Random_exploration,
-                      rand_exploration_policy_par=dict(state_dim=4, input_dim=2, u_max=1.0, dtype=DT), f_control_policy=Policy.PD_controller,
-                      control_policy_par=ppar, f_cost_function=Cost_function.Expected_saturated_distance,
-                      cost_function_par=dict(target_state=G([0.2, -0.1]), lengthscales=G([0.5, 0.5]), active_dims=np.array([0, 1])), log_path=None,
-                      dtype=DT, device=dev())
-        if cls_name == "MC_PILCO4PMS":
-            obj = MC_PILCO.MC_PILCO4PMS(pos_indeces=[int(i) for i in k("pos_indeces")], vel_indeces=[int(i) for i in k("vel_indeces")],
-                                        std_meas_noise=np.asarray(k("std_meas_noise")), filtering_dict={"fc": float(k("fc"))}, **common)
-        else:
-            obj = MC_PILCO.MC_PILCO(**common)
-    return obj
+    ppar = dict(clf.arm_pd_par(k("sqrt_kp"), k("sqrt_kd"), k("target")), u_max=float(k("u_max")))
+    pms = dict(pos_indeces=[int(i) for i in k("pos_indeces")], vel_indeces=[int(i) for i in k("vel_indeces")],
+               std_meas_noise=np.asarray(k("std_meas_noise")), filtering_dict={"fc": float(k("fc"))})
+    ml = clf.trained(ml, k("states_tr"), k("inputs_tr"))
+    return clf.policy_learning_object(ml, Ts, Policy.PD_controller, ppar, pms if cls_name == "MC_PILCO4PMS" else None)
 
 
 def _sim(fx, kind, M, T):
-    k = lambda n: fx[kind + "_" + n]
-    return dict(particles_initial_state_mean=G(k("x0_mean")), particles_initial_state_var=G(k("x0_var")), flg_particles_init_uniform=False,
-                particles_init_up_bound=None, particles_init_low_bound=None, flg_particles_init_multi_gauss=False, num_particles=M, T_control=T)
+    return clf.sim_args(M, T, fx[kind + "_x0_mean"], fx[kind + "_x0_var"])
 
 
 @pytest.mark.parametrize("kind", ["speed", "delta"])
@@ -421,8 +312,6 @@ def test_class_path_against_the_reference(golden, kind):
     """MC_PILCO4PMS with the trainable PD controller in "reference" noise mode: the fused launch is taken, and states / inputs / the weighted-sum
     cost / the gains' gradients are the reference's own (tests/golden/rollout_pd_pms.npz); the step loop (fused_feedback = False) gives the same
     numbers to the bounds."""
-    from test_gpu_pd_rollout import _normal_draws_on_the_cpu
-
     fx = golden("rollout_pd_pms")
     k = lambda n: fx[kind + "_" + n]
     T, M = k("states").shape[:2]
@@ -433,7 +322,7 @@ def test_class_path_against_the_reference(golden, kind):
         obj.noise_mode = "reference"
         obj.fused_feedback = fused
         torch.manual_seed(seed)
-        with _normal_draws_on_the_cpu():
+        with clf.normal_draws_on_the_cpu():
             st, inp = obj.apply_policy(**_sim(fx, kind, M, T))
         assert obj.last_feedback_fused is fused and (obj.last_status is not None) is fused
         if fused:
@@ -455,78 +344,19 @@ def test_class_path_against_the_reference(golden, kind):
 
 
 # ---- 6. class path, two ranks on one device -------------------------------------------------------------------------------------------------
-def _free_port():
-    import socket
-
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _rank(rank, world, port, out_q):
-    import torch.distributed as dist
-
     import mcp_boot  # noqa: F401
 
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
     torch.cuda.set_device(dev())
-    if world > 1:
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-    fx = conftest.load_golden("rollout_pd_pms")
-    M, T = 17, 6
-    res = {}
-    for cls_name in ("MC_PILCO", "MC_PILCO4PMS"):
-        obj = _fixture_object(fx, "speed", cls_name)
-        obj.seed = 17
-        if world > 1:
-            obj.shard_particles()
-        torch.manual_seed(23)  # (every rank alike: x0 is drawn for the whole swarm and sliced)
-        st, inp = obj.apply_policy(**_sim(fx, "speed", M, T))
-        assert obj.last_feedback_fused is True
-        cost, std, flags = obj._cost_backward(st, inp, 0)
-        torch.cuda.synchronize()
-        pol = obj.control_policy
-        res[cls_name] = (float(cost), float(std), [float(v) for v in flags.tolist()], pol.sqrt_Kp_gains.grad.cpu().numpy().copy(),
-                         pol.sqrt_Kd_gains.grad.cpu().numpy().copy(), st.detach().cpu().numpy(), obj._shard)
-    out_q.put((rank, res))
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    with rank_group(rank, world, port):
+        fx = conftest.load_golden("rollout_pd_pms")
+        out_q.put((rank, {cls_name: clf.sharded_step(PD, _fixture_object(fx, "speed", cls_name), world, _sim(fx, "speed", 17, 6))
+                          for cls_name in ("MC_PILCO", "MC_PILCO4PMS")}))
 
 
 def test_two_rank_particle_sharding_matches_single_process():
     """MC_PILCO and MC_PILCO4PMS with the PD policy under shard_particles (M = 17, Philox): each rank's states are the matching slice of the
     one-process run bit for bit; the pooled cost, its std and the gains' gradients agree to the bounds (another order of the sums)."""
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    p1 = ctx.Process(target=_rank, args=(0, 1, 0, q))
-    p1.start()
-    _, one = q.get(timeout=300)
-    p1.join(timeout=60)
-    assert p1.exitcode == 0
-    port = _free_port()
-    procs = [ctx.Process(target=_rank, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    two = dict(q.get(timeout=300) for _ in procs)
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    for cls_name in ("MC_PILCO", "MC_PILCO4PMS"):
-        c1, s1, f1, gp1, gd1, st1, _ = one[cls_name]
-        assert f1 == [0.0, 0.0, 0.0] and float(np.abs(gp1).max()) > 0
-        seen = 0
-        for r in range(2):
-            c2, s2, f2, gp2, gd2, st2, (off, cnt) = two[r][cls_name]
-            assert np.array_equal(st2, st1[:, off:off + cnt])  # same noise per GLOBAL particle
-            seen += cnt
-            print("%s rank %d: cost %.3e std %.3e g_sqrt_kp %.3e g_sqrt_kd %.3e" % (cls_name, r, abs(c2 - c1), abs(s2 - s1),
-                                                                                 np.abs(gp2 - gp1).max() / np.abs(gp1).max(),
-                                                                                 np.abs(gd2 - gd1).max() / np.abs(gd1).max()))
-            assert f2 == [0.0, 0.0, 0.0]
-            assert abs(c2 - c1) < GRAD_TOL * abs(c1) and abs(s2 - s1) < GRAD_TOL * abs(s1)
-            assert np.abs(gp2 - gp1).max() < GRAD_TOL * np.abs(gp1).max() and np.abs(gd2 - gd1).max() < GRAD_TOL * np.abs(gd1).max()
-        assert seen == 17
+    one = run_ranks(_rank, 1)
+    two = run_ranks(_rank, 2)
+    clf.two_ranks_match_one_process(PD, one, two, GRAD_TOL, n_grads=2)

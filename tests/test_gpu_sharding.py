@@ -2,40 +2,28 @@
 particle ids, this rank's cost share and adjoint sweep, then ONE all-reduce of [gradient | cost sums | flags]
 (sharding.StepReducer, mcp_cost_sums / mcp_cost_finalize_sums) -- reproduces the single-process HIP result on the
 same particles; the two-exchange form of round 1 (all-gathered moments + gradient all-reduce) is checked beside it."""
-import os
-import socket
-
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
 
 import conftest  # noqa: F401  (registers the package, also in spawned workers)
+from rank_harness import rank_group, run_ranks
 
 pytestmark = pytest.mark.gpu
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _run(rank, world, port, out_q, fused=True):
-    import torch.distributed as dist
-
     import mcp_boot  # noqa: F401
-    from mc_pilco_amd import ops, sharding, workloads
 
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    if world > 1:
-        dist.init_process_group("gloo", rank=rank, world_size=world)
-    group = dist.group.WORLD if world > 1 else None
+    with rank_group(rank, world, port) as group:
+        _step(rank, world, group, out_q, fused, dev)
+
+
+def _step(rank, world, group, out_q, fused, dev):
+    from mc_pilco_amd import ops, sharding, workloads
+
     m_total, Tn = 48, 10
     w = workloads.build("tiny", device=dev, M=m_total, T=Tn)
     off, cnt = sharding.shard_range(m_total, world, rank)
@@ -70,27 +58,12 @@ def _run(rank, world, port, out_q, fused=True):
     res = (float(cost), float(std), [p.grad.cpu().numpy().copy() for p in w.params], st.detach().cpu().numpy(), off, cnt)
     if rank == 0 or world == 1:
         out_q.put(res)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 @pytest.mark.parametrize("fused", [True, False])
 def test_two_rank_hip_sharding_matches_single_process(fused):
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    p1 = ctx.Process(target=_run, args=(0, 1, 0, q))
-    p1.start()
-    c1, s1, g1, st1, _, _ = q.get(timeout=300)
-    p1.join(timeout=60)
-    port = _free_port()
-    procs = [ctx.Process(target=_run, args=(r, 2, port, q, fused)) for r in range(2)]
-    for p in procs:
-        p.start()
-    c2, s2, g2, st2, off, cnt = q.get(timeout=300)
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    c1, s1, g1, st1, _, _ = run_ranks(_run, 1)[0]
+    c2, s2, g2, st2, off, cnt = run_ranks(_run, 2, args=(fused,), expect=1)[0]
     assert np.array_equal(st2, st1[:, off:off + cnt])  # same noise per GLOBAL particle: bit-identical trajectories
     assert abs(c2 - c1) < 1e-13 * abs(c1)
     assert abs(s2 - s1) < 1e-10 * abs(s1)
@@ -98,7 +71,7 @@ def test_two_rank_hip_sharding_matches_single_process(fused):
         assert np.max(np.abs(a - b)) < 1e-12 * max(1.0, np.max(np.abs(b)))
 
 
-def _abi_comm_single_rank(out_q):
+def _abi_comm_single_rank(rank, world, port, out_q):
     """mcp_comm_* / mcp_allreduce_grad on a one-rank communicator (all a one-GPU box can host): RCCL loads at run time, the
     communicator is created once, an all-reduce over one rank is the identity, a second init with the same geometry is a no-op."""
     import ctypes as C
@@ -120,11 +93,5 @@ def _abi_comm_single_rank(out_q):
 
 
 def test_abi_collective_on_a_single_rank_communicator():
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    p = ctx.Process(target=_abi_comm_single_rank, args=(q,))
-    p.start()
-    rc, same = q.get(timeout=300)
-    p.join(timeout=60)
-    assert p.exitcode == 0
+    rc, same = run_ranks(_abi_comm_single_rank, 1)[0]
     assert rc == [0, 0, 1, 0, 0, -1, 0, 0] and same  # (a second init with another geometry is refused: one communicator per process)

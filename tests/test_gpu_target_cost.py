@@ -47,7 +47,7 @@ def cost_std_grad(pc, states):
 # ---- 1: the reference's own numbers ------------------------------------------------------------------------------------------------------
 def test_packed_target_cost_matches_the_reference_fixture(golden):
     """simple_costs.npz (T = 6, M = 10, S = 4, active [0, 1, 2], one target row; written by the reference's classes): cost, std and state
-    gradient of both kinds at 1e-12 relative, the bound test_gpu_dropin.py:509-511 holds these quantities to."""
+    gradient of both kinds at 1e-12 relative, the bound test_gpu_dropin.py:500-502 holds these quantities to."""
     fx = golden("simple_costs")
     act = [int(i) for i in fx["active_dims"]]
     assert fx["target"].shape == (1, 3)
