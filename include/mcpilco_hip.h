@@ -206,6 +206,20 @@ typedef struct mcp_mlp_policy {
   const double* b[3];               /* [h0]    | [h1] or NULL     | [U]                           */
 } mcp_mlp_policy;
 
+/* Target-trajectory features of the tanh MLP -- the feature map of the reference's Sum_of_gaussians_with_target_trajectory (policy_in =
+ * cat(x, x*_t - x), policy_learning/Policy.py:389-403) behind mcp_mlp_policy's own: the feature row of policy evaluation t (every row
+ * 0 .. T - 1) is
+ *   f_t = [x[non_angle], sin x[angle], cos x[angle], target[t][idx[i]] - x[idx[i]]  (i = 0 .. n - 1)]
+ * so the descriptor's P = n_non_angle + 2 n_angle + n (without lists S + n) and W[0] is [h0][P] with the error columns LAST.  The error
+ * is the plain difference target - x, not wrapped on angle components (as the reference and mcp_pd_policy have it).  The target is a
+ * constant of the launch: no gradient. */
+typedef struct mcp_mlp_track {
+  int32_t n;                    /* error features; 0: none                       */
+  int32_t idx[MCP_MAX_STATE];   /* distinct state components                     */
+  int32_t rows;                 /* rows of target, >= T                          */
+  const double* target;         /* DEVICE [rows][S]                              */
+} mcp_mlp_track;
+
 /* ---- library ------------------------------------------------------------------------ */
 int mcp_abi_version(void);
 const char* mcp_build_info(void);
@@ -480,6 +494,33 @@ int mcp_rollout_mlp_drop(const mcp_model* model, const mcp_mlp_policy* mlp, cons
 int mcp_rollout_mlp_drop_bwd(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_meas* meas, const mcp_noise* noise, double p_drop, int M,
                              int T, const double* states, const double* inputs, const double* jac, const double* g_states,
                              const double* g_inputs /* may be NULL */, double* g_params, double* g_x0, void* stream);
+/* mcp_rollout_mlp_drop with TARGET-TRAJECTORY FEATURES (mcp_mlp_track): the network tracks -- in policy evaluation t it also sees the errors
+ * target[t][idx[i]] - x_t[idx[i]], written behind the cosines (measured form: x is the simulated measurement y_t everywhere, errors
+ * included: the network sees only the measurement).  mlp->P is the FULL feature width n_non_angle + 2 n_angle + track->n (without lists
+ * S + track->n), at most MCP_MAX_PFEAT; W[0] is [h0][P], the error columns last.  Dropout, the output layer, the squashing, the noise
+ * addressing, the status flags (a NaN in a target row reaches the inputs: MCP_STATUS_NAN), T == 1, the tile ladder and the weights' LDS
+ * copy are mcp_rollout_mlp_drop's, and so are the bit identities (mcp_rollout_open on the launch's own inputs; plain against recording
+ * launch).  track NULL or track->n == 0: mcp_rollout_mlp_drop itself on the same arguments (same kernels, same bits).  Checks in this
+ * order: a NULL pointer, M <= 0, T < 1, p_drop -> MCP_ERR_ARG; MCP_MAX_* of the model -> MCP_ERR_LIMIT; the model -> MCP_ERR_ARG; the
+ * descriptor's limits, track->n > MCP_MAX_STATE and P > MCP_MAX_PFEAT among them -> MCP_ERR_LIMIT; the descriptor's other errors, then
+ * the track's -- n < 0, an idx entry out of range or repeated, rows < T, target NULL with n > 0, P != n_non_angle + 2 n_angle + n -- each
+ * MCP_ERR_ARG; then the measurement's.  Replaces the loop of MC_PILCO.apply_policy (policy_learning/MC_PILCO.py:615-674; measured:
+ * MC_PILCO4PMS.apply_policy, :808-906) with Policy.MLP_policy on the feature map of policy_learning/Policy.py:389-403 over
+ * Model_learning.get_next_state (model_learning/Model_learning.py:210-229, 471-494, 685-718). */
+int mcp_rollout_mlp_track(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_mlp_track* track /* NULL or n == 0: no errors */,
+                          const mcp_meas* meas /* NULL or n == 0: the true state */, const mcp_noise* noise, double p_drop, int M, int T,
+                          int particle_pred, const double* x0, double* states, double* inputs, double* mu, double* var,
+                          double* jac /* NULL: no record */, uint32_t* status, void* stream);
+/* Reverse-time sweep of mcp_rollout_mlp_track: mcp_rollout_mlp_drop_bwd with the error features in the activation rows -- recomputed from
+ * states (measured form: meas->meas) and target with the forward's statement, so g_W0 gets their columns through the same outer sums -- and
+ * their pull on the state, lambda[idx[i]] -= fbar[n_non_angle + 2 n_angle + i] (measured form: the same term on the measurement, which
+ * reaches the state through the filter's adjoint).  The parameter order and the slab layout are unchanged; n_param grows with P.  noise may
+ * be NULL only when p_drop == 0.  track NULL or track->n == 0: mcp_rollout_mlp_drop_bwd itself.  The argument checks of the forward entry;
+ * with neither output asked for MCP_OK without a launch.  Replaces autograd's backward (MC_PILCO.py:522) through the loops named above. */
+int mcp_rollout_mlp_track_bwd(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_mlp_track* track, const mcp_meas* meas,
+                              const mcp_noise* noise /* NULL ok iff p_drop == 0 */, double p_drop, int M, int T, const double* states,
+                              const double* inputs, const double* jac, const double* g_states, const double* g_inputs /* may be NULL */,
+                              double* g_params, double* g_x0, void* stream);
 /* Reverse-time adjoint of the rollout: given dJ/dstates, dJ/dinputs (either may be NULL) returns
  * dJ/d{log_lengthscales [P], centers [B][P], f_linear.weight [U][B]} (overwritten, this rank's
  * particles only; with policy->bias also dJ/dbias into policy->g_bias) and optionally dJ/dx0 [M][S].  Replaces autograd's backward through

@@ -7,6 +7,8 @@
 //                        MC_PILCO4PMS.apply_policy, policy_learning/MC_PILCO.py:808-906, as mcp_rollout_pd_meas has it for the PD law)
 //   mcp_rollout_mlp_drop, mcp_rollout_mlp_drop_bwd   either pair with inverted dropout on the hidden units (template DROP; masks from the
 //                        launch's mcp_noise: a buffer, or Philox on the RBF masks' stream); p_drop == 0: the kernels without DROP
+//   mcp_rollout_mlp_track, mcp_rollout_mlp_track_bwd   the dropout pair with target-trajectory features behind the network's own (template TRK:
+//                        the errors target[t][idx[i]] - x[idx[i]], the map of policy_learning/Policy.py:389-403); no track: the dropout pair
 // The forward kernel is the step loop of rollout_open.hip's feedback form with the PD law exchanged for the network: phases S, K, V, J, J', F
 // and the noise addressing are the same functions (rollout_open_phases.h) and the same statements on the same operands, and the library is
 // built without floating-point contraction, so the states carry the bits of mcp_rollout_open fed with the launch's own inputs.  Per step
@@ -144,13 +146,33 @@ template <bool PMS>
 struct OpenArgsMlpDrop : MlpArgsOf<PMS>::type {
   MlpDropArgs drop;
 };
-template <bool PMS, bool DROP>
+// TRACKING form (template TRK, mcp_rollout_mlp_track): n more feature sources per trajectory -- source nnp + nap + i reads component idx[i]
+// of the row the other sources read (xs; measured form: the measurement row) and of target[t], and writes the error target - x behind the
+// cosines, at nnp + 2 nap + i.  At most 2 * MCP_MAX_STATE sources in all (the two lists are disjoint): with PT = 16 exactly the RF_NT threads.
+// The target is read from global memory at the top of the step, ahead of the barrier that publishes x_t.  The tracking forms are built on the
+// dropout forms' arguments and statements alone (p_drop == 0: `nodrop`, every unit kept at scale 1 -- the bits of the forms without
+// dropout -- and neither masks nor Philox are looked at); the forms without TRK take no part in any of it.
+struct MlpTrackArgs {
+  int n, nodrop;
+  int idx[MCP_MAX_STATE];
+  const double* target;  // [rows >= T][S]
+};
+static_assert(2 * MCP_MAX_STATE * 16 <= RF_NT, "a feature source per thread in the widest tile");
+template <bool PMS>
+struct OpenArgsMlpTrack : OpenArgsMlpDrop<PMS> {
+  MlpTrackArgs trk;
+};
+template <bool PMS, bool DROP, bool TRK = false>
 struct MlpKernelArgs {
   typedef typename MlpArgsOf<PMS>::type type;
 };
 template <bool PMS>
-struct MlpKernelArgs<PMS, true> {
+struct MlpKernelArgs<PMS, true, false> {
   typedef OpenArgsMlpDrop<PMS> type;
+};
+template <bool PMS>
+struct MlpKernelArgs<PMS, true, true> {
+  typedef OpenArgsMlpTrack<PMS> type;
 };
 // whether unit `unit` of trajectory m (of this launch's M; the descriptor adds particle_offset) is kept in row t
 __device__ __forceinline__ bool mlp_keep(const mcp_noise& nzl, uint32_t thr, int H, int M, int m, int t, int unit) {
@@ -158,17 +180,19 @@ __device__ __forceinline__ bool mlp_keep(const mcp_noise& nzl, uint32_t thr, int
 }
 template <int PT>
 __device__ __forceinline__ void mlp_layer_fwd_drop(const double* W, const double* b, int pitch, int in, int out, const double* x, int xp, double* y,
-                                                   int yp, int tid, const mcp_noise& nzl, const MlpDropArgs& dr, int H, int off, int M, int m0, int t) {
+                                                   int yp, int tid, const mcp_noise& nzl, const MlpDropArgs& dr, int H, int off, int M, int m0, int t,
+                                                   bool all = false) {  // (all: a tracking form without dropout -- every unit kept)
   for (int it = tid; it < PT * out; it += RF_NT) {
     const int p = it / out, j = it - p * out;
-    const bool keep = mlp_keep(nzl, dr.thr, H, M, imin(m0 + p, M - 1), t, off + j);
+    const bool keep = all || mlp_keep(nzl, dr.thr, H, M, imin(m0 + p, M - 1), t, off + j);
     const double h = fast_tanh(mlp_unit(W + j * pitch, b[j], x + p * xp, in));
     y[p * yp + j] = keep ? dr.scale * h : 0.0;
   }
 }
 
-template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool WLDS, bool PMS = false, bool DROP = false>
-__global__ __launch_bounds__(RF_NT) void rollout_mlp_kernel(typename MlpKernelArgs<PMS, DROP>::type a) {
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool WLDS, bool PMS = false, bool DROP = false, bool TRK = false>
+__global__ __launch_bounds__(RF_NT) void rollout_mlp_kernel(typename MlpKernelArgs<PMS, DROP, TRK>::type a) {
+  static_assert(DROP || !TRK, "the tracking forms are built on the dropout forms");
   extern __shared__ double smem[];
   const mcp_model& md = a.model;
   const mcp_mlp_policy& pl = a.mlp;
@@ -239,10 +263,19 @@ __global__ __launch_bounds__(RF_NT) void rollout_mlp_kernel(typename MlpKernelAr
   unsigned bad = 0;
   int cur = 0;
   // the network: thread (trajectory fq, feature source fi) of the feature stage; the output threads' bound
-  const int nnp = pl.n_non_angle, nap = pl.n_angle, nsrc = nnp + nap;
+  int ntr = 0;         // (tracking form: the error sources behind the two lists' -- at most PT * nsrc = RF_NT threads, launch_mlp_w looks)
+  bool alldrop = false;  // (and whether it runs without dropout)
+  if constexpr (TRK) ntr = a.trk.n, alldrop = a.trk.nodrop != 0;
+  (void)alldrop;
+  const int nnp = pl.n_non_angle, nap = pl.n_angle, nsrc = nnp + nap + ntr;
   const bool isf = tid < PT * nsrc;
   const int fq = isf ? tid / nsrc : 0, fi = isf ? tid - fq * nsrc : 0;
-  const int fsrc = fi < nnp ? pl.non_angle[fi] : pl.angle[fi - nnp];
+  int fsrc = fi < nnp ? pl.non_angle[fi] : pl.angle[TRK ? imin(fi - nnp, MCP_MAX_STATE - 1) : fi - nnp];
+  bool iserr = false;
+  if constexpr (TRK) {
+    iserr = isf && fi >= nnp + nap;
+    if (iserr) fsrc = a.trk.idx[fi - nnp - nap];
+  }
   const double umax = isu ? pl.u_max[uk] : 1.0;
   const int nh = pl.n_hidden, H0 = pl.h[0], H1 = nh > 1 ? pl.h[1] : 0;
   const int HL = nh > 1 ? H1 : H0;                // the last hidden layer: its width, row pitch and rows
@@ -269,6 +302,10 @@ __global__ __launch_bounds__(RF_NT) void rollout_mlp_kernel(typename MlpKernelAr
   lds_barrier();
 
   for (int t = 0; t < T; ++t) {
+    double tgv = 0.0;  // (tracking form) this error source's component of target[t]: asked for here, needed behind the barrier
+    if constexpr (TRK) {
+      if (iserr) tgv = a.trk.target[(size_t)t * S + fsrc];
+    }
     // ---- phase S: publish x_t ----------------------------------------------------------------------------------------
     if (own) {
       xs[cur * PT * S + op * S + os] = xn;
@@ -313,17 +350,19 @@ __global__ __launch_bounds__(RF_NT) void rollout_mlp_kernel(typename MlpKernelAr
       double* fr = fl + fq * A.fp;
       if (fi < nnp) {
         fr[fi] = xv;
-      } else {
+      } else if (!iserr) {
         double sn, cs;
         sincos_fast(xv, &sn, &cs);
         fr[fi] = sn;
         fr[fi + nap] = cs;
+      } else {
+        fr[fi + nap] = tgv - xv;  // (nnp + 2 nap + i, i = fi - nnp - nap; the sweep's workers repeat this statement)
       }
     }
     lds_barrier();
     if constexpr (DROP) {
       mlp_layer_fwd_drop<PT>(WLDS ? wlc + mg.wl[0] : wtab[0], WLDS ? wlc + mg.bl[0] : wtab[3], WLDS ? mg.pitch[0] : pl.P, pl.P, H0, fl, A.fp, hl0,
-                             A.hp[0], tid, nzl, a.drop, H0 + H1, 0, M, m0, t);
+                             A.hp[0], tid, nzl, a.drop, H0 + H1, 0, M, m0, t, alldrop);
     } else if (WLDS) {
       mlp_layer_fwd<PT>(wlc + mg.wl[0], wlc + mg.bl[0], mg.pitch[0], pl.P, H0, fl, A.fp, hl0, A.hp[0], tid);
     } else {
@@ -333,7 +372,7 @@ __global__ __launch_bounds__(RF_NT) void rollout_mlp_kernel(typename MlpKernelAr
     if (nh > 1) {
       if constexpr (DROP) {
         mlp_layer_fwd_drop<PT>(WLDS ? wlc + mg.wl[1] : wtab[1], WLDS ? wlc + mg.bl[1] : wtab[4], WLDS ? mg.pitch[1] : H0, H0, H1, hl0, A.hp[0], hl1,
-                               A.hp[1], tid, nzl, a.drop, H0 + H1, H0, M, m0, t);
+                               A.hp[1], tid, nzl, a.drop, H0 + H1, H0, M, m0, t, alldrop);
       } else if (WLDS) {
         mlp_layer_fwd<PT>(wlc + mg.wl[1], wlc + mg.bl[1], mg.pitch[1], H0, H1, hl0, A.hp[0], hl1, A.hp[1], tid);
       } else {
@@ -454,9 +493,11 @@ __global__ __launch_bounds__(RF_NT) void rollout_mlp_kernel(typename MlpKernelAr
 
 // ---- descriptor checks (host fields only: the weights are device memory) ------------------------------------------------------------------
 // The precedence of pd_policy_check: a compiled limit first (MCP_ERR_LIMIT), then everything else (MCP_ERR_ARG).  n_hidden is looked at
-// before the widths it counts.
-static int mlp_policy_check(const mcp_model* model, const mcp_mlp_policy* p) {
-  if (p->U > MCP_MAX_INPUT || p->S > MCP_MAX_STATE || p->P > MCP_MAX_PFEAT) return MCP_ERR_LIMIT;
+// before the widths it counts.  `tr` (the track entries; NULL: none): its n is a compiled limit with the descriptor's and counts in P; its
+// own errors come behind the descriptor's, T being the rows the launch reads of its target.
+static int mlp_policy_check(const mcp_model* model, const mcp_mlp_policy* p, const mcp_mlp_track* tr = nullptr, int T = 0) {
+  const int ntr = tr ? tr->n : 0;
+  if (p->U > MCP_MAX_INPUT || p->S > MCP_MAX_STATE || p->P > MCP_MAX_PFEAT || ntr > MCP_MAX_STATE) return MCP_ERR_LIMIT;
   if (p->n_hidden < 1 || p->n_hidden > 2) return MCP_ERR_ARG;
   for (int l = 0; l < p->n_hidden; ++l)
     if (p->h[l] > MCP_MAX_HIDDEN) return MCP_ERR_LIMIT;
@@ -465,7 +506,7 @@ static int mlp_policy_check(const mcp_model* model, const mcp_mlp_policy* p) {
   for (int l = 0; l < p->n_hidden; ++l)
     if (p->h[l] < 1) return MCP_ERR_ARG;
   const bool lists = p->n_angle > 0 || p->n_non_angle > 0;
-  if (p->P != (lists ? p->n_non_angle + 2 * p->n_angle : p->S)) return MCP_ERR_ARG;
+  if (p->P != (lists ? p->n_non_angle + 2 * p->n_angle : p->S) + (ntr > 0 ? ntr : 0)) return MCP_ERR_ARG;
   unsigned seen = 0;  // an index at most once in the two lists together
   for (int i = 0; i < p->n_angle + p->n_non_angle; ++i) {
     const int s = i < p->n_angle ? p->angle[i] : p->non_angle[i - p->n_angle];
@@ -478,7 +519,26 @@ static int mlp_policy_check(const mcp_model* model, const mcp_mlp_policy* p) {
   }
   for (int k = 0; p->squash && k < p->U; ++k)
     if (!(p->u_max[k] > 0.0)) return MCP_ERR_ARG;
+  if (ntr < 0) return MCP_ERR_ARG;
+  if (ntr > 0) {
+    if (!tr->target || tr->rows < T) return MCP_ERR_ARG;
+    unsigned errs = 0;  // an error feature per component at most
+    for (int i = 0; i < ntr; ++i) {
+      const int s = tr->idx[i];
+      if (s < 0 || s >= p->S || (errs >> s & 1u)) return MCP_ERR_ARG;
+      errs |= 1u << s;
+    }
+  }
   return MCP_OK;
+}
+// whether a track entry runs its tracking kernels (tr NULL or n == 0: the dropout entry's own kernels on the same arguments)
+static inline bool track_active(const mcp_mlp_track* tr) { return tr && tr->n > 0; }
+static MlpTrackArgs mlp_track_args(const mcp_mlp_track* tr, double p_drop) {
+  MlpTrackArgs t;
+  memset(&t, 0, sizeof(t));
+  t.n = tr->n, t.nodrop = p_drop > 0.0 ? 0 : 1, t.target = tr->target;
+  for (int i = 0; i < tr->n; ++i) t.idx[i] = tr->idx[i];
+  return t;
 }
 // the descriptor the kernels see: without lists the features are the state
 static mcp_mlp_policy mlp_normalised(const mcp_mlp_policy* p) {
@@ -493,25 +553,28 @@ static mcp_mlp_policy mlp_normalised(const mcp_mlp_policy* p) {
 
 // ---- host path of the forward entry: checks -> fill -> ladder -----------------------------------------------------------------------------
 // one rung: the weights in LDS where the layout then fits, else in global memory; MCP_ERR_LIMIT where the rung does not fit at all
-template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool WLDS, bool PMS, bool DROP>
-static int launch_mlp_w(const typename MlpKernelArgs<PMS, DROP>::type& a, hipStream_t st) {
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool WLDS, bool PMS, bool DROP, bool TRK = false>
+static int launch_mlp_w(const typename MlpKernelArgs<PMS, DROP, TRK>::type& a, hipStream_t st) {
   const MlpActs A = mlp_acts(PT, a.mlp, mlp_geom(a.mlp), WLDS);
   const OpenLayout L = open_layout(PT, NEEDVAR, a.model.S, a.model.D, a.model.G, a.NpadMax, NEEDJAC, a.na, PMS, A.total);
   const size_t lds = (size_t)L.total * sizeof(double);
   if (lds > MCP_LDS_LIMIT) return MCP_ERR_LIMIT;
-  MCP_ENSURE_MAX_LDS((rollout_mlp_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, WLDS, PMS, DROP>));
-  hipLaunchKernelGGL((rollout_mlp_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, WLDS, PMS, DROP>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
+  if constexpr (TRK) {  // a thread per feature source (not reached within the compiled limits: the lists are disjoint, n <= MCP_MAX_STATE)
+    if (PT * (a.mlp.n_non_angle + a.mlp.n_angle + a.trk.n) > RF_NT) return MCP_ERR_LIMIT;
+  }
+  MCP_ENSURE_MAX_LDS((rollout_mlp_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, WLDS, PMS, DROP, TRK>));
+  hipLaunchKernelGGL((rollout_mlp_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, WLDS, PMS, DROP, TRK>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
 }
-template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool PMS, bool DROP>
-static int launch_mlp(const typename MlpKernelArgs<PMS, DROP>::type& a, hipStream_t st) {
-  const int rc = launch_mlp_w<PT, MAXDEG, NEEDVAR, NEEDJAC, true, PMS, DROP>(a, st);
-  return rc == MCP_ERR_LIMIT ? launch_mlp_w<PT, MAXDEG, NEEDVAR, NEEDJAC, false, PMS, DROP>(a, st) : rc;
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool PMS, bool DROP, bool TRK = false>
+static int launch_mlp(const typename MlpKernelArgs<PMS, DROP, TRK>::type& a, hipStream_t st) {
+  const int rc = launch_mlp_w<PT, MAXDEG, NEEDVAR, NEEDJAC, true, PMS, DROP, TRK>(a, st);
+  return rc == MCP_ERR_LIMIT ? launch_mlp_w<PT, MAXDEG, NEEDVAR, NEEDJAC, false, PMS, DROP, TRK>(a, st) : rc;
 }
-template <int PT, bool NEEDVAR, bool NEEDJAC, bool PMS, bool DROP>
-static int launch_mlp_deg(const typename MlpKernelArgs<PMS, DROP>::type& a, int maxdeg, hipStream_t st) {
-  return maxdeg == 0 ? launch_mlp<PT, 0, NEEDVAR, NEEDJAC, PMS, DROP>(a, st) : launch_mlp<PT, 2, NEEDVAR, NEEDJAC, PMS, DROP>(a, st);
+template <int PT, bool NEEDVAR, bool NEEDJAC, bool PMS, bool DROP, bool TRK = false>
+static int launch_mlp_deg(const typename MlpKernelArgs<PMS, DROP, TRK>::type& a, int maxdeg, hipStream_t st) {
+  return maxdeg == 0 ? launch_mlp<PT, 0, NEEDVAR, NEEDJAC, PMS, DROP, TRK>(a, st) : launch_mlp<PT, 2, NEEDVAR, NEEDJAC, PMS, DROP, TRK>(a, st);
 }
 // The ladder of tiles of rollout_open.hip's launch_open_tiles (at every compiled limit at once the one-trajectory recording rung takes
 // 85 KB + 1.3 KB of activations, the measured form one row [PT][S] more: nothing within the limits is refused), entered one rung lower
@@ -522,19 +585,19 @@ static int launch_mlp_deg(const typename MlpKernelArgs<PMS, DROP>::type& a, int 
 // width changes no bit of a trajectory (a column of phases K, V, J is computed the same way in every width: the identities with
 // mcp_rollout_open hold across the rungs).
 #define MLP_SMALL_SWARM 1024  // 4 trajectories x the 256 compute units of the MI355X
-template <bool PMS, bool DROP = false>
-static int launch_mlp_tiles(const typename MlpKernelArgs<PMS, DROP>::type& a, int maxdeg, bool wantvar, hipStream_t st) {
+template <bool PMS, bool DROP = false, bool TRK = false>
+static int launch_mlp_tiles(const typename MlpKernelArgs<PMS, DROP, TRK>::type& a, int maxdeg, bool wantvar, hipStream_t st) {
   const bool small = a.M <= MLP_SMALL_SWARM;
   if (!a.jac) {
-    if (!a.sample && !wantvar) return launch_mlp_deg<1, false, false, PMS, DROP>(a, maxdeg, st);
-    int rc = small ? MCP_ERR_LIMIT : launch_mlp_deg<16, true, false, PMS, DROP>(a, maxdeg, st);
-    if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<4, true, false, PMS, DROP>(a, maxdeg, st);
+    if (!a.sample && !wantvar) return launch_mlp_deg<1, false, false, PMS, DROP, TRK>(a, maxdeg, st);
+    int rc = small ? MCP_ERR_LIMIT : launch_mlp_deg<16, true, false, PMS, DROP, TRK>(a, maxdeg, st);
+    if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<4, true, false, PMS, DROP, TRK>(a, maxdeg, st);
     return rc;
   }
-  if (!a.sample && !wantvar) return launch_mlp_deg<1, false, true, PMS, DROP>(a, maxdeg, st);
-  int rc = small ? MCP_ERR_LIMIT : launch_mlp_deg<16, true, true, PMS, DROP>(a, maxdeg, st);
-  if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<4, true, true, PMS, DROP>(a, maxdeg, st);
-  if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<1, true, true, PMS, DROP>(a, maxdeg, st);
+  if (!a.sample && !wantvar) return launch_mlp_deg<1, false, true, PMS, DROP, TRK>(a, maxdeg, st);
+  int rc = small ? MCP_ERR_LIMIT : launch_mlp_deg<16, true, true, PMS, DROP, TRK>(a, maxdeg, st);
+  if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<4, true, true, PMS, DROP, TRK>(a, maxdeg, st);
+  if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<1, true, true, PMS, DROP, TRK>(a, maxdeg, st);
   return rc;
 }
 
@@ -550,12 +613,21 @@ static DropArgs mlp_with_drop(const Args& a, double p_drop) {
   return d;
 }
 
-// what mcp_rollout_mlp, mcp_rollout_mlp_meas and mcp_rollout_mlp_drop share (ms NULL: no measurement; p_drop 0: the kernels without dropout)
+// the arguments of a tracking form: those of the dropout form (at any p_drop), and the track
+template <class TrackArgs, class Args>
+static TrackArgs mlp_with_track(const Args& a, double p_drop, const mcp_mlp_track* trk) {
+  TrackArgs d = mlp_with_drop<TrackArgs, Args>(a, p_drop);
+  d.trk = mlp_track_args(trk, p_drop);
+  return d;
+}
+
+// what mcp_rollout_mlp, mcp_rollout_mlp_meas, mcp_rollout_mlp_drop and mcp_rollout_mlp_track share (ms NULL: no measurement; p_drop 0: the
+// kernels without dropout; trk NULL or n == 0: the kernels without the error features)
 static int mlp_dispatch(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_meas* ms, const mcp_noise* noise, double p_drop, int M, int T,
                         int particle_pred, const double* x0, double* states, double* inputs, double* mu, double* var, double* jac,
-                        uint32_t* status, void* stream) {
+                        uint32_t* status, void* stream, const mcp_mlp_track* trk = nullptr) {
   const int crc = closed_loop_checks(model && mlp && noise && x0 && states && inputs && status && mlp_drop_ok(p_drop), M, T, model, ms, false,
-                                     [&] { return mlp_policy_check(model, mlp); });
+                                     [&] { return mlp_policy_check(model, mlp, trk, T); });
   if (crc != MCP_OK) return crc;
   OpenArgsMlpMeas a;
   // (T == 1: the policy alone -- no transition, nothing to record)
@@ -563,6 +635,12 @@ static int mlp_dispatch(const mcp_model* model, const mcp_mlp_policy* mlp, const
   a.mlp = mlp_normalised(mlp);
   a.inputs = inputs;
   hipStream_t st = (hipStream_t)stream;
+  if (track_active(trk)) {
+    if (!meas_active(ms))
+      return launch_mlp_tiles<false, true, true>(mlp_with_track<OpenArgsMlpTrack<false>, OpenArgsMlp>(a, p_drop, trk), maxdeg, var != nullptr, st);
+    a.ms = *ms;
+    return launch_mlp_tiles<true, true, true>(mlp_with_track<OpenArgsMlpTrack<true>, OpenArgsMlpMeas>(a, p_drop, trk), maxdeg, var != nullptr, st);
+  }
   const bool drop = p_drop > 0.0;
   if (!meas_active(ms)) {
     if (drop) return launch_mlp_tiles<false, true>(mlp_with_drop<OpenArgsMlpDrop<false>, OpenArgsMlp>(a, p_drop), maxdeg, var != nullptr, st);
@@ -597,6 +675,16 @@ extern "C" int mcp_rollout_mlp_drop(const mcp_model* model, const mcp_mlp_policy
                                     int M, int T, int particle_pred, const double* x0, double* states, double* inputs, double* mu, double* var,
                                     double* jac, uint32_t* status, void* stream) {
   return mlp_dispatch(model, mlp, meas, noise, p_drop, M, T, particle_pred, x0, states, inputs, mu, var, jac, status, stream);
+}
+
+// mcp_rollout_mlp_drop with the target-trajectory features of the reference's Sum_of_gaussians_with_target_trajectory (policy_in =
+// cat(x, x*_t - x), policy_learning/Policy.py:389-403) behind the network's own: the TRK forms above, over the loops the other entries
+// replace (policy_learning/MC_PILCO.py:615-674, measured :808-906).  track NULL or track->n == 0: the kernels of mcp_rollout_mlp_drop on the
+// same arguments, the same bits.
+extern "C" int mcp_rollout_mlp_track(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_mlp_track* track, const mcp_meas* meas,
+                                     const mcp_noise* noise, double p_drop, int M, int T, int particle_pred, const double* x0, double* states,
+                                     double* inputs, double* mu, double* var, double* jac, uint32_t* status, void* stream) {
+  return mlp_dispatch(model, mlp, meas, noise, p_drop, M, T, particle_pred, x0, states, inputs, mu, var, jac, status, stream, track);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -672,24 +760,39 @@ struct MlpBwdArgsDrop : MlpBwdArgsOf<PMS>::type {
   mcp_noise nz;
   MlpDropArgs drop;
 };
-template <bool PMS, bool DROP>
+// TRACKING form (template TRK, mcp_rollout_mlp_track_bwd; built on the dropout form, as the forward's): the workers recompute the error
+// features of a row from the row the forward's network read and target[r] with the forward's statement (target - x), so the activation
+// rows -- and through them the outer sums' columns of g_W0 -- carry the forward's bits; stage C takes the errors' pull
+//   lambda[idx[i]] -= fbar[nnp + 2 nap + i]        (measured form: the same term in ybar, which reaches lambda through the filter's adjoint)
+// from a table ferr[s] (the error feature of component s, or -1) beside fplain / fang, in a region of its own: the layouts of the forms
+// without TRK do not move.
+template <bool PMS>
+struct MlpBwdArgsTrack : MlpBwdArgsDrop<PMS> {
+  MlpTrackArgs trk;
+};
+template <bool PMS, bool DROP, bool TRK = false>
 struct MlpBwdKernelArgs {
   typedef typename MlpBwdArgsOf<PMS>::type type;
 };
 template <bool PMS>
-struct MlpBwdKernelArgs<PMS, true> {
+struct MlpBwdKernelArgs<PMS, true, false> {
   typedef MlpBwdArgsDrop<PMS> type;
+};
+template <bool PMS>
+struct MlpBwdKernelArgs<PMS, true, true> {
+  typedef MlpBwdArgsTrack<PMS> type;
 };
 
 struct MlpBwdLayout {
   int rec, xs, gs, lam, gd, gz, tab, ul, gul, fbar, act, del, w, total;  // offsets in doubles
   int car, mtab;               // measured form: the filter's carries | pvel, ppos
   int keep;                    // dropout form: the keep words [3][pts][2]
+  int etab;                    // tracking form: ferr (ints, per state component)
   int rp, fp, ap, dp;          // pitches: record row | fbar row | activation row | delta row (odd)
   int aoff[3], one, doff[3];   // inside an activation row: the input of layer l, the constant 1; inside a delta row: the output of layer l
 };
 __host__ __device__ inline MlpBwdLayout mlp_bwd_layout(int pts, int S, int U, int G, int D, const mcp_mlp_policy& p, const MlpGeom& g, bool wlds,
-                                                       bool pms = false, bool drop = false) {
+                                                       bool pms = false, bool drop = false, bool trk = false) {
   MlpBwdLayout L;
   int o = 0;
   auto take = [&](int n) {
@@ -725,6 +828,7 @@ __host__ __device__ inline MlpBwdLayout mlp_bwd_layout(int pts, int S, int U, in
   L.car = pms ? take(2 * pts * S) : 0;     // [trajectory][position component]: mvbar | nvbar of the row behind
   L.mtab = pms ? take(MCP_MAX_STATE) : 0;  // ints: pvel (per state component: the velocity of the pair it is the position of, or -1) | ppos (the converse)
   L.keep = drop ? take(3 * pts * 2) : 0;   // 64-bit words: bit j = unit j of hidden layer l of the row's trajectory is kept
+  L.etab = trk ? take(MCP_MAX_STATE / 2) : 0;  // ints: ferr (per state component: the error feature that reads it, or -1)
   L.w = o;
   L.total = o + (wlds ? g.lds : 0);
   return L;
@@ -759,19 +863,29 @@ template <bool PMS>
 __device__ __forceinline__ mcp_noise mlp_bwd_noise(const MlpBwdArgsDrop<PMS>& a) {
   return noise_of_launch(a.nz);
 }
+template <bool PMS>
+__device__ __forceinline__ mcp_noise mlp_bwd_noise(const MlpBwdArgsTrack<PMS>& a) {  // (built on the dropout form's arguments)
+  return noise_of_launch(a.nz);
+}
 template <class Args>
 __device__ __forceinline__ mcp_noise mlp_bwd_noise(const Args&) {
   return mcp_noise{};
 }
 
-template <bool WLDS, bool PMS = false, bool DROP = false>
-__global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdKernelArgs<PMS, DROP>::type a) {
+template <bool WLDS, bool PMS = false, bool DROP = false, bool TRK = false>
+__global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdKernelArgs<PMS, DROP, TRK>::type a) {
+  static_assert(DROP || !TRK, "the tracking forms are built on the dropout forms");
   extern __shared__ double smem[];
   const mcp_mlp_policy& pl = a.mlp;
   const int S = a.S, U = a.U, G = a.G, D = a.D, M = a.M, T = a.T, nna = a.nna, na = a.na, pts = a.pts;
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const MlpGeom mg = mlp_geom(pl);
-  const MlpBwdLayout L = mlp_bwd_layout(pts, S, U, G, D, pl, mg, WLDS, PMS, DROP);
+  const MlpBwdLayout L = mlp_bwd_layout(pts, S, U, G, D, pl, mg, WLDS, PMS, DROP, TRK);
+  int ntr = 0;           // (tracking form: the error features; whether it runs without dropout; ferr)
+  bool alldrop = false;
+  if constexpr (TRK) ntr = a.trk.n, alldrop = a.trk.nodrop != 0;
+  (void)alldrop;
+  int* ferr = reinterpret_cast<int*>(smem + L.etab);
   const int GD = G * D, RP = L.rp;
   double* rec = smem + L.rec;
   double* xsl = smem + L.xs;
@@ -837,6 +951,12 @@ __global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdK
     zang[s] = za;
     fplain[s] = fpl;
     fang[s] = fan;
+    if constexpr (TRK) {
+      int fe = -1;
+      for (int i = 0; i < ntr; ++i)
+        if (a.trk.idx[i] == s) fe = i;
+      ferr[s] = fe;
+    }
     if constexpr (PMS) {
       int pv = -1, pp = -1;
       for (int i = 0; i < a.ms.n; ++i) {
@@ -891,6 +1011,12 @@ __global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdK
           A[lane + nap] = cs;
         }
       }
+      if constexpr (TRK) {  // the forward's statement on the forward's operands (at most 32 sources: a lane each)
+        if (lane >= nnp + nap && lane < nnp + nap + ntr) {
+          const int s = a.trk.idx[lane - nnp - nap];
+          A[lane + nap] = a.trk.target[(size_t)r * S + s] - xr[s];
+        }
+      }
       if (lane == 0) A[L.one] = 1.0;
       wave_lds_sync();
 #pragma unroll
@@ -898,7 +1024,7 @@ __global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdK
         if (l + 1 >= nl) continue;  // (uniform)
         if constexpr (DROP) {  // (every lane of the wave is here: the ballot is the layer's row of decisions)
           const bool unit = lane < mg.out[l];
-          const bool keep = unit && mlp_keep(nzl, a.drop.thr, Hd, M, imin(mp0 + p, M - 1), r, L.doff[l] + lane);
+          const bool keep = unit && (alldrop || mlp_keep(nzl, a.drop.thr, Hd, M, imin(mp0 + p, M - 1), r, L.doff[l] + lane));
           const unsigned long long kw = __ballot(keep);
           if (unit) {
             const double h = fast_tanh(mlp_unit(Wl[l] + lane * wp[l], bl[l][lane], A + L.aoff[l], mg.in[l]));
@@ -1055,12 +1181,18 @@ __global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdK
             if (r <= len - 1) {
               if (fplain[s] >= 0) v += fb[fplain[s]];
               if (fang[s] >= 0) v += fb[nnp + fang[s]] * Ar[nnp + nap + fang[s]] - fb[nnp + nap + fang[s]] * Ar[nnp + fang[s]];
+              if constexpr (TRK) {
+                if (ferr[s] >= 0) v -= fb[nnp + 2 * nap + ferr[s]];  // e = target - x
+              }
             }
           } else if (r <= len - 1) {
             auto ybar = [&](int c) {  // the policy's pull on component c of the measurement
               double y = 0.0;
               if (fplain[c] >= 0) y += fb[fplain[c]];
               if (fang[c] >= 0) y += fb[nnp + fang[c]] * Ar[nnp + nap + fang[c]] - fb[nnp + nap + fang[c]] * Ar[nnp + fang[c]];
+              if constexpr (TRK) {
+                if (ferr[c] >= 0) y -= fb[nnp + 2 * nap + ferr[c]];  // e = target - y
+              }
               return y;
             };
             const int pv = pvel[s], pp = ppos[s];
@@ -1110,10 +1242,10 @@ __global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdK
 
 // what mcp_rollout_mlp_bwd, mcp_rollout_mlp_meas_bwd and mcp_rollout_mlp_drop_bwd share (ms NULL: no measurement; p_drop 0: the kernels
 // without dropout, and `noise` is not looked at)
-template <bool WLDS, bool PMS, bool DROP = false>
-static int launch_mlp_bwd(const typename MlpBwdKernelArgs<PMS, DROP>::type& a, size_t lds, hipStream_t st) {
-  MCP_ENSURE_MAX_LDS((rollout_mlp_bwd_kernel<WLDS, PMS, DROP>));
-  hipLaunchKernelGGL((rollout_mlp_bwd_kernel<WLDS, PMS, DROP>), dim3((a.M + MB_PT - 1) / MB_PT), dim3(MB_NT), lds, st, a);
+template <bool WLDS, bool PMS, bool DROP = false, bool TRK = false>
+static int launch_mlp_bwd(const typename MlpBwdKernelArgs<PMS, DROP, TRK>::type& a, size_t lds, hipStream_t st) {
+  MCP_ENSURE_MAX_LDS((rollout_mlp_bwd_kernel<WLDS, PMS, DROP, TRK>));
+  hipLaunchKernelGGL((rollout_mlp_bwd_kernel<WLDS, PMS, DROP, TRK>), dim3((a.M + MB_PT - 1) / MB_PT), dim3(MB_NT), lds, st, a);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
 }
@@ -1123,12 +1255,20 @@ static int launch_mlp_bwd_drop(const Args& a, const mcp_noise* noise, double p_d
   d.nz = *noise;
   return a.wlds ? launch_mlp_bwd<true, PMS, true>(d, lds, st) : launch_mlp_bwd<false, PMS, true>(d, lds, st);
 }
+// a tracking sweep: the dropout form's arguments at any p_drop (the noise only where decisions are drawn again), and the track
+template <bool PMS, class Args>
+static int launch_mlp_bwd_track(const Args& a, const mcp_noise* noise, double p_drop, const mcp_mlp_track* trk, size_t lds, hipStream_t st) {
+  MlpBwdArgsTrack<PMS> d = mlp_with_track<MlpBwdArgsTrack<PMS>, Args>(a, p_drop, trk);
+  memset(&d.nz, 0, sizeof(d.nz));
+  if (noise && p_drop > 0.0) d.nz = *noise;
+  return a.wlds ? launch_mlp_bwd<true, PMS, true, true>(d, lds, st) : launch_mlp_bwd<false, PMS, true, true>(d, lds, st);
+}
 static int mlp_bwd_dispatch(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_meas* ms, const mcp_noise* noise, double p_drop, int M, int T,
                             const double* states, const double* inputs, const double* jac, const double* g_states, const double* g_inputs,
-                            double* g_params, double* g_x0, void* stream) {
-  const bool drop = p_drop > 0.0;
+                            double* g_params, double* g_x0, void* stream, const mcp_mlp_track* trk = nullptr) {
+  const bool drop = p_drop > 0.0, track = track_active(trk);
   const int crc = closed_loop_checks(model && mlp && states && inputs && g_states && (jac || T <= 1) && mlp_drop_ok(p_drop) && (noise || !drop), M, T,
-                                     model, ms, true, [&] { return mlp_policy_check(model, mlp); });
+                                     model, ms, true, [&] { return mlp_policy_check(model, mlp, trk, T); });
   if (crc != MCP_OK) return crc;
   if (!g_x0 && !g_params) return MCP_OK;  // nothing asked for
   const bool pms = meas_active(ms);
@@ -1143,12 +1283,14 @@ static int mlp_bwd_dispatch(const mcp_model* model, const mcp_mlp_policy* mlp, c
   size_t lds = 0;
   for (int pts = MB_PT; pts >= 1 && !a.pts; pts >>= 1)
     for (int wl = 1; wl >= 0 && !a.pts; --wl) {
-      const MlpBwdLayout L = mlp_bwd_layout(pts, a.S, a.U, a.G, a.D, a.mlp, mg, wl != 0, pms, drop);
+      const MlpBwdLayout L = mlp_bwd_layout(pts, a.S, a.U, a.G, a.D, a.mlp, mg, wl != 0, pms, drop || track, track);
       lds = (size_t)L.total * sizeof(double);
       if (lds <= MCP_LDS_LIMIT) a.pts = pts, a.wlds = wl;
     }
   if (!a.pts) return MCP_ERR_LIMIT;  // (not reached within the compiled limits: one trajectory takes 22 KB at all of them at once)
   hipStream_t st = (hipStream_t)stream;
+  if (track)
+    return pms ? launch_mlp_bwd_track<true, MlpBwdArgsMeas>(a, noise, p_drop, trk, lds, st) : launch_mlp_bwd_track<false, MlpBwdArgs>(a, noise, p_drop, trk, lds, st);
   if (drop) return pms ? launch_mlp_bwd_drop<true, MlpBwdArgsMeas>(a, noise, p_drop, lds, st) : launch_mlp_bwd_drop<false, MlpBwdArgs>(a, noise, p_drop, lds, st);
   if (pms) return a.wlds ? launch_mlp_bwd<true, true>(a, lds, st) : launch_mlp_bwd<false, true>(a, lds, st);
   return a.wlds ? launch_mlp_bwd<true, false>(a, lds, st) : launch_mlp_bwd<false, false>(a, lds, st);  // (the base part of `a`: mcp_rollout_mlp_bwd's own kernels)
@@ -1178,4 +1320,14 @@ extern "C" int mcp_rollout_mlp_drop_bwd(const mcp_model* model, const mcp_mlp_po
                                         int M, int T, const double* states, const double* inputs, const double* jac, const double* g_states,
                                         const double* g_inputs, double* g_params, double* g_x0, void* stream) {
   return mlp_bwd_dispatch(model, mlp, meas, noise, p_drop, M, T, states, inputs, jac, g_states, g_inputs, g_params, g_x0, stream);
+}
+
+// Reverse-time sweep of mcp_rollout_mlp_track: the TRK forms of the sweep above -- the error features recomputed in the activation rows,
+// their pull lambda[idx[i]] -= fbar[n_non_angle + 2 n_angle + i] in stage C (measured form: in the pull on the measurement).  track NULL or
+// track->n == 0: the kernels of mcp_rollout_mlp_drop_bwd on the same arguments, the same bits.
+extern "C" int mcp_rollout_mlp_track_bwd(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_mlp_track* track, const mcp_meas* meas,
+                                         const mcp_noise* noise, double p_drop, int M, int T, const double* states, const double* inputs,
+                                         const double* jac, const double* g_states, const double* g_inputs, double* g_params, double* g_x0,
+                                         void* stream) {
+  return mlp_bwd_dispatch(model, mlp, meas, noise, p_drop, M, T, states, inputs, jac, g_states, g_inputs, g_params, g_x0, stream, track);
 }

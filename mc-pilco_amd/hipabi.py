@@ -73,6 +73,11 @@ class MLPPolicy(C.Structure):
                 ("u_max", C.c_double * MAX_INPUT), ("W", dptr * 3), ("b", dptr * 3)]
 
 
+class MLPTrack(C.Structure):
+    """mcp_mlp_track: the error features target[t][idx[i]] - x[idx[i]] of the tracking entries, behind the cosines (n == 0: none)."""
+    _fields_ = [("n", C.c_int32), ("idx", C.c_int32 * MAX_STATE), ("rows", C.c_int32), ("target", dptr)]
+
+
 class OptState(C.Structure):
     _fields_ = [("step", C.c_int64), ("attempt", C.c_int64), ("pending", C.c_int64), ("adam_t", C.c_int64), ("total_attempts", C.c_int64),
                 ("es2", C.c_double), ("cost_prev", C.c_double)]
@@ -173,6 +178,10 @@ _SIGS = {
                                        C.c_int, dptr, dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
     "mcp_rollout_mlp_drop_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(MLPPolicy), C.POINTER(Meas), C.POINTER(Noise), C.c_double, C.c_int, C.c_int,
                                            dptr, dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
+    "mcp_rollout_mlp_track": (C.c_int, [C.POINTER(Model), C.POINTER(MLPPolicy), C.POINTER(MLPTrack), C.POINTER(Meas), C.POINTER(Noise), C.c_double,
+                                        C.c_int, C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
+    "mcp_rollout_mlp_track_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(MLPPolicy), C.POINTER(MLPTrack), C.POINTER(Meas), C.POINTER(Noise),
+                                            C.c_double, C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
     "mcp_rollout_bwd":(C.c_int, [C.POINTER(Model), C.POINTER(Policy), C.POINTER(Noise), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr,
                                   dptr, dptr, dptr, dptr, dptr, C.c_size_t, dptr]),
     "mcp_rollout_fwd_ex": (C.c_int, [C.POINTER(Model), C.POINTER(Policy), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr, dptr,

@@ -664,6 +664,8 @@ def model_step(model: PackedModel, x, u, t, noise: Optional[NoiseSpec] = None, p
 #   grad_tile, grad_shape   the raw parameter-gradient buffer of a sweep is [ceil(M / grad_tile)] + grad_shape
 #   fwd_drop, bwd_drop, drop_width   (a policy with dropout) the entries that take the probability -- and a measurement model or NULL, and
 #                  in the sweep the noise -- and the width of a row of its masks
+#   fwd_track, bwd_track, track_c()   (a policy that can track) the entries that take an mcp_mlp_track ahead of the dropout entries' arguments,
+#                  and the track itself -- None: the policy has no target, and the calls are the ones above
 #   check(model, T)   the policy's own refusals
 class PackedPD:
     """mcp_pd_policy of a ``Policy.PD_controller`` (reference policy_learning/Policy.py:406-449): the two gain parameters are kept as they
@@ -728,10 +730,13 @@ class PackedPD:
 class PackedMLP:
     """mcp_mlp_policy of a ``Policy.MLP_policy``: the parameter tensors (W0, b0, [W1, b1], Wout, bout) are kept as they are -- every
     launch takes the LIVE tensors, so an optimizer's in-place updates are seen.  Features f = [x[non_angle], sin x[angle], cos x[angle]]
-    (both lists empty: f = x)."""
+    (both lists empty: f = x).  A policy with a target trajectory (``policy.target_traj`` [rows, S], ``policy.error_indices``) appends the
+    tracking errors target[t][idx[i]] - x[idx[i]] behind them (mcp_mlp_track): ``track_idx`` and ``target`` (a contiguous float64 GPU copy,
+    not differentiable) are carried here, ``P`` counts them, and the launches go to the track entries."""
 
     fwd, bwd = ("mcp_rollout_mlp", "mcp_rollout_mlp_meas"), ("mcp_rollout_mlp_bwd", "mcp_rollout_mlp_meas_bwd")
     fwd_drop, bwd_drop = "mcp_rollout_mlp_drop", "mcp_rollout_mlp_drop_bwd"
+    fwd_track, bwd_track = "mcp_rollout_mlp_track", "mcp_rollout_mlp_track_bwd"  # (a policy with a track: whatever meas and p_drop are)
     fwd_outputs = ("mu", "var", "jac")
     grad_tile = 16  # one slab of parameter gradients per workgroup of the sweep
 
@@ -741,6 +746,13 @@ class PackedMLP:
         self.hidden = [int(h) for h in policy.hidden_sizes]
         self.angle, self.non_angle = [int(i) for i in policy.angle_indices], [int(i) for i in policy.non_angle_indices]
         self.P = len(self.non_angle) + 2 * len(self.angle) if (self.angle or self.non_angle) else self.S
+        self.track_idx, self.target = None, None
+        if getattr(policy, "target_traj", None) is not None:
+            self.track_idx = [int(i) for i in policy.error_indices]
+            if len(self.track_idx) > abi.MAX_STATE:
+                raise RuntimeError("at most %d error features" % abi.MAX_STATE)
+            self.target = _t(policy.target_traj, _dev(self.params[0].device)).reshape(-1, self.S).contiguous()
+            self.P += len(self.track_idx)
         self.squash = bool(policy.flg_squash)
         um = policy._u_max_values() or ()  # (floats, wherever the bounds are kept)
         self.u_max = np.full(self.U, um[0]) if len(um) == 1 else np.asarray(um, dtype=np.float64)
@@ -764,6 +776,18 @@ class PackedMLP:
             raise RuntimeError("the MLP policy is for %d states and %d inputs, the model has %d and %d" % (self.S, self.U, model.S, model.U))
         if T < 1:
             raise RuntimeError("the rollout needs at least one row")
+        if self.target is not None and self.target.shape[0] < T:
+            raise RuntimeError("the target trajectory has %d rows, the rollout needs %d" % (self.target.shape[0], T))
+
+    def track_c(self):
+        """mcp_mlp_track over the target held here, or None for a policy without one."""
+        if self.target is None:
+            return None
+        c = abi.MLPTrack()
+        c.n, c.rows, c.target = len(self.track_idx), int(self.target.shape[0]), self.target.data_ptr()
+        for i, v in enumerate(self.track_idx):
+            c.idx[i] = v
+        return c
 
     def to_c(self, *tensors):
         """The descriptor over ``tensors``: contiguous float64 GPU tensors in the parameter order, of the parameters' shapes."""
@@ -797,14 +821,27 @@ def _meas_arg(meas, T, M, meas_buf):
 
 
 def _drop_args(meas_arg, nz, p_drop):
-    """What a dropout entry takes between the policy and the sizes: the measurement model or NULL, the noise, the probability."""
-    return [meas_arg[0] if meas_arg else None, C.byref(nz), float(p_drop)]
+    """What a dropout entry takes between the policy and the sizes: the measurement model or NULL, the noise (None: NULL), the probability."""
+    return [meas_arg[0] if meas_arg else None, None if nz is None else C.byref(nz), float(p_drop)]
+
+
+def _entry(packed, names, plain, marg, nz, p_drop):
+    """(name, arguments between the policy and the sizes) of the launch or sweep of ``packed``, ``names`` = (plain and measured, dropout,
+    track): a policy with a track takes its track entry (the track, then the dropout entry's arguments) whatever ``marg`` and ``p_drop``
+    are; else p_drop > 0 the dropout entry; else the plain or measured one with ``plain`` behind the measurement."""
+    tc = packed.track_c() if names[2] else None
+    if tc is not None:
+        return names[2], [C.byref(tc)] + _drop_args(marg, nz, p_drop)
+    if p_drop > 0.0:
+        return names[1], _drop_args(marg, nz, p_drop)
+    return names[0][bool(marg)], marg + plain
 
 
 def _closed_launch(model, packed, tensors, noise, x0, T, particle_pred, status, record, meas=None, p_drop=0.0):
     """(states [T,M,S], inputs [T,M,U], jac or None) of ONE launch of the closed loop under ``packed`` over its parameter ``tensors``
     (packed.fwd); ``record`` and T > 1: the recording form.  With ``meas`` the measured entry, which writes ``meas.measured`` [T,M,S].
-    ``p_drop`` > 0: the policy's dropout entry (packed.fwd_drop), whatever ``meas`` is."""
+    ``p_drop`` > 0: the policy's dropout entry (packed.fwd_drop), whatever ``meas`` is.  A packed policy with a track (PackedMLP.track_c):
+    its track entry (packed.fwd_track), whatever ``meas`` and ``p_drop`` are; without one exactly the calls above."""
     M, dev = int(x0.shape[0]), model.device
     states, inputs, jac = _record_buffers(dev, T, M, model.S, model.U, model.G, model.D, record and T > 1)
     pc, nz = packed.to_c(*tensors), noise.to_c()
@@ -813,7 +850,7 @@ def _closed_launch(model, packed, tensors, noise, x0, T, particle_pred, status, 
         meas_buf = meas.measured = torch.empty(T, M, model.S, dtype=DT, device=dev)  # (allocated as rollout_forward_raw allocates it)
     outputs = {"jac": jac, "mu": None, "var": None}
     marg = _meas_arg(meas, T, M, meas_buf)
-    name, head = (packed.fwd_drop, _drop_args(marg, nz, p_drop)) if p_drop > 0.0 else (packed.fwd[meas is not None], marg + [C.byref(nz)])
+    name, head = _entry(packed, (packed.fwd, getattr(packed, "fwd_drop", None), getattr(packed, "fwd_track", None)), [C.byref(nz)], marg, nz, p_drop)
     abi.check(getattr(abi.lib(), name)(_mc(model), C.byref(pc), *head, M, T,
                                        int(bool(particle_pred)), abi.ptr(x0), abi.ptr(states), abi.ptr(inputs),
                                        *[abi.ptr(outputs[k]) for k in packed.fwd_outputs], abi.ptr(status), abi.stream()), name)
@@ -824,13 +861,15 @@ def _closed_sweep(model, packed, tensors, states, inputs, jac, g_states, g_input
                   p_drop=0.0):
     """(raw parameter gradients [ceil(M / grad_tile)] + grad_shape or None, g_x0 [M,S] or None) of ONE reverse-time sweep over the record
     (packed.bwd); with ``meas`` (and the measured states ``meas_buf`` its forward launch wrote) the measured entry.  ``p_drop`` > 0: the
-    policy's dropout entry (packed.bwd_drop) with the forward launch's ``noise``, from which it recomputes the keep decisions."""
+    policy's dropout entry (packed.bwd_drop) with the forward launch's ``noise``, from which it recomputes the keep decisions.  A packed
+    policy with a track: packed.bwd_track, as in ``_closed_launch``."""
     T, M, dev = int(states.shape[0]), int(states.shape[1]), states.device
     g_x0 = torch.empty(M, model.S, dtype=DT, device=dev) if want_x0 else None
     raw = torch.empty(((M + packed.grad_tile - 1) // packed.grad_tile,) + packed.grad_shape, dtype=DT, device=dev) if want_params else None
     pc = packed.to_c(*tensors)
     marg = _meas_arg(meas, T, M, meas_buf)
-    name, head = (packed.bwd_drop, _drop_args(marg, noise.to_c(), p_drop)) if p_drop > 0.0 else (packed.bwd[meas is not None], marg)
+    nz = noise.to_c() if p_drop > 0.0 else None  # (only the keep decisions are drawn again)
+    name, head = _entry(packed, (packed.bwd, getattr(packed, "bwd_drop", None), getattr(packed, "bwd_track", None)), [], marg, nz, p_drop)
     abi.check(getattr(abi.lib(), name)(_mc(model), C.byref(pc), *head, M, T, abi.ptr(states), abi.ptr(inputs),
                                        abi.ptr(jac), abi.ptr(g_states), abi.ptr(g_inputs), abi.ptr(raw), abi.ptr(g_x0), abi.stream()), name)
     return raw, g_x0
@@ -914,7 +953,9 @@ def rollout_mlp(model: PackedModel, mlp: PackedMLP, noise: Optional[NoiseSpec], 
     the PD law's place; the gradients go to the parameters that require them and to x0.  ``p_drop`` > 0: inverted dropout on the hidden
     units, h = keep ? tanh(.) / (1 - p_drop) : 0, one row of decisions per policy evaluation -- ``noise.masks`` [T,M,H] uint8 (H: the
     hidden widths added, layer 0's units first) or, without a buffer, Philox by seed / call / global particle, shard-invariant; the sweep
-    draws the same decisions again.  0 (the default): the calls made without the argument."""
+    draws the same decisions again.  0 (the default): the calls made without the argument.  A tracking policy (``mlp.target`` [rows >= T, S]:
+    features [x[non_angle], sin x[angle], cos x[angle], target[t][idx] - x[idx]], under ``meas`` with the measurement in x's place) runs the
+    track entries; the target gets no gradient."""
     return _rollout_closed("rollout_mlp", "the parameters", model, mlp, noise, x0, T, particle_pred, status, meas, p_drop)
 
 

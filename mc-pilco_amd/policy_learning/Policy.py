@@ -11,7 +11,8 @@ Dropout noise: ``noise_mode = "philox"`` (in-kernel counter-based generator, def
 drawn exactly like ``torch.nn.functional.dropout`` draws it on the CPU -- parity with the reference).
 ``scale_factor`` (plain ``Sum_of_gaussians`` only, as in the reference) is folded into the operands handed to the kernels.
 ``flg_bias`` adds ``f_linear.bias`` (not dropped out) to the linear layer inside the kernels; its gradient comes out of the adjoint sweep.
-``MLP_policy`` (this project's own: a tanh multilayer perceptron on the same features) runs inside the fused closed loop, mcp_rollout_mlp.
+``MLP_policy`` (this project's own: a tanh multilayer perceptron on the same features) runs inside the fused closed loop, mcp_rollout_mlp;
+with ``target_traj`` it tracks: the errors target_traj[t] - x behind its features (Policy.py:389-403's map), mcp_rollout_mlp_track.
 Exploration policies (Random_exploration, Sum_of_sinusoids :94-150, PD_controller :406-449) drive the simulated system once per
 trial (61-201 samples): host-side, their ``np.random`` draws in the reference's order so that a seeded launch script collects the
 same data.
@@ -158,19 +159,30 @@ class MLP_policy(Policy):
     draws the row with ONE ``bernoulli_(1 - p)`` call, ``MC_PILCO.reference_draws``' own (on ``draw_device``, set by MC_PILCO in "reference"
     noise mode, else on the policy's device), so the step loop and the fused launch see the same masks from the same seed; the fused
     launch takes them as a buffer or draws them in the kernel (ops.rollout_mlp, ``p_drop``).  ``flg_drop=False`` (the default):
-    ``p_dropout`` is accepted and ignored."""
+    ``p_dropout`` is accepted and ignored.
+    Tracking (``target_traj`` [rows, S]; the feature map of the reference's ``Sum_of_gaussians_with_target_trajectory``,
+    policy_learning/Policy.py:389-403, behind this class's own): the evaluation at time step ``t`` appends the errors
+    target_traj[t][i] - x[i], i in ``error_indices`` (default: all S components in order; the plain difference, not wrapped on angles),
+    so f = [x[non_angle], sin x[angle], cos x[angle], errors], ``feature_dim`` counts them and W0's last columns are theirs.  ``forward`` and
+    ``features`` then need ``t``.  The fused loop (mcp_rollout_mlp_track) reads row t of the target in policy evaluation t; the target is a
+    constant: it gets no gradient.  ``target_traj=None`` (the default): the class without any of it."""
 
     def __init__(self, state_dim, input_dim, hidden_sizes, angle_indices=None, non_angle_indices=None, u_max=1.0, flg_squash=True, weight_init=None,
-                 dtype=torch.float64, device=torch.device("cuda"), flg_drop=False):
+                 dtype=torch.float64, device=torch.device("cuda"), flg_drop=False, target_traj=None, error_indices=None):
         super().__init__(state_dim=state_dim, input_dim=input_dim, flg_squash=flg_squash, u_max=u_max, dtype=dtype, device=device)
         self.flg_drop = bool(flg_drop)
+        self.target_traj = None if target_traj is None else torch.as_tensor(target_traj).detach().to(self.device)  # (its own dtype: fusable() asks for float64)
+        if target_traj is None and error_indices is not None:
+            raise ValueError("error_indices needs a target_traj")
+        self.error_indices = [] if target_traj is None else (list(range(int(state_dim))) if error_indices is None else
+                                                             [int(i) for i in np.atleast_1d(error_indices)])
         self.hidden_sizes = [int(h) for h in np.atleast_1d(hidden_sizes)]
         if len(self.hidden_sizes) not in (1, 2) or any(h < 1 for h in self.hidden_sizes):
             raise ValueError("hidden_sizes holds one or two positive widths")
         self.angle_indices = [] if angle_indices is None else [int(i) for i in np.atleast_1d(angle_indices)]
         self.non_angle_indices = [] if non_angle_indices is None else [int(i) for i in np.atleast_1d(non_angle_indices)]
         self._lists = bool(self.angle_indices or self.non_angle_indices)
-        self.feature_dim = len(self.non_angle_indices) + 2 * len(self.angle_indices) if self._lists else int(state_dim)
+        self.feature_dim = (len(self.non_angle_indices) + 2 * len(self.angle_indices) if self._lists else int(state_dim)) + len(self.error_indices)
         self.drop_width = sum(self.hidden_sizes)  # a row of dropout decisions: the hidden units, layer 0's first
         widths = [self.feature_dim] + self.hidden_sizes + [int(input_dim)]
         names = ["0", "1", "out"] if len(self.hidden_sizes) == 2 else ["0", "out"]
@@ -201,14 +213,21 @@ class MLP_policy(Policy):
             else:
                 q.data.zero_()
 
-    def features(self, states):
+    def features(self, states, t=None):
         x = states.reshape([-1, self.state_dim])
-        if not self._lists:
-            return x
-        return torch.cat([x[:, self.non_angle_indices], torch.sin(x[:, self.angle_indices]), torch.cos(x[:, self.angle_indices])], dim=1)
+        if self.target_traj is None:
+            if not self._lists:
+                return x
+            return torch.cat([x[:, self.non_angle_indices], torch.sin(x[:, self.angle_indices]), torch.cos(x[:, self.angle_indices])], dim=1)
+        if t is None:
+            raise ValueError("a tracking MLP_policy is evaluated at a time step: pass t")
+        row = torch.as_tensor(self.target_traj).to(x.device)[int(t)].reshape(1, -1)
+        err = row[:, self.error_indices] - x[:, self.error_indices]
+        own = [x[:, self.non_angle_indices], torch.sin(x[:, self.angle_indices]), torch.cos(x[:, self.angle_indices])] if self._lists else [x]
+        return torch.cat(own + [err], dim=1)
 
     def forward(self, states, t=None, p_dropout=0.0):
-        h = self.features(states)
+        h = self.features(states, t)
         ps = self.mlp_parameters()
         p = float(p_dropout) if self.flg_drop else 0.0
         keep = None
@@ -233,8 +252,10 @@ class MLP_policy(Policy):
             return None
 
     def packed(self) -> "ops.PackedMLP":
-        """mcp_mlp_policy over the LIVE parameters (rebuilt if a tensor was replaced or a setting changed)."""
-        key = tuple(q.data_ptr() for q in self.mlp_parameters()) + (self.flg_squash, self._u_max_values())
+        """mcp_mlp_policy over the LIVE parameters (rebuilt if a tensor or the target was replaced or a setting changed)."""
+        tt = self.target_traj
+        key = tuple(q.data_ptr() for q in self.mlp_parameters()) + (self.flg_squash, self._u_max_values(), id(tt),
+                                                                    tt.data_ptr() if isinstance(tt, torch.Tensor) else None, tuple(self.error_indices))
         hit = self.__dict__.get("_packed_mlp")
         if hit is None or hit[0] != key:
             hit = self.__dict__["_packed_mlp"] = (key, ops.PackedMLP(self))
@@ -242,7 +263,9 @@ class MLP_policy(Policy):
 
     def fusable(self, model, T):
         """Whether T steps of this policy on ``model`` (an ops.PackedModel, or anything with ``S`` and ``U``) can run as the fused closed loop:
-        float64 parameters on a GPU, S and U those of the model, the index lists in range and disjoint, every width within the kernels' limits."""
+        float64 parameters on a GPU, S and U those of the model, the index lists in range and disjoint, every width within the kernels' limits
+        (``feature_dim``, the error features included, at most MAX_PFEAT); with a target: a float64 tensor [rows >= T, S], the error indices in
+        range and distinct."""
         S, U = int(self.state_dim), int(self.input_dim)
         if int(getattr(model, "S", -1)) != S or int(getattr(model, "U", -1)) != U or U > ops.abi.MAX_INPUT or S > ops.abi.MAX_STATE or int(T) < 1:
             return False
@@ -251,6 +274,12 @@ class MLP_policy(Policy):
         idx = self.angle_indices + self.non_angle_indices
         if any(i < 0 or i >= S for i in idx) or len(set(idx)) != len(idx):
             return False
+        tt, err = self.target_traj, self.error_indices
+        if tt is not None:
+            if not isinstance(tt, torch.Tensor) or tt.dtype != torch.float64 or tt.dim() != 2 or int(tt.shape[1]) != S or int(tt.shape[0]) < int(T):
+                return False
+            if any(i < 0 or i >= S for i in err) or len(set(err)) != len(err):
+                return False
         if self.feature_dim < 1 or self.feature_dim > ops.abi.MAX_PFEAT or any(h < 1 or h > ops.abi.MAX_HIDDEN for h in self.hidden_sizes):
             return False
         um = self._u_max_values()  # (by value: a list of bounds changed in place gives a new descriptor, a tensor on any device is read)
