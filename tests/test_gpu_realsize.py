@@ -447,6 +447,7 @@ def test_row_split_cluster_block_shares(name, N, M, T, parts, cmap):
             out[split] = (st.detach().clone(), inp.detach().clone(), [q.grad.clone() for q in w.params])
     finally:
         L.mcp_debug_set_row_split(-1)
+        L.mcp_debug_set_cluster_map(-1)
     es = float((out[1][0] - out[0][0]).abs().max())
     eu = float((out[1][1] - out[0][1]).abs().max())
     eg = max(float((a - b).abs().max() / b.abs().max()) for a, b in zip(out[1][2], out[0][2]))
