@@ -571,6 +571,38 @@ int mcp_cost_sums(int T, int M, const double* moments, const double* shift, doub
 int mcp_cost_finalize_sums(int T, int64_t n_total, const double* sums, const double* shift, double* out, double* mean_out,
                            void* stream);
 
+/* Control-effort and input-rate terms next to the state cost (the project's own extension: the reference's cost functions receive
+ * inputs_sequence and ignore it).  With d_x the scaled state distance of `mcp_cost`, idx = used[0..n_used) (distinct) and
+ *   d_u = sum_i ((u_t[idx[i]] - target[i]) / scales[i])^2                  (present when scales != NULL),
+ *   d_r = sum_i ((u_t[idx[i]] - u_{t-1}[idx[i]]) / rate_scales[i])^2, t >= 1; 0 at t = 0   (present when rate_scales != NULL),
+ *   f(d) = 1 - exp(-d)  (MCP_COST_CARTPOLE / _TRAJ / _TARGET),  f(d) = d  (MCP_COST_TARGET_QUAD):
+ *   MCP_COST_U_ADD:   c = f(d_x) + d_u + d_r    (the penalty stays active where the state cost saturates)
+ *   MCP_COST_U_JOINT: c = f(d_x + d_u + d_r)    (one saturated distance over states and inputs)
+ * Row T-1 of the inputs takes part in both terms.  NULL descriptor, n_used == 0 or both scale pointers NULL: no input terms -- the
+ * entries below run the kernels of mcp_cost_fwd / mcp_cost_bwd (the same bits) and `inputs` may be NULL. */
+#define MCP_COST_U_ADD 0
+#define MCP_COST_U_JOINT 1
+typedef struct mcp_cost_inputs {
+  int32_t U, mode, n_used;
+  int32_t used[MCP_MAX_INPUT];
+  const double* target;      /* [n_used] or NULL (= 0)            */
+  const double* scales;      /* [n_used] l_i, or NULL: no effort  */
+  const double* rate_scales; /* [n_used] r_i, or NULL: no rate    */
+} mcp_cost_inputs;
+/* costs[t][m] = c(x_{t,m}, u_{t,m}, u_{t-1,m}); moments and status as mcp_cost_fwd leaves them (mcp_cost_finalize, mcp_cost_sums and
+ * mcp_cost_finalize_sums take them unchanged).  inputs [T][M][U].  Replaces the caller's torch ops of a generic
+ * Expected_cost(lambda x, u, k: state_cost(x) + ((u - u*) / l)^2 + ((u_t - u_{t-1}) / r)^2) up to torch.mean / torch.std. */
+int mcp_cost_u_fwd(const mcp_cost* cost, const mcp_cost_inputs* cin, int T, int M, const double* states, const double* inputs,
+                   double* costs, double* moments, uint32_t* status, void* stream);
+/* g_states[t][m][:] and g_inputs[t][m][:] = (*g_cost) * gscale * d(sum_t sum_m c)/d{x, u}_{t,m}: whole rows are written (zeros on the
+ * components the cost does not read); the rate term couples u_t with u_{t-1} and u_{t+1} of the same particle, nothing else.  g_inputs
+ * NULL: state gradient only; without input terms a g_inputs given is zero-filled on `stream` ([T][M][cin->U]: with a NULL descriptor its width
+ * is unknown and it must be NULL).  No atomics: a particle's rows depend on
+ * that particle alone.  Replaces autograd's backward through the torch ops named above; g_inputs is what the adjoint sweeps
+ * (mcp_rollout_bwd, mcp_rollout_pd_bwd, mcp_rollout_mlp*_bwd, mcp_rollout_open_bwd) take as dJ/dinputs. */
+int mcp_cost_u_bwd(const mcp_cost* cost, const mcp_cost_inputs* cin, int T, int M, const double* states, const double* inputs,
+                   const double* g_cost, double gscale, double* g_states, double* g_inputs, void* stream);
+
 /* ---- the optimizer loop's bookkeeping on the device (MC_PILCO.reinforce_policy, policy_learning/MC_PILCO.py:475-607) ----------
  * The reference decides on the host, from torch.isnan(cost), whether a rollout counts, and so reads every step's cost back before
  * it can launch the next one.  These two entry points take the same decisions from device memory after each ATTEMPT (rollout +

@@ -5,6 +5,8 @@
 // The target-state distance is summed in the difference form sum_i ((x_i - x*_i) / l_i)^2; the reference
 // expands it (||x/l||^2 + ||x*/l||^2 - 2 (x/l).(x*/l)), which only adds cancellation: the two agree to the
 // rounding of the expanded form, within the 1e-12 the reference's fixture is held to.
+// cost_u_fwd_kernel / cost_u_bwd_kernel add control-effort and input-rate terms on the applied inputs (mcp_cost_inputs; no counterpart in the
+// reference) and the gradient in the inputs; the five kernels of the state costs are untouched by them.
 #include "mcp_device.h"
 
 using namespace mcp;
@@ -184,6 +186,155 @@ __global__ void cost_bwd_kernel(mcp_cost c, int T, int M, const double* __restri
   }
 }
 
+// ---- control-effort and input-rate terms (mcp_cost_inputs; the project's own extension, include/mcpilco_hip.h) ------------------------
+// d_u = sum_i ((u[idx_i] - u*_i) / l_i)^2 and d_r = sum_i ((u[idx_i] - up[idx_i]) / r_i)^2 (up: the particle's row t - 1, NULL at t = 0),
+// each absent (0) without its scales; summed in index order like cost_point's distance.
+__device__ __forceinline__ void input_dist(const mcp_cost_inputs& ci, const double* u, const double* up, double* du_out, double* dr_out) {
+  double du = 0.0, dr = 0.0;
+  if (ci.scales)
+    for (int i = 0; i < ci.n_used; ++i) {
+      double r = (u[ci.used[i]] - (ci.target ? ci.target[i] : 0.0)) / ci.scales[i];
+      du = fma(r, r, du);
+    }
+  if (ci.rate_scales && up)
+    for (int i = 0; i < ci.n_used; ++i) {
+      double r = (u[ci.used[i]] - up[ci.used[i]]) / ci.rate_scales[i];
+      dr = fma(r, r, dr);
+    }
+  *du_out = du;
+  *dr_out = dr;
+}
+
+// MCP_COST_U_ADD: f(d_x) + d_u + d_r;  MCP_COST_U_JOINT: f(d_x + d_u + d_r)
+__device__ __forceinline__ double cost_u_point(const mcp_cost& c, const mcp_cost_inputs& ci, const double* x, const double* u, const double* up,
+                                               int t) {
+  double dx, du, dr;
+  const double fx = cost_point(c, x, t, &dx);
+  input_dist(ci, u, up, &du, &dr);
+  if (ci.mode == MCP_COST_U_ADD) return (fx + du) + dr;
+  const double d = (dx + du) + dr;
+  if (c.kind == MCP_COST_TARGET_QUAD) return d;
+  return 1.0 - exp(-d);
+}
+
+// The factor a on the input terms of one (t, m) and (b_out) the factor b on d d_x / dx, G = g_cost gscale:
+// ADD: a = G, b = G f'(d_x);  JOINT: a = b = G f'(d_x + d_u + d_r).
+__device__ __forceinline__ double cost_u_factors(const mcp_cost& c, const mcp_cost_inputs& ci, const double* x, const double* u,
+                                                 const double* up, int t, double G, double* b_out) {
+  const bool quad = c.kind == MCP_COST_TARGET_QUAD;
+  double dx;
+  cost_point(c, x, t, &dx);
+  if (ci.mode == MCP_COST_U_ADD) {
+    if (b_out) *b_out = quad ? G : G * exp(-dx);
+    return G;
+  }
+  double du, dr;
+  input_dist(ci, u, up, &du, &dr);
+  const double a = quad ? G : G * exp(-((dx + du) + dr));
+  if (b_out) *b_out = a;
+  return a;
+}
+
+// cost_fwd_kernel with the input terms: one workgroup per time step, the same two passes and reduction order
+__global__ __launch_bounds__(256) void cost_u_fwd_kernel(mcp_cost c, mcp_cost_inputs ci, int T, int M, const double* __restrict__ states,
+                                                         const double* __restrict__ inputs, double* __restrict__ costs,
+                                                         double* __restrict__ moments, uint32_t* __restrict__ status) {
+  __shared__ double red[4];
+  __shared__ double mean_s;
+  const int t = blockIdx.x, tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+  double s = 0.0;
+  uint32_t bad = 0;
+  for (int m = tid; m < M; m += 256) {
+    const size_t i = (size_t)t * M + m;
+    const double* u = inputs + i * ci.U;
+    double v = cost_u_point(c, ci, states + i * c.S, u, t > 0 ? u - (size_t)M * ci.U : nullptr, t);
+    costs[i] = v;
+    if (is_bad(v)) bad |= MCP_STATUS_NAN;
+    s += v;
+  }
+  s = wave_sum(s);
+  if (lane == 0) red[wv] = s;
+  __syncthreads();
+  if (tid == 0) mean_s = ((red[0] + red[1]) + (red[2] + red[3])) / (double)M;
+  __syncthreads();
+  const double mean = mean_s;
+  double q = 0.0;
+  for (int m = tid; m < M; m += 256) {
+    double d = costs[(size_t)t * M + m] - mean;
+    q = fma(d, d, q);
+  }
+  q = wave_sum(q);
+  __syncthreads();
+  if (lane == 0) red[wv] = q;
+  __syncthreads();
+  if (tid == 0) {
+    moments[2 * t] = mean;
+    moments[2 * t + 1] = (red[0] + red[1]) + (red[2] + red[3]);
+  }
+  if (bad) atomicOr(status, bad);
+}
+
+// One thread per (t, m): its whole rows of g_states (cost_bwd_kernel's statements with the factor b_t) and of g_inputs
+//   g_inputs[t][j] = a_t (2 (u_t - u*) / l^2 + [t >= 1] 2 (u_t - u_{t-1}) / r^2) - [t + 1 < T] a_{t+1} 2 (u_{t+1} - u_t) / r^2;
+// a_{t+1} is recomputed from the particle's rows t + 1 (JOINT mode; ADD: a = G everywhere): no second pass, no atomics.
+__global__ void cost_u_bwd_kernel(mcp_cost c, mcp_cost_inputs ci, int T, int M, const double* __restrict__ states,
+                                  const double* __restrict__ inputs, const double* __restrict__ g_cost, double gscale,
+                                  double* __restrict__ g_states, double* __restrict__ g_inputs) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)T * M) return;
+  int t = (int)(i / M);
+  const size_t row = (size_t)M * ci.U;  // doubles between a particle's input rows t and t + 1
+  const double* x = states + i * c.S;
+  const double* u = inputs + i * ci.U;
+  const double* up = t > 0 ? u - row : nullptr;
+  double* g = g_states + i * c.S;
+  const double G = (g_cost ? *g_cost : 1.0) * gscale;
+  double e;
+  const double a = cost_u_factors(c, ci, x, u, up, t, G, &e);
+  for (int s = 0; s < c.S; ++s) g[s] = 0.0;
+  if (c.kind == MCP_COST_CARTPOLE) {
+    double th = x[c.angle_index];
+    double p = (fabs(th) - c.target_angle) / c.ls_angle;
+    double b = (x[c.pos_index] - c.target_pos) / c.ls_pos;
+    double sg = th > 0.0 ? 1.0 : (th < 0.0 ? -1.0 : 0.0);
+    g[c.angle_index] += e * 2.0 * p * sg / c.ls_angle;
+    g[c.pos_index] += e * 2.0 * b / c.ls_pos;
+  } else if (c.kind == MCP_COST_TRAJ) {
+    for (int k = 0; k < c.n_used; ++k) {
+      int s = c.used[k];
+      double r = (x[s] - c.target_traj[(size_t)t * c.S + s]) / c.lengthscales[k];
+      g[s] += e * 2.0 * r / c.lengthscales[k];
+    }
+  } else {
+    for (int k = 0; k < c.n_used; ++k) {
+      int s = c.used[k];
+      double r = (x[s] - c.target_traj[k]) / c.lengthscales[k];
+      g[s] += e * 2.0 * r / c.lengthscales[k];
+    }
+  }
+  if (!g_inputs) return;
+  double* gu = g_inputs + i * ci.U;
+  for (int j = 0; j < ci.U; ++j) gu[j] = 0.0;
+  const bool next = ci.rate_scales && t + 1 < T;
+  double an = G;
+  if (next && ci.mode != MCP_COST_U_ADD) an = cost_u_factors(c, ci, x + (size_t)M * c.S, u + row, u, t + 1, G, nullptr);
+  for (int k = 0; k < ci.n_used; ++k) {
+    int j = ci.used[k];
+    if (ci.scales) {
+      double r = (u[j] - (ci.target ? ci.target[k] : 0.0)) / ci.scales[k];
+      gu[j] += a * 2.0 * r / ci.scales[k];
+    }
+    if (ci.rate_scales && up) {
+      double r = (u[j] - up[j]) / ci.rate_scales[k];
+      gu[j] += a * 2.0 * r / ci.rate_scales[k];
+    }
+    if (next) {
+      double r = (u[row + j] - u[j]) / ci.rate_scales[k];
+      gu[j] -= an * 2.0 * r / ci.rate_scales[k];
+    }
+  }
+}
+
 static bool cost_ok(const mcp_cost* c) {
   if (!c || c->S <= 0 || c->S > MCP_MAX_STATE) return false;
   if (c->kind == MCP_COST_CARTPOLE)
@@ -237,6 +388,49 @@ extern "C" int mcp_cost_bwd(const mcp_cost* cost, int T, int M, const double* st
   size_t n = (size_t)T * M;
   hipLaunchKernelGGL(cost_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *cost, T, M, states, g_cost,
                      gscale, g_states);
+  MCP_LAUNCH_CHECK();
+  return MCP_OK;
+}
+
+// the inputs descriptor, when there is one: sizes, mode, distinct indices inside [0, U)
+static bool cost_inputs_ok(const mcp_cost_inputs* ci) {
+  if (!ci) return true;
+  if (ci->U < 1 || ci->U > MCP_MAX_INPUT || ci->n_used < 0 || ci->n_used > MCP_MAX_INPUT) return false;
+  if (ci->mode != MCP_COST_U_ADD && ci->mode != MCP_COST_U_JOINT) return false;
+  for (int i = 0; i < ci->n_used; ++i) {
+    if (ci->used[i] < 0 || ci->used[i] >= ci->U) return false;
+    for (int k = 0; k < i; ++k)
+      if (ci->used[k] == ci->used[i]) return false;
+  }
+  return true;
+}
+static bool cost_inputs_none(const mcp_cost_inputs* ci) { return !ci || ci->n_used == 0 || (!ci->scales && !ci->rate_scales); }
+
+extern "C" int mcp_cost_u_fwd(const mcp_cost* cost, const mcp_cost_inputs* cin, int T, int M, const double* states, const double* inputs,
+                              double* costs, double* moments, uint32_t* status, void* stream) {
+  if (!cost_ok(cost) || !cost_inputs_ok(cin)) return MCP_ERR_ARG;
+  if (cost_inputs_none(cin)) return mcp_cost_fwd(cost, T, M, states, costs, moments, status, stream);
+  if (!states || !inputs || !costs || !moments || !status || T <= 0 || M <= 0) return MCP_ERR_ARG;
+  hipLaunchKernelGGL(cost_u_fwd_kernel, dim3(T), dim3(256), 0, (hipStream_t)stream, *cost, *cin, T, M, states, inputs, costs, moments,
+                     status);
+  MCP_LAUNCH_CHECK();
+  return MCP_OK;
+}
+
+extern "C" int mcp_cost_u_bwd(const mcp_cost* cost, const mcp_cost_inputs* cin, int T, int M, const double* states, const double* inputs,
+                              const double* g_cost, double gscale, double* g_states, double* g_inputs, void* stream) {
+  if (!cost_ok(cost) || !cost_inputs_ok(cin)) return MCP_ERR_ARG;
+  if (cost_inputs_none(cin)) {
+    // (no descriptor, no U: the width of g_inputs is then unknown, so it cannot be given)
+    if ((g_inputs && !cin) || !states || !g_states || T <= 0 || M <= 0) return MCP_ERR_ARG;
+    if (g_inputs && hipMemsetAsync(g_inputs, 0, (size_t)T * M * cin->U * sizeof(double), (hipStream_t)stream) != hipSuccess)
+      return MCP_ERR_LAUNCH;
+    return mcp_cost_bwd(cost, T, M, states, g_cost, gscale, g_states, stream);
+  }
+  if (!states || !inputs || !g_states || T <= 0 || M <= 0) return MCP_ERR_ARG;
+  size_t n = (size_t)T * M;
+  hipLaunchKernelGGL(cost_u_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *cost, *cin, T, M, states,
+                     inputs, g_cost, gscale, g_states, g_inputs);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
 }

@@ -25,6 +25,7 @@ FWD_NO_GP_SHARDING = 2  # flag in mcp_rollout_fwd's particle_pred argument (MCP_
 FWD_KT_PACKED, FWD_XJ_PACKED = 4, 8  # the workspace still holds the packed operand copies of an earlier call on the same model (MCP_FWD_*_PACKED)
 POLICY_PLAIN, POLICY_ANGLES, POLICY_TRAJ = 0, 1, 2
 COST_CARTPOLE, COST_TRAJ, COST_TARGET, COST_TARGET_QUAD = 0, 1, 2, 3
+COST_U_ADD, COST_U_JOINT = 0, 1  # mcp_cost_inputs.mode: f(d_x) + d_u + d_r / f(d_x + d_u + d_r)
 
 dptr = C.c_void_p
 
@@ -96,6 +97,12 @@ class Cost(C.Structure):
     _fields_ = [("kind", C.c_int32), ("S", C.c_int32), ("angle_index", C.c_int32), ("pos_index", C.c_int32),
                 ("target_angle", C.c_double), ("target_pos", C.c_double), ("ls_angle", C.c_double), ("ls_pos", C.c_double),
                 ("n_used", C.c_int32), ("used", C.c_int32 * MAX_STATE), ("target_traj", dptr), ("lengthscales", dptr)]
+
+
+class CostInputs(C.Structure):
+    """mcp_cost_inputs: the control-effort and input-rate terms next to a state cost (scales NULL: no effort; rate_scales NULL: no rate)."""
+    _fields_ = [("U", C.c_int32), ("mode", C.c_int32), ("n_used", C.c_int32), ("used", C.c_int32 * MAX_INPUT), ("target", dptr),
+                ("scales", dptr), ("rate_scales", dptr)]
 
 
 class Dispatch(C.Structure):
@@ -195,6 +202,8 @@ _SIGS = {
     "mcp_cost_fwd": (C.c_int, [C.POINTER(Cost), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr]),
     "mcp_cost_finalize": (C.c_int, [C.c_int, C.c_int, dptr, C.POINTER(C.c_int64), dptr, dptr]),
     "mcp_cost_bwd": (C.c_int, [C.POINTER(Cost), C.c_int, C.c_int, dptr, dptr, C.c_double, dptr, dptr]),
+    "mcp_cost_u_fwd": (C.c_int, [C.POINTER(Cost), C.POINTER(CostInputs), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr]),
+    "mcp_cost_u_bwd": (C.c_int, [C.POINTER(Cost), C.POINTER(CostInputs), C.c_int, C.c_int, dptr, dptr, dptr, C.c_double, dptr, dptr, dptr]),
     "mcp_cost_sums": (C.c_int, [C.c_int, C.c_int, dptr, dptr, dptr, dptr]),
     "mcp_cost_finalize_sums": (C.c_int, [C.c_int, C.c_int64, dptr, dptr, dptr, dptr, dptr]),
     "mcp_adam_step_guarded": (C.c_int, [C.c_int, C.POINTER(dptr), C.POINTER(dptr), C.POINTER(dptr), C.POINTER(dptr), C.POINTER(C.c_int64), C.c_double,

@@ -1100,14 +1100,87 @@ class PackedCost:
         self.kind, self.c, self.device = kind, c, dev
 
 
+def _host(x):
+    return x.detach().cpu().numpy().astype(np.float64) if isinstance(x, torch.Tensor) else np.asarray(x, dtype=np.float64)
+
+
+class PackedCostInputs:
+    """mcp_cost_inputs: control-effort and input-rate terms next to a PackedCost (include/mcpilco_hip.h).  ``input_indices`` (None: every
+    input) are the columns of the inputs the terms read; ``lengthscales`` l_i / ``rate_lengthscales`` r_i switch the effort term
+    sum_i ((u_i - u*_i) / l_i)^2 and the rate term sum_i ((u_t,i - u_t-1,i) / r_i)^2 on (at least one is required);
+    ``target_input`` u* (None: 0); ``joint``: f(d_x + d_u + d_r) instead of f(d_x) + d_u + d_r.  Everything is checked on the host values
+    first: a bad descriptor raises ValueError before a device is touched."""
+
+    def __init__(self, U, device, input_indices=None, lengthscales=None, rate_lengthscales=None, target_input=None, joint=False):
+        U = int(U)
+        if not 1 <= U <= abi.MAX_INPUT:
+            raise ValueError("input cost: 1..%d inputs are supported (%d given)" % (abi.MAX_INPUT, U))
+        idx = list(range(U)) if input_indices is None else [int(i) for i in np.asarray(input_indices).reshape(-1)]
+        if not 1 <= len(idx) <= abi.MAX_INPUT:
+            raise ValueError("input cost: 1..%d input indices are supported (%d given)" % (abi.MAX_INPUT, len(idx)))
+        if any(i < 0 or i >= U for i in idx):
+            raise ValueError("input cost: input indices %s outside [0, %d)" % (idx, U))
+        if len(set(idx)) != len(idx):
+            raise ValueError("input cost: an input index is listed twice in %s" % (idx,))
+        if lengthscales is None and rate_lengthscales is None:
+            raise ValueError("input cost: lengthscales (effort term) or rate_lengthscales (rate term) must be given")
+        host = {}
+        for name, v in (("lengthscales", lengthscales), ("rate_lengthscales", rate_lengthscales), ("target_input", target_input)):
+            if v is None:
+                continue
+            h = _host(v).reshape(-1)
+            if h.size != len(idx):
+                raise ValueError("input cost: %d input indices but %d entries in %s" % (len(idx), h.size, name))
+            if name != "target_input" and not bool(np.all(np.isfinite(h) & (h > 0))):
+                raise ValueError("input cost: %s must be finite and > 0 (%s)" % (name, h.tolist()))
+            if name == "target_input" and not bool(np.all(np.isfinite(h))):
+                raise ValueError("input cost: target_input must be finite (%s)" % (h.tolist(),))
+            host[name] = h
+        dev = _dev(device)
+        c = abi.CostInputs()
+        c.U, c.mode, c.n_used = U, (abi.COST_U_JOINT if joint else abi.COST_U_ADD), len(idx)
+        for i, u in enumerate(idx):
+            c.used[i] = u
+        self._keep = {k: _t(h, dev) for k, h in host.items()}
+        for field, name in (("scales", "lengthscales"), ("rate_scales", "rate_lengthscales"), ("target", "target_input")):
+            if name in self._keep:
+                setattr(c, field, self._keep[name].data_ptr())
+        self.c, self.device, self.U, self.used, self.joint = c, dev, U, idx, bool(joint)
+
+
+def _check_cost_inputs(states, inputs, cost_inputs):
+    """The inputs [T,M,U] of a cost with input terms, detached and contiguous."""
+    if inputs is None or cost_inputs is None:
+        raise ValueError("a cost with input terms takes both `inputs` and `cost_inputs`")
+    T, M, _ = states.shape
+    if inputs.dim() != 3 or tuple(inputs.shape) != (T, M, cost_inputs.U) or inputs.dtype != DT or inputs.device != states.device:
+        raise RuntimeError("inputs must be float64 [T=%d, M=%d, U=%d] on the states' device (got %s %s)"
+                           % (T, M, cost_inputs.U, tuple(inputs.shape), inputs.dtype))
+    return inputs.detach().contiguous()
+
+
+def _cost_u_bwd(cost, states, g_cost, gscale, inputs, cost_inputs, want_g_inputs=True):
+    """mcp_cost_u_bwd -> (g_states, g_inputs or None)."""
+    T, M, _ = states.shape
+    st = states.contiguous()
+    g = torch.empty_like(st)
+    g_in = torch.empty_like(inputs) if want_g_inputs else None
+    abi.check(abi.lib().mcp_cost_u_bwd(C.byref(cost.c), C.byref(cost_inputs.c), T, M, abi.ptr(st), abi.ptr(inputs), abi.ptr(g_cost), gscale,
+                                       abi.ptr(g), abi.ptr(g_in), abi.stream()), "mcp_cost_u_bwd")
+    return g, g_in
+
+
 _COST_STATUS_SINK = {}  # per device: where mcp_cost_fwd ORs its flags when the caller does not ask for them (never read, never zeroed again)
 
 
-def cost_moments(cost: PackedCost, states, status=None):
+def cost_moments(cost: PackedCost, states, status=None, inputs=None, cost_inputs=None):
     """Per-time-step (mean, centred sum of squares) over this rank's particles -> [T,2], plus costs [T,M].  ``status``: a zeroed int32[1] to receive the
     kernel's flags (NaN in the costs); None: the flags go to a per-device sink -- the loops decide on the NaN of the cost itself, and a zero-fill
-    launch per optimizer step is 4 us of the 0.8 ms a launch-script step takes."""
+    launch per optimizer step is 4 us of the 0.8 ms a launch-script step takes.  With ``inputs`` [T,M,U] and ``cost_inputs`` (a
+    PackedCostInputs) the costs carry the control-effort / input-rate terms (mcp_cost_u_fwd)."""
     T, M, _ = states.shape
+    if inputs is not None or cost_inputs is not None:
+        inputs = _check_cost_inputs(states, inputs, cost_inputs)
     if cost.kind == "traj" and cost.traj_len != T:
         raise RuntimeError("target trajectory has %d rows but the rollout has %d steps" % (cost.traj_len, T))
     st = states.detach().contiguous()
@@ -1117,6 +1190,10 @@ def cost_moments(cost: PackedCost, states, status=None):
         status = _COST_STATUS_SINK.get(st.device)
         if status is None:
             status = _COST_STATUS_SINK[st.device] = torch.zeros(1, dtype=torch.int32, device=st.device)
+    if cost_inputs is not None:
+        abi.check(abi.lib().mcp_cost_u_fwd(C.byref(cost.c), C.byref(cost_inputs.c), T, M, abi.ptr(st), abi.ptr(inputs), abi.ptr(costs),
+                                           abi.ptr(mom), abi.ptr(status), abi.stream()), "mcp_cost_u_fwd")
+        return mom, costs, status
     abi.check(abi.lib().mcp_cost_fwd(C.byref(cost.c), T, M, abi.ptr(st), abi.ptr(costs), abi.ptr(mom), abi.ptr(status), abi.stream()),
               "mcp_cost_fwd")
     return mom, costs, status
@@ -1134,12 +1211,14 @@ def cost_finalize(moments_all, counts):
 class ExpectedCostFunction(torch.autograd.Function):
     """states [T,M,S] -> (sum_t mean_m c, sum_t std_m c) with the HIP cost kernels; with a
     torch.distributed ``group`` the mean/std pool all ranks' particles (one all-gather of the
-    [T,2] moments).  ``counts``: particles per rank (default: every rank holds M)."""
+    [T,2] moments).  ``counts``: particles per rank (default: every rank holds M).  With ``inputs`` [T,M,U] and ``cost_inputs`` the cost
+    carries the input terms and the backward returns a gradient for the inputs as well."""
 
     @staticmethod
-    def forward(ctx, states, cost, group, counts):
+    def forward(ctx, states, cost, group, counts, inputs=None, cost_inputs=None):
         ctx.set_materialize_grads(False)
-        mom, _, _ = cost_moments(cost, states)
+        mom, _, _ = cost_moments(cost, states, None, inputs, cost_inputs)
+        ctx.cost_inputs = cost_inputs
         M = states.shape[1]
         if group is not None:
             from . import sharding
@@ -1151,38 +1230,55 @@ class ExpectedCostFunction(torch.autograd.Function):
             mom_all = mom.unsqueeze(0)
         out = cost_finalize(mom_all, counts)
         ctx.cost, ctx.m_total = cost, sum(counts)
-        ctx.save_for_backward(states.detach())
+        if cost_inputs is None:
+            ctx.save_for_backward(states.detach())
+        else:
+            ctx.save_for_backward(states.detach(), inputs.detach().contiguous())
         return out[0], out[1]
 
     @staticmethod
     def backward(ctx, g_cost, _g_std):
+        if ctx.cost_inputs is not None:
+            states, inputs = ctx.saved_tensors
+            if g_cost is None:
+                return torch.zeros_like(states), None, None, None, (torch.zeros_like(inputs) if ctx.needs_input_grad[4] else None), None
+            gc = g_cost.detach().to(dtype=DT).reshape(1).contiguous()
+            g, g_in = _cost_u_bwd(ctx.cost, states, gc, 1.0 / float(ctx.m_total), inputs, ctx.cost_inputs, ctx.needs_input_grad[4])
+            return g, None, None, None, g_in, None
         (states,) = ctx.saved_tensors
         T, M, _ = states.shape
         if g_cost is None:  # (only the std output is used downstream: this operator carries no gradient through it, as before)
-            return torch.zeros_like(states), None, None, None
+            return (torch.zeros_like(states),) + (None,) * (len(ctx.needs_input_grad) - 1)
         g = torch.empty_like(states)
         st = states.contiguous()
         gc = g_cost.detach().to(dtype=DT).reshape(1).contiguous()  # stays on the device: no host sync
         abi.check(abi.lib().mcp_cost_bwd(C.byref(ctx.cost.c), T, M, abi.ptr(st), abi.ptr(gc), 1.0 / float(ctx.m_total), abi.ptr(g), abi.stream()),
                   "mcp_cost_bwd")
-        return g, None, None, None
+        return (g,) + (None,) * (len(ctx.needs_input_grad) - 1)
 
 
-def expected_cost_raw(cost: PackedCost, states, g_one):
+def expected_cost_raw(cost: PackedCost, states, g_one, inputs=None, cost_inputs=None, want_g_inputs=False):
     """(cost, std, dJ/dstates) of this process's particles without autograd: exactly the launches ExpectedCostFunction's forward and backward
     make (``g_one``: a device scalar 1.0, the upstream gradient ``cost.backward()`` starts from).  For callers that replay the step from a
-    HIP graph (MC_PILCO.reinforce_policy): the autograd engine's own stream bookkeeping does not survive a stream capture."""
-    mom, _, _ = cost_moments(cost, states)
+    HIP graph (MC_PILCO.reinforce_policy): the autograd engine's own stream bookkeeping does not survive a stream capture.  With
+    ``inputs`` / ``cost_inputs`` the cost carries the input terms; ``want_g_inputs``: dJ/dinputs is returned as a fourth value (None for a
+    cost without input terms: the adjoint sweeps take that as "no gradient")."""
+    mom, _, _ = cost_moments(cost, states, None, inputs, cost_inputs)
     T, M, _ = states.shape
     out = cost_finalize(mom.unsqueeze(0), [M])
     st = states.detach().contiguous()
+    if cost_inputs is not None:
+        g, g_in = _cost_u_bwd(cost, st, g_one, 1.0 / float(M), inputs.detach().contiguous(), cost_inputs, want_g_inputs)
+        return (out[0], out[1], g, g_in) if want_g_inputs else (out[0], out[1], g)
     g = torch.empty_like(st)
     abi.check(abi.lib().mcp_cost_bwd(C.byref(cost.c), T, M, abi.ptr(st), abi.ptr(g_one), 1.0 / float(M), abi.ptr(g), abi.stream()), "mcp_cost_bwd")
-    return out[0], out[1], g
+    return (out[0], out[1], g, None) if want_g_inputs else (out[0], out[1], g)
 
 
-def expected_cost(cost: PackedCost, states, group=None, counts=None):
-    return ExpectedCostFunction.apply(states, cost, group, counts)
+def expected_cost(cost: PackedCost, states, group=None, counts=None, inputs=None, cost_inputs=None):
+    if inputs is None and cost_inputs is None:
+        return ExpectedCostFunction.apply(states, cost, group, counts)
+    return ExpectedCostFunction.apply(states, cost, group, counts, inputs, cost_inputs)
 
 
 class LocalCostFunction(torch.autograd.Function):
@@ -1191,8 +1287,9 @@ class LocalCostFunction(torch.autograd.Function):
     d(sum_t mean_m c)/dtheta],  sums [2T] = mcp_cost_sums: per time step sum_m (c - shift_t) and sum_m (c - shift_t)^2)."""
 
     @staticmethod
-    def forward(ctx, states, cost, m_total, shift, sums_out=None):
-        mom, _, _ = cost_moments(cost, states)
+    def forward(ctx, states, cost, m_total, shift, sums_out=None, inputs=None, cost_inputs=None):
+        mom, _, _ = cost_moments(cost, states, None, inputs, cost_inputs)
+        ctx.cost_inputs = cost_inputs
         T, M = states.shape[0], states.shape[1]
         # (sums_out: a 1-tuple holding the caller's slot of the step's all-reduce message, sharding.StepMessage.sums -- in a tuple so that
         #  autograd does not take the slot for an input of this function)
@@ -1202,12 +1299,20 @@ class LocalCostFunction(torch.autograd.Function):
         abi.check(abi.lib().mcp_cost_sums(T, M, abi.ptr(mom), abi.ptr(shift), abi.ptr(sums), abi.stream()), "mcp_cost_sums")
         local = cost_finalize(mom.unsqueeze(0), [M])[0] * (float(M) / float(m_total))
         ctx.cost, ctx.m_total = cost, int(m_total)
-        ctx.save_for_backward(states.detach())
+        if cost_inputs is None:
+            ctx.save_for_backward(states.detach())
+        else:
+            ctx.save_for_backward(states.detach(), inputs.detach().contiguous())
         ctx.mark_non_differentiable(sums)
         return local, sums
 
     @staticmethod
     def backward(ctx, g_local, _g_sums):
+        if ctx.cost_inputs is not None:
+            states, inputs = ctx.saved_tensors
+            gc = g_local.detach().to(dtype=DT).reshape(1).contiguous()
+            g, g_in = _cost_u_bwd(ctx.cost, states, gc, 1.0 / float(ctx.m_total), inputs, ctx.cost_inputs, ctx.needs_input_grad[5])
+            return g, None, None, None, None, g_in, None
         (states,) = ctx.saved_tensors
         T, M, _ = states.shape
         g = torch.empty_like(states)
@@ -1215,11 +1320,13 @@ class LocalCostFunction(torch.autograd.Function):
         gc = g_local.detach().to(dtype=DT).reshape(1).contiguous()
         abi.check(abi.lib().mcp_cost_bwd(C.byref(ctx.cost.c), T, M, abi.ptr(st), abi.ptr(gc), 1.0 / float(ctx.m_total), abi.ptr(g), abi.stream()),
                   "mcp_cost_bwd")
-        return g, None, None, None, None
+        return (g,) + (None,) * (len(ctx.needs_input_grad) - 1)
 
 
-def local_cost(cost: PackedCost, states, m_total, shift=None, sums_out=None):
-    return LocalCostFunction.apply(states, cost, int(m_total), shift, None if sums_out is None else (sums_out,))
+def local_cost(cost: PackedCost, states, m_total, shift=None, sums_out=None, inputs=None, cost_inputs=None):
+    if inputs is None and cost_inputs is None:
+        return LocalCostFunction.apply(states, cost, int(m_total), shift, None if sums_out is None else (sums_out,))
+    return LocalCostFunction.apply(states, cost, int(m_total), shift, None if sums_out is None else (sums_out,), inputs, cost_inputs)
 
 
 def cost_from_sums(sums, n_total, shift=None, mean_out=None):

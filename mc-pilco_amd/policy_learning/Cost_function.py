@@ -12,6 +12,10 @@ sums of a sharded step.  With several target rows, on CPU tensors or in another 
 ``cost_function`` (kept as an attribute: user code may call it) as ordinary torch ops, exactly as before.  A generic
 ``Expected_cost(cost_function)`` with a user-supplied torch function keeps working the same way (it is user code).
 ``forward(..., group=None)``: with a torch.distributed group the mean / std pool every rank's particles.
+
+The project's own extension (the reference's cost functions receive ``inputs_sequence`` and ignore it): ``Input_penalty`` adds a
+control-effort and an input-rate term on the applied inputs (``input_distance``) to one of the four kernel costs and runs in the HIP
+cost kernels too (mcp_cost_u_fwd / mcp_cost_u_bwd), which then return the gradient in the inputs the adjoint sweeps take.
 """
 import numpy as np
 import torch
@@ -96,6 +100,10 @@ class _HipExpectedCost(Expected_cost):
         """Whether this cost (for these states, when given) is evaluated by the HIP cost kernels: what makes an attempt recordable into a
         HIP graph (MC_PILCO.reinforce_policy).  A subclass that keeps a torch path for some instances or inputs answers for them here."""
         return True
+
+    def inputs_packed_for(self, inputs):
+        """The kernels' descriptor of the terms of this cost that read the inputs (ops.PackedCostInputs); None: it reads the states only."""
+        return None
 
     def forward(self, states_sequence, inputs_sequence=None, trial_index=None, group=None, counts=None):
         if not self.runs_on_kernels(states_sequence):
@@ -246,3 +254,110 @@ class Expected_saturated_distance(_TargetStateCost):
 
     _saturate = True
     _torch_cost = staticmethod(saturated_distance_from_target)
+
+
+# ---- control-effort and input-rate terms (the project's own extension: the reference's cost functions ignore inputs_sequence) -----------
+def input_distance(inputs_sequence, lengthscales=None, rate_lengthscales=None, target_input=None, input_indices=None):
+    """(d_u, d_r), each [T,M], over the input columns ``input_indices`` (None: every input):
+    d_u = sum_i ((u_t,i - u*_i) / l_i)^2 (zeros without ``lengthscales``; ``target_input`` None: u* = 0) and
+    d_r = sum_i ((u_t,i - u_t-1,i) / r_i)^2 for t >= 1, 0 at t = 0 (zeros without ``rate_lengthscales``).  Plain differentiable torch ops
+    in the difference form, like distance_from_target."""
+    u = inputs_sequence if input_indices is None else inputs_sequence[:, :, input_indices]
+
+    def as_t(v):
+        return torch.as_tensor(v, dtype=u.dtype, device=u.device).reshape(-1)
+
+    zero = torch.zeros(u.shape[0], u.shape[1], dtype=u.dtype, device=u.device)
+    d_u, d_r = zero, zero
+    if lengthscales is not None:
+        d = (u if target_input is None else u - as_t(target_input)) / as_t(lengthscales)
+        d_u = (d * d).sum(2)
+    if rate_lengthscales is not None:
+        d = (u[1:] - u[:-1]) / as_t(rate_lengthscales)
+        d_r = torch.cat([zero[:1], (d * d).sum(2)])
+    return d_u, d_r
+
+
+class Input_penalty(_HipExpectedCost):
+    """A state cost of this module with a control-effort term d_u and an input-rate term d_r (``input_distance``) on the inputs the policy
+    applied: ``state_cost`` is an instance of Cart_pole_cost, Expected_saturated_distance_from_trajectory, Expected_distance or
+    Expected_saturated_distance; with f(d) = 1 - exp(-d) (f(d) = d for Expected_distance) and d_x its scaled state distance,
+
+        joint=False:  c = f(d_x) + d_u + d_r      (the penalty stays active where the state cost saturates)
+        joint=True:   c = f(d_x + d_u + d_r)      (one saturated distance over states and inputs)
+
+    ``lengthscales`` l_i switch the effort term on, ``rate_lengthscales`` r_i the rate term (at least one); ``target_input`` u* (None: 0);
+    ``input_indices`` (None: every input).  On float64 GPU states and inputs [T,M,U <= MCP_MAX_INPUT] it runs in the HIP cost kernels
+    (mcp_cost_u_fwd / _bwd: the three-launch cost, recordable attempts, the sharded step's sums); everything else -- CPU tensors, another
+    dtype, trainable scales, a state cost that itself keeps its torch path -- evaluates ``cost_function``, the torch formula of the whole
+    cost, through ``Expected_cost``, call by call."""
+
+    def __init__(self, state_cost, lengthscales=None, rate_lengthscales=None, target_input=None, input_indices=None, joint=False):
+        super().__init__()
+        if not isinstance(state_cost, (Cart_pole_cost, Expected_saturated_distance_from_trajectory, _TargetStateCost)):
+            raise TypeError("Input_penalty: state_cost must be one of this module's kernel costs (got %s)" % type(state_cost).__name__)
+        if lengthscales is None and rate_lengthscales is None:
+            raise ValueError("Input_penalty: lengthscales (effort term) or rate_lengthscales (rate term) must be given")
+        self.state_cost, self.joint = state_cost, bool(joint)
+        self.lengthscales, self.rate_lengthscales, self.target_input = lengthscales, rate_lengthscales, target_input
+        self.input_indices = None if input_indices is None else [int(i) for i in np.asarray(input_indices).reshape(-1)]
+        self._trainable = any(isinstance(v, torch.Tensor) and v.requires_grad for v in (lengthscales, rate_lengthscales, target_input))
+        self._in_packs = {}  # the inputs descriptor, one per (U, device)
+        self.cost_function = self._torch_cost
+
+    def _torch_cost(self, states_sequence, inputs_sequence, trial_index):
+        """The whole cost [T,M] as torch ops, composed from the module's plain functions."""
+        sc, x, u, k = self.state_cost, states_sequence, inputs_sequence, trial_index
+        d_u, d_r = input_distance(u, self.lengthscales, self.rate_lengthscales, self.target_input, self.input_indices)
+        if isinstance(sc, _TargetStateCost):
+            d_x = distance_from_target(x, u, k, sc.target_state, sc.lengthscales, sc.active_dims)
+            if not sc._saturate:
+                return d_x + d_u + d_r  # (both modes coincide for the plain distance)
+            if self.joint:
+                return 1 - torch.exp(-(d_x + d_u + d_r))
+            return saturated_distance_from_target(x, u, k, sc.target_state, sc.lengthscales, sc.active_dims) + d_u + d_r
+        if isinstance(sc, Cart_pole_cost):
+            f_x = cart_pole_cost(x, u, k, sc.target_state, sc.lengthscales, sc.angle_index, sc.pos_index)
+        else:
+            f_x = saturated_distance_from_trajectory(x, u, k, sc.target_traj, sc.lengthscales, sc.flg_var_lengthscales, sc.used_indeces)
+        if self.joint:  # (these two plain functions return 1 - exp(-d_x): 1 - exp(-(d_x + d_u + d_r)) = 1 - (1 - f_x) exp(-(d_u + d_r)))
+            return 1 - (1 - f_x) * torch.exp(-(d_u + d_r))
+        return f_x + d_u + d_r
+
+    def runs_on_kernels(self, states=None):
+        if self._trainable or not self.state_cost.runs_on_kernels(states):
+            return False
+        return states is None or (states.is_cuda and states.dtype == torch.float64 and states.dim() == 3)
+
+    def _inputs_fit(self, states, inputs):
+        if not isinstance(inputs, torch.Tensor) or inputs.dim() != 3:
+            return False
+        U = inputs.shape[2]
+        return (inputs.is_cuda and inputs.dtype == torch.float64 and inputs.device == states.device and inputs.shape[:2] == states.shape[:2]
+                and 1 <= U <= ops.abi.MAX_INPUT and (self.input_indices is None or all(-U <= i < U for i in self.input_indices)))
+
+    def packed_for(self, states, trial_index=None):
+        self._packed = self.state_cost.packed_for(states, trial_index)  # (the state cost keeps its own per-trial descriptors)
+        return self._packed
+
+    def inputs_packed_for(self, inputs):
+        U = inputs.shape[2]
+        key = (U, inputs.device)
+        if key not in self._in_packs:
+            idx = None if self.input_indices is None else [i % U for i in self.input_indices]
+            self._in_packs[key] = ops.PackedCostInputs(U, inputs.device, idx, self.lengthscales, self.rate_lengthscales, self.target_input, self.joint)
+        return self._in_packs[key]
+
+    def forward(self, states_sequence, inputs_sequence=None, trial_index=None, group=None, counts=None):
+        if not (self.runs_on_kernels(states_sequence) and self._inputs_fit(states_sequence, inputs_sequence)):
+            return Expected_cost.forward(self, states_sequence, inputs_sequence, trial_index, group, counts)
+        return ops.expected_cost(self.packed_for(states_sequence, trial_index), states_sequence, group, counts, inputs_sequence,
+                                 self.inputs_packed_for(inputs_sequence))
+
+    def local_moments(self, states_sequence, inputs_sequence, trial_index, m_total, shift=None, sums_out=None):
+        if not (self.runs_on_kernels(states_sequence) and self._inputs_fit(states_sequence, inputs_sequence)):
+            return Expected_cost.local_moments(self, states_sequence, inputs_sequence, trial_index, m_total, shift, sums_out)
+        return ops.local_cost(self.packed_for(states_sequence, trial_index), states_sequence, m_total, shift, sums_out, inputs_sequence,
+                              self.inputs_packed_for(inputs_sequence))
+
+    from_sums = staticmethod(_TargetStateCost.from_sums)  # (the sums of either path have one meaning: pooled where local_moments left them)

@@ -512,8 +512,11 @@ class MC_PILCO(torch.nn.Module):
         model, pk = self.model_learning.packed(), pol.packed()
         states, inputs, jac, status = ops.rollout_forward_raw(model, pk, noise, x0, T, p, True, need_jac=True, gp_sharding=self.gp_sharding)
         self.last_status = status
-        cost, std, g_states = ops.expected_cost_raw(self.cost_function.packed_for(states, lp.trial_index), states, lp.graphs.one)
-        g_ls, g_c, g_w, _, g_b = ops.rollout_backward_raw(model, pk, noise, states, inputs, jac, g_states, None, p)
+        cf = self.cost_function
+        cin = cf.inputs_packed_for(inputs)  # (None: the cost reads the states only -- no inputs gradient, the sweep takes NULL as before)
+        cost, std, g_states, g_inputs = ops.expected_cost_raw(cf.packed_for(states, lp.trial_index), states, lp.graphs.one,
+                                                              None if cin is None else inputs, cin, want_g_inputs=True)
+        g_ls, g_c, g_w, _, g_b = ops.rollout_backward_raw(model, pk, noise, states, inputs, jac, g_states, g_inputs, p)
         by_param = {id(pol.log_lengthscales): g_ls, id(pol.centers): g_c, id(pol.f_linear.weight): g_w}
         if pol.f_linear.bias is not None:
             by_param[id(pol.f_linear.bias)] = g_b
