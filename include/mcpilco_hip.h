@@ -158,7 +158,11 @@ typedef struct mcp_policy {
 /* Where the rollout's random numbers come from.  Parity mode: the host draws them with the
  * reference's own torch calls (SURVEY 8c order) and passes buffers.  Performance mode:
  * eps==NULL / masks==NULL -> Philox4x32-10 keyed by (seed, call) and counted by GLOBAL particle
- * id (m + particle_offset), so a sharded run draws the same numbers as a single-GPU run. */
+ * id (m + particle_offset), so a sharded run draws the same numbers as a single-GPU run.
+ * Supported ranges of the addressing (csrc/mcp_device.h, philox_draw; restated and tested by tests/noise_truth.py): a time step t < 2^22 and a
+ * global particle id < 2^40 -- one counter word holds the id's high word, t << 8 and the stream at bit 30, so particle 2^40 at t = 0 is particle
+ * 0 at t = 1 and t = 2^22 is another stream's t = 0.  Every `call` of one seed draws other numbers (call + *call_dev is taken mod 2^64); the high
+ * word of `call` is XORed into the key word that holds the seed's low word, so two SEEDS are independent of each other while call < 2^32. */
 typedef struct mcp_noise {
   const double* eps;      /* [T-1][M][G] standard normals, or NULL                     */
   const uint8_t* masks;   /* [T][M][B]   dropout keep-masks {0,1}, or NULL (mcp_rollout_mlp_drop: [T][M][H], the hidden units) */

@@ -315,11 +315,16 @@ def check(c, con, M):
 def packed(c, con, M):
     """(model, policy, noise, meas, x0) on the GPU on the operands of ``operands(c, con, M)``: wm.packed with the construction's Kinv, var_scale, x0
     and noise rows."""
+    return packed_op(c, operands(c, con, M))
+
+
+def packed_op(c, op, philox=None):
+    """``packed`` on any operand dict of the layout of ``operands``.  ``philox``: a NoiseSpec without buffers that takes the place of the
+    operands' eps, masks and position noise (the in-kernel generator draws all three)."""
     from gpu_helpers import G as GG
     from gpu_helpers import dev, spec_from
     from mc_pilco_amd import ops
 
-    op = operands(c, con, M)
     md, pi = wm.model(c), wm.policy(c)
     pol = ops.PackedPolicy(c.kind, c.S, torch.log(GG(pi["ls"])).reshape(1, -1).requires_grad_(True), GG(pi["centers"]).requires_grad_(True),
                            GG(pi["weight"]).requires_grad_(True), c.u_max if np.isscalar(c.u_max) else list(c.u_max), True, angle=list(c.pol_angle),
@@ -328,11 +333,12 @@ def packed(c, con, M):
     gps = [ops.PackedGP(spec_from(q["ls"], wm.SIGMA_N, 1.0, q["poly"]), GG(q["cache"].X.numpy()), GG(q["cache"].alpha.numpy()), GG(k.numpy()))
            for q, k in zip(md["gps"], op["Kinv"])]
     pm = ops.PackedModel(gps, c.S, c.U, wm.TS, list(c.angle), list(c.not_angle), list(c.vel), list(c.not_vel), var_scale=op["var_scale"])
-    nz = ops.NoiseSpec(eps=GG(op["eps"].numpy()), masks=op["masks"].to(torch.uint8).to(dev()).contiguous())
+    nz = philox if philox is not None else ops.NoiseSpec(eps=GG(op["eps"].numpy()), masks=op["masks"].to(torch.uint8).to(dev()).contiguous())
     meas = None
     if c.pms is not None:
         b, a = orc.butter1(wm.FC)
-        meas = ops.MeasSpec(pos=list(c.pms[0]), vel=list(c.pms[1]), std_pos=list(pi["std_pos"]), b=b, a=a, pos_noise=GG(op["pos_noise"].numpy()))
+        meas = ops.MeasSpec(pos=list(c.pms[0]), vel=list(c.pms[1]), std_pos=list(pi["std_pos"]), b=b, a=a,
+                            pos_noise=None if philox is not None else GG(op["pos_noise"].numpy()))
     return pm, pol, nz, meas, GG(op["x0"].numpy())
 
 

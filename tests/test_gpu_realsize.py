@@ -618,14 +618,15 @@ def test_philox_normals_are_standard_normal_and_independent():
     assert not np.array_equal(e, e2)
 
 
-def _keep_bits(p, M, Tn, seed, call, forced=0):
+def _keep_bits(p, M, Tn, seed, call, forced=0, B=200, offset=0):
     """Dropout keep decisions of the in-kernel generator for every (t, particle, basis), read back EXACTLY: all RBF centres sit
     far inside one huge lengthscale (phi == 1 to 1e-12), weights are powers of two (25 basis functions per input, 8 inputs = 200),
-    no squashing -> u_k (1 - p) is the integer sum_j 2^j keep_j.  Returns bool [Tn, M, 200]."""
+    no squashing -> u_k (1 - p) is the integer sum_j 2^j keep_j.  Returns bool [Tn, M, B] (B <= 200; ``offset``: the particle_offset)."""
     from gpu_helpers import G, dev, forced_variant, spec_from
     from mc_pilco_amd import ops
 
-    S, U, B = 4, 8, 200
+    S, U = 4, 8
+    assert 176 <= B <= 200  # (every input has a basis function)
     Wm = np.zeros((U, B))
     for b in range(B):
         Wm[b // 25, b] = 2.0 ** (b % 25)
@@ -636,13 +637,13 @@ def _keep_bits(p, M, Tn, seed, call, forced=0):
     model = ops.PackedModel([gp, gp], S, U, 0.05, [], list(range(S)), [1, 3], [0, 2])
     x0 = G(np.zeros((M, S)))
     with forced_variant(forced), torch.no_grad():
-        st, inp, status = ops.rollout(model, pol, ops.NoiseSpec(seed=seed, call=call), x0, Tn, p)
+        st, inp, status = ops.rollout(model, pol, ops.NoiseSpec(seed=seed, call=call, particle_offset=offset), x0, Tn, p)
     assert int(status.item()) == 0
     v = (inp * (1.0 - p)).cpu().numpy()
     iv = np.rint(v).astype(np.int64)
     assert np.abs(v - iv).max() < 1e-3 and iv.min() >= 0 and iv.max() < 2 ** 25
     bits = ((iv[..., None] >> np.arange(25)) & 1).astype(bool)  # [Tn, M, U, 25]
-    return bits.reshape(Tn, M, B)
+    return bits.reshape(Tn, M, 200)[:, :, :B]
 
 
 @pytest.mark.parametrize("p", [0.25, 0.1])

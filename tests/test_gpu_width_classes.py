@@ -106,12 +106,13 @@ def _relerr(a, b):
     return float(np.abs(a.detach().cpu().numpy() - b).max() / max(np.abs(b).max(), 1e-300))
 
 
-def _run(c, code, pb, pipe, M, want_gx0):
-    """One rollout + expected cost + backward through the forced variant.  Returns (states, inputs, cost, policy, x0 with .grad, report)."""
+def _run(c, code, pb, pipe, M, want_gx0, philox=None):
+    """One rollout + expected cost + backward through the forced variant.  Returns (states, inputs, cost, policy, x0 with .grad, report).
+    ``philox``: a NoiseSpec without buffers (wm.packed)."""
     from gpu_helpers import forced_variant
     from mc_pilco_amd import hipabi, ops
 
-    model, pol, cost, nz, meas, x0 = wm.packed(c, M)
+    model, pol, cost, nz, meas, x0 = wm.packed(c, M, philox)
     if want_gx0:
         x0.requires_grad_(True)
     L = hipabi.lib()

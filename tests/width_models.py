@@ -219,8 +219,9 @@ def oracle_cost(c, st):
     return orc.traj_cost(st, TT(pi["traj"]), TT(pi["cost_ls"]), list(c.used))
 
 
-def oracle_rollout(c, M, pp, x0):
-    _, eps, masks, pos_noise = noise(c, M)
+def oracle_rollout(c, M, pp, x0, tables=None):
+    """``tables``: (eps, masks, pos_noise) in the place of the recorded noise of ``noise(c, M)``."""
+    eps, masks, pos_noise = noise(c, M)[1:] if tables is None else tables
     om = model(c)["om"]
     step = lambda m, x, u, e, sample: orc.mixed_next_state(m, x, u, e, sample, c.var_scale)  # noqa: E731
     if c.pms is not None:
@@ -243,8 +244,9 @@ def oracle(c, M):
     return st.detach().numpy(), inp.detach().numpy(), float(cost.detach()), g
 
 
-def packed(c, M):
-    """(model, policy, cost, noise, meas, x0) on the GPU, on the oracle's own X / alpha / Kinv."""
+def packed(c, M, philox=None):
+    """(model, policy, cost, noise, meas, x0) on the GPU, on the oracle's own X / alpha / Kinv.  ``philox``: a NoiseSpec without buffers in the
+    place of the recorded eps, masks and position noise."""
     from gpu_helpers import G as GG
     from gpu_helpers import dev, spec_from
     from mc_pilco_amd import ops
@@ -262,9 +264,10 @@ def packed(c, M):
         cost = ops.PackedCost("target", c.S, dev(), target_state=pi["traj"][-1, list(c.used)], lengthscales=pi["cost_ls"], active_dims=list(c.used))
     else:
         cost = ops.PackedCost("traj", c.S, dev(), target_traj=pi["traj"], lengthscales=pi["cost_ls"], used=list(c.used))
-    nz = ops.NoiseSpec(eps=GG(eps.numpy()), masks=masks.to(torch.uint8).to(dev()).contiguous())
+    nz = philox if philox is not None else ops.NoiseSpec(eps=GG(eps.numpy()), masks=masks.to(torch.uint8).to(dev()).contiguous())
     meas = None
     if c.pms is not None:
         b, a = orc.butter1(FC)
-        meas = ops.MeasSpec(pos=list(c.pms[0]), vel=list(c.pms[1]), std_pos=list(pi["std_pos"]), b=b, a=a, pos_noise=GG(pos_noise.numpy()))
+        meas = ops.MeasSpec(pos=list(c.pms[0]), vel=list(c.pms[1]), std_pos=list(pi["std_pos"]), b=b, a=a,
+                            pos_noise=None if philox is not None else GG(pos_noise.numpy()))
     return pm, pol, cost, nz, meas, GG(x0.numpy())
