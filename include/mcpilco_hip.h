@@ -607,6 +607,38 @@ int mcp_cost_u_fwd(const mcp_cost* cost, const mcp_cost_inputs* cin, int T, int 
 int mcp_cost_u_bwd(const mcp_cost* cost, const mcp_cost_inputs* cin, int T, int M, const double* states, const double* inputs,
                    const double* g_cost, double gscale, double* g_states, double* g_inputs, void* stream);
 
+/* Time-weighted, risk-sensitive objective over any of the costs above (the project's own extension: the reference minimises
+ * sum_t mean_m c and only prints sum_t std_m c).  With mu_t / sigma_t the pooled mean / unbiased (n - 1) std over the n particles of the
+ * swarm at step t:
+ *   J = sum_t w_t (mu_t + kappa sigma_t)    (what is minimised; kappa > 0 cautious, kappa < 0 uncertainty-seeking: PILCO's cost.expl)
+ *   S = sum_t w_t sigma_t                   (monitor; carries no gradient)
+ *   dJ/dc_tm = w_t [1/n + kappa (c_tm - mu_t) / ((n - 1) sigma_t)]
+ * -- unlike the reference's monitor, the kappa sigma term IS differentiated.  A row whose particles all have the same cost (sigma_t == 0,
+ * e.g. t = 0 with a zero-variance x0) keeps the factor w_t / n: the sigma term of that row's gradient is dropped, where autograd through
+ * torch.std gives NaN.  w: w_t >= 0, finite, not all zero (the caller's to ensure: it is device memory); kappa: any finite real;
+ * kappa != 0 needs n >= 2 (MCP_ERR_ARG).  w == NULL, kappa == 0 is the plain expected cost. */
+typedef struct mcp_objective {
+  const double* w; /* DEVICE [T]; NULL: ones */
+  double kappa;
+} mcp_objective;
+/* mcp_cost_finalize that also writes rows [T][2] = pooled (mean_t, unbiased std_t) and weights the sums: out[0] = J, out[1] = S.  The
+ * same pooling over R ranks and the same reduction tree: obj NULL (= {NULL, 0}) gives mcp_cost_finalize's out, bit for bit. */
+int mcp_cost_rows(int T, int R, const double* moments, const int64_t* counts, const mcp_objective* obj, double* rows, double* out,
+                  void* stream);
+/* mcp_cost_finalize_sums in the same way (the clamp of a negative variance and mean_out included). */
+int mcp_cost_rows_sums(int T, int64_t n_total, const double* sums, const double* shift, const mcp_objective* obj, double* rows,
+                       double* out, double* mean_out, void* stream);
+/* g_states (and g_inputs, when cin has terms and g_inputs != NULL) of (*g_cost) * J for this process's M particles of a swarm of n_total
+ * (n_total == M on one device).  costs: the [T][M] buffer mcp_cost_fwd / mcp_cost_u_fwd wrote (read, not recomputed); rows: from one of the
+ * two calls above, of the WHOLE swarm (both are read only where kappa != 0, and must be given regardless).  cin NULL (or without terms): the state costs' gradient; g_inputs as for mcp_cost_u_bwd.  The
+ * kernels are mcp_cost_bwd's / mcp_cost_u_bwd's with the scalar (*g_cost) * gscale replaced by (*g_cost) * dJ/dc_tm (gscale = 1 / n_total);
+ * the rate term's neighbour factor a_{t+1} is built from dJ/dc_{t+1,m}.  obj NULL gives their bits.  One thread per (t, m), no atomics.
+ * MCP_ERR_LIMIT: cin->U > MCP_MAX_INPUT;  MCP_ERR_ARG: a NULL pointer, T < 1, M < 1, n_total < M, a non-finite kappa, kappa != 0 with
+ * n_total < 2, a bad descriptor. */
+int mcp_cost_bwd_shaped(const mcp_cost* cost, const mcp_cost_inputs* cin, const mcp_objective* obj, int T, int M, int64_t n_total,
+                        const double* states, const double* inputs, const double* costs, const double* rows, const double* g_cost,
+                        double* g_states, double* g_inputs, void* stream);
+
 /* ---- the optimizer loop's bookkeeping on the device (MC_PILCO.reinforce_policy, policy_learning/MC_PILCO.py:475-607) ----------
  * The reference decides on the host, from torch.isnan(cost), whether a rollout counts, and so reads every step's cost back before
  * it can launch the next one.  These two entry points take the same decisions from device memory after each ATTEMPT (rollout +

@@ -7,7 +7,11 @@
 // rounding of the expanded form, within the 1e-12 the reference's fixture is held to.
 // cost_u_fwd_kernel / cost_u_bwd_kernel add control-effort and input-rate terms on the applied inputs (mcp_cost_inputs; no counterpart in the
 // reference) and the gradient in the inputs; the five kernels of the state costs are untouched by them.
+// cost_rows_kernel / cost_rows_sums_kernel / cost_*bwd_shaped_kernel evaluate the time-weighted, risk-sensitive objective (mcp_objective; no
+// counterpart in the reference either) on the costs and moments the forward kernels leave; every kernel above is untouched by them.
 #include "mcp_device.h"
+
+#include <cmath>
 
 using namespace mcp;
 
@@ -335,6 +339,197 @@ __global__ void cost_u_bwd_kernel(mcp_cost c, mcp_cost_inputs ci, int T, int M, 
   }
 }
 
+// ---- time-weighted, risk-sensitive objective (mcp_objective; the project's own extension, include/mcpilco_hip.h) -------------------------
+//   J = sum_t w_t (mu_t + kappa sigma_t),  S = sum_t w_t sigma_t,  dJ/dc_tm = w_t [1/n + kappa (c_tm - mu_t) / ((n - 1) sigma_t)]
+// over the pooled swarm of n particles.  The per-particle kernels above do not change: the two finalize kernels gain the rows
+// (mu_t, sigma_t) and the weights, the two gradient kernels a per-element upstream factor in place of their scalar.
+
+// cost_finalize_kernel, writing rows[t] = (pooled mean, unbiased std) and weighting the two sums: the same Chan pooling and the same
+// reduction tree, so that w == NULL, kappa == 0 gives cost_finalize_kernel's bits.
+__global__ __launch_bounds__(256) void cost_rows_kernel(int T, int R, const double* __restrict__ moments, RankCounts rc,
+                                                        const double* __restrict__ w, double kappa, double* __restrict__ rows,
+                                                        double* __restrict__ out) {
+  const int64_t* counts = rc.n;
+  __shared__ double red[2][4];
+  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+  double n_tot = 0.0;
+  for (int r = 0; r < R; ++r) n_tot += (double)counts[r];
+  double cs = 0.0, ss = 0.0;
+  for (int t = tid; t < T; t += 256) {
+    double mean = 0.0;
+    for (int r = 0; r < R; ++r) mean += (double)counts[r] * moments[((size_t)r * T + t) * 2];
+    mean /= n_tot;
+    double m2 = 0.0;
+    for (int r = 0; r < R; ++r) {
+      double d = moments[((size_t)r * T + t) * 2] - mean;
+      m2 += moments[((size_t)r * T + t) * 2 + 1] + (double)counts[r] * d * d;
+    }
+    const double sd = sqrt(m2 / (n_tot - 1.0));
+    rows[2 * t] = mean;
+    rows[2 * t + 1] = sd;
+    double j = mean, s = sd;
+    if (kappa != 0.0) j += kappa * sd;
+    if (w) {
+      j *= w[t];
+      s *= w[t];
+    }
+    cs += j;
+    ss += s;
+  }
+  cs = wave_sum(cs);
+  ss = wave_sum(ss);
+  if (lane == 0) {
+    red[0][wv] = cs;
+    red[1][wv] = ss;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    out[0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+    out[1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+  }
+}
+
+// cost_finalize_sums_kernel in the same way (the fmax(m2, 0) clamp and mean_out included)
+__global__ __launch_bounds__(256) void cost_rows_sums_kernel(int T, double n_tot, const double* __restrict__ sums,
+                                                             const double* __restrict__ shift, const double* __restrict__ w, double kappa,
+                                                             double* __restrict__ rows, double* __restrict__ out,
+                                                             double* __restrict__ mean_out) {
+  __shared__ double red[2][4];
+  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+  double cs = 0.0, ss = 0.0;
+  for (int t = tid; t < T; t += 256) {
+    const double a = sums[t], b = sums[T + t];
+    const double mean = (shift ? shift[t] : 0.0) + a / n_tot;
+    const double m2 = b - a * a / n_tot;
+    const double sd = sqrt(fmax(m2, 0.0) / (n_tot - 1.0));
+    rows[2 * t] = mean;
+    rows[2 * t + 1] = sd;
+    double j = mean, s = sd;
+    if (kappa != 0.0) j += kappa * sd;
+    if (w) {
+      j *= w[t];
+      s *= w[t];
+    }
+    cs += j;
+    ss += s;
+    if (mean_out) mean_out[t] = mean;
+  }
+  cs = wave_sum(cs);
+  ss = wave_sum(ss);
+  if (lane == 0) {
+    red[0][wv] = cs;
+    red[1][wv] = ss;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    out[0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+    out[1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+  }
+}
+
+// What a gradient kernel needs of the objective: w and kappa, the forward's costs [T][M], the pooled rows [T][2] and n - 1.
+struct ObjectiveArgs {
+  const double* w;
+  double kappa;
+  const double* costs;
+  const double* rows;
+  double n1;
+};
+
+// fac_tm = d J / d c_tm = w_t [1/n + kappa (c_tm - mu_t) / ((n - 1) sigma_t)] for element i = t M + m; gscale = 1/n.  A row of zero spread
+// (sigma_t == 0: every particle has the same cost) keeps w_t / n, where autograd through torch.std gives NaN.
+__device__ __forceinline__ double objective_factor(const ObjectiveArgs& o, double gscale, size_t i, int t) {
+  double fac = gscale;
+  if (o.kappa != 0.0) {
+    const double sd = o.rows[2 * t + 1];
+    if (sd > 0.0) fac += o.kappa * (o.costs[i] - o.rows[2 * t]) / (o.n1 * sd);
+  }
+  if (o.w) fac *= o.w[t];
+  return fac;
+}
+
+// the rows of g_states of one (t, m) with the factor e on d d_x / dx: cost_bwd_kernel's statements
+__device__ __forceinline__ void state_grad_rows(const mcp_cost& c, const double* x, int t, double e, double* g) {
+  for (int s = 0; s < c.S; ++s) g[s] = 0.0;
+  if (c.kind == MCP_COST_CARTPOLE) {
+    double th = x[c.angle_index];
+    double a = (fabs(th) - c.target_angle) / c.ls_angle;
+    double b = (x[c.pos_index] - c.target_pos) / c.ls_pos;
+    double sg = th > 0.0 ? 1.0 : (th < 0.0 ? -1.0 : 0.0);
+    g[c.angle_index] += e * 2.0 * a * sg / c.ls_angle;
+    g[c.pos_index] += e * 2.0 * b / c.ls_pos;
+  } else if (c.kind == MCP_COST_TRAJ) {
+    for (int k = 0; k < c.n_used; ++k) {
+      int s = c.used[k];
+      double r = (x[s] - c.target_traj[(size_t)t * c.S + s]) / c.lengthscales[k];
+      g[s] += e * 2.0 * r / c.lengthscales[k];
+    }
+  } else {
+    for (int k = 0; k < c.n_used; ++k) {
+      int s = c.used[k];
+      double r = (x[s] - c.target_traj[k]) / c.lengthscales[k];
+      g[s] += e * 2.0 * r / c.lengthscales[k];
+    }
+  }
+}
+
+// cost_bwd_kernel with the per-element factor: one thread per (t, m), its whole row
+__global__ void cost_bwd_shaped_kernel(mcp_cost c, ObjectiveArgs o, int T, int M, const double* __restrict__ states,
+                                       const double* __restrict__ g_cost, double gscale, double* __restrict__ g_states) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)T * M) return;
+  int t = (int)(i / M);
+  const double* x = states + i * c.S;
+  double dist;
+  cost_point(c, x, t, &dist);
+  double e = (g_cost ? *g_cost : 1.0) * objective_factor(o, gscale, i, t);
+  if (c.kind != MCP_COST_TARGET_QUAD) e *= exp(-dist);
+  state_grad_rows(c, x, t, e, g_states + i * c.S);
+}
+
+// cost_u_bwd_kernel with the per-element factor.  The rate term couples rows t and t + 1 of a particle, and the factor now differs between
+// them: a_{t+1} is built from G_{t+1,m} -- row t + 1 of costs, rows and w --, not from this element's G.
+__global__ void cost_u_bwd_shaped_kernel(mcp_cost c, mcp_cost_inputs ci, ObjectiveArgs o, int T, int M, const double* __restrict__ states,
+                                         const double* __restrict__ inputs, const double* __restrict__ g_cost, double gscale,
+                                         double* __restrict__ g_states, double* __restrict__ g_inputs) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)T * M) return;
+  int t = (int)(i / M);
+  const size_t row = (size_t)M * ci.U;
+  const double* x = states + i * c.S;
+  const double* u = inputs + i * ci.U;
+  const double* up = t > 0 ? u - row : nullptr;
+  const double g0 = g_cost ? *g_cost : 1.0;
+  const double G = g0 * objective_factor(o, gscale, i, t);
+  double e;
+  const double a = cost_u_factors(c, ci, x, u, up, t, G, &e);
+  state_grad_rows(c, x, t, e, g_states + i * c.S);
+  if (!g_inputs) return;
+  double* gu = g_inputs + i * ci.U;
+  for (int j = 0; j < ci.U; ++j) gu[j] = 0.0;
+  const bool next = ci.rate_scales && t + 1 < T;
+  double an = G;
+  if (next) {
+    an = g0 * objective_factor(o, gscale, i + M, t + 1);
+    if (ci.mode != MCP_COST_U_ADD) an = cost_u_factors(c, ci, x + (size_t)M * c.S, u + row, u, t + 1, an, nullptr);
+  }
+  for (int k = 0; k < ci.n_used; ++k) {
+    int j = ci.used[k];
+    if (ci.scales) {
+      double r = (u[j] - (ci.target ? ci.target[k] : 0.0)) / ci.scales[k];
+      gu[j] += a * 2.0 * r / ci.scales[k];
+    }
+    if (ci.rate_scales && up) {
+      double r = (u[j] - up[j]) / ci.rate_scales[k];
+      gu[j] += a * 2.0 * r / ci.rate_scales[k];
+    }
+    if (next) {
+      double r = (u[row + j] - u[j]) / ci.rate_scales[k];
+      gu[j] -= an * 2.0 * r / ci.rate_scales[k];
+    }
+  }
+}
+
 static bool cost_ok(const mcp_cost* c) {
   if (!c || c->S <= 0 || c->S > MCP_MAX_STATE) return false;
   if (c->kind == MCP_COST_CARTPOLE)
@@ -431,6 +626,63 @@ extern "C" int mcp_cost_u_bwd(const mcp_cost* cost, const mcp_cost_inputs* cin, 
   size_t n = (size_t)T * M;
   hipLaunchKernelGGL(cost_u_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *cost, *cin, T, M, states,
                      inputs, g_cost, gscale, g_states, g_inputs);
+  MCP_LAUNCH_CHECK();
+  return MCP_OK;
+}
+
+// the objective, when there is one: a finite kappa, and two particles or more where the std term is on
+static bool objective_ok(const mcp_objective* obj, int64_t n_total) {
+  if (!obj) return true;
+  if (!std::isfinite(obj->kappa)) return false;
+  return obj->kappa == 0.0 || n_total >= 2;
+}
+
+extern "C" int mcp_cost_rows(int T, int R, const double* moments, const int64_t* counts, const mcp_objective* obj, double* rows,
+                             double* out, void* stream) {
+  if (!moments || !counts || !rows || !out || T <= 0 || R <= 0) return MCP_ERR_ARG;
+  if (R > 64) return MCP_ERR_LIMIT;
+  RankCounts rc;
+  int64_t n_total = 0;
+  for (int r = 0; r < 64; ++r) {
+    rc.n[r] = r < R ? counts[r] : 0;
+    n_total += rc.n[r];
+  }
+  if (!objective_ok(obj, n_total)) return MCP_ERR_ARG;
+  hipLaunchKernelGGL(cost_rows_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, T, R, moments, rc, obj ? obj->w : nullptr,
+                     obj ? obj->kappa : 0.0, rows, out);
+  MCP_LAUNCH_CHECK();
+  return MCP_OK;
+}
+
+extern "C" int mcp_cost_rows_sums(int T, int64_t n_total, const double* sums, const double* shift, const mcp_objective* obj, double* rows,
+                                  double* out, double* mean_out, void* stream) {
+  if (!sums || !rows || !out || T <= 0 || n_total <= 0 || !objective_ok(obj, n_total)) return MCP_ERR_ARG;
+  hipLaunchKernelGGL(cost_rows_sums_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, T, (double)n_total, sums, shift,
+                     obj ? obj->w : nullptr, obj ? obj->kappa : 0.0, rows, out, mean_out);
+  MCP_LAUNCH_CHECK();
+  return MCP_OK;
+}
+
+extern "C" int mcp_cost_bwd_shaped(const mcp_cost* cost, const mcp_cost_inputs* cin, const mcp_objective* obj, int T, int M,
+                                   int64_t n_total, const double* states, const double* inputs, const double* costs, const double* rows,
+                                   const double* g_cost, double* g_states, double* g_inputs, void* stream) {
+  if (cin && cin->U > MCP_MAX_INPUT) return MCP_ERR_LIMIT;
+  if (!cost_ok(cost) || !cost_inputs_ok(cin)) return MCP_ERR_ARG;
+  if (!states || !costs || !rows || !g_states || T <= 0 || M <= 0 || n_total < M || !objective_ok(obj, n_total)) return MCP_ERR_ARG;
+  const ObjectiveArgs o = {obj ? obj->w : nullptr, obj ? obj->kappa : 0.0, costs, rows, (double)(n_total - 1)};
+  const double gscale = 1.0 / (double)n_total;
+  const size_t n = (size_t)T * M;
+  if (cost_inputs_none(cin)) {
+    if (g_inputs && !cin) return MCP_ERR_ARG;  // (no descriptor, no U: as mcp_cost_u_bwd)
+    if (g_inputs && hipMemsetAsync(g_inputs, 0, n * cin->U * sizeof(double), (hipStream_t)stream) != hipSuccess) return MCP_ERR_LAUNCH;
+    hipLaunchKernelGGL(cost_bwd_shaped_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *cost, o, T, M, states,
+                       g_cost, gscale, g_states);
+    MCP_LAUNCH_CHECK();
+    return MCP_OK;
+  }
+  if (!inputs) return MCP_ERR_ARG;
+  hipLaunchKernelGGL(cost_u_bwd_shaped_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *cost, *cin, o, T, M,
+                     states, inputs, g_cost, gscale, g_states, g_inputs);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
 }

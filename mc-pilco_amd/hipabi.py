@@ -105,6 +105,11 @@ class CostInputs(C.Structure):
                 ("scales", dptr), ("rate_scales", dptr)]
 
 
+class Objective(C.Structure):
+    """mcp_objective: the time weights (device [T]; NULL: ones) and the risk parameter kappa of J = sum_t w_t (mean_t + kappa std_t)."""
+    _fields_ = [("w", dptr), ("kappa", C.c_double)]
+
+
 class Dispatch(C.Structure):
     """include/mcpilco_hip_debug.h: struct mcp_dispatch -- the request a call carries (all zero = automatic) and what it reports back."""
     _fields_ = [("fwd_particles", C.c_int32), ("gp_sharding", C.c_int32), ("fwd_lean", C.c_int32), ("policy_split", C.c_int32), ("row_split", C.c_int32),
@@ -206,6 +211,10 @@ _SIGS = {
     "mcp_cost_u_bwd": (C.c_int, [C.POINTER(Cost), C.POINTER(CostInputs), C.c_int, C.c_int, dptr, dptr, dptr, C.c_double, dptr, dptr, dptr]),
     "mcp_cost_sums": (C.c_int, [C.c_int, C.c_int, dptr, dptr, dptr, dptr]),
     "mcp_cost_finalize_sums": (C.c_int, [C.c_int, C.c_int64, dptr, dptr, dptr, dptr, dptr]),
+    "mcp_cost_rows": (C.c_int, [C.c_int, C.c_int, dptr, C.POINTER(C.c_int64), C.POINTER(Objective), dptr, dptr, dptr]),
+    "mcp_cost_rows_sums": (C.c_int, [C.c_int, C.c_int64, dptr, dptr, C.POINTER(Objective), dptr, dptr, dptr, dptr]),
+    "mcp_cost_bwd_shaped": (C.c_int, [C.POINTER(Cost), C.POINTER(CostInputs), C.POINTER(Objective), C.c_int, C.c_int, C.c_int64, dptr, dptr,
+                                      dptr, dptr, dptr, dptr, dptr, dptr]),
     "mcp_adam_step_guarded": (C.c_int, [C.c_int, C.POINTER(dptr), C.POINTER(dptr), C.POINTER(dptr), C.POINTER(dptr), C.POINTER(C.c_int64), C.c_double,
                                         C.c_double, C.c_double, C.c_double, dptr, C.c_int64, C.c_int, dptr, dptr, dptr, dptr]),
     "mcp_nll_epoch_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

@@ -1148,6 +1148,69 @@ class PackedCostInputs:
         self.c, self.device, self.U, self.used, self.joint = c, dev, U, idx, bool(joint)
 
 
+class PackedObjective:
+    """mcp_objective: J = sum_t w_t (mean_t + kappa std_t) over the T steps of a rollout (include/mcpilco_hip.h).  ``time_weights`` (at least T
+    entries, the first T are used; None: ones), ``discount`` gamma in (0, 1] (w_t = gamma^t; None: 1), or the product of both; ``risk``
+    kappa, any finite real.  Everything is checked on the host values first: a bad objective raises ValueError before a device is touched.
+    The [T] device tensor of the weights is kept alive here (``w``; None when neither option is given: the kernels take NULL as ones)."""
+
+    def __init__(self, T, device, time_weights=None, discount=None, risk=0.0):
+        T = int(T)
+        if T < 1:
+            raise ValueError("objective: T must be at least 1 (%d given)" % T)
+        host = objective_weights(T, time_weights, discount)
+        kappa = float(risk)
+        if not np.isfinite(kappa):
+            raise ValueError("objective: risk must be finite (%r)" % (risk,))
+        dev = _dev(device)
+        c = abi.Objective()
+        c.kappa = kappa
+        self.w = None if host is None else _t(host, dev)
+        if self.w is not None:
+            c.w = self.w.data_ptr()
+        self.c, self.device, self.T, self.kappa = c, dev, T, kappa
+        self._mean = None
+
+    def mean_part(self):
+        """The same weights (the same device tensor) with kappa = 0: what a rank's share of a sharded step is formed with."""
+        if self.kappa == 0.0:
+            return self
+        if self._mean is None:
+            m = object.__new__(PackedObjective)
+            m.c = abi.Objective()
+            m.c.w, m.c.kappa = self.c.w, 0.0
+            m.w, m.device, m.T, m.kappa, m._mean = self.w, self.device, self.T, 0.0, None
+            self._mean = m
+        return self._mean
+
+    def check_particles(self, n_total):
+        if self.kappa != 0.0 and int(n_total) < 2:
+            raise ValueError("objective: the std term (risk = %g) needs at least two particles (%d given)" % (self.kappa, int(n_total)))
+
+
+def objective_weights(T, time_weights=None, discount=None):
+    """The host values w_t = time_weights[t] gamma^t, t < T, of an objective (None: neither option is given), checked: finite, >= 0, not all
+    zero, at least T entries, gamma in (0, 1]."""
+    if time_weights is None and discount is None:
+        return None
+    w = np.ones(T)
+    if time_weights is not None:
+        h = _host(time_weights).reshape(-1)
+        if h.size < T:
+            raise ValueError("objective: %d time weights for %d time steps" % (h.size, T))
+        w = h[:T].copy()
+        if not bool(np.all(np.isfinite(w) & (w >= 0))):
+            raise ValueError("objective: time weights must be finite and >= 0 (%s)" % (w.tolist(),))
+    if discount is not None:
+        g = float(discount)
+        if not (0.0 < g <= 1.0):  # (NaN fails both comparisons)
+            raise ValueError("objective: discount must lie in (0, 1] (%r)" % (discount,))
+        w = w * g ** np.arange(T)
+    if not bool(np.any(w > 0)):
+        raise ValueError("objective: at least one time weight must be > 0")
+    return w
+
+
 def _check_cost_inputs(states, inputs, cost_inputs):
     """The inputs [T,M,U] of a cost with input terms, detached and contiguous."""
     if inputs is None or cost_inputs is None:
@@ -1257,12 +1320,21 @@ class ExpectedCostFunction(torch.autograd.Function):
         return (g,) + (None,) * (len(ctx.needs_input_grad) - 1)
 
 
-def expected_cost_raw(cost: PackedCost, states, g_one, inputs=None, cost_inputs=None, want_g_inputs=False):
+def expected_cost_raw(cost: PackedCost, states, g_one, inputs=None, cost_inputs=None, want_g_inputs=False, objective=None):
     """(cost, std, dJ/dstates) of this process's particles without autograd: exactly the launches ExpectedCostFunction's forward and backward
     make (``g_one``: a device scalar 1.0, the upstream gradient ``cost.backward()`` starts from).  For callers that replay the step from a
     HIP graph (MC_PILCO.reinforce_policy): the autograd engine's own stream bookkeeping does not survive a stream capture.  With
     ``inputs`` / ``cost_inputs`` the cost carries the input terms; ``want_g_inputs``: dJ/dinputs is returned as a fourth value (None for a
-    cost without input terms: the adjoint sweeps take that as "no gradient")."""
+    cost without input terms: the adjoint sweeps take that as "no gradient").  With ``objective`` (a PackedObjective) the three launches are
+    mcp_cost_fwd / mcp_cost_rows / mcp_cost_bwd_shaped and (cost, std) are (J, S)."""
+    if objective is not None:
+        T, M, _ = states.shape
+        _check_objective(objective, T, M)
+        mom, costs, _ = cost_moments(cost, states, None, inputs, cost_inputs)
+        rows, out = cost_rows(mom.unsqueeze(0), [M], objective)
+        g, g_in = _cost_bwd_shaped(cost, cost_inputs, objective, states.detach().contiguous(), None if cost_inputs is None else inputs.detach().contiguous(),
+                                   costs, rows, g_one, M, want_g_inputs and cost_inputs is not None)
+        return (out[0], out[1], g, g_in) if want_g_inputs else (out[0], out[1], g)
     mom, _, _ = cost_moments(cost, states, None, inputs, cost_inputs)
     T, M, _ = states.shape
     out = cost_finalize(mom.unsqueeze(0), [M])
@@ -1275,7 +1347,9 @@ def expected_cost_raw(cost: PackedCost, states, g_one, inputs=None, cost_inputs=
     return (out[0], out[1], g, None) if want_g_inputs else (out[0], out[1], g)
 
 
-def expected_cost(cost: PackedCost, states, group=None, counts=None, inputs=None, cost_inputs=None):
+def expected_cost(cost: PackedCost, states, group=None, counts=None, inputs=None, cost_inputs=None, objective=None):
+    if objective is not None:
+        return ShapedCostFunction.apply(states, cost, group, counts, inputs, cost_inputs, objective)
     if inputs is None and cost_inputs is None:
         return ExpectedCostFunction.apply(states, cost, group, counts)
     return ExpectedCostFunction.apply(states, cost, group, counts, inputs, cost_inputs)
@@ -1323,19 +1397,152 @@ class LocalCostFunction(torch.autograd.Function):
         return (g,) + (None,) * (len(ctx.needs_input_grad) - 1)
 
 
-def local_cost(cost: PackedCost, states, m_total, shift=None, sums_out=None, inputs=None, cost_inputs=None):
+def local_cost(cost: PackedCost, states, m_total, shift=None, sums_out=None, inputs=None, cost_inputs=None, objective=None, reducer=None):
+    """``objective`` (a PackedObjective): the share is this rank's part of J.  With kappa != 0 the gradient needs the POOLED rows of this very
+    step, so ``reducer`` (sharding.StepReducer) is required: one additional small all-reduce of a copy of the 2T sums (ShapedLocalCostFunction)."""
+    if objective is not None:
+        return ShapedLocalCostFunction.apply(states, cost, int(m_total), shift, None if sums_out is None else (sums_out,), inputs, cost_inputs,
+                                             objective, reducer)
     if inputs is None and cost_inputs is None:
         return LocalCostFunction.apply(states, cost, int(m_total), shift, None if sums_out is None else (sums_out,))
     return LocalCostFunction.apply(states, cost, int(m_total), shift, None if sums_out is None else (sums_out,), inputs, cost_inputs)
 
 
-def cost_from_sums(sums, n_total, shift=None, mean_out=None):
-    """Pooled (sum_t mean_m c, sum_t unbiased std_m c) from the all-reduced sums of ``local_cost`` -> tensor [2]."""
+def cost_from_sums(sums, n_total, shift=None, mean_out=None, objective=None):
+    """Pooled (sum_t mean_m c, sum_t unbiased std_m c) from the all-reduced sums of ``local_cost`` -> tensor [2]; with ``objective`` the
+    pooled (J, S) (mcp_cost_rows_sums)."""
+    if objective is not None:
+        return cost_rows_sums(sums, n_total, shift, mean_out, objective)[1]
     T = sums.numel() // 2
     out = torch.empty(2, dtype=DT, device=sums.device)
     abi.check(abi.lib().mcp_cost_finalize_sums(T, int(n_total), abi.ptr(sums.contiguous()), abi.ptr(shift), abi.ptr(out), abi.ptr(mean_out),
                                                abi.stream()), "mcp_cost_finalize_sums")
     return out
+
+
+# ---- the time-weighted, risk-sensitive objective (PackedObjective; mcp_cost_rows / mcp_cost_rows_sums / mcp_cost_bwd_shaped) ------------------
+def _check_objective(objective, T, n_total):
+    if objective.T != int(T):
+        raise RuntimeError("the objective holds %d time weights but the rollout has %d steps" % (objective.T, int(T)))
+    objective.check_particles(n_total)
+
+
+def cost_rows(moments_all, counts, objective=None):
+    """moments_all [R,T,2] (all ranks), counts: R ints -> (rows [T,2] = pooled (mean_t, unbiased std_t), out [2] = (J, S)).  objective None:
+    out holds cost_finalize's bits."""
+    R, T = moments_all.shape[0], moments_all.shape[1]
+    rows = torch.empty(T, 2, dtype=DT, device=moments_all.device)
+    out = torch.empty(2, dtype=DT, device=moments_all.device)
+    cnt = (C.c_int64 * R)(*[int(c) for c in counts])
+    abi.check(abi.lib().mcp_cost_rows(T, R, abi.ptr(moments_all.contiguous()), cnt, None if objective is None else C.byref(objective.c), abi.ptr(rows),
+                                      abi.ptr(out), abi.stream()), "mcp_cost_rows")
+    return rows, out
+
+
+def cost_rows_sums(sums, n_total, shift=None, mean_out=None, objective=None):
+    """The all-reduced sums of ``local_cost`` -> (rows [T,2], out [2] = (J, S)) of the pooled swarm."""
+    T = sums.numel() // 2
+    rows = torch.empty(T, 2, dtype=DT, device=sums.device)
+    out = torch.empty(2, dtype=DT, device=sums.device)
+    abi.check(abi.lib().mcp_cost_rows_sums(T, int(n_total), abi.ptr(sums.contiguous()), abi.ptr(shift), None if objective is None else C.byref(objective.c),
+                                           abi.ptr(rows), abi.ptr(out), abi.ptr(mean_out), abi.stream()), "mcp_cost_rows_sums")
+    return rows, out
+
+
+def _cost_bwd_shaped(cost, cost_inputs, objective, states, inputs, costs, rows, g_cost, n_total, want_g_inputs=True):
+    """mcp_cost_bwd_shaped -> (g_states, g_inputs or None); states / inputs detached and contiguous."""
+    T, M, _ = states.shape
+    g = torch.empty_like(states)
+    g_in = torch.empty_like(inputs) if (want_g_inputs and cost_inputs is not None) else None
+    abi.check(abi.lib().mcp_cost_bwd_shaped(C.byref(cost.c), None if cost_inputs is None else C.byref(cost_inputs.c),
+                                            None if objective is None else C.byref(objective.c), T, M, int(n_total), abi.ptr(states), abi.ptr(inputs),
+                                            abi.ptr(costs), abi.ptr(rows), abi.ptr(g_cost), abi.ptr(g), abi.ptr(g_in), abi.stream()),
+              "mcp_cost_bwd_shaped")
+    return g, g_in
+
+
+class ShapedCostFunction(torch.autograd.Function):
+    """ExpectedCostFunction under a PackedObjective: states [T,M,S] (and inputs) -> (J, S) = (sum_t w_t (mean_t + kappa std_t), sum_t w_t std_t)
+    with the gradient of J (S carries none).  Three launches on one rank, as without an objective: forward, rows + objective, backward; with a
+    ``group`` the rows pool every rank's gathered moments and the backward takes n_total = sum(counts)."""
+
+    @staticmethod
+    def forward(ctx, states, cost, group, counts, inputs, cost_inputs, objective):
+        ctx.set_materialize_grads(False)
+        T, M, _ = states.shape
+        if group is not None:
+            from . import sharding
+
+            mom, costs, _ = cost_moments(cost, states, None, inputs, cost_inputs)
+            mom_all = sharding.gather_moments(mom, group)
+            counts = [M] * mom_all.shape[0] if counts is None else [int(c) for c in counts]
+            _check_objective(objective, T, sum(counts))
+        else:
+            counts = [M]
+            _check_objective(objective, T, M)
+            mom, costs, _ = cost_moments(cost, states, None, inputs, cost_inputs)
+            mom_all = mom.unsqueeze(0)
+        rows, out = cost_rows(mom_all, counts, objective)
+        ctx.cost, ctx.cost_inputs, ctx.objective, ctx.m_total = cost, cost_inputs, objective, sum(counts)
+        if cost_inputs is None:
+            ctx.save_for_backward(states.detach(), costs, rows)
+        else:
+            ctx.save_for_backward(states.detach(), costs, rows, inputs.detach().contiguous())
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_cost, _g_std):
+        states, costs, rows = ctx.saved_tensors[:3]
+        inputs = ctx.saved_tensors[3] if ctx.cost_inputs is not None else None
+        want_in = ctx.cost_inputs is not None and ctx.needs_input_grad[4]
+        if g_cost is None:  # (only S is used downstream: no gradient goes through it)
+            return torch.zeros_like(states), None, None, None, (torch.zeros_like(inputs) if want_in else None), None, None
+        gc = g_cost.detach().to(dtype=DT).reshape(1).contiguous()  # stays on the device: no host sync
+        g, g_in = _cost_bwd_shaped(ctx.cost, ctx.cost_inputs, ctx.objective, states.contiguous(), inputs, costs, rows, gc, ctx.m_total, want_in)
+        return g, None, None, None, g_in, None, None
+
+
+class ShapedLocalCostFunction(torch.autograd.Function):
+    """LocalCostFunction under a PackedObjective: (share, sums [2T]) of a particle-sharded step; the sums are those of the plain cost (the
+    pooled (J, S) are finalised from their all-reduced form with the weights: cost_from_sums(..., objective)).
+      kappa == 0: share = sum_t w_t sum_m c_tm / m_total; the gradient needs nothing from the other ranks, the step keeps its ONE all-reduce.
+      kappa != 0: the gradient factor holds the pooled (mean_t, std_t) of THIS step, so the forward all-reduces a copy of the 2T sums through
+                  ``reducer`` (one additional small collective) and forms the pooled rows (mcp_cost_rows_sums) before the sweep.  The share's
+                  value stays the mean part above (the value only feeds the NaN flag; the step's J comes from the reduced message).  A NaN on
+                  another rank makes these rows NaN and this rank's gradient NaN -- harmless: the pooled cost is then non-finite on every rank
+                  and the attempt is discarded, as without an objective."""
+
+    @staticmethod
+    def forward(ctx, states, cost, m_total, shift, sums_out, inputs, cost_inputs, objective, reducer):
+        T, M = states.shape[0], states.shape[1]
+        _check_objective(objective, T, m_total)
+        if objective.kappa != 0.0 and reducer is None:
+            raise ValueError("a sharded cost with risk != 0 needs the step's reducer for the pooled rows")
+        mom, costs, _ = cost_moments(cost, states, None, inputs, cost_inputs)
+        sums = sums_out[0] if sums_out is not None else torch.empty(2 * T, dtype=DT, device=states.device)
+        if sums.numel() != 2 * T or sums.dtype != DT or not sums.is_contiguous():
+            raise RuntimeError("sums_out must be a contiguous float64 tensor of 2 T entries")
+        abi.check(abi.lib().mcp_cost_sums(T, M, abi.ptr(mom), abi.ptr(shift), abi.ptr(sums), abi.stream()), "mcp_cost_sums")
+        rows, out = cost_rows(mom.unsqueeze(0), [M], objective.mean_part())
+        local = out[0] * (float(M) / float(m_total))
+        if objective.kappa != 0.0:
+            rows, _ = cost_rows_sums(reducer.allreduce_(sums.clone()), m_total, shift, None, objective)
+        ctx.cost, ctx.cost_inputs, ctx.objective, ctx.m_total = cost, cost_inputs, objective, int(m_total)
+        if cost_inputs is None:
+            ctx.save_for_backward(states.detach(), costs, rows)
+        else:
+            ctx.save_for_backward(states.detach(), costs, rows, inputs.detach().contiguous())
+        ctx.mark_non_differentiable(sums)
+        return local, sums
+
+    @staticmethod
+    def backward(ctx, g_local, _g_sums):
+        states, costs, rows = ctx.saved_tensors[:3]
+        inputs = ctx.saved_tensors[3] if ctx.cost_inputs is not None else None
+        gc = g_local.detach().to(dtype=DT).reshape(1).contiguous()
+        g, g_in = _cost_bwd_shaped(ctx.cost, ctx.cost_inputs, ctx.objective, states.contiguous(), inputs, costs, rows, gc, ctx.m_total,
+                                   ctx.cost_inputs is not None and ctx.needs_input_grad[5])
+        return g, None, None, None, None, g_in, None, None, None
 
 
 # --------------------------------------------------------------------------------------

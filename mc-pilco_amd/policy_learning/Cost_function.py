@@ -16,6 +16,8 @@ sums of a sharded step.  With several target rows, on CPU tensors or in another 
 The project's own extension (the reference's cost functions receive ``inputs_sequence`` and ignore it): ``Input_penalty`` adds a
 control-effort and an input-rate term on the applied inputs (``input_distance``) to one of the four kernel costs and runs in the HIP
 cost kernels too (mcp_cost_u_fwd / mcp_cost_u_bwd), which then return the gradient in the inputs the adjoint sweeps take.
+``Cost_shaping`` wraps one of these costs into the time-weighted, risk-sensitive objective J = sum_t w_t (mean_t + risk std_t) (a discount, explicit
+per-step weights, PILCO's ``cost.expl``), still three launches on the kernels (mcp_cost_rows / mcp_cost_bwd_shaped); the std term IS differentiated.
 """
 import numpy as np
 import torch
@@ -103,6 +105,10 @@ class _HipExpectedCost(Expected_cost):
 
     def inputs_packed_for(self, inputs):
         """The kernels' descriptor of the terms of this cost that read the inputs (ops.PackedCostInputs); None: it reads the states only."""
+        return None
+
+    def objective_for(self, states):
+        """The kernels' descriptor of what is made of the per-particle costs (ops.PackedObjective); None: sum_t mean_m c."""
         return None
 
     def forward(self, states_sequence, inputs_sequence=None, trial_index=None, group=None, counts=None):
@@ -361,3 +367,206 @@ class Input_penalty(_HipExpectedCost):
                               self.inputs_packed_for(inputs_sequence))
 
     from_sums = staticmethod(_TargetStateCost.from_sums)  # (the sums of either path have one meaning: pooled where local_moments left them)
+
+
+# ---- time weights and risk sensitivity (the project's own extension: the reference minimises sum_t mean_m c and prints sum_t std_m c) --------
+class Cost_shaping(_HipExpectedCost):
+    """One of this module's kernel costs (Cart_pole_cost, Expected_saturated_distance_from_trajectory, Expected_distance,
+    Expected_saturated_distance) or an Input_penalty, under a time-weighted, risk-sensitive objective.  With mu_t / sigma_t the mean / unbiased
+    std of its per-particle costs c_tm over the n pooled particles at step t:
+
+        J = sum_t w_t (mu_t + risk sigma_t)    first output: what is minimised (risk > 0 cautious, risk < 0 uncertainty-seeking)
+        S = sum_t w_t sigma_t                  second output: the monitor, no gradient
+        dJ/dc_tm = w_t [1/n + risk (c_tm - mu_t) / ((n - 1) sigma_t)]
+
+    ``time_weights`` (at least T entries, the first T are used; >= 0, finite, not all zero), ``discount`` gamma in (0, 1] (w_t = gamma^t), or
+    the product of both; ``risk`` any finite real (risk != 0 needs two particles or more: ValueError).  Unlike the reference's monitor the
+    sigma term IS differentiated.  A row whose particles all have the same cost (sigma_t = 0: t = 0 with a zero-variance x0) keeps the factor
+    w_t / n -- its sigma term is dropped from the gradient, where autograd through torch.std gives NaN: a stated departure.
+
+    Where the wrapped cost runs on the HIP cost kernels it stays there: three launches (forward, rows + objective, backward), recordable
+    attempts, the sharded step's sums.  CPU tensors, another dtype, a wrapped cost that keeps its torch path, a ``time_weights`` tensor that
+    requires grad: the same formula as torch ops on the wrapped cost's torch formula.  With no option set it is the wrapped cost, launch for
+    launch.  A sharded step with risk != 0 makes one additional small all-reduce (``local_moments(..., reducer=)``: the gradient needs the pooled
+    rows of the current step); with risk == 0 the step keeps its single one."""
+
+    def __init__(self, cost, time_weights=None, discount=None, risk=0.0):
+        super().__init__()
+        if not isinstance(cost, (Cart_pole_cost, Expected_saturated_distance_from_trajectory, _TargetStateCost, Input_penalty)):
+            raise TypeError("Cost_shaping: cost must be one of this module's kernel costs or an Input_penalty (got %s)" % type(cost).__name__)
+        self.cost, self.time_weights, self.discount, self.risk = cost, time_weights, discount, float(risk)
+        if not np.isfinite(self.risk):
+            raise ValueError("Cost_shaping: risk must be finite (%r)" % (risk,))
+        n_w = 1 if time_weights is None else ops._count(time_weights)
+        ops.objective_weights(n_w, time_weights, discount)  # (the values, checked once over every entry given; per T again when packed)
+        self._trainable = isinstance(time_weights, torch.Tensor) and time_weights.requires_grad
+        self._plain = time_weights is None and discount is None and self.risk == 0.0
+        self._objectives = {}  # the objective's descriptor, one per (T, device)
+        self.cost_function = self._torch_cost_of(cost)
+
+    needs_pooled_rows = property(lambda self: self.risk != 0.0)  # (a sharded step then hands local_moments its reducer)
+
+    @staticmethod
+    def _torch_cost_of(cost):
+        """The per-particle costs [T,M] of the wrapped cost as torch ops."""
+        if isinstance(cost, Cart_pole_cost):
+            return lambda x, u, k: cart_pole_cost(x, u, k, cost.target_state, cost.lengthscales, cost.angle_index, cost.pos_index)
+        if isinstance(cost, Expected_saturated_distance_from_trajectory):
+            return lambda x, u, k: saturated_distance_from_trajectory(x, u, k, cost.target_traj, cost.lengthscales, cost.flg_var_lengthscales,
+                                                                      cost.used_indeces)
+        return cost.cost_function
+
+    # -- the kernels ----------------------------------------------------------------------------------------------------------------------
+    def runs_on_kernels(self, states=None):
+        if self._trainable or not self.cost.runs_on_kernels(states):
+            return False
+        return states is None or (states.is_cuda and states.dtype == torch.float64 and states.dim() == 3)
+
+    def _on_kernels(self, states, inputs):
+        if not self.runs_on_kernels(states):
+            return False
+        return not isinstance(self.cost, Input_penalty) or self.cost._inputs_fit(states, inputs)
+
+    def packed_for(self, states, trial_index=None):
+        self._packed = self.cost.packed_for(states, trial_index)
+        return self._packed
+
+    def inputs_packed_for(self, inputs):
+        return self.cost.inputs_packed_for(inputs)
+
+    def objective_for(self, states):
+        return None if self._plain else self._objective(states.shape[0], states.device)
+
+    def _objective(self, T, device):
+        key = (int(T), device)
+        if key not in self._objectives:
+            self._objectives[key] = ops.PackedObjective(T, device, self.time_weights, self.discount, self.risk)
+        return self._objectives[key]
+
+    def _kernel_args(self, states, inputs, trial_index):
+        cin = self.inputs_packed_for(inputs) if isinstance(self.cost, Input_penalty) else None
+        return self.packed_for(states, trial_index), (None if cin is None else inputs), cin
+
+    def forward(self, states_sequence, inputs_sequence=None, trial_index=None, group=None, counts=None):
+        if self._plain:
+            return self.cost(states_sequence, inputs_sequence, trial_index, group, counts)
+        if not self._on_kernels(states_sequence, inputs_sequence):
+            return self._torch_forward(states_sequence, inputs_sequence, trial_index, group, counts)
+        pc, inp, cin = self._kernel_args(states_sequence, inputs_sequence, trial_index)
+        return ops.expected_cost(pc, states_sequence, group, counts, inp, cin, self.objective_for(states_sequence))
+
+    def local_moments(self, states_sequence, inputs_sequence, trial_index, m_total, shift=None, sums_out=None, reducer=None):
+        if self._plain:
+            return self.cost.local_moments(states_sequence, inputs_sequence, trial_index, m_total, shift, sums_out)
+        if not self._on_kernels(states_sequence, inputs_sequence):
+            return self._torch_local_moments(states_sequence, inputs_sequence, trial_index, m_total, shift, sums_out, reducer)
+        pc, inp, cin = self._kernel_args(states_sequence, inputs_sequence, trial_index)
+        return ops.local_cost(pc, states_sequence, m_total, shift, sums_out, inp, cin, self.objective_for(states_sequence), reducer)
+
+    def from_sums(self, sums, n_total, shift=None, mean_out=None):
+        """(J, S) of the pooled swarm from the all-reduced sums (an instance method: the weights are the object's)."""
+        if self._plain:
+            return self.cost.from_sums(sums, n_total, shift, mean_out)
+        T = sums.numel() // 2
+        if sums.is_cuda and sums.dtype == torch.float64 and not self._trainable:
+            objective = self._objective(T, sums.device)
+            objective.check_particles(n_total)
+            out = ops.cost_from_sums(sums, n_total, shift, mean_out, objective)
+            return out[0], out[1]
+        a, b = sums[:T], sums[T:]
+        mean = a / n_total + (0.0 if shift is None else shift)
+        if mean_out is not None:
+            mean_out.copy_(mean)
+        self._check_particles(n_total)
+        sd = torch.sqrt(torch.clamp(b - a * a / n_total, min=0.0) / (n_total - 1))
+        w = self._weights(T, sums)
+        j = mean + self.risk * sd if self.risk != 0.0 else mean
+        return (torch.sum(j), torch.sum(sd)) if w is None else (torch.sum(w * j), torch.sum(w.detach() * sd))
+
+    # -- the torch path -------------------------------------------------------------------------------------------------------------------
+    def _check_particles(self, n):
+        if self.risk != 0.0 and n < 2:
+            raise ValueError("Cost_shaping: the std term (risk = %g) needs at least two particles (%d given)" % (self.risk, n))
+
+    def _weights(self, T, like):
+        """w [T] on the device and in the dtype of ``like`` (None: ones); a trainable ``time_weights`` stays in the graph."""
+        if self.time_weights is None and self.discount is None:
+            return None
+        host = ops.objective_weights(T, self.time_weights, self.discount)  # (the checks)
+        if not self._trainable:
+            return torch.as_tensor(host, dtype=like.dtype, device=like.device)
+        w = self.time_weights.reshape(-1)[:T].to(dtype=like.dtype, device=like.device)
+        if self.discount is not None:
+            w = w * torch.as_tensor(float(self.discount) ** np.arange(T), dtype=like.dtype, device=like.device)
+        return w
+
+    def _shaped(self, costs, mean, m2, n):
+        """(J, S) from the per-particle costs and the (detached) pooled mean and centred sum of squares per step: the value is
+        sum_t w_t (mean_t + risk sd_t), the gradient that of sum_tm fac_tm c_tm with fac the hand form of the class docstring (rows of zero spread
+        without their sigma term).  What a rank of several holds is its part of the gradient; the value is the pooled one."""
+        T = costs.shape[0]
+        w = self._weights(T, costs)
+        sd = torch.sqrt(m2 / (n - 1)) if n > 1 else torch.full_like(m2, float("nan"))
+        fac = torch.full_like(costs.detach(), 1.0 / n)
+        j = mean
+        if self.risk != 0.0:
+            spread = sd > 0
+            safe = torch.where(spread, sd, torch.ones_like(sd))
+            fac = fac + torch.where(spread, self.risk / ((n - 1) * safe), torch.zeros_like(sd))[:, None] * (costs.detach() - mean[:, None])
+            j = mean + self.risk * sd
+        if w is not None:
+            fac, j, s = fac * w[:, None], w * j, w.detach() * sd
+        else:
+            s = sd
+        part = (fac * costs).sum()
+        return part, part + (torch.sum(j) - part).detach(), torch.sum(s)
+
+    def _torch_forward(self, states, inputs, trial_index, group, counts):
+        costs = self.cost_function(states, inputs, trial_index)
+        cd = costs.detach()
+        if group is None:
+            n = costs.shape[1]
+            self._check_particles(n)
+            mean = cd.mean(1)
+            m2 = ((cd - mean[:, None]) ** 2).sum(1)
+            m2 = torch.where(cd.amax(1) > cd.amin(1), m2, torch.zeros_like(m2))  # (identical costs: exactly 0, whatever the mean rounded to)
+        else:
+            import torch.distributed as dist
+
+            if counts is None:
+                nt = torch.tensor([float(costs.shape[1])], dtype=costs.dtype, device=costs.device)
+                dist.all_reduce(nt, group=group)
+                n = int(nt.item())
+            else:
+                n = sum(int(c) for c in counts)
+            self._check_particles(n)
+            s1 = cd.sum(1)
+            dist.all_reduce(s1, group=group)
+            mean = s1 / n
+            m2 = ((cd - mean[:, None]) ** 2).sum(1)
+            dist.all_reduce(m2, group=group)
+        _, J, S = self._shaped(costs, mean, m2, n)
+        return J, S
+
+    def _torch_local_moments(self, states, inputs, trial_index, m_total, shift, sums_out, reducer):
+        costs = self.cost_function(states, inputs, trial_index)
+        T, n = costs.shape[0], int(m_total)
+        self._check_particles(n)
+        d = costs.detach() - (0.0 if shift is None else shift.reshape(-1, 1))
+        sums = torch.cat([d.sum(1), (d * d).sum(1)])
+        if sums_out is not None:
+            sums_out.copy_(sums)
+            sums = sums_out
+        if self.risk == 0.0:  # (the factor w_t / n needs nothing from the other ranks)
+            mean, m2 = torch.zeros(T, dtype=costs.dtype, device=costs.device), torch.ones(T, dtype=costs.dtype, device=costs.device)
+        else:
+            if reducer is None:
+                raise ValueError("Cost_shaping: a sharded cost with risk != 0 needs the step's reducer for the pooled rows")
+            # one additional small all-reduce: the pooled rows of THIS step.  A NaN on another rank makes them, and this rank's gradient, NaN:
+            # harmless -- the pooled cost is then non-finite on every rank and the attempt is discarded, as without the std term
+            pooled = reducer.allreduce_(sums.detach().clone())
+            a, b = pooled[:T], pooled[T:]
+            mean = a / n + (0.0 if shift is None else shift)
+            m2 = torch.clamp(b - a * a / n, min=0.0)
+        share, _, _ = self._shaped(costs, mean, m2, n)
+        return share, sums

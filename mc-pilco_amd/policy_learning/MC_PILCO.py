@@ -308,7 +308,12 @@ class MC_PILCO(torch.nn.Module):
         if msg is None or not msg.fits(n_grad, T, 3, states.device):
             msg = self._step_msgs[bool(backward)] = sharding.StepMessage(n_grad, T, 3, states.device, self.dtype)
         packed = self.control_policy.packed() if (backward and isinstance(self.control_policy, _Policy.Sum_of_gaussians)) else None
-        share, sums = cf.local_moments(states, inputs, trial_index, self._m_total, self._cost_shift, sums_out=msg.sums)
+        if getattr(cf, "needs_pooled_rows", False):
+            # (Cost_shaping with risk != 0: the gradient factor holds the pooled mean / std of THIS step, so the cost makes one additional small
+            #  all-reduce of a copy of the 2T sums through the step's reducer before the sweep; the step's message below is unchanged)
+            share, sums = cf.local_moments(states, inputs, trial_index, self._m_total, self._cost_shift, sums_out=msg.sums, reducer=self._reducer)
+        else:
+            share, sums = cf.local_moments(states, inputs, trial_index, self._m_total, self._cost_shift, sums_out=msg.sums)
         if backward:
             if packed is not None and packed.grad_numel() == n_grad:
                 packed.grad_flat = msg.grad  # (mcp_rollout_bwd leaves log_ls | centers | weight | bias there: the order of `params`)
@@ -503,7 +508,7 @@ class MC_PILCO(torch.nn.Module):
 
     def _attempt_raw(self, lp, rec_row):
         """The same attempt as the operators underneath make it, without the autograd engine (whose stream bookkeeping does not survive a
-        stream capture): x0 -> mcp_rollout_fwd -> mcp_cost_fwd / _finalize / _bwd -> mcp_rollout_bwd -> guarded Adam -> commit.  Identical
+        stream capture): x0 -> mcp_rollout_fwd -> mcp_cost_fwd / _finalize / _bwd (under a Cost_shaping: / _rows / _bwd_shaped) -> mcp_rollout_bwd -> guarded Adam -> commit.  Identical
         launches with identical arguments, hence identical bits; this is the form that is recorded and replayed."""
         pol = self.control_policy
         self._call_dev.add_(1)
@@ -515,7 +520,8 @@ class MC_PILCO(torch.nn.Module):
         cf = self.cost_function
         cin = cf.inputs_packed_for(inputs)  # (None: the cost reads the states only -- no inputs gradient, the sweep takes NULL as before)
         cost, std, g_states, g_inputs = ops.expected_cost_raw(cf.packed_for(states, lp.trial_index), states, lp.graphs.one,
-                                                              None if cin is None else inputs, cin, want_g_inputs=True)
+                                                              None if cin is None else inputs, cin, want_g_inputs=True,
+                                                              objective=cf.objective_for(states))
         g_ls, g_c, g_w, _, g_b = ops.rollout_backward_raw(model, pk, noise, states, inputs, jac, g_states, g_inputs, p)
         by_param = {id(pol.log_lengthscales): g_ls, id(pol.centers): g_c, id(pol.f_linear.weight): g_w}
         if pol.f_linear.bias is not None:
