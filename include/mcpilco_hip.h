@@ -224,6 +224,23 @@ typedef struct mcp_mlp_track {
   const double* target;         /* DEVICE [rows][S]                              */
 } mcp_mlp_track;
 
+/* PD term of the RESIDUAL policy -- mcp_pd_policy's law added to the network's output ahead of the ONE squashing, so that a stabilising
+ * PD controller (the UR5 launch script's) is kept and the network learns a correction on top of it:
+ *   a[k] = (W[2] h + b[2])[k] + sqrt_kp[k]^2 (target[t][pos[k]] - x[pos[k]]) + sqrt_kd[k]^2 (target[t][vel[k]] - x[vel[k]])
+ *   u[k] = u_max[k] tanh(a[k] / u_max[k]) (squash) or a[k]                 in every policy evaluation t = 0 .. T - 1, row T - 1 included
+ * The gains are squared once per launch; the errors are plain differences, not wrapped; dropout never touches the term; in the measured
+ * form x is the simulated measurement y_t here as everywhere else (as mcp_rollout_pd_meas has it).  The target is a constant of the
+ * launch (no gradient) and may be the track's tensor or another. */
+typedef struct mcp_mlp_pd {
+  int32_t on;                   /* 0: no PD term                                                 */
+  int32_t pos[MCP_MAX_INPUT];   /* distinct state components                                     */
+  int32_t vel[MCP_MAX_INPUT];   /* distinct state components                                     */
+  const double* sqrt_kp;        /* DEVICE [U]: an optimizer updates it in place                  */
+  const double* sqrt_kd;        /* DEVICE [U]                                                    */
+  const double* target;         /* DEVICE [rows][S]; may be the track's tensor or another        */
+  int32_t rows;                 /* >= T                                                          */
+} mcp_mlp_pd;
+
 /* ---- library ------------------------------------------------------------------------ */
 int mcp_abi_version(void);
 const char* mcp_build_info(void);
@@ -525,6 +542,34 @@ int mcp_rollout_mlp_track_bwd(const mcp_model* model, const mcp_mlp_policy* mlp,
                               const mcp_noise* noise /* NULL ok iff p_drop == 0 */, double p_drop, int M, int T, const double* states,
                               const double* inputs, const double* jac, const double* g_states, const double* g_inputs /* may be NULL */,
                               double* g_params, double* g_x0, void* stream);
+/* mcp_rollout_mlp_track with the PD TERM of mcp_mlp_pd added to the network's output ahead of the squashing (the residual policy
+ * u = squash(PD(x, t) + net(x, t))): the RES forms of the tracking kernels -- the output threads read the two components of the row the
+ * feature threads read (the state; measured form: the measurement y_t) and the two entries of res->target[t]; no barrier is added.  The
+ * track (dropout, error features, measured form), the noise addressing, the status flags (a NaN gain or a NaN row of res->target reaches
+ * the inputs: MCP_STATUS_NAN), T == 1, the tile ladder and the bit identities (mcp_rollout_open on the launch's own inputs; plain against
+ * recording launch) are mcp_rollout_mlp_track's; track NULL or track->n == 0 is legal with the term (the network then sees no errors).
+ * res NULL or res->on == 0: mcp_rollout_mlp_track itself on the same arguments (same kernels, same bits).  Checks in the order of
+ * mcp_rollout_mlp_track up to and including the track's; then the residual's -- a pos / vel entry out of range, an entry repeated within
+ * pos or within vel, sqrt_kp, sqrt_kd or target NULL, rows < T -- each MCP_ERR_ARG (more than MCP_MAX_INPUT inputs is already a limit of
+ * the model); then the measurement's.  Replaces the loop of MC_PILCO.apply_policy (policy_learning/MC_PILCO.py:615-674; measured:
+ * :808-906) with the sum of PD_controller.forward (policy_learning/Policy.py:406-449) and Policy.MLP_policy under one squashing. */
+int mcp_rollout_mlp_res(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_mlp_track* track /* NULL or n == 0: no errors */,
+                        const mcp_mlp_pd* res /* NULL or on == 0: no PD term */, const mcp_meas* meas /* NULL or n == 0: the true state */,
+                        const mcp_noise* noise, double p_drop, int M, int T, int particle_pred, const double* x0, double* states,
+                        double* inputs, double* mu, double* var, double* jac /* NULL: no record */, uint32_t* status, void* stream);
+/* Reverse-time sweep of mcp_rollout_mlp_res: mcp_rollout_mlp_track_bwd with the PD term's pull on the state,
+ *   lambda[pos[k]] -= sqrt_kp[k]^2 abar_k;   lambda[vel[k]] -= sqrt_kd[k]^2 abar_k      (measured form: the same pull on the measurement,
+ *                                                                                         which reaches the state through the filter's adjoint)
+ * and the gain gradients g_sqrt_kp[k] += 2 sqrt_kp[k] e[pos[k]] abar_k, g_sqrt_kd[k] += 2 sqrt_kd[k] e[vel[k]] abar_k, e = target[r] - x_r
+ * (measured: y_r), abar the adjoint of the output layer's pre-activation; the network's deltas are unchanged.  With the term g_params is
+ * [ceil(M / 16)][n_param + 2 U]: g_sqrt_kp [U] | g_sqrt_kd [U] behind bout in every slab, summed like the other entries (no atomics, a
+ * fixed order, a slab from its own 16 trajectories alone, in parts where the layout asks for them).  The tail is written whenever g_params
+ * is given (the descriptor has no switch for fixed gains: a caller with fixed gains ignores it); g_params NULL: nothing of it is computed.
+ * res NULL or res->on == 0: mcp_rollout_mlp_track_bwd itself (slabs of n_param).  The argument checks of the forward entry. */
+int mcp_rollout_mlp_res_bwd(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_mlp_track* track, const mcp_mlp_pd* res,
+                            const mcp_meas* meas, const mcp_noise* noise /* NULL ok iff p_drop == 0 */, double p_drop, int M, int T,
+                            const double* states, const double* inputs, const double* jac, const double* g_states,
+                            const double* g_inputs /* may be NULL */, double* g_params, double* g_x0, void* stream);
 /* Reverse-time adjoint of the rollout: given dJ/dstates, dJ/dinputs (either may be NULL) returns
  * dJ/d{log_lengthscales [P], centers [B][P], f_linear.weight [U][B]} (overwritten, this rank's
  * particles only; with policy->bias also dJ/dbias into policy->g_bias) and optionally dJ/dx0 [M][S].  Replaces autograd's backward through

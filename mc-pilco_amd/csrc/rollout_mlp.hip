@@ -9,6 +9,8 @@
 //                        launch's mcp_noise: a buffer, or Philox on the RBF masks' stream); p_drop == 0: the kernels without DROP
 //   mcp_rollout_mlp_track, mcp_rollout_mlp_track_bwd   the dropout pair with target-trajectory features behind the network's own (template TRK:
 //                        the errors target[t][idx[i]] - x[idx[i]], the map of policy_learning/Policy.py:389-403); no track: the dropout pair
+//   mcp_rollout_mlp_res, mcp_rollout_mlp_res_bwd   the tracking pair with a PD term added to the network's output ahead of the squashing (template
+//                        RES: PD_controller's law, policy_learning/Policy.py:406-449, and the network as its correction); no term: the tracking pair
 // The forward kernel is the step loop of rollout_open.hip's feedback form with the PD law exchanged for the network: phases S, K, V, J, J', F
 // and the noise addressing are the same functions (rollout_open_phases.h) and the same statements on the same operands, and the library is
 // built without floating-point contraction, so the states carry the bits of mcp_rollout_open fed with the launch's own inputs.  Per step
@@ -162,17 +164,38 @@ template <bool PMS>
 struct OpenArgsMlpTrack : OpenArgsMlpDrop<PMS> {
   MlpTrackArgs trk;
 };
-template <bool PMS, bool DROP, bool TRK = false>
+// RESIDUAL form (template RES, mcp_rollout_mlp_res): the PD law's term joins the network's output ahead of the one squashing,
+//   av = a_mlp + (kp2 * ep + kd2 * ev),   kp2 = sqrt_kp[k]^2, kd2 = sqrt_kd[k]^2 (squared once per launch, as rollout_open.hip's PD kernel),
+//   ep = target[t][pos[k]] - x[pos[k]],  ev = target[t][vel[k]] - x[vel[k]]
+// in the output thread of (trajectory, k): x is the row the feature threads read (xs; measured form: the measurement row), still standing
+// behind the layers' barriers, and the two entries of target[t] are asked for at the top of the step, beside tgv: no barrier is added.
+// Dropout never touches the term.  The residual forms are built on the tracking forms' arguments and statements (trk.n == 0 and p_drop == 0
+// are legal there); the forms without RES take no part in any of it.
+struct MlpResArgs {
+  int pos[MCP_MAX_INPUT], vel[MCP_MAX_INPUT];
+  const double* sqrt_kp;
+  const double* sqrt_kd;
+  const double* target;  // [rows >= T][S]
+};
+template <bool PMS>
+struct OpenArgsMlpRes : OpenArgsMlpTrack<PMS> {
+  MlpResArgs res;
+};
+template <bool PMS, bool DROP, bool TRK = false, bool RES = false>
 struct MlpKernelArgs {
   typedef typename MlpArgsOf<PMS>::type type;
 };
 template <bool PMS>
-struct MlpKernelArgs<PMS, true, false> {
+struct MlpKernelArgs<PMS, true, false, false> {
   typedef OpenArgsMlpDrop<PMS> type;
 };
 template <bool PMS>
-struct MlpKernelArgs<PMS, true, true> {
+struct MlpKernelArgs<PMS, true, true, false> {
   typedef OpenArgsMlpTrack<PMS> type;
+};
+template <bool PMS>
+struct MlpKernelArgs<PMS, true, true, true> {
+  typedef OpenArgsMlpRes<PMS> type;
 };
 // whether unit `unit` of trajectory m (of this launch's M; the descriptor adds particle_offset) is kept in row t
 __device__ __forceinline__ bool mlp_keep(const mcp_noise& nzl, uint32_t thr, int H, int M, int m, int t, int unit) {
@@ -190,9 +213,10 @@ __device__ __forceinline__ void mlp_layer_fwd_drop(const double* W, const double
   }
 }
 
-template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool WLDS, bool PMS = false, bool DROP = false, bool TRK = false>
-__global__ __launch_bounds__(RF_NT) void rollout_mlp_kernel(typename MlpKernelArgs<PMS, DROP, TRK>::type a) {
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool WLDS, bool PMS = false, bool DROP = false, bool TRK = false, bool RES = false>
+__global__ __launch_bounds__(RF_NT) void rollout_mlp_kernel(typename MlpKernelArgs<PMS, DROP, TRK, RES>::type a) {
   static_assert(DROP || !TRK, "the tracking forms are built on the dropout forms");
+  static_assert(TRK || !RES, "the residual forms are built on the tracking forms");
   extern __shared__ double smem[];
   const mcp_model& md = a.model;
   const mcp_mlp_policy& pl = a.mlp;
@@ -277,6 +301,19 @@ __global__ __launch_bounds__(RF_NT) void rollout_mlp_kernel(typename MlpKernelAr
     if (iserr) fsrc = a.trk.idx[fi - nnp - nap];
   }
   const double umax = isu ? pl.u_max[uk] : 1.0;
+  // (residual form) the output thread's PD term: its two components, its gains squared, its two entries of the PD target's row t (declared
+  // here, outside the loop: a declaration inside it, dead as it is without RES, moved the spilled scalars of a tracking form)
+  int rpos = 0, rvel = 0;
+  double kp2 = 0.0, kd2 = 0.0, tgp = 0.0, tgq = 0.0;
+  if constexpr (RES) {
+    if (isu) {
+      const double kp = a.res.sqrt_kp[uk], kd = a.res.sqrt_kd[uk];
+      rpos = a.res.pos[uk], rvel = a.res.vel[uk];
+      kp2 = kp * kp;
+      kd2 = kd * kd;
+    }
+  }
+  (void)rpos, (void)rvel, (void)kp2, (void)kd2, (void)tgp, (void)tgq;
   const int nh = pl.n_hidden, H0 = pl.h[0], H1 = nh > 1 ? pl.h[1] : 0;
   const int HL = nh > 1 ? H1 : H0;                // the last hidden layer: its width, row pitch and rows
   const int hpL = nh > 1 ? A.hp[1] : A.hp[0];
@@ -305,6 +342,9 @@ __global__ __launch_bounds__(RF_NT) void rollout_mlp_kernel(typename MlpKernelAr
     double tgv = 0.0;  // (tracking form) this error source's component of target[t]: asked for here, needed behind the barrier
     if constexpr (TRK) {
       if (iserr) tgv = a.trk.target[(size_t)t * S + fsrc];
+    }
+    if constexpr (RES) {  // the output thread's two entries of the PD target's row t: asked for here as well
+      if (isu) tgp = a.res.target[(size_t)t * S + rpos], tgq = a.res.target[(size_t)t * S + rvel];
     }
     // ---- phase S: publish x_t ----------------------------------------------------------------------------------------
     if (own) {
@@ -383,8 +423,13 @@ __global__ __launch_bounds__(RF_NT) void rollout_mlp_kernel(typename MlpKernelAr
     double ufb = 0.0;
     if (isu) {
       const double* hr = hlL + up * hpL;
-      const double av = WLDS ? mlp_unit(wlc + wlo + uk * pto, wlc[blo + uk], hr, HL)
-                               : mlp_unit(wtab[2] + uk * HL, wtab[5][uk], hr, HL);
+      double av = WLDS ? mlp_unit(wlc + wlo + uk * pto, wlc[blo + uk], hr, HL)
+                         : mlp_unit(wtab[2] + uk * HL, wtab[5][uk], hr, HL);
+      if constexpr (RES) {  // the row the feature threads read: its next writer is behind the barriers below
+        const double* xr = PMS ? smem + L.ym + up * S : xs + cur * PT * S + up * S;
+        const double ep = tgp - xr[rpos], ev = tgq - xr[rvel];
+        av = av + (kp2 * ep + kd2 * ev);
+      }
       ufb = pl.squash ? umax * fast_tanh(av / umax) : av;
       if (ovalid) {
         a.inputs[((size_t)t * M + m0 + up) * U + uk] = ufb;
@@ -540,6 +585,40 @@ static MlpTrackArgs mlp_track_args(const mcp_mlp_track* tr, double p_drop) {
   for (int i = 0; i < tr->n; ++i) t.idx[i] = tr->idx[i];
   return t;
 }
+// The PD term of the residual entries (res NULL or on == 0: none), behind the descriptor's and the track's checks: T the rows the launch
+// reads of its target.  (More than MCP_MAX_INPUT inputs is a limit of the model, refused before.)
+static inline bool res_active(const mcp_mlp_pd* res) { return res && res->on != 0; }
+static int mlp_res_check(const mcp_mlp_policy* p, const mcp_mlp_pd* res, int T) {
+  if (!res_active(res)) return MCP_OK;
+  unsigned seenp = 0, seenv = 0;
+  for (int k = 0; k < p->U; ++k) {
+    const int sp = res->pos[k], sv = res->vel[k];
+    if (sp < 0 || sp >= p->S || sv < 0 || sv >= p->S) return MCP_ERR_ARG;
+  }
+  for (int k = 0; k < p->U; ++k) {
+    const int sp = res->pos[k], sv = res->vel[k];
+    if ((seenp >> sp & 1u) || (seenv >> sv & 1u)) return MCP_ERR_ARG;
+    seenp |= 1u << sp, seenv |= 1u << sv;
+  }
+  if (!res->sqrt_kp || !res->sqrt_kd || !res->target) return MCP_ERR_ARG;
+  if (res->rows < T) return MCP_ERR_ARG;
+  return MCP_OK;
+}
+static MlpResArgs mlp_res_args(const mcp_mlp_pd* res) {
+  MlpResArgs r;
+  memset(&r, 0, sizeof(r));
+  for (int k = 0; k < MCP_MAX_INPUT; ++k) r.pos[k] = res->pos[k], r.vel[k] = res->vel[k];
+  r.sqrt_kp = res->sqrt_kp, r.sqrt_kd = res->sqrt_kd, r.target = res->target;
+  return r;
+}
+// the track a residual form runs on: the caller's, or one without errors
+static MlpTrackArgs mlp_track_args_or_none(const mcp_mlp_track* tr, double p_drop) {
+  if (tr && tr->n > 0) return mlp_track_args(tr, p_drop);
+  MlpTrackArgs t;
+  memset(&t, 0, sizeof(t));
+  t.nodrop = p_drop > 0.0 ? 0 : 1;
+  return t;
+}
 // the descriptor the kernels see: without lists the features are the state
 static mcp_mlp_policy mlp_normalised(const mcp_mlp_policy* p) {
   mcp_mlp_policy q = *p;
@@ -553,8 +632,8 @@ static mcp_mlp_policy mlp_normalised(const mcp_mlp_policy* p) {
 
 // ---- host path of the forward entry: checks -> fill -> ladder -----------------------------------------------------------------------------
 // one rung: the weights in LDS where the layout then fits, else in global memory; MCP_ERR_LIMIT where the rung does not fit at all
-template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool WLDS, bool PMS, bool DROP, bool TRK = false>
-static int launch_mlp_w(const typename MlpKernelArgs<PMS, DROP, TRK>::type& a, hipStream_t st) {
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool WLDS, bool PMS, bool DROP, bool TRK = false, bool RES = false>
+static int launch_mlp_w(const typename MlpKernelArgs<PMS, DROP, TRK, RES>::type& a, hipStream_t st) {
   const MlpActs A = mlp_acts(PT, a.mlp, mlp_geom(a.mlp), WLDS);
   const OpenLayout L = open_layout(PT, NEEDVAR, a.model.S, a.model.D, a.model.G, a.NpadMax, NEEDJAC, a.na, PMS, A.total);
   const size_t lds = (size_t)L.total * sizeof(double);
@@ -562,19 +641,19 @@ static int launch_mlp_w(const typename MlpKernelArgs<PMS, DROP, TRK>::type& a, h
   if constexpr (TRK) {  // a thread per feature source (not reached within the compiled limits: the lists are disjoint, n <= MCP_MAX_STATE)
     if (PT * (a.mlp.n_non_angle + a.mlp.n_angle + a.trk.n) > RF_NT) return MCP_ERR_LIMIT;
   }
-  MCP_ENSURE_MAX_LDS((rollout_mlp_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, WLDS, PMS, DROP, TRK>));
-  hipLaunchKernelGGL((rollout_mlp_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, WLDS, PMS, DROP, TRK>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
+  MCP_ENSURE_MAX_LDS((rollout_mlp_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, WLDS, PMS, DROP, TRK, RES>));
+  hipLaunchKernelGGL((rollout_mlp_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, WLDS, PMS, DROP, TRK, RES>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
 }
-template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool PMS, bool DROP, bool TRK = false>
-static int launch_mlp(const typename MlpKernelArgs<PMS, DROP, TRK>::type& a, hipStream_t st) {
-  const int rc = launch_mlp_w<PT, MAXDEG, NEEDVAR, NEEDJAC, true, PMS, DROP, TRK>(a, st);
-  return rc == MCP_ERR_LIMIT ? launch_mlp_w<PT, MAXDEG, NEEDVAR, NEEDJAC, false, PMS, DROP, TRK>(a, st) : rc;
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool PMS, bool DROP, bool TRK = false, bool RES = false>
+static int launch_mlp(const typename MlpKernelArgs<PMS, DROP, TRK, RES>::type& a, hipStream_t st) {
+  const int rc = launch_mlp_w<PT, MAXDEG, NEEDVAR, NEEDJAC, true, PMS, DROP, TRK, RES>(a, st);
+  return rc == MCP_ERR_LIMIT ? launch_mlp_w<PT, MAXDEG, NEEDVAR, NEEDJAC, false, PMS, DROP, TRK, RES>(a, st) : rc;
 }
-template <int PT, bool NEEDVAR, bool NEEDJAC, bool PMS, bool DROP, bool TRK = false>
-static int launch_mlp_deg(const typename MlpKernelArgs<PMS, DROP, TRK>::type& a, int maxdeg, hipStream_t st) {
-  return maxdeg == 0 ? launch_mlp<PT, 0, NEEDVAR, NEEDJAC, PMS, DROP, TRK>(a, st) : launch_mlp<PT, 2, NEEDVAR, NEEDJAC, PMS, DROP, TRK>(a, st);
+template <int PT, bool NEEDVAR, bool NEEDJAC, bool PMS, bool DROP, bool TRK = false, bool RES = false>
+static int launch_mlp_deg(const typename MlpKernelArgs<PMS, DROP, TRK, RES>::type& a, int maxdeg, hipStream_t st) {
+  return maxdeg == 0 ? launch_mlp<PT, 0, NEEDVAR, NEEDJAC, PMS, DROP, TRK, RES>(a, st) : launch_mlp<PT, 2, NEEDVAR, NEEDJAC, PMS, DROP, TRK, RES>(a, st);
 }
 // The ladder of tiles of rollout_open.hip's launch_open_tiles (at every compiled limit at once the one-trajectory recording rung takes
 // 85 KB + 1.3 KB of activations, the measured form one row [PT][S] more: nothing within the limits is refused), entered one rung lower
@@ -585,19 +664,19 @@ static int launch_mlp_deg(const typename MlpKernelArgs<PMS, DROP, TRK>::type& a,
 // width changes no bit of a trajectory (a column of phases K, V, J is computed the same way in every width: the identities with
 // mcp_rollout_open hold across the rungs).
 #define MLP_SMALL_SWARM 1024  // 4 trajectories x the 256 compute units of the MI355X
-template <bool PMS, bool DROP = false, bool TRK = false>
-static int launch_mlp_tiles(const typename MlpKernelArgs<PMS, DROP, TRK>::type& a, int maxdeg, bool wantvar, hipStream_t st) {
+template <bool PMS, bool DROP = false, bool TRK = false, bool RES = false>
+static int launch_mlp_tiles(const typename MlpKernelArgs<PMS, DROP, TRK, RES>::type& a, int maxdeg, bool wantvar, hipStream_t st) {
   const bool small = a.M <= MLP_SMALL_SWARM;
   if (!a.jac) {
-    if (!a.sample && !wantvar) return launch_mlp_deg<1, false, false, PMS, DROP, TRK>(a, maxdeg, st);
-    int rc = small ? MCP_ERR_LIMIT : launch_mlp_deg<16, true, false, PMS, DROP, TRK>(a, maxdeg, st);
-    if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<4, true, false, PMS, DROP, TRK>(a, maxdeg, st);
+    if (!a.sample && !wantvar) return launch_mlp_deg<1, false, false, PMS, DROP, TRK, RES>(a, maxdeg, st);
+    int rc = small ? MCP_ERR_LIMIT : launch_mlp_deg<16, true, false, PMS, DROP, TRK, RES>(a, maxdeg, st);
+    if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<4, true, false, PMS, DROP, TRK, RES>(a, maxdeg, st);
     return rc;
   }
-  if (!a.sample && !wantvar) return launch_mlp_deg<1, false, true, PMS, DROP, TRK>(a, maxdeg, st);
-  int rc = small ? MCP_ERR_LIMIT : launch_mlp_deg<16, true, true, PMS, DROP, TRK>(a, maxdeg, st);
-  if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<4, true, true, PMS, DROP, TRK>(a, maxdeg, st);
-  if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<1, true, true, PMS, DROP, TRK>(a, maxdeg, st);
+  if (!a.sample && !wantvar) return launch_mlp_deg<1, false, true, PMS, DROP, TRK, RES>(a, maxdeg, st);
+  int rc = small ? MCP_ERR_LIMIT : launch_mlp_deg<16, true, true, PMS, DROP, TRK, RES>(a, maxdeg, st);
+  if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<4, true, true, PMS, DROP, TRK, RES>(a, maxdeg, st);
+  if (rc == MCP_ERR_LIMIT) rc = launch_mlp_deg<1, true, true, PMS, DROP, TRK, RES>(a, maxdeg, st);
   return rc;
 }
 
@@ -621,13 +700,25 @@ static TrackArgs mlp_with_track(const Args& a, double p_drop, const mcp_mlp_trac
   return d;
 }
 
-// what mcp_rollout_mlp, mcp_rollout_mlp_meas, mcp_rollout_mlp_drop and mcp_rollout_mlp_track share (ms NULL: no measurement; p_drop 0: the
-// kernels without dropout; trk NULL or n == 0: the kernels without the error features)
+// the arguments of a residual form: those of the tracking form (with or without errors), and the PD term
+template <class ResArgs, class Args>
+static ResArgs mlp_with_res(const Args& a, double p_drop, const mcp_mlp_track* trk, const mcp_mlp_pd* res) {
+  ResArgs d = mlp_with_drop<ResArgs, Args>(a, p_drop);
+  d.trk = mlp_track_args_or_none(trk, p_drop);
+  d.res = mlp_res_args(res);
+  return d;
+}
+
+// what mcp_rollout_mlp, mcp_rollout_mlp_meas, mcp_rollout_mlp_drop, mcp_rollout_mlp_track and mcp_rollout_mlp_res share (ms NULL: no
+// measurement; p_drop 0: the kernels without dropout; trk NULL or n == 0: the kernels without the error features; res NULL or on == 0:
+// the kernels without the PD term)
 static int mlp_dispatch(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_meas* ms, const mcp_noise* noise, double p_drop, int M, int T,
                         int particle_pred, const double* x0, double* states, double* inputs, double* mu, double* var, double* jac,
-                        uint32_t* status, void* stream, const mcp_mlp_track* trk = nullptr) {
-  const int crc = closed_loop_checks(model && mlp && noise && x0 && states && inputs && status && mlp_drop_ok(p_drop), M, T, model, ms, false,
-                                     [&] { return mlp_policy_check(model, mlp, trk, T); });
+                        uint32_t* status, void* stream, const mcp_mlp_track* trk = nullptr, const mcp_mlp_pd* res = nullptr) {
+  const int crc = closed_loop_checks(model && mlp && noise && x0 && states && inputs && status && mlp_drop_ok(p_drop), M, T, model, ms, false, [&] {
+    const int prc = mlp_policy_check(model, mlp, trk, T);
+    return prc != MCP_OK ? prc : mlp_res_check(mlp, res, T);
+  });
   if (crc != MCP_OK) return crc;
   OpenArgsMlpMeas a;
   // (T == 1: the policy alone -- no transition, nothing to record)
@@ -635,6 +726,12 @@ static int mlp_dispatch(const mcp_model* model, const mcp_mlp_policy* mlp, const
   a.mlp = mlp_normalised(mlp);
   a.inputs = inputs;
   hipStream_t st = (hipStream_t)stream;
+  if (res_active(res)) {
+    if (!meas_active(ms))
+      return launch_mlp_tiles<false, true, true, true>(mlp_with_res<OpenArgsMlpRes<false>, OpenArgsMlp>(a, p_drop, trk, res), maxdeg, var != nullptr, st);
+    a.ms = *ms;
+    return launch_mlp_tiles<true, true, true, true>(mlp_with_res<OpenArgsMlpRes<true>, OpenArgsMlpMeas>(a, p_drop, trk, res), maxdeg, var != nullptr, st);
+  }
   if (track_active(trk)) {
     if (!meas_active(ms))
       return launch_mlp_tiles<false, true, true>(mlp_with_track<OpenArgsMlpTrack<false>, OpenArgsMlp>(a, p_drop, trk), maxdeg, var != nullptr, st);
@@ -687,6 +784,16 @@ extern "C" int mcp_rollout_mlp_track(const mcp_model* model, const mcp_mlp_polic
   return mlp_dispatch(model, mlp, meas, noise, p_drop, M, T, particle_pred, x0, states, inputs, mu, var, jac, status, stream, track);
 }
 
+// mcp_rollout_mlp_track with the PD term of the residual policy, u = squash(PD(x, t) + net(x, t)) -- the UR5 launch script's tracking
+// controller (PD_controller.forward, policy_learning/Policy.py:406-449) kept, and Policy.MLP_policy as its correction under the one
+// squashing: the RES forms above, over the loops the other entries replace (policy_learning/MC_PILCO.py:615-674, measured :808-906).
+// res NULL or res->on == 0: the kernels of mcp_rollout_mlp_track on the same arguments, the same bits.
+extern "C" int mcp_rollout_mlp_res(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_mlp_track* track, const mcp_mlp_pd* res,
+                                   const mcp_meas* meas, const mcp_noise* noise, double p_drop, int M, int T, int particle_pred, const double* x0,
+                                   double* states, double* inputs, double* mu, double* var, double* jac, uint32_t* status, void* stream) {
+  return mlp_dispatch(model, mlp, meas, noise, p_drop, M, T, particle_pred, x0, states, inputs, mu, var, jac, status, stream, track, res);
+}
+
 // ---------------------------------------------------------------------------------------
 // Reverse-time sweep of the closed loop under the network: the open-loop sweep (rollout_open.hip: stages A, B, C, the loader wave) with
 // the policy's stage between B and C.  Per row r and trajectory, with gu = gz[input slots] + g_inputs[r] (row T - 1: g_inputs alone):
@@ -719,8 +826,9 @@ extern "C" int mcp_rollout_mlp_track(const mcp_model* model, const mcp_mlp_polic
 #define MB_NT 512
 #define MB_NWORK (MB_NT - 128)  // worker threads
 #define MB_NACC 18              // parameter entries per worker thread
-static_assert(MCP_MAX_HIDDEN * (MCP_MAX_PFEAT + 1) + MCP_MAX_HIDDEN * (MCP_MAX_HIDDEN + 1) + MCP_MAX_INPUT * (MCP_MAX_HIDDEN + 1) <= MB_NACC * MB_NWORK,
-              "a worker thread's share of the parameters");
+static_assert(MCP_MAX_HIDDEN * (MCP_MAX_PFEAT + 1) + MCP_MAX_HIDDEN * (MCP_MAX_HIDDEN + 1) + MCP_MAX_INPUT * (MCP_MAX_HIDDEN + 1) + 2 * MCP_MAX_INPUT <=
+                  MB_NACC * MB_NWORK,
+              "a worker thread's share of the parameters (the residual form's two gain vectors included)");
 #define MB_CMAX (MCP_MAX_HIDDEN / 4)  // columns per lane of the chain wave
 
 struct MlpBwdArgs {
@@ -770,17 +878,34 @@ template <bool PMS>
 struct MlpBwdArgsTrack : MlpBwdArgsDrop<PMS> {
   MlpTrackArgs trk;
 };
-template <bool PMS, bool DROP, bool TRK = false>
+// RESIDUAL form (template RES, mcp_rollout_mlp_res_bwd; built on the tracking form): with abar_k the adjoint of the output layer's
+// pre-activation, which stage M leaves in LDS as delta_out[k],
+//   lambda[pos[k]] -= sqrt_kp[k]^2 abar_k;   lambda[vel[k]] -= sqrt_kd[k]^2 abar_k          (stage C, tables kpos / kvel per state component and
+//                                                                                             the squared gains in LDS; measured form: in ybar)
+//   g_sqrt_kp[k] += 2 sqrt_kp[k] e[pos[k]] abar_k;   g_sqrt_kd[k] += 2 sqrt_kd[k] e[vel[k]] abar_k,   e = target[r] - x_r  (measured: y_r)
+// The gain gradients are 2 U more entries of the workers' outer sums, behind bout: their delta is delta_out[k], their "activation" the
+// factor 2 sqrt_k e, which the workers write behind the constant 1 of an activation row from the forward's operands, beside the error
+// features.  So they stay off the chain wave, need no reduction of their own (the PD sweep's per-lane sums end in one), and the slab
+// keeps its rule: one store per entry, a fixed order of sums.  The network's deltas are unchanged.
+template <bool PMS>
+struct MlpBwdArgsRes : MlpBwdArgsTrack<PMS> {
+  MlpResArgs res;
+};
+template <bool PMS, bool DROP, bool TRK = false, bool RES = false>
 struct MlpBwdKernelArgs {
   typedef typename MlpBwdArgsOf<PMS>::type type;
 };
 template <bool PMS>
-struct MlpBwdKernelArgs<PMS, true, false> {
+struct MlpBwdKernelArgs<PMS, true, false, false> {
   typedef MlpBwdArgsDrop<PMS> type;
 };
 template <bool PMS>
-struct MlpBwdKernelArgs<PMS, true, true> {
+struct MlpBwdKernelArgs<PMS, true, true, false> {
   typedef MlpBwdArgsTrack<PMS> type;
+};
+template <bool PMS>
+struct MlpBwdKernelArgs<PMS, true, true, true> {
+  typedef MlpBwdArgsRes<PMS> type;
 };
 
 struct MlpBwdLayout {
@@ -788,11 +913,12 @@ struct MlpBwdLayout {
   int car, mtab;               // measured form: the filter's carries | pvel, ppos
   int keep;                    // dropout form: the keep words [3][pts][2]
   int etab;                    // tracking form: ferr (ints, per state component)
+  int ktab, gnl, res0;         // residual form: kpos | kvel (ints, per state component), sqrt_kp^2 | sqrt_kd^2; inside an activation row: 2 sqrt_k e
   int rp, fp, ap, dp;          // pitches: record row | fbar row | activation row | delta row (odd)
   int aoff[3], one, doff[3];   // inside an activation row: the input of layer l, the constant 1; inside a delta row: the output of layer l
 };
 __host__ __device__ inline MlpBwdLayout mlp_bwd_layout(int pts, int S, int U, int G, int D, const mcp_mlp_policy& p, const MlpGeom& g, bool wlds,
-                                                       bool pms = false, bool drop = false, bool trk = false) {
+                                                       bool pms = false, bool drop = false, bool trk = false, bool res = false) {
   MlpBwdLayout L;
   int o = 0;
   auto take = [&](int n) {
@@ -811,7 +937,8 @@ __host__ __device__ inline MlpBwdLayout mlp_bwd_layout(int pts, int S, int U, in
     dd += g.out[l];
   }
   L.one = ao;
-  L.ap = (ao + 1) | 1;
+  L.res0 = ao + 1;
+  L.ap = (ao + 1 + (res ? 2 * U : 0)) | 1;
   L.dp = dd | 1;
   L.rec = take(2 * pts * L.rp);
   L.xs = take(2 * pts * S);
@@ -829,6 +956,8 @@ __host__ __device__ inline MlpBwdLayout mlp_bwd_layout(int pts, int S, int U, in
   L.mtab = pms ? take(MCP_MAX_STATE) : 0;  // ints: pvel (per state component: the velocity of the pair it is the position of, or -1) | ppos (the converse)
   L.keep = drop ? take(3 * pts * 2) : 0;   // 64-bit words: bit j = unit j of hidden layer l of the row's trajectory is kept
   L.etab = trk ? take(MCP_MAX_STATE / 2) : 0;  // ints: ferr (per state component: the error feature that reads it, or -1)
+  L.ktab = res ? take(MCP_MAX_STATE) : 0;      // ints: kpos | kvel (per state component: the input that reads it as position / velocity, or -1)
+  L.gnl = res ? take(2 * MCP_MAX_INPUT) : 0;   // sqrt_kp^2 | sqrt_kd^2
   L.w = o;
   L.total = o + (wlds ? g.lds : 0);
   return L;
@@ -867,25 +996,34 @@ template <bool PMS>
 __device__ __forceinline__ mcp_noise mlp_bwd_noise(const MlpBwdArgsTrack<PMS>& a) {  // (built on the dropout form's arguments)
   return noise_of_launch(a.nz);
 }
+template <bool PMS>
+__device__ __forceinline__ mcp_noise mlp_bwd_noise(const MlpBwdArgsRes<PMS>& a) {
+  return noise_of_launch(a.nz);
+}
 template <class Args>
 __device__ __forceinline__ mcp_noise mlp_bwd_noise(const Args&) {
   return mcp_noise{};
 }
 
-template <bool WLDS, bool PMS = false, bool DROP = false, bool TRK = false>
-__global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdKernelArgs<PMS, DROP, TRK>::type a) {
+template <bool WLDS, bool PMS = false, bool DROP = false, bool TRK = false, bool RES = false>
+__global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdKernelArgs<PMS, DROP, TRK, RES>::type a) {
   static_assert(DROP || !TRK, "the tracking forms are built on the dropout forms");
+  static_assert(TRK || !RES, "the residual forms are built on the tracking forms");
   extern __shared__ double smem[];
   const mcp_mlp_policy& pl = a.mlp;
   const int S = a.S, U = a.U, G = a.G, D = a.D, M = a.M, T = a.T, nna = a.nna, na = a.na, pts = a.pts;
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const MlpGeom mg = mlp_geom(pl);
-  const MlpBwdLayout L = mlp_bwd_layout(pts, S, U, G, D, pl, mg, WLDS, PMS, DROP, TRK);
+  const MlpBwdLayout L = mlp_bwd_layout(pts, S, U, G, D, pl, mg, WLDS, PMS, DROP, TRK, RES);
   int ntr = 0;           // (tracking form: the error features; whether it runs without dropout; ferr)
   bool alldrop = false;
   if constexpr (TRK) ntr = a.trk.n, alldrop = a.trk.nodrop != 0;
   (void)alldrop;
   int* ferr = reinterpret_cast<int*>(smem + L.etab);
+  int* kpos = reinterpret_cast<int*>(smem + L.ktab);  // (residual form; so are the next two)
+  int* kvel = kpos + MCP_MAX_STATE;
+  double* gn2 = smem + L.gnl;
+  const int ntot = mg.nparam + (RES ? 2 * U : 0);  // the entries of a slab
   const int GD = G * D, RP = L.rp;
   double* rec = smem + L.rec;
   double* xsl = smem + L.xs;
@@ -957,6 +1095,15 @@ __global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdK
         if (a.trk.idx[i] == s) fe = i;
       ferr[s] = fe;
     }
+    if constexpr (RES) {
+      int kp = -1, kv = -1;
+      for (int k = 0; k < U; ++k) {
+        if (a.res.pos[k] == s) kp = k;
+        if (a.res.vel[k] == s) kv = k;
+      }
+      kpos[s] = kp;
+      kvel[s] = kv;
+    }
     if constexpr (PMS) {
       int pv = -1, pp = -1;
       for (int i = 0; i < a.ms.n; ++i) {
@@ -967,9 +1114,17 @@ __global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdK
       ppos[s] = pp;
     }
   }
+  if constexpr (RES) {
+    if (tid >= 64 && tid < 64 + U) {  // the gains squared once, as the forward squares them
+      const int k = tid - 64;
+      const double kp = a.res.sqrt_kp[k], kd = a.res.sqrt_kd[k];
+      gn2[k] = kp * kp;
+      gn2[MCP_MAX_INPUT + k] = kd * kd;
+    }
+  }
   // a worker thread's entries of the parameter vector: where their delta and their activation sit in a row; the running sums
   const int wt = tid - 128;
-  const int nused = (mg.nparam + MB_NWORK - 1) / MB_NWORK;  // (uniform)
+  const int nused = (ntot + MB_NWORK - 1) / MB_NWORK;  // (uniform)
   int dof[MB_NACC], aof[MB_NACC];
   double gacc[MB_NACC];
 #pragma unroll
@@ -977,7 +1132,7 @@ __global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdK
     dof[i] = aof[i] = 0;
     gacc[i] = 0.0;
     const int e = wt + MB_NWORK * i;
-    if (wt >= 0 && e < mg.nparam) {
+    if (wt >= 0 && e < ntot) {
 #pragma unroll
       for (int l = 0; l < 3; ++l) {
         if (l >= nl) continue;
@@ -988,6 +1143,13 @@ __global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdK
         } else if (e >= mg.boff[l] && e < mg.boff[l] + mg.out[l]) {
           dof[i] = L.doff[l] + e - mg.boff[l];
           aof[i] = L.one;
+        }
+      }
+      if constexpr (RES) {  // g_sqrt_kp | g_sqrt_kd: delta_out[k] times the row's 2 sqrt_k e
+        if (e >= mg.nparam) {
+          const int j = e - mg.nparam;
+          dof[i] = dlast + (j < U ? j : j - U);
+          aof[i] = L.res0 + j;
         }
       }
     }
@@ -1015,6 +1177,15 @@ __global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdK
         if (lane >= nnp + nap && lane < nnp + nap + ntr) {
           const int s = a.trk.idx[lane - nnp - nap];
           A[lane + nap] = a.trk.target[(size_t)r * S + s] - xr[s];
+        }
+      }
+      if constexpr (RES) {  // the gain gradients' factors 2 sqrt_k e, e the forward's difference on the forward's operands
+        if (lane < 2 * U) {
+          const bool isp = lane < U;
+          const int k = isp ? lane : lane - U;
+          const int s = isp ? a.res.pos[k] : a.res.vel[k];
+          const double e = a.res.target[(size_t)r * S + s] - xr[s];
+          A[L.res0 + lane] = 2.0 * (isp ? a.res.sqrt_kp[k] : a.res.sqrt_kd[k]) * e;
         }
       }
       if (lane == 0) A[L.one] = 1.0;
@@ -1184,6 +1355,10 @@ __global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdK
               if constexpr (TRK) {
                 if (ferr[s] >= 0) v -= fb[nnp + 2 * nap + ferr[s]];  // e = target - x
               }
+              if constexpr (RES) {
+                if (kpos[s] >= 0) v -= gn2[kpos[s]] * dr[dlast + kpos[s]];
+                if (kvel[s] >= 0) v -= gn2[MCP_MAX_INPUT + kvel[s]] * dr[dlast + kvel[s]];
+              }
             }
           } else if (r <= len - 1) {
             auto ybar = [&](int c) {  // the policy's pull on component c of the measurement
@@ -1192,6 +1367,10 @@ __global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdK
               if (fang[c] >= 0) y += fb[nnp + fang[c]] * Ar[nnp + nap + fang[c]] - fb[nnp + nap + fang[c]] * Ar[nnp + fang[c]];
               if constexpr (TRK) {
                 if (ferr[c] >= 0) y -= fb[nnp + 2 * nap + ferr[c]];  // e = target - y
+              }
+              if constexpr (RES) {
+                if (kpos[c] >= 0) y -= gn2[kpos[c]] * dr[dlast + kpos[c]];
+                if (kvel[c] >= 0) y -= gn2[MCP_MAX_INPUT + kvel[c]] * dr[dlast + kvel[c]];
               }
               return y;
             };
@@ -1235,17 +1414,17 @@ __global__ __launch_bounds__(MB_NT) void rollout_mlp_bwd_kernel(typename MlpBwdK
 #pragma unroll
     for (int i = 0; i < MB_NACC; ++i) {
       const int e = wt + MB_NWORK * i;
-      if (e < mg.nparam) a.g_params[(size_t)blockIdx.x * mg.nparam + e] = gacc[i];
+      if (e < ntot) a.g_params[(size_t)blockIdx.x * ntot + e] = gacc[i];
     }
   }
 }
 
 // what mcp_rollout_mlp_bwd, mcp_rollout_mlp_meas_bwd and mcp_rollout_mlp_drop_bwd share (ms NULL: no measurement; p_drop 0: the kernels
 // without dropout, and `noise` is not looked at)
-template <bool WLDS, bool PMS, bool DROP = false, bool TRK = false>
-static int launch_mlp_bwd(const typename MlpBwdKernelArgs<PMS, DROP, TRK>::type& a, size_t lds, hipStream_t st) {
-  MCP_ENSURE_MAX_LDS((rollout_mlp_bwd_kernel<WLDS, PMS, DROP, TRK>));
-  hipLaunchKernelGGL((rollout_mlp_bwd_kernel<WLDS, PMS, DROP, TRK>), dim3((a.M + MB_PT - 1) / MB_PT), dim3(MB_NT), lds, st, a);
+template <bool WLDS, bool PMS, bool DROP = false, bool TRK = false, bool RES = false>
+static int launch_mlp_bwd(const typename MlpBwdKernelArgs<PMS, DROP, TRK, RES>::type& a, size_t lds, hipStream_t st) {
+  MCP_ENSURE_MAX_LDS((rollout_mlp_bwd_kernel<WLDS, PMS, DROP, TRK, RES>));
+  hipLaunchKernelGGL((rollout_mlp_bwd_kernel<WLDS, PMS, DROP, TRK, RES>), dim3((a.M + MB_PT - 1) / MB_PT), dim3(MB_NT), lds, st, a);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
 }
@@ -1263,12 +1442,24 @@ static int launch_mlp_bwd_track(const Args& a, const mcp_noise* noise, double p_
   if (noise && p_drop > 0.0) d.nz = *noise;
   return a.wlds ? launch_mlp_bwd<true, PMS, true, true>(d, lds, st) : launch_mlp_bwd<false, PMS, true, true>(d, lds, st);
 }
+// a residual sweep: the tracking form's arguments (with or without errors), and the PD term
+template <bool PMS, class Args>
+static int launch_mlp_bwd_res(const Args& a, const mcp_noise* noise, double p_drop, const mcp_mlp_track* trk, const mcp_mlp_pd* res, size_t lds,
+                              hipStream_t st) {
+  MlpBwdArgsRes<PMS> d = mlp_with_res<MlpBwdArgsRes<PMS>, Args>(a, p_drop, trk, res);
+  memset(&d.nz, 0, sizeof(d.nz));
+  if (noise && p_drop > 0.0) d.nz = *noise;
+  return a.wlds ? launch_mlp_bwd<true, PMS, true, true, true>(d, lds, st) : launch_mlp_bwd<false, PMS, true, true, true>(d, lds, st);
+}
 static int mlp_bwd_dispatch(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_meas* ms, const mcp_noise* noise, double p_drop, int M, int T,
                             const double* states, const double* inputs, const double* jac, const double* g_states, const double* g_inputs,
-                            double* g_params, double* g_x0, void* stream, const mcp_mlp_track* trk = nullptr) {
-  const bool drop = p_drop > 0.0, track = track_active(trk);
+                            double* g_params, double* g_x0, void* stream, const mcp_mlp_track* trk = nullptr, const mcp_mlp_pd* res = nullptr) {
+  const bool drop = p_drop > 0.0, resid = res_active(res), track = track_active(trk) || resid;
   const int crc = closed_loop_checks(model && mlp && states && inputs && g_states && (jac || T <= 1) && mlp_drop_ok(p_drop) && (noise || !drop), M, T,
-                                     model, ms, true, [&] { return mlp_policy_check(model, mlp, trk, T); });
+                                     model, ms, true, [&] {
+                                       const int prc = mlp_policy_check(model, mlp, trk, T);
+                                       return prc != MCP_OK ? prc : mlp_res_check(mlp, res, T);
+                                     });
   if (crc != MCP_OK) return crc;
   if (!g_x0 && !g_params) return MCP_OK;  // nothing asked for
   const bool pms = meas_active(ms);
@@ -1283,12 +1474,15 @@ static int mlp_bwd_dispatch(const mcp_model* model, const mcp_mlp_policy* mlp, c
   size_t lds = 0;
   for (int pts = MB_PT; pts >= 1 && !a.pts; pts >>= 1)
     for (int wl = 1; wl >= 0 && !a.pts; --wl) {
-      const MlpBwdLayout L = mlp_bwd_layout(pts, a.S, a.U, a.G, a.D, a.mlp, mg, wl != 0, pms, drop || track, track);
+      const MlpBwdLayout L = mlp_bwd_layout(pts, a.S, a.U, a.G, a.D, a.mlp, mg, wl != 0, pms, drop || track, track, resid);
       lds = (size_t)L.total * sizeof(double);
       if (lds <= MCP_LDS_LIMIT) a.pts = pts, a.wlds = wl;
     }
   if (!a.pts) return MCP_ERR_LIMIT;  // (not reached within the compiled limits: one trajectory takes 22 KB at all of them at once)
   hipStream_t st = (hipStream_t)stream;
+  if (resid)
+    return pms ? launch_mlp_bwd_res<true, MlpBwdArgsMeas>(a, noise, p_drop, trk, res, lds, st)
+               : launch_mlp_bwd_res<false, MlpBwdArgs>(a, noise, p_drop, trk, res, lds, st);
   if (track)
     return pms ? launch_mlp_bwd_track<true, MlpBwdArgsMeas>(a, noise, p_drop, trk, lds, st) : launch_mlp_bwd_track<false, MlpBwdArgs>(a, noise, p_drop, trk, lds, st);
   if (drop) return pms ? launch_mlp_bwd_drop<true, MlpBwdArgsMeas>(a, noise, p_drop, lds, st) : launch_mlp_bwd_drop<false, MlpBwdArgs>(a, noise, p_drop, lds, st);
@@ -1330,4 +1524,15 @@ extern "C" int mcp_rollout_mlp_track_bwd(const mcp_model* model, const mcp_mlp_p
                                          const double* jac, const double* g_states, const double* g_inputs, double* g_params, double* g_x0,
                                          void* stream) {
   return mlp_bwd_dispatch(model, mlp, meas, noise, p_drop, M, T, states, inputs, jac, g_states, g_inputs, g_params, g_x0, stream, track);
+}
+
+// Reverse-time sweep of mcp_rollout_mlp_res: the RES forms of the sweep above -- the PD term's pull on the state in stage C (measured form:
+// on the measurement), the gain gradients g_sqrt_kp [U] | g_sqrt_kd [U] behind bout in every slab of n_param + 2 U entries.  res NULL or
+// res->on == 0: the kernels of mcp_rollout_mlp_track_bwd on the same arguments, the same bits.  Replaces autograd's backward
+// (MC_PILCO.py:522) through the loops named at the forward entry.
+extern "C" int mcp_rollout_mlp_res_bwd(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_mlp_track* track, const mcp_mlp_pd* res,
+                                       const mcp_meas* meas, const mcp_noise* noise, double p_drop, int M, int T, const double* states,
+                                       const double* inputs, const double* jac, const double* g_states, const double* g_inputs, double* g_params,
+                                       double* g_x0, void* stream) {
+  return mlp_bwd_dispatch(model, mlp, meas, noise, p_drop, M, T, states, inputs, jac, g_states, g_inputs, g_params, g_x0, stream, track, res);
 }

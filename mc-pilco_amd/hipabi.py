@@ -79,6 +79,13 @@ class MLPTrack(C.Structure):
     _fields_ = [("n", C.c_int32), ("idx", C.c_int32 * MAX_STATE), ("rows", C.c_int32), ("target", dptr)]
 
 
+class MLPResidual(C.Structure):
+    """mcp_mlp_pd: the PD term sqrt_kp[k]^2 e[pos[k]] + sqrt_kd[k]^2 e[vel[k]], e = target[t] - x, added to the network's output ahead of
+    the squashing by the residual entries (on == 0: none)."""
+    _fields_ = [("on", C.c_int32), ("pos", C.c_int32 * MAX_INPUT), ("vel", C.c_int32 * MAX_INPUT), ("sqrt_kp", dptr), ("sqrt_kd", dptr),
+                ("target", dptr), ("rows", C.c_int32)]
+
+
 class OptState(C.Structure):
     _fields_ = [("step", C.c_int64), ("attempt", C.c_int64), ("pending", C.c_int64), ("adam_t", C.c_int64), ("total_attempts", C.c_int64),
                 ("es2", C.c_double), ("cost_prev", C.c_double)]
@@ -194,6 +201,10 @@ _SIGS = {
                                         C.c_int, C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
     "mcp_rollout_mlp_track_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(MLPPolicy), C.POINTER(MLPTrack), C.POINTER(Meas), C.POINTER(Noise),
                                             C.c_double, C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
+    "mcp_rollout_mlp_res": (C.c_int, [C.POINTER(Model), C.POINTER(MLPPolicy), C.POINTER(MLPTrack), C.POINTER(MLPResidual), C.POINTER(Meas),
+                                      C.POINTER(Noise), C.c_double, C.c_int, C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
+    "mcp_rollout_mlp_res_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(MLPPolicy), C.POINTER(MLPTrack), C.POINTER(MLPResidual), C.POINTER(Meas),
+                                          C.POINTER(Noise), C.c_double, C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
     "mcp_rollout_bwd":(C.c_int, [C.POINTER(Model), C.POINTER(Policy), C.POINTER(Noise), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr,
                                   dptr, dptr, dptr, dptr, dptr, C.c_size_t, dptr]),
     "mcp_rollout_fwd_ex": (C.c_int, [C.POINTER(Model), C.POINTER(Policy), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr, dptr,

@@ -666,6 +666,8 @@ def model_step(model: PackedModel, x, u, t, noise: Optional[NoiseSpec] = None, p
 #                  in the sweep the noise -- and the width of a row of its masks
 #   fwd_track, bwd_track, track_c()   (a policy that can track) the entries that take an mcp_mlp_track ahead of the dropout entries' arguments,
 #                  and the track itself -- None: the policy has no target, and the calls are the ones above
+#   fwd_res, bwd_res, res_c()   (a policy that can carry a PD term) the entries that take an mcp_mlp_pd behind the track, and the term itself --
+#                  None: the policy has none, and the calls are the ones above
 #   check(model, T)   the policy's own refusals
 class PackedPD:
     """mcp_pd_policy of a ``Policy.PD_controller`` (reference policy_learning/Policy.py:406-449): the two gain parameters are kept as they
@@ -732,16 +734,21 @@ class PackedMLP:
     launch takes the LIVE tensors, so an optimizer's in-place updates are seen.  Features f = [x[non_angle], sin x[angle], cos x[angle]]
     (both lists empty: f = x).  A policy with a target trajectory (``policy.target_traj`` [rows, S], ``policy.error_indices``) appends the
     tracking errors target[t][idx[i]] - x[idx[i]] behind them (mcp_mlp_track): ``track_idx`` and ``target`` (a contiguous float64 GPU copy,
-    not differentiable) are carried here, ``P`` counts them, and the launches go to the track entries."""
+    not differentiable) are carried here, ``P`` counts them, and the launches go to the track entries.  A ``Policy.Residual_MLP_policy`` adds
+    the PD term of mcp_mlp_pd ahead of the squashing: its two gain parameters come LAST in ``params`` / ``shapes`` / ``n_param`` (a launch takes
+    them as [U] tensors, ``tensors()``), ``res_target`` / ``res_pos`` / ``res_vel`` are carried here, and the launches go to the residual
+    entries (``res_c()``), whose sweep's slabs hold g_sqrt_kp | g_sqrt_kd behind bout."""
 
     fwd, bwd = ("mcp_rollout_mlp", "mcp_rollout_mlp_meas"), ("mcp_rollout_mlp_bwd", "mcp_rollout_mlp_meas_bwd")
     fwd_drop, bwd_drop = "mcp_rollout_mlp_drop", "mcp_rollout_mlp_drop_bwd"
     fwd_track, bwd_track = "mcp_rollout_mlp_track", "mcp_rollout_mlp_track_bwd"  # (a policy with a track: whatever meas and p_drop are)
+    fwd_res, bwd_res = "mcp_rollout_mlp_res", "mcp_rollout_mlp_res_bwd"  # (a policy with the PD term: whatever meas, p_drop and the track are)
     fwd_outputs = ("mu", "var", "jac")
     grad_tile = 16  # one slab of parameter gradients per workgroup of the sweep
 
     def __init__(self, policy):
         self.params = list(policy.mlp_parameters())
+        self.n_net = len(self.params)  # the network's own tensors; a residual policy's two gains come behind them
         self.S, self.U = int(policy.state_dim), int(policy.input_dim)
         self.hidden = [int(h) for h in policy.hidden_sizes]
         self.angle, self.non_angle = [int(i) for i in policy.angle_indices], [int(i) for i in policy.non_angle_indices]
@@ -758,18 +765,33 @@ class PackedMLP:
         self.u_max = np.full(self.U, um[0]) if len(um) == 1 else np.asarray(um, dtype=np.float64)
         if self.u_max.size != self.U or self.U > abi.MAX_INPUT:
             raise RuntimeError("u_max must be a scalar or hold one bound per input (at most %d inputs)" % abi.MAX_INPUT)
-        if len(self.hidden) not in (1, 2) or len(self.params) != 2 * len(self.hidden) + 2:
+        if len(self.hidden) not in (1, 2) or self.n_net != 2 * len(self.hidden) + 2:
             raise RuntimeError("the MLP policy has one or two hidden layers")
         if len(self.angle) > abi.MAX_STATE or len(self.non_angle) > abi.MAX_STATE:
             raise RuntimeError("at most %d indices per feature list" % abi.MAX_STATE)
         self.shapes = [tuple(q.shape) for q in self.params]
         self.n_param = sum(int(q.numel()) for q in self.params)
+        # the PD term of a Policy.Residual_MLP_policy (mcp_mlp_pd): the two gain parameters last in params / shapes / n_param -- a launch takes
+        # them as [U] tensors (a scalar gain expanded on the parameter's graph, as PackedPD.gains), the sweep's slab has 2 U more entries
+        self.res_gains, self.res_target, self._res_live = None, None, None
+        if getattr(policy, "pd_target_traj", None) is not None:
+            self.res_gains = [policy.sqrt_Kp_gains, policy.sqrt_Kd_gains]
+            self.res_pos, self.res_vel = [int(i) for i in policy.pd_pos_indices], [int(i) for i in policy.pd_vel_indices]
+            if len(self.res_pos) != self.U or len(self.res_vel) != self.U or any(int(g.numel()) not in (1, self.U) for g in self.res_gains):
+                raise RuntimeError("the PD term has one position, one velocity and one gain pair per input (or one gain for all)")
+            same = self.target is not None and policy.pd_target_traj is policy.target_traj
+            self.res_target = self.target if same else _t(policy.pd_target_traj, _dev(self.params[0].device)).reshape(-1, self.S).contiguous()
+            self.params += self.res_gains
+            self.shapes += [(self.U,), (self.U,)]
+            self.n_param += 2 * self.U
         self.grad_shape = (self.n_param,)
         self.drop_width = sum(self.hidden)  # a row of keep-masks: the hidden units, layer 0's first
         self.device = self.params[0].device
 
     def tensors(self):
-        return self.params
+        if self.res_gains is None:
+            return self.params
+        return self.params[:self.n_net] + [g.reshape(-1).expand(self.U) if g.numel() == 1 and self.U > 1 else g.reshape(-1) for g in self.res_gains]
 
     def check(self, model, T):
         if self.S != model.S or self.U != model.U:
@@ -778,6 +800,20 @@ class PackedMLP:
             raise RuntimeError("the rollout needs at least one row")
         if self.target is not None and self.target.shape[0] < T:
             raise RuntimeError("the target trajectory has %d rows, the rollout needs %d" % (self.target.shape[0], T))
+        if self.res_target is not None and self.res_target.shape[0] < T:
+            raise RuntimeError("the PD term's target has %d rows, the rollout needs %d" % (self.res_target.shape[0], T))
+
+    def res_c(self):
+        """mcp_mlp_pd over the gains of the launch whose descriptor ``to_c`` made last, or None for a policy without the PD term."""
+        if self.res_gains is None:
+            return None
+        kp, kd = self._res_live
+        c = abi.MLPResidual()
+        c.on, c.rows, c.target = 1, int(self.res_target.shape[0]), self.res_target.data_ptr()
+        c.sqrt_kp, c.sqrt_kd = kp.data_ptr(), kd.data_ptr()
+        for k in range(self.U):
+            c.pos[k], c.vel[k] = self.res_pos[k], self.res_vel[k]
+        return c
 
     def track_c(self):
         """mcp_mlp_track over the target held here, or None for a policy without one."""
@@ -794,6 +830,8 @@ class PackedMLP:
         for t, shp in zip(tensors, self.shapes):
             if t.dtype != DT or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shp:
                 raise RuntimeError("the MLP parameters must be contiguous float64 GPU tensors of their declared shapes")
+        if self.res_gains is not None:
+            self._res_live = (tensors[self.n_net], tensors[self.n_net + 1])  # (this launch's gains: res_c points at them)
         c = abi.MLPPolicy()
         c.S, c.U, c.P, c.n_hidden, c.squash = self.S, self.U, self.P, len(self.hidden), int(self.squash)
         for l, h in enumerate(self.hidden):
@@ -827,9 +865,12 @@ def _drop_args(meas_arg, nz, p_drop):
 
 def _entry(packed, names, plain, marg, nz, p_drop):
     """(name, arguments between the policy and the sizes) of the launch or sweep of ``packed``, ``names`` = (plain and measured, dropout,
-    track): a policy with a track takes its track entry (the track, then the dropout entry's arguments) whatever ``marg`` and ``p_drop``
+    track, residual): a policy with the PD term (PackedMLP.res_c) takes its residual entry whatever the rest is; a policy with a track takes its track entry (the track, then the dropout entry's arguments) whatever ``marg`` and ``p_drop``
     are; else p_drop > 0 the dropout entry; else the plain or measured one with ``plain`` behind the measurement."""
     tc = packed.track_c() if names[2] else None
+    rc = packed.res_c() if len(names) > 3 and names[3] else None
+    if rc is not None:  # (the PD term: the track or NULL, the term, then the dropout entry's arguments)
+        return names[3], [None if tc is None else C.byref(tc), C.byref(rc)] + _drop_args(marg, nz, p_drop)
     if tc is not None:
         return names[2], [C.byref(tc)] + _drop_args(marg, nz, p_drop)
     if p_drop > 0.0:
@@ -850,7 +891,8 @@ def _closed_launch(model, packed, tensors, noise, x0, T, particle_pred, status, 
         meas_buf = meas.measured = torch.empty(T, M, model.S, dtype=DT, device=dev)  # (allocated as rollout_forward_raw allocates it)
     outputs = {"jac": jac, "mu": None, "var": None}
     marg = _meas_arg(meas, T, M, meas_buf)
-    name, head = _entry(packed, (packed.fwd, getattr(packed, "fwd_drop", None), getattr(packed, "fwd_track", None)), [C.byref(nz)], marg, nz, p_drop)
+    name, head = _entry(packed, (packed.fwd, getattr(packed, "fwd_drop", None), getattr(packed, "fwd_track", None),
+                                 getattr(packed, "fwd_res", None)), [C.byref(nz)], marg, nz, p_drop)
     abi.check(getattr(abi.lib(), name)(_mc(model), C.byref(pc), *head, M, T,
                                        int(bool(particle_pred)), abi.ptr(x0), abi.ptr(states), abi.ptr(inputs),
                                        *[abi.ptr(outputs[k]) for k in packed.fwd_outputs], abi.ptr(status), abi.stream()), name)
@@ -869,7 +911,8 @@ def _closed_sweep(model, packed, tensors, states, inputs, jac, g_states, g_input
     pc = packed.to_c(*tensors)
     marg = _meas_arg(meas, T, M, meas_buf)
     nz = noise.to_c() if p_drop > 0.0 else None  # (only the keep decisions are drawn again)
-    name, head = _entry(packed, (packed.bwd, getattr(packed, "bwd_drop", None), getattr(packed, "bwd_track", None)), [], marg, nz, p_drop)
+    name, head = _entry(packed, (packed.bwd, getattr(packed, "bwd_drop", None), getattr(packed, "bwd_track", None),
+                                 getattr(packed, "bwd_res", None)), [], marg, nz, p_drop)
     abi.check(getattr(abi.lib(), name)(_mc(model), C.byref(pc), *head, M, T, abi.ptr(states), abi.ptr(inputs),
                                        abi.ptr(jac), abi.ptr(g_states), abi.ptr(g_inputs), abi.ptr(raw), abi.ptr(g_x0), abi.stream()), name)
     return raw, g_x0

@@ -13,6 +13,8 @@ drawn exactly like ``torch.nn.functional.dropout`` draws it on the CPU -- parity
 ``flg_bias`` adds ``f_linear.bias`` (not dropped out) to the linear layer inside the kernels; its gradient comes out of the adjoint sweep.
 ``MLP_policy`` (this project's own: a tanh multilayer perceptron on the same features) runs inside the fused closed loop, mcp_rollout_mlp;
 with ``target_traj`` it tracks: the errors target_traj[t] - x behind its features (Policy.py:389-403's map), mcp_rollout_mlp_track.
+``Residual_MLP_policy`` keeps a PD law (PD_controller's term, :437-449) and adds the network as its correction ahead of the one squashing,
+u = squash(PD(x, t) + net(x, t)), mcp_rollout_mlp_res.
 Exploration policies (Random_exploration, Sum_of_sinusoids :94-150, PD_controller :406-449) drive the simulated system once per
 trial (61-201 samples): host-side, their ``np.random`` draws in the reference's order so that a seeded launch script collects the
 same data.
@@ -227,6 +229,10 @@ class MLP_policy(Policy):
         return torch.cat(own + [err], dim=1)
 
     def forward(self, states, t=None, p_dropout=0.0):
+        return self.f_squash(self.network(states, t, p_dropout))
+
+    def network(self, states, t=None, p_dropout=0.0):
+        """a = Wout h + bout: the network's output ahead of the squashing."""
         h = self.features(states, t)
         ps = self.mlp_parameters()
         p = float(p_dropout) if self.flg_drop else 0.0
@@ -241,7 +247,7 @@ class MLP_policy(Policy):
             if keep is not None:
                 h = keep[:, off:off + width] * h * (1.0 / (1.0 - p))
                 off += width
-        return self.f_squash(h @ ps[-2].t() + ps[-1])
+        return h @ ps[-2].t() + ps[-1]
 
     def _u_max_values(self):
         """The bounds as a tuple of floats (a scalar: one entry), or None where ``u_max`` is nothing of the kind."""
@@ -256,6 +262,7 @@ class MLP_policy(Policy):
         tt = self.target_traj
         key = tuple(q.data_ptr() for q in self.mlp_parameters()) + (self.flg_squash, self._u_max_values(), id(tt),
                                                                     tt.data_ptr() if isinstance(tt, torch.Tensor) else None, tuple(self.error_indices))
+        key += self._packed_key_extra()
         hit = self.__dict__.get("_packed_mlp")
         if hit is None or hit[0] != key:
             hit = self.__dict__["_packed_mlp"] = (key, ops.PackedMLP(self))
@@ -287,6 +294,99 @@ class MLP_policy(Policy):
             return False
         if self.flg_squash and not all(v > 0 for v in um):
             return False
+        return True
+
+    def _packed_key_extra(self):
+        return ()
+
+
+class Residual_MLP_policy(MLP_policy):
+    """A PD law with a learned correction, u = squash(PD(x, t) + net(x, t)): ``PD_controller``'s term
+        a_pd[k] = sqrt_Kp_gains[k]^2 (pd_target_traj[t][pos[k]] - x[pos[k]]) + sqrt_Kd_gains[k]^2 (pd_target_traj[t][vel[k]] - x[vel[k]])
+    added to ``MLP_policy``'s output a = Wout h + bout AHEAD of the one squashing (one actuator bound); errors are plain differences,
+    dropout never touches the PD term, and the target is a constant.  ``MLP_policy``'s arguments, and
+      sqrt_Kp_gains, sqrt_Kd_gains   the gains' square roots (``torch.nn.Parameter``s): one value per input, or one for all
+      flg_train_gains                ``requires_grad`` of the two
+      pd_target_traj                 [rows, S]; None: ``target_traj``, which is then required
+      pd_pos_indices, pd_vel_indices the state components input k reads; None: the reference's layout 0 .. U-1 and S/2 .. S/2+U-1,
+                                     which needs an even S and U == S/2 -- otherwise both lists are required
+      zero_output                    Wout and bout start at zero and ``reinit`` leaves them zero: training starts from the PD law itself
+    ``error_indices=[]``: the network sees no error features while the PD term still has its target.  ``forward`` is the torch formula;
+    inside ``MC_PILCO`` the fused closed loop is mcp_rollout_mlp_res (ops.rollout_mlp), its sweep returning the gains' gradients behind
+    the network's."""
+
+    def __init__(self, state_dim, input_dim, hidden_sizes, angle_indices=None, non_angle_indices=None, u_max=1.0, flg_squash=True, weight_init=None,
+                 dtype=torch.float64, device=torch.device("cuda"), flg_drop=False, target_traj=None, error_indices=None, *, sqrt_Kp_gains,
+                 sqrt_Kd_gains, flg_train_gains=False, pd_target_traj=None, pd_pos_indices=None, pd_vel_indices=None, zero_output=False):
+        super().__init__(state_dim, input_dim, hidden_sizes, angle_indices=angle_indices, non_angle_indices=non_angle_indices, u_max=u_max,
+                         flg_squash=flg_squash, weight_init=weight_init, dtype=dtype, device=device, flg_drop=flg_drop, target_traj=target_traj,
+                         error_indices=error_indices)
+        S, U = int(state_dim), int(input_dim)
+        if pd_target_traj is None and target_traj is None:
+            raise ValueError("the PD term needs a target: pd_target_traj or target_traj")
+        self.pd_target_traj = self.target_traj if pd_target_traj is None else torch.as_tensor(pd_target_traj).detach().to(self.device)
+        if (pd_pos_indices is None) != (pd_vel_indices is None):
+            raise ValueError("pd_pos_indices and pd_vel_indices come together")
+        if pd_pos_indices is None:
+            if S % 2 != 0 or U != S // 2:
+                raise ValueError("the default PD layout needs an even state_dim and input_dim == state_dim / 2: pass pd_pos_indices and pd_vel_indices")
+            pd_pos_indices, pd_vel_indices = range(U), range(S // 2, S // 2 + U)
+        self.pd_pos_indices, self.pd_vel_indices = [int(i) for i in pd_pos_indices], [int(i) for i in pd_vel_indices]
+        if len(self.pd_pos_indices) != U or len(self.pd_vel_indices) != U:
+            raise ValueError("pd_pos_indices and pd_vel_indices hold one state component per input")
+        gain = lambda g: torch.nn.Parameter(torch.as_tensor(np.asarray(g.detach().cpu() if isinstance(g, torch.Tensor) else g), dtype=dtype)
+                                            .to(self.device).contiguous(), requires_grad=bool(flg_train_gains))
+        self.sqrt_Kp_gains, self.sqrt_Kd_gains = gain(sqrt_Kp_gains), gain(sqrt_Kd_gains)
+        if any(int(g.numel()) not in (1, U) for g in (self.sqrt_Kp_gains, self.sqrt_Kd_gains)):
+            raise ValueError("a gain holds one value per input, or one for all")
+        self.zero_output = bool(zero_output)
+        if self.zero_output:
+            self._zero_output_layer()
+
+    def _zero_output_layer(self):
+        for q in self.mlp_parameters()[-2:]:
+            q.data.zero_()
+
+    def reinit(self, scaling=1):
+        super().reinit(scaling)
+        if getattr(self, "zero_output", False):
+            self._zero_output_layer()
+
+    def gains(self):
+        """(sqrt_kp, sqrt_kd) as [U] tensors on the parameters' autograd graph: views, or a scalar gain expanded to every input."""
+        U = int(self.input_dim)
+        return [g.reshape(-1).expand(U) if g.numel() == 1 and U > 1 else g.reshape(-1) for g in (self.sqrt_Kp_gains, self.sqrt_Kd_gains)]
+
+    def pd_term(self, states, t):
+        x = states.reshape([-1, self.state_dim])
+        kp, kd = self.gains()
+        e = torch.as_tensor(self.pd_target_traj).to(x.device)[int(t)].reshape(1, -1) - x
+        return kp ** 2 * e[:, self.pd_pos_indices] + kd ** 2 * e[:, self.pd_vel_indices]
+
+    def forward(self, states, t=None, p_dropout=0.0):
+        if t is None:
+            raise ValueError("a Residual_MLP_policy is evaluated at a time step: pass t")
+        return self.f_squash(self.network(states, t, p_dropout) + self.pd_term(states, t))
+
+    def _packed_key_extra(self):
+        pt = self.pd_target_traj
+        return (self.sqrt_Kp_gains.data_ptr(), self.sqrt_Kd_gains.data_ptr(), id(pt), pt.data_ptr() if isinstance(pt, torch.Tensor) else None,
+                tuple(self.pd_pos_indices), tuple(self.pd_vel_indices))
+
+    def fusable(self, model, T):
+        """``MLP_policy.fusable``, and: float64 gains on a GPU, the PD target a float64 tensor [rows >= T, S], pos and vel in range and each
+        without a repeated entry."""
+        if not super().fusable(model, T):
+            return False
+        S = int(self.state_dim)
+        if any(g.dtype != torch.float64 or not g.is_cuda for g in (self.sqrt_Kp_gains, self.sqrt_Kd_gains)):
+            return False
+        pt = self.pd_target_traj
+        if not isinstance(pt, torch.Tensor) or pt.dtype != torch.float64 or pt.dim() != 2 or int(pt.shape[1]) != S or int(pt.shape[0]) < int(T):
+            return False
+        for lst in (self.pd_pos_indices, self.pd_vel_indices):
+            if any(i < 0 or i >= S for i in lst) or len(set(lst)) != len(lst):
+                return False
         return True
 
 
