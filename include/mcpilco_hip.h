@@ -241,6 +241,29 @@ typedef struct mcp_mlp_pd {
   int32_t rows;                 /* >= T                                                          */
 } mcp_mlp_pd;
 
+/* Integral term of the PD law in closed loop -- mcp_pd_policy's law with a clamped integral of the position error (anti-windup), the
+ * first law here whose control depends on controller state carried across the steps.  The reference has no integral law: without this
+ * term it is a stateful torch policy in the step loop of MC_PILCO.apply_policy (policy_learning/MC_PILCO.py:615-674; measured: :808-906).
+ * For input k with p = pos[k], v = vel[k] of the mcp_pd_policy beside it, e_t = target_traj[t] - x_t (measured form: y_t in place of x_t):
+ *   q_t[k] = I_{t-1}[k] + dt e_t[p],  I_{-1} = 0;      I_t[k] = min(max(q_t[k], -i_max[k]), +i_max[k])      (i_max[k] = +inf: no clamp)
+ *   a_t[k] = (sqrt_kp[k]^2 e_t[p] + sqrt_kd[k]^2 e_t[v]) + sqrt_ki[k]^2 I_t[k];    u_t[k] = u_max[k] tanh(a_t[k] / u_max[k]) (squash) or a_t[k]
+ * in every row t = 0 .. T - 1.  The PD products are mcp_rollout_pd's expression in its order and the integral product is added last, so
+ * sqrt_ki == 0 (with a finite I) reproduces the PD launch bit for bit.  The errors are plain differences, not wrapped.  A NaN passes
+ * through the clamp.  The clamp passes gradient iff |I_t[k]| < i_max[k] and blocks it where I_t sits on a bound; the forward launch
+ * writes I to integ and the sweep reads it there, so the sweep never re-decides a clamp.  Adjoint, per row r from T - 1 down, with abar
+ * the adjoint of a (mcp_rollout_pd_bwd's) and c_T = 0:
+ *   Ibar_r[k] = sqrt_ki[k]^2 abar_r[k] + c_{r+1}[k];   c_r[k] = (|I_r[k]| < i_max[k]) ? Ibar_r[k] : 0
+ *   lambda_r[pos[k]] -= dt c_r[k]  (beside - sqrt_kp[k]^2 abar_r[k]; measured form: on the measurement's adjoint, through the filter's)
+ *   g_sqrt_ki[k] += 2 sqrt_ki[k] I_r[k] abar_r[k]
+ * c is one double per (trajectory, input), kept in registers: no atomics, no sum across trajectories, the same bits run after run. */
+typedef struct mcp_pid_term {
+  int32_t on;                   /* 0: no integral term                                           */
+  const double* sqrt_ki;        /* DEVICE [U]: an optimizer updates it in place                  */
+  double i_max[MCP_MAX_INPUT];  /* > 0; +inf: no clamp                                           */
+  double dt;                    /* > 0: the integration step (the class passes T_sampling)       */
+  double* integ;                /* DEVICE [T][M][U]: I, written by the forward, read by the sweep */
+} mcp_pid_term;
+
 /* ---- library ------------------------------------------------------------------------ */
 int mcp_abi_version(void);
 const char* mcp_build_info(void);
@@ -466,6 +489,27 @@ int mcp_rollout_pd_meas(const mcp_model* model, const mcp_pd_policy* pd, const m
 int mcp_rollout_pd_meas_bwd(const mcp_model* model, const mcp_pd_policy* pd, const mcp_meas* meas, int M, int T, const double* states,
                             const double* inputs, const double* jac, const double* g_states, const double* g_inputs, double* g_gains,
                             double* g_x0, void* stream);
+/* mcp_rollout_pd / mcp_rollout_pd_meas with the INTEGRAL TERM (mcp_pid_term: the law, its clamp and the derivative convention are stated
+ * there), ONE launch.  meas NULL or n == 0: the law on the true state; else on the simulated measurement.  pid->integ [T][M][U] receives
+ * I_t of every row.  Everything else -- states, inputs, jac, mu / var, noise addressing, status flags (a NaN gain or target row reaches
+ * inputs and raises MCP_STATUS_NAN), T == 1, no ragged lengths -- as mcp_rollout_pd; the states carry the bits of mcp_rollout_open fed
+ * with the launch's own inputs, and the plain launch those of the recording launch.  pid NULL or pid->on == 0: mcp_rollout_pd /
+ * mcp_rollout_pd_meas on the same arguments (same kernels, same bits).  The checks of those entries in their order, then the term's:
+ * sqrt_ki or integ NULL; dt not > 0 (a NaN included); an i_max[k], k < U, not > 0 (a NaN included; +inf is legal) -- each MCP_ERR_ARG.
+ * Replaces a stateful torch policy (the reference has none) in the loop of MC_PILCO.apply_policy (policy_learning/MC_PILCO.py:615-674)
+ * or MC_PILCO4PMS.apply_policy (:808-906) over Model_learning.get_next_state (model_learning/Model_learning.py:210-229, 471-494, 685-718). */
+int mcp_rollout_pid(const mcp_model* model, const mcp_pd_policy* pd, const mcp_pid_term* pid /* NULL or on == 0: no integral term */,
+                    const mcp_meas* meas /* NULL or n == 0: the true state */, const mcp_noise* noise, int M, int T, int particle_pred,
+                    const double* x0, double* states, double* inputs, double* jac /* NULL: no record */, double* mu, double* var,
+                    uint32_t* status, void* stream);
+/* Reverse-time sweep of mcp_rollout_pid: mcp_rollout_pd_bwd / mcp_rollout_pd_meas_bwd with the adjoint of the integral carried down the
+ * rows (mcp_pid_term).  g_gains [M][3][U] = dJ/d(sqrt_kp, sqrt_kd, sqrt_ki) PER TRAJECTORY and g_x0 [M][S]; each may be NULL.  Reads
+ * pid->integ as the forward launch wrote it.  No atomics: bitwise reproducible, a trajectory's results do not depend on the others.
+ * pid NULL or pid->on == 0: mcp_rollout_pd_bwd / mcp_rollout_pd_meas_bwd on the same arguments, g_gains [M][2][U].  The same argument
+ * checks as the forward entry.  Replaces autograd's backward (MC_PILCO.py:522) through the loops named there. */
+int mcp_rollout_pid_bwd(const mcp_model* model, const mcp_pd_policy* pd, const mcp_pid_term* pid, const mcp_meas* meas, int M, int T,
+                        const double* states, const double* inputs, const double* jac, const double* g_states, const double* g_inputs,
+                        double* g_gains, double* g_x0, void* stream);
 /* mcp_rollout_mlp with the network evaluated on a SIMULATED MEASUREMENT of the state (mcp_meas, as mcp_rollout_pd_meas has it for the PD
  * law: noisy positions, backward-difference velocities through the first-order filter; row 0 is measured true), ONE launch: the particles
  * evolve on their true states, u_t = mlp(y_t).  Per pair i (p = pos[i], v = vel[i]) and row t >= 1: np_t = x_t[p] + std_pos[i] n_{t,i},

@@ -4,8 +4,10 @@
 //   recording          mcp_rollout_open_rec     the same, and the Jacobians of the increments are recorded for mcp_rollout_open_bwd
 //   feedback           mcp_rollout_pd           u_t is the PD law on x_t (struct OpenArgsPd); with jac the record for mcp_rollout_pd_bwd
 //   measured feedback  mcp_rollout_pd_meas      the PD law on a simulated measurement of x_t (struct OpenArgsPdMeas); mcp_rollout_pd_meas_bwd
-// All forward forms are one kernel template, rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, FB, PMS>, the three sweeps one,
-// rollout_open_bwd_kernel<FB, PMS>.  The host path is the same for every entry point: checks (rollout_common.h: model_within_limits,
+//   integral feedback  mcp_rollout_pid          either feedback form with a clamped integral of the position error in the law (struct
+//                                               OpenArgsPid); mcp_rollout_pid_bwd
+// All forward forms are one kernel template, rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, FB, PMS, PID>, the sweeps one,
+// rollout_open_bwd_kernel<FB, PMS, PID>.  The host path is the same for every entry point: checks (rollout_common.h: model_within_limits,
 // model_ok / model_lists_ok, meas_model_check -- for the closed loops in closed_loop_checks' one order; here: pd_policy_check), one fill of
 // the arguments' base part per direction (open_fill, open_bwd_fill over sweep_fill_model), one ladder of tiles (launch_open_tiles) -- a refused call makes no HIP call.
 //
@@ -45,6 +47,8 @@
 // jac for that trajectory alone) and MCP_STATUS_NONPOS_VAR is raised.  Rows of jac from len - 1 on are NEVER WRITTEN and never read.
 // The arguments' base part (OpenArgs, open_fill), the LDS layout (open_layout) and phases K, V, J, J' are in rollout_open_phases.h: model_step.hip
 // runs the same step, one per launch, and rollout_mlp.hip the same loop under the tanh-MLP policy.
+#include <type_traits>
+
 #include "rollout_open_phases.h"
 
 using namespace mcp;
@@ -72,22 +76,40 @@ struct OpenArgsPd : OpenArgs {
 struct OpenArgsPdMeas : OpenArgsPd {
   mcp_meas ms;
 };
-template <bool FB, bool PMS = false>
+// INTEGRAL form (template PID with FB, with or without PMS, mcp_rollout_pid): the law gains a clamped integral of the position error, the
+// first control here that depends on controller state carried across the steps (the reference has no such law: this replaces a stateful
+// torch policy in the loop of MC_PILCO.apply_policy, policy_learning/MC_PILCO.py:615-674, measured: :856-899).  With e as above (on y_t in
+// the measured form), p = pos[k], I_{-1} = 0:
+//   q_t = I_{t-1}[k] + dt e[p];   I_t[k] = min(max(q_t, -i_max[k]), +i_max[k]);   a_k = (sqrt_kp[k]^2 e[p] + sqrt_kd[k]^2 e[vel[k]]) + sqrt_ki[k]^2 I_t[k]
+// The input thread (up, uk) keeps I in a register across the step loop, forms it from the row it already reads behind the barrier the
+// feedback form already has, and stores it to pid.integ [T][M][U] beside inputs (the sweep reads it and never re-decides a clamp).  The PD
+// products stay the PD form's expression and the integral product is added last: sqrt_ki == 0 reproduces the PD launch bit for bit.  The
+// clamp is written as two comparisons: a NaN passes through, as through torch.clamp.
+template <bool PMS>
+struct OpenArgsPid : std::conditional<PMS, OpenArgsPdMeas, OpenArgsPd>::type {
+  mcp_pid_term pid;
+};
+template <bool FB, bool PMS = false, bool PID = false>
 struct OpenArgsOf {
   typedef OpenArgs type;
 };
 template <>
-struct OpenArgsOf<true, false> {
+struct OpenArgsOf<true, false, false> {
   typedef OpenArgsPd type;
 };
 template <>
-struct OpenArgsOf<true, true> {
+struct OpenArgsOf<true, true, false> {
   typedef OpenArgsPdMeas type;
 };
+template <bool PMS>
+struct OpenArgsOf<true, PMS, true> {
+  typedef OpenArgsPid<PMS> type;
+};
 
-template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool FB = false, bool PMS = false>
-__global__ __launch_bounds__(RF_NT) void rollout_open_kernel(typename OpenArgsOf<FB, PMS>::type a) {
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool FB = false, bool PMS = false, bool PID = false>
+__global__ __launch_bounds__(RF_NT) void rollout_open_kernel(typename OpenArgsOf<FB, PMS, PID>::type a) {
   static_assert(FB || !PMS, "the measurement model belongs to the feedback form");
+  static_assert(FB || !PID, "the integral term belongs to the feedback form");
   extern __shared__ double smem[];
   const mcp_model& md = a.model;
   const int S = md.S, U = md.U, G = md.G, D = md.D, M = a.M, T = a.T;
@@ -163,6 +185,16 @@ __global__ __launch_bounds__(RF_NT) void rollout_open_kernel(typename OpenArgsOf
       ivel = a.pd.vel[uk];
     }
   }
+  // integral form: the squared gain, the bound, the step and the integral of input uk (I_{-1} = 0)
+  double ki2 = 0.0, imax = 0.0, idt = 0.0, integ = 0.0;
+  if constexpr (PID) {
+    if (isu) {
+      const double ki = a.pid.sqrt_ki[uk];
+      ki2 = ki * ki;
+      imax = a.pid.i_max[uk];
+      idt = a.pid.dt;
+    }
+  }
   // measured feedback form: the pair of this state component (pm_pos: it is the pair's position and carries the filter; pm_vel: it is
   // the pair's velocity and leaves its slot of the measurement row to the position's thread)
   int pm_pos = -1, pm_vel = -1, pm_vc = 0;
@@ -225,7 +257,13 @@ __global__ __launch_bounds__(RF_NT) void rollout_open_kernel(typename OpenArgsOf
       if (isu) {
         const double* xr = PMS ? smem + L.ym + up * S : xs + cur * PT * S + up * S;
         const double* tg = a.pd.target_traj + (size_t)t * S;
-        const double av = kp2 * (tg[ipos] - xr[ipos]) + kd2 * (tg[ivel] - xr[ivel]);
+        double av = kp2 * (tg[ipos] - xr[ipos]) + kd2 * (tg[ivel] - xr[ivel]);
+        if constexpr (PID) {
+          const double q = integ + idt * (tg[ipos] - xr[ipos]);
+          integ = q < -imax ? -imax : (q > imax ? imax : q);
+          av = av + ki2 * integ;
+          if (ovalid) a.pid.integ[((size_t)t * M + m0 + up) * U + uk] = integ;
+        }
         ufb = a.pd.squash ? umax * fast_tanh(av / umax) : av;
         if (ovalid) {
           a.inputs[((size_t)t * M + m0 + up) * U + uk] = ufb;
@@ -344,38 +382,38 @@ __global__ __launch_bounds__(RF_NT) void rollout_open_kernel(typename OpenArgsOf
 // ---- host path of the forward entry points: checks -> fill -> ladder -----------------------------------------------------------------
 // (an entry checks its own pointers and sizes, then the limits, the model, its descriptors -- every refusal before any HIP call --, fills
 // the base part of the arguments with open_fill, adds what is its own and hands them to the one ladder of tiles, launch_open_tiles)
-template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool FB, bool PMS>
-static int launch_open(const typename OpenArgsOf<FB, PMS>::type& a, hipStream_t st) {
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool FB, bool PMS, bool PID>
+static int launch_open(const typename OpenArgsOf<FB, PMS, PID>::type& a, hipStream_t st) {
   const OpenLayout L = open_layout(PT, NEEDVAR, a.model.S, a.model.D, a.model.G, a.NpadMax, NEEDJAC, a.na, PMS);
   const size_t lds = (size_t)L.total * sizeof(double);
   if (lds > MCP_LDS_LIMIT) return MCP_ERR_LIMIT;
-  MCP_ENSURE_MAX_LDS((rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, FB, PMS>));
-  hipLaunchKernelGGL((rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, FB, PMS>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
+  MCP_ENSURE_MAX_LDS((rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, FB, PMS, PID>));
+  hipLaunchKernelGGL((rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, FB, PMS, PID>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
 }
-template <int PT, bool NEEDVAR, bool NEEDJAC, bool FB, bool PMS>
-static int launch_open_deg(const typename OpenArgsOf<FB, PMS>::type& a, int maxdeg, hipStream_t st) {
-  return maxdeg == 0 ? launch_open<PT, 0, NEEDVAR, NEEDJAC, FB, PMS>(a, st) : launch_open<PT, 2, NEEDVAR, NEEDJAC, FB, PMS>(a, st);
+template <int PT, bool NEEDVAR, bool NEEDJAC, bool FB, bool PMS, bool PID>
+static int launch_open_deg(const typename OpenArgsOf<FB, PMS, PID>::type& a, int maxdeg, hipStream_t st) {
+  return maxdeg == 0 ? launch_open<PT, 0, NEEDVAR, NEEDJAC, FB, PMS, PID>(a, st) : launch_open<PT, 2, NEEDVAR, NEEDJAC, FB, PMS, PID>(a, st);
 }
-// The ladder of tiles, the same for every form (the feedback adds nothing to the LDS layout, the measurement one row [PT][S]); a.jac: the
+// The ladder of tiles, the same for every form (the feedback and its integral add nothing to the LDS layout, the measurement one row [PT][S]); a.jac: the
 // recording form.  The mean chain (no sampling, no variance asked for) touches no Kinv: one trajectory per workgroup.  With a variance:
 //   no record  16 trajectories per workgroup, 4 where the k panel of 16 does not fit (at every compiled limit at once -- S = 16, D = 32, G = 8,
 //              Npad = 4096 -- that layout takes 148 KB of the 160, so nothing within MCP_MAX_* is refused)
 //   record     two panels: 16 up to Npad ~ 500, 4 up to ~ 2000, beyond that one (at every compiled limit at once: 2 x 32 KB of panels, 85 KB
 //              in all; the recording mean chain: 85 KB, X^T then stays in global memory)
-template <bool FB, bool PMS>
-static int launch_open_tiles(const typename OpenArgsOf<FB, PMS>::type& a, int maxdeg, bool wantvar, hipStream_t st) {
+template <bool FB, bool PMS, bool PID = false>
+static int launch_open_tiles(const typename OpenArgsOf<FB, PMS, PID>::type& a, int maxdeg, bool wantvar, hipStream_t st) {
   if (!a.jac) {
-    if (!a.sample && !wantvar) return launch_open_deg<1, false, false, FB, PMS>(a, maxdeg, st);
-    int rc = launch_open_deg<16, true, false, FB, PMS>(a, maxdeg, st);
-    if (rc == MCP_ERR_LIMIT) rc = launch_open_deg<4, true, false, FB, PMS>(a, maxdeg, st);
+    if (!a.sample && !wantvar) return launch_open_deg<1, false, false, FB, PMS, PID>(a, maxdeg, st);
+    int rc = launch_open_deg<16, true, false, FB, PMS, PID>(a, maxdeg, st);
+    if (rc == MCP_ERR_LIMIT) rc = launch_open_deg<4, true, false, FB, PMS, PID>(a, maxdeg, st);
     return rc;
   }
-  if (!a.sample && !wantvar) return launch_open_deg<1, false, true, FB, PMS>(a, maxdeg, st);
-  int rc = launch_open_deg<16, true, true, FB, PMS>(a, maxdeg, st);
-  if (rc == MCP_ERR_LIMIT) rc = launch_open_deg<4, true, true, FB, PMS>(a, maxdeg, st);
-  if (rc == MCP_ERR_LIMIT) rc = launch_open_deg<1, true, true, FB, PMS>(a, maxdeg, st);
+  if (!a.sample && !wantvar) return launch_open_deg<1, false, true, FB, PMS, PID>(a, maxdeg, st);
+  int rc = launch_open_deg<16, true, true, FB, PMS, PID>(a, maxdeg, st);
+  if (rc == MCP_ERR_LIMIT) rc = launch_open_deg<4, true, true, FB, PMS, PID>(a, maxdeg, st);
+  if (rc == MCP_ERR_LIMIT) rc = launch_open_deg<1, true, true, FB, PMS, PID>(a, maxdeg, st);
   return rc;
 }
 
@@ -419,13 +457,35 @@ static int pd_policy_check(const mcp_model* model, const mcp_pd_policy* pd, int 
   return MCP_OK;
 }
 
+// the integral term (host fields and the two pointers), looked at behind every check of the PD entries.  pid NULL or on == 0: no term
+static inline bool pid_active(const mcp_pid_term* pid) { return pid && pid->on != 0; }
+static int pid_term_check(const mcp_pid_term* pid, int U) {
+  if (!pid_active(pid)) return MCP_OK;
+  if (!pid->sqrt_ki || !pid->integ) return MCP_ERR_ARG;
+  if (!(pid->dt > 0.0)) return MCP_ERR_ARG;  // (a NaN is refused too)
+  for (int k = 0; k < U; ++k)
+    if (!(pid->i_max[k] > 0.0)) return MCP_ERR_ARG;  // (+inf: no clamp)
+  return MCP_OK;
+}
+// the arguments of an integral form: those of the feedback form it extends, and the term
+template <class PidArgs, class Args>
+static PidArgs pd_with_pid(const Args& a, const mcp_pid_term* pid) {
+  PidArgs d;
+  static_cast<Args&>(d) = a;
+  d.pid = *pid;
+  return d;
+}
+
 // Closed-loop rollout under the PD law: replaces the loop of MC_PILCO.apply_policy (policy_learning/MC_PILCO.py:615-674) with
 // Policy.PD_controller.forward (policy_learning/Policy.py:437-449) as the policy, over Model_learning.get_next_state
 // (model_learning/Model_learning.py:210-229, 471-494, 685-718).  jac != NULL: the recording form (what autograd would keep of that loop).
+// pid (NULL or on == 0: none): the integral forms of the same kernels.
 static int pd_dispatch(const mcp_model* model, const mcp_pd_policy* pd, const mcp_meas* ms, const mcp_noise* noise, int M, int T, int particle_pred,
-                       const double* x0, double* states, double* inputs, double* jac, double* mu, double* var, uint32_t* status, void* stream) {
-  const int crc = closed_loop_checks(model && pd && noise && x0 && states && inputs && status, M, T, model, ms, false,
-                                     [&] { return pd_policy_check(model, pd, T); });
+                       const double* x0, double* states, double* inputs, double* jac, double* mu, double* var, uint32_t* status, void* stream,
+                       const mcp_pid_term* pid = nullptr) {
+  int crc = closed_loop_checks(model && pd && noise && x0 && states && inputs && status, M, T, model, ms, false,
+                               [&] { return pd_policy_check(model, pd, T); });
+  if (crc == MCP_OK) crc = pid_term_check(pid, pd->U);
   if (crc != MCP_OK) return crc;
   OpenArgsPdMeas a;
   // (T == 1: the policy alone -- no transition, nothing to record)
@@ -433,6 +493,11 @@ static int pd_dispatch(const mcp_model* model, const mcp_pd_policy* pd, const mc
   a.pd = *pd;
   a.inputs = inputs;
   hipStream_t st = (hipStream_t)stream;
+  if (pid_active(pid)) {
+    if (!meas_active(ms)) return launch_open_tiles<true, false, true>(pd_with_pid<OpenArgsPid<false>, OpenArgsPd>(a, pid), maxdeg, var != nullptr, st);
+    a.ms = *ms;
+    return launch_open_tiles<true, true, true>(pd_with_pid<OpenArgsPid<true>, OpenArgsPdMeas>(a, pid), maxdeg, var != nullptr, st);
+  }
   if (!meas_active(ms)) return launch_open_tiles<true, false>(a, maxdeg, var != nullptr, st);  // (the base part of `a`: mcp_rollout_pd's own kernels)
   a.ms = *ms;
   return launch_open_tiles<true, true>(a, maxdeg, var != nullptr, st);
@@ -453,6 +518,17 @@ extern "C" int mcp_rollout_pd_meas(const mcp_model* model, const mcp_pd_policy* 
                                    uint32_t* status, void* stream) {
   if (!meas) return MCP_ERR_ARG;
   return pd_dispatch(model, pd, meas, noise, M, T, particle_pred, x0, states, inputs, jac, mu, var, status, stream);
+}
+
+// Closed-loop rollout under the PD law with the integral term (mcp_pid_term; the law and its clamp: OpenArgsPid above), on the true state
+// (meas NULL or n == 0) or on the simulated measurement: replaces a stateful torch policy in the loop of MC_PILCO.apply_policy
+// (policy_learning/MC_PILCO.py:615-674) or MC_PILCO4PMS.apply_policy (:808-906) over Model_learning.get_next_state
+// (model_learning/Model_learning.py:210-229, 471-494, 685-718) -- the reference has no integral law.  pid NULL or on == 0: mcp_rollout_pd /
+// mcp_rollout_pd_meas on the same arguments.
+extern "C" int mcp_rollout_pid(const mcp_model* model, const mcp_pd_policy* pd, const mcp_pid_term* pid, const mcp_meas* meas, const mcp_noise* noise,
+                               int M, int T, int particle_pred, const double* x0, double* states, double* inputs, double* jac, double* mu,
+                               double* var, uint32_t* status, void* stream) {
+  return pd_dispatch(model, pd, meas, noise, M, T, particle_pred, x0, states, inputs, jac, mu, var, status, stream, pid);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -510,17 +586,32 @@ struct OpenBwdArgsPd : OpenBwdArgs {
 struct OpenBwdArgsPdMeas : OpenBwdArgsPd {
   mcp_meas ms;
 };
-template <bool FB, bool PMS = false>
+// INTEGRAL form of the sweep (template PID with FB, with or without PMS, mcp_rollout_pid_bwd): I_r feeds a_r and I_{r+1}, so its adjoint
+// is a carry c down the rows, one double per (trajectory, input), zero behind the last row, in the registers of the chain lane that
+// keeps that input's gain sums.  Per row r, in stage B' behind abar (I_r: pid.integ, brought by the loader like inputs[r]):
+//   Ibar_k = sqrt_ki[k]^2 abar_k + c_k;   c_k = (|I_r[k]| < i_max[k]) ? Ibar_k : 0;   g_sqrt_ki[k] += 2 sqrt_ki[k] I_r[k] abar_k
+// (the clamp passes gradient iff I_r sits strictly inside its bounds; the forward's stored I decides, never a recomputation), and in
+// stage C beside the proportional pull:  lambda[pos[k]] -= dt c_k  (measured form: on ybar[pos[k]], through the filter adjoint unchanged).
+// The lane leaves c_k to stage C in the slot of the integral's row buffer it has just read.  g_gains is [M][3][U]: kp | kd | ki.
+template <bool PMS>
+struct OpenBwdArgsPid : std::conditional<PMS, OpenBwdArgsPdMeas, OpenBwdArgsPd>::type {
+  mcp_pid_term pid;
+};
+template <bool FB, bool PMS = false, bool PID = false>
 struct OpenBwdArgsOf {
   typedef OpenBwdArgs type;
 };
 template <>
-struct OpenBwdArgsOf<true, false> {
+struct OpenBwdArgsOf<true, false, false> {
   typedef OpenBwdArgsPd type;
 };
 template <>
-struct OpenBwdArgsOf<true, true> {
+struct OpenBwdArgsOf<true, true, false> {
   typedef OpenBwdArgsPdMeas type;
+};
+template <bool PMS>
+struct OpenBwdArgsOf<true, PMS, true> {
+  typedef OpenBwdArgsPid<PMS> type;
 };
 #define OB_KMAX ((MCP_MAX_INPUT + 3) / 4)  // inputs per lane of the chain wave
 
@@ -529,8 +620,9 @@ struct OpenBwdLayout {
   int rp;                                    // pitch of a trajectory's record row (odd: bank spread)
   int ul, gul, tgl, abl, ktab, gnl;          // feedback form: inputs | g_inputs | target row (double buffers) | abar | kpos, kvel | gains^2
   int yml, car, mtab;                        // measured feedback form: measurement rows (double buffer) | the filter's carries | pvel, ppos
+  int itl, gil;                              // integral form: the integral's rows (double buffer; stage B' leaves the carry there) | sqrt_ki^2, i_max
 };
-__host__ __device__ inline OpenBwdLayout open_bwd_layout(int S, int G, int D, bool fb = false, int U = 0, bool pms = false) {
+__host__ __device__ inline OpenBwdLayout open_bwd_layout(int S, int G, int D, bool fb = false, int U = 0, bool pms = false, bool pid = false) {
   OpenBwdLayout L;
   int o = 0;
   auto take = [&](int n) {
@@ -555,17 +647,20 @@ __host__ __device__ inline OpenBwdLayout open_bwd_layout(int S, int G, int D, bo
   L.yml = pms ? take(2 * OB_PT * S) : 0;
   L.car = pms ? take(2 * OB_PT * S) : 0;     // [trajectory][position component]: mvbar | nvbar of the row behind
   L.mtab = pms ? take(MCP_MAX_STATE) : 0;    // ints: pvel (per state component: the velocity of the pair it is the position of, or -1) | ppos (the converse)
+  L.itl = pid ? take(2 * OB_PT * U) : 0;
+  L.gil = pid ? take(2 * MCP_MAX_INPUT) : 0;  // the gain table's second half: sqrt_ki^2 | i_max
   L.total = o;
   return L;
 }
 
-template <bool FB, bool PMS = false>
-__global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBwdArgsOf<FB, PMS>::type a) {
+template <bool FB, bool PMS = false, bool PID = false>
+__global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBwdArgsOf<FB, PMS, PID>::type a) {
   static_assert(FB || !PMS, "the measurement model belongs to the feedback form");
+  static_assert(FB || !PID, "the integral term belongs to the feedback form");
   extern __shared__ double smem[];
   const int S = a.S, U = a.U, G = a.G, D = a.D, M = a.M, T = a.T, nna = a.nna, na = a.na;
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const OpenBwdLayout L = open_bwd_layout(S, G, D, FB, U, PMS);
+  const OpenBwdLayout L = open_bwd_layout(S, G, D, FB, U, PMS, PID);
   const int GD = G * D, RP = L.rp;
   double* rec = smem + L.rec;
   double* xsl = smem + L.xs;
@@ -590,6 +685,8 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
   double* car = smem + L.car;
   int* pvel = reinterpret_cast<int*>(smem + L.mtab);
   int* ppos = pvel + MCP_MAX_STATE;
+  double* itl = smem + L.itl;  // (integral form)
+  double* gil = smem + L.gil;
   const int m0 = blockIdx.x * OB_PT;
 
   if (tid < S) {  // which GP a component integrates, as the forward kernel decides it
@@ -633,6 +730,11 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
       const double kp = a.pd.sqrt_kp[k], kd = a.pd.sqrt_kd[k];
       gnl[k] = kp * kp;
       gnl[MCP_MAX_INPUT + k] = kd * kd;
+      if constexpr (PID) {
+        const double ki = a.pid.sqrt_ki[k];
+        gil[k] = ki * ki;
+        gil[MCP_MAX_INPUT + k] = a.pid.i_max[k];
+      }
     }
   }
   if (tid >= 64 && tid < 64 + OB_PT) {
@@ -672,6 +774,7 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
         if (r <= lenl[p] - 1) {
           ull[(b * OB_PT + p) * U + k] = a.inputs[((size_t)r * M + m0 + p) * U + k];
           gul[(b * OB_PT + p) * U + k] = a.g_inputs ? a.g_inputs[((size_t)r * M + m0 + p) * U + k] : 0.0;
+          if constexpr (PID) itl[(b * OB_PT + p) * U + k] = a.pid.integ[((size_t)r * M + m0 + p) * U + k];
         }
       }
       for (int s = l; s < S; s += 64) tgl[b * S + s] = a.pd.target_traj[(size_t)r * S + s];
@@ -696,6 +799,16 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
       fpos[i] = k < U ? a.pd.pos[k] : 0;
       fvel[i] = k < U ? a.pd.vel[k] : 0;
       gkp[i] = gkd[i] = 0.0;
+    }
+  }
+  // integral form: sqrt_ki of the same inputs, the sums of its gradient and the carry c (zero behind the last row)
+  double fki[OB_KMAX], gki[OB_KMAX], cin[OB_KMAX];
+  if constexpr (PID) {
+#pragma unroll
+    for (int i = 0; i < OB_KMAX; ++i) {
+      const int k = (lane >> 4) + 4 * i;
+      fki[i] = k < U ? a.pid.sqrt_ki[k] : 0.0;
+      gki[i] = cin[i] = 0.0;
     }
   }
   if (wv == 1) load_row(tl - 1, 0, lane);
@@ -748,6 +861,14 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
               abl[p * U + k] = ab;
               gkp[i] += 2.0 * fkp[i] * (tg[fpos[i]] - ec[fpos[i]]) * ab;
               gkd[i] += 2.0 * fkd[i] * (tg[fvel[i]] - ec[fvel[i]]) * ab;
+              if constexpr (PID) {
+                double* ir = itl + (b * OB_PT + p) * U + k;
+                const double iv = *ir;
+                const double ib = gil[k] * ab + cin[i];
+                cin[i] = fabs(iv) < gil[MCP_MAX_INPUT + k] ? ib : 0.0;
+                gki[i] += 2.0 * fki[i] * iv * ab;
+                *ir = cin[i];  // (to stage C)
+              }
             }
           }
         }
@@ -774,6 +895,8 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
           if (r <= len - 1) {
             const int kp = kpos[s], kv = kvel[s];
             if (kp >= 0) v -= gnl[kp] * abl[p * U + kp];
+            if constexpr (PID)
+              if (kp >= 0) v -= a.pid.dt * itl[(b * OB_PT + p) * U + kp];
             if (kv >= 0) v -= gnl[MCP_MAX_INPUT + kv] * abl[p * U + kv];
           }
         }
@@ -783,6 +906,8 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
               const int kp = kpos[c], kv = kvel[c];
               double y = 0.0;
               if (kp >= 0) y -= gnl[kp] * abl[p * U + kp];
+              if constexpr (PID)
+                if (kp >= 0) y -= a.pid.dt * itl[(b * OB_PT + p) * U + kp];
               if (kv >= 0) y -= gnl[MCP_MAX_INPUT + kv] * abl[p * U + kv];
               return y;
             };
@@ -829,8 +954,9 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
         for (int i = 0; i < OB_KMAX; ++i) {
           const int k = q + 4 * i;
           if (k < U) {
-            a.g_gains[((size_t)(m0 + p) * 2 + 0) * U + k] = gkp[i];
-            a.g_gains[((size_t)(m0 + p) * 2 + 1) * U + k] = gkd[i];
+            a.g_gains[((size_t)(m0 + p) * (PID ? 3 : 2) + 0) * U + k] = gkp[i];
+            a.g_gains[((size_t)(m0 + p) * (PID ? 3 : 2) + 1) * U + k] = gkd[i];
+            if constexpr (PID) a.g_gains[((size_t)(m0 + p) * 3 + 2) * U + k] = gki[i];
           }
         }
       }
@@ -850,14 +976,14 @@ static void open_bwd_fill(OpenBwdArgs& a, const mcp_model* model, int M, int T, 
   a.g_x0 = g_x0;
   a.g_u = g_u;
 }
-// (at every compiled limit at once the layout takes 72 KB, the feedback form 89 KB, the measured form 98 KB)
-template <bool FB, bool PMS>
-static int launch_open_bwd(const typename OpenBwdArgsOf<FB, PMS>::type& a, hipStream_t st) {
-  const OpenBwdLayout L = open_bwd_layout(a.S, a.G, a.D, FB, a.U, PMS);
+// (at every compiled limit at once the layout takes 72 KB, the feedback form 89 KB, the measured form 98 KB, the integral 2 KB more)
+template <bool FB, bool PMS, bool PID = false>
+static int launch_open_bwd(const typename OpenBwdArgsOf<FB, PMS, PID>::type& a, hipStream_t st) {
+  const OpenBwdLayout L = open_bwd_layout(a.S, a.G, a.D, FB, a.U, PMS, PID);
   const size_t lds = (size_t)L.total * sizeof(double);
   if (lds > MCP_LDS_LIMIT) return MCP_ERR_LIMIT;
-  MCP_ENSURE_MAX_LDS((rollout_open_bwd_kernel<FB, PMS>));
-  hipLaunchKernelGGL((rollout_open_bwd_kernel<FB, PMS>), dim3((a.M + OB_PT - 1) / OB_PT), dim3(OB_NT), lds, st, a);
+  MCP_ENSURE_MAX_LDS((rollout_open_bwd_kernel<FB, PMS, PID>));
+  hipLaunchKernelGGL((rollout_open_bwd_kernel<FB, PMS, PID>), dim3((a.M + OB_PT - 1) / OB_PT), dim3(OB_NT), lds, st, a);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
 }
@@ -880,9 +1006,10 @@ extern "C" int mcp_rollout_open_bwd(const mcp_model* model, int M, int T, const 
 // get_next_state with its integrators (model_learning/Model_learning.py:210-229, 471-494, 685-718), from the record alone.
 static int pd_bwd_dispatch(const mcp_model* model, const mcp_pd_policy* pd, const mcp_meas* ms, int M, int T, const double* states,
                            const double* inputs, const double* jac, const double* g_states, const double* g_inputs, double* g_gains, double* g_x0,
-                           void* stream) {
-  const int crc = closed_loop_checks(model && pd && states && inputs && g_states && (jac || T <= 1), M, T, model, ms, true,
-                                     [&] { return pd_policy_check(model, pd, T); });
+                           void* stream, const mcp_pid_term* pid = nullptr) {
+  int crc = closed_loop_checks(model && pd && states && inputs && g_states && (jac || T <= 1), M, T, model, ms, true,
+                               [&] { return pd_policy_check(model, pd, T); });
+  if (crc == MCP_OK) crc = pid_term_check(pid, pd->U);
   if (crc != MCP_OK) return crc;
   if (!g_x0 && !g_gains) return MCP_OK;  // nothing asked for
   OpenBwdArgsPdMeas a;
@@ -893,6 +1020,11 @@ static int pd_bwd_dispatch(const mcp_model* model, const mcp_pd_policy* pd, cons
   a.g_inputs = g_inputs;
   a.g_gains = g_gains;
   hipStream_t st = (hipStream_t)stream;
+  if (pid_active(pid)) {
+    if (!meas_active(ms)) return launch_open_bwd<true, false, true>(pd_with_pid<OpenBwdArgsPid<false>, OpenBwdArgsPd>(a, pid), st);
+    a.ms = *ms;
+    return launch_open_bwd<true, true, true>(pd_with_pid<OpenBwdArgsPid<true>, OpenBwdArgsPdMeas>(a, pid), st);
+  }
   if (meas_active(ms)) {
     a.ms = *ms;
     return launch_open_bwd<true, true>(a, st);
@@ -915,4 +1047,13 @@ extern "C" int mcp_rollout_pd_meas_bwd(const mcp_model* model, const mcp_pd_poli
                                        double* g_x0, void* stream) {
   if (!meas) return MCP_ERR_ARG;
   return pd_bwd_dispatch(model, pd, meas, M, T, states, inputs, jac, g_states, g_inputs, g_gains, g_x0, stream);
+}
+
+// Reverse-time sweep of mcp_rollout_pid (the carry of the integral's adjoint: OpenBwdArgsPid above): replaces autograd's backward
+// (MC_PILCO.py:522) through the same loops with a stateful torch policy in them.  g_gains [M][3][U].  pid NULL or on == 0:
+// mcp_rollout_pd_bwd / mcp_rollout_pd_meas_bwd on the same arguments (g_gains [M][2][U]).
+extern "C" int mcp_rollout_pid_bwd(const mcp_model* model, const mcp_pd_policy* pd, const mcp_pid_term* pid, const mcp_meas* meas, int M, int T,
+                                   const double* states, const double* inputs, const double* jac, const double* g_states, const double* g_inputs,
+                                   double* g_gains, double* g_x0, void* stream) {
+  return pd_bwd_dispatch(model, pd, meas, M, T, states, inputs, jac, g_states, g_inputs, g_gains, g_x0, stream, pid);
 }

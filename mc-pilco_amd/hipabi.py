@@ -86,6 +86,13 @@ class MLPResidual(C.Structure):
                 ("target", dptr), ("rows", C.c_int32)]
 
 
+class PIDTerm(C.Structure):
+    """mcp_pid_term: the clamped integral I_t = clamp(I_{t-1} + dt e[pos[k]], +-i_max[k]) of the position error and its product
+    sqrt_ki[k]^2 I_t[k] behind the PD law's two, of the integral entries (on == 0: none); integ [T][M][U] is written by the rollout and read
+    by the sweep."""
+    _fields_ = [("on", C.c_int32), ("sqrt_ki", dptr), ("i_max", C.c_double * MAX_INPUT), ("dt", C.c_double), ("integ", dptr)]
+
+
 class OptState(C.Structure):
     _fields_ = [("step", C.c_int64), ("attempt", C.c_int64), ("pending", C.c_int64), ("adam_t", C.c_int64), ("total_attempts", C.c_int64),
                 ("es2", C.c_double), ("cost_prev", C.c_double)]
@@ -189,6 +196,10 @@ _SIGS = {
                                       dptr, dptr, dptr, dptr, dptr, dptr]),
     "mcp_rollout_pd_meas_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(PDPolicy), C.POINTER(Meas), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr,
                                           dptr, dptr]),
+    "mcp_rollout_pid": (C.c_int, [C.POINTER(Model), C.POINTER(PDPolicy), C.POINTER(PIDTerm), C.POINTER(Meas), C.POINTER(Noise), C.c_int, C.c_int,
+                                  C.c_int, dptr, dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
+    "mcp_rollout_pid_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(PDPolicy), C.POINTER(PIDTerm), C.POINTER(Meas), C.c_int, C.c_int, dptr, dptr, dptr,
+                                      dptr, dptr, dptr, dptr, dptr]),
     "mcp_rollout_mlp_meas": (C.c_int, [C.POINTER(Model), C.POINTER(MLPPolicy), C.POINTER(Meas), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr,
                                        dptr, dptr, dptr, dptr, dptr, dptr]),
     "mcp_rollout_mlp_meas_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(MLPPolicy), C.POINTER(Meas), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr,

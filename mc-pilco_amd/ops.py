@@ -668,6 +668,9 @@ def model_step(model: PackedModel, x, u, t, noise: Optional[NoiseSpec] = None, p
 #                  and the track itself -- None: the policy has no target, and the calls are the ones above
 #   fwd_res, bwd_res, res_c()   (a policy that can carry a PD term) the entries that take an mcp_mlp_pd behind the track, and the term itself --
 #                  None: the policy has none, and the calls are the ones above
+#   fwd_pid, bwd_pid, term_c(integ)   (a policy with the integral term) the ONE pair of entries that take an mcp_pid_term behind the policy and
+#                  a measurement model or NULL behind that, and the term over a launch's buffer ``integ`` [T,M,U] -- which the launch
+#                  allocates, leaves in ``packed.integ`` and the Function saves for the sweep like the measurement buffer
 #   check(model, T)   the policy's own refusals
 class PackedPD:
     """mcp_pd_policy of a ``Policy.PD_controller`` (reference policy_learning/Policy.py:406-449): the two gain parameters are kept as they
@@ -726,6 +729,54 @@ class PackedPD:
             c.pos[k], c.vel[k], c.u_max[k] = self.pos[k], self.vel[k], float(self.u_max[k])
         c.sqrt_kp, c.sqrt_kd = kp.data_ptr(), kd.data_ptr()
         c.target_traj, c.target_rows = self.target_traj.data_ptr(), int(self.target_traj.shape[0])
+        return c
+
+
+class PackedPID(PackedPD):
+    """mcp_pd_policy and mcp_pid_term of a ``Policy.PID_controller``: PackedPD with the third gain parameter ``sqrt_Ki_gains`` behind the two,
+    the step ``dt`` (the class passes T_sampling) and the bound ``i_max`` of the integral per input (inf: no clamp).  ``integ`` is the
+    integral I [T,M,U] of the LAST launch made through this object (not differentiable; the recording launch's is saved with the record)."""
+
+    fwd_pid, bwd_pid = "mcp_rollout_pid", "mcp_rollout_pid_bwd"
+
+    def __init__(self, policy):
+        super().__init__(policy)
+        self.sqrt_ki = policy.sqrt_Ki_gains
+        self.params = [self.sqrt_kp, self.sqrt_kd, self.sqrt_ki]
+        self.shapes, self.grad_shape = [(self.U,)] * 3, (3, self.U)
+        self.dt = float(policy.T_sampling)
+        im = policy.i_max
+        self.i_max = np.full(self.U, np.inf if im is None else float(im)) if (im is None or np.isscalar(im)) else np.asarray(im, dtype=np.float64).reshape(-1)
+        if self.i_max.size != self.U:
+            raise RuntimeError("i_max must be None, a scalar or hold one bound per input")
+        if not self.dt > 0.0 or not bool(np.all(self.i_max > 0.0)):
+            raise RuntimeError("the integral term needs T_sampling > 0 and every i_max > 0 (inf: no clamp)")
+        self.integ = None
+
+    def gains(self):
+        """(sqrt_kp, sqrt_kd, sqrt_ki) as [U] tensors on the autograd graph of the parameters, as PackedPD.gains has the two."""
+        g = self.sqrt_ki.reshape(-1)
+        if g.numel() == 1 and self.U > 1:
+            g = g.expand(self.U)
+        if g.numel() != self.U:
+            raise RuntimeError("the PID gains must hold one value per input (or one for all)")
+        return super().gains() + [g]
+
+    tensors = gains
+
+    def to_c(self, kp, kd, ki):
+        """The PD descriptor over (kp, kd); the integral gain of this launch is kept for ``term_c``."""
+        if ki.dtype != DT or not ki.is_cuda or not ki.is_contiguous() or ki.numel() != self.U:
+            raise RuntimeError("the PID gains must be contiguous float64 GPU tensors with one value per input")
+        self._ki = ki
+        return super().to_c(kp, kd)
+
+    def term_c(self, integ):
+        """The mcp_pid_term over the integral gain handed to ``to_c`` and the buffer ``integ`` [T,M,U]."""
+        c = abi.PIDTerm()
+        c.on, c.sqrt_ki, c.dt, c.integ = 1, self._ki.data_ptr(), self.dt, integ.data_ptr()
+        for k in range(self.U):
+            c.i_max[k] = float(self.i_max[k])
         return c
 
 
@@ -863,10 +914,13 @@ def _drop_args(meas_arg, nz, p_drop):
     return [meas_arg[0] if meas_arg else None, None if nz is None else C.byref(nz), float(p_drop)]
 
 
-def _entry(packed, names, plain, marg, nz, p_drop):
+def _entry(packed, names, plain, marg, nz, p_drop, integ=None):
     """(name, arguments between the policy and the sizes) of the launch or sweep of ``packed``, ``names`` = (plain and measured, dropout,
-    track, residual): a policy with the PD term (PackedMLP.res_c) takes its residual entry whatever the rest is; a policy with a track takes its track entry (the track, then the dropout entry's arguments) whatever ``marg`` and ``p_drop``
+    track, residual, integral): a policy with the integral term (PackedPID.term_c, ``integ`` its buffer) takes its one entry -- the term, the
+    measurement or NULL, then ``plain``; a policy with the PD term (PackedMLP.res_c) takes its residual entry whatever the rest is; a policy with a track takes its track entry (the track, then the dropout entry's arguments) whatever ``marg`` and ``p_drop``
     are; else p_drop > 0 the dropout entry; else the plain or measured one with ``plain`` behind the measurement."""
+    if integ is not None:
+        return names[4], [C.byref(packed.term_c(integ)), marg[0] if marg else None] + plain
     tc = packed.track_c() if names[2] else None
     rc = packed.res_c() if len(names) > 3 and names[3] else None
     if rc is not None:  # (the PD term: the track or NULL, the term, then the dropout entry's arguments)
@@ -882,7 +936,8 @@ def _closed_launch(model, packed, tensors, noise, x0, T, particle_pred, status, 
     """(states [T,M,S], inputs [T,M,U], jac or None) of ONE launch of the closed loop under ``packed`` over its parameter ``tensors``
     (packed.fwd); ``record`` and T > 1: the recording form.  With ``meas`` the measured entry, which writes ``meas.measured`` [T,M,S].
     ``p_drop`` > 0: the policy's dropout entry (packed.fwd_drop), whatever ``meas`` is.  A packed policy with a track (PackedMLP.track_c):
-    its track entry (packed.fwd_track), whatever ``meas`` and ``p_drop`` are; without one exactly the calls above."""
+    its track entry (packed.fwd_track), whatever ``meas`` and ``p_drop`` are; without one exactly the calls above.  A packed policy with the
+    integral term (PackedPID): its entry (packed.fwd_pid), which writes ``packed.integ`` [T,M,U]."""
     M, dev = int(x0.shape[0]), model.device
     states, inputs, jac = _record_buffers(dev, T, M, model.S, model.U, model.G, model.D, record and T > 1)
     pc, nz = packed.to_c(*tensors), noise.to_c()
@@ -891,8 +946,11 @@ def _closed_launch(model, packed, tensors, noise, x0, T, particle_pred, status, 
         meas_buf = meas.measured = torch.empty(T, M, model.S, dtype=DT, device=dev)  # (allocated as rollout_forward_raw allocates it)
     outputs = {"jac": jac, "mu": None, "var": None}
     marg = _meas_arg(meas, T, M, meas_buf)
+    integ = None
+    if getattr(packed, "fwd_pid", None):
+        integ = packed.integ = torch.empty(T, M, model.U, dtype=DT, device=dev)
     name, head = _entry(packed, (packed.fwd, getattr(packed, "fwd_drop", None), getattr(packed, "fwd_track", None),
-                                 getattr(packed, "fwd_res", None)), [C.byref(nz)], marg, nz, p_drop)
+                                 getattr(packed, "fwd_res", None), getattr(packed, "fwd_pid", None)), [C.byref(nz)], marg, nz, p_drop, integ)
     abi.check(getattr(abi.lib(), name)(_mc(model), C.byref(pc), *head, M, T,
                                        int(bool(particle_pred)), abi.ptr(x0), abi.ptr(states), abi.ptr(inputs),
                                        *[abi.ptr(outputs[k]) for k in packed.fwd_outputs], abi.ptr(status), abi.stream()), name)
@@ -900,11 +958,12 @@ def _closed_launch(model, packed, tensors, noise, x0, T, particle_pred, status, 
 
 
 def _closed_sweep(model, packed, tensors, states, inputs, jac, g_states, g_inputs, want_params, want_x0, meas=None, meas_buf=None, noise=None,
-                  p_drop=0.0):
+                  p_drop=0.0, integ=None):
     """(raw parameter gradients [ceil(M / grad_tile)] + grad_shape or None, g_x0 [M,S] or None) of ONE reverse-time sweep over the record
     (packed.bwd); with ``meas`` (and the measured states ``meas_buf`` its forward launch wrote) the measured entry.  ``p_drop`` > 0: the
     policy's dropout entry (packed.bwd_drop) with the forward launch's ``noise``, from which it recomputes the keep decisions.  A packed
-    policy with a track: packed.bwd_track, as in ``_closed_launch``."""
+    policy with a track: packed.bwd_track, as in ``_closed_launch``.  ``integ``: the integral the forward launch of a PackedPID wrote
+    (packed.bwd_pid)."""
     T, M, dev = int(states.shape[0]), int(states.shape[1]), states.device
     g_x0 = torch.empty(M, model.S, dtype=DT, device=dev) if want_x0 else None
     raw = torch.empty(((M + packed.grad_tile - 1) // packed.grad_tile,) + packed.grad_shape, dtype=DT, device=dev) if want_params else None
@@ -912,7 +971,7 @@ def _closed_sweep(model, packed, tensors, states, inputs, jac, g_states, g_input
     marg = _meas_arg(meas, T, M, meas_buf)
     nz = noise.to_c() if p_drop > 0.0 else None  # (only the keep decisions are drawn again)
     name, head = _entry(packed, (packed.bwd, getattr(packed, "bwd_drop", None), getattr(packed, "bwd_track", None),
-                                 getattr(packed, "bwd_res", None)), [], marg, nz, p_drop)
+                                 getattr(packed, "bwd_res", None), getattr(packed, "bwd_pid", None)), [], marg, nz, p_drop, integ)
     abi.check(getattr(abi.lib(), name)(_mc(model), C.byref(pc), *head, M, T, abi.ptr(states), abi.ptr(inputs),
                                        abi.ptr(jac), abi.ptr(g_states), abi.ptr(g_inputs), abi.ptr(raw), abi.ptr(g_x0), abi.stream()), name)
     return raw, g_x0
@@ -924,16 +983,20 @@ class RolloutClosedFunction(torch.autograd.Function):
     sweep's raw parameter gradients (per trajectory, or per workgroup) are added in torch's fixed order (``sum(0)``); the GP model is
     frozen.  With a measurement model (``meas``) the two launches are the measured entries; the measured states [T,M,S] the forward launch
     wrote (``meas.measured``) are saved with the record and handed to the sweep.  With dropout (``p_drop`` > 0) the launch's noise goes to
-    the sweep as well: the keep decisions are not recorded, the sweep draws them again."""
+    the sweep as well: the keep decisions are not recorded, the sweep draws them again.  Under a PackedPID the integral [T,M,U] the forward
+    launch wrote (``packed.integ``) is saved with the record too."""
 
     @staticmethod
     def forward(ctx, model, packed, noise, T, particle_pred, status, meas, p_drop, x0, *tensors):
         states, inputs, jac = _closed_launch(model, packed, tensors, noise, x0, T, particle_pred, status, True, meas, p_drop)
         ctx.model, ctx.packed, ctx.has_jac, ctx.meas = model, packed, jac is not None, meas
         ctx.noise, ctx.p_drop = noise, p_drop
+        integ = packed.integ if getattr(packed, "fwd_pid", None) else None
+        ctx.has_integ = integ is not None
         ctx.set_materialize_grads(False)
         # (saved tensors: autograd refuses a backward after an in-place change of any of them -- the record, or a parameter stepped too early)
-        ctx.save_for_backward(states, inputs, *tensors, *((jac,) if jac is not None else ()), *((meas.measured,) if meas is not None else ()))
+        ctx.save_for_backward(states, inputs, *tensors, *((jac,) if jac is not None else ()), *((meas.measured,) if meas is not None else ()),
+                              *((integ,) if integ is not None else ()))
         return states, inputs
 
     @staticmethod
@@ -942,10 +1005,12 @@ class RolloutClosedFunction(torch.autograd.Function):
         states, inputs, tensors, rest = ctx.saved_tensors[0], ctx.saved_tensors[1], ctx.saved_tensors[2:2 + n], list(ctx.saved_tensors[2 + n:])
         jac = rest.pop(0) if ctx.has_jac else None
         meas_buf = rest.pop(0) if ctx.meas is not None else None
+        integ = rest.pop(0) if ctx.has_integ else None
         gs = torch.zeros_like(states) if g_states is None else g_states.to(dtype=DT).contiguous()
         gi = None if g_inputs is None else g_inputs.to(dtype=DT).contiguous()
         want_x0, want = ctx.needs_input_grad[8], ctx.needs_input_grad[9:]
-        raw, g_x0 = _closed_sweep(ctx.model, packed, tensors, states, inputs, jac, gs, gi, any(want), want_x0, ctx.meas, meas_buf, ctx.noise, ctx.p_drop)
+        raw, g_x0 = _closed_sweep(ctx.model, packed, tensors, states, inputs, jac, gs, gi, any(want), want_x0, ctx.meas, meas_buf, ctx.noise, ctx.p_drop,
+                                  integ)
         grads = [None] * n
         if raw is not None:
             flat, o = raw.sum(0).reshape(-1), 0  # the trajectories' / workgroups' rows added in torch's fixed order
@@ -986,7 +1051,9 @@ def rollout_pd(model: PackedModel, pd: PackedPD, noise: Optional[NoiseSpec], x0,
     ``sqrt_Kp_gains``, ``sqrt_Kd_gains`` and x0); otherwise nothing is recorded.  The same states and inputs, bit for bit, either way.
     ``meas``: a measurement model between the particles and the PD law (partially measurable systems, as in ``rollout``); the measured
     states [T,M,S] the law was evaluated on are left in ``meas.measured`` (not differentiable).  None: the law sees the true state, and
-    the calls made are the ones made without the argument.  The return has the same three elements either way."""
+    the calls made are the ones made without the argument.  The return has the same three elements either way.
+    ``pd`` a PackedPID (``Policy.PID_controller``): the law with the clamped integral of the position error, mcp_rollout_pid and its sweep
+    (gradients to ``sqrt_Ki_gains`` too); the integral [T,M,U] is left in ``pd.integ`` (not differentiable)."""
     return _rollout_closed("rollout_pd", "the gains", model, pd, noise, x0, T, particle_pred, status, meas)
 
 

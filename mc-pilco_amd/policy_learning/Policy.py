@@ -15,6 +15,8 @@ drawn exactly like ``torch.nn.functional.dropout`` draws it on the CPU -- parity
 with ``target_traj`` it tracks: the errors target_traj[t] - x behind its features (Policy.py:389-403's map), mcp_rollout_mlp_track.
 ``Residual_MLP_policy`` keeps a PD law (PD_controller's term, :437-449) and adds the network as its correction ahead of the one squashing,
 u = squash(PD(x, t) + net(x, t)), mcp_rollout_mlp_res.
+``PID_controller`` (this project's own) is PD_controller with a clamped integral of the position error and a third trainable gain; it runs
+inside the fused closed loop like its parent, mcp_rollout_pid.
 Exploration policies (Random_exploration, Sum_of_sinusoids :94-150, PD_controller :406-449) drive the simulated system once per
 trial (61-201 samples): host-side, their ``np.random`` draws in the reference's order so that a seeded launch script collects the
 same data.
@@ -144,6 +146,75 @@ class PD_controller(Policy):
         err = self.target_traj[t, :].reshape(1, -1) - states
         h = int(self.state_dim / 2)
         return self.f_squash(self.sqrt_Kp_gains ** 2 * err[:, 0:h] + self.sqrt_Kd_gains ** 2 * err[:, h:])
+
+
+class PID_controller(PD_controller):
+    """PD_controller with an integral term and anti-windup (this project's own: the reference has none).  Per input k, with e = target_traj[t]
+    - state, p = k and v = state_dim / 2 + k (PD_controller's layout):
+        I_t[k] = clamp(I_{t-1}[k] + T_sampling e[p], -i_max[k], +i_max[k]),  I_{-1} = 0
+        u[k]   = squash(sqrt_Kp^2 e[p] + sqrt_Kd^2 e[v] + sqrt_Ki^2 I_t[k])
+    ``i_max``: None (no clamp), a scalar, or one bound per input (inf: that input unclamped).  The clamp passes gradient where I_t lies
+    strictly inside its bounds.  ``flg_trainable`` covers the three gains.  ``forward(states, t)`` is the torch formula of the step loop and
+    of the system simulator; it HOLDS the integral: t == 0 resets it, every other call must come with the previous t + 1 and the same number
+    of particles (ValueError otherwise).  As ``MC_PILCO``'s control policy it runs inside the fused closed loop like its parent
+    (``packed()``: an ops.PackedPID, mcp_rollout_pid and its sweep), where the integral is a register of the launch and this object's is not
+    touched."""
+
+    def __init__(self, state_dim, input_dim, sqrt_Kp_gains, sqrt_Kd_gains, sqrt_Ki_gains, T_sampling, i_max=None, target_traj=None, flg_squash=True,
+                 u_max=1.0, flg_trainable=False, dtype=torch.float64, device=torch.device("cpu")):
+        super().__init__(state_dim=state_dim, input_dim=input_dim, sqrt_Kp_gains=sqrt_Kp_gains, sqrt_Kd_gains=sqrt_Kd_gains, target_traj=target_traj,
+                         flg_squash=flg_squash, u_max=u_max, flg_trainable=flg_trainable, dtype=dtype, device=device)
+        self.sqrt_Ki_gains = torch.nn.Parameter(torch.tensor(sqrt_Ki_gains, dtype=self.dtype, device=self.device), requires_grad=flg_trainable)
+        self.T_sampling = float(T_sampling)
+        self.i_max = i_max
+        self._integral, self._t_prev = None, None
+
+    def _i_max_values(self):
+        """One bound per input as floats (inf: no clamp), or None when ``i_max`` does not describe that."""
+        U = int(self.input_dim)
+        if self.i_max is None or np.isscalar(self.i_max):
+            return [float("inf") if self.i_max is None else float(self.i_max)] * U
+        v = [float(x) for x in np.asarray(self.i_max, dtype=float).reshape(-1)]
+        return v if len(v) == U else None
+
+    def packed(self) -> "ops.PackedPID":
+        """mcp_pd_policy and mcp_pid_term over the LIVE gain parameters (rebuilt if a tensor, the target, the step or the bound was replaced)."""
+        key = (self.sqrt_Kp_gains.data_ptr(), self.sqrt_Kd_gains.data_ptr(), self.sqrt_Ki_gains.data_ptr(), id(self.target_traj), self.flg_squash,
+               id(self.u_max), self.T_sampling, id(self.i_max))
+        hit = self.__dict__.get("_packed_pid")
+        if hit is None or hit[0] != key:
+            hit = self.__dict__["_packed_pid"] = (key, ops.PackedPID(self))
+        return hit[1]
+
+    def fusable(self, model, T):
+        """The parent's conditions, and the term's: the third gain holds one value per input (or one for all) in float64 on the GPU,
+        T_sampling > 0, every bound > 0."""
+        if not super().fusable(model, T):
+            return False
+        ki = self.sqrt_Ki_gains
+        if int(ki.numel()) not in (1, int(self.input_dim)) or ki.dtype != torch.float64 or not ki.is_cuda:
+            return False
+        im = self._i_max_values()
+        return bool(self.T_sampling > 0.0) and im is not None and all(v > 0.0 for v in im)
+
+    def forward(self, states, t, p_dropout=0.0):
+        states = states.reshape([-1, self.state_dim])
+        t = int(t)
+        if t == 0:
+            self._integral = torch.zeros(states.shape[0], self.input_dim, dtype=states.dtype, device=states.device)
+        elif self._t_prev is None or t != self._t_prev + 1:
+            raise ValueError("PID_controller.forward holds the integral: called with t = %d after t = %s (t == 0 resets it)" % (t, self._t_prev))
+        elif self._integral.shape[0] != states.shape[0]:
+            raise ValueError("PID_controller.forward holds the integral of %d particles, called with %d" % (self._integral.shape[0], states.shape[0]))
+        self._t_prev = t
+        err = self.target_traj[t, :].reshape(1, -1) - states
+        h = int(self.state_dim / 2)
+        im = self._i_max_values()
+        if im is None:
+            raise ValueError("i_max must be None, a scalar or hold one bound per input")
+        bound = torch.tensor(im, dtype=states.dtype, device=states.device)
+        q = self._integral = torch.clamp(self._integral + self.T_sampling * err[:, 0:h], -bound, bound)
+        return self.f_squash(self.sqrt_Kp_gains ** 2 * err[:, 0:h] + self.sqrt_Kd_gains ** 2 * err[:, h:] + self.sqrt_Ki_gains ** 2 * q)
 
 
 class MLP_policy(Policy):
