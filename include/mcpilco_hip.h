@@ -241,6 +241,21 @@ typedef struct mcp_mlp_pd {
   int32_t rows;                 /* >= T                                                          */
 } mcp_mlp_pd;
 
+/* MEMORY of the tanh MLP -- the network reads the last h rows it was shown, so that it can learn its own estimator from them.  The fused
+ * entries take it on the TRUE STATE only: with h > 1 and an active measurement model they return MCP_ERR_ARG (a measured form is not
+ * built; MC_PILCO4PMS runs such a policy on its step loop).  With r_t the row the policy reads in evaluation t (the state x_t) and
+ * phi the descriptor's own map [r[non_angle], sin r[angle], cos r[angle]] (or r), of width P0, the feature row of evaluation t (every row
+ * 0 .. T - 1) is
+ *   f_t = [phi(r_t), phi(r_{t-1}), ..., phi(r_{t-h+1}), target[t][idx[i]] - r_t[idx[i]]  (i = 0 .. n - 1)],   r_{t-j} := r_0 for t - j < 0
+ * the NEWEST block first, the track's errors (of the current row only) last; rows before 0 REPEAT row 0 (no zero padding: f_0 is h copies
+ * of phi(r_0)).  The descriptor's P = h P0 + track->n and W[0] is [h0][P].  The PD term and dropout are untouched: both see the current
+ * row / the hidden units alone.  ADJOINT: block j of row t pulls on r_{max(t-j, 0)} through phi at THAT row, so row 0 collects the pull of
+ * every block that was clamped onto it. */
+#define MCP_MAX_HIST 4
+typedef struct mcp_mlp_hist {
+  int32_t h;                    /* 1 .. MCP_MAX_HIST; 1: no history */
+} mcp_mlp_hist;
+
 /* Integral term of the PD law in closed loop -- mcp_pd_policy's law with a clamped integral of the position error (anti-windup), the
  * first law here whose control depends on controller state carried across the steps.  The reference has no integral law: without this
  * term it is a stateful torch policy in the step loop of MC_PILCO.apply_policy (policy_learning/MC_PILCO.py:615-674; measured: :808-906).
@@ -614,6 +629,35 @@ int mcp_rollout_mlp_res_bwd(const mcp_model* model, const mcp_mlp_policy* mlp, c
                             const mcp_meas* meas, const mcp_noise* noise /* NULL ok iff p_drop == 0 */, double p_drop, int M, int T,
                             const double* states, const double* inputs, const double* jac, const double* g_states,
                             const double* g_inputs /* may be NULL */, double* g_params, double* g_x0, void* stream);
+/* mcp_rollout_mlp_res with MEMORY (mcp_mlp_hist): u_t = net(f_t) (+ the PD term), f_t the window of the last hist->h rows as stated at
+ * mcp_mlp_hist -- newest block first, rows before 0 repeat row 0, the errors of the current row last; mlp->P = h P0 + track->n.  The HIST
+ * forms of the residual kernels: per step the feature threads still compute ONE block, phi(r_t); the older blocks are the earlier steps'
+ * block 0, moved one place down the feature row in LDS behind layer 0 (a thread per trajectory and column, no barrier added); at t = 0 the
+ * feature threads write every block.  track NULL / n == 0, res NULL / on == 0 and p_drop == 0 are all legal; hist->h > 1 needs meas NULL
+ * or meas->n == 0 (the true state): with an active measurement model the entry returns MCP_ERR_ARG.  Noise
+ * addressing, inputs[T - 1], the status flags (a NaN anywhere in W[0] reaches the inputs: MCP_STATUS_NAN), T == 1, the tile ladder, the
+ * weights' LDS copy and the bit identities (mcp_rollout_open on the launch's own inputs; plain against recording launch) are
+ * mcp_rollout_mlp_res's.  hist NULL or hist->h == 1: mcp_rollout_mlp_res itself on the same arguments (same kernels, same bits).  Checks
+ * in the order of mcp_rollout_mlp_res, the memory's with the descriptor's: hist->h > MCP_MAX_HIST or P > MCP_MAX_PFEAT is MCP_ERR_LIMIT
+ * (with the descriptor's other limits, first); hist->h < 1 and P != h P0 + track->n are MCP_ERR_ARG; LAST, behind the track's, the PD term's
+ * and the measurement's own checks (and in the sweep ahead of "nothing asked for"): hist->h > 1 with meas->n > 0 is MCP_ERR_ARG. */
+int mcp_rollout_mlp_hist(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_mlp_hist* hist /* NULL or h == 1: no memory */,
+                         const mcp_mlp_track* track /* NULL or n == 0: no errors */, const mcp_mlp_pd* res /* NULL or on == 0: no PD term */,
+                         const mcp_meas* meas /* NULL or n == 0: the true state; n > 0 only with h == 1 */, const mcp_noise* noise,
+                         double p_drop, int M, int T, int particle_pred, const double* x0, double* states, double* inputs, double* mu,
+                         double* var, double* jac /* NULL: no record */, uint32_t* status, void* stream);
+/* Reverse-time sweep of mcp_rollout_mlp_hist: mcp_rollout_mlp_res_bwd with the window in the activation rows (recomputed from rows
+ * r .. r - h + 1 of states, clamped at 0, with the forward's functions: the forward's bits) and the ADJOINT of the window:
+ * fbar = W0^T delta_1 has P columns; block j of row r pulls on row max(r - j, 0) through phi at that row, whose sines and cosines are
+ * block j of row r's own activation row:   plain source i: fbar[j P0 + i];   angle source i: fbar[j P0 + nnp + i] cos - fbar[j P0 + nnp +
+ * nap + i] sin.  The pulls of blocks j >= 1 are added, j ascending, into a ring pend[h][trajectory][S] in LDS at slot max(r - j, 0) mod h;
+ * row r' adds slot r' mod h beside block 0's pull and clears it.  Row 0 collects every clamped block.  Slabs, g_x0, the gain gradients, the parts and the
+ * fixed order of every sum as mcp_rollout_mlp_res_bwd.  hist NULL or hist->h == 1: mcp_rollout_mlp_res_bwd itself.  The argument checks
+ * of the forward entry. */
+int mcp_rollout_mlp_hist_bwd(const mcp_model* model, const mcp_mlp_policy* mlp, const mcp_mlp_hist* hist, const mcp_mlp_track* track,
+                             const mcp_mlp_pd* res, const mcp_meas* meas, const mcp_noise* noise /* NULL ok iff p_drop == 0 */, double p_drop,
+                             int M, int T, const double* states, const double* inputs, const double* jac, const double* g_states,
+                             const double* g_inputs /* may be NULL */, double* g_params, double* g_x0, void* stream);
 /* Reverse-time adjoint of the rollout: given dJ/dstates, dJ/dinputs (either may be NULL) returns
  * dJ/d{log_lengthscales [P], centers [B][P], f_linear.weight [U][B]} (overwritten, this rank's
  * particles only; with policy->bias also dJ/dbias into policy->g_bias) and optionally dJ/dx0 [M][S].  Replaces autograd's backward through

@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(HERE, "libmcpilco_hip.so")
 MAX_GP, MAX_STATE, MAX_INPUT, MAX_GPDIM, MAX_PFEAT, MAX_BASIS, MAX_TRAIN = 8, 16, 8, 32, 32, 1024, 4096
 MAX_BASIS_WIDE = 512  # B of a wide policy (P > 16 or U > 4): MCP_MAX_BASIS_WIDE
 MAX_HIDDEN = 64  # units of a hidden layer of mcp_mlp_policy: MCP_MAX_HIDDEN
+MAX_HIST = 4  # rows a policy with memory reads (mcp_mlp_hist.h): MCP_MAX_HIST
 OK = 0
 ERRORS = {-1: "MCP_ERR_ARG", -2: "MCP_ERR_LIMIT", -3: "MCP_ERR_WORKSPACE", -4: "MCP_ERR_LAUNCH", -5: "MCP_ERR_COMM"}
 ABI_VERSION = 7
@@ -84,6 +85,11 @@ class MLPResidual(C.Structure):
     the squashing by the residual entries (on == 0: none)."""
     _fields_ = [("on", C.c_int32), ("pos", C.c_int32 * MAX_INPUT), ("vel", C.c_int32 * MAX_INPUT), ("sqrt_kp", dptr), ("sqrt_kd", dptr),
                 ("target", dptr), ("rows", C.c_int32)]
+
+
+class MLPHist(C.Structure):
+    """mcp_mlp_hist: the network reads the features of the last h rows, newest block first (rows before 0 repeat row 0); h == 1: no memory."""
+    _fields_ = [("h", C.c_int32)]
 
 
 class PIDTerm(C.Structure):
@@ -216,6 +222,12 @@ _SIGS = {
                                       C.POINTER(Noise), C.c_double, C.c_int, C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
     "mcp_rollout_mlp_res_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(MLPPolicy), C.POINTER(MLPTrack), C.POINTER(MLPResidual), C.POINTER(Meas),
                                           C.POINTER(Noise), C.c_double, C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
+    "mcp_rollout_mlp_hist": (C.c_int, [C.POINTER(Model), C.POINTER(MLPPolicy), C.POINTER(MLPHist), C.POINTER(MLPTrack), C.POINTER(MLPResidual),
+                                       C.POINTER(Meas), C.POINTER(Noise), C.c_double, C.c_int, C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr,
+                                       dptr, dptr]),
+    "mcp_rollout_mlp_hist_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(MLPPolicy), C.POINTER(MLPHist), C.POINTER(MLPTrack), C.POINTER(MLPResidual),
+                                           C.POINTER(Meas), C.POINTER(Noise), C.c_double, C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr,
+                                           dptr, dptr]),
     "mcp_rollout_bwd":(C.c_int, [C.POINTER(Model), C.POINTER(Policy), C.POINTER(Noise), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr,
                                   dptr, dptr, dptr, dptr, dptr, C.c_size_t, dptr]),
     "mcp_rollout_fwd_ex": (C.c_int, [C.POINTER(Model), C.POINTER(Policy), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr, dptr,

@@ -668,6 +668,8 @@ def model_step(model: PackedModel, x, u, t, noise: Optional[NoiseSpec] = None, p
 #                  and the track itself -- None: the policy has no target, and the calls are the ones above
 #   fwd_res, bwd_res, res_c()   (a policy that can carry a PD term) the entries that take an mcp_mlp_pd behind the track, and the term itself --
 #                  None: the policy has none, and the calls are the ones above
+#   fwd_hist, bwd_hist, hist_c(), history   (a policy with memory, ``history`` > 1) the entries that take an mcp_mlp_hist behind the policy and
+#                  ahead of the track, and the depth itself -- ``history`` == 1: the calls are the ones above
 #   fwd_pid, bwd_pid, term_c(integ)   (a policy with the integral term) the ONE pair of entries that take an mcp_pid_term behind the policy and
 #                  a measurement model or NULL behind that, and the term over a launch's buffer ``integ`` [T,M,U] -- which the launch
 #                  allocates, leaves in ``packed.integ`` and the Function saves for the sweep like the measurement buffer
@@ -788,12 +790,15 @@ class PackedMLP:
     not differentiable) are carried here, ``P`` counts them, and the launches go to the track entries.  A ``Policy.Residual_MLP_policy`` adds
     the PD term of mcp_mlp_pd ahead of the squashing: its two gain parameters come LAST in ``params`` / ``shapes`` / ``n_param`` (a launch takes
     them as [U] tensors, ``tensors()``), ``res_target`` / ``res_pos`` / ``res_vel`` are carried here, and the launches go to the residual
-    entries (``res_c()``), whose sweep's slabs hold g_sqrt_kp | g_sqrt_kd behind bout."""
+    entries (``res_c()``), whose sweep's slabs hold g_sqrt_kp | g_sqrt_kd behind bout.  A policy with memory (``policy.history`` = H > 1) reads
+    the last H rows' features, newest block first, ahead of the errors: ``history`` is carried here, ``P`` = H P0 + the errors, and the
+    launches go to the history entries (``hist_c()``) whatever the measurement, the dropout, the track and the PD term are."""
 
     fwd, bwd = ("mcp_rollout_mlp", "mcp_rollout_mlp_meas"), ("mcp_rollout_mlp_bwd", "mcp_rollout_mlp_meas_bwd")
     fwd_drop, bwd_drop = "mcp_rollout_mlp_drop", "mcp_rollout_mlp_drop_bwd"
     fwd_track, bwd_track = "mcp_rollout_mlp_track", "mcp_rollout_mlp_track_bwd"  # (a policy with a track: whatever meas and p_drop are)
     fwd_res, bwd_res = "mcp_rollout_mlp_res", "mcp_rollout_mlp_res_bwd"  # (a policy with the PD term: whatever meas, p_drop and the track are)
+    fwd_hist, bwd_hist = "mcp_rollout_mlp_hist", "mcp_rollout_mlp_hist_bwd"  # (history > 1: whatever meas, p_drop, the track and the PD term are)
     fwd_outputs = ("mu", "var", "jac")
     grad_tile = 16  # one slab of parameter gradients per workgroup of the sweep
 
@@ -803,7 +808,10 @@ class PackedMLP:
         self.S, self.U = int(policy.state_dim), int(policy.input_dim)
         self.hidden = [int(h) for h in policy.hidden_sizes]
         self.angle, self.non_angle = [int(i) for i in policy.angle_indices], [int(i) for i in policy.non_angle_indices]
-        self.P = len(self.non_angle) + 2 * len(self.angle) if (self.angle or self.non_angle) else self.S
+        self.history = int(getattr(policy, "history", 1))
+        if not 1 <= self.history <= abi.MAX_HIST:
+            raise RuntimeError("the MLP policy reads 1 .. %d rows" % abi.MAX_HIST)
+        self.P = self.history * (len(self.non_angle) + 2 * len(self.angle) if (self.angle or self.non_angle) else self.S)
         self.track_idx, self.target = None, None
         if getattr(policy, "target_traj", None) is not None:
             self.track_idx = [int(i) for i in policy.error_indices]
@@ -866,6 +874,12 @@ class PackedMLP:
             c.pos[k], c.vel[k] = self.res_pos[k], self.res_vel[k]
         return c
 
+    def hist_c(self):
+        """mcp_mlp_hist: the depth of the window (1: none)."""
+        c = abi.MLPHist()
+        c.h = self.history
+        return c
+
     def track_c(self):
         """mcp_mlp_track over the target held here, or None for a policy without one."""
         if self.target is None:
@@ -923,6 +937,8 @@ def _entry(packed, names, plain, marg, nz, p_drop, integ=None):
         return names[4], [C.byref(packed.term_c(integ)), marg[0] if marg else None] + plain
     tc = packed.track_c() if names[2] else None
     rc = packed.res_c() if len(names) > 3 and names[3] else None
+    if len(names) > 5 and names[5] and getattr(packed, "history", 1) > 1:  # (memory: the depth, the track or NULL, the term or NULL, the rest)
+        return names[5], [C.byref(packed.hist_c()), None if tc is None else C.byref(tc), None if rc is None else C.byref(rc)] + _drop_args(marg, nz, p_drop)
     if rc is not None:  # (the PD term: the track or NULL, the term, then the dropout entry's arguments)
         return names[3], [None if tc is None else C.byref(tc), C.byref(rc)] + _drop_args(marg, nz, p_drop)
     if tc is not None:
@@ -950,7 +966,8 @@ def _closed_launch(model, packed, tensors, noise, x0, T, particle_pred, status, 
     if getattr(packed, "fwd_pid", None):
         integ = packed.integ = torch.empty(T, M, model.U, dtype=DT, device=dev)
     name, head = _entry(packed, (packed.fwd, getattr(packed, "fwd_drop", None), getattr(packed, "fwd_track", None),
-                                 getattr(packed, "fwd_res", None), getattr(packed, "fwd_pid", None)), [C.byref(nz)], marg, nz, p_drop, integ)
+                                 getattr(packed, "fwd_res", None), getattr(packed, "fwd_pid", None), getattr(packed, "fwd_hist", None)),
+                        [C.byref(nz)], marg, nz, p_drop, integ)
     abi.check(getattr(abi.lib(), name)(_mc(model), C.byref(pc), *head, M, T,
                                        int(bool(particle_pred)), abi.ptr(x0), abi.ptr(states), abi.ptr(inputs),
                                        *[abi.ptr(outputs[k]) for k in packed.fwd_outputs], abi.ptr(status), abi.stream()), name)
@@ -971,7 +988,8 @@ def _closed_sweep(model, packed, tensors, states, inputs, jac, g_states, g_input
     marg = _meas_arg(meas, T, M, meas_buf)
     nz = noise.to_c() if p_drop > 0.0 else None  # (only the keep decisions are drawn again)
     name, head = _entry(packed, (packed.bwd, getattr(packed, "bwd_drop", None), getattr(packed, "bwd_track", None),
-                                 getattr(packed, "bwd_res", None), getattr(packed, "bwd_pid", None)), [], marg, nz, p_drop, integ)
+                                 getattr(packed, "bwd_res", None), getattr(packed, "bwd_pid", None), getattr(packed, "bwd_hist", None)), [],
+                        marg, nz, p_drop, integ)
     abi.check(getattr(abi.lib(), name)(_mc(model), C.byref(pc), *head, M, T, abi.ptr(states), abi.ptr(inputs),
                                        abi.ptr(jac), abi.ptr(g_states), abi.ptr(g_inputs), abi.ptr(raw), abi.ptr(g_x0), abi.stream()), name)
     return raw, g_x0
@@ -1066,6 +1084,8 @@ def rollout_mlp(model: PackedModel, mlp: PackedMLP, noise: Optional[NoiseSpec], 
     draws the same decisions again.  0 (the default): the calls made without the argument.  A tracking policy (``mlp.target`` [rows >= T, S]:
     features [x[non_angle], sin x[angle], cos x[angle], target[t][idx] - x[idx]], under ``meas`` with the measurement in x's place) runs the
     track entries; the target gets no gradient."""
+    if meas is not None and getattr(mlp, "history", 1) > 1:
+        raise RuntimeError("rollout_mlp: a policy with memory (history > 1) has no fused form on a simulated measurement")
     return _rollout_closed("rollout_mlp", "the parameters", model, mlp, noise, x0, T, particle_pred, status, meas, p_drop)
 
 

@@ -205,6 +205,7 @@ class MC_PILCO(torch.nn.Module):
         pol, ml = self.control_policy, self.model_learning
         if not _has_fused_layout(ml):
             return None
+        measured = meas_of is not None
         model_of, meas_of = model_of or ml.packed, meas_of or (lambda pos_noise: None)
         if isinstance(pol, _Policy.Sum_of_gaussians):  # (on measurements the kernels carry the filter's states per particle, mcp_meas)
             noise, pos_noise, p = self._rollout_noise(T, p_dropout, n_pos=n_pos)
@@ -212,6 +213,8 @@ class MC_PILCO(torch.nn.Module):
         # the closed loop under the PD law or the tanh MLP: one launch (and one sweep in backward); the eps draws, and for an MLP with
         # dropout (flg_drop) the masks of its hidden units -- the PD law has none
         mlp = isinstance(pol, _Policy.MLP_policy)
+        if mlp and measured and int(getattr(pol, "history", 1)) > 1:
+            return None  # (an MLP with memory has no fused form on simulated measurements: the step loop, which holds its window)
         op = ops.rollout_pd if isinstance(pol, _Policy.PD_controller) else ops.rollout_mlp if mlp else None
         model = model_of() if op is not None and self.fused_feedback else None
         if model is None or not pol.fusable(model, T):

@@ -238,11 +238,29 @@ class MLP_policy(Policy):
     target_traj[t][i] - x[i], i in ``error_indices`` (default: all S components in order; the plain difference, not wrapped on angles),
     so f = [x[non_angle], sin x[angle], cos x[angle], errors], ``feature_dim`` counts them and W0's last columns are theirs.  ``forward`` and
     ``features`` then need ``t``.  The fused loop (mcp_rollout_mlp_track) reads row t of the target in policy evaluation t; the target is a
-    constant: it gets no gradient.  ``target_traj=None`` (the default): the class without any of it."""
+    constant: it gets no gradient.  ``target_traj=None`` (the default): the class without any of it.
+    Memory (``history`` = H, 1 .. 4): the network reads the features of the last H rows it was shown, so that it can learn its own estimator
+    from them.  ``MC_PILCO`` runs it fused; ``MC_PILCO4PMS`` does NOT (no measured form of the kernels is built): there the object runs the
+    step loop, ``last_feedback_fused`` False, this ``forward`` holding the window.  With r_t the row of evaluation t and phi the map above (width P0),
+        f_t = [phi(r_t), phi(r_{t-1}), ..., phi(r_{t-H+1}), errors_t],   r_{t-j} := r_0 for t - j < 0
+    the newest block first, the errors (of the current row only) last, rows before 0 REPEATING row 0 (no zero padding: f_0 is H copies of
+    phi(r_0), and row 0 collects the gradient of every block clamped onto it); ``feature_dim`` = H P0 + the errors, at most 32 (ValueError
+    otherwise).  A residual policy's PD term reads the current row only; dropout acts on the hidden units as before.  ``forward`` and
+    ``features`` then need ``t`` and HOLD the window the way ``PID_controller.forward`` holds its integral: t == 0 resets it, every other
+    call must come with the previous t + 1 and the same number of particles (ValueError otherwise).  The fused loop (mcp_rollout_mlp_hist)
+    keeps the window in the launch's LDS and never touches this object's.  ``t`` is the STEP INDEX (``int(t)``), as for ``PID_controller``:
+    a caller that passes time in seconds -- the system simulator behind ``get_data_from_system`` does, t = k dt -- resets the window while
+    t < 1 and is refused at the first repeated integer, so a policy with memory cannot be deployed through that loop as it stands.  The held
+    window keeps the last rollout's autograd graph alive until the next ``t == 0`` (``reset_window()`` drops it).  ``history=1`` (the
+    default): the class without any of it."""
 
     def __init__(self, state_dim, input_dim, hidden_sizes, angle_indices=None, non_angle_indices=None, u_max=1.0, flg_squash=True, weight_init=None,
-                 dtype=torch.float64, device=torch.device("cuda"), flg_drop=False, target_traj=None, error_indices=None):
+                 dtype=torch.float64, device=torch.device("cuda"), flg_drop=False, target_traj=None, error_indices=None, history=1):
         super().__init__(state_dim=state_dim, input_dim=input_dim, flg_squash=flg_squash, u_max=u_max, dtype=dtype, device=device)
+        self.history = int(history)
+        if not 1 <= self.history <= ops.abi.MAX_HIST:
+            raise ValueError("history is 1 .. %d rows" % ops.abi.MAX_HIST)
+        self._window, self._t_prev = None, None
         self.flg_drop = bool(flg_drop)
         self.target_traj = None if target_traj is None else torch.as_tensor(target_traj).detach().to(self.device)  # (its own dtype: fusable() asks for float64)
         if target_traj is None and error_indices is not None:
@@ -255,7 +273,9 @@ class MLP_policy(Policy):
         self.angle_indices = [] if angle_indices is None else [int(i) for i in np.atleast_1d(angle_indices)]
         self.non_angle_indices = [] if non_angle_indices is None else [int(i) for i in np.atleast_1d(non_angle_indices)]
         self._lists = bool(self.angle_indices or self.non_angle_indices)
-        self.feature_dim = (len(self.non_angle_indices) + 2 * len(self.angle_indices) if self._lists else int(state_dim)) + len(self.error_indices)
+        self.feature_dim = self.history * (len(self.non_angle_indices) + 2 * len(self.angle_indices) if self._lists else int(state_dim)) + len(self.error_indices)
+        if self.history > 1 and self.feature_dim > ops.abi.MAX_PFEAT:
+            raise ValueError("a policy with memory has at most %d features: history * own features + errors = %d" % (ops.abi.MAX_PFEAT, self.feature_dim))
         self.drop_width = sum(self.hidden_sizes)  # a row of dropout decisions: the hidden units, layer 0's first
         widths = [self.feature_dim] + self.hidden_sizes + [int(input_dim)]
         names = ["0", "1", "out"] if len(self.hidden_sizes) == 2 else ["0", "out"]
@@ -286,8 +306,35 @@ class MLP_policy(Policy):
             else:
                 q.data.zero_()
 
+    def reset_window(self):
+        """Forgets the held window (and with it the autograd graph of the rollout that filled it); the next call must come with t == 0."""
+        self._window, self._t_prev = None, None
+
+    def _window_blocks(self, own, t):
+        """[phi(r_t), phi(r_{t-1}), ..., phi(r_{t-H+1})] with ``own`` = phi(r_t); holds the H - 1 newest blocks for the next call."""
+        if t is None:
+            raise ValueError("an MLP_policy with memory is evaluated at a time step: pass t")
+        t = int(t)
+        if t == 0:
+            self._window = [own] * (self.history - 1)  # (rows before 0 repeat row 0)
+        elif self._t_prev is None or t != self._t_prev + 1:
+            raise ValueError("MLP_policy.forward holds the window: called with t = %d after t = %s (t == 0 resets it)" % (t, self._t_prev))
+        elif self._window[0].shape[0] != own.shape[0]:
+            raise ValueError("MLP_policy.forward holds the window of %d particles, called with %d" % (self._window[0].shape[0], own.shape[0]))
+        self._t_prev = t
+        blocks = [own] + self._window
+        self._window = blocks[:self.history - 1]
+        return blocks
+
     def features(self, states, t=None):
         x = states.reshape([-1, self.state_dim])
+        if self.history > 1:
+            own = torch.cat([x[:, self.non_angle_indices], torch.sin(x[:, self.angle_indices]), torch.cos(x[:, self.angle_indices])], dim=1) if self._lists else x
+            blocks = self._window_blocks(own, t)
+            if self.target_traj is not None:
+                row = torch.as_tensor(self.target_traj).to(x.device)[int(t)].reshape(1, -1)
+                blocks = blocks + [row[:, self.error_indices] - x[:, self.error_indices]]
+            return torch.cat(blocks, dim=1)
         if self.target_traj is None:
             if not self._lists:
                 return x
@@ -333,7 +380,7 @@ class MLP_policy(Policy):
         tt = self.target_traj
         key = tuple(q.data_ptr() for q in self.mlp_parameters()) + (self.flg_squash, self._u_max_values(), id(tt),
                                                                     tt.data_ptr() if isinstance(tt, torch.Tensor) else None, tuple(self.error_indices))
-        key += self._packed_key_extra()
+        key += (self.history,) + self._packed_key_extra()
         hit = self.__dict__.get("_packed_mlp")
         if hit is None or hit[0] != key:
             hit = self.__dict__["_packed_mlp"] = (key, ops.PackedMLP(self))
@@ -342,7 +389,7 @@ class MLP_policy(Policy):
     def fusable(self, model, T):
         """Whether T steps of this policy on ``model`` (an ops.PackedModel, or anything with ``S`` and ``U``) can run as the fused closed loop:
         float64 parameters on a GPU, S and U those of the model, the index lists in range and disjoint, every width within the kernels' limits
-        (``feature_dim``, the error features included, at most MAX_PFEAT); with a target: a float64 tensor [rows >= T, S], the error indices in
+        (``feature_dim``, the window's blocks and the error features included, at most MAX_PFEAT; ``history`` 1 .. MAX_HIST); with a target: a float64 tensor [rows >= T, S], the error indices in
         range and distinct."""
         S, U = int(self.state_dim), int(self.input_dim)
         if int(getattr(model, "S", -1)) != S or int(getattr(model, "U", -1)) != U or U > ops.abi.MAX_INPUT or S > ops.abi.MAX_STATE or int(T) < 1:
@@ -358,6 +405,8 @@ class MLP_policy(Policy):
                 return False
             if any(i < 0 or i >= S for i in err) or len(set(err)) != len(err):
                 return False
+        if not 1 <= int(self.history) <= ops.abi.MAX_HIST:
+            return False
         if self.feature_dim < 1 or self.feature_dim > ops.abi.MAX_PFEAT or any(h < 1 or h > ops.abi.MAX_HIDDEN for h in self.hidden_sizes):
             return False
         um = self._u_max_values()  # (by value: a list of bounds changed in place gives a new descriptor, a tensor on any device is read)
@@ -387,11 +436,11 @@ class Residual_MLP_policy(MLP_policy):
     the network's."""
 
     def __init__(self, state_dim, input_dim, hidden_sizes, angle_indices=None, non_angle_indices=None, u_max=1.0, flg_squash=True, weight_init=None,
-                 dtype=torch.float64, device=torch.device("cuda"), flg_drop=False, target_traj=None, error_indices=None, *, sqrt_Kp_gains,
-                 sqrt_Kd_gains, flg_train_gains=False, pd_target_traj=None, pd_pos_indices=None, pd_vel_indices=None, zero_output=False):
+                 dtype=torch.float64, device=torch.device("cuda"), flg_drop=False, target_traj=None, error_indices=None, history=1, *,
+                 sqrt_Kp_gains, sqrt_Kd_gains, flg_train_gains=False, pd_target_traj=None, pd_pos_indices=None, pd_vel_indices=None, zero_output=False):
         super().__init__(state_dim, input_dim, hidden_sizes, angle_indices=angle_indices, non_angle_indices=non_angle_indices, u_max=u_max,
                          flg_squash=flg_squash, weight_init=weight_init, dtype=dtype, device=device, flg_drop=flg_drop, target_traj=target_traj,
-                         error_indices=error_indices)
+                         error_indices=error_indices, history=history)
         S, U = int(state_dim), int(input_dim)
         if pd_target_traj is None and target_traj is None:
             raise ValueError("the PD term needs a target: pd_target_traj or target_traj")
