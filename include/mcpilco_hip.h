@@ -279,6 +279,26 @@ typedef struct mcp_pid_term {
   double* integ;                /* DEVICE [T][M][U]: I, written by the forward, read by the sweep */
 } mcp_pid_term;
 
+/* TIME-VARYING LINEAR FEEDBACK in closed loop -- Policy.TV_linear_controller (this project's own class; the reference has none): a
+ * feedforward sequence plus per-step dense gains around a reference, the local controller of trajectory optimisation.  For row
+ * t = 0 .. T - 1, with r_t the state x_t (measured form: the simulated measurement y_t of mcp_meas):
+ *   e_t = target_traj[t] - r_t;   a_t[k] = (sum_s gain[t][k][s] e_t[s]) + ff[t][k]   (s ascending from 0.0, the feedforward added last)
+ *   u_t[k] = u_max[k] tanh(a_t[k] / u_max[k]) (squash) or a_t[k]
+ * The gains are plain (not squared) and dense over all S components; no index layout applies (S may be odd, U need not be S / 2).  The
+ * errors are plain differences, not wrapped.  gain_rows == 1: one matrix [U][S] for every row.  ff_rows == 0: no feedforward (ff may be
+ * NULL).  The three tensors are DEVICE pointers: an optimizer updates gain and ff in place; the target is a constant of the launch. */
+typedef struct mcp_tvl_policy {
+  int32_t U, S;                 /* == model->U, == model->S                                      */
+  int32_t squash;               /* flg_squash                                                    */
+  int32_t gain_rows;            /* 1: shared, else >= T                                          */
+  int32_t ff_rows;              /* 0: no feedforward, else >= T                                  */
+  int32_t target_rows;          /* >= T                                                          */
+  double u_max[MCP_MAX_INPUT];  /* > 0 with squash                                               */
+  const double* gain;           /* DEVICE [gain_rows][U][S]                                      */
+  const double* ff;             /* DEVICE [ff_rows][U], or NULL with ff_rows == 0                */
+  const double* target_traj;    /* DEVICE [target_rows][S]                                       */
+} mcp_tvl_policy;
+
 /* ---- library ------------------------------------------------------------------------ */
 int mcp_abi_version(void);
 const char* mcp_build_info(void);
@@ -525,6 +545,30 @@ int mcp_rollout_pid(const mcp_model* model, const mcp_pd_policy* pd, const mcp_p
 int mcp_rollout_pid_bwd(const mcp_model* model, const mcp_pd_policy* pd, const mcp_pid_term* pid, const mcp_meas* meas, int M, int T,
                         const double* states, const double* inputs, const double* jac, const double* g_states, const double* g_inputs,
                         double* g_gains, double* g_x0, void* stream);
+/* Closed-loop rollout under the time-varying linear feedback law (mcp_tvl_policy), ONE launch: mcp_rollout_pd / mcp_rollout_pd_meas with
+ * the descriptor exchanged.  meas NULL or n == 0: the law on the true state; else on the simulated measurement (meas->meas [T][M][S]
+ * receives y).  Everything else -- states, inputs (row T - 1 stored), jac, mu / var, noise addressing, status flags (a NaN input raises
+ * MCP_STATUS_NAN), T == 1 evaluates the policy only, no ragged lengths -- as there; the states carry the bits of mcp_rollout_open fed
+ * with the launch's own inputs[:T-1], and the plain launch (jac NULL) those of the recording launch.  Row t + 1 of gain, ff and the
+ * target is brought into LDS while step t runs: nothing of the law is fetched from global memory between the step's barrier and u_t.
+ * Limits first, as for the PD law: MCP_ERR_LIMIT beyond MCP_MAX_* (tvl->U, tvl->S included); MCP_ERR_ARG: a NULL required pointer,
+ * M <= 0, T < 1, tvl->U / tvl->S not the model's, target_rows < T, gain_rows neither 1 nor >= T, ff_rows neither 0 nor >= T, ff_rows > 0
+ * with ff NULL, a u_max <= 0 with squash, the measurement checks of mcp_rollout_pd_meas.  Replaces a torch policy in the loop of
+ * MC_PILCO.apply_policy (policy_learning/MC_PILCO.py:615-674) or MC_PILCO4PMS.apply_policy (:808-906) over
+ * Model_learning.get_next_state (model_learning/Model_learning.py:210-229, 471-494, 685-718). */
+int mcp_rollout_tvl(const mcp_model* model, const mcp_tvl_policy* tvl, const mcp_meas* meas /* NULL or n == 0: the true state */,
+                    const mcp_noise* noise, int M, int T, int particle_pred, const double* x0, double* states, double* inputs,
+                    double* jac /* NULL: no record */, double* mu, double* var, uint32_t* status, void* stream);
+/* Reverse-time sweep of mcp_rollout_tvl: g_states [T][M][S] (required) and g_inputs [T][M][U] (may be NULL) -> g_x0 [M][S] and
+ * g_part [ceil(M/16)][T][U][S+1]: ONE PARTIAL PER WORKGROUP of 16 trajectories and PER ROW -- columns 0 .. S - 1 are dJ/dgain[t][k][s],
+ * column S is dJ/dff[t][k].  Every row 0 .. T - 1 of every slab is written (row T - 1 holds exact zeros when g_inputs is NULL; the absent
+ * trajectories of a ragged last tile add nothing).  The sum over the slabs is the caller's, and so is the sum over the rows for a shared
+ * gain.  No atomics; the 16 trajectories of a row are added in a fixed order: bitwise reproducible, and a slab depends on its own
+ * trajectories alone.  Either output may be NULL; with both NULL the call returns MCP_OK without a launch.  states, inputs, jac: what
+ * mcp_rollout_tvl wrote (jac may be NULL when T == 1); meas->meas as it wrote it.  The argument checks of the forward entry. */
+int mcp_rollout_tvl_bwd(const mcp_model* model, const mcp_tvl_policy* tvl, const mcp_meas* meas, int M, int T, const double* states,
+                        const double* inputs, const double* jac, const double* g_states, const double* g_inputs /* may be NULL */,
+                        double* g_part, double* g_x0, void* stream);
 /* mcp_rollout_mlp with the network evaluated on a SIMULATED MEASUREMENT of the state (mcp_meas, as mcp_rollout_pd_meas has it for the PD
  * law: noisy positions, backward-difference velocities through the first-order filter; row 0 is measured true), ONE launch: the particles
  * evolve on their true states, u_t = mlp(y_t).  Per pair i (p = pos[i], v = vel[i]) and row t >= 1: np_t = x_t[p] + std_pos[i] n_{t,i},

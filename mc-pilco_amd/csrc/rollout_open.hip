@@ -6,8 +6,10 @@
 //   measured feedback  mcp_rollout_pd_meas      the PD law on a simulated measurement of x_t (struct OpenArgsPdMeas); mcp_rollout_pd_meas_bwd
 //   integral feedback  mcp_rollout_pid          either feedback form with a clamped integral of the position error in the law (struct
 //                                               OpenArgsPid); mcp_rollout_pid_bwd
-// All forward forms are one kernel template, rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, FB, PMS, PID>, the sweeps one,
-// rollout_open_bwd_kernel<FB, PMS, PID>.  The host path is the same for every entry point: checks (rollout_common.h: model_within_limits,
+//   time-varying law   mcp_rollout_tvl          either feedback form with a dense gain row and a feedforward per step in the PD law's place
+//                                               (struct OpenArgsTvl); mcp_rollout_tvl_bwd
+// All forward forms are one kernel template, rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, FB, PMS, PID, TVL>, the sweeps one,
+// rollout_open_bwd_kernel<FB, PMS, PID, TVL>.  The host path is the same for every entry point: checks (rollout_common.h: model_within_limits,
 // model_ok / model_lists_ok, meas_model_check -- for the closed loops in closed_loop_checks' one order; here: pd_policy_check), one fill of
 // the arguments' base part per direction (open_fill, open_bwd_fill over sweep_fill_model), one ladder of tiles (launch_open_tiles) -- a refused call makes no HIP call.
 //
@@ -89,9 +91,34 @@ template <bool PMS>
 struct OpenArgsPid : std::conditional<PMS, OpenArgsPdMeas, OpenArgsPd>::type {
   mcp_pid_term pid;
 };
-template <bool FB, bool PMS = false, bool PID = false>
+// TIME-VARYING LINEAR form (template TVL with FB, with or without PMS, mcp_rollout_tvl): the law is a dense row of gains and a feedforward
+// per step (Policy.TV_linear_controller; the reference has no such class: this replaces a torch policy in the loops named above).  With e
+// as above (on y_t in the measured form):
+//   a_k = (sum_s gain[t][k][s] e[s]) + ff[t][k]       (s ascending from 0.0, the feedforward last)
+// The input thread (up, uk) forms the dot behind the barrier the feedback form already has, from the row it already reads and from LDS
+// alone: row t of gain | ff | target ([U][S] | [U] | [S] doubles) sits in one half of a double buffer (the layout's `ext` region) and row
+// t + 1 is brought into the other half by the LAST threads of the workgroup (the state and input threads are the first) right behind the
+// barrier that opens phase K of step t -- a step ahead, off the stretch between the feedback barrier and u_t, and without a barrier of
+// its own: the write of step t and the reads of steps t - 1 and t + 1 are separated by the step's existing barriers.  Registers were the
+// other way; the variance forms of this kernel sit at their register bound, the buffer costs none.  The base parts' pd carries U, squash,
+// u_max and the target; its gains and index lists are not read.
+struct TvlRows {
+  const double* gain;  // [gain_rows][U][S]
+  const double* ff;    // [ff_rows][U] or NULL
+  int gain_rows, ff_rows;
+};
+#define TVL_ROW(U, S) ((U) * (S) + (U) + (S))
+template <bool PMS>
+struct OpenArgsTvl : std::conditional<PMS, OpenArgsPdMeas, OpenArgsPd>::type {
+  TvlRows tv;
+};
+template <bool FB, bool PMS = false, bool PID = false, bool TVL = false>
 struct OpenArgsOf {
   typedef OpenArgs type;
+};
+template <bool PMS>
+struct OpenArgsOf<true, PMS, false, true> {
+  typedef OpenArgsTvl<PMS> type;
 };
 template <>
 struct OpenArgsOf<true, false, false> {
@@ -106,16 +133,32 @@ struct OpenArgsOf<true, PMS, true> {
   typedef OpenArgsPid<PMS> type;
 };
 
-template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool FB = false, bool PMS = false, bool PID = false>
-__global__ __launch_bounds__(RF_NT) void rollout_open_kernel(typename OpenArgsOf<FB, PMS, PID>::type a) {
+// row t of the time-varying law into one half of its LDS buffer: gain[t] (row 0 of a shared gain) | ff[t] (zeros without one) | target[t]
+__device__ __forceinline__ void tvl_stage_row(const TvlRows& tv, const double* target, int t, int U, int S, double* dst, int tid) {
+  const int US = U * S;
+  for (int it = RF_NT - 1 - tid; it < TVL_ROW(U, S); it += RF_NT) {
+    double v;
+    if (it < US)
+      v = tv.gain[(tv.gain_rows == 1 ? (size_t)0 : (size_t)t * US) + it];
+    else if (it < US + U)
+      v = tv.ff_rows ? tv.ff[(size_t)t * U + (it - US)] : 0.0;
+    else
+      v = target[(size_t)t * S + (it - US - U)];
+    dst[it] = v;
+  }
+}
+
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool FB = false, bool PMS = false, bool PID = false, bool TVL = false>
+__global__ __launch_bounds__(RF_NT) void rollout_open_kernel(typename OpenArgsOf<FB, PMS, PID, TVL>::type a) {
   static_assert(FB || !PMS, "the measurement model belongs to the feedback form");
   static_assert(FB || !PID, "the integral term belongs to the feedback form");
+  static_assert((FB && !PID) || !TVL, "the time-varying law is a feedback form of its own");
   extern __shared__ double smem[];
   const mcp_model& md = a.model;
   const int S = md.S, U = md.U, G = md.G, D = md.D, M = a.M, T = a.T;
   const int nna = md.n_not_angle, na = md.n_angle;
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const OpenLayout L = open_layout(PT, NEEDVAR, S, D, G, a.NpadMax, NEEDJAC, a.na, PMS);
+  const OpenLayout L = open_layout(PT, NEEDVAR, S, D, G, a.NpadMax, NEEDJAC, a.na, PMS, TVL ? 2 * TVL_ROW(U, S) : 0);
   double* xs = smem + L.xs;
   double* z = smem + L.z;
   double* red = smem + L.red;  // [2][G][RF_NW][PT]
@@ -175,7 +218,7 @@ __global__ __launch_bounds__(RF_NT) void rollout_open_kernel(typename OpenArgsOf
   // feedback form: the gains (squared once, as the reference squares them in every evaluation), bound and state components of input uk
   double kp2 = 0.0, kd2 = 0.0, umax = 1.0;
   int ipos = 0, ivel = 0;
-  if constexpr (FB) {
+  if constexpr (FB && !TVL) {
     if (isu) {
       const double kp = a.pd.sqrt_kp[uk], kd = a.pd.sqrt_kd[uk];
       kp2 = kp * kp;
@@ -211,6 +254,13 @@ __global__ __launch_bounds__(RF_NT) void rollout_open_kernel(typename OpenArgsOf
       }
       if (pm_pos >= 0) pm_nv = pm_mv = a.x0[(size_t)om * S + pm_vc];
     }
+  }
+  // time-varying form: the bound of input uk; row 0 of the law into the first half of its buffer
+  double* tvr = smem + L.ext;
+  (void)tvr;
+  if constexpr (TVL) {
+    if (isu) umax = a.pd.u_max[uk];
+    tvl_stage_row(a.tv, a.pd.target_traj, 0, U, S, tvr, tid);
   }
   lds_barrier();
 
@@ -257,7 +307,17 @@ __global__ __launch_bounds__(RF_NT) void rollout_open_kernel(typename OpenArgsOf
       if (isu) {
         const double* xr = PMS ? smem + L.ym + up * S : xs + cur * PT * S + up * S;
         const double* tg = a.pd.target_traj + (size_t)t * S;
-        double av = kp2 * (tg[ipos] - xr[ipos]) + kd2 * (tg[ivel] - xr[ivel]);
+        double av;
+        if constexpr (TVL) {  // the dense row: gain, feedforward and target of step t from LDS alone
+          const double* gr = tvr + (t & 1) * TVL_ROW(U, S);
+          const double* gk = gr + uk * S;
+          const double* tgr = gr + U * S + U;
+          double acc = 0.0;
+          for (int s = 0; s < S; ++s) acc += gk[s] * (tgr[s] - xr[s]);
+          av = acc + gr[U * S + uk];
+        } else {
+          av = kp2 * (tg[ipos] - xr[ipos]) + kd2 * (tg[ivel] - xr[ivel]);
+        }
         if constexpr (PID) {
           const double q = integ + idt * (tg[ipos] - xr[ipos]);
           integ = q < -imax ? -imax : (q > imax ? imax : q);
@@ -292,6 +352,7 @@ __global__ __launch_bounds__(RF_NT) void rollout_open_kernel(typename OpenArgsOf
       if (ovalid && t + 1 < len && is_bad(uv)) bad |= MCP_STATUS_NAN;
     }
     lds_barrier();
+    if constexpr (TVL) tvl_stage_row(a.tv, a.pd.target_traj, t + 1, U, S, tvr + ((t + 1) & 1) * TVL_ROW(U, S), tid);  // (t + 1 < T here)
     // ---- phases K (and V) per GP ---------------------------------------------------------------------------------------
     for (int g = 0; g < G; ++g) {
       const GpL gp = gpl[g];
@@ -382,38 +443,38 @@ __global__ __launch_bounds__(RF_NT) void rollout_open_kernel(typename OpenArgsOf
 // ---- host path of the forward entry points: checks -> fill -> ladder -----------------------------------------------------------------
 // (an entry checks its own pointers and sizes, then the limits, the model, its descriptors -- every refusal before any HIP call --, fills
 // the base part of the arguments with open_fill, adds what is its own and hands them to the one ladder of tiles, launch_open_tiles)
-template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool FB, bool PMS, bool PID>
-static int launch_open(const typename OpenArgsOf<FB, PMS, PID>::type& a, hipStream_t st) {
-  const OpenLayout L = open_layout(PT, NEEDVAR, a.model.S, a.model.D, a.model.G, a.NpadMax, NEEDJAC, a.na, PMS);
+template <int PT, int MAXDEG, bool NEEDVAR, bool NEEDJAC, bool FB, bool PMS, bool PID, bool TVL = false>
+static int launch_open(const typename OpenArgsOf<FB, PMS, PID, TVL>::type& a, hipStream_t st) {
+  const OpenLayout L = open_layout(PT, NEEDVAR, a.model.S, a.model.D, a.model.G, a.NpadMax, NEEDJAC, a.na, PMS, TVL ? 2 * TVL_ROW(a.model.U, a.model.S) : 0);
   const size_t lds = (size_t)L.total * sizeof(double);
   if (lds > MCP_LDS_LIMIT) return MCP_ERR_LIMIT;
-  MCP_ENSURE_MAX_LDS((rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, FB, PMS, PID>));
-  hipLaunchKernelGGL((rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, FB, PMS, PID>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
+  MCP_ENSURE_MAX_LDS((rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, FB, PMS, PID, TVL>));
+  hipLaunchKernelGGL((rollout_open_kernel<PT, MAXDEG, NEEDVAR, NEEDJAC, FB, PMS, PID, TVL>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
 }
-template <int PT, bool NEEDVAR, bool NEEDJAC, bool FB, bool PMS, bool PID>
-static int launch_open_deg(const typename OpenArgsOf<FB, PMS, PID>::type& a, int maxdeg, hipStream_t st) {
-  return maxdeg == 0 ? launch_open<PT, 0, NEEDVAR, NEEDJAC, FB, PMS, PID>(a, st) : launch_open<PT, 2, NEEDVAR, NEEDJAC, FB, PMS, PID>(a, st);
+template <int PT, bool NEEDVAR, bool NEEDJAC, bool FB, bool PMS, bool PID, bool TVL = false>
+static int launch_open_deg(const typename OpenArgsOf<FB, PMS, PID, TVL>::type& a, int maxdeg, hipStream_t st) {
+  return maxdeg == 0 ? launch_open<PT, 0, NEEDVAR, NEEDJAC, FB, PMS, PID, TVL>(a, st) : launch_open<PT, 2, NEEDVAR, NEEDJAC, FB, PMS, PID, TVL>(a, st);
 }
-// The ladder of tiles, the same for every form (the feedback and its integral add nothing to the LDS layout, the measurement one row [PT][S]); a.jac: the
+// The ladder of tiles, the same for every form (the feedback and its integral add nothing to the LDS layout, the measurement one row [PT][S], the time-varying law two rows of at most 152 doubles); a.jac: the
 // recording form.  The mean chain (no sampling, no variance asked for) touches no Kinv: one trajectory per workgroup.  With a variance:
 //   no record  16 trajectories per workgroup, 4 where the k panel of 16 does not fit (at every compiled limit at once -- S = 16, D = 32, G = 8,
 //              Npad = 4096 -- that layout takes 148 KB of the 160, so nothing within MCP_MAX_* is refused)
 //   record     two panels: 16 up to Npad ~ 500, 4 up to ~ 2000, beyond that one (at every compiled limit at once: 2 x 32 KB of panels, 85 KB
 //              in all; the recording mean chain: 85 KB, X^T then stays in global memory)
-template <bool FB, bool PMS, bool PID = false>
-static int launch_open_tiles(const typename OpenArgsOf<FB, PMS, PID>::type& a, int maxdeg, bool wantvar, hipStream_t st) {
+template <bool FB, bool PMS, bool PID = false, bool TVL = false>
+static int launch_open_tiles(const typename OpenArgsOf<FB, PMS, PID, TVL>::type& a, int maxdeg, bool wantvar, hipStream_t st) {
   if (!a.jac) {
-    if (!a.sample && !wantvar) return launch_open_deg<1, false, false, FB, PMS, PID>(a, maxdeg, st);
-    int rc = launch_open_deg<16, true, false, FB, PMS, PID>(a, maxdeg, st);
-    if (rc == MCP_ERR_LIMIT) rc = launch_open_deg<4, true, false, FB, PMS, PID>(a, maxdeg, st);
+    if (!a.sample && !wantvar) return launch_open_deg<1, false, false, FB, PMS, PID, TVL>(a, maxdeg, st);
+    int rc = launch_open_deg<16, true, false, FB, PMS, PID, TVL>(a, maxdeg, st);
+    if (rc == MCP_ERR_LIMIT) rc = launch_open_deg<4, true, false, FB, PMS, PID, TVL>(a, maxdeg, st);
     return rc;
   }
-  if (!a.sample && !wantvar) return launch_open_deg<1, false, true, FB, PMS, PID>(a, maxdeg, st);
-  int rc = launch_open_deg<16, true, true, FB, PMS, PID>(a, maxdeg, st);
-  if (rc == MCP_ERR_LIMIT) rc = launch_open_deg<4, true, true, FB, PMS, PID>(a, maxdeg, st);
-  if (rc == MCP_ERR_LIMIT) rc = launch_open_deg<1, true, true, FB, PMS, PID>(a, maxdeg, st);
+  if (!a.sample && !wantvar) return launch_open_deg<1, false, true, FB, PMS, PID, TVL>(a, maxdeg, st);
+  int rc = launch_open_deg<16, true, true, FB, PMS, PID, TVL>(a, maxdeg, st);
+  if (rc == MCP_ERR_LIMIT) rc = launch_open_deg<4, true, true, FB, PMS, PID, TVL>(a, maxdeg, st);
+  if (rc == MCP_ERR_LIMIT) rc = launch_open_deg<1, true, true, FB, PMS, PID, TVL>(a, maxdeg, st);
   return rc;
 }
 
@@ -531,6 +592,52 @@ extern "C" int mcp_rollout_pid(const mcp_model* model, const mcp_pd_policy* pd, 
   return pd_dispatch(model, pd, meas, noise, M, T, particle_pred, x0, states, inputs, jac, mu, var, status, stream, pid);
 }
 
+// ---- time-varying linear form: checks, entry ---------------------------------------------------------------------------------------------
+// the descriptor against the model and the horizon (host fields and the pointers' presence), limits first as for the PD law
+static int tvl_policy_check(const mcp_model* model, const mcp_tvl_policy* tv, int T) {
+  if (tv->U > MCP_MAX_INPUT || tv->S > MCP_MAX_STATE) return MCP_ERR_LIMIT;
+  if (tv->U < 1 || tv->U != model->U || tv->S != model->S || tv->target_rows < T || !tv->gain || !tv->target_traj) return MCP_ERR_ARG;
+  if (tv->gain_rows != 1 && tv->gain_rows < T) return MCP_ERR_ARG;
+  if (tv->ff_rows != 0 && (tv->ff_rows < T || !tv->ff)) return MCP_ERR_ARG;
+  for (int k = 0; k < tv->U; ++k)
+    if (tv->squash && !(tv->u_max[k] > 0.0)) return MCP_ERR_ARG;
+  return MCP_OK;
+}
+// what the kernels read of the descriptor through the feedback form's pd (U, squash, u_max, the target; no gains, no index lists)
+static mcp_pd_policy tvl_as_pd(const mcp_tvl_policy* tv) {
+  mcp_pd_policy pd;
+  memset(&pd, 0, sizeof(pd));
+  pd.U = tv->U, pd.squash = tv->squash, pd.target_traj = tv->target_traj, pd.target_rows = tv->target_rows;
+  for (int k = 0; k < MCP_MAX_INPUT; ++k) pd.u_max[k] = tv->u_max[k];
+  return pd;
+}
+
+// Closed-loop rollout under the time-varying linear feedback law (the law and how its rows reach the step: OpenArgsTvl above), on the true
+// state (meas NULL or n == 0) or on the simulated measurement: replaces a torch policy (Policy.TV_linear_controller; the reference has no
+// such law) in the loop of MC_PILCO.apply_policy (policy_learning/MC_PILCO.py:615-674) or MC_PILCO4PMS.apply_policy (:808-906) over
+// Model_learning.get_next_state (model_learning/Model_learning.py:210-229, 471-494, 685-718).
+extern "C" int mcp_rollout_tvl(const mcp_model* model, const mcp_tvl_policy* tvl, const mcp_meas* meas, const mcp_noise* noise, int M, int T,
+                               int particle_pred, const double* x0, double* states, double* inputs, double* jac, double* mu, double* var,
+                               uint32_t* status, void* stream) {
+  const int crc = closed_loop_checks(model && tvl && noise && x0 && states && inputs && status, M, T, model, meas, false,
+                                     [&] { return tvl_policy_check(model, tvl, T); });
+  if (crc != MCP_OK) return crc;
+  OpenArgsTvl<true> a;
+  const int maxdeg = open_fill(a, model, noise, M, T, particle_pred, x0, nullptr, M, nullptr, states, mu, var, T == 1 ? nullptr : jac, status);
+  a.pd = tvl_as_pd(tvl);
+  a.inputs = inputs;
+  a.tv.gain = tvl->gain, a.tv.ff = tvl->ff, a.tv.gain_rows = tvl->gain_rows, a.tv.ff_rows = tvl->ff_rows;
+  hipStream_t st = (hipStream_t)stream;
+  if (meas_active(meas)) {
+    a.ms = *meas;
+    return launch_open_tiles<true, true, false, true>(a, maxdeg, var != nullptr, st);
+  }
+  OpenArgsTvl<false> b;
+  static_cast<OpenArgsPd&>(b) = a;
+  b.tv = a.tv;
+  return launch_open_tiles<true, false, false, true>(b, maxdeg, var != nullptr, st);
+}
+
 // ---------------------------------------------------------------------------------------
 // Reverse-time sweep of the open-loop rollout: what autograd's backward does through the step loop of MC_PILCO.rollout
 // (MC_PILCO.py:347-373) over get_next_state (Model_learning.py:210-229, 471-494, 685-718), from the record alone.
@@ -597,9 +704,31 @@ template <bool PMS>
 struct OpenBwdArgsPid : std::conditional<PMS, OpenBwdArgsPdMeas, OpenBwdArgsPd>::type {
   mcp_pid_term pid;
 };
-template <bool FB, bool PMS = false, bool PID = false>
+// TIME-VARYING LINEAR form of the sweep (template TVL with FB, with or without PMS, mcp_rollout_tvl_bwd): stage B' is the feedback form's
+// (abar through the squashing); stage C takes the dense pull
+//   lambda_r[s] -= sum_k gain[r][k][s] abar_k       (measured form: on ybar_r[s], through the filter's adjoint unchanged)
+// with gain[r] brought by the loader beside the row.  The parameter gradient is PER ROW: one partial per workgroup,
+//   g_part[tile][r][k][s] = sum_p abar[p][k] e_r[p][s]  (s < S),   g_part[tile][r][k][S] = sum_p abar[p][k],   e_r = target_traj[r] - x_r (or y_r)
+// over the tile's valid trajectories p in a fixed order.  The sum lives in WAVE 1, behind the chain: abar is double-buffered by row
+// parity, and in the iteration in which wave 0 runs row r the loader first reduces row r + 1 out of the buffer half it is about to refill
+// (16 entries (k, s) at a time, each quarter of the wave adding four trajectories and the quarters meeting by the row / half swaps:
+// (p 0-3 + p 4-7) + (p 8-11 + p 12-15), a fixed tree), then loads row r - 1 into it; row 0 is reduced behind the loop.  A reduction across
+// the 16 lanes p of wave 0 would put U (S + 1) / 4 four-step lane reductions on every row of the serial chain instead.  One lane per
+// entry adding all 16 trajectories was measured first: the loader then finishes behind the chain (sweep 0.69 against the PD twin's 0.47 ms
+// at M = 400, T = 150, profiles/NOTES.md part AE).
+template <bool PMS>
+struct OpenBwdArgsTvl : std::conditional<PMS, OpenBwdArgsPdMeas, OpenBwdArgsPd>::type {
+  const double* gain;  // [gain_rows][U][S]
+  int gain_rows;
+  double* g_part;      // [tiles][T][U][S + 1] or NULL
+};
+template <bool FB, bool PMS = false, bool PID = false, bool TVL = false>
 struct OpenBwdArgsOf {
   typedef OpenBwdArgs type;
+};
+template <bool PMS>
+struct OpenBwdArgsOf<true, PMS, false, true> {
+  typedef OpenBwdArgsTvl<PMS> type;
 };
 template <>
 struct OpenBwdArgsOf<true, false, false> {
@@ -621,8 +750,10 @@ struct OpenBwdLayout {
   int ul, gul, tgl, abl, ktab, gnl;          // feedback form: inputs | g_inputs | target row (double buffers) | abar | kpos, kvel | gains^2
   int yml, car, mtab;                        // measured feedback form: measurement rows (double buffer) | the filter's carries | pvel, ppos
   int itl, gil;                              // integral form: the integral's rows (double buffer; stage B' leaves the carry there) | sqrt_ki^2, i_max
+  int gnr;                                   // time-varying form: the gain rows [2][U][S] (double buffer); abar is [2][OB_PT][U] there
 };
-__host__ __device__ inline OpenBwdLayout open_bwd_layout(int S, int G, int D, bool fb = false, int U = 0, bool pms = false, bool pid = false) {
+__host__ __device__ inline OpenBwdLayout open_bwd_layout(int S, int G, int D, bool fb = false, int U = 0, bool pms = false, bool pid = false,
+                                                         bool tvl = false) {
   OpenBwdLayout L;
   int o = 0;
   auto take = [&](int n) {
@@ -641,7 +772,7 @@ __host__ __device__ inline OpenBwdLayout open_bwd_layout(int S, int G, int D, bo
   L.ul = fb ? take(2 * OB_PT * U) : 0;
   L.gul = fb ? take(2 * OB_PT * U) : 0;
   L.tgl = fb ? take(2 * S) : 0;
-  L.abl = fb ? take(OB_PT * U) : 0;
+  L.abl = fb ? take((tvl ? 2 : 1) * OB_PT * U) : 0;
   L.ktab = fb ? take(MCP_MAX_STATE) : 0;  // ints: kpos | kvel (per state component: the input that reads it as position / velocity, or -1)
   L.gnl = fb ? take(2 * MCP_MAX_INPUT) : 0;  // sqrt_kp^2 | sqrt_kd^2
   L.yml = pms ? take(2 * OB_PT * S) : 0;
@@ -649,18 +780,20 @@ __host__ __device__ inline OpenBwdLayout open_bwd_layout(int S, int G, int D, bo
   L.mtab = pms ? take(MCP_MAX_STATE) : 0;    // ints: pvel (per state component: the velocity of the pair it is the position of, or -1) | ppos (the converse)
   L.itl = pid ? take(2 * OB_PT * U) : 0;
   L.gil = pid ? take(2 * MCP_MAX_INPUT) : 0;  // the gain table's second half: sqrt_ki^2 | i_max
+  L.gnr = tvl ? take(2 * U * S) : 0;
   L.total = o;
   return L;
 }
 
-template <bool FB, bool PMS = false, bool PID = false>
-__global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBwdArgsOf<FB, PMS, PID>::type a) {
+template <bool FB, bool PMS = false, bool PID = false, bool TVL = false>
+__global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBwdArgsOf<FB, PMS, PID, TVL>::type a) {
   static_assert(FB || !PMS, "the measurement model belongs to the feedback form");
   static_assert(FB || !PID, "the integral term belongs to the feedback form");
+  static_assert((FB && !PID) || !TVL, "the time-varying law is a feedback form of its own");
   extern __shared__ double smem[];
   const int S = a.S, U = a.U, G = a.G, D = a.D, M = a.M, T = a.T, nna = a.nna, na = a.na;
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const OpenBwdLayout L = open_bwd_layout(S, G, D, FB, U, PMS, PID);
+  const OpenBwdLayout L = open_bwd_layout(S, G, D, FB, U, PMS, PID, TVL);
   const int GD = G * D, RP = L.rp;
   double* rec = smem + L.rec;
   double* xsl = smem + L.xs;
@@ -687,6 +820,8 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
   int* ppos = pvel + MCP_MAX_STATE;
   double* itl = smem + L.itl;  // (integral form)
   double* gil = smem + L.gil;
+  double* gnr = smem + L.gnr;  // (time-varying form)
+  (void)gnr;
   const int m0 = blockIdx.x * OB_PT;
 
   if (tid < S) {  // which GP a component integrates, as the forward kernel decides it
@@ -705,7 +840,7 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
     velof[s] = g_pos >= 0 ? a.vel[g_pos] : -1;
     zplain[s] = zp;
     zang[s] = za;
-    if constexpr (FB) {
+    if constexpr (FB && !TVL) {
       int kp = -1, kv = -1;
       for (int k = 0; k < U; ++k) {
         if (a.pd.pos[k] == s) kp = k;
@@ -724,7 +859,7 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
       ppos[s] = pp;
     }
   }
-  if constexpr (FB) {
+  if constexpr (FB && !TVL) {
     if (tid >= 64 + OB_PT && tid < 64 + OB_PT + U) {
       const int k = tid - 64 - OB_PT;
       const double kp = a.pd.sqrt_kp[k], kd = a.pd.sqrt_kd[k];
@@ -744,6 +879,8 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
   for (int it = tid; it < 2 * OB_PT * S; it += OB_NT) lam[it] = 0.0;
   if constexpr (PMS)
     for (int it = tid; it < 2 * OB_PT * S; it += OB_NT) car[it] = 0.0;
+  if constexpr (TVL)  // (the absent trajectories of a ragged tile never write their abar)
+    for (int it = tid; it < 2 * OB_PT * U; it += OB_NT) abl[it] = 0.0;
   __syncthreads();
   int tl = 1;
   for (int p = 0; p < OB_PT; ++p) tl = imax(tl, lenl[p]);
@@ -778,6 +915,8 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
         }
       }
       for (int s = l; s < S; s += 64) tgl[b * S + s] = a.pd.target_traj[(size_t)r * S + s];
+      if constexpr (TVL)
+        for (int it = l; it < U * S; it += 64) gnr[b * U * S + it] = a.gain[(a.gain_rows == 1 ? (size_t)0 : (size_t)r * U * S) + it];
     }
     for (int it = l; it < OB_PT * GD; it += 64) {
       const int p = it / GD, e = it - p * GD;
@@ -785,11 +924,45 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
     }
   };
 
+  // time-varying form, the loader's other work (64 lanes): the row's partial of the parameter gradient, from the row's buffer half `bb`
+  // and the abar of its parity -- the tile's valid trajectories are added in a fixed tree
+  auto reduce_row = [&](int r, int bb, int l) {
+    if constexpr (TVL) {
+      if (!a.g_part) return;
+      const int npv = imin(OB_PT, M - m0);
+      const double* ab = abl + (r & 1) * OB_PT * U;
+      const double* er = (PMS ? yml : xsl) + bb * OB_PT * S;
+      double* out = a.g_part + ((size_t)blockIdx.x * T + r) * U * (S + 1);
+      const int pq = 4 * (l >> 4);  // this quarter of the wave adds trajectories pq .. pq + 3; the quarters meet by the row / half swaps
+      for (int i0 = 0; i0 < U * (S + 1); i0 += 16) {  // (uniform: the swaps want every lane)
+        const int it = i0 + (l & 15);
+        const bool on = it < U * (S + 1);
+        const int k = on ? it / (S + 1) : 0, s = on ? it - k * (S + 1) : 0;
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int p = pq + i;
+          const double v = s < S ? ab[p * U + k] * (tgl[bb * S + s] - er[p * S + s]) : ab[p * U + k];
+          acc += p < npv ? v : 0.0;  // (an absent trajectory's row of the buffer was never written)
+        }
+        acc = sum_xor32(sum_xor16(acc));  // (p 0-3 + p 4-7) + (p 8-11 + p 12-15), the same bits in every quarter
+        if (on && l < 16) out[it] = acc;
+      }
+    }
+  };
+
   int b = 0, lc = 0;
   // feedback form: this lane's inputs q, q + 4, ... of trajectory p and the running sums of their gain gradients
   double fkp[OB_KMAX], fkd[OB_KMAX], fum[OB_KMAX], gkp[OB_KMAX], gkd[OB_KMAX];
   int fpos[OB_KMAX], fvel[OB_KMAX];
-  if constexpr (FB) {
+  if constexpr (TVL) {
+#pragma unroll
+    for (int i = 0; i < OB_KMAX; ++i) {
+      const int k = (lane >> 4) + 4 * i;
+      fum[i] = k < U ? a.pd.u_max[k] : 1.0;
+    }
+  }
+  if constexpr (FB && !TVL) {
 #pragma unroll
     for (int i = 0; i < OB_KMAX; ++i) {
       const int k = (lane >> 4) + 4 * i;
@@ -815,6 +988,7 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
   __syncthreads();
   for (int r = tl - 1; r >= 0; --r) {
     if (wv == 1) {
+      if (r < tl - 1) reduce_row(r + 1, b ^ 1, lane);  // (before that half is refilled)
       if (r > 0) load_row(r - 1, b ^ 1, lane);
     } else {
       const int p = lane & 15, q = lane >> 4;
@@ -858,9 +1032,11 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
                 const double th = ull[(b * OB_PT + p) * U + k] / fum[i];
                 ab = gu * (1.0 - th * th);
               }
-              abl[p * U + k] = ab;
-              gkp[i] += 2.0 * fkp[i] * (tg[fpos[i]] - ec[fpos[i]]) * ab;
-              gkd[i] += 2.0 * fkd[i] * (tg[fvel[i]] - ec[fvel[i]]) * ab;
+              abl[(TVL ? (r & 1) * OB_PT * U : 0) + p * U + k] = ab;
+              if constexpr (!TVL) {
+                gkp[i] += 2.0 * fkp[i] * (tg[fpos[i]] - ec[fpos[i]]) * ab;
+                gkd[i] += 2.0 * fkd[i] * (tg[fvel[i]] - ec[fvel[i]]) * ab;
+              }
               if constexpr (PID) {
                 double* ir = itl + (b * OB_PT + p) * U + k;
                 const double iv = *ir;
@@ -891,7 +1067,19 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
             v += gzl[p * D + nna + zang[s]] * cs - gzl[p * D + nna + na + zang[s]] * sn;
           }
         }
-        if constexpr (FB && !PMS) {
+        // time-varying form: the dense pull of the law on component c of the row it read
+        auto tvl_pull = [&](int c) {
+          const double* gr = gnr + b * U * S + c;
+          const double* ab = abl + (r & 1) * OB_PT * U + p * U;
+          double y = 0.0;
+          for (int k = 0; k < U; ++k) y -= gr[k * S] * ab[k];
+          return y;
+        };
+        (void)tvl_pull;
+        if constexpr (TVL && !PMS) {
+          if (r <= len - 1) v += tvl_pull(s);
+        }
+        if constexpr (FB && !PMS && !TVL) {
           if (r <= len - 1) {
             const int kp = kpos[s], kv = kvel[s];
             if (kp >= 0) v -= gnl[kp] * abl[p * U + kp];
@@ -903,6 +1091,7 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
         if constexpr (PMS) {
           if (r <= len - 1) {
             auto ybar = [&](int c) {  // the policy's pull on component c of the measurement
+              if constexpr (TVL) return tvl_pull(c);
               const int kp = kpos[c], kv = kvel[c];
               double y = 0.0;
               if (kp >= 0) y -= gnl[kp] * abl[p * U + kp];
@@ -946,7 +1135,10 @@ __global__ __launch_bounds__(OB_NT) void rollout_open_bwd_kernel(typename OpenBw
     if (lenl[p] > 0)
       for (int s = q; s < S; s += 4) a.g_x0[(size_t)(m0 + p) * S + s] = lam[(lc * OB_PT + p) * S + s];
   }
-  if constexpr (FB) {
+  if constexpr (TVL) {
+    if (wv == 1) reduce_row(0, b ^ 1, lane);  // (row 0's abar came out of the last iteration)
+  }
+  if constexpr (FB && !TVL) {
     if (wv == 0 && a.g_gains) {
       const int p = lane & 15, q = lane >> 4;
       if (lenl[p] > 0) {
@@ -976,14 +1168,14 @@ static void open_bwd_fill(OpenBwdArgs& a, const mcp_model* model, int M, int T, 
   a.g_x0 = g_x0;
   a.g_u = g_u;
 }
-// (at every compiled limit at once the layout takes 72 KB, the feedback form 89 KB, the measured form 98 KB, the integral 2 KB more)
-template <bool FB, bool PMS, bool PID = false>
-static int launch_open_bwd(const typename OpenBwdArgsOf<FB, PMS, PID>::type& a, hipStream_t st) {
-  const OpenBwdLayout L = open_bwd_layout(a.S, a.G, a.D, FB, a.U, PMS, PID);
+// (at every compiled limit at once the layout takes 72 KB, the feedback form 89 KB, the measured form 98 KB, the integral 2 KB more, the time-varying law 3 KB more)
+template <bool FB, bool PMS, bool PID = false, bool TVL = false>
+static int launch_open_bwd(const typename OpenBwdArgsOf<FB, PMS, PID, TVL>::type& a, hipStream_t st) {
+  const OpenBwdLayout L = open_bwd_layout(a.S, a.G, a.D, FB, a.U, PMS, PID, TVL);
   const size_t lds = (size_t)L.total * sizeof(double);
   if (lds > MCP_LDS_LIMIT) return MCP_ERR_LIMIT;
-  MCP_ENSURE_MAX_LDS((rollout_open_bwd_kernel<FB, PMS, PID>));
-  hipLaunchKernelGGL((rollout_open_bwd_kernel<FB, PMS, PID>), dim3((a.M + OB_PT - 1) / OB_PT), dim3(OB_NT), lds, st, a);
+  MCP_ENSURE_MAX_LDS((rollout_open_bwd_kernel<FB, PMS, PID, TVL>));
+  hipLaunchKernelGGL((rollout_open_bwd_kernel<FB, PMS, PID, TVL>), dim3((a.M + OB_PT - 1) / OB_PT), dim3(OB_NT), lds, st, a);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
 }
@@ -1056,4 +1248,31 @@ extern "C" int mcp_rollout_pid_bwd(const mcp_model* model, const mcp_pd_policy* 
                                    const double* states, const double* inputs, const double* jac, const double* g_states, const double* g_inputs,
                                    double* g_gains, double* g_x0, void* stream) {
   return pd_bwd_dispatch(model, pd, meas, M, T, states, inputs, jac, g_states, g_inputs, g_gains, g_x0, stream, pid);
+}
+
+// Reverse-time sweep of mcp_rollout_tvl (the dense pull and the per-row partials: OpenBwdArgsTvl above): replaces autograd's backward
+// (MC_PILCO.py:522) through the loops named at the forward entry with a torch policy in them.  g_part [ceil(M/16)][T][U][S+1].
+extern "C" int mcp_rollout_tvl_bwd(const mcp_model* model, const mcp_tvl_policy* tvl, const mcp_meas* meas, int M, int T, const double* states,
+                                   const double* inputs, const double* jac, const double* g_states, const double* g_inputs, double* g_part,
+                                   double* g_x0, void* stream) {
+  const int crc = closed_loop_checks(model && tvl && states && inputs && g_states && (jac || T <= 1), M, T, model, meas, true,
+                                     [&] { return tvl_policy_check(model, tvl, T); });
+  if (crc != MCP_OK) return crc;
+  if (!g_x0 && !g_part) return MCP_OK;  // nothing asked for
+  OpenBwdArgsTvl<true> a;
+  memset(&a, 0, sizeof(a));
+  open_bwd_fill(a, model, M, T, states, nullptr, jac, g_states, g_x0, nullptr);
+  a.pd = tvl_as_pd(tvl);
+  a.inputs = inputs;
+  a.g_inputs = g_inputs;
+  a.gain = tvl->gain, a.gain_rows = tvl->gain_rows, a.g_part = g_part;
+  hipStream_t st = (hipStream_t)stream;
+  if (meas_active(meas)) {
+    a.ms = *meas;
+    return launch_open_bwd<true, true, false, true>(a, st);
+  }
+  OpenBwdArgsTvl<false> b;
+  static_cast<OpenBwdArgsPd&>(b) = a;
+  b.gain = a.gain, b.gain_rows = a.gain_rows, b.g_part = a.g_part;
+  return launch_open_bwd<true, false, false, true>(b, st);
 }

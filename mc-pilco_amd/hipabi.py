@@ -99,6 +99,13 @@ class PIDTerm(C.Structure):
     _fields_ = [("on", C.c_int32), ("sqrt_ki", dptr), ("i_max", C.c_double * MAX_INPUT), ("dt", C.c_double), ("integ", dptr)]
 
 
+class TVLPolicy(C.Structure):
+    """mcp_tvl_policy: the time-varying linear feedback law a_t = gain[t] (target[t] - r_t) + ff[t] (gain_rows == 1: one matrix for all
+    rows; ff_rows == 0: no feedforward)."""
+    _fields_ = [("U", C.c_int32), ("S", C.c_int32), ("squash", C.c_int32), ("gain_rows", C.c_int32), ("ff_rows", C.c_int32),
+                ("target_rows", C.c_int32), ("u_max", C.c_double * MAX_INPUT), ("gain", dptr), ("ff", dptr), ("target_traj", dptr)]
+
+
 class OptState(C.Structure):
     _fields_ = [("step", C.c_int64), ("attempt", C.c_int64), ("pending", C.c_int64), ("adam_t", C.c_int64), ("total_attempts", C.c_int64),
                 ("es2", C.c_double), ("cost_prev", C.c_double)]
@@ -206,6 +213,10 @@ _SIGS = {
                                   C.c_int, dptr, dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
     "mcp_rollout_pid_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(PDPolicy), C.POINTER(PIDTerm), C.POINTER(Meas), C.c_int, C.c_int, dptr, dptr, dptr,
                                       dptr, dptr, dptr, dptr, dptr]),
+    "mcp_rollout_tvl": (C.c_int, [C.POINTER(Model), C.POINTER(TVLPolicy), C.POINTER(Meas), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr,
+                                  dptr, dptr, dptr, dptr, dptr, dptr]),
+    "mcp_rollout_tvl_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(TVLPolicy), C.POINTER(Meas), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr,
+                                      dptr, dptr]),
     "mcp_rollout_mlp_meas": (C.c_int, [C.POINTER(Model), C.POINTER(MLPPolicy), C.POINTER(Meas), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr,
                                        dptr, dptr, dptr, dptr, dptr, dptr]),
     "mcp_rollout_mlp_meas_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(MLPPolicy), C.POINTER(Meas), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr,

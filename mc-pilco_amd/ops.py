@@ -782,6 +782,83 @@ class PackedPID(PackedPD):
         return c
 
 
+class PackedTVL:
+    """mcp_tvl_policy of a ``Policy.TV_linear_controller``: the LIVE tensors ``gain`` ([rows, U, S], or [U, S] shared by every row) and
+    ``ff`` ([rows, U], or None) are kept as they are -- every launch reads them where they lie, so an optimizer's in-place updates are seen --
+    and the target trajectory is held on the device.  The sweep leaves one partial [T, U, S + 1] per workgroup of ``grad_tile``
+    trajectories; ``split_grad`` adds them (and the rows, for a shared gain) and cuts the sum into the two tensors' shapes."""
+
+    fwd, bwd = ("mcp_rollout_tvl",) * 2, ("mcp_rollout_tvl_bwd",) * 2
+    meas_slot = True  # (one entry for both forms: the measurement model or NULL always stands between the policy and the rest)
+    fwd_outputs = ("jac", "mu", "var")
+    grad_tile = 16  # one partial per workgroup of the sweep
+
+    def __init__(self, policy):
+        self.gain, self.ff = policy.gain, policy.ff
+        self.params = [self.gain] + ([self.ff] if self.ff is not None else [])
+        self.S, self.U = int(policy.state_dim), int(policy.input_dim)
+        self.shared = self.gain.dim() == 2
+        if tuple(self.gain.shape[-2:]) != (self.U, self.S) or self.gain.dim() not in (2, 3):
+            raise RuntimeError("the gain must be [rows, U, S] or [U, S]")
+        if self.ff is not None and (self.ff.dim() != 2 or int(self.ff.shape[1]) != self.U):
+            raise RuntimeError("the feedforward must be [rows, U]")
+        self.shapes = [tuple(q.shape) for q in self.params]
+        dev = _dev(self.gain.device)
+        if policy.target_traj is None:
+            raise RuntimeError("the controller has no target trajectory")
+        self.target_traj = _t(policy.target_traj, dev).reshape(-1, self.S).contiguous()
+        self.squash = bool(policy.flg_squash)
+        self.u_max = np.full(self.U, float(policy.u_max)) if np.isscalar(policy.u_max) else np.asarray(policy.u_max, dtype=np.float64).reshape(-1)
+        if self.u_max.size != self.U or self.U > abi.MAX_INPUT or self.S > abi.MAX_STATE:
+            raise RuntimeError("u_max must be a scalar or hold one bound per input (at most %d inputs, %d states)" % (abi.MAX_INPUT, abi.MAX_STATE))
+        self.device = dev
+
+    def tensors(self):
+        return self.params
+
+    def grad_shape_of(self, T):
+        return (int(T), self.U, self.S + 1)  # (the sweep's partial has one row per policy evaluation)
+
+    def check(self, model, T):
+        if self.S != model.S or self.U != model.U:
+            raise RuntimeError("the controller is for %d states and %d inputs, the model has %d and %d" % (self.S, self.U, model.S, model.U))
+        rows = [int(self.target_traj.shape[0])] + ([] if self.shared else [int(self.gain.shape[0])]) + ([int(self.ff.shape[0])] if self.ff is not None else [])
+        if T < 1 or min(rows) < T:
+            raise RuntimeError("the gain, the feedforward and the target trajectory must have at least %d rows (have %s)" % (T, rows))
+
+    def to_c(self, gain, ff=None):
+        """The descriptor over (gain, ff): contiguous float64 GPU tensors of the parameters' shapes."""
+        for t, shp in zip((gain, ff), self.shapes):
+            if t.dtype != DT or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shp:
+                raise RuntimeError("the gain and the feedforward must be contiguous float64 GPU tensors of their declared shapes")
+        c = abi.TVLPolicy()
+        c.U, c.S, c.squash = self.U, self.S, int(self.squash)
+        c.gain_rows = 1 if self.shared else int(gain.shape[0])
+        c.ff_rows = 0 if ff is None else int(ff.shape[0])
+        c.target_rows = int(self.target_traj.shape[0])
+        for k in range(self.U):
+            c.u_max[k] = float(self.u_max[k])
+        c.gain, c.ff, c.target_traj = gain.data_ptr(), None if ff is None else ff.data_ptr(), self.target_traj.data_ptr()
+        return c
+
+    def split_grad(self, raw, want):
+        """The sweep's partials [tiles, T, U, S + 1] -> the gradients of (gain, ff) in their shapes (None where ``want`` is False): the slabs
+        added in torch's fixed order, the rows too for a shared gain; rows beyond T of a longer tensor get zeros."""
+        tot, T = raw.sum(0), int(raw.shape[1])
+        g_gain = g_ff = None
+        if want[0]:
+            g = tot[..., :self.S]
+            if self.shared:
+                g_gain = g.sum(0)
+            else:
+                g_gain = g.new_zeros(self.shapes[0])
+                g_gain[:T] = g
+        if self.ff is not None and want[1]:
+            g_ff = tot.new_zeros(self.shapes[1])
+            g_ff[:T] = tot[..., self.S]
+        return [g_gain] + ([g_ff] if self.ff is not None else [])
+
+
 class PackedMLP:
     """mcp_mlp_policy of a ``Policy.MLP_policy``: the parameter tensors (W0, b0, [W1, b1], Wout, bout) are kept as they are -- every
     launch takes the LIVE tensors, so an optimizer's in-place updates are seen.  Features f = [x[non_angle], sin x[angle], cos x[angle]]
@@ -935,6 +1012,8 @@ def _entry(packed, names, plain, marg, nz, p_drop, integ=None):
     are; else p_drop > 0 the dropout entry; else the plain or measured one with ``plain`` behind the measurement."""
     if integ is not None:
         return names[4], [C.byref(packed.term_c(integ)), marg[0] if marg else None] + plain
+    if getattr(packed, "meas_slot", False):  # (one entry for the true state and the measurement: the model or NULL, then ``plain``)
+        return names[0][0], [marg[0] if marg else None] + plain
     tc = packed.track_c() if names[2] else None
     rc = packed.res_c() if len(names) > 3 and names[3] else None
     if len(names) > 5 and names[5] and getattr(packed, "history", 1) > 1:  # (memory: the depth, the track or NULL, the term or NULL, the rest)
@@ -983,7 +1062,8 @@ def _closed_sweep(model, packed, tensors, states, inputs, jac, g_states, g_input
     (packed.bwd_pid)."""
     T, M, dev = int(states.shape[0]), int(states.shape[1]), states.device
     g_x0 = torch.empty(M, model.S, dtype=DT, device=dev) if want_x0 else None
-    raw = torch.empty(((M + packed.grad_tile - 1) // packed.grad_tile,) + packed.grad_shape, dtype=DT, device=dev) if want_params else None
+    grad_shape = packed.grad_shape_of(T) if hasattr(packed, "grad_shape_of") else packed.grad_shape  # (a per-row gradient: its rows are the launch's)
+    raw = torch.empty(((M + packed.grad_tile - 1) // packed.grad_tile,) + grad_shape, dtype=DT, device=dev) if want_params else None
     pc = packed.to_c(*tensors)
     marg = _meas_arg(meas, T, M, meas_buf)
     nz = noise.to_c() if p_drop > 0.0 else None  # (only the keep decisions are drawn again)
@@ -1030,7 +1110,9 @@ class RolloutClosedFunction(torch.autograd.Function):
         raw, g_x0 = _closed_sweep(ctx.model, packed, tensors, states, inputs, jac, gs, gi, any(want), want_x0, ctx.meas, meas_buf, ctx.noise, ctx.p_drop,
                                   integ)
         grads = [None] * n
-        if raw is not None:
+        if raw is not None and hasattr(packed, "split_grad"):  # (a gradient per row: the policy's own cut of the partials)
+            grads = packed.split_grad(raw, want)
+        elif raw is not None:
             flat, o = raw.sum(0).reshape(-1), 0  # the trajectories' / workgroups' rows added in torch's fixed order
             for i, shp in enumerate(packed.shapes):  # (only the parameters that need one get a gradient)
                 k = int(np.prod(shp))
@@ -1073,6 +1155,14 @@ def rollout_pd(model: PackedModel, pd: PackedPD, noise: Optional[NoiseSpec], x0,
     ``pd`` a PackedPID (``Policy.PID_controller``): the law with the clamped integral of the position error, mcp_rollout_pid and its sweep
     (gradients to ``sqrt_Ki_gains`` too); the integral [T,M,U] is left in ``pd.integ`` (not differentiable)."""
     return _rollout_closed("rollout_pd", "the gains", model, pd, noise, x0, T, particle_pred, status, meas)
+
+
+def rollout_tvl(model: PackedModel, packed: PackedTVL, noise: Optional[NoiseSpec], x0, T, particle_pred=True, status=None,
+                meas: Optional[MeasSpec] = None):
+    """Closed-loop rollout under a time-varying linear feedback law (``Policy.TV_linear_controller``) in ONE launch: arguments, return and
+    recording rule of ``rollout_pd``, with u_t = squash(gain[t] (target[t] - r_t) + ff[t]) in the PD law's place (mcp_rollout_tvl and its
+    sweep); the gradients go to ``gain`` and ``ff`` where they require one, per row, and to x0.  The target gets no gradient."""
+    return _rollout_closed("rollout_tvl", "the gain and the feedforward", model, packed, noise, x0, T, particle_pred, status, meas)
 
 
 def rollout_mlp(model: PackedModel, mlp: PackedMLP, noise: Optional[NoiseSpec], x0, T, particle_pred=True, status=None,

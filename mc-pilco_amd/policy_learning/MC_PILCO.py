@@ -210,12 +210,13 @@ class MC_PILCO(torch.nn.Module):
         if isinstance(pol, _Policy.Sum_of_gaussians):  # (on measurements the kernels carry the filter's states per particle, mcp_meas)
             noise, pos_noise, p = self._rollout_noise(T, p_dropout, n_pos=n_pos)
             return self._fused(*ops.rollout(model_of(), pol.packed(), noise, x0, T, p, meas=meas_of(pos_noise), gp_sharding=self.gp_sharding))
-        # the closed loop under the PD law or the tanh MLP: one launch (and one sweep in backward); the eps draws, and for an MLP with
+        # the closed loop under the PD law, the time-varying linear law or the tanh MLP: one launch (and one sweep in backward); the eps draws, and for an MLP with
         # dropout (flg_drop) the masks of its hidden units -- the PD law has none
         mlp = isinstance(pol, _Policy.MLP_policy)
         if mlp and measured and int(getattr(pol, "history", 1)) > 1:
             return None  # (an MLP with memory has no fused form on simulated measurements: the step loop, which holds its window)
-        op = ops.rollout_pd if isinstance(pol, _Policy.PD_controller) else ops.rollout_mlp if mlp else None
+        op = (ops.rollout_pd if isinstance(pol, _Policy.PD_controller) else ops.rollout_tvl if isinstance(pol, _Policy.TV_linear_controller)
+              else ops.rollout_mlp if mlp else None)
         model = model_of() if op is not None and self.fused_feedback else None
         if model is None or not pol.fusable(model, T):
             return None
@@ -240,7 +241,7 @@ class MC_PILCO(torch.nn.Module):
         if self._world()[0] > 1:
             # its noise (torch draws inside get_next_state / the policy's dropout) is per LOCAL particle: identically seeded ranks
             # would simulate correlated shards, not the particles one GPU would
-            raise NotImplementedError("particle sharding needs the fused rollout (Sum_of_gaussians, PD_controller or MLP_policy policy + a model "
+            raise NotImplementedError("particle sharding needs the fused rollout (Sum_of_gaussians, PD_controller, TV_linear_controller or MLP_policy policy + a model "
                                       "with a fused layout)")
         step = self._step_fused(T)
         xs = [x0]
@@ -844,7 +845,7 @@ class MC_PILCO4PMS(MC_PILCO):
             return out
         self.last_status = None  # (no fused launch)
         if self._world()[0] > 1:  # (per-LOCAL-particle torch draws: identically seeded ranks would simulate correlated shards)
-            raise NotImplementedError("particle sharding needs the fused rollout (fused=True, Sum_of_gaussians, PD_controller or MLP_policy "
+            raise NotImplementedError("particle sharding needs the fused rollout (fused=True, Sum_of_gaussians, PD_controller, TV_linear_controller or MLP_policy "
                                       "policy, a model with a fused layout)")
         std_pos = torch.tensor(np.asarray(self.std_meas_noise_sim)[pos], dtype=self.dtype, device=self.device)
         step = self._step_fused(T, n_pos=len(pos))

@@ -217,6 +217,101 @@ class PID_controller(PD_controller):
         return self.f_squash(self.sqrt_Kp_gains ** 2 * err[:, 0:h] + self.sqrt_Kd_gains ** 2 * err[:, h:] + self.sqrt_Ki_gains ** 2 * q)
 
 
+class TV_linear_controller(Policy):
+    """Feedforward sequence plus time-varying linear feedback around a reference (this project's own: the reference has none) -- the local
+    controller of trajectory optimisation (iLQR / TVLQR, guided policy search).  For row t, with e = target_traj[t] - state:
+        a[k] = sum_s gain[t][k][s] e[s] + ff[t][k];    u[k] = squash(a[k])
+    ``gain`` is [rows, U, S] (``flg_time_varying_gains=False``: [U, S], one matrix for every row), plain (not squared) and dense over all S
+    components -- no index layout applies, S may be odd and U need not be S / 2; ``ff`` is [rows, U] or None (no feedforward);
+    ``target_traj`` is [rows, S].  The error is the plain difference, not wrapped on angle components.  ``flg_train_gains`` /
+    ``flg_train_feedforward`` choose which of the two is a trainable Parameter.  ``from_pd`` builds a ``PD_controller``'s law as the special
+    case.  ``forward(states, t)`` is the torch formula of the step loop and of the system simulator; it is stateless and raises ValueError
+    for a row the tensors do not have.  As ``MC_PILCO``'s control policy it runs inside the fused closed loop (``packed()``: an
+    ops.PackedTVL, mcp_rollout_tvl and its sweep, whose parameter gradient is per row)."""
+
+    def __init__(self, state_dim, input_dim, gain, ff=None, target_traj=None, flg_time_varying_gains=True, flg_train_gains=True,
+                 flg_train_feedforward=True, flg_squash=True, u_max=1.0, dtype=torch.float64, device=torch.device("cpu")):
+        super().__init__(state_dim=state_dim, input_dim=input_dim, flg_squash=flg_squash, u_max=u_max, dtype=dtype, device=device)
+        self.flg_time_varying_gains = bool(flg_time_varying_gains)
+        self.target_traj = target_traj
+        gain = torch.as_tensor(gain, dtype=self.dtype).detach().clone().to(self.device)
+        want = (3 if self.flg_time_varying_gains else 2)
+        if gain.dim() != want or tuple(gain.shape[-2:]) != (int(input_dim), int(state_dim)):
+            raise ValueError("gain must be [rows, U, S] (flg_time_varying_gains=False: [U, S]), got %s" % (tuple(gain.shape),))
+        self.gain = torch.nn.Parameter(gain.contiguous(), requires_grad=bool(flg_train_gains))
+        self.ff = None
+        if ff is not None:
+            ff = torch.as_tensor(ff, dtype=self.dtype).detach().clone().to(self.device)
+            if ff.dim() != 2 or int(ff.shape[1]) != int(input_dim):
+                raise ValueError("ff must be [rows, U], got %s" % (tuple(ff.shape),))
+            self.ff = torch.nn.Parameter(ff.contiguous(), requires_grad=bool(flg_train_feedforward))
+
+    @classmethod
+    def from_pd(cls, pd_controller, T, flg_feedforward=True, **kwargs):
+        """The law of ``pd_controller`` (a PD_controller: input k reads position k and velocity S / 2 + k) over T rows:
+        gain[t][k][k] = sqrt_Kp[k]^2, gain[t][k][S / 2 + k] = sqrt_Kd[k]^2, ff = 0 (``flg_feedforward=False``: none).  Target, squashing,
+        bound, dtype and device are the controller's; ``kwargs`` go to the constructor."""
+        S, U, T = int(pd_controller.state_dim), int(pd_controller.input_dim), int(T)
+        with torch.no_grad():
+            kp2 = (pd_controller.sqrt_Kp_gains.detach().reshape(-1) ** 2).expand(U)
+            kd2 = (pd_controller.sqrt_Kd_gains.detach().reshape(-1) ** 2).expand(U)
+            g = torch.zeros(U, S, dtype=pd_controller.dtype, device=kp2.device)
+            idx = torch.arange(U, device=kp2.device)
+            g[idx, idx] = kp2
+            g[idx, S // 2 + idx] = kd2
+            tv = kwargs.pop("flg_time_varying_gains", True)
+            gain = g.unsqueeze(0).repeat(T, 1, 1) if tv else g
+            ff = torch.zeros(T, U, dtype=pd_controller.dtype, device=kp2.device) if flg_feedforward else None
+        args = dict(target_traj=pd_controller.target_traj, flg_squash=pd_controller.flg_squash, u_max=pd_controller.u_max,
+                    dtype=pd_controller.dtype, device=pd_controller.device)
+        args.update(kwargs)
+        return cls(S, U, gain, ff, flg_time_varying_gains=tv, **args)
+
+    def _rows(self):
+        rows = [int(np.shape(self.target_traj)[0])] if self.target_traj is not None else [0]
+        if self.flg_time_varying_gains:
+            rows.append(int(self.gain.shape[0]))
+        if self.ff is not None:
+            rows.append(int(self.ff.shape[0]))
+        return min(rows)
+
+    def packed(self) -> "ops.PackedTVL":
+        """mcp_tvl_policy over the LIVE tensors (rebuilt if a tensor or the target was replaced)."""
+        key = (self.gain.data_ptr(), None if self.ff is None else self.ff.data_ptr(), id(self.target_traj), self.flg_squash, id(self.u_max))
+        hit = self.__dict__.get("_packed_tvl")
+        if hit is None or hit[0] != key:
+            hit = self.__dict__["_packed_tvl"] = (key, ops.PackedTVL(self))
+        return hit[1]
+
+    def fusable(self, model, T):
+        """Whether T steps of this controller on ``model`` (an ops.PackedModel, or anything with ``S`` and ``U``) can run as the fused
+        closed loop: S and U are the model's and within the compiled limits, gain, ff and the target cover the horizon, and everything is
+        float64 on a GPU."""
+        S, U = int(self.state_dim), int(self.input_dim)
+        if U < 1 or U > ops.abi.MAX_INPUT or S > ops.abi.MAX_STATE:
+            return False
+        if int(getattr(model, "S", -1)) != S or int(getattr(model, "U", -1)) != U:
+            return False
+        tt = self.target_traj
+        if tt is None or np.ndim(tt) != 2 or int(np.shape(tt)[1]) != S or self._rows() < int(T) or int(T) < 1:
+            return False
+        if not np.isscalar(self.u_max) and np.asarray(self.u_max).size != U:
+            return False
+        tensors = [self.gain] + ([self.ff] if self.ff is not None else [])
+        return self.dtype == torch.float64 and all(q.dtype == torch.float64 and q.is_cuda for q in tensors)
+
+    def forward(self, states, t, p_dropout=0.0):
+        t = int(t)
+        if t < 0 or t >= self._rows():
+            raise ValueError("TV_linear_controller.forward: row %d is beyond the %d rows of gain / ff / target_traj" % (t, self._rows()))
+        states = states.reshape([-1, self.state_dim])
+        err = self.target_traj[t, :].reshape(1, -1) - states
+        a = err @ (self.gain[t] if self.flg_time_varying_gains else self.gain).T
+        if self.ff is not None:
+            a = a + self.ff[t].reshape(1, -1)
+        return self.f_squash(a)
+
+
 class MLP_policy(Policy):
     """Tanh multilayer perceptron (this project's own policy class; the reference has none).  Features as in
     ``Sum_of_gaussians_with_angles``, in the order f = [x[non_angle], sin x[angle], cos x[angle]] (both lists None: f = x); then
