@@ -711,6 +711,45 @@ int mcp_rollout_bwd(const mcp_model* model, const mcp_policy* policy, const mcp_
                     const double* g_inputs, double* g_log_ls, double* g_centers, double* g_weight, double* g_x0,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- trajectory optimisation on the model: linearisation and the iLQR backward pass (the project's own: the reference has no
+ * trajectory optimiser; mcp_tvl_policy is the controller these entries compute) --------------------------------------------------- */
+#define MCP_LQR_MAX_T 2048 /* rows of one mcp_lqr_pass / mcp_linearize call: the pass keeps two doubles per row in LDS, within the 64 KiB a launch gets unasked */
+/* Dense Jacobians of one model step along a recorded rollout: x_{t+1} ~ A_t dx + B_t da for t = 0 .. T - 2.  states [T][M][S] and jac
+ * [T-1][M][G][D]: what mcp_rollout_open_rec (or a closed-loop recording launch) wrote -- the mean form's record is the nominal of the GP
+ * mean model, a sampled form's has the sampling folded in.  A [T-1][M][S][S], B [T-1][M][S][U]; either may be NULL, both NULL: MCP_OK
+ * without a launch.  With row J_g = jac[t][m][g], na = n_not_angle, z = [x[not_angle], sin x[angle], cos x[angle], u]:
+ *   d delta_g / dx[not_angle[i]] = J_g[i];   d delta_g / dx[angle[j]] = J_g[na + j] cos x[angle[j]] - J_g[na + n_angle + j] sin x[angle[j]]
+ *   d delta_g / du[k] = J_g[na + 2 n_angle + k]
+ *   A = I + Ts E[not_vel[g], vel[g]] + sum_g (e_vel[g] + Ts/2 e_not_vel[g]) (d delta_g / dx)^T     (mcp_model's step maps; B alike, from d/du)
+ * A row of a component that no GP integrates is zero, as the rollouts write that component.  du_da [T][M][U] (NULL: ones; row T - 1 is
+ * not read) scales column k of B by du_da[t][m][k] -- the derivative of the squashing at the nominal, so that B refers to the pre-squash
+ * variable a of mcp_tvl_policy.  The operations are those of mcp_model_step_bwd / mcp_rollout_open_bwd row by row: g^T A and g^T B agree
+ * with those sweeps to rounding.  Only the model's index maps and Ts are read (no GP array).  MCP_ERR_ARG: model, states or jac NULL,
+ * M <= 0, T < 2, a model whose scalars or index lists model_ok refuses; MCP_ERR_LIMIT: a dimension beyond MCP_MAX_*, T > MCP_LQR_MAX_T.
+ * A refused call makes no HIP call.  Replaces torch.autograd.functional.jacobian through Model_learning.get_next_state
+ * (model_learning/Model_learning.py:210-229, 471-494, 685-718), T - 1 times. */
+int mcp_linearize(const mcp_model* model, int M, int T, const double* states, const double* jac, const double* du_da /* [T][M][U] or NULL = ones */,
+                  double* A, double* B, void* stream);
+/* The iLQR (Gauss-Newton) backward pass of M independent trajectories, ONE launch, one workgroup per trajectory.  states, jac, du_da as
+ * for mcp_linearize (A_t and B_t are composed in LDS and never written).  lx [T][M][S], lu [T][M][U]: the stage cost's gradient along the
+ * nominal; hxx [T][M][S], huu [T][M][U]: its DIAGONAL Hessians -- lu and huu in the pre-squash variable a (the caller's chain rule).
+ * reg >= 0 is added to the diagonal of Quu.  gain [M][T][U][S] (slab m is an mcp_tvl_policy gain tensor), kff [M][T][U], dv [M][2]:
+ *   row T - 1:  Vx = lx, Vxx = diag(hxx), gain = 0, kff = -lu / (huu + reg)
+ *   row t = T - 2 .. 0:  Qx = lx + A^T Vx, Qu = lu + B^T Vx, Qxx = diag(hxx) + A^T Vxx A, Qux = B^T Vxx A,
+ *     Quu = diag(huu) + B^T Vxx B + reg I = L L^T (Cholesky, its lower triangle read);  kff = -Quu^-1 Qu, gain = Quu^-1 Qux,
+ *     Vx = Qx + Qux^T kff,  Vxx = (W + W^T) / 2 with W = Qxx - Qux^T gain
+ *   dv[m] = (sum_t kff^T Qu, sum_t kff^T Quu kff), every row's term added in ascending t (row T - 1: Qu = lu, Quu = diag(huu + reg))
+ * Sign convention: mcp_tvl_policy's law is a = gain (x* - x) + ff, so with x* the nominal states the update is ff <- a_nominal +
+ * alpha kff and gain is used as written; the predicted change of the cost is alpha dv[0] + alpha^2 dv[1] / 2.
+ * A pivot <= 0 (row T - 1: huu + reg <= 0) raises MCP_STATUS_NOT_SPD, a non-finite operand or pivot MCP_STATUS_NAN; that trajectory's
+ * gain, kff and dv are then all NaN and the other trajectories are unaffected.  One thread per output element, every sum in index order,
+ * no atomics on results: bitwise reproducible, and a trajectory's bits depend neither on M nor on the other trajectories.
+ * MCP_ERR_ARG: a NULL pointer other than du_da, M <= 0, T < 2, reg negative or not finite (looked at with the sizes), a model as for
+ * mcp_linearize; MCP_ERR_LIMIT as there.  A refused call makes no HIP call. */
+int mcp_lqr_pass(const mcp_model* model, int M, int T, const double* states, const double* jac, const double* du_da /* [T][M][U] or NULL = ones */,
+                 const double* lx, const double* lu, const double* hxx, const double* huu, double reg, double* gain, double* kff, double* dv,
+                 uint32_t* status, void* stream);
+
 /* ---- cost (policy_learning/Cost_function.py) ------------------------------------------ */
 #define MCP_COST_CARTPOLE 0 /* cart_pole_cost, Cost_function.py:170-182                          */
 #define MCP_COST_TRAJ 1     /* saturated_distance_from_trajectory, Cost_function.py:124-147      */

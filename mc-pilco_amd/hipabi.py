@@ -17,6 +17,7 @@ MAX_GP, MAX_STATE, MAX_INPUT, MAX_GPDIM, MAX_PFEAT, MAX_BASIS, MAX_TRAIN = 8, 16
 MAX_BASIS_WIDE = 512  # B of a wide policy (P > 16 or U > 4): MCP_MAX_BASIS_WIDE
 MAX_HIDDEN = 64  # units of a hidden layer of mcp_mlp_policy: MCP_MAX_HIDDEN
 MAX_HIST = 4  # rows a policy with memory reads (mcp_mlp_hist.h): MCP_MAX_HIST
+LQR_MAX_T = 2048  # rows of one mcp_lqr_pass / mcp_linearize call: MCP_LQR_MAX_T
 OK = 0
 ERRORS = {-1: "MCP_ERR_ARG", -2: "MCP_ERR_LIMIT", -3: "MCP_ERR_WORKSPACE", -4: "MCP_ERR_LAUNCH", -5: "MCP_ERR_COMM"}
 ABI_VERSION = 7
@@ -217,6 +218,9 @@ _SIGS = {
                                   dptr, dptr, dptr, dptr, dptr, dptr]),
     "mcp_rollout_tvl_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(TVLPolicy), C.POINTER(Meas), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr,
                                       dptr, dptr]),
+    "mcp_linearize": (C.c_int, [C.POINTER(Model), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr]),
+    "mcp_lqr_pass": (C.c_int, [C.POINTER(Model), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr, dptr, dptr, C.c_double, dptr, dptr, dptr, dptr,
+                               dptr]),
     "mcp_rollout_mlp_meas": (C.c_int, [C.POINTER(Model), C.POINTER(MLPPolicy), C.POINTER(Meas), C.POINTER(Noise), C.c_int, C.c_int, C.c_int, dptr, dptr,
                                        dptr, dptr, dptr, dptr, dptr, dptr]),
     "mcp_rollout_mlp_meas_bwd": (C.c_int, [C.POINTER(Model), C.POINTER(MLPPolicy), C.POINTER(Meas), C.c_int, C.c_int, dptr, dptr, dptr, dptr, dptr,

@@ -654,6 +654,95 @@ def model_step(model: PackedModel, x, u, t, noise: Optional[NoiseSpec] = None, p
 
 
 # --------------------------------------------------------------------------------------
+# trajectory optimisation on the model: the dense linearisation of a record and the iLQR backward pass (no autograd)
+# --------------------------------------------------------------------------------------
+def _lqr_operands(dev, *named):
+    """The tensors of ``named`` = (name, tensor or None, shape) as the trajectory-optimisation entries take them -- contiguous float64 of that
+    shape on ``dev`` -- or ValueError: every dtype and shape is looked at first, then where the tensors live."""
+    for name, t, shape in named:
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != DT:
+            raise ValueError("%s must be a float64 tensor" % name)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError("%s must have the shape %s, not %s" % (name, list(shape), list(t.shape)))
+    for name, t, _ in named:
+        if t is None:
+            continue
+        if not t.is_cuda or t.device != dev:
+            raise ValueError("%s must be on the model's device %s, not on %s; there is no CPU path" % (name, dev, t.device))
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+    return [None if t is None else t.detach() for _, t, _ in named]
+
+
+def _lqr_sizes(model, states):
+    """(T, M) of a record's states [T,M,S]."""
+    if not isinstance(states, torch.Tensor) or states.dim() != 3 or states.shape[0] < 2 or states.shape[1] < 1:
+        raise ValueError("states must be a tensor [T,M,%d] with T >= 2 and M >= 1" % model.S)
+    if int(states.shape[0]) > abi.LQR_MAX_T:
+        raise ValueError("at most %d rows (got %d)" % (abi.LQR_MAX_T, int(states.shape[0])))
+    return int(states.shape[0]), int(states.shape[1])
+
+
+def rollout_open_record(model: PackedModel, x0, u, *, noise: Optional[NoiseSpec] = None, particle_pred=False, status=None):
+    """The recording open-loop launch without autograd (mcp_rollout_open_rec): arguments of ``rollout_open`` (no ragged lengths) ->
+    (states [T,M,S], jac [T-1,M,G,D], status) -- the operands of ``linearize`` and ``lqr_pass``.  The states carry the bits of
+    ``rollout_open``; the mean form's record (``particle_pred`` False) is the nominal trajectory of the GP mean model."""
+    for name, t in (("x0", x0), ("u", u)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError("rollout_open_record operates on GPU memory only (%s is not a GPU tensor); there is no CPU path" % name)
+    x0, u, T, _, noise, status = _open_operands(model, x0.detach(), u.detach(), None, None, noise, particle_pred, status)
+    M = int(x0.shape[0])
+    states, _, jac = _record_buffers(model.device, T, M, model.S, None, model.G, model.D, True)
+    nz = noise.to_c()
+    abi.check(abi.lib().mcp_rollout_open_rec(_mc(model), C.byref(nz), M, T, int(bool(particle_pred)), abi.ptr(x0), abi.ptr(u), int(u.shape[1]), None,
+                                             abi.ptr(states), None, None, abi.ptr(jac), abi.ptr(status), abi.stream()), "mcp_rollout_open_rec")
+    return states, jac, status
+
+
+def linearize(model: PackedModel, states, jac, du_da=None, want=(True, True)):
+    """Dense Jacobians of the model step along a recorded rollout in ONE launch (mcp_linearize): states [T,M,S] and jac [T-1,M,G,D] (the
+    record of the recording open-loop or closed-loop launches; the mean form's is the nominal of the GP mean model) -> A [T-1,M,S,S],
+    B [T-1,M,S,U] with x_{t+1} ~ A_t dx + B_t da.  ``du_da`` [T,M,U] scales B's columns (the derivative of the squashing at the nominal:
+    B then refers to the pre-squash variable of ``TV_linear_controller``); None: ones.  ``want`` = (A, B): an output not wanted is None and
+    is not computed.  No autograd.  ValueError for an operand of the wrong dtype, shape or device."""
+    T, M = _lqr_sizes(model, states)
+    states, jac, du_da = _lqr_operands(model.device, ("states", states, (T, M, model.S)), ("jac", jac, (T - 1, M, model.G, model.D)),
+                                       ("du_da", du_da, (T, M, model.U)))
+    A = torch.empty(T - 1, M, model.S, model.S, dtype=DT, device=model.device) if want[0] else None
+    B = torch.empty(T - 1, M, model.S, model.U, dtype=DT, device=model.device) if want[1] else None
+    abi.check(abi.lib().mcp_linearize(_mc(model), M, T, abi.ptr(states), abi.ptr(jac), abi.ptr(du_da), abi.ptr(A), abi.ptr(B), abi.stream()),
+              "mcp_linearize")
+    return A, B
+
+
+def lqr_pass(model: PackedModel, states, jac, lx, lu, hxx, huu, reg=0.0, du_da=None, status=None):
+    """The iLQR (Gauss-Newton) backward pass of M independent trajectories in ONE launch (mcp_lqr_pass): the record of ``linearize`` and the
+    stage cost's expansion along it -- gradients lx [T,M,S], lu [T,M,U], diagonal Hessians hxx [T,M,S], huu [T,M,U], the input terms in the
+    pre-squash variable when ``du_da`` is given -- -> (gain [M,T,U,S], kff [M,T,U], dv [M,2]).  gain[m] is a ``TV_linear_controller`` gain
+    tensor: with the nominal states as its target the step is ff <- a_nominal + alpha kff[m], and alpha dv[m,0] + alpha^2 dv[m,1] / 2 is the
+    predicted change of the cost.  ``reg`` >= 0 is added to the diagonal of Quu.  ``status``: an int32[1] the kernel ORs its flags into
+    (MCP_STATUS_NOT_SPD: a pivot <= 0; MCP_STATUS_NAN: a non-finite operand or pivot) -- the outputs of such a trajectory are NaN, the
+    others are unaffected (a caller that wants the flags passes its own word; ``dv`` is NaN exactly where a trajectory failed).  No autograd.
+    ValueError for an operand of the wrong dtype, shape or device, or a reg that is negative or not finite."""
+    T, M = _lqr_sizes(model, states)
+    dev, xs, us = model.device, (T, M, model.S), (T, M, model.U)
+    states, jac, du_da, lx, lu, hxx, huu = _lqr_operands(dev, ("states", states, xs), ("jac", jac, (T - 1, M, model.G, model.D)), ("du_da", du_da, us),
+                                                         ("lx", lx, xs), ("lu", lu, us), ("hxx", hxx, xs), ("huu", huu, us))
+    reg = float(reg)
+    if not (0.0 <= reg < math.inf):
+        raise ValueError("reg must be finite and not negative")
+    status = _status_word(status, dev, "the model's device")
+    gain = torch.empty(M, T, model.U, model.S, dtype=DT, device=dev)
+    kff = torch.empty(M, T, model.U, dtype=DT, device=dev)
+    dv = torch.empty(M, 2, dtype=DT, device=dev)
+    abi.check(abi.lib().mcp_lqr_pass(_mc(model), M, T, abi.ptr(states), abi.ptr(jac), abi.ptr(du_da), abi.ptr(lx), abi.ptr(lu), abi.ptr(hxx),
+                                     abi.ptr(huu), reg, abi.ptr(gain), abi.ptr(kff), abi.ptr(dv), abi.ptr(status), abi.stream()), "mcp_lqr_pass")
+    return gain, kff, dv
+
+
+# --------------------------------------------------------------------------------------
 # fused closed loop under a feedback policy (autograd): the PD law, the tanh MLP
 # --------------------------------------------------------------------------------------
 # What the one host path below (_closed_launch, _closed_sweep, RolloutClosedFunction, _rollout_closed) reads of a packed policy:

@@ -225,7 +225,7 @@ class TV_linear_controller(Policy):
     components -- no index layout applies, S may be odd and U need not be S / 2; ``ff`` is [rows, U] or None (no feedforward);
     ``target_traj`` is [rows, S].  The error is the plain difference, not wrapped on angle components.  ``flg_train_gains`` /
     ``flg_train_feedforward`` choose which of the two is a trainable Parameter.  ``from_pd`` builds a ``PD_controller``'s law as the special
-    case.  ``forward(states, t)`` is the torch formula of the step loop and of the system simulator; it is stateless and raises ValueError
+    case; ``from_lqr`` computes nominal, feedforward and gains by iLQR on the GP mean model (policy_learning/ilqr.py).  ``forward(states, t)`` is the torch formula of the step loop and of the system simulator; it is stateless and raises ValueError
     for a row the tensors do not have.  As ``MC_PILCO``'s control policy it runs inside the fused closed loop (``packed()``: an
     ops.PackedTVL, mcp_rollout_tvl and its sweep, whose parameter gradient is per row)."""
 
@@ -266,6 +266,22 @@ class TV_linear_controller(Policy):
                     dtype=pd_controller.dtype, device=pd_controller.device)
         args.update(kwargs)
         return cls(S, U, gain, ff, flg_time_varying_gains=tv, **args)
+
+    @classmethod
+    def from_lqr(cls, model, x0, a_init, cost, **kwargs):
+        """The controller iLQR computes on the GP mean model of ``model`` (an ops.PackedModel, or a Model_learning with a fused layout) from
+        the state ``x0`` [S] and the pre-squash input sequence ``a_init`` [T, U] under ``cost`` (an ilqr.Quadratic_tracking_cost):
+        ``target_traj`` = the optimised nominal states, ``ff`` = its pre-squash inputs, ``gain`` = the time-varying LQR gains about it --
+        the starting point of guided policy search, which ``MC_PILCO.reinforce_policy`` then trains on the particles.
+        ``flg_train_gains`` / ``flg_train_feedforward`` go to the constructor (``flg_time_varying_gains`` must be True: the gains are per
+        row); every other keyword is ``policy_learning.ilqr.ilqr``'s (iterations, u_max, flg_squash, reg_init, ...).  ``iterations=0`` is
+        plain TVLQR about the rollout of ``a_init``."""
+        from mc_pilco_amd.policy_learning.ilqr import ilqr
+
+        if not kwargs.pop("flg_time_varying_gains", True):
+            raise ValueError("from_lqr computes one gain matrix per row: flg_time_varying_gains must be True")
+        par = {k: kwargs.pop(k) for k in ("flg_train_gains", "flg_train_feedforward") if k in kwargs}
+        return ilqr(model, x0, a_init, cost, controller_par=par, **kwargs)[0]
 
     def _rows(self):
         rows = [int(np.shape(self.target_traj)[0])] if self.target_traj is not None else [0]
