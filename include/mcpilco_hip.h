@@ -101,7 +101,12 @@ typedef struct mcp_gp {
  * models Model_learning_RBF(_angle_state), Model_learning_RBF_MPK_angle_state (Model_learning.py:471-493,
  * 495-618) are G = S, vel = 0..S-1, every not_vel = -1 (Ts then only serves a measurement model).
  * A library older than this rule refuses such a descriptor (MCP_ERR_ARG).
- * GP input z=[x[not_angle], sin x[angle], cos x[angle], u]. */
+ * GP input z=[x[not_angle], sin x[angle], cos x[angle], u].
+ * The index lists: no index twice within angle, none twice within not_angle (an index may be in angle AND in
+ * not_angle: both features are formed); no index twice in vel, no non-negative index twice in not_vel, and no
+ * component that is vel[g] and not_vel[g'] -- every component is written by at most one GP.  A descriptor that
+ * breaks one of these is refused by every entry point (MCP_ERR_ARG) before any HIP call.  A component that is
+ * neither a vel nor a not_vel is 0 from row 1 on. */
 typedef struct mcp_model {
   int32_t S, U, G, D;
   int32_t n_angle, n_not_angle;

@@ -67,7 +67,8 @@ static inline bool model_within_limits(const mcp_model* m, bool train = true) {
   return true;
 }
 
-// the model's scalars and index lists: ranges, D = n_not_angle + 2 n_angle + U, every index inside the state.  No GP operand is looked at.
+// the model's scalars and index lists: ranges, D = n_not_angle + 2 n_angle + U, every index inside the state, no index twice in a list, no component
+// written by two GPs.  No GP operand is looked at.
 static inline bool model_lists_ok(const mcp_model* m) {
   if (!m) return false;
   if (m->S <= 0 || m->S > MCP_MAX_STATE || m->U <= 0 || m->U > MCP_MAX_INPUT || m->G <= 0 || m->G > MCP_MAX_GP) return false;
@@ -80,6 +81,21 @@ static inline bool model_lists_ok(const mcp_model* m) {
   // not_vel[g] == -1: GP g has no integrated position (delta-state model, x'[vel] = x[vel] + delta)
   for (int g = 0; g < m->G; ++g)
     if (m->vel[g] < 0 || m->vel[g] >= m->S || m->not_vel[g] < -1 || m->not_vel[g] >= m->S) return false;
+  // No index twice within angle or within not_angle: the kernels find a component's place in z with a last-match loop, so the slot of an
+  // earlier entry would never be written.  (The same index in angle AND in not_angle is allowed: both slots are written.)
+  for (int i = 0; i < m->n_angle; ++i)
+    for (int j = 0; j < i; ++j)
+      if (m->angle[i] == m->angle[j]) return false;
+  for (int i = 0; i < m->n_not_angle; ++i)
+    for (int j = 0; j < i; ++j)
+      if (m->not_angle[i] == m->not_angle[j]) return false;
+  // Every component is written by at most one GP, as its velocity or as its position: the forward kernels let the thread of vel[g] report
+  // GP g's mu / var, and the sweeps keep one pull per component.
+  for (int g = 0; g < m->G; ++g)
+    for (int h = 0; h < m->G; ++h) {
+      if (h < g && (m->vel[g] == m->vel[h] || (m->not_vel[g] >= 0 && m->not_vel[g] == m->not_vel[h]))) return false;
+      if (m->vel[g] == m->not_vel[h]) return false;
+    }
   return true;
 }
 

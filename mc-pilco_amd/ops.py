@@ -248,6 +248,14 @@ class PackedModel:
 
     def __init__(self, gps: Sequence[PackedGP], S, U, Ts, angle, not_angle, vel, not_vel, var_scale=None):
         self.gps = list(gps)
+        # (what model_lists_ok refuses with a bare MCP_ERR_ARG: every component at most once per role, written by at most one GP)
+        for name, lst in (("angle", angle), ("not_angle", not_angle), ("vel", vel), ("not_vel", [v for v in not_vel if int(v) >= 0])):
+            ints = [int(v) for v in lst]
+            if len(set(ints)) != len(ints):
+                raise ValueError("the model's %s list names an index twice: %s" % (name, ints))
+        both = sorted(set(int(v) for v in vel) & set(int(v) for v in not_vel))
+        if both:
+            raise ValueError("the model's vel and not_vel lists share the components %s: a component is written by one GP at the most" % both)
         m = abi.Model()
         m.S, m.U, m.G, m.D = int(S), int(U), len(self.gps), self.gps[0].D
         m.n_angle, m.n_not_angle = len(angle), len(not_angle)

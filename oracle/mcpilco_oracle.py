@@ -287,6 +287,10 @@ def mixed_next_state(m: SpeedModel, x, u, eps: Optional[torch.Tensor], particle_
     vel, not_vel = list(m.vel), list(m.not_vel)
     nxt = torch.zeros_like(x)
     nxt[:, vel] = x[:, vel] + delta
+    gd = [g for g, q in enumerate(not_vel) if q < 0]
+    if gd and particle_pred:  # a GP without a position: the delta rule in delta_next_state's order of the sums, (x + mu) + sqrt(var) eps
+        v = [vel[g] for g in gd]
+        nxt[:, v] = x[:, v] + dmu[:, gd] + torch.sqrt(dvar[:, gd]) * eps[:, gd]
     gs = [g for g, q in enumerate(not_vel) if q >= 0]
     if gs:
         q, v = [not_vel[g] for g in gs], [vel[g] for g in gs]

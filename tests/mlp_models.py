@@ -8,10 +8,9 @@ tests/pd_models.py.  No GPU and no project code beyond the oracle.
 import numpy as np
 import torch
 
+import layout_models
 import pd_models
-from helpers import hyper
 from open_grad_models import oracle_step
-from oracle import mcpilco_oracle as orc
 from pd_models import family, inputs_for  # noqa: F401  (re-exported: the GPU module builds its inputs from these)
 
 DT = torch.float64
@@ -19,33 +18,14 @@ PAIR_SEED = 3
 
 # pd_models' shapes and one at every compiled limit of the model at once (S = 16, U = 8, G = 8, D = 8 + 16 + 8 = 32; speed integration): with a
 # (64, 64) network the sweep's layout for 16 trajectories does not fit the LDS, and a workgroup sweeps its tile in two parts of 8
-SHAPES = dict(pd_models.SHAPES, limits=dict(S=16, U=8, G=8, angle=list(range(8)), not_angle=list(range(8, 16)), vel=list(range(8, 16)),
-                                            not_vel=list(range(8)), Ts=0.02))
+SHAPES = dict(pd_models.SHAPES, limits=layout_models.LAYOUTS["limits"])
 
 
 def build_pair(shape, N, deg, seed):
     """pd_models.build_pair, for the shapes of this module's table: (cfg, oracle model, per-GP (lengthscales, sigma_n, lam, poly_w))."""
     if shape in pd_models.SHAPES:
         return pd_models.build_pair(shape, N, deg, seed)
-    c = SHAPES[shape]
-    D = len(c["not_angle"]) + 2 * len(c["angle"]) + c["U"]
-    gen = torch.Generator().manual_seed(seed)
-    X = torch.rand(N, D, dtype=DT, generator=gen) * 2 - 1
-    hyp, caches, specs = [], [], []
-    for g in range(c["G"]):
-        w = torch.randn(D, 1, dtype=DT, generator=gen) / np.sqrt(D)
-        Y = 0.3 * torch.sin(2.0 * X @ w) + 0.01 * torch.randn(N, 1, dtype=DT, generator=gen)
-        ls = (1.5 + torch.rand(D, dtype=DT, generator=gen)).numpy()
-        poly = None
-        if deg >= 1:
-            poly = [(0.1 + 0.2 * torch.rand(D + 1, dtype=DT, generator=gen)).numpy()]
-        if deg >= 2:
-            poly.append((0.05 + 0.1 * torch.rand(2 * D, dtype=DT, generator=gen)).numpy())
-        h = hyper(ls, 0.1, 1.0, poly)
-        hyp.append(h)
-        caches.append(orc.pretrain_gp(h, X, Y))
-        specs.append((ls, 0.1, 1.0, poly))
-    return c, orc.SpeedModel(hyp, caches, c["Ts"], c["angle"], c["not_angle"], c["vel"], c["not_vel"]), specs
+    return layout_models.build_pair(shape, N, deg, seed)  # (the same recipe and draws)
 
 
 def feature_lists(c, opt):

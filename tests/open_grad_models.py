@@ -57,7 +57,12 @@ def inputs_for(c, M, T, seed, shared=False):
 
 def oracle_step(shape, m, x, u, eps, sample, var_scale=None):
     """orc.next_state / orc.delta_next_state; with ``var_scale`` (flg_norm: Model_learning.py:220-221 scales the GP variances by
-    norm_list^2 before sampling) the same step written out on the oracle's posterior.  Returns (next state, scaled variances)."""
+    norm_list^2 before sampling) the same step written out on the oracle's posterior.  "mixed" (the layouts of tests/layout_models.py: GPs
+    with and without an integrated position in one model, components nothing integrates): orc.mixed_next_state, which takes ``var_scale``
+    itself.  Returns (next state, scaled variances)."""
+    if shape == "mixed":
+        nx, _, var = orc.mixed_next_state(m, x, u, eps, sample, var_scale)
+        return nx, var
     if var_scale is None:
         nx, _, var = (orc.delta_next_state if shape == "delta" else orc.next_state)(m, x, u, eps, sample)
         return nx, var

@@ -5,6 +5,7 @@ tests/open_grad_models.py::build_pair builds its pairs, with a table of its own.
 import numpy as np
 import torch
 
+import layout_models
 from helpers import hyper
 from open_grad_models import SHAPES as _OPEN_SHAPES
 from open_grad_models import oracle_step
@@ -22,7 +23,10 @@ SHAPES = {
 
 
 def family(shape):
-    """The name tests/open_grad_models.oracle_step knows the integrator by."""
+    """The name tests/open_grad_models.oracle_step knows the integrator by (the layouts of tests/layout_models.py: "mixed", and "delta"
+    for its delta-state one)."""
+    if shape in layout_models.LAYOUTS:
+        return layout_models.family(shape)
     return "delta" if shape == "arm2_delta" else "speed"
 
 
@@ -79,19 +83,20 @@ def pd_law(x, t, kp, kd, target, u_max, squash, pos, vel):
     return um * torch.tanh(a / um)
 
 
-def pd_truth(shape, m, x0, kp, kd, target, eps, w, wu, sample, u_max=1.0, squash=True, var_scale=None):
+def pd_truth(shape, m, x0, kp, kd, target, eps, w, wu, sample, u_max=1.0, squash=True, var_scale=None, pos=None, step=oracle_step):
     """torch autograd through oracle_step with the policy formula written out.  L = sum w * states + sum wu * inputs (wu None: states only).
-    Returns (states [T,M,S], inputs [T,M,U], dL/dsqrt_kp, dL/dsqrt_kd, dL/dx0, smallest variance met)."""
+    Returns (states [T,M,S], inputs [T,M,U], dL/dsqrt_kp, dL/dsqrt_kd, dL/dx0, smallest variance met).  ``pos`` / ``step``: other position
+    indices than the rule's, another step than oracle_step -- the deliberately wrong variants of tests/test_layout_models_cpu.py."""
     S, U = x0.shape[1], kp.shape[0]
     h = S // 2
-    pos, vel = list(range(U)), list(range(h, h + U))
+    pos, vel = list(range(U)) if pos is None else list(pos), list(range(h, h + U))
     x0 = x0.clone().requires_grad_(True)
     kp = kp.clone().requires_grad_(True)
     kd = kd.clone().requires_grad_(True)
     T = w.shape[0]
     xs, us, vmin = [x0], [pd_law(x0, 0, kp, kd, target, u_max, squash, pos, vel)], float("inf")
     for t in range(1, T):
-        nx, var = oracle_step(family(shape), m, xs[-1], us[-1], eps[t - 1], sample, var_scale)
+        nx, var = step(family(shape), m, xs[-1], us[-1], eps[t - 1], sample, var_scale)
         vmin = min(vmin, float(var.detach().min()))
         xs.append(nx)
         us.append(pd_law(nx, t, kp, kd, target, u_max, squash, pos, vel))

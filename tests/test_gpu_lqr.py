@@ -6,7 +6,10 @@ Bounds.  Linearisation: GRAD_TOL of tests/test_gpu_tvl_rollout.py, 1e-9 relative
 the sweep that test bounds composes it); against ops.model_step's backward on the same row 1e-12 relative.  Pass: per case and output
 (gain, kff, dv) max(1e-12, 64 d_ref) relative to the output's largest entry, d_ref the difference between the recursion in float64 and in
 long double on that case (the truth's own rounding measures the case's conditioning; 64 allows for another order of the sums over
-T <= 12 rows); the truth is given the KERNEL's A and B, so only the recursion's arithmetic differs."""
+T <= 12 rows); the truth is given the KERNEL's A and B, so only the recursion's arithmetic differs.  The same bound holds the longest
+horizon, T = MCP_LQR_MAX_T = 2048 (arm2, reg 1e-3, cond(Quu) <= 5.9), where an MI355X measured gain / kff / dv 9.3e-16 / 1.3e-15 / 7.0e-16
+against the float64 recursion at d_ref 9.3e-16 / 1.5e-15 / 1.1e-15: the kernel is inside 64 d_ref there as at T = 12 (the regularised
+recursion contracts, its rounding does not grow with the horizon), so no second float64 truth was needed."""
 import contextlib
 import functools
 import io
@@ -16,6 +19,7 @@ import pytest
 import torch
 
 import closed_loop_family as clf
+import layout_models
 import lqr_models as lm
 import pd_models
 from gpu_helpers import DT, G, dev, relmax
@@ -27,7 +31,9 @@ cid = lambda c: "-".join(str(v) for v in c)
 
 
 def pair(shape, N, deg):
-    return clf.pair(pd_models.build_pair, shape, N, deg, N + deg, None, pd_models.family(shape) == "delta")
+    """A shape of pd_models or a layout of tests/layout_models.py."""
+    models = layout_models if shape in layout_models.LAYOUTS else pd_models
+    return clf.pair(models.build_pair, shape, N, deg, N + deg, None, pd_models.family(shape) == "delta")
 
 
 def bound(d):
@@ -119,7 +125,10 @@ def check_pass(what, got, f64, ld, cond):
         assert e <= bound(dr)
 
 
-PASS_CASES = [c + (reg, 1.0) for c in CASES for reg in (0.0, 1e-3)] + [("arm2", 0, 37, 12, 5, 1e-3, (0.4, 1.7)), ("ur5", 1, 48, 3, 17, 0.0, (0.5, 0.7, 0.9, 1.1, 1.3, 1.5))]
+PASS_CASES = [c + (reg, 1.0) for c in CASES for reg in (0.0, 1e-3)] + [("arm2", 0, 37, 12, 5, 1e-3, (0.4, 1.7)), ("ur5", 1, 48, 3, 17, 0.0, (0.5, 0.7, 0.9, 1.1, 1.3, 1.5)),
+                                                                           # every compiled limit of the model at once (G D = 256 = the pass's threads: the whole
+                                                                           # workgroup prefetches jac), a bound per input
+                                                                           ("limits", 0, 37, 3, 17, 0.0, (0.5, 0.6, 0.7, 0.8, 0.9, 1.1, 1.3, 1.5))]
 
 
 @pytest.mark.parametrize("case", PASS_CASES, ids=cid)
@@ -148,6 +157,56 @@ def test_pass_without_du_da_reads_ones():
     J, lx, lu, hxx, huu, s = cost_rows(c, 12, states, a, target)
     assert all(torch.equal(p, q) for p, q in zip(ops.lqr_pass(pm, states, jac, lx, lu, hxx, huu, reg=1e-3),
                                                  ops.lqr_pass(pm, states, jac, lx, lu, hxx, huu, reg=1e-3, du_da=torch.ones_like(s))))
+
+
+# ---- 2b. the size limits: the longest horizon, the grid stride of the linearisation ------------------------------------------------------------
+LONG = ("arm2", 0, 37)
+
+
+def test_the_longest_horizon():
+    """T = MCP_LQR_MAX_T = 2048 (dvt in dynamic LDS at its largest), M = 2, reg = 1e-3, mean record: status 0, every output finite, the pass
+    against the recursion on the kernel's own A, B within bound(d_ref) -- d_ref at this length is the reference's own measure of the
+    conditioning, printed beside the kernel's error --, and trajectory 0 carries the bits of an M = 1 launch."""
+    from mc_pilco_amd import hipabi, ops
+
+    T, M, reg = hipabi.LQR_MAX_T, 2, 1e-3
+    assert T == 2048
+    c, m, pm, (x0, a, u, du, eps, target), states, jac = record(*LONG, T, M, False)
+    J, lx, lu, hxx, huu, s = cost_rows(c, T, states, a, target)
+    status = torch.zeros(1, dtype=torch.int32, device=dev())
+    got = ops.lqr_pass(pm, states, jac, lx, lu, hxx, huu, reg=reg, du_da=s, status=status)
+    assert int(status.item()) == 0 and bool(torch.isfinite(states).all()) and all(bool(torch.isfinite(v).all()) for v in got)
+    A, B = ops.linearize(pm, states, jac, du_da=s)
+    assert bool(torch.isfinite(A).all()) and bool(torch.isfinite(B).all())
+    torch.set_num_threads(1)
+    f64, ld, cond = truth_of_the_pass(A, B, (lx, lu, hxx, huu), reg)
+    check_pass("T %d M %d reg %g" % (T, M, reg), got, f64, ld, cond)
+    one = ops.lqr_pass(pm, *[v[:, :1].contiguous() for v in (states, jac, lx, lu, hxx, huu)], reg=reg, du_da=s[:, :1].contiguous())
+    assert all(torch.equal(p[0], q[0]) for p, q in zip(one, got))
+
+
+def test_the_grid_stride_of_the_linearisation():
+    """T = 2048, M = 33: (T - 1) M = 67 551 elements' worth of rows, above the 65 536 blocks of one pass over the grid.  The launch over the
+    whole record equals, bit for bit, its launches over the slices [:, 0:16], [:, 16:32], [:, 32:33], each below that limit -- with and
+    without du_da, and with one output alone."""
+    from mc_pilco_amd import hipabi, ops
+
+    T, M = hipabi.LQR_MAX_T, 33
+    assert (T - 1) * M > 65536 > (T - 1) * 16
+    c, m, pm, (x0, a, u, du, eps, target), states, jac = record(*LONG, T, M, False)
+    dg = G(du)
+    assert bool(torch.isfinite(states).all()) and bool(torch.isfinite(jac).all())
+    cut = lambda v, sl: None if v is None else v[:, sl].contiguous()
+    for d in (None, dg):
+        for want in ((True, True), (True, False), (False, True)):
+            whole = ops.linearize(pm, states, jac, du_da=d, want=want)
+            parts = [ops.linearize(pm, cut(states, sl), cut(jac, sl), du_da=cut(d, sl), want=want) for sl in (slice(0, 16), slice(16, 32), slice(32, 33))]
+            for i, out in enumerate(whole):
+                assert (out is None) == (not want[i])
+                if out is not None:
+                    assert bool(torch.isfinite(out).all()) and torch.equal(out, torch.cat([p[i] for p in parts], 1))
+    A, B = ops.linearize(pm, states, jac)
+    assert float(A.abs().max()) > 0 and float(B[T - 2, M - 1].abs().max()) > 0  # (the last element of the last row was written)
 
 
 # ---- 3. independence and reproducibility -------------------------------------------------------------------------------------------------------

@@ -11,7 +11,7 @@ import types
 import pytest
 import torch
 
-from test_open_refusals_cpu import PTR, M, T, abi, model
+from test_open_refusals_cpu import PTR, REPEATED_INDEX, M, T, abi, model
 
 SIGS = {
     "linearize": ("model", "M", "T", "states", "jac", "du_da", "A", "B"),
@@ -77,6 +77,12 @@ def test_limits_and_the_model():
     assert codes(model=model(not_vel=(1, -2))) == both(-1)
     assert codes(model=model(D=7)) == both(-1)  # D != n_not_angle + 2 n_angle + U
     assert codes(model=model(S=0)) == both(-1) and codes(model=model(G=0)) == both(-1) and codes(model=model(U=0)) == both(-1)
+
+
+@pytest.mark.parametrize("edit", REPEATED_INDEX, ids=str)
+def test_an_index_listed_twice(edit):
+    """The model's lists name a component once per role (tests/test_open_refusals_cpu.py): linearize refuses with nothing asked for."""
+    assert codes(model=model(**edit)) == both(-1)
 
 
 def test_precedence():

@@ -12,7 +12,7 @@ import subprocess
 
 import pytest
 
-from test_open_refusals_cpu import PTR, M, T, abi, model
+from test_open_refusals_cpu import PTR, REPEATED_INDEX, M, T, abi, model
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIGS = {
@@ -156,6 +156,14 @@ def test_descriptor_errors():
     assert codes(mlp=mlp_desc(u_max=(0, 0.0))) == both(-1)  # squash needs u_max > 0
     assert codes(mlp=mlp_desc(u_max=(0, float("nan")))) == both(-1)
     assert call("mlp_bwd", mlp=mlp_desc(u_max=(0, 0.0), squash=0)) == 0  # without squashing u_max is not read
+
+
+@pytest.mark.parametrize("edit", REPEATED_INDEX, ids=str)
+def test_a_model_index_listed_twice(edit):
+    """The model's lists name a component once per role (tests/test_open_refusals_cpu.py), as the policy's do above; a policy without
+    lists of its own changes nothing about that."""
+    assert codes(model=model(**edit)) == both(-1)
+    assert codes(model=model(**edit), mlp=mlp_desc(lists=False)) == both(-1)
 
 
 def test_precedence():

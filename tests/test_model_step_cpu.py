@@ -6,7 +6,7 @@ entry launches whenever it accepts, so every forward call below is a refusal; th
 import ctypes as C
 
 import pytest
-from test_open_refusals_cpu import PTR, abi, model
+from test_open_refusals_cpu import PTR, REPEATED_INDEX, abi, model
 
 M = 5
 FWD = ("model", "noise", "M", "t", "particle_pred", "x", "u", "x_next", "mean", "var", "jac", "status")
@@ -77,7 +77,8 @@ def test_precedence():
 
 
 @pytest.mark.parametrize("edit", [dict(angle=(0, 9)), dict(angle=(0, -1)), dict(not_angle=(0, 4)), dict(vel=(0, 4)), dict(vel=(1, -1)),
-                                  dict(not_vel=(0, -2)), dict(not_vel=(1, 4)), dict(n_not_angle=2), dict(n_angle=-1), dict(S=0), dict(G=0)], ids=str)
+                                  dict(not_vel=(0, -2)), dict(not_vel=(1, 4)), dict(n_not_angle=2), dict(n_angle=-1), dict(S=0), dict(G=0)] + REPEATED_INDEX,
+                         ids=str)
 def test_broken_index_lists(edit):
     """Refused by both entries -- by the sweep even though nothing is asked for."""
     assert both(model=model(**edit)) == (-1, -1)

@@ -161,12 +161,24 @@ def test_precedence():
     assert codes(MEAS, pd=pd_desc(U=9), meas=meas_desc(a0=0.0)) == all_are(MEAS, -2)  # the PD descriptor before the measurement
 
 
+# An index listed twice, on model() (angle [2], not_angle [0, 1, 3], vel [1, 3], not_vel [0, 2]): the kernels find a component's place with a
+# last-match loop and let the thread of vel[g] report GP g, so each of these would leave a z slot or a mu / var row unwritten.  In order: twice
+# in angle (angle [2, 2], not_angle [0]: D stays 6), twice in not_angle, twice in vel, twice in not_vel, vel[1] also not_vel[0].
+REPEATED_INDEX = [dict(n_angle=2, angle=(1, 2), n_not_angle=1), dict(not_angle=(1, 0)), dict(vel=(0, 3)), dict(not_vel=(1, 0)), dict(not_vel=(0, 3))]
+
+
 @pytest.mark.parametrize("edit", [dict(angle=(0, 9)), dict(angle=(0, -1)), dict(not_angle=(0, 4)), dict(vel=(0, 4)), dict(vel=(1, -1)),
                                   dict(not_vel=(0, -2)), dict(not_vel=(1, 4)), dict(n_not_angle=2), dict(n_angle=-1), dict(n_not_angle=-1),
-                                  dict(S=0), dict(G=0)], ids=str)
+                                  dict(S=0), dict(G=0)] + REPEATED_INDEX, ids=str)
 def test_model_list_errors(edit):
     """Refused by every entry -- by the sweeps even though nothing is asked for."""
     assert codes(ALL, model=model(**edit)) == all_are(ALL, -1)
+
+
+def test_an_index_in_angle_and_in_not_angle_is_allowed():
+    """Both features are formed (tests/width_models.py narrow_overlap_d7, tests/layout_models.py mixed5): component 2 as the fourth plain one."""
+    assert codes(BWD, model=model(n_not_angle=4, not_angle=(3, 2), D=7)) == all_are(BWD, 0)
+    assert codes(BWD, model=model(not_vel=(0, -1))) == all_are(BWD, 0) and codes(BWD, model=model(not_vel=(1, -1))) == all_are(BWD, 0)
 
 
 def test_not_vel_minus_one_is_a_delta_state_gp():
@@ -226,3 +238,20 @@ def test_measurement():
     # Ts <= 0 is the measurement's own check: the same model passes when no pair is measured
     assert call("pd_meas_bwd", model=model(Ts=0.0), meas=abi().Meas()) == 0
     assert call("pd_meas_bwd", meas=meas_desc()) == 0
+
+
+def test_packed_model_names_the_list():
+    """ops.PackedModel raises ValueError with the list's name where the C entries would answer a bare MCP_ERR_ARG (before anything is
+    packed: no GPU is touched)."""
+    from mc_pilco_amd import ops
+
+    good = dict(angle=[2], not_angle=[0, 1, 3], vel=[1, 3], not_vel=[0, 2])
+    for name, bad in (("angle", [2, 2]), ("not_angle", [0, 0, 3]), ("vel", [3, 3]), ("not_vel", [0, 0])):
+        with pytest.raises(ValueError, match="model's %s list" % name):
+            ops.PackedModel([], 4, 1, 0.05, **dict(good, **{name: bad}))
+    with pytest.raises(ValueError, match="vel and not_vel lists share"):
+        ops.PackedModel([], 4, 1, 0.05, **dict(good, not_vel=[3, 2]))
+    # allowed: an index in angle and in not_angle, several GPs without a position -- these get as far as the (here empty) list of GPs
+    for ok in (dict(good, not_angle=[0, 1, 2, 3]), dict(good, not_vel=[-1, -1])):
+        with pytest.raises(IndexError):
+            ops.PackedModel([], 4, 1, 0.05, **ok)

@@ -10,7 +10,7 @@ import ctypes as C
 import pytest
 
 from test_mlp_meas_refusals_cpu import meas_desc
-from test_open_refusals_cpu import PTR, M, T, abi, model
+from test_open_refusals_cpu import PTR, REPEATED_INDEX, M, T, abi, model
 
 SIGS = {
     "tvl": ("model", "tvl", "meas", "noise", "M", "T", "particle_pred", "x0", "states", "inputs", "jac", "mu", "var", "status"),
@@ -98,6 +98,13 @@ def test_the_descriptor():
     assert codes(tvl=tvl_desc(u_max=(0, float("nan")))) == both(-1)
     assert codes(model=model(2), tvl=tvl_desc(2, u_max=(1, 0.0))) == both(-1)  # every input's bound
     assert call("tvl_bwd", tvl=tvl_desc(u_max=(1, 0.0))) == 0  # (beyond U: not read)
+
+
+@pytest.mark.parametrize("edit", REPEATED_INDEX, ids=str)
+def test_a_model_index_listed_twice(edit):
+    """The model's lists name a component once per role (tests/test_open_refusals_cpu.py): the sweep refuses with nothing asked for."""
+    assert codes(model=model(**edit)) == both(-1)
+    assert codes(model=model(**edit), meas=meas_desc()) == both(-1)
 
 
 def test_precedence():
