@@ -860,6 +860,63 @@ int mcp_cost_bwd_shaped(const mcp_cost* cost, const mcp_cost_inputs* cin, const 
                         const double* states, const double* inputs, const double* costs, const double* rows, const double* g_cost,
                         double* g_states, double* g_inputs, void* stream);
 
+/* ---- sampling MPC on the model: the MPPI rollout-cost and update (the project's own: the reference has no planner) -----------------
+ * K candidate input sequences of H rows around a nominal a [H][U] (pre-squash), P model particles per candidate: trajectory m = k P + p,
+ * M = K P.  Row t of trajectory m takes  u = squash(a[t] + sigma (.) xi(k, t, .)),  squash(v) = u_max tanh(v / u_max) (the closed-loop
+ * kernels' own, mcp_pd_policy / mcp_tvl_policy) or v.  CANDIDATE 0 HAS xi = 0: the nominal is always among the candidates.  For k >= 1,
+ * xi(k, t, u) = xi[(t K + k) U + u] from the buffer, or -- xi == NULL -- the standard normal of Philox stream MCP_STREAM_PLAN = 3
+ * (csrc/mcp_device.h; streams 0..2: eps, masks, measurement noise) at (noise: seed, call, call_dev, particle_offset; particle = k, time
+ * step t, index u): philox_normal(noise, k, t, u, MCP_STREAM_PLAN).  Nothing else of the perturbations is ever stored. */
+#define MCP_MPPI_MAX_K 65536 /* candidates of one plan: the update's one workgroup walks them in a fixed order */
+#define MCP_MPPI_MAX_M (1 << 30) /* K * P: trajectory indices (and a tile's past-the-end ones) stay inside an int32 */
+typedef struct mcp_mppi {
+  int32_t K, P, H;              /* candidates, particles per candidate, rows of the plan (H >= 2; H - 1 transitions) */
+  int32_t U, squash;            /* inputs, == model->U; flg_squash                                                    */
+  double u_max[MCP_MAX_INPUT];  /* > 0 with squash                                                                    */
+  double sigma[MCP_MAX_INPUT];  /* >= 0, finite: std of the perturbation in the pre-squash variable a                 */
+  double lambda;                /* temperature > 0, finite                                                            */
+  double kappa;                 /* S_k = mean_p J + kappa * unbiased std_p J; != 0 needs P >= 2                        */
+  int32_t t0;                   /* >= 0: row offset into the cost's target trajectory (receding horizon)              */
+  const double* a;              /* DEVICE [H][U] nominal, pre-squash                                                  */
+  const double* xi;             /* DEVICE [H][K][U] standard normals, or NULL: Philox                                 */
+  const double* w;              /* DEVICE [H] time weights, or NULL: ones                                             */
+} mcp_mppi;
+/* Rolls the M = K P trajectories out from the ONE state x0 [S] through the model and reduces each to a single number, ONE launch:
+ *   traj_cost[m] = sum_{t=0}^{H-1} w_t c(x_t, u_t, u_{t-1}),  added in ascending t from 0.0 in a register of the thread that owns m
+ * with c = cost_u_point of (cost, cin) -- cost_point of cost where cin is NULL or has no terms -- evaluated at row t0 + t of the cost's
+ * target (MCP_COST_TRAJ: target_traj must hold t0 + H rows); row H - 1 takes part and the rate term is 0 at t = 0, as in mcp_cost_u_fwd,
+ * whose costs[t][m] these terms equal bit for bit.  The step is mcp_rollout_open's (csrc/rollout_open_phases.h: the same phases on the same
+ * operands, the same tile ladder 16 -> 4 by LDS fit, one trajectory per workgroup in mean mode).  COMMON RANDOM NUMBERS: the GP
+ * increment of trajectory m is drawn with particle id p = m mod P -- noise->eps is [H-1][P][G], Philox counts particle p +
+ * particle_offset -- so every candidate meets the same model draws.  particle_pred bit 0 clear: the posterior-mean model (P may be 1, no
+ * Kinv is read).  states [H][M][S] and inputs [H][M][U] are OPTIONAL (NULL: nothing of size [H][M] is written); inputs holds every row,
+ * H - 1 included, and states carries the bits of mcp_rollout_open given those inputs (Mu == M) and the eps buffer repeated per
+ * candidate; traj_cost does not depend on whether they are asked for.  status: MCP_STATUS_NAN for a non-finite state, input, GP moment
+ * or trajectory cost, MCP_STATUS_NONPOS_VAR as mcp_rollout_open.  The nominal's H U doubles are kept in LDS.
+ * MCP_ERR_ARG: model, mppi, mppi->a, cost, noise, x0, traj_cost or status NULL; K, P < 1 or H < 2; U != model->U (U < 1); lambda <= 0 or
+ * not finite; a negative or non-finite sigma; u_max <= 0 with squash; kappa not finite, or != 0 with P < 2; t0 < 0; a model that model_ok
+ * refuses; a bad cost descriptor (cin->U != U included).  MCP_ERR_LIMIT: a dimension beyond MCP_MAX_*, K > MCP_MPPI_MAX_K, K P >
+ * MCP_MPPI_MAX_M, a plan whose rows do not fit the LDS beside the step's operands (H U > 20480 doubles is refused outright).  A refused call makes no HIP call.  Replaces, per
+ * planning iteration, a torch materialisation of [H][M][U] inputs, mcp_rollout_open with Mu == M, mcp_cost_u_fwd and a sum over t. */
+int mcp_mppi_rollout(const mcp_model* model, const mcp_mppi* mppi, const mcp_cost* cost, const mcp_cost_inputs* cin /* may be NULL */,
+                     const mcp_noise* noise, int particle_pred, const double* x0, double* traj_cost, double* states /* or NULL */,
+                     double* inputs /* or NULL */, uint32_t* status, void* stream);
+/* The MPPI update from traj_cost [K P] (two launches, no atomics on results, no host synchronisation):
+ *   cand_cost[k] = S_k = mean_p J + kappa std_p J   (J = traj_cost[k P + p]; the mean over ascending p, the unbiased std in two passes;
+ *                                                    kappa == 0: the mean alone)
+ *   S_min, argmin over the FINITE S_k (the lowest k among equals);  e_k = exp(-(S_k - S_min) / lambda), 0 for a non-finite S_k
+ *   weights[k] = w_k = e_k / sum_k e_k;   a_new[t][u] = a[t][u] + sigma[u] sum_{k >= 1, w_k != 0} w_k xi(k, t, u)
+ * with xi REGENERATED as above (candidate 0 contributes nothing).  stats [4] = S_min, argmin k (as a double), 1 / sum_k w_k^2 (the
+ * effective sample size), sum_k w_k S_k over the finite candidates.  A non-finite S_k raises MCP_STATUS_NAN; if NO candidate is finite,
+ * a_new = a, the weights are 0 and stats = NaN, -1, 0, NaN.  Every sum over k is taken by 256 threads, thread i adding k = i, i + 256, ...
+ * in ascending order, then the 256 partial sums pairwise (i with i + 128, 64, ... 1): a fixed order, bitwise reproducible.
+ * MCP_ERR_ARG: mppi, mppi->a, noise, traj_cost, a_new, cand_cost, weights, stats or status NULL, a_new == a, and the descriptor's refusals
+ * above (U < 1 in place of U != model->U); MCP_ERR_LIMIT: U > MCP_MAX_INPUT, K > MCP_MPPI_MAX_K, K P > MCP_MPPI_MAX_M, H U > 20480 (a plan the
+ * rollout cannot take).  A refused call
+ * makes no HIP call.  Replaces torch's softmax over the candidates and an einsum over a [H][K][U] perturbation buffer. */
+int mcp_mppi_update(const mcp_mppi* mppi, const mcp_noise* noise, const double* traj_cost, double* a_new /* [H][U], != a */,
+                    double* cand_cost /* [K] */, double* weights /* [K] */, double* stats /* [4] */, uint32_t* status, void* stream);
+
 /* ---- the optimizer loop's bookkeeping on the device (MC_PILCO.reinforce_policy, policy_learning/MC_PILCO.py:475-607) ----------
  * The reference decides on the host, from torch.isnan(cost), whether a rollout counts, and so reads every step's cost back before
  * it can launch the next one.  These two entry points take the same decisions from device memory after each ATTEMPT (rollout +

@@ -8,9 +8,9 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["gp_pretrain.hip", "gp_linalg.hip", "gp_sod.hip", "gp_nll.hip", "rollout_fwd.hip", "rollout_fwd_lean.hip", "rollout_fwd_tile.hip", "rollout_open.hip", "rollout_mlp.hip", "rollout_mlp_hist.hip", "model_step.hip", "lqr.hip", "rollout_bwd.hip", "cost.hip", "policy_opt.hip", "comm.hip"]
+SOURCES = ["gp_pretrain.hip", "gp_linalg.hip", "gp_sod.hip", "gp_nll.hip", "rollout_fwd.hip", "rollout_fwd_lean.hip", "rollout_fwd_tile.hip", "rollout_open.hip", "rollout_mlp.hip", "rollout_mlp_hist.hip", "model_step.hip", "lqr.hip", "mppi.hip", "rollout_bwd.hip", "cost.hip", "policy_opt.hip", "comm.hip"]
 HEADERS = [os.path.join(CSRC, "mcp_device.h"), os.path.join(CSRC, "gp_launch.h"), os.path.join(CSRC, "rollout_common.h"), os.path.join(CSRC, "rollout_fwd_shared.h"), os.path.join(CSRC, "rollout_plan.h"),
-           os.path.join(CSRC, "rollout_open_phases.h"), os.path.join(CSRC, "rollout_mlp_kernels.h"),
+           os.path.join(CSRC, "rollout_open_phases.h"), os.path.join(CSRC, "rollout_mlp_kernels.h"), os.path.join(CSRC, "cost_point.h"),
            os.path.join(os.path.dirname(HERE), "include", "mcpilco_hip.h"),
            os.path.join(os.path.dirname(HERE), "include", "mcpilco_hip_debug.h")]  # (mcp_dispatch: every translation unit must see the same layout)
 LIB = os.path.join(HERE, "libmcpilco_hip.so")

@@ -231,6 +231,7 @@ __device__ __forceinline__ u32x4 philox4x32_10(u32x4 c, uint32_t k0, uint32_t k1
 #define MCP_STREAM_EPS 0u
 #define MCP_STREAM_MASK 1u
 #define MCP_STREAM_POS 2u  // position measurement noise of the partially-measurable-system rollout
+#define MCP_STREAM_PLAN 3u  // input perturbations of the sampling planner (mppi.hip); the stream field is two bits wide: this is the last
 
 // the launch's noise descriptor with the device counter (mcp_noise.call_dev, if any) folded into `call` -- read ONCE at the top of a kernel; the
 // draws below see a plain descriptor (graph replays: include/mcpilco_hip.h)

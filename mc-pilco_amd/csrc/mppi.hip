@@ -1,0 +1,423 @@
+// Sampling MPC on the model for gfx950 (MI355X): the MPPI rollout-cost and update, mcp_mppi_rollout / mcp_mppi_update (the project's own:
+// the reference has no planner).  One planning iteration is three launches and no buffer of size [H][M]:
+//   mppi_rollout_kernel<PT, MAXDEG, NEEDVAR>   the open-loop step loop of rollout_open.hip over the shared phases of rollout_open_phases.h
+//                                              (K, V and the statements of F: the same operations on the same operands, so a trajectory
+//                                              carries mcp_rollout_open's bits), with two differences:
+//       input    u_t is not read from a buffer: the LAST PT * U threads of the workgroup form  squash(a[t] + sigma xi(k, t, .))  from the
+//                nominal rows in LDS (the layout's `ext` region) and a perturbation that is read, or drawn from Philox stream
+//                MCP_STREAM_PLAN, ONE ROW AHEAD: u_{t+1} is formed behind the barrier that opens phase K of step t and kept in a
+//                register -- the inputs do not depend on the state, so nothing of them sits on the step's serial chain.  Those threads
+//                have the highest training indices of phase K (none below Npad ~ 370): the draw hides behind the others' kernel rows.
+//       cost     the PT threads in front of them each own a trajectory of the tile: behind the same barrier the thread reads x_t from
+//                the published xs row and u_t, u_{t-1} from a two-row LDS buffer, evaluates cost_u_point / cost_point (cost_point.h: the
+//                cost kernels' own text) at target row t0 + t and adds w_t c to a running sum in a register; one store per trajectory
+//                at the end.  states / inputs are written only when the caller asks.
+//     Common random numbers: the GP increment of trajectory m = k P + p is drawn with particle id p (eps [H-1][P][G], or Philox).
+//   mppi_weights_kernel   one workgroup: S_k per candidate, the minimum over the finite ones, the softmax weights, the statistics
+//   mppi_mean_kernel      one workgroup per row t: a_new[t] = a[t] + sigma sum_k w_k xi(k, t, .), the perturbations regenerated
+// Every sum of the update runs in a fixed order (mppi_block_sum); no atomics on results.
+#include "cost_point.h"
+#include "rollout_open_phases.h"
+
+using namespace mcp;
+
+struct MppiArgs : OpenArgs {
+  mcp_mppi mp;
+  mcp_cost cost;
+  mcp_cost_inputs cin;
+  int has_cin;
+  double* traj_cost;  // [M]
+  double* inputs;     // [H][M][U] or NULL
+};
+
+// doubles of the layout's `ext` region: the nominal [H][U] | u_t, u_{t-1} of the tile's trajectories [2][PT][U]
+__host__ __device__ inline int mppi_extra(int PT, int H, int U) { return H * U + 2 * PT * U; }
+
+// xi(k, t, u): 0 for the nominal's candidate, else the buffer's entry or the Philox normal
+__device__ __forceinline__ double mppi_xi(const mcp_mppi& mp, const mcp_noise& nzl, int k, int t, int u) {
+  if (k == 0) return 0.0;
+  return mp.xi ? mp.xi[((size_t)t * mp.K + k) * mp.U + u] : philox_normal(nzl, k, t, u, MCP_STREAM_PLAN);
+}
+
+template <int PT, int MAXDEG, bool NEEDVAR>
+__global__ __launch_bounds__(RF_NT) void mppi_rollout_kernel(MppiArgs a) {
+  extern __shared__ double smem[];
+  const mcp_model& md = a.model;
+  const int S = md.S, U = md.U, G = md.G, D = md.D, M = a.M, T = a.T, P = a.mp.P;
+  const int nna = md.n_not_angle, na = md.n_angle;
+  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const OpenLayout L = open_layout(PT, NEEDVAR, S, D, G, a.NpadMax, false, 0, false, mppi_extra(PT, T, U));
+  double* xs = smem + L.xs;
+  double* z = smem + L.z;
+  double* red = smem + L.red;  // [2][G][RF_NW][PT]
+  GpL* gpl = reinterpret_cast<GpL*>(smem + L.gpl);
+  double* kpar = smem + L.kpar;
+  double* panel = smem + L.panel;
+  double* nom = smem + L.ext;   // [T][U]
+  double* ub = nom + T * U;     // [2][PT][U]
+  const mcp_noise nzl = noise_of_launch(a.nz);
+  const int m0 = blockIdx.x * PT;
+
+  stage_gp_tables(md.gp, md.var_scale, G, D, gpl, kpar, tid);
+  if (L.xl) {  // mean mode: the small operands of phase K come from LDS for the whole launch
+    const int NP = a.NpadMax;
+    for (int g = 0; g < G; ++g) {
+      const mcp_gp& gp = md.gp[g];
+      for (int it = tid; it < D * NP; it += RF_NT) {
+        const int d = it / NP, j = it - d * NP;
+        smem[L.xt + (g * D + d) * NP + j] = j < gp.Npad ? gp.Xt[(size_t)d * gp.Npad + j] : 0.0;
+      }
+      for (int j = tid; j < NP; j += RF_NT) smem[L.al + g * NP + j] = j < gp.Npad ? gp.alpha[j] : 0.0;
+    }
+  }
+  for (int it = tid; it < T * U; it += RF_NT) nom[it] = a.mp.a[it];
+  __syncthreads();
+  // thread (p, s) owns state component s of trajectory p of the tile; the LAST PT * U threads form the inputs, the PT in front of them
+  // each own a trajectory's cost (PT (S + U + 1) <= 400 of the 512 threads at every compiled limit: the three sets are disjoint)
+  const bool own = tid < PT * S;
+  const int op = own ? tid / S : 0, os = own ? tid - op * S : 0;
+  const int ut = RF_NT - 1 - tid;
+  const bool isu = ut < PT * U;
+  const int up = isu ? ut / U : 0, uk = isu ? ut - up * U : 0;
+  const int ct = ut - PT * U;
+  const bool isc = ct >= 0 && ct < PT;
+  const int tp = own ? op : (isu ? up : (isc ? ct : 0));
+  const int om = imin(m0 + tp, M - 1);
+  const bool ovalid = m0 + tp < M;
+  const int kc = om / P;       // the candidate
+  const int pp = om - kc * P;  // the model particle: the id the GP increments are drawn with
+  double xn = own ? a.x0[os] : 0.0;
+  int zi_plain = -1, zi_ang = -1, g_vel = -1, g_pos = -1, vel_of_pos = 0;
+  if (own) {
+    for (int i = 0; i < nna; ++i)
+      if (md.not_angle[i] == os) zi_plain = i;
+    for (int i = 0; i < na; ++i)
+      if (md.angle[i] == os) zi_ang = i;
+    for (int g = 0; g < G; ++g) {
+      if (md.vel[g] == os) g_vel = g;
+      if (md.not_vel[g] == os) {
+        g_pos = g;
+        vel_of_pos = md.vel[g];
+      }
+    }
+  }
+  const int og = g_pos >= 0 ? g_pos : g_vel;  // the GP whose increment this component integrates
+  const double Ts = md.Ts;
+  unsigned bad = 0;
+  int cur = 0;
+  // the input of row 0 (and, in the loop, of row t + 1 a step ahead): the law of the closed-loop kernels' squashing
+  double sig = 0.0, umax = 1.0, ucur = 0.0;
+  if (isu) {
+    sig = a.mp.sigma[uk];
+    umax = a.mp.u_max[uk];
+    const double av = nom[uk] + sig * mppi_xi(a.mp, nzl, kc, 0, uk);
+    ucur = a.mp.squash ? umax * fast_tanh(av / umax) : av;
+  }
+  double jsum = 0.0;  // the trajectory's running cost
+  lds_barrier();
+
+  for (int t = 0; t < T; ++t) {
+    const bool more = t + 1 < T;
+    // ---- phase S: publish x_t, u_t and the GP features -------------------------------------------------------------------
+    if (own) {
+      xs[cur * PT * S + op * S + os] = xn;
+      if (ovalid) {
+        if (a.states) a.states[((size_t)t * M + m0 + op) * S + os] = xn;
+        if (is_bad(xn)) bad |= MCP_STATUS_NAN;
+      }
+      if (more) {
+        double* zp = z + op * D;
+        if (zi_plain >= 0) zp[zi_plain] = xn;
+        if (zi_ang >= 0) {
+          double sn, cs;
+          sincos_fast(xn, &sn, &cs);
+          zp[nna + zi_ang] = sn;
+          zp[nna + na + zi_ang] = cs;
+        }
+      }
+    }
+    if (isu) {
+      ub[((t & 1) * PT + up) * U + uk] = ucur;
+      if (more) z[up * D + nna + 2 * na + uk] = ucur;
+      if (ovalid) {
+        if (a.inputs) a.inputs[((size_t)t * M + m0 + up) * U + uk] = ucur;
+        if (is_bad(ucur)) bad |= MCP_STATUS_NAN;
+      }
+    }
+    lds_barrier();
+    // ---- the row's cost, in the thread that owns the trajectory (rows t and t - 1 of ub; the next write of either slot is two barriers away) ----
+    if (isc) {
+      const double* xr = xs + cur * PT * S + ct * S;
+      const double* ur = ub + ((t & 1) * PT + ct) * U;
+      const double* upr = t > 0 ? ub + (((t - 1) & 1) * PT + ct) * U : nullptr;
+      const double c = a.has_cin ? cost_u_point(a.cost, a.cin, xr, ur, upr, a.mp.t0 + t) : cost_point(a.cost, xr, a.mp.t0 + t, nullptr);
+      jsum += a.mp.w ? a.mp.w[t] * c : c;
+    }
+    if (!more) break;  // (uniform)
+    if (isu) {         // u_{t+1}, a row ahead
+      const double av = nom[(t + 1) * U + uk] + sig * mppi_xi(a.mp, nzl, kc, t + 1, uk);
+      ucur = a.mp.squash ? umax * fast_tanh(av / umax) : av;
+    }
+    // ---- phases K (and V) per GP ---------------------------------------------------------------------------------------
+    for (int g = 0; g < G; ++g) {
+      const GpL gp = gpl[g];
+      const double* Xt = L.xl ? smem + L.xt + g * D * a.NpadMax : gp.Xt;
+      const double* al = L.xl ? smem + L.al + g * a.NpadMax : gp.alpha;
+      open_phase_k<PT, MAXDEG, NEEDVAR>(gp, kpar + g * KP_STRIDE(D), D, z, panel, red + g * RF_NW * PT, tid, wv, lane, Xt, al,
+                                        L.xl ? a.NpadMax : gp.Npad);
+      if (NEEDVAR) {
+        lds_barrier();
+        const int Npad = __builtin_amdgcn_readfirstlane(gp.Npad);
+        double q = 0.0;
+        for (int I0 = 32 * wv; I0 < Npad; I0 += 32 * RF_NW) q += open_v_block<PT, false>(gp.Kinv, Npad, I0, panel, nullptr, lane);
+        q = fold_kk(q);
+        if (lane < PT) red[(G + g) * RF_NW * PT + wv * PT + lane] = q;
+        lds_barrier();  // the panel is rewritten by the next GP
+      }
+    }
+    if (!NEEDVAR) lds_barrier();
+    // ---- phase F: moments, sample, integrate   v' = v + delta ;  q' = q + Ts v + Ts/2 delta   (rollout_open.hip's statements) ----
+    if (own) {
+      const double* xc = xs + cur * PT * S + op * S;
+      double nx = 0.0;
+      if (og >= 0) {
+        const GpL& gp = gpl[og];
+        const double* kp = kpar + og * KP_STRIDE(D);
+        const double* zp = z + op * D;
+        double mu = gp.mean;
+#pragma unroll
+        for (int w = 0; w < RF_NW; ++w) mu += red[og * RF_NW * PT + w * PT + op];
+        double var = 0.0, dv = mu;
+        if (NEEDVAR) {
+          double ktv = 0.0;
+#pragma unroll
+          for (int w = 0; w < RF_NW; ++w) ktv += red[(G + og) * RF_NW * PT + w * PT + op];
+          double kzz = gp.lambda;
+          if (MAXDEG >= 1 && gp.deg >= 1) {
+            double p1 = kp[KP_W1(D) + D];
+            for (int d = 0; d < D; ++d) p1 = fma(kp[KP_W1(D) + d] * zp[d], zp[d], p1);
+            kzz += p1;
+            if (MAXDEG >= 2 && gp.deg >= 2) {
+              double Sa = 0.0, Sb = 0.0;
+              for (int d = 0; d < D; ++d) {
+                const double zz = zp[d] * zp[d];
+                Sa = fma(kp[KP_W20(D) + d], zz, Sa);
+                Sb = fma(kp[KP_W21(D) + d], zz, Sb);
+              }
+              kzz = fma(Sa, Sb, kzz);
+            }
+          }
+          var = (kzz - ktv) * gp.var_scale;
+          if (a.sample) {
+            const double e = nzl.eps ? nzl.eps[((size_t)t * P + pp) * G + og] : philox_normal(nzl, pp, t, og);
+            dv = fma(sqrt(var), e, mu);
+          }
+        }
+        if (og == g_vel && ovalid) {  // every GP has exactly one velocity component: its thread reports
+          if (a.sample && var <= 0.0) bad |= MCP_STATUS_NONPOS_VAR;  // (finite and not positive: a NaN variance is MCP_STATUS_NAN)
+          if (is_bad(mu) || is_bad(var)) bad |= MCP_STATUS_NAN;
+        }
+        nx = og == g_pos ? xc[os] + Ts * xc[vel_of_pos] + 0.5 * Ts * dv : xc[os] + dv;
+      }
+      xn = nx;
+    }
+    if (NEEDVAR && MAXDEG >= 1) lds_barrier();  // k(z, z) above reads z, which the next step's phase S rewrites
+    cur ^= 1;
+  }
+  if (isc && ovalid) {
+    a.traj_cost[m0 + ct] = jsum;
+    if (is_bad(jsum)) bad |= MCP_STATUS_NAN;
+  }
+  if (bad) atomicOr(a.status, bad);
+}
+
+// ---- the update ---------------------------------------------------------------------------------------------------------------------------
+#define MU_NT 256
+
+// the sum of the workgroup's MU_NT values in a fixed order (i with i + 128, 64, ... 1), in every thread; `red`: MU_NT doubles of LDS
+__device__ __forceinline__ double mppi_block_sum(double v, double* red, int tid) {
+  __syncthreads();  // (the buffer's previous readers)
+  red[tid] = v;
+  __syncthreads();
+  for (int s = MU_NT / 2; s > 0; s >>= 1) {
+    if (tid < s) red[tid] = red[tid] + red[tid + s];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+__global__ __launch_bounds__(MU_NT) void mppi_weights_kernel(mcp_mppi mp, const double* __restrict__ traj_cost, double* __restrict__ cand_cost,
+                                                             double* __restrict__ weights, double* __restrict__ stats,
+                                                             uint32_t* __restrict__ status) {
+  __shared__ double red[MU_NT];
+  __shared__ double mins[MU_NT];
+  __shared__ int mink[MU_NT];
+  const int tid = threadIdx.x, K = mp.K, P = mp.P;
+  // S_k, and this thread's minimum over the finite ones (ascending k: the lowest k among equals)
+  double smin = 0.0;
+  int kmin = -1;
+  bool nonfinite = false;
+  for (int k = tid; k < K; k += MU_NT) {
+    const double* J = traj_cost + (size_t)k * P;
+    double s = 0.0;
+    for (int p = 0; p < P; ++p) s += J[p];
+    double Sk = s / (double)P;
+    if (mp.kappa != 0.0) {
+      double q = 0.0;
+      for (int p = 0; p < P; ++p) {
+        const double d = J[p] - Sk;
+        q = fma(d, d, q);
+      }
+      Sk += mp.kappa * sqrt(q / (double)(P - 1));
+    }
+    cand_cost[k] = Sk;
+    if (is_bad(Sk)) {
+      nonfinite = true;
+    } else if (kmin < 0 || Sk < smin) {
+      smin = Sk;
+      kmin = k;
+    }
+  }
+  mins[tid] = smin;
+  mink[tid] = kmin;
+  __syncthreads();
+  for (int s = MU_NT / 2; s > 0; s >>= 1) {
+    if (tid < s) {
+      const int ko = mink[tid + s];
+      const double so = mins[tid + s];
+      const int km = mink[tid];
+      if (ko >= 0 && (km < 0 || so < mins[tid] || (so == mins[tid] && ko < km))) {
+        mins[tid] = so;
+        mink[tid] = ko;
+      }
+    }
+    __syncthreads();
+  }
+  smin = mins[0];
+  kmin = mink[0];
+  if (nonfinite) atomicOr(status, MCP_STATUS_NAN);
+  if (kmin < 0) {  // no finite candidate: the mean kernel then leaves a_new = a
+    for (int k = tid; k < K; k += MU_NT) weights[k] = 0.0;
+    if (tid == 0) {
+      const double nanv = __longlong_as_double(0x7ff8000000000000ll);
+      stats[0] = nanv, stats[1] = -1.0, stats[2] = 0.0, stats[3] = nanv;
+    }
+    return;
+  }
+  double es = 0.0;
+  for (int k = tid; k < K; k += MU_NT) {
+    const double Sk = cand_cost[k];
+    const double e = is_bad(Sk) ? 0.0 : exp(-(Sk - smin) / mp.lambda);
+    weights[k] = e;  // (this thread's own entries: read back below by the same thread)
+    es += e;
+  }
+  const double esum = mppi_block_sum(es, red, tid);
+  double w2 = 0.0, ws = 0.0;
+  for (int k = tid; k < K; k += MU_NT) {
+    const double w = weights[k] / esum;
+    weights[k] = w;
+    w2 = fma(w, w, w2);
+    if (w != 0.0) ws = fma(w, cand_cost[k], ws);
+  }
+  w2 = mppi_block_sum(w2, red, tid);
+  ws = mppi_block_sum(ws, red, tid);
+  if (tid == 0) stats[0] = smin, stats[1] = (double)kmin, stats[2] = 1.0 / w2, stats[3] = ws;
+}
+
+// one workgroup per row t: a_new[t][u] = a[t][u] + sigma[u] sum_{k >= 1, w_k != 0} w_k xi(k, t, u)
+__global__ __launch_bounds__(MU_NT) void mppi_mean_kernel(mcp_mppi mp, mcp_noise nz, const double* __restrict__ weights, double* __restrict__ a_new) {
+  __shared__ double red[MU_NT];
+  const int tid = threadIdx.x, t = blockIdx.x, K = mp.K, U = mp.U;
+  const mcp_noise nzl = noise_of_launch(nz);
+  for (int u = 0; u < U; ++u) {
+    double acc = 0.0;
+    for (int k = tid; k < K; k += MU_NT) {
+      const double w = weights[k];
+      if (k >= 1 && w != 0.0) acc = fma(w, mppi_xi(mp, nzl, k, t, u), acc);
+    }
+    acc = mppi_block_sum(acc, red, tid);
+    if (tid == 0) a_new[(size_t)t * U + u] = mp.a[(size_t)t * U + u] + mp.sigma[u] * acc;
+  }
+}
+
+// ---- host path: checks -> fill -> ladder (a refused call makes no HIP call) ----------------------------------------------------------------
+static inline bool mppi_finite(double v) { return fabs(v) <= 1.79769313486231570815e308; }
+
+// the descriptor's own refusals, behind the entry's pointers: the sizes and the compiled limits (the entries' one order: MCP_ERR_ARG for what
+// is missing or not positive, then MCP_ERR_LIMIT), and -- behind the model's checks in the rollout -- the values
+static int mppi_sizes(const mcp_mppi* mp) {
+  if (!mp->a || mp->K < 1 || mp->P < 1 || mp->H < 2 || mp->U < 1 || mp->t0 < 0) return MCP_ERR_ARG;
+  if (mp->U > MCP_MAX_INPUT || mp->K > MCP_MPPI_MAX_K || (int64_t)mp->K * mp->P > MCP_MPPI_MAX_M) return MCP_ERR_LIMIT;
+  if ((int64_t)mp->H * mp->U > MCP_LDS_LIMIT / (int)sizeof(double)) return MCP_ERR_LIMIT;  // (the nominal alone would not fit: no layout is tried)
+  return MCP_OK;
+}
+static int mppi_values(const mcp_mppi* mp) {
+  if (!(mp->lambda > 0.0) || !mppi_finite(mp->lambda) || !mppi_finite(mp->kappa) || (mp->kappa != 0.0 && mp->P < 2)) return MCP_ERR_ARG;
+  for (int k = 0; k < mp->U; ++k) {
+    if (!(mp->sigma[k] >= 0.0) || !mppi_finite(mp->sigma[k])) return MCP_ERR_ARG;
+    if (mp->squash && !(mp->u_max[k] > 0.0)) return MCP_ERR_ARG;
+  }
+  return MCP_OK;
+}
+
+template <int PT, int MAXDEG, bool NEEDVAR>
+static int launch_mppi(const MppiArgs& a, hipStream_t st) {
+  const OpenLayout L = open_layout(PT, NEEDVAR, a.model.S, a.model.D, a.model.G, a.NpadMax, false, 0, false, mppi_extra(PT, a.T, a.model.U));
+  const size_t lds = (size_t)L.total * sizeof(double);
+  if (lds > MCP_LDS_LIMIT) return MCP_ERR_LIMIT;
+  MCP_ENSURE_MAX_LDS((mppi_rollout_kernel<PT, MAXDEG, NEEDVAR>));
+  hipLaunchKernelGGL((mppi_rollout_kernel<PT, MAXDEG, NEEDVAR>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
+  MCP_LAUNCH_CHECK();
+  return MCP_OK;
+}
+template <int PT, bool NEEDVAR>
+static int launch_mppi_deg(const MppiArgs& a, int maxdeg, hipStream_t st) {
+  return maxdeg == 0 ? launch_mppi<PT, 0, NEEDVAR>(a, st) : launch_mppi<PT, 2, NEEDVAR>(a, st);
+}
+
+// the nominal's rows beside the largest layout of a rung must fit the LDS: looked at BEFORE the first launch attempt's HIP calls
+static bool mppi_fits(const MppiArgs& a, int PT, bool needvar) {
+  const OpenLayout L = open_layout(PT, needvar, a.model.S, a.model.D, a.model.G, a.NpadMax, false, 0, false, mppi_extra(PT, a.T, a.model.U));
+  return (size_t)L.total * sizeof(double) <= MCP_LDS_LIMIT;
+}
+
+extern "C" int mcp_mppi_rollout(const mcp_model* model, const mcp_mppi* mppi, const mcp_cost* cost, const mcp_cost_inputs* cin, const mcp_noise* noise,
+                                int particle_pred, const double* x0, double* traj_cost, double* states, double* inputs, uint32_t* status,
+                                void* stream) {
+  if (!model || !mppi || !cost || !noise || !x0 || !traj_cost || !status) return MCP_ERR_ARG;
+  const int src = mppi_sizes(mppi);
+  if (src != MCP_OK) return src;
+  if (!model_within_limits(model)) return MCP_ERR_LIMIT;
+  if (!model_ok(model) || mppi->U != model->U || mppi_values(mppi) != MCP_OK) return MCP_ERR_ARG;
+  if (!cost_ok(cost) || cost->S != model->S || !cost_inputs_ok(cin) || (cin && cin->U != model->U)) return MCP_ERR_ARG;
+  MppiArgs a;
+  const int maxdeg = open_fill(a, model, noise, mppi->K * mppi->P, mppi->H, particle_pred, x0, nullptr, 0, nullptr, states, nullptr, nullptr, nullptr, status);
+  a.mp = *mppi;
+  a.cost = *cost;
+  a.has_cin = cost_inputs_none(cin) ? 0 : 1;
+  if (a.has_cin)
+    a.cin = *cin;
+  else
+    memset(&a.cin, 0, sizeof(a.cin));
+  a.traj_cost = traj_cost;
+  a.inputs = inputs;
+  hipStream_t st = (hipStream_t)stream;
+  // the ladder of rollout_open.hip's forward form without a record: the mean chain one trajectory per workgroup, with variances 16, then 4
+  if (!a.sample) return mppi_fits(a, 1, false) ? launch_mppi_deg<1, false>(a, maxdeg, st) : MCP_ERR_LIMIT;
+  if (mppi_fits(a, 16, true)) return launch_mppi_deg<16, true>(a, maxdeg, st);
+  return mppi_fits(a, 4, true) ? launch_mppi_deg<4, true>(a, maxdeg, st) : MCP_ERR_LIMIT;
+}
+
+extern "C" int mcp_mppi_update(const mcp_mppi* mppi, const mcp_noise* noise, const double* traj_cost, double* a_new, double* cand_cost,
+                               double* weights, double* stats, uint32_t* status, void* stream) {
+  if (!mppi || !noise || !traj_cost || !a_new || !cand_cost || !weights || !stats || !status) return MCP_ERR_ARG;
+  const int rc = mppi_sizes(mppi);
+  if (rc != MCP_OK) return rc;
+  if (mppi_values(mppi) != MCP_OK || a_new == mppi->a) return MCP_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(mppi_weights_kernel, dim3(1), dim3(MU_NT), 0, st, *mppi, traj_cost, cand_cost, weights, stats, status);
+  MCP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(mppi_mean_kernel, dim3(mppi->H), dim3(MU_NT), 0, st, *mppi, *noise, weights, a_new);
+  MCP_LAUNCH_CHECK();
+  return MCP_OK;
+}

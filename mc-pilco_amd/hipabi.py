@@ -18,6 +18,8 @@ MAX_BASIS_WIDE = 512  # B of a wide policy (P > 16 or U > 4): MCP_MAX_BASIS_WIDE
 MAX_HIDDEN = 64  # units of a hidden layer of mcp_mlp_policy: MCP_MAX_HIDDEN
 MAX_HIST = 4  # rows a policy with memory reads (mcp_mlp_hist.h): MCP_MAX_HIST
 LQR_MAX_T = 2048  # rows of one mcp_lqr_pass / mcp_linearize call: MCP_LQR_MAX_T
+MPPI_MAX_K = 65536  # candidates of one plan (mcp_mppi.K): MCP_MPPI_MAX_K
+MPPI_MAX_M = 1 << 30  # trajectories of one plan (mcp_mppi.K * P): MCP_MPPI_MAX_M
 OK = 0
 ERRORS = {-1: "MCP_ERR_ARG", -2: "MCP_ERR_LIMIT", -3: "MCP_ERR_WORKSPACE", -4: "MCP_ERR_LAUNCH", -5: "MCP_ERR_COMM"}
 ABI_VERSION = 7
@@ -136,6 +138,14 @@ class CostInputs(C.Structure):
 class Objective(C.Structure):
     """mcp_objective: the time weights (device [T]; NULL: ones) and the risk parameter kappa of J = sum_t w_t (mean_t + kappa std_t)."""
     _fields_ = [("w", dptr), ("kappa", C.c_double)]
+
+
+class MPPI(C.Structure):
+    """mcp_mppi: K candidates x P model particles over H rows around the pre-squash nominal ``a`` [H][U]; u = squash(a + sigma xi), xi from the
+    buffer [H][K][U] or (NULL) from Philox stream 3; S_k = mean_p J + kappa std_p J, weights exp(-(S_k - S_min) / lambda)."""
+    _fields_ = [("K", C.c_int32), ("P", C.c_int32), ("H", C.c_int32), ("U", C.c_int32), ("squash", C.c_int32),
+                ("u_max", C.c_double * MAX_INPUT), ("sigma", C.c_double * MAX_INPUT), ("lam", C.c_double), ("kappa", C.c_double),
+                ("t0", C.c_int32), ("a", dptr), ("xi", dptr), ("w", dptr)]
 
 
 class Dispatch(C.Structure):
@@ -264,6 +274,9 @@ _SIGS = {
     "mcp_cost_rows_sums": (C.c_int, [C.c_int, C.c_int64, dptr, dptr, C.POINTER(Objective), dptr, dptr, dptr, dptr]),
     "mcp_cost_bwd_shaped": (C.c_int, [C.POINTER(Cost), C.POINTER(CostInputs), C.POINTER(Objective), C.c_int, C.c_int, C.c_int64, dptr, dptr,
                                       dptr, dptr, dptr, dptr, dptr, dptr]),
+    "mcp_mppi_rollout": (C.c_int, [C.POINTER(Model), C.POINTER(MPPI), C.POINTER(Cost), C.POINTER(CostInputs), C.POINTER(Noise), C.c_int, dptr, dptr,
+                                   dptr, dptr, dptr, dptr]),
+    "mcp_mppi_update": (C.c_int, [C.POINTER(MPPI), C.POINTER(Noise), dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
     "mcp_adam_step_guarded": (C.c_int, [C.c_int, C.POINTER(dptr), C.POINTER(dptr), C.POINTER(dptr), C.POINTER(dptr), C.POINTER(C.c_int64), C.c_double,
                                         C.c_double, C.c_double, C.c_double, dptr, C.c_int64, C.c_int, dptr, dptr, dptr, dptr]),
     "mcp_nll_epoch_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

@@ -751,6 +751,121 @@ def lqr_pass(model: PackedModel, states, jac, lx, lu, hxx, huu, reg=0.0, du_da=N
 
 
 # --------------------------------------------------------------------------------------
+# sampling MPC on the model: the MPPI rollout-cost and update (no autograd)
+# --------------------------------------------------------------------------------------
+class PackedMPPI:
+    """mcp_mppi without its device pointers (include/mcpilco_hip.h): ``K`` candidates x ``P`` model particles over ``H`` rows of ``U`` inputs,
+    u = squash(a + sigma xi) with the closed-loop kernels' squashing (``u_max`` a scalar or one bound per input, > 0 with ``squash``),
+    ``sigma`` (a scalar or one per input, >= 0) the std of the perturbation in the pre-squash variable, ``lam`` the temperature, ``kappa`` the
+    weight of the particles' std in a candidate's cost (kappa != 0 needs P >= 2).  Everything is checked on the host values first: a bad
+    descriptor raises ValueError before a device is touched.  ``to_c(a, xi, w, t0)`` binds the nominal [H,U], the perturbation buffer
+    [H,K,U] (None: Philox), the time weights [H] (None: ones) and the row offset into the cost's target."""
+
+    def __init__(self, K, P, H, U, sigma, lam, kappa=0.0, u_max=1.0, squash=True):
+        K, P, H, U = int(K), int(P), int(H), int(U)
+        if K < 1 or P < 1 or H < 2:
+            raise ValueError("mppi: K >= 1 candidates, P >= 1 particles and H >= 2 rows are needed (K %d, P %d, H %d)" % (K, P, H))
+        if not 1 <= U <= abi.MAX_INPUT:
+            raise ValueError("mppi: 1..%d inputs are supported (%d given)" % (abi.MAX_INPUT, U))
+        if K > abi.MPPI_MAX_K or K * P > abi.MPPI_MAX_M:
+            raise ValueError("mppi: at most %d candidates and %d trajectories (K %d, K P %d)" % (abi.MPPI_MAX_K, abi.MPPI_MAX_M, K, K * P))
+        per_input = lambda v, name: np.full(U, float(v)) if np.ndim(v) == 0 else _host(v).reshape(-1)
+        sg, um = per_input(sigma, "sigma"), per_input(u_max, "u_max")
+        if sg.size != U or um.size != U:
+            raise ValueError("mppi: sigma and u_max hold one entry per input or are scalars")
+        if not bool(np.all(np.isfinite(sg) & (sg >= 0))):
+            raise ValueError("mppi: sigma must be finite and >= 0 (%s)" % (sg.tolist(),))
+        if squash and not bool(np.all(um > 0)):
+            raise ValueError("mppi: u_max must be > 0 with squashing (%s)" % (um.tolist(),))
+        lam, kappa = float(lam), float(kappa)
+        if not (0.0 < lam < math.inf):
+            raise ValueError("mppi: the temperature lam must be finite and > 0 (%r)" % (lam,))
+        if not np.isfinite(kappa) or (kappa != 0.0 and P < 2):
+            raise ValueError("mppi: kappa must be finite, and kappa != 0 needs P >= 2 (kappa %r, P %d)" % (kappa, P))
+        self.K, self.P, self.H, self.U, self.M = K, P, H, U, K * P
+        self.sigma, self.u_max, self.lam, self.kappa, self.squash = sg, um, lam, kappa, bool(squash)
+
+    def to_c(self, a, xi=None, w=None, t0=0):
+        if int(t0) < 0:
+            raise ValueError("mppi: t0 must be >= 0 (%d)" % int(t0))
+        c = abi.MPPI()
+        c.K, c.P, c.H, c.U, c.squash, c.lam, c.kappa, c.t0 = self.K, self.P, self.H, self.U, int(self.squash), self.lam, self.kappa, int(t0)
+        for k in range(self.U):
+            c.u_max[k], c.sigma[k] = float(self.u_max[k]), float(self.sigma[k])
+        c.a = a.data_ptr()
+        c.xi = None if xi is None else xi.data_ptr()
+        c.w = None if w is None else w.data_ptr()
+        return c
+
+
+def _mppi_operands(mp, dev, a, xi, w):
+    """a [H,U], xi [H,K,U] or None, w [H] or None as the planner's entries take them (the checks of ``_lqr_operands``)."""
+    return _lqr_operands(dev, ("a", a, (mp.H, mp.U)), ("xi", xi, (mp.H, mp.K, mp.U)), ("w", w, (mp.H,)))
+
+
+def mppi_rollout(model: PackedModel, mppi: PackedMPPI, cost: "PackedCost", x0, a, *, cost_inputs: Optional["PackedCostInputs"] = None,
+                 noise: Optional[NoiseSpec] = None, particle_pred=False, xi=None, w=None, t0=0, want_states=False, want_inputs=False,
+                 traj_cost=None, status=None):
+    """The planner's rollout-cost in ONE launch (mcp_mppi_rollout): K P trajectories from the one state ``x0`` [S] under the inputs
+    squash(a + sigma xi) -- candidate 0 unperturbed, ``xi`` [H,K,U] or Philox stream 3 of ``noise`` (seed, call) -- each reduced to
+    traj_cost[k P + p] = sum_t w_t c(x_t, u_t, u_t-1) with ``cost`` / ``cost_inputs`` read at target row t0 + t.  ``particle_pred``: sampled
+    increments with COMMON random numbers -- ``noise.eps`` is [H-1,P,G], Philox counts particle p -- else the mean model (P may be 1).
+    ``want_states`` / ``want_inputs``: also [H,M,S] / [H,M,U] (tests, reading one plan's prediction back); without them nothing of that
+    size is written.  ``traj_cost``: an output buffer [M] to reuse.  Returns (traj_cost, states or None, inputs or None, status).  No
+    autograd.  ValueError for an operand of the wrong dtype, shape or device, or a trajectory cost shorter than t0 + H rows."""
+    dev = model.device
+    if mppi.U != model.U:
+        raise ValueError("mppi: the plan has %d inputs, the model %d" % (mppi.U, model.U))
+    a, xi, w = _mppi_operands(mppi, dev, a, xi, w)
+    (x0,) = _lqr_operands(dev, ("x0", x0, (model.S,)))
+    (traj_cost,) = _lqr_operands(dev, ("traj_cost", traj_cost, (mppi.M,)))
+    if cost.kind == "traj" and cost.traj_len < int(t0) + mppi.H:
+        raise ValueError("target trajectory has %d rows but the plan reads rows %d .. %d" % (cost.traj_len, int(t0), int(t0) + mppi.H - 1))
+    if cost_inputs is not None and cost_inputs.U != model.U:
+        raise ValueError("mppi: the input cost is over %d inputs, the model has %d" % (cost_inputs.U, model.U))
+    noise = NoiseSpec() if noise is None else noise
+    if particle_pred:
+        _check_noise(noise, mppi.H, mppi.P, model.G, 0)
+    status = _status_word(status, dev, "the model's device")
+    if traj_cost is None:
+        traj_cost = torch.empty(mppi.M, dtype=DT, device=dev)
+    states = torch.empty(mppi.H, mppi.M, model.S, dtype=DT, device=dev) if want_states else None
+    inputs = torch.empty(mppi.H, mppi.M, model.U, dtype=DT, device=dev) if want_inputs else None
+    mc, nz = mppi.to_c(a, xi, w, t0), noise.to_c()
+    abi.check(abi.lib().mcp_mppi_rollout(_mc(model), C.byref(mc), C.byref(cost.c), None if cost_inputs is None else C.byref(cost_inputs.c),
+                                         C.byref(nz), int(bool(particle_pred)), abi.ptr(x0), abi.ptr(traj_cost), abi.ptr(states),
+                                         abi.ptr(inputs), abi.ptr(status), abi.stream()), "mcp_mppi_rollout")
+    return traj_cost, states, inputs, status
+
+
+def mppi_update(mppi: PackedMPPI, traj_cost, a, *, noise: Optional[NoiseSpec] = None, xi=None, a_new=None, out=None, status=None):
+    """The MPPI update in two small launches (mcp_mppi_update): candidate costs S_k = mean_p J + kappa std_p J, softmax weights
+    exp(-(S_k - S_min) / lam) over the finite candidates, a_new = a + sigma sum_k w_k xi(k) with the perturbations REGENERATED (``xi``
+    [H,K,U], or Philox stream 3 of ``noise``: the rollout's own).  ``a_new`` [H,U] (not ``a``) and ``out`` = (cand_cost [K], weights [K],
+    stats [4]) are buffers to reuse.  Returns (a_new, cand_cost, weights, stats, status); stats = S_min, argmin k, the effective sample
+    size 1 / sum w^2, sum_k w_k S_k.  A non-finite candidate gets weight 0 and raises MCP_STATUS_NAN in ``status``; with no finite
+    candidate a_new = a.  Bitwise reproducible.  No autograd.  ValueError for an operand of the wrong dtype, shape or device."""
+    if not isinstance(traj_cost, torch.Tensor):
+        raise ValueError("traj_cost must be a float64 tensor")
+    dev = traj_cost.device
+    cand, wts, stats = (None, None, None) if out is None else out
+    traj_cost, a, xi, a_new, cand, wts, stats = _lqr_operands(dev, ("traj_cost", traj_cost, (mppi.M,)), ("a", a, (mppi.H, mppi.U)),
+                                                              ("xi", xi, (mppi.H, mppi.K, mppi.U)), ("a_new", a_new, (mppi.H, mppi.U)),
+                                                              ("cand_cost", cand, (mppi.K,)), ("weights", wts, (mppi.K,)), ("stats", stats, (4,)))
+    if a_new is not None and a_new.data_ptr() == a.data_ptr():
+        raise ValueError("mppi: a_new must not be the nominal's own buffer")
+    new = lambda *s: torch.empty(*s, dtype=DT, device=dev)
+    a_new = new(mppi.H, mppi.U) if a_new is None else a_new
+    cand, wts, stats = (new(mppi.K) if cand is None else cand), (new(mppi.K) if wts is None else wts), (new(4) if stats is None else stats)
+    status = _status_word(status, dev, "the plan's device")
+    noise = NoiseSpec() if noise is None else noise
+    mc, nz = mppi.to_c(a, xi, None, 0), noise.to_c()
+    abi.check(abi.lib().mcp_mppi_update(C.byref(mc), C.byref(nz), abi.ptr(traj_cost), abi.ptr(a_new), abi.ptr(cand), abi.ptr(wts), abi.ptr(stats),
+                                        abi.ptr(status), abi.stream()), "mcp_mppi_update")
+    return a_new, cand, wts, stats, status
+
+
+# --------------------------------------------------------------------------------------
 # fused closed loop under a feedback policy (autograd): the PD law, the tanh MLP
 # --------------------------------------------------------------------------------------
 # What the one host path below (_closed_launch, _closed_sweep, RolloutClosedFunction, _rollout_closed) reads of a packed policy:

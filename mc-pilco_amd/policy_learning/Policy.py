@@ -17,6 +17,8 @@ with ``target_traj`` it tracks: the errors target_traj[t] - x behind its feature
 u = squash(PD(x, t) + net(x, t)), mcp_rollout_mlp_res.
 ``PID_controller`` (this project's own) is PD_controller with a clamped integral of the position error and a third trainable gain; it runs
 inside the fused closed loop like its parent, mcp_rollout_pid.
+``MPPI_controller`` (this project's own) is the receding-horizon sampling planner on the learned model: policy_learning/mppi.py once per control
+step (mcp_mppi_rollout, mcp_mppi_update); no trainable parameters, host-side interface (``forward_np``, ``get_np_policy``).
 Exploration policies (Random_exploration, Sum_of_sinusoids :94-150, PD_controller :406-449) drive the simulated system once per
 trial (61-201 samples): host-side, their ``np.random`` draws in the reference's order so that a seeded launch script collects the
 same data.
@@ -326,6 +328,62 @@ class TV_linear_controller(Policy):
         if self.ff is not None:
             a = a + self.ff[t].reshape(1, -1)
         return self.f_squash(a)
+
+
+class MPPI_controller(Policy):
+    """Receding-horizon sampling MPC on the learned model (this project's own: the reference has none) -- ``policy_learning.mppi.plan`` once
+    per control step.  ``forward_np(state, t)`` plans ``iterations`` MPPI iterations from ``state`` over the horizon of the warm start
+    (``a_init`` [H, U], pre-squash; None: zeros over ``horizon`` rows), returns the applied input u_0 = squash(a[0]) and shifts the nominal
+    one row for the next step, repeating the last row.  ``t == 0`` starts an episode: the warm start is ``a_init`` again, the step count
+    and the noise's call are those of the first step (two episodes plan with the same draws).  The controller counts its own steps -- the
+    system simulator hands ``t`` in seconds -- and step k plans with ``t0 = k`` when the cost tracks a trajectory
+    (Expected_saturated_distance_from_trajectory, alone or wrapped: it needs k + H rows), else ``t0 = 0``; its call is
+    ``noise.call + k * iterations``, so no two iterations of an episode share perturbations.  ``plan_par``: ``plan``'s further keywords
+    (K, P, sigma, lam, kappa, particle_pred).  ``info``: the last plan's.  It has no trainable parameters, and ``forward`` on a batch of
+    particles is not defined: as ``MC_PILCO``'s control policy it is not wired in; ``get_np_policy()`` drives
+    ``simulation_class.Model.rollout``."""
+
+    def __init__(self, state_dim, input_dim, model, cost, horizon=None, a_init=None, iterations=5, noise=None, flg_squash=True, u_max=1.0,
+                 dtype=torch.float64, device=torch.device("cuda"), **plan_par):
+        super().__init__(state_dim=state_dim, input_dim=input_dim, flg_squash=flg_squash, u_max=u_max, dtype=dtype, device=device)
+        if a_init is None:
+            if horizon is None or int(horizon) < 2:
+                raise ValueError("MPPI_controller needs a_init [H, U] or a horizon of at least 2 rows")
+            a_init = torch.zeros(int(horizon), int(input_dim), dtype=torch.float64)
+        self.a_init = torch.as_tensor(a_init, dtype=torch.float64).detach().clone()
+        if self.a_init.dim() != 2 or int(self.a_init.shape[1]) != int(input_dim) or int(self.a_init.shape[0]) < 2:
+            raise ValueError("a_init must be [H >= 2, U], got %s" % (tuple(self.a_init.shape),))
+        self.__dict__.update(model=model, cost=cost)  # (kept out of this module's registry: the planner owns no parameters)
+        self.iterations, self.plan_par = int(iterations), dict(plan_par)
+        self.noise = ops.NoiseSpec() if noise is None else noise
+        self.a, self.step, self.info = self.a_init, 0, None
+
+    def _tracks(self):
+        from mc_pilco_amd.policy_learning import Cost_function as cf
+
+        c = self.cost
+        while isinstance(c, (cf.Input_penalty, cf.Cost_shaping)):
+            c = c.state_cost if isinstance(c, cf.Input_penalty) else c.cost
+        return isinstance(c, cf.Expected_saturated_distance_from_trajectory)
+
+    def forward(self, states, t=None, p_dropout=0.0):
+        raise NotImplementedError("MPPI_controller plans from one state at a time: use forward_np / get_np_policy()")
+
+    def forward_np(self, state, t=None):
+        from mc_pilco_amd.policy_learning import mppi
+
+        if t is not None and float(t) == 0.0:
+            self.a, self.step = self.a_init, 0
+        nz = ops.NoiseSpec(eps=self.noise.eps, seed=self.noise.seed, call=int(self.noise.call) + self.step * self.iterations,
+                           particle_offset=self.noise.particle_offset, call_dev=self.noise.call_dev)
+        a, self.info = mppi.plan(self.model, np.asarray(state, dtype=np.float64).reshape(-1), self.a, self.cost, iterations=self.iterations,
+                                 u_max=self.u_max, flg_squash=self.flg_squash, noise=nz, t0=self.step if self._tracks() else 0, **self.plan_par)
+        u0 = a[0].detach().cpu()
+        if self.flg_squash:
+            um = torch.as_tensor(np.asarray(self.u_max, dtype=np.float64))
+            u0 = um * torch.tanh(u0 / um)
+        self.a, self.step = mppi.shift_warm_start(a), self.step + 1
+        return u0.numpy().reshape(1, -1)
 
 
 class MLP_policy(Policy):

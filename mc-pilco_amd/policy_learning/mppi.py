@@ -1,0 +1,105 @@
+"""Sampling MPC on the learned GP model -- MPPI / random shooting (this project's own: the reference has no planner).
+
+``plan`` improves a pre-squash input sequence a [H,U] from a state x0 by sampling: K candidate sequences a + sigma xi around the nominal
+(candidate 0 IS the nominal), each rolled out through the model -- the mean model, or P particles per candidate under common random
+numbers -- and scored by a cost of ``Cost_function``; the next nominal is the softmax-weighted mean of the candidates.  It needs no
+gradient and no linearisation, works with the saturated costs whose Hessians iLQR cannot use, and its result is the ``a_init`` that
+``Policy.TV_linear_controller.from_lqr`` takes.  One iteration is three fused launches of ``ops``:
+
+  rollout-cost   ops.mppi_rollout   (mcp_mppi_rollout: inputs generated, trajectories rolled out and reduced to one number each on the chip)
+  update         ops.mppi_update    (mcp_mppi_update: candidate costs and weights in one workgroup, the weighted perturbation sum per row)
+
+and the iterations of one ``plan`` run back to back on the stream with no host synchronisation between them: two nominal buffers are
+swapped, ``noise.call`` advances by one per iteration, the statistics of every iteration stay on the device until the end.
+
+``Policy.MPPI_controller`` is the receding-horizon controller over ``plan``.
+Not built: elite-set / CEM updates, time-correlated perturbations, a previous-input argument for the rate term at
+t = 0, a throughput layout for mean-mode planning, GP-sharded forms, the measured (PMS) form, a state per candidate."""
+import numpy as np
+import torch
+
+from mc_pilco_amd import ops
+from mc_pilco_amd.policy_learning.ilqr import _packed_model
+
+
+class _Like:
+    """What a cost object reads of a tensor [., ., n] when it chooses and packs its descriptor: nothing is allocated."""
+
+    def __init__(self, n, device):
+        self.shape, self.device, self.dtype, self.is_cuda = (0, 0, int(n)), torch.device(device), ops.DT, torch.device(device).type == "cuda"
+
+    def dim(self):
+        return 3
+
+
+def kernel_cost(cost, S, U, H, device, trial_index=None):
+    """(PackedCost, PackedCostInputs or None, time weights [H] on ``device`` or None) of a ``Cost_function`` object the HIP cost kernels
+    evaluate -- ``runs_on_kernels()``: Cart_pole_cost, the trajectory and target costs, an ``Input_penalty`` over one of them, a
+    ``Cost_shaping`` with time weights / a discount (counted from the plan's row 0) -- else NotImplementedError.  A ``Cost_shaping`` with
+    risk != 0 is refused too: its std is per time step over the swarm, the planner's ``kappa`` is over a candidate's trajectory costs.
+    ``trial_index``: for a trajectory cost with per-trial lengthscales."""
+    from mc_pilco_amd.policy_learning import Cost_function as cf
+
+    like_x = _Like(S, device)
+    if not isinstance(cost, cf._HipExpectedCost) or not cost.runs_on_kernels(like_x):
+        raise NotImplementedError("mppi plans under the costs the HIP cost kernels evaluate (Cost_function's classes with runs_on_kernels()), "
+                                  "not under %s" % type(cost).__name__)
+    w = None
+    if isinstance(cost, cf.Cost_shaping):
+        if cost.risk != 0.0:
+            raise NotImplementedError("mppi: a Cost_shaping with risk != 0 is not a per-trajectory cost (use kappa)")
+        if not cost._plain:
+            w = ops._t(ops.objective_weights(int(H), cost.time_weights, cost.discount), device)
+    cin = cost.inputs_packed_for(_Like(U, device))
+    return cost.packed_for(like_x, trial_index), cin, w
+
+
+def _check_rows(pc, t0, H):
+    if pc.kind == "traj" and pc.traj_len < int(t0) + int(H):
+        raise ValueError("the cost's target trajectory has %d rows but the plan reads rows %d .. %d" % (pc.traj_len, int(t0), int(t0) + int(H) - 1))
+
+
+def plan(model, x0, a_init, cost, K, P=1, iterations=1, sigma=0.3, lam=1.0, kappa=0.0, u_max=1.0, flg_squash=True, particle_pred=False,
+         noise=None, t0=0, trial_index=None):
+    """MPPI on the GP model from the state ``x0`` [S] and the pre-squash input sequence ``a_init`` [H,U] (row H - 1 moves nothing but enters
+    the cost).  ``model``: an ops.PackedModel or a Model_learning with a fused layout; ``cost``: see ``kernel_cost``; ``K`` candidates,
+    ``P`` model particles each (``particle_pred``: sampled increments under common random numbers, else the mean model); ``sigma`` the
+    perturbation's std per input in the pre-squash variable, ``lam`` the temperature, ``kappa`` the weight of the particles' std in a
+    candidate's cost; ``noise``: an ops.NoiseSpec -- seed, call (iteration i plans with call + i; an ``eps`` buffer [H-1,P,G] is read by
+    every iteration) -- None: seed 0, call 0; ``t0``: the row of the cost's target trajectory that plan row 0 reads (receding horizon);
+    ``trial_index``: for a trajectory cost with per-trial lengthscales.
+
+    Runs ``iterations`` x (rollout-cost, update) on the current stream without a host synchronisation in between.  Returns (a, info):
+    ``a`` [H,U] the new nominal; ``info``: "S_min", "nominal_cost" (the cost of the nominal each iteration STARTED from, cand_cost[0]),
+    "ess" (effective sample size) and "mean_cost" per iteration as lists, "status" (the status words OR-ed), "iterations".
+    NotImplementedError for a cost the kernels do not evaluate, ValueError for a trajectory cost with fewer than t0 + H rows."""
+    pm = _packed_model(model)
+    dev = pm.device
+    x0 = torch.as_tensor(x0).detach().to(device=dev, dtype=ops.DT).reshape(-1).contiguous()
+    a = torch.as_tensor(a_init).detach().to(device=dev, dtype=ops.DT).contiguous().clone()
+    if x0.numel() != pm.S or a.dim() != 2 or a.shape[1] != pm.U or a.shape[0] < 2:
+        raise ValueError("mppi.plan takes x0 [%d] and a_init [H >= 2, %d]" % (pm.S, pm.U))
+    H, n_it = int(a.shape[0]), int(iterations)
+    if n_it < 1:
+        raise ValueError("mppi.plan: at least one iteration")
+    mp = ops.PackedMPPI(K, P, H, pm.U, sigma, lam, kappa, u_max, flg_squash)
+    pc, cin, w = kernel_cost(cost, pm.S, pm.U, H, dev, trial_index)
+    _check_rows(pc, t0, H)
+    noise = ops.NoiseSpec() if noise is None else noise
+    new = lambda *s: torch.empty(*s, dtype=ops.DT, device=dev)
+    b, traj, cand, wts, stats = new(H, pm.U), new(mp.M), new(n_it, mp.K), new(mp.K), new(n_it, 4)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    for i in range(n_it):
+        nz = ops.NoiseSpec(eps=noise.eps, seed=noise.seed, call=int(noise.call) + i, particle_offset=noise.particle_offset, call_dev=noise.call_dev)
+        ops.mppi_rollout(pm, mp, pc, x0, a, cost_inputs=cin, noise=nz, particle_pred=particle_pred, w=w, t0=t0, traj_cost=traj, status=status)
+        ops.mppi_update(mp, traj, a, noise=nz, a_new=b, out=(cand[i], wts, stats[i]), status=status)
+        a, b = b, a
+    st, nom = stats.cpu(), cand[:, 0].cpu()  # (the one synchronisation)
+    info = dict(S_min=st[:, 0].tolist(), nominal_cost=nom.tolist(), ess=st[:, 2].tolist(), mean_cost=st[:, 3].tolist(),
+                status=int(status.item()), iterations=n_it)
+    return a, info
+
+
+def shift_warm_start(a):
+    """The nominal of the next control step: every row moved up by one, the last row repeated."""
+    return torch.cat([a[1:], a[-1:]], 0).contiguous()
