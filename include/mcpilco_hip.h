@@ -917,6 +917,60 @@ int mcp_mppi_rollout(const mcp_model* model, const mcp_mppi* mppi, const mcp_cos
 int mcp_mppi_update(const mcp_mppi* mppi, const mcp_noise* noise, const double* traj_cost, double* a_new /* [H][U], != a */,
                     double* cand_cost /* [K] */, double* weights /* [K] */, double* stats /* [4] */, uint32_t* status, void* stream);
 
+/* ---- the planner's extension: a std per row, AR(1)-coloured perturbations, the input applied before row 0, the CEM update -------------
+ * With n(k, t, u) the WHITE normal above (the xi buffer's entry, or the Philox normal), the perturbation of candidate k >= 1 is
+ *   xi_0 = n_0,   xi_t = fma(beta, xi_{t-1}, c n_t),   c = sqrt(1 - beta^2) formed once on the host  (beta == 0: c == 1.0, xi_t has n_t's bits)
+ * -- a xi buffer always holds the WHITE normals, the colouring happens in the kernels -- and row t takes
+ *   u = squash(a[t] + s(t, .) (.) xi_t(k, .)),   s(t, u) = sigma_rows ? sigma_rows[t U + u] : mppi->sigma[u].
+ * Candidate 0 keeps xi = 0.  The rows of sigma_rows live on the device: that they are >= 0 and finite is the CALLER's to check (ops.py does,
+ * on the host values).  n_elite, alpha and sigma_min are read by mcp_cem_update alone. */
+#define MCP_CEM_MAX_ELITE 1024 /* elites of one CEM update: they are sorted in the LDS of one workgroup */
+typedef struct mcp_plan_ext {
+  const double* sigma_rows;        /* DEVICE [H][U] std per row and input, or NULL: mppi->sigma for every row              */
+  const double* u_prev;            /* DEVICE [U] post-squash input applied before row 0, or NULL (the rollout only)        */
+  double beta;                     /* AR(1) coefficient in [0, 1); 0: white                                                */
+  double alpha;                    /* CEM: smoothing in [0, 1) of mean and variance towards the previous ones              */
+  double sigma_min[MCP_MAX_INPUT]; /* CEM: floor of the new std per input, >= 0 and finite                                 */
+  int32_t n_elite;                 /* CEM: 1 .. min(K, MCP_CEM_MAX_ELITE)                                                  */
+} mcp_plan_ext;
+/* mcp_mppi_rollout under the extension: the same arguments with `ext` behind `mppi`.  ext NULL, or sigma_rows NULL, u_prev NULL and beta 0:
+ * the call launches what mcp_mppi_rollout launches (the same kernel, rung and bits).  Otherwise the input threads of the same kernel read
+ * s(t, u) from one more [H][U] block of LDS, carry xi in a register across the rows (still one row ahead of the step) and, with u_prev, the
+ * rate term at t = 0 is taken against u_prev: c(x_0, u_0, u_prev) as mcp_cost_u_fwd forms row 1 of a run whose row 0 has u_prev as its
+ * input.  Without a rate term u_prev changes no bit.  states carries mcp_rollout_open's bits given the launch's own inputs, as above.
+ * Refusals in mcp_mppi_rollout's order; MCP_ERR_ARG also for beta outside [0, 1) (NaN included), MCP_ERR_LIMIT also for a plan whose
+ * 2 H U + 2 PT U doubles do not fit the LDS beside the step's operands.  A refused call makes no HIP call. */
+int mcp_plan_rollout(const mcp_model* model, const mcp_mppi* mppi, const mcp_plan_ext* ext /* may be NULL */, const mcp_cost* cost,
+                     const mcp_cost_inputs* cin /* may be NULL */, const mcp_noise* noise, int particle_pred, const double* x0,
+                     double* traj_cost, double* states /* or NULL */, double* inputs /* or NULL */, uint32_t* status, void* stream);
+/* mcp_mppi_update under the extension: a_new[t][u] = a[t][u] + s(t, u) sum_{k >= 1, w_k != 0} w_k xi_t(k, u).  The sum is linear in n: the
+ * weighted sums N_t[u] = sum_k w_k n(k, t, u) are formed per row exactly as mcp_mppi_update forms them, then ONE thread per input runs the
+ * filter X_0 = N_0, X_t = fma(beta, X_{t-1}, c N_t) over the rows and a_new = a + s X (three launches; nothing is regenerated twice).
+ * Weights, cand_cost, stats and status as mcp_mppi_update.  ext NULL, or sigma_rows NULL and beta 0 (u_prev is not read): mcp_mppi_update
+ * itself, bit for bit.  Refusals as mcp_mppi_update, MCP_ERR_ARG also for beta outside [0, 1) and a_new == sigma_rows. */
+int mcp_mppi_update_ext(const mcp_mppi* mppi, const mcp_plan_ext* ext /* may be NULL */, const mcp_noise* noise, const double* traj_cost,
+                        double* a_new /* [H][U], != a */, double* cand_cost /* [K] */, double* weights /* [K] */, double* stats /* [4] */,
+                        uint32_t* status, void* stream);
+/* The CEM update from traj_cost [K P] around the nominal mppi->a and the current std s(t, u) of ext (two launches, no host
+ * synchronisation, no atomics on floating-point results; mppi->lambda is checked and not read):
+ *   cand_cost[k] = S_k as mcp_mppi_update forms it (kappa included); a non-finite S_k is never elite and raises MCP_STATUS_NAN
+ *   the elites: the E' = min(n_elite, #finite) candidates with the smallest (S_k, k) -- ties go to the lower k, -0.0 == 0.0 --;
+ *   elite[r], r < E', in that order (int32; -1 for E' <= r < n_elite).  Candidate 0 competes like any other and contributes xi = 0.
+ *   One workgroup: a radix select on the 80-bit composite (order-preserving key of S_k, k), then a sort of the E' survivors in LDS.
+ *   with xi regenerated for the elites alone (coloured as above):
+ *     m[t][u] = (1 / E') sum_r xi_t(elite[r], u),   v[t][u] = (1 / E') sum_r (xi_t(elite[r], u) - m[t][u])^2   (two passes)
+ *     a_new = alpha a + (1 - alpha) (a + s m),   sigma_new = max(sigma_min[u], sqrt(alpha s^2 + (1 - alpha) s^2 v))
+ *   every sum over r: thread i adds the ranks i, i + 256, ... in ascending order, then the 256 partial sums pairwise as mcp_mppi_update's.
+ *   The chains of a thread's at most four ranks live in registers across the rows: there is no workspace.
+ * stats [4] = S_min, argmin k (= elite[0]), E', the mean cost of the elites.  No finite candidate: a_new = a, sigma_new = s, elite all -1,
+ * stats = NaN, -1, 0, NaN.  MCP_ERR_ARG: a NULL pointer (ext included), the sizes of mcp_mppi_update, n_elite < 1; then MCP_ERR_LIMIT: its
+ * limits, n_elite > MCP_CEM_MAX_ELITE, n_elite > K; then MCP_ERR_ARG: its values, beta or alpha outside [0, 1), a negative or non-finite
+ * sigma_min[u < U], an output that is mppi->a, sigma_rows or the other output.  A refused call makes no HIP call.  Replaces torch's topk, a
+ * gather from a [H][K][U] perturbation buffer and mean / var over the elites. */
+int mcp_cem_update(const mcp_mppi* mppi, const mcp_plan_ext* ext, const mcp_noise* noise, const double* traj_cost, double* a_new /* [H][U] */,
+                   double* sigma_new /* [H][U] */, double* cand_cost /* [K] */, int32_t* elite /* [n_elite] */, double* stats /* [4] */,
+                   uint32_t* status, void* stream);
+
 /* ---- the optimizer loop's bookkeeping on the device (MC_PILCO.reinforce_policy, policy_learning/MC_PILCO.py:475-607) ----------
  * The reference decides on the host, from torch.isnan(cost), whether a rollout counts, and so reads every step's cost back before
  * it can launch the next one.  These two entry points take the same decisions from device memory after each ATTEMPT (rollout +

@@ -16,8 +16,18 @@
 //   mppi_weights_kernel   one workgroup: S_k per candidate, the minimum over the finite ones, the softmax weights, the statistics
 //   mppi_mean_kernel      one workgroup per row t: a_new[t] = a[t] + sigma sum_k w_k xi(k, t, .), the perturbations regenerated
 // Every sum of the update runs in a fixed order (mppi_block_sum); no atomics on results.
+// Under mcp_plan_ext (mcp_plan_rollout, mcp_mppi_update_ext, mcp_cem_update):
+//   mppi_rollout_kernel<.., EXT = true>   the same kernel with the input threads reading the std of row t from one more [H][U] block of the
+//                                         `ext` region, carrying the AR(1) perturbation xi_t = fma(beta, xi_{t-1}, c n_t) in a register -- still
+//                                         one row ahead, off the chain -- and staging u_prev in the row -1 slot of the two-row input buffer.
+//                                         EXT is a template flag and the extended form has its own argument type: the EXT = false
+//                                         instantiations are the kernels mcp_mppi_rollout always launched.
+//   mppi_mean_kernel<RAW> + mppi_filter_kernel   the weighted sums of the WHITE normals per row, then the AR(1) filter over those H U sums
+//   cem_select_kernel, cem_fit_kernel     the elite set (an on-device radix select and an LDS sort) and the fit of mean and std to it
 #include "cost_point.h"
 #include "rollout_open_phases.h"
+
+#include <type_traits>
 
 using namespace mcp;
 
@@ -30,8 +40,19 @@ struct MppiArgs : OpenArgs {
   double* inputs;     // [H][M][U] or NULL
 };
 
-// doubles of the layout's `ext` region: the nominal [H][U] | u_t, u_{t-1} of the tile's trajectories [2][PT][U]
-__host__ __device__ inline int mppi_extra(int PT, int H, int U) { return H * U + 2 * PT * U; }
+// what mcp_plan_rollout's own form takes on top (mcp_plan_ext): a separate argument type, so that the plain form's kernel argument -- and
+// with it its code and resource numbers -- is what it was before the extension existed
+struct PlanArgs : MppiArgs {
+  const double* sigma_rows;  // [H][U] or NULL: mp.sigma per row
+  const double* u_prev;      // [U] or NULL
+  double beta, cnew;         // xi_t = fma(beta, xi_{t-1}, cnew n_t), cnew = sqrt(1 - beta^2) formed once on the host
+};
+template <bool EXT>
+using MppiKernelArgs = typename std::conditional<EXT, PlanArgs, MppiArgs>::type;
+
+// doubles of the layout's `ext` region: the nominal [H][U] | u_t, u_{t-1} of the tile's trajectories [2][PT][U] | -- the extended form only --
+// the std of every row [H][U]
+__host__ __device__ inline int mppi_extra(int PT, int H, int U, bool ext = false) { return H * U + 2 * PT * U + (ext ? H * U : 0); }
 
 // xi(k, t, u): 0 for the nominal's candidate, else the buffer's entry or the Philox normal
 __device__ __forceinline__ double mppi_xi(const mcp_mppi& mp, const mcp_noise& nzl, int k, int t, int u) {
@@ -39,14 +60,14 @@ __device__ __forceinline__ double mppi_xi(const mcp_mppi& mp, const mcp_noise& n
   return mp.xi ? mp.xi[((size_t)t * mp.K + k) * mp.U + u] : philox_normal(nzl, k, t, u, MCP_STREAM_PLAN);
 }
 
-template <int PT, int MAXDEG, bool NEEDVAR>
-__global__ __launch_bounds__(RF_NT) void mppi_rollout_kernel(MppiArgs a) {
+template <int PT, int MAXDEG, bool NEEDVAR, bool EXT>
+__global__ __launch_bounds__(RF_NT) void mppi_rollout_kernel(MppiKernelArgs<EXT> a) {
   extern __shared__ double smem[];
   const mcp_model& md = a.model;
   const int S = md.S, U = md.U, G = md.G, D = md.D, M = a.M, T = a.T, P = a.mp.P;
   const int nna = md.n_not_angle, na = md.n_angle;
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const OpenLayout L = open_layout(PT, NEEDVAR, S, D, G, a.NpadMax, false, 0, false, mppi_extra(PT, T, U));
+  const OpenLayout L = open_layout(PT, NEEDVAR, S, D, G, a.NpadMax, false, 0, false, mppi_extra(PT, T, U, EXT));
   double* xs = smem + L.xs;
   double* z = smem + L.z;
   double* red = smem + L.red;  // [2][G][RF_NW][PT]
@@ -55,6 +76,7 @@ __global__ __launch_bounds__(RF_NT) void mppi_rollout_kernel(MppiArgs a) {
   double* panel = smem + L.panel;
   double* nom = smem + L.ext;   // [T][U]
   double* ub = nom + T * U;     // [2][PT][U]
+  double* srow = ub + 2 * PT * U;  // [T][U], the extended form only
   const mcp_noise nzl = noise_of_launch(a.nz);
   const int m0 = blockIdx.x * PT;
 
@@ -71,6 +93,8 @@ __global__ __launch_bounds__(RF_NT) void mppi_rollout_kernel(MppiArgs a) {
     }
   }
   for (int it = tid; it < T * U; it += RF_NT) nom[it] = a.mp.a[it];
+  if constexpr (EXT)
+    for (int it = tid; it < T * U; it += RF_NT) srow[it] = a.sigma_rows ? a.sigma_rows[it] : a.mp.sigma[it % U];
   __syncthreads();
   // thread (p, s) owns state component s of trajectory p of the tile; the LAST PT * U threads form the inputs, the PT in front of them
   // each own a trajectory's cost (PT (S + U + 1) <= 400 of the 512 threads at every compiled limit: the three sets are disjoint)
@@ -107,12 +131,22 @@ __global__ __launch_bounds__(RF_NT) void mppi_rollout_kernel(MppiArgs a) {
   int cur = 0;
   // the input of row 0 (and, in the loop, of row t + 1 a step ahead): the law of the closed-loop kernels' squashing
   double sig = 0.0, umax = 1.0, ucur = 0.0;
+  double xic = 0.0;  // (the extended form) the coloured perturbation of the row in ucur, carried across the rows
+  bool has_up = false;
   if (isu) {
-    sig = a.mp.sigma[uk];
     umax = a.mp.u_max[uk];
-    const double av = nom[uk] + sig * mppi_xi(a.mp, nzl, kc, 0, uk);
+    if constexpr (EXT) {
+      xic = mppi_xi(a.mp, nzl, kc, 0, uk);  // xi_0 = n_0
+      sig = srow[uk];
+      if (a.u_prev) ub[(PT + up) * U + uk] = a.u_prev[uk];  // row -1 has the slot of the odd rows: rewritten by row 1, two barriers on
+    } else {
+      sig = a.mp.sigma[uk];
+      xic = mppi_xi(a.mp, nzl, kc, 0, uk);
+    }
+    const double av = nom[uk] + sig * xic;
     ucur = a.mp.squash ? umax * fast_tanh(av / umax) : av;
   }
+  if constexpr (EXT) has_up = a.u_prev != nullptr;
   double jsum = 0.0;  // the trajectory's running cost
   lds_barrier();
 
@@ -149,13 +183,19 @@ __global__ __launch_bounds__(RF_NT) void mppi_rollout_kernel(MppiArgs a) {
     if (isc) {
       const double* xr = xs + cur * PT * S + ct * S;
       const double* ur = ub + ((t & 1) * PT + ct) * U;
-      const double* upr = t > 0 ? ub + (((t - 1) & 1) * PT + ct) * U : nullptr;
+      const double* upr = (t > 0 || (EXT && has_up)) ? ub + (((t + 1) & 1) * PT + ct) * U : nullptr;
       const double c = a.has_cin ? cost_u_point(a.cost, a.cin, xr, ur, upr, a.mp.t0 + t) : cost_point(a.cost, xr, a.mp.t0 + t, nullptr);
       jsum += a.mp.w ? a.mp.w[t] * c : c;
     }
     if (!more) break;  // (uniform)
     if (isu) {         // u_{t+1}, a row ahead
-      const double av = nom[(t + 1) * U + uk] + sig * mppi_xi(a.mp, nzl, kc, t + 1, uk);
+      double av;
+      if constexpr (EXT) {
+        xic = fma(a.beta, xic, a.cnew * mppi_xi(a.mp, nzl, kc, t + 1, uk));
+        av = nom[(t + 1) * U + uk] + srow[(t + 1) * U + uk] * xic;
+      } else {
+        av = nom[(t + 1) * U + uk] + sig * mppi_xi(a.mp, nzl, kc, t + 1, uk);
+      }
       ucur = a.mp.squash ? umax * fast_tanh(av / umax) : av;
     }
     // ---- phases K (and V) per GP ---------------------------------------------------------------------------------------
@@ -324,7 +364,9 @@ __global__ __launch_bounds__(MU_NT) void mppi_weights_kernel(mcp_mppi mp, const 
   if (tid == 0) stats[0] = smin, stats[1] = (double)kmin, stats[2] = 1.0 / w2, stats[3] = ws;
 }
 
-// one workgroup per row t: a_new[t][u] = a[t][u] + sigma[u] sum_{k >= 1, w_k != 0} w_k xi(k, t, u)
+// one workgroup per row t: a_new[t][u] = a[t][u] + sigma[u] sum_{k >= 1, w_k != 0} w_k xi(k, t, u); RAW (mcp_mppi_update_ext): the weighted
+// sum N_t[u] of the WHITE normals alone is left in a_new[t][u] for mppi_filter_kernel
+template <bool RAW>
 __global__ __launch_bounds__(MU_NT) void mppi_mean_kernel(mcp_mppi mp, mcp_noise nz, const double* __restrict__ weights, double* __restrict__ a_new) {
   __shared__ double red[MU_NT];
   const int tid = threadIdx.x, t = blockIdx.x, K = mp.K, U = mp.U;
@@ -336,7 +378,215 @@ __global__ __launch_bounds__(MU_NT) void mppi_mean_kernel(mcp_mppi mp, mcp_noise
       if (k >= 1 && w != 0.0) acc = fma(w, mppi_xi(mp, nzl, k, t, u), acc);
     }
     acc = mppi_block_sum(acc, red, tid);
-    if (tid == 0) a_new[(size_t)t * U + u] = mp.a[(size_t)t * U + u] + mp.sigma[u] * acc;
+    if (tid == 0) a_new[(size_t)t * U + u] = RAW ? acc : mp.a[(size_t)t * U + u] + mp.sigma[u] * acc;
+  }
+}
+
+// The perturbation sum is linear in the white normals, so the AR(1) filter runs over the H U weighted sums instead of over every candidate:
+// thread u walks the rows, X_0 = N_0, X_t = fma(beta, X_{t-1}, cnew N_t), a_new[t][u] = a[t][u] + s(t, u) X_t (in place of N_t).
+__global__ __launch_bounds__(MCP_MAX_INPUT) void mppi_filter_kernel(mcp_mppi mp, const double* __restrict__ sigma_rows, double beta, double cnew,
+                                                                    double* __restrict__ a_new) {
+  const int u = threadIdx.x, U = mp.U;
+  if (u >= U) return;
+  double x = 0.0;
+  for (int t = 0; t < mp.H; ++t) {
+    const size_t i = (size_t)t * U + u;
+    const double n = a_new[i];
+    x = t == 0 ? n : fma(beta, x, cnew * n);
+    a_new[i] = mp.a[i] + (sigma_rows ? sigma_rows[i] : mp.sigma[u]) * x;
+  }
+}
+
+// ---- the CEM update: mcp_cem_update ---------------------------------------------------------------------------------------------------------
+//   cem_select_kernel   one workgroup: S_k as mppi_weights_kernel forms it; E' = min(n_elite, #finite); a radix select (ten passes of eight
+//                       bits, most significant first) on the 80-bit composite (order-preserving key of S_k, k) finds its E'-th smallest
+//                       value -- the composite is unique, so exactly E' candidates lie at or below it --; they are gathered in LDS in any
+//                       order and sorted there (bitonic, 1024 slots): unique keys make the result independent of the gathering order.
+//                       Integer LDS atomics count; no floating-point result goes through an atomic.
+//   cem_fit_kernel      one workgroup per input u: thread i owns the ranks i, i + 256, ... (at most CEM_SLOTS) and carries their AR(1)
+//                       chains in registers across the rows; per row the mean, then -- the values still in registers -- the squared
+//                       deviations from it: no [H][E][U] scratch.
+#define CEM_SLOTS (MCP_CEM_MAX_ELITE / MU_NT)
+
+// the order of the finite doubles as unsigned integers (-0.0 counts as 0.0: equal costs tie, and ties go to the lower k)
+__device__ __forceinline__ unsigned long long cem_key(double s) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(s == 0.0 ? 0.0 : s);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+// digit p (0 .. 9, most significant first) of the composite (key, k), k < 65536
+__device__ __forceinline__ int cem_digit(unsigned long long key, int k, int p) { return p < 8 ? (int)((key >> (56 - 8 * p)) & 255u) : ((k >> (8 * (9 - p))) & 255); }
+// whether the digits above p equal the threshold's
+__device__ __forceinline__ bool cem_match(unsigned long long key, int k, unsigned long long tkey, int tk, int p) {
+  if (p == 0) return true;
+  if (p < 8) return (key >> (64 - 8 * p)) == (tkey >> (64 - 8 * p));
+  return key == tkey && (p == 8 || (k >> 8) == (tk >> 8));
+}
+
+__global__ __launch_bounds__(MU_NT) void cem_select_kernel(mcp_mppi mp, int n_elite, const double* __restrict__ traj_cost, double* __restrict__ cand_cost,
+                                                           int32_t* __restrict__ elite, double* __restrict__ stats, uint32_t* __restrict__ status) {
+  __shared__ double red[MU_NT];
+  __shared__ unsigned long long skey[MCP_CEM_MAX_ELITE];
+  __shared__ int sk[MCP_CEM_MAX_ELITE];
+  __shared__ int hist[MU_NT], scan[MU_NT];
+  __shared__ int nfin, sel, need, nsurv;
+  const int tid = threadIdx.x, K = mp.K, P = mp.P;
+  if (tid == 0) nfin = 0, nsurv = 0;
+  __syncthreads();
+  int fin = 0;
+  bool nonfinite = false;
+  for (int k = tid; k < K; k += MU_NT) {  // (mppi_weights_kernel's statements)
+    const double* J = traj_cost + (size_t)k * P;
+    double s = 0.0;
+    for (int p = 0; p < P; ++p) s += J[p];
+    double Sk = s / (double)P;
+    if (mp.kappa != 0.0) {
+      double q = 0.0;
+      for (int p = 0; p < P; ++p) {
+        const double d = J[p] - Sk;
+        q = fma(d, d, q);
+      }
+      Sk += mp.kappa * sqrt(q / (double)(P - 1));
+    }
+    cand_cost[k] = Sk;  // (read back below by this thread alone)
+    if (is_bad(Sk))
+      nonfinite = true;
+    else
+      ++fin;
+  }
+  if (fin) atomicAdd(&nfin, fin);
+  if (nonfinite) atomicOr(status, MCP_STATUS_NAN);
+  __syncthreads();
+  const int E = imin(n_elite, nfin);
+  for (int r = E + tid; r < n_elite; r += MU_NT) elite[r] = -1;
+  if (E == 0) {  // (uniform) no finite candidate: cem_fit_kernel then leaves a_new = a, sigma_new = s
+    if (tid == 0) {
+      const double nanv = __longlong_as_double(0x7ff8000000000000ll);
+      stats[0] = nanv, stats[1] = -1.0, stats[2] = 0.0, stats[3] = nanv;
+    }
+    return;
+  }
+  // the E-th smallest composite, digit by digit
+  unsigned long long tkey = 0;
+  int tk = 0;
+  if (tid == 0) need = E;
+  for (int p = 0; p < 10; ++p) {
+    hist[tid] = 0;
+    __syncthreads();
+    for (int k = tid; k < K; k += MU_NT) {
+      const double Sk = cand_cost[k];
+      if (is_bad(Sk)) continue;
+      const unsigned long long key = cem_key(Sk);
+      if (cem_match(key, k, tkey, tk, p)) atomicAdd(&hist[cem_digit(key, k, p)], 1);
+    }
+    __syncthreads();
+    scan[tid] = hist[tid];
+    __syncthreads();
+    for (int off = 1; off < MU_NT; off <<= 1) {  // inclusive prefix counts over the 256 digits
+      const int v = tid >= off ? scan[tid - off] : 0;
+      __syncthreads();
+      scan[tid] += v;
+      __syncthreads();
+    }
+    const int want = need;
+    __syncthreads();
+    if (scan[tid] - hist[tid] < want && want <= scan[tid]) {  // exactly one digit
+      sel = tid;
+      need = want - (scan[tid] - hist[tid]);
+    }
+    __syncthreads();
+    if (p < 8)
+      tkey |= (unsigned long long)sel << (56 - 8 * p);
+    else
+      tk |= sel << (8 * (9 - p));
+  }
+  // gather the E candidates at or below it, then sort them by (key, k)
+  for (int r = tid; r < MCP_CEM_MAX_ELITE; r += MU_NT) skey[r] = ~0ull, sk[r] = 0x7fffffff;
+  __syncthreads();
+  for (int k = tid; k < K; k += MU_NT) {
+    const double Sk = cand_cost[k];
+    if (is_bad(Sk)) continue;
+    const unsigned long long key = cem_key(Sk);
+    if (key < tkey || (key == tkey && k <= tk)) {
+      const int slot = atomicAdd(&nsurv, 1);
+      if (slot < MCP_CEM_MAX_ELITE) skey[slot] = key, sk[slot] = k;  // (exactly E <= MCP_CEM_MAX_ELITE of them: the guard never bites)
+    }
+  }
+  __syncthreads();
+  int n2 = 2;  // the power of two the E slots fit in (the slots behind them hold the largest composite)
+  while (n2 < E) n2 <<= 1;
+  for (int len = 2; len <= n2; len <<= 1)
+    for (int j = len >> 1; j > 0; j >>= 1) {
+      for (int i = tid; i < n2; i += MU_NT) {
+        const int l = i ^ j;
+        if (l > i) {
+          const bool up = (i & len) == 0;
+          const unsigned long long ki = skey[i], kl = skey[l];
+          const int ci = sk[i], cl = sk[l];
+          const bool gt = ki > kl || (ki == kl && ci > cl);
+          if (gt == up) skey[i] = kl, skey[l] = ki, sk[i] = cl, sk[l] = ci;
+        }
+      }
+      __syncthreads();
+    }
+  double cs = 0.0;
+  for (int r = tid; r < E; r += MU_NT) {
+    elite[r] = sk[r];
+    cs += cand_cost[sk[r]];
+  }
+  cs = mppi_block_sum(cs, red, tid);
+  if (tid == 0) stats[0] = cand_cost[sk[0]], stats[1] = (double)sk[0], stats[2] = (double)E, stats[3] = cs / (double)E;
+}
+
+__global__ __launch_bounds__(MU_NT) void cem_fit_kernel(mcp_mppi mp, mcp_noise nz, mcp_plan_ext ex, double cnew, const int32_t* __restrict__ elite,
+                                                        const double* __restrict__ stats, double* __restrict__ a_new, double* __restrict__ sigma_new) {
+  __shared__ double red[MU_NT];
+  const int tid = threadIdx.x, u = blockIdx.x, U = mp.U, H = mp.H;
+  const mcp_noise nzl = noise_of_launch(nz);
+  const double* sigma_rows = ex.sigma_rows;
+  const double beta = ex.beta, alpha = ex.alpha, sigma_min = ex.sigma_min[u];
+  const int E = imin((int)stats[2], ex.n_elite);  // (E' of cem_select_kernel, earlier on the stream)
+  if (E <= 0) {
+    for (int t = tid; t < H; t += MU_NT) {
+      const size_t i = (size_t)t * U + u;
+      a_new[i] = mp.a[i];
+      sigma_new[i] = sigma_rows ? sigma_rows[i] : mp.sigma[u];
+    }
+    return;
+  }
+  int ks[CEM_SLOTS];
+  double xi[CEM_SLOTS];
+#pragma unroll
+  for (int j = 0; j < CEM_SLOTS; ++j) {
+    const int r = tid + j * MU_NT;
+    ks[j] = r < E ? elite[r] : -1;
+    xi[j] = 0.0;
+  }
+  const double inv = (double)E;
+  for (int t = 0; t < H; ++t) {
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < CEM_SLOTS; ++j)
+      if (ks[j] >= 0) {  // ascending rank
+        const double n = mppi_xi(mp, nzl, ks[j], t, u);
+        xi[j] = t == 0 ? n : fma(beta, xi[j], cnew * n);
+        acc += xi[j];
+      }
+    const double mean = mppi_block_sum(acc, red, tid) / inv;
+    double q = 0.0;
+#pragma unroll
+    for (int j = 0; j < CEM_SLOTS; ++j)
+      if (ks[j] >= 0) {
+        const double d = xi[j] - mean;
+        q = fma(d, d, q);
+      }
+    const double v = mppi_block_sum(q, red, tid) / inv;
+    if (tid == 0) {
+      const size_t i = (size_t)t * U + u;
+      const double s = sigma_rows ? sigma_rows[i] : mp.sigma[u], a = mp.a[i];
+      a_new[i] = alpha * a + (1.0 - alpha) * (a + s * mean);
+      const double s2 = s * s;
+      sigma_new[i] = fmax(sigma_min, sqrt(alpha * s2 + (1.0 - alpha) * s2 * v));
+    }
   }
 }
 
@@ -360,38 +610,52 @@ static int mppi_values(const mcp_mppi* mp) {
   return MCP_OK;
 }
 
-template <int PT, int MAXDEG, bool NEEDVAR>
-static int launch_mppi(const MppiArgs& a, hipStream_t st) {
-  const OpenLayout L = open_layout(PT, NEEDVAR, a.model.S, a.model.D, a.model.G, a.NpadMax, false, 0, false, mppi_extra(PT, a.T, a.model.U));
+template <int PT, int MAXDEG, bool NEEDVAR, bool EXT>
+static int launch_mppi(const MppiKernelArgs<EXT>& a, hipStream_t st) {
+  const OpenLayout L = open_layout(PT, NEEDVAR, a.model.S, a.model.D, a.model.G, a.NpadMax, false, 0, false, mppi_extra(PT, a.T, a.model.U, EXT));
   const size_t lds = (size_t)L.total * sizeof(double);
   if (lds > MCP_LDS_LIMIT) return MCP_ERR_LIMIT;
-  MCP_ENSURE_MAX_LDS((mppi_rollout_kernel<PT, MAXDEG, NEEDVAR>));
-  hipLaunchKernelGGL((mppi_rollout_kernel<PT, MAXDEG, NEEDVAR>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
+  MCP_ENSURE_MAX_LDS((mppi_rollout_kernel<PT, MAXDEG, NEEDVAR, EXT>));
+  hipLaunchKernelGGL((mppi_rollout_kernel<PT, MAXDEG, NEEDVAR, EXT>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
 }
-template <int PT, bool NEEDVAR>
-static int launch_mppi_deg(const MppiArgs& a, int maxdeg, hipStream_t st) {
-  return maxdeg == 0 ? launch_mppi<PT, 0, NEEDVAR>(a, st) : launch_mppi<PT, 2, NEEDVAR>(a, st);
+template <int PT, bool NEEDVAR, bool EXT>
+static int launch_mppi_deg(const MppiKernelArgs<EXT>& a, int maxdeg, hipStream_t st) {
+  return maxdeg == 0 ? launch_mppi<PT, 0, NEEDVAR, EXT>(a, st) : launch_mppi<PT, 2, NEEDVAR, EXT>(a, st);
 }
 
-// the nominal's rows beside the largest layout of a rung must fit the LDS: looked at BEFORE the first launch attempt's HIP calls
-static bool mppi_fits(const MppiArgs& a, int PT, bool needvar) {
-  const OpenLayout L = open_layout(PT, needvar, a.model.S, a.model.D, a.model.G, a.NpadMax, false, 0, false, mppi_extra(PT, a.T, a.model.U));
+// the nominal's rows (the extended form: and the std's) beside the largest layout of a rung must fit the LDS: looked at BEFORE the first
+// launch attempt's HIP calls
+static bool mppi_fits(const MppiArgs& a, int PT, bool needvar, bool ext = false) {
+  const OpenLayout L = open_layout(PT, needvar, a.model.S, a.model.D, a.model.G, a.NpadMax, false, 0, false, mppi_extra(PT, a.T, a.model.U, ext));
   return (size_t)L.total * sizeof(double) <= MCP_LDS_LIMIT;
 }
 
-extern "C" int mcp_mppi_rollout(const mcp_model* model, const mcp_mppi* mppi, const mcp_cost* cost, const mcp_cost_inputs* cin, const mcp_noise* noise,
-                                int particle_pred, const double* x0, double* traj_cost, double* states, double* inputs, uint32_t* status,
-                                void* stream) {
+// the ladder of rollout_open.hip's forward form without a record: the mean chain one trajectory per workgroup, with variances 16, then 4
+template <bool EXT>
+static int mppi_ladder(const MppiKernelArgs<EXT>& a, int maxdeg, hipStream_t st) {
+  if (!a.sample) return mppi_fits(a, 1, false, EXT) ? launch_mppi_deg<1, false, EXT>(a, maxdeg, st) : MCP_ERR_LIMIT;
+  if (mppi_fits(a, 16, true, EXT)) return launch_mppi_deg<16, true, EXT>(a, maxdeg, st);
+  return mppi_fits(a, 4, true, EXT) ? launch_mppi_deg<4, true, EXT>(a, maxdeg, st) : MCP_ERR_LIMIT;
+}
+
+// the extension's own refusals (MCP_ERR_ARG; the device rows of sigma_rows are the caller's to check): what the rollout and the MPPI update
+// read of it, and what the CEM update alone reads
+static bool plan_ext_default(const mcp_plan_ext* e) { return !e || (!e->sigma_rows && !e->u_prev && e->beta == 0.0); }
+static int plan_ext_values(const mcp_plan_ext* e) { return (e && !(e->beta >= 0.0 && e->beta < 1.0)) ? MCP_ERR_ARG : MCP_OK; }
+
+// the checks of both rollout entries in their one order, then the fill
+static int mppi_rollout_fill(MppiArgs& a, int* maxdeg, const mcp_model* model, const mcp_mppi* mppi, const mcp_plan_ext* ext, const mcp_cost* cost,
+                             const mcp_cost_inputs* cin, const mcp_noise* noise, int particle_pred, const double* x0, double* traj_cost,
+                             double* states, double* inputs, uint32_t* status) {
   if (!model || !mppi || !cost || !noise || !x0 || !traj_cost || !status) return MCP_ERR_ARG;
   const int src = mppi_sizes(mppi);
   if (src != MCP_OK) return src;
   if (!model_within_limits(model)) return MCP_ERR_LIMIT;
-  if (!model_ok(model) || mppi->U != model->U || mppi_values(mppi) != MCP_OK) return MCP_ERR_ARG;
+  if (!model_ok(model) || mppi->U != model->U || mppi_values(mppi) != MCP_OK || plan_ext_values(ext) != MCP_OK) return MCP_ERR_ARG;
   if (!cost_ok(cost) || cost->S != model->S || !cost_inputs_ok(cin) || (cin && cin->U != model->U)) return MCP_ERR_ARG;
-  MppiArgs a;
-  const int maxdeg = open_fill(a, model, noise, mppi->K * mppi->P, mppi->H, particle_pred, x0, nullptr, 0, nullptr, states, nullptr, nullptr, nullptr, status);
+  *maxdeg = open_fill(a, model, noise, mppi->K * mppi->P, mppi->H, particle_pred, x0, nullptr, 0, nullptr, states, nullptr, nullptr, nullptr, status);
   a.mp = *mppi;
   a.cost = *cost;
   a.has_cin = cost_inputs_none(cin) ? 0 : 1;
@@ -401,11 +665,31 @@ extern "C" int mcp_mppi_rollout(const mcp_model* model, const mcp_mppi* mppi, co
     memset(&a.cin, 0, sizeof(a.cin));
   a.traj_cost = traj_cost;
   a.inputs = inputs;
-  hipStream_t st = (hipStream_t)stream;
-  // the ladder of rollout_open.hip's forward form without a record: the mean chain one trajectory per workgroup, with variances 16, then 4
-  if (!a.sample) return mppi_fits(a, 1, false) ? launch_mppi_deg<1, false>(a, maxdeg, st) : MCP_ERR_LIMIT;
-  if (mppi_fits(a, 16, true)) return launch_mppi_deg<16, true>(a, maxdeg, st);
-  return mppi_fits(a, 4, true) ? launch_mppi_deg<4, true>(a, maxdeg, st) : MCP_ERR_LIMIT;
+  return MCP_OK;
+}
+
+extern "C" int mcp_mppi_rollout(const mcp_model* model, const mcp_mppi* mppi, const mcp_cost* cost, const mcp_cost_inputs* cin, const mcp_noise* noise,
+                                int particle_pred, const double* x0, double* traj_cost, double* states, double* inputs, uint32_t* status,
+                                void* stream) {
+  MppiArgs a;
+  int maxdeg = 0;
+  const int rc = mppi_rollout_fill(a, &maxdeg, model, mppi, nullptr, cost, cin, noise, particle_pred, x0, traj_cost, states, inputs, status);
+  return rc != MCP_OK ? rc : mppi_ladder<false>(a, maxdeg, (hipStream_t)stream);
+}
+
+extern "C" int mcp_plan_rollout(const mcp_model* model, const mcp_mppi* mppi, const mcp_plan_ext* ext, const mcp_cost* cost,
+                                const mcp_cost_inputs* cin, const mcp_noise* noise, int particle_pred, const double* x0, double* traj_cost,
+                                double* states, double* inputs, uint32_t* status, void* stream) {
+  PlanArgs a;
+  int maxdeg = 0;
+  const int rc = mppi_rollout_fill(a, &maxdeg, model, mppi, ext, cost, cin, noise, particle_pred, x0, traj_cost, states, inputs, status);
+  if (rc != MCP_OK) return rc;
+  if (plan_ext_default(ext)) return mppi_ladder<false>(a, maxdeg, (hipStream_t)stream);  // mcp_mppi_rollout's own launch
+  a.sigma_rows = ext->sigma_rows;
+  a.u_prev = ext->u_prev;
+  a.beta = ext->beta;
+  a.cnew = sqrt(1.0 - ext->beta * ext->beta);  // (beta == 0: exactly 1)
+  return mppi_ladder<true>(a, maxdeg, (hipStream_t)stream);
 }
 
 extern "C" int mcp_mppi_update(const mcp_mppi* mppi, const mcp_noise* noise, const double* traj_cost, double* a_new, double* cand_cost,
@@ -417,7 +701,46 @@ extern "C" int mcp_mppi_update(const mcp_mppi* mppi, const mcp_noise* noise, con
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(mppi_weights_kernel, dim3(1), dim3(MU_NT), 0, st, *mppi, traj_cost, cand_cost, weights, stats, status);
   MCP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(mppi_mean_kernel, dim3(mppi->H), dim3(MU_NT), 0, st, *mppi, *noise, weights, a_new);
+  hipLaunchKernelGGL(mppi_mean_kernel<false>, dim3(mppi->H), dim3(MU_NT), 0, st, *mppi, *noise, weights, a_new);
+  MCP_LAUNCH_CHECK();
+  return MCP_OK;
+}
+
+extern "C" int mcp_mppi_update_ext(const mcp_mppi* mppi, const mcp_plan_ext* ext, const mcp_noise* noise, const double* traj_cost, double* a_new,
+                                   double* cand_cost, double* weights, double* stats, uint32_t* status, void* stream) {
+  if (plan_ext_default(ext) && plan_ext_values(ext) == MCP_OK)
+    return mcp_mppi_update(mppi, noise, traj_cost, a_new, cand_cost, weights, stats, status, stream);  // (u_prev is the rollout's alone)
+  if (!mppi || !noise || !traj_cost || !a_new || !cand_cost || !weights || !stats || !status) return MCP_ERR_ARG;
+  const int rc = mppi_sizes(mppi);
+  if (rc != MCP_OK) return rc;
+  if (mppi_values(mppi) != MCP_OK || plan_ext_values(ext) != MCP_OK || a_new == mppi->a || a_new == ext->sigma_rows) return MCP_ERR_ARG;
+  if (!ext->sigma_rows && ext->beta == 0.0) return mcp_mppi_update(mppi, noise, traj_cost, a_new, cand_cost, weights, stats, status, stream);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(mppi_weights_kernel, dim3(1), dim3(MU_NT), 0, st, *mppi, traj_cost, cand_cost, weights, stats, status);
+  MCP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(mppi_mean_kernel<true>, dim3(mppi->H), dim3(MU_NT), 0, st, *mppi, *noise, weights, a_new);
+  MCP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(mppi_filter_kernel, dim3(1), dim3(MCP_MAX_INPUT), 0, st, *mppi, ext->sigma_rows, ext->beta, sqrt(1.0 - ext->beta * ext->beta), a_new);
+  MCP_LAUNCH_CHECK();
+  return MCP_OK;
+}
+
+extern "C" int mcp_cem_update(const mcp_mppi* mppi, const mcp_plan_ext* ext, const mcp_noise* noise, const double* traj_cost, double* a_new,
+                              double* sigma_new, double* cand_cost, int32_t* elite, double* stats, uint32_t* status, void* stream) {
+  if (!mppi || !ext || !noise || !traj_cost || !a_new || !sigma_new || !cand_cost || !elite || !stats || !status) return MCP_ERR_ARG;
+  if (ext->n_elite < 1) return MCP_ERR_ARG;  // (a size: with the plan's, ahead of every limit)
+  const int rc = mppi_sizes(mppi);
+  if (rc != MCP_OK) return rc;
+  if (ext->n_elite > MCP_CEM_MAX_ELITE || ext->n_elite > mppi->K) return MCP_ERR_LIMIT;
+  if (mppi_values(mppi) != MCP_OK || plan_ext_values(ext) != MCP_OK || !(ext->alpha >= 0.0 && ext->alpha < 1.0)) return MCP_ERR_ARG;
+  for (int k = 0; k < mppi->U; ++k)
+    if (!(ext->sigma_min[k] >= 0.0) || !mppi_finite(ext->sigma_min[k])) return MCP_ERR_ARG;
+  if (a_new == mppi->a || a_new == ext->sigma_rows || sigma_new == mppi->a || sigma_new == ext->sigma_rows || a_new == sigma_new) return MCP_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(cem_select_kernel, dim3(1), dim3(MU_NT), 0, st, *mppi, ext->n_elite, traj_cost, cand_cost, elite, stats, status);
+  MCP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(cem_fit_kernel, dim3(mppi->U), dim3(MU_NT), 0, st, *mppi, *noise, *ext, sqrt(1.0 - ext->beta * ext->beta), elite, stats, a_new,
+                     sigma_new);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
 }

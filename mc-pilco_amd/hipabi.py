@@ -20,6 +20,7 @@ MAX_HIST = 4  # rows a policy with memory reads (mcp_mlp_hist.h): MCP_MAX_HIST
 LQR_MAX_T = 2048  # rows of one mcp_lqr_pass / mcp_linearize call: MCP_LQR_MAX_T
 MPPI_MAX_K = 65536  # candidates of one plan (mcp_mppi.K): MCP_MPPI_MAX_K
 MPPI_MAX_M = 1 << 30  # trajectories of one plan (mcp_mppi.K * P): MCP_MPPI_MAX_M
+CEM_MAX_ELITE = 1024  # elites of one CEM update (mcp_plan_ext.n_elite): MCP_CEM_MAX_ELITE
 OK = 0
 ERRORS = {-1: "MCP_ERR_ARG", -2: "MCP_ERR_LIMIT", -3: "MCP_ERR_WORKSPACE", -4: "MCP_ERR_LAUNCH", -5: "MCP_ERR_COMM"}
 ABI_VERSION = 7
@@ -146,6 +147,14 @@ class MPPI(C.Structure):
     _fields_ = [("K", C.c_int32), ("P", C.c_int32), ("H", C.c_int32), ("U", C.c_int32), ("squash", C.c_int32),
                 ("u_max", C.c_double * MAX_INPUT), ("sigma", C.c_double * MAX_INPUT), ("lam", C.c_double), ("kappa", C.c_double),
                 ("t0", C.c_int32), ("a", dptr), ("xi", dptr), ("w", dptr)]
+
+
+class PlanExt(C.Structure):
+    """mcp_plan_ext: the planner's extension -- a std per row (``sigma_rows`` [H][U], NULL: mcp_mppi.sigma), the AR(1) coefficient ``beta`` of
+    the perturbations, the input applied before row 0 (``u_prev`` [U], NULL: none), and what the CEM update alone reads: ``n_elite``, the
+    smoothing ``alpha``, the std's floor ``sigma_min`` per input."""
+    _fields_ = [("sigma_rows", dptr), ("u_prev", dptr), ("beta", C.c_double), ("alpha", C.c_double), ("sigma_min", C.c_double * MAX_INPUT),
+                ("n_elite", C.c_int32)]
 
 
 class Dispatch(C.Structure):
@@ -277,6 +286,10 @@ _SIGS = {
     "mcp_mppi_rollout": (C.c_int, [C.POINTER(Model), C.POINTER(MPPI), C.POINTER(Cost), C.POINTER(CostInputs), C.POINTER(Noise), C.c_int, dptr, dptr,
                                    dptr, dptr, dptr, dptr]),
     "mcp_mppi_update": (C.c_int, [C.POINTER(MPPI), C.POINTER(Noise), dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
+    "mcp_plan_rollout": (C.c_int, [C.POINTER(Model), C.POINTER(MPPI), C.POINTER(PlanExt), C.POINTER(Cost), C.POINTER(CostInputs), C.POINTER(Noise),
+                                   C.c_int, dptr, dptr, dptr, dptr, dptr, dptr]),
+    "mcp_mppi_update_ext": (C.c_int, [C.POINTER(MPPI), C.POINTER(PlanExt), C.POINTER(Noise), dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
+    "mcp_cem_update": (C.c_int, [C.POINTER(MPPI), C.POINTER(PlanExt), C.POINTER(Noise), dptr, dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
     "mcp_adam_step_guarded": (C.c_int, [C.c_int, C.POINTER(dptr), C.POINTER(dptr), C.POINTER(dptr), C.POINTER(dptr), C.POINTER(C.c_int64), C.c_double,
                                         C.c_double, C.c_double, C.c_double, dptr, C.c_int64, C.c_int, dptr, dptr, dptr, dptr]),
     "mcp_nll_epoch_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

@@ -865,6 +865,176 @@ def mppi_update(mppi: PackedMPPI, traj_cost, a, *, noise: Optional[NoiseSpec] = 
     return a_new, cand, wts, stats, status
 
 
+class PackedPlanExt:
+    """mcp_plan_ext without its device pointers (include/mcpilco_hip.h): the planner's extension over ``H`` rows of ``U`` inputs.  ``beta`` in
+    [0, 1): the AR(1) coefficient of the perturbations (0: white); ``sigma_rows`` [H,U] HOST values (None: PackedMPPI's sigma for every row)
+    -- a std per row and input, >= 0 and finite, uploaded once per device --; and what the CEM update alone reads: ``n_elite`` >= 1 (at most
+    MCP_CEM_MAX_ELITE; against K when an entry sees the plan), the smoothing ``alpha`` in [0, 1), the floor ``sigma_min`` of the new std (a
+    scalar or one per input, >= 0 and finite).  Everything is checked on the host values first: a bad descriptor raises ValueError before a
+    device is touched.  ``to_c(dev, sigma_rows, u_prev)`` binds the std -- ``sigma_rows``: a DEVICE buffer [H,U] in place of this object's own,
+    e.g. the CEM update's output, which the caller vouches for -- and the input applied before row 0 (device [U], or None)."""
+
+    def __init__(self, H, U, beta=0.0, sigma_rows=None, n_elite=1, alpha=0.0, sigma_min=0.0):
+        H, U = int(H), int(U)
+        if H < 2 or not 1 <= U <= abi.MAX_INPUT:
+            raise ValueError("plan ext: H >= 2 rows and 1..%d inputs are needed (H %d, U %d)" % (abi.MAX_INPUT, H, U))
+        beta, alpha, n_elite = float(beta), float(alpha), int(n_elite)
+        if not 0.0 <= beta < 1.0:
+            raise ValueError("plan ext: the AR(1) coefficient beta must lie in [0, 1) (%r)" % (beta,))
+        if not 0.0 <= alpha < 1.0:
+            raise ValueError("plan ext: the smoothing alpha must lie in [0, 1) (%r)" % (alpha,))
+        if not 1 <= n_elite <= abi.CEM_MAX_ELITE:
+            raise ValueError("plan ext: 1..%d elites are supported (%d given)" % (abi.CEM_MAX_ELITE, n_elite))
+        smin = np.full(U, float(sigma_min)) if np.ndim(sigma_min) == 0 else _host(sigma_min).reshape(-1)
+        if smin.size != U or not bool(np.all(np.isfinite(smin) & (smin >= 0))):
+            raise ValueError("plan ext: sigma_min holds one finite entry >= 0 per input or is such a scalar (%s)" % (smin.tolist(),))
+        if sigma_rows is not None:
+            sigma_rows = np.ascontiguousarray(_host(sigma_rows))
+            if sigma_rows.shape != (H, U):
+                raise ValueError("plan ext: sigma_rows must have the shape [%d, %d], not %s" % (H, U, list(sigma_rows.shape)))
+            if not bool(np.all(np.isfinite(sigma_rows) & (sigma_rows >= 0))):
+                raise ValueError("plan ext: every entry of sigma_rows must be finite and >= 0")
+        self.H, self.U, self.beta, self.alpha, self.n_elite, self.sigma_min, self.sigma_rows = H, U, beta, alpha, n_elite, smin, sigma_rows
+        self._dev = {}
+
+    def rows_on(self, dev):
+        """This object's own sigma_rows on ``dev`` (uploaded once), or None."""
+        if self.sigma_rows is None:
+            return None
+        key = str(dev)
+        if key not in self._dev:
+            self._dev[key] = _t(self.sigma_rows, dev)
+        return self._dev[key]
+
+    def to_c(self, dev, sigma_rows=None, u_prev=None):
+        rows = self.rows_on(dev) if sigma_rows is None else sigma_rows
+        c = abi.PlanExt()
+        c.beta, c.alpha, c.n_elite = self.beta, self.alpha, self.n_elite
+        for k in range(self.U):
+            c.sigma_min[k] = float(self.sigma_min[k])
+        c.sigma_rows = None if rows is None else rows.data_ptr()
+        c.u_prev = None if u_prev is None else u_prev.data_ptr()
+        c._keep = (rows, u_prev)  # (the buffers live as long as the descriptor)
+        return c
+
+
+def _ext_operands(ext, mp, dev, sigma_rows, u_prev):
+    """The extension against the plan, its device operands checked: (ext or None, sigma_rows, u_prev)."""
+    if ext is not None and (ext.H != mp.H or ext.U != mp.U):
+        raise ValueError("plan ext: made for H %d, U %d, the plan has H %d, U %d" % (ext.H, ext.U, mp.H, mp.U))
+    if ext is None and (sigma_rows is not None or u_prev is not None):
+        ext = PackedPlanExt(mp.H, mp.U)
+    sigma_rows, u_prev = _lqr_operands(dev, ("sigma_rows", sigma_rows, (mp.H, mp.U)), ("u_prev", u_prev, (mp.U,)))
+    return ext, sigma_rows, u_prev
+
+
+def plan_rollout(model: PackedModel, mppi: PackedMPPI, ext: Optional[PackedPlanExt], cost: "PackedCost", x0, a, *, sigma_rows=None, u_prev=None,
+                 cost_inputs: Optional["PackedCostInputs"] = None, noise: Optional[NoiseSpec] = None, particle_pred=False, xi=None, w=None, t0=0,
+                 want_states=False, want_inputs=False, traj_cost=None, status=None):
+    """``mppi_rollout`` under the planner's extension (mcp_plan_rollout): inputs squash(a[t] + s(t) xi_t) with the std per row of ``ext`` --
+    or of the DEVICE buffer ``sigma_rows`` [H,U] in its place -- and the perturbations coloured by ext.beta (``xi`` [H,K,U] holds the WHITE
+    normals; the colouring happens in the kernel); ``u_prev`` (device [U], post-squash): the input applied before row 0, which the rate term
+    at t = 0 is then taken against.  ``ext`` None and neither buffer given, or an ext with every field at its default: the launch of
+    ``mppi_rollout``, bit for bit.  Everything else as ``mppi_rollout``."""
+    dev = model.device
+    if mppi.U != model.U:
+        raise ValueError("mppi: the plan has %d inputs, the model %d" % (mppi.U, model.U))
+    ext, sigma_rows, u_prev = _ext_operands(ext, mppi, dev, sigma_rows, u_prev)
+    a, xi, w = _mppi_operands(mppi, dev, a, xi, w)
+    (x0,) = _lqr_operands(dev, ("x0", x0, (model.S,)))
+    (traj_cost,) = _lqr_operands(dev, ("traj_cost", traj_cost, (mppi.M,)))
+    if cost.kind == "traj" and cost.traj_len < int(t0) + mppi.H:
+        raise ValueError("target trajectory has %d rows but the plan reads rows %d .. %d" % (cost.traj_len, int(t0), int(t0) + mppi.H - 1))
+    if cost_inputs is not None and cost_inputs.U != model.U:
+        raise ValueError("mppi: the input cost is over %d inputs, the model has %d" % (cost_inputs.U, model.U))
+    noise = NoiseSpec() if noise is None else noise
+    if particle_pred:
+        _check_noise(noise, mppi.H, mppi.P, model.G, 0)
+    status = _status_word(status, dev, "the model's device")
+    if traj_cost is None:
+        traj_cost = torch.empty(mppi.M, dtype=DT, device=dev)
+    states = torch.empty(mppi.H, mppi.M, model.S, dtype=DT, device=dev) if want_states else None
+    inputs = torch.empty(mppi.H, mppi.M, model.U, dtype=DT, device=dev) if want_inputs else None
+    mc, nz = mppi.to_c(a, xi, w, t0), noise.to_c()
+    ec = None if ext is None else ext.to_c(dev, sigma_rows, u_prev)
+    abi.check(abi.lib().mcp_plan_rollout(_mc(model), C.byref(mc), None if ec is None else C.byref(ec), C.byref(cost.c),
+                                         None if cost_inputs is None else C.byref(cost_inputs.c), C.byref(nz), int(bool(particle_pred)),
+                                         abi.ptr(x0), abi.ptr(traj_cost), abi.ptr(states), abi.ptr(inputs), abi.ptr(status), abi.stream()),
+              "mcp_plan_rollout")
+    return traj_cost, states, inputs, status
+
+
+def mppi_update_ext(mppi: PackedMPPI, ext: Optional[PackedPlanExt], traj_cost, a, *, sigma_rows=None, noise: Optional[NoiseSpec] = None, xi=None,
+                    a_new=None, out=None, status=None):
+    """``mppi_update`` under the planner's extension (mcp_mppi_update_ext): a_new = a + s(t) sum_k w_k xi_t(k) with the std per row and the
+    AR(1) colouring of ``ext`` (``sigma_rows``: a DEVICE buffer [H,U] in place of ext's own; ``xi`` holds the WHITE normals): the weighted
+    sums of the white normals per row, then the filter over those H U sums.  A default ext (or None): ``mppi_update``, bit for bit.
+    Returns (a_new, cand_cost, weights, stats, status) as ``mppi_update``."""
+    if not isinstance(traj_cost, torch.Tensor):
+        raise ValueError("traj_cost must be a float64 tensor")
+    dev = traj_cost.device
+    cand, wts, stats = (None, None, None) if out is None else out
+    traj_cost, a, xi, a_new, cand, wts, stats = _lqr_operands(dev, ("traj_cost", traj_cost, (mppi.M,)), ("a", a, (mppi.H, mppi.U)),
+                                                              ("xi", xi, (mppi.H, mppi.K, mppi.U)), ("a_new", a_new, (mppi.H, mppi.U)),
+                                                              ("cand_cost", cand, (mppi.K,)), ("weights", wts, (mppi.K,)), ("stats", stats, (4,)))
+    ext, sigma_rows, _ = _ext_operands(ext, mppi, dev, sigma_rows, None)
+    if a_new is not None and a_new.data_ptr() == a.data_ptr():
+        raise ValueError("mppi: a_new must not be the nominal's own buffer")
+    new = lambda *s: torch.empty(*s, dtype=DT, device=dev)
+    a_new = new(mppi.H, mppi.U) if a_new is None else a_new
+    cand, wts, stats = (new(mppi.K) if cand is None else cand), (new(mppi.K) if wts is None else wts), (new(4) if stats is None else stats)
+    status = _status_word(status, dev, "the plan's device")
+    noise = NoiseSpec() if noise is None else noise
+    mc, nz = mppi.to_c(a, xi, None, 0), noise.to_c()
+    ec = None if ext is None else ext.to_c(dev, sigma_rows, None)
+    abi.check(abi.lib().mcp_mppi_update_ext(C.byref(mc), None if ec is None else C.byref(ec), C.byref(nz), abi.ptr(traj_cost), abi.ptr(a_new),
+                                            abi.ptr(cand), abi.ptr(wts), abi.ptr(stats), abi.ptr(status), abi.stream()), "mcp_mppi_update_ext")
+    return a_new, cand, wts, stats, status
+
+
+def cem_update(mppi: PackedMPPI, ext: PackedPlanExt, traj_cost, a, *, sigma_rows=None, noise: Optional[NoiseSpec] = None, xi=None, a_new=None,
+               sigma_new=None, out=None, status=None):
+    """The CEM update in two small launches (mcp_cem_update): candidate costs as ``mppi_update``; the elites are the E' = min(ext.n_elite,
+    #finite) candidates with the smallest (S_k, k), selected and ranked on the device; with the perturbations REGENERATED for the elites
+    alone (``xi`` [H,K,U] white normals or Philox stream 3 of ``noise``, coloured by ext.beta), m and v their mean and (two-pass, 1 / E')
+    variance per row and input, a_new = alpha a + (1 - alpha)(a + s m) and sigma_new = max(sigma_min, sqrt(alpha s^2 + (1 - alpha) s^2 v))
+    around the current std s of ``ext`` (``sigma_rows``: a DEVICE buffer [H,U] in its place).  ``a_new``, ``sigma_new`` [H,U] (neither of
+    them ``a`` or the std's buffer) and ``out`` = (cand_cost [K], elite int32 [n_elite], stats [4]) are buffers to reuse.  Returns (a_new,
+    sigma_new, cand_cost, elite, stats, status); elite holds -1 behind the E' used, stats = S_min, argmin k, E', the elites' mean cost.
+    With no finite candidate a_new = a and sigma_new = s.  Bitwise reproducible.  No autograd."""
+    if not isinstance(traj_cost, torch.Tensor):
+        raise ValueError("traj_cost must be a float64 tensor")
+    if ext is None:
+        raise ValueError("cem: a PackedPlanExt (n_elite, alpha, sigma_min) is needed")
+    if ext.n_elite > mppi.K:
+        raise ValueError("cem: %d elites of %d candidates" % (ext.n_elite, mppi.K))
+    dev = traj_cost.device
+    cand, elite, stats = (None, None, None) if out is None else out
+    traj_cost, a, xi, a_new, sigma_new, cand, stats = _lqr_operands(dev, ("traj_cost", traj_cost, (mppi.M,)), ("a", a, (mppi.H, mppi.U)),
+                                                                    ("xi", xi, (mppi.H, mppi.K, mppi.U)), ("a_new", a_new, (mppi.H, mppi.U)),
+                                                                    ("sigma_new", sigma_new, (mppi.H, mppi.U)), ("cand_cost", cand, (mppi.K,)),
+                                                                    ("stats", stats, (4,)))
+    ext, sigma_rows, _ = _ext_operands(ext, mppi, dev, sigma_rows, None)
+    if elite is not None and (not isinstance(elite, torch.Tensor) or elite.dtype != torch.int32 or tuple(elite.shape) != (ext.n_elite,)
+                              or elite.device != dev or not elite.is_contiguous()):
+        raise ValueError("elite must be a contiguous int32 tensor [%d] on the plan's device" % ext.n_elite)
+    ec = ext.to_c(dev, sigma_rows, None)
+    taken = {a.data_ptr()} | ({ec._keep[0].data_ptr()} if ec._keep[0] is not None else set())
+    outs = [t.data_ptr() for t in (a_new, sigma_new) if t is not None]
+    if any(p in taken for p in outs) or len(set(outs)) != len(outs):
+        raise ValueError("cem: a_new and sigma_new are buffers of their own, neither the nominal's nor the std's")
+    new = lambda *s: torch.empty(*s, dtype=DT, device=dev)
+    a_new, sigma_new = (new(mppi.H, mppi.U) if a_new is None else a_new), (new(mppi.H, mppi.U) if sigma_new is None else sigma_new)
+    cand, stats = (new(mppi.K) if cand is None else cand), (new(4) if stats is None else stats)
+    elite = torch.empty(ext.n_elite, dtype=torch.int32, device=dev) if elite is None else elite
+    status = _status_word(status, dev, "the plan's device")
+    noise = NoiseSpec() if noise is None else noise
+    mc, nz = mppi.to_c(a, xi, None, 0), noise.to_c()
+    abi.check(abi.lib().mcp_cem_update(C.byref(mc), C.byref(ec), C.byref(nz), abi.ptr(traj_cost), abi.ptr(a_new), abi.ptr(sigma_new), abi.ptr(cand),
+                                       abi.ptr(elite), abi.ptr(stats), abi.ptr(status), abi.stream()), "mcp_cem_update")
+    return a_new, sigma_new, cand, elite, stats, status
+
+
 # --------------------------------------------------------------------------------------
 # fused closed loop under a feedback policy (autograd): the PD law, the tanh MLP
 # --------------------------------------------------------------------------------------

@@ -18,7 +18,7 @@ u = squash(PD(x, t) + net(x, t)), mcp_rollout_mlp_res.
 ``PID_controller`` (this project's own) is PD_controller with a clamped integral of the position error and a third trainable gain; it runs
 inside the fused closed loop like its parent, mcp_rollout_pid.
 ``MPPI_controller`` (this project's own) is the receding-horizon sampling planner on the learned model: policy_learning/mppi.py once per control
-step (mcp_mppi_rollout, mcp_mppi_update); no trainable parameters, host-side interface (``forward_np``, ``get_np_policy``).
+step (mcp_mppi_rollout, mcp_mppi_update; with ``method="cem"``, ``beta``, ``sigma_rows`` or ``charge_first_rate`` the entries of mcp_plan_ext); no trainable parameters, host-side interface (``forward_np``, ``get_np_policy``).
 Exploration policies (Random_exploration, Sum_of_sinusoids :94-150, PD_controller :406-449) drive the simulated system once per
 trial (61-201 samples): host-side, their ``np.random`` draws in the reference's order so that a seeded launch script collects the
 same data.
@@ -339,12 +339,15 @@ class MPPI_controller(Policy):
     system simulator hands ``t`` in seconds -- and step k plans with ``t0 = k`` when the cost tracks a trajectory
     (Expected_saturated_distance_from_trajectory, alone or wrapped: it needs k + H rows), else ``t0 = 0``; its call is
     ``noise.call + k * iterations``, so no two iterations of an episode share perturbations.  ``plan_par``: ``plan``'s further keywords
-    (K, P, sigma, lam, kappa, particle_pred).  ``info``: the last plan's.  It has no trainable parameters, and ``forward`` on a batch of
+    (K, P, sigma, lam, kappa, particle_pred, and method, n_elite, alpha, sigma_min, beta, sigma_rows); every control step starts from the
+    std given here -- CEM's narrowed std is not carried over.  ``charge_first_rate``: each plan after an episode's first is handed the input
+    this controller returned last as ``u_prev``, so that a cost with a rate term charges the jump from the input just applied (step 0 of an
+    episode passes nothing).  ``info``: the last plan's.  It has no trainable parameters, and ``forward`` on a batch of
     particles is not defined: as ``MC_PILCO``'s control policy it is not wired in; ``get_np_policy()`` drives
     ``simulation_class.Model.rollout``."""
 
     def __init__(self, state_dim, input_dim, model, cost, horizon=None, a_init=None, iterations=5, noise=None, flg_squash=True, u_max=1.0,
-                 dtype=torch.float64, device=torch.device("cuda"), **plan_par):
+                 dtype=torch.float64, device=torch.device("cuda"), charge_first_rate=False, **plan_par):
         super().__init__(state_dim=state_dim, input_dim=input_dim, flg_squash=flg_squash, u_max=u_max, dtype=dtype, device=device)
         if a_init is None:
             if horizon is None or int(horizon) < 2:
@@ -357,6 +360,7 @@ class MPPI_controller(Policy):
         self.iterations, self.plan_par = int(iterations), dict(plan_par)
         self.noise = ops.NoiseSpec() if noise is None else noise
         self.a, self.step, self.info = self.a_init, 0, None
+        self.charge_first_rate, self.u_last = bool(charge_first_rate), None
 
     def _tracks(self):
         from mc_pilco_amd.policy_learning import Cost_function as cf
@@ -373,16 +377,17 @@ class MPPI_controller(Policy):
         from mc_pilco_amd.policy_learning import mppi
 
         if t is not None and float(t) == 0.0:
-            self.a, self.step = self.a_init, 0
+            self.a, self.step, self.u_last = self.a_init, 0, None
         nz = ops.NoiseSpec(eps=self.noise.eps, seed=self.noise.seed, call=int(self.noise.call) + self.step * self.iterations,
                            particle_offset=self.noise.particle_offset, call_dev=self.noise.call_dev)
         a, self.info = mppi.plan(self.model, np.asarray(state, dtype=np.float64).reshape(-1), self.a, self.cost, iterations=self.iterations,
-                                 u_max=self.u_max, flg_squash=self.flg_squash, noise=nz, t0=self.step if self._tracks() else 0, **self.plan_par)
+                                 u_max=self.u_max, flg_squash=self.flg_squash, noise=nz, t0=self.step if self._tracks() else 0,
+                                 **(dict(self.plan_par, u_prev=self.u_last) if self.charge_first_rate and self.u_last is not None else self.plan_par))
         u0 = a[0].detach().cpu()
         if self.flg_squash:
             um = torch.as_tensor(np.asarray(self.u_max, dtype=np.float64))
             u0 = um * torch.tanh(u0 / um)
-        self.a, self.step = mppi.shift_warm_start(a), self.step + 1
+        self.a, self.step, self.u_last = mppi.shift_warm_start(a), self.step + 1, u0.numpy().reshape(-1).copy()
         return u0.numpy().reshape(1, -1)
 
 

@@ -13,8 +13,12 @@ and the iterations of one ``plan`` run back to back on the stream with no host s
 swapped, ``noise.call`` advances by one per iteration, the statistics of every iteration stay on the device until the end.
 
 ``Policy.MPPI_controller`` is the receding-horizon controller over ``plan``.
-Not built: elite-set / CEM updates, time-correlated perturbations, a previous-input argument for the rate term at
-t = 0, a throughput layout for mean-mode planning, GP-sharded forms, the measured (PMS) form, a state per candidate."""
+Beyond the plain planner (``method``, ``beta``, ``sigma_rows``, ``u_prev`` of ``plan``; mcp_plan_ext): the elite-set / CEM update
+(ops.cem_update: the elites selected and ranked on the device, mean and std PER ROW fitted to them, smoothed and floored), AR(1)-coloured
+perturbations and a std per row (ops.plan_rollout, ops.mppi_update_ext: the colouring happens in the kernels, still one row ahead of the
+step), and the input applied before row 0 for the rate term at t = 0.  With all of them at their defaults the calls are the plain ones.
+Not built: elites kept across iterations, a momentum on the mean, coloured noise other than AR(1), a throughput layout
+for mean-mode planning, GP-sharded forms, the measured (PMS) form, a state per candidate."""
 import numpy as np
 import torch
 
@@ -60,7 +64,7 @@ def _check_rows(pc, t0, H):
 
 
 def plan(model, x0, a_init, cost, K, P=1, iterations=1, sigma=0.3, lam=1.0, kappa=0.0, u_max=1.0, flg_squash=True, particle_pred=False,
-         noise=None, t0=0, trial_index=None):
+         noise=None, t0=0, trial_index=None, method="mppi", n_elite=None, alpha=0.1, sigma_min=0.0, beta=0.0, sigma_rows=None, u_prev=None):
     """MPPI on the GP model from the state ``x0`` [S] and the pre-squash input sequence ``a_init`` [H,U] (row H - 1 moves nothing but enters
     the cost).  ``model``: an ops.PackedModel or a Model_learning with a fused layout; ``cost``: see ``kernel_cost``; ``K`` candidates,
     ``P`` model particles each (``particle_pred``: sampled increments under common random numbers, else the mean model); ``sigma`` the
@@ -68,6 +72,15 @@ def plan(model, x0, a_init, cost, K, P=1, iterations=1, sigma=0.3, lam=1.0, kapp
     candidate's cost; ``noise``: an ops.NoiseSpec -- seed, call (iteration i plans with call + i; an ``eps`` buffer [H-1,P,G] is read by
     every iteration) -- None: seed 0, call 0; ``t0``: the row of the cost's target trajectory that plan row 0 reads (receding horizon);
     ``trial_index``: for a trajectory cost with per-trial lengthscales.
+    ``method``: "mppi" (the softmax-weighted mean) or "cem" -- the next nominal and the next std PER ROW are fitted to the ``n_elite``
+    cheapest candidates (None: K // 8, at least 1), smoothed by ``alpha`` towards the previous ones, the std floored at ``sigma_min``; the
+    temperature is not read.  ``beta`` in [0, 1): AR(1)-coloured perturbations xi_t = beta xi_{t-1} + sqrt(1 - beta^2) n_t (0: white);
+    ``sigma_rows`` [H,U]: a std per row and input in place of ``sigma`` (host values; CEM starts from it); ``u_prev`` [U]: the post-squash
+    input applied before row 0 -- the rate term of the cost at t = 0 is then taken against it.  With every one of these at its default the
+    calls are those of the plain planner (ops.mppi_rollout, ops.mppi_update); otherwise ops.plan_rollout with ops.mppi_update_ext or
+    ops.cem_update.  CEM carries (a, std) in two swapped buffer pairs and returns, beside "S_min", "nominal_cost", "status" and
+    "iterations": "sigma" [H,U] (the final std, on the device), "elite_cost" (the elites' mean cost) and "n_elite_used" per iteration,
+    "elite" (every iteration's ranked candidate indices).
 
     Runs ``iterations`` x (rollout-cost, update) on the current stream without a host synchronisation in between.  Returns (a, info):
     ``a`` [H,U] the new nominal; ``info``: "S_min", "nominal_cost" (the cost of the nominal each iteration STARTED from, cand_cost[0]),
@@ -82,19 +95,44 @@ def plan(model, x0, a_init, cost, K, P=1, iterations=1, sigma=0.3, lam=1.0, kapp
     H, n_it = int(a.shape[0]), int(iterations)
     if n_it < 1:
         raise ValueError("mppi.plan: at least one iteration")
+    if method not in ("mppi", "cem"):
+        raise ValueError("mppi.plan: method is \"mppi\" or \"cem\" (%r)" % (method,))
     mp = ops.PackedMPPI(K, P, H, pm.U, sigma, lam, kappa, u_max, flg_squash)
+    plain = method == "mppi" and float(beta) == 0.0 and sigma_rows is None and u_prev is None
+    if not plain:
+        ext = ops.PackedPlanExt(H, pm.U, beta, sigma_rows, max(1, int(K) // 8) if n_elite is None else n_elite, alpha, sigma_min)
+        if method == "cem" and ext.n_elite > mp.K:
+            raise ValueError("mppi.plan: %d elites of %d candidates" % (ext.n_elite, mp.K))
+        if u_prev is not None:
+            u_prev = ops._t(u_prev, dev).reshape(-1)
     pc, cin, w = kernel_cost(cost, pm.S, pm.U, H, dev, trial_index)
     _check_rows(pc, t0, H)
     noise = ops.NoiseSpec() if noise is None else noise
     new = lambda *s: torch.empty(*s, dtype=ops.DT, device=dev)
     b, traj, cand, wts, stats = new(H, pm.U), new(mp.M), new(n_it, mp.K), new(mp.K), new(n_it, 4)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
+    if method == "cem":
+        s = (ext.rows_on(dev) if sigma_rows is not None else ops._t(np.tile(mp.sigma, (H, 1)), dev)).clone()
+        s2, elite = new(H, pm.U), torch.empty(n_it, ext.n_elite, dtype=torch.int32, device=dev)
     for i in range(n_it):
         nz = ops.NoiseSpec(eps=noise.eps, seed=noise.seed, call=int(noise.call) + i, particle_offset=noise.particle_offset, call_dev=noise.call_dev)
-        ops.mppi_rollout(pm, mp, pc, x0, a, cost_inputs=cin, noise=nz, particle_pred=particle_pred, w=w, t0=t0, traj_cost=traj, status=status)
-        ops.mppi_update(mp, traj, a, noise=nz, a_new=b, out=(cand[i], wts, stats[i]), status=status)
+        if plain:
+            ops.mppi_rollout(pm, mp, pc, x0, a, cost_inputs=cin, noise=nz, particle_pred=particle_pred, w=w, t0=t0, traj_cost=traj, status=status)
+            ops.mppi_update(mp, traj, a, noise=nz, a_new=b, out=(cand[i], wts, stats[i]), status=status)
+        elif method == "mppi":
+            ops.plan_rollout(pm, mp, ext, pc, x0, a, u_prev=u_prev, cost_inputs=cin, noise=nz, particle_pred=particle_pred, w=w, t0=t0,
+                             traj_cost=traj, status=status)
+            ops.mppi_update_ext(mp, ext, traj, a, noise=nz, a_new=b, out=(cand[i], wts, stats[i]), status=status)
+        else:
+            ops.plan_rollout(pm, mp, ext, pc, x0, a, sigma_rows=s, u_prev=u_prev, cost_inputs=cin, noise=nz, particle_pred=particle_pred, w=w,
+                             t0=t0, traj_cost=traj, status=status)
+            ops.cem_update(mp, ext, traj, a, sigma_rows=s, noise=nz, a_new=b, sigma_new=s2, out=(cand[i], elite[i], stats[i]), status=status)
+            s, s2 = s2, s
         a, b = b, a
     st, nom = stats.cpu(), cand[:, 0].cpu()  # (the one synchronisation)
+    if method == "cem":
+        return a, dict(S_min=st[:, 0].tolist(), nominal_cost=nom.tolist(), elite_cost=st[:, 3].tolist(), n_elite_used=[int(v) for v in st[:, 2].tolist()],
+                       elite=[[k for k in row if k >= 0] for row in elite.cpu().tolist()], sigma=s, status=int(status.item()), iterations=n_it)
     info = dict(S_min=st[:, 0].tolist(), nominal_cost=nom.tolist(), ess=st[:, 2].tolist(), mean_cost=st[:, 3].tolist(),
                 status=int(status.item()), iterations=n_it)
     return a, info
