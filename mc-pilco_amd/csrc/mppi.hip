@@ -60,6 +60,18 @@ __device__ __forceinline__ double mppi_xi(const mcp_mppi& mp, const mcp_noise& n
   return mp.xi ? mp.xi[((size_t)t * mp.K + k) * mp.U + u] : philox_normal(nzl, k, t, u, MCP_STREAM_PLAN);
 }
 
+// sin and cos of a state angle with sincos_fast's bits, lane by lane.  sincos_fast sends the WHOLE wave through the library routine when one
+// lane is outside its range (NaN / inf included), and the two routines differ in the last bit here and there: a candidate lost to a NaN
+// perturbation would move the states of the healthy trajectories that share its wave -- and with them their costs and the plan.  A
+// planner drops such a candidate and keeps the rest, so the rest must not depend on it: lanes outside the range go through the library
+// routine alone, the others see a wave that is inside it.  On a wave without such a lane these are sincos_fast's (and so
+// mcp_rollout_open's) bits.
+__device__ __forceinline__ void mppi_sincos(double x, double* sp, double* cp) {
+  const bool far = !(fabs(x) < 1.0e5);
+  sincos_fast(far ? 0.0 : x, sp, cp);
+  if (__builtin_expect(far, 0)) sincos(x, sp, cp);
+}
+
 template <int PT, int MAXDEG, bool NEEDVAR, bool EXT>
 __global__ __launch_bounds__(RF_NT) void mppi_rollout_kernel(MppiKernelArgs<EXT> a) {
   extern __shared__ double smem[];
@@ -164,7 +176,7 @@ __global__ __launch_bounds__(RF_NT) void mppi_rollout_kernel(MppiKernelArgs<EXT>
         if (zi_plain >= 0) zp[zi_plain] = xn;
         if (zi_ang >= 0) {
           double sn, cs;
-          sincos_fast(xn, &sn, &cs);
+          mppi_sincos(xn, &sn, &cs);
           zp[nna + zi_ang] = sn;
           zp[nna + na + zi_ang] = cs;
         }

@@ -93,17 +93,23 @@ def point_costs(spec, x, u, t0=0):
     return f(dx) + du + dr
 
 
-def oracle_states(shape, m, x0, u, P, eps, sample):
+def oracle_states(shape, m, x0, u, P, eps, sample, fam=None, var_scale=None, step=None):
     """states [H, K P, S] of the oracle's step loop from the ONE state x0 [S] on the inputs u [H, K, U] (row H - 1 moves nothing):
-    trajectory k P + p takes candidate k's inputs and particle p's draws eps [H-1, P, G] (common random numbers)."""
+    trajectory k P + p takes candidate k's inputs and particle p's draws eps [H-1, P, G] (common random numbers).  ``fam``: the integrator
+    by the name oracle_step knows it (tests/plan_models.py hands over layout_models.family(layout)); None: pd_models.family(shape), as
+    ever.  ``var_scale``: handed to the step when given.  ``step``: a callable in oracle_step's place -- tests/plan_models.py's recording
+    step and its deliberately wrong variants."""
     Hn, K, U = u.shape
     M = K * P
+    fam = family(shape) if fam is None else fam
+    step = oracle_step if step is None else step
+    kw = {} if var_scale is None else dict(var_scale=var_scale)
     ut = torch.as_tensor(np.asarray(u, dtype=np.float64)).repeat_interleave(P, dim=1)
     xs = [torch.as_tensor(np.asarray(x0, dtype=np.float64)).reshape(1, -1).repeat(M, 1)]
     with torch.no_grad():
         for t in range(Hn - 1):
             e = torch.zeros(M, 1, dtype=DT) if eps is None else torch.as_tensor(np.asarray(eps[t], dtype=np.float64)).repeat(K, 1)
-            xs.append(oracle_step(family(shape), m, xs[-1], ut[t], e, sample)[0])
+            xs.append(step(fam, m, xs[-1], ut[t], e, sample, **kw)[0])
     return torch.stack(xs).numpy(), ut.numpy()
 
 
