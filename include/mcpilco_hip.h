@@ -971,6 +971,48 @@ int mcp_cem_update(const mcp_mppi* mppi, const mcp_plan_ext* ext, const mcp_nois
                    double* sigma_new /* [H][U] */, double* cand_cost /* [K] */, int32_t* elite /* [n_elite] */, double* stats /* [4] */,
                    uint32_t* status, void* stream);
 
+/* ---- the batched planner: B independent plans in the launches of one ----------------------------------------------------------------
+ * B problems of the SAME shape (K, P, H, U), model, cost, time weights, t0, sigma, lambda, kappa and extension scalars, each with its own
+ * start state, nominal and -- under the extension -- std rows and u_prev.  Batched operands are problem-major: mppi->a is [B][H][U],
+ * ext->sigma_rows (when given) [B][H][U], ext->u_prev (when given) [B][U], every output carries a leading B.
+ * THE CONTRACT: problem b's slice of every output carries the bits of the single-problem entry (mcp_plan_rollout, mcp_mppi_update_ext,
+ * mcp_cem_update -- and through them the plain ones when ext is default) called on problem b's operands with
+ * noise->particle_offset + b * particle_stride and the b-th xi / eps buffer.  status[b] receives problem b's flags alone; a problem with a
+ * non-finite x0 or without a finite candidate keeps its nominal (and its CEM std) and reports stats NaN, -1, 0, NaN as the single-problem
+ * entries do, and changes no bit of any other problem.
+ * The rollout runs on a grid of (ceil(K P / PT), B) workgroups -- a tile never spans two problems; the tile ladder and the LDS fit rules
+ * are the single-problem ones --, the weights / select / filter kernels on B workgroups, the mean kernel on (H, B), the CEM fit on (U, B):
+ * the summation orders inside a problem are the single-problem kernels'. */
+#define MCP_PLAN_MAX_B 4096
+typedef struct mcp_plan_batch {
+  int32_t B;                /* problems, 1 .. MCP_PLAN_MAX_B; B K P <= MCP_MPPI_MAX_M                                           */
+  int32_t x0_per_particle;  /* 0: x0 is [B][S];  1: x0 is [B][P][S], trajectory m = k P + p of problem b starts at x0[b][p]     */
+  int64_t particle_stride;  /* >= 0: problem b draws BOTH Philox streams (plan perturbations, particle id k; model increments,
+                               particle id p) as the single-problem entry does with noise->particle_offset + b * particle_stride */
+  int64_t xi_stride;        /* doubles between the problems' mppi->xi buffers: 0 (one [H][K][U] buffer for all) or >= H K U     */
+  int64_t eps_stride;       /* the same for noise->eps: 0 or >= (H-1) P G                                                       */
+} mcp_plan_batch;
+/* mcp_plan_rollout for B problems in ONE launch.  x0: [B][S] or [B][P][S] (batch->x0_per_particle); traj_cost [B][K P]; states
+ * [B][H][K P][S] and inputs [B][H][K P][U] optional; status uint32 [B].  MCP_ERR_ARG: a NULL pointer (batch included), B < 1, a negative
+ * particle_stride, a non-zero xi_stride / eps_stride below the buffer's size, and every refusal of mcp_plan_rollout; MCP_ERR_LIMIT:
+ * B > MCP_PLAN_MAX_B, B K P > MCP_MPPI_MAX_M and the limits of mcp_plan_rollout -- in that entry's one order (pointers; sizes; limits;
+ * values; the LDS fit last).  A refused call makes no HIP call. */
+int mcp_plan_batch_rollout(const mcp_model* model, const mcp_mppi* mppi, const mcp_plan_ext* ext /* may be NULL */, const mcp_plan_batch* batch,
+                           const mcp_cost* cost, const mcp_cost_inputs* cin /* may be NULL */, const mcp_noise* noise, int particle_pred,
+                           const double* x0, double* traj_cost, double* states /* or NULL */, double* inputs /* or NULL */, uint32_t* status,
+                           void* stream);
+/* mcp_mppi_update_ext for B problems: traj_cost [B][K P] -> a_new [B][H][U], cand_cost [B][K], weights [B][K], stats [B][4], status [B]
+ * (two launches, three under sigma_rows or beta != 0).  batch->eps_stride and x0_per_particle are not read.  Refusals: the batch's as
+ * above, then mcp_mppi_update_ext's. */
+int mcp_plan_batch_update(const mcp_mppi* mppi, const mcp_plan_ext* ext /* may be NULL */, const mcp_plan_batch* batch, const mcp_noise* noise,
+                          const double* traj_cost, double* a_new, double* cand_cost, double* weights, double* stats, uint32_t* status,
+                          void* stream);
+/* mcp_cem_update for B problems: a_new and sigma_new [B][H][U], cand_cost [B][K], elite int32 [B][n_elite], stats [B][4], status [B] (two
+ * launches).  Refusals: the batch's as above, then mcp_cem_update's. */
+int mcp_cem_batch_update(const mcp_mppi* mppi, const mcp_plan_ext* ext, const mcp_plan_batch* batch, const mcp_noise* noise,
+                         const double* traj_cost, double* a_new, double* sigma_new, double* cand_cost, int32_t* elite, double* stats,
+                         uint32_t* status, void* stream);
+
 /* ---- the optimizer loop's bookkeeping on the device (MC_PILCO.reinforce_policy, policy_learning/MC_PILCO.py:475-607) ----------
  * The reference decides on the host, from torch.isnan(cost), whether a rollout counts, and so reads every step's cost back before
  * it can launch the next one.  These two entry points take the same decisions from device memory after each ATTEMPT (rollout +

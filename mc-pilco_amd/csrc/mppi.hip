@@ -24,6 +24,11 @@
 //                                         instantiations are the kernels mcp_mppi_rollout always launched.
 //   mppi_mean_kernel<RAW> + mppi_filter_kernel   the weighted sums of the WHITE normals per row, then the AR(1) filter over those H U sums
 //   cem_select_kernel, cem_fit_kernel     the elite set (an on-device radix select and an LDS sort) and the fit of mean and std to it
+// Under mcp_plan_batch (mcp_plan_batch_rollout, mcp_plan_batch_update, mcp_cem_batch_update): B problems of one shape in the launches of one.
+//   mppi_rollout_kernel<.., BATCH = true>   a grid of (tiles, B): workgroup (., b) is a workgroup of the single-problem launch on problem b's
+//                                           operands (PlanProb); a tile never spans two problems
+//   *_batch_kernel                          the update kernels' bodies on B workgroups (weights, select, filter), (H, B) (mean), (U, B) (fit)
+//   Problem b's slice of every output carries the bits of the single-problem entry: nothing is reduced across problems.
 #include "cost_point.h"
 #include "rollout_open_phases.h"
 
@@ -60,6 +65,34 @@ __device__ __forceinline__ double mppi_xi(const mcp_mppi& mp, const mcp_noise& n
   return mp.xi ? mp.xi[((size_t)t * mp.K + k) * mp.U + u] : philox_normal(nzl, k, t, u, MCP_STREAM_PLAN);
 }
 
+// ---- the batched forms (mcp_plan_batch_rollout, mcp_plan_batch_update, mcp_cem_batch_update) ------------------------------------------------
+// BATCH is a template flag like EXT.  With BATCH = false every operand is the kernel argument itself and `pb` is never read: the rollout's
+// BATCH = false instantiations are the kernels mcp_mppi_rollout / mcp_plan_rollout always launched (the batched form has its own argument
+// type), and the update kernels keep their names and arguments over bodies they share with thin batched kernels.  With BATCH = true the
+// problem b is a grid coordinate and the operands that differ between problems come from `pb`: the arguments moved to problem b's slices.
+// `BATCH ? pb.x : arg.x` is decided where the template is instantiated.
+struct PlanProb {
+  const double *x0, *a, *xi, *sigma_rows, *u_prev;
+  double *traj_cost, *states, *inputs;
+  uint32_t* status;
+  int x0_per_particle;
+  mcp_noise nz;
+};
+// the noise of problem b: the launch's (the device counter folded in: the bodies' own noise_of_launch finds none) at particle_offset +
+// b * particle_stride, with the b-th eps buffer
+__device__ __forceinline__ mcp_noise noise_of_problem(const mcp_noise& nz, const mcp_plan_batch& bt, size_t b) {
+  mcp_noise r = noise_of_launch(nz);
+  r.call_dev = nullptr;
+  r.particle_offset += (int64_t)b * bt.particle_stride;
+  if (r.eps) r.eps += b * (size_t)bt.eps_stride;
+  return r;
+}
+// mppi_xi over the problem's own buffer
+__device__ __forceinline__ double plan_xi(const mcp_mppi& mp, const double* xi, const mcp_noise& nzl, int k, int t, int u) {
+  if (k == 0) return 0.0;
+  return xi ? xi[((size_t)t * mp.K + k) * mp.U + u] : philox_normal(nzl, k, t, u, MCP_STREAM_PLAN);
+}
+
 // sin and cos of a state angle with sincos_fast's bits, lane by lane.  sincos_fast sends the WHOLE wave through the library routine when one
 // lane is outside its range (NaN / inf included), and the two routines differ in the last bit here and there: a candidate lost to a NaN
 // perturbation would move the states of the healthy trajectories that share its wave -- and with them their costs and the plan.  A
@@ -72,9 +105,42 @@ __device__ __forceinline__ void mppi_sincos(double x, double* sp, double* cp) {
   if (__builtin_expect(far, 0)) sincos(x, sp, cp);
 }
 
-template <int PT, int MAXDEG, bool NEEDVAR, bool EXT>
-__global__ __launch_bounds__(RF_NT) void mppi_rollout_kernel(MppiKernelArgs<EXT> a) {
+// the batched rollout's arguments: the single-problem form's with the batch descriptor behind them, on a grid of (tiles, B) -- workgroup
+// (., b) is a workgroup of the single-problem launch on problem b's operands
+template <bool EXT>
+struct PlanBatchArgs : MppiKernelArgs<EXT> {
+  mcp_plan_batch bt;
+};
+template <bool EXT, bool BATCH>
+using LaunchArgs = typename std::conditional<BATCH, PlanBatchArgs<EXT>, MppiKernelArgs<EXT>>::type;
+
+// problem b of a batched rollout
+template <bool EXT>
+__device__ __forceinline__ PlanProb rollout_problem(const PlanBatchArgs<EXT>& a, size_t b) {
+  const size_t M = a.M, T = a.T, S = a.model.S, U = a.model.U;
+  PlanProb pb;
+  pb.x0_per_particle = a.bt.x0_per_particle;
+  pb.x0 = a.x0 + b * (a.bt.x0_per_particle ? (size_t)a.mp.P * S : S);
+  pb.a = a.mp.a + b * T * U;
+  pb.xi = a.mp.xi ? a.mp.xi + b * (size_t)a.bt.xi_stride : nullptr;
+  pb.sigma_rows = pb.u_prev = nullptr;
+  if constexpr (EXT) {
+    pb.sigma_rows = a.sigma_rows ? a.sigma_rows + b * T * U : nullptr;
+    pb.u_prev = a.u_prev ? a.u_prev + b * U : nullptr;
+  }
+  pb.traj_cost = a.traj_cost + b * M;
+  pb.states = a.states ? a.states + b * T * M * S : nullptr;
+  pb.inputs = a.inputs ? a.inputs + b * T * M * U : nullptr;
+  pb.status = a.status + b;
+  pb.nz = noise_of_problem(a.nz, a.bt, b);
+  return pb;
+}
+
+template <int PT, int MAXDEG, bool NEEDVAR, bool EXT, bool BATCH = false>
+__global__ __launch_bounds__(RF_NT) void mppi_rollout_kernel(LaunchArgs<EXT, BATCH> a) {
   extern __shared__ double smem[];
+  PlanProb pb;
+  if constexpr (BATCH) pb = rollout_problem<EXT>(a, blockIdx.y);
   const mcp_model& md = a.model;
   const int S = md.S, U = md.U, G = md.G, D = md.D, M = a.M, T = a.T, P = a.mp.P;
   const int nna = md.n_not_angle, na = md.n_angle;
@@ -89,7 +155,7 @@ __global__ __launch_bounds__(RF_NT) void mppi_rollout_kernel(MppiKernelArgs<EXT>
   double* nom = smem + L.ext;   // [T][U]
   double* ub = nom + T * U;     // [2][PT][U]
   double* srow = ub + 2 * PT * U;  // [T][U], the extended form only
-  const mcp_noise nzl = noise_of_launch(a.nz);
+  const mcp_noise nzl = noise_of_launch(BATCH ? pb.nz : a.nz);
   const int m0 = blockIdx.x * PT;
 
   stage_gp_tables(md.gp, md.var_scale, G, D, gpl, kpar, tid);
@@ -104,9 +170,17 @@ __global__ __launch_bounds__(RF_NT) void mppi_rollout_kernel(MppiKernelArgs<EXT>
       for (int j = tid; j < NP; j += RF_NT) smem[L.al + g * NP + j] = j < gp.Npad ? gp.alpha[j] : 0.0;
     }
   }
-  for (int it = tid; it < T * U; it += RF_NT) nom[it] = a.mp.a[it];
-  if constexpr (EXT)
+  for (int it = tid; it < T * U; it += RF_NT) nom[it] = (BATCH ? pb.a : a.mp.a)[it];
+  if constexpr (EXT && BATCH) {  // (two loops: one load per loop, so that no pointer into the arguments meets a device pointer in a phi --
+                                 // the compiler then keeps a private copy of the whole argument block)
+    if (pb.sigma_rows) {
+      for (int it = tid; it < T * U; it += RF_NT) srow[it] = pb.sigma_rows[it];
+    } else {
+      for (int it = tid; it < T * U; it += RF_NT) srow[it] = a.mp.sigma[it % U];
+    }
+  } else if constexpr (EXT) {
     for (int it = tid; it < T * U; it += RF_NT) srow[it] = a.sigma_rows ? a.sigma_rows[it] : a.mp.sigma[it % U];
+  }
   __syncthreads();
   // thread (p, s) owns state component s of trajectory p of the tile; the LAST PT * U threads form the inputs, the PT in front of them
   // each own a trajectory's cost (PT (S + U + 1) <= 400 of the 512 threads at every compiled limit: the three sets are disjoint)
@@ -122,7 +196,9 @@ __global__ __launch_bounds__(RF_NT) void mppi_rollout_kernel(MppiKernelArgs<EXT>
   const bool ovalid = m0 + tp < M;
   const int kc = om / P;       // the candidate
   const int pp = om - kc * P;  // the model particle: the id the GP increments are drawn with
-  double xn = own ? a.x0[os] : 0.0;
+  double xn = own ? (BATCH ? pb.x0 : a.x0)[os] : 0.0;
+  if constexpr (BATCH)
+    if (own && pb.x0_per_particle) xn = pb.x0[pp * S + os];  // a start state per model particle
   int zi_plain = -1, zi_ang = -1, g_vel = -1, g_pos = -1, vel_of_pos = 0;
   if (own) {
     for (int i = 0; i < nna; ++i)
@@ -148,17 +224,18 @@ __global__ __launch_bounds__(RF_NT) void mppi_rollout_kernel(MppiKernelArgs<EXT>
   if (isu) {
     umax = a.mp.u_max[uk];
     if constexpr (EXT) {
-      xic = mppi_xi(a.mp, nzl, kc, 0, uk);  // xi_0 = n_0
+      xic = BATCH ? plan_xi(a.mp, pb.xi, nzl, kc, 0, uk) : mppi_xi(a.mp, nzl, kc, 0, uk);  // xi_0 = n_0
       sig = srow[uk];
-      if (a.u_prev) ub[(PT + up) * U + uk] = a.u_prev[uk];  // row -1 has the slot of the odd rows: rewritten by row 1, two barriers on
+      const double* u_prev = BATCH ? pb.u_prev : a.u_prev;
+      if (u_prev) ub[(PT + up) * U + uk] = u_prev[uk];  // row -1 has the slot of the odd rows: rewritten by row 1, two barriers on
     } else {
       sig = a.mp.sigma[uk];
-      xic = mppi_xi(a.mp, nzl, kc, 0, uk);
+      xic = BATCH ? plan_xi(a.mp, pb.xi, nzl, kc, 0, uk) : mppi_xi(a.mp, nzl, kc, 0, uk);
     }
     const double av = nom[uk] + sig * xic;
     ucur = a.mp.squash ? umax * fast_tanh(av / umax) : av;
   }
-  if constexpr (EXT) has_up = a.u_prev != nullptr;
+  if constexpr (EXT) has_up = (BATCH ? pb.u_prev : a.u_prev) != nullptr;
   double jsum = 0.0;  // the trajectory's running cost
   lds_barrier();
 
@@ -168,7 +245,8 @@ __global__ __launch_bounds__(RF_NT) void mppi_rollout_kernel(MppiKernelArgs<EXT>
     if (own) {
       xs[cur * PT * S + op * S + os] = xn;
       if (ovalid) {
-        if (a.states) a.states[((size_t)t * M + m0 + op) * S + os] = xn;
+        double* states = BATCH ? pb.states : a.states;
+        if (states) states[((size_t)t * M + m0 + op) * S + os] = xn;
         if (is_bad(xn)) bad |= MCP_STATUS_NAN;
       }
       if (more) {
@@ -186,7 +264,8 @@ __global__ __launch_bounds__(RF_NT) void mppi_rollout_kernel(MppiKernelArgs<EXT>
       ub[((t & 1) * PT + up) * U + uk] = ucur;
       if (more) z[up * D + nna + 2 * na + uk] = ucur;
       if (ovalid) {
-        if (a.inputs) a.inputs[((size_t)t * M + m0 + up) * U + uk] = ucur;
+        double* inputs = BATCH ? pb.inputs : a.inputs;
+        if (inputs) inputs[((size_t)t * M + m0 + up) * U + uk] = ucur;
         if (is_bad(ucur)) bad |= MCP_STATUS_NAN;
       }
     }
@@ -203,10 +282,10 @@ __global__ __launch_bounds__(RF_NT) void mppi_rollout_kernel(MppiKernelArgs<EXT>
     if (isu) {         // u_{t+1}, a row ahead
       double av;
       if constexpr (EXT) {
-        xic = fma(a.beta, xic, a.cnew * mppi_xi(a.mp, nzl, kc, t + 1, uk));
+        xic = fma(a.beta, xic, a.cnew * (BATCH ? plan_xi(a.mp, pb.xi, nzl, kc, t + 1, uk) : mppi_xi(a.mp, nzl, kc, t + 1, uk)));
         av = nom[(t + 1) * U + uk] + srow[(t + 1) * U + uk] * xic;
       } else {
-        av = nom[(t + 1) * U + uk] + sig * mppi_xi(a.mp, nzl, kc, t + 1, uk);
+        av = nom[(t + 1) * U + uk] + sig * (BATCH ? plan_xi(a.mp, pb.xi, nzl, kc, t + 1, uk) : mppi_xi(a.mp, nzl, kc, t + 1, uk));
       }
       ucur = a.mp.squash ? umax * fast_tanh(av / umax) : av;
     }
@@ -277,10 +356,10 @@ __global__ __launch_bounds__(RF_NT) void mppi_rollout_kernel(MppiKernelArgs<EXT>
     cur ^= 1;
   }
   if (isc && ovalid) {
-    a.traj_cost[m0 + ct] = jsum;
+    (BATCH ? pb.traj_cost : a.traj_cost)[m0 + ct] = jsum;
     if (is_bad(jsum)) bad |= MCP_STATUS_NAN;
   }
-  if (bad) atomicOr(a.status, bad);
+  if (bad) atomicOr(BATCH ? pb.status : a.status, bad);
 }
 
 // ---- the update ---------------------------------------------------------------------------------------------------------------------------
@@ -298,9 +377,10 @@ __device__ __forceinline__ double mppi_block_sum(double v, double* red, int tid)
   return red[0];
 }
 
-__global__ __launch_bounds__(MU_NT) void mppi_weights_kernel(mcp_mppi mp, const double* __restrict__ traj_cost, double* __restrict__ cand_cost,
-                                                             double* __restrict__ weights, double* __restrict__ stats,
-                                                             uint32_t* __restrict__ status) {
+// Every update kernel is a body over ONE problem's operands and two thin kernels: the single-problem one hands it its arguments, the batched one
+// (grid y, or x where the single-problem kernel is one workgroup: the problem b) its arguments moved to problem b's slices.
+__device__ __forceinline__ void mppi_weights_body(const mcp_mppi& mp, const double* __restrict__ traj_cost, double* __restrict__ cand_cost,
+                                                  double* __restrict__ weights, double* __restrict__ stats, uint32_t* __restrict__ status) {
   __shared__ double red[MU_NT];
   __shared__ double mins[MU_NT];
   __shared__ int mink[MU_NT];
@@ -375,11 +455,31 @@ __global__ __launch_bounds__(MU_NT) void mppi_weights_kernel(mcp_mppi mp, const 
   ws = mppi_block_sum(ws, red, tid);
   if (tid == 0) stats[0] = smin, stats[1] = (double)kmin, stats[2] = 1.0 / w2, stats[3] = ws;
 }
+__global__ __launch_bounds__(MU_NT) void mppi_weights_kernel(mcp_mppi mp, const double* __restrict__ traj_cost, double* __restrict__ cand_cost,
+                                                             double* __restrict__ weights, double* __restrict__ stats,
+                                                             uint32_t* __restrict__ status) {
+  mppi_weights_body(mp, traj_cost, cand_cost, weights, stats, status);
+}
+__global__ __launch_bounds__(MU_NT) void mppi_weights_batch_kernel(mcp_mppi mp, const double* __restrict__ traj_cost, double* __restrict__ cand_cost,
+                                                                   double* __restrict__ weights, double* __restrict__ stats,
+                                                                   uint32_t* __restrict__ status) {
+  const size_t b = blockIdx.x;
+  mppi_weights_body(mp, traj_cost + b * (size_t)mp.K * mp.P, cand_cost + b * mp.K, weights + b * mp.K, stats + 4 * b, status + b);
+}
+
+// the nominal and the xi buffer of problem b of a batched update (what its bodies read of a PlanProb)
+__device__ __forceinline__ PlanProb update_problem(const mcp_mppi& mp, const mcp_plan_batch& bt, size_t b) {
+  PlanProb pb;
+  pb.a = mp.a + b * (size_t)mp.H * mp.U;
+  pb.xi = mp.xi ? mp.xi + b * (size_t)bt.xi_stride : nullptr;
+  return pb;
+}
 
 // one workgroup per row t: a_new[t][u] = a[t][u] + sigma[u] sum_{k >= 1, w_k != 0} w_k xi(k, t, u); RAW (mcp_mppi_update_ext): the weighted
 // sum N_t[u] of the WHITE normals alone is left in a_new[t][u] for mppi_filter_kernel
-template <bool RAW>
-__global__ __launch_bounds__(MU_NT) void mppi_mean_kernel(mcp_mppi mp, mcp_noise nz, const double* __restrict__ weights, double* __restrict__ a_new) {
+template <bool RAW, bool BATCH>
+__device__ __forceinline__ void mppi_mean_body(const mcp_mppi& mp, const mcp_noise& nz, const PlanProb& pb, const double* __restrict__ weights,
+                                               double* __restrict__ a_new) {
   __shared__ double red[MU_NT];
   const int tid = threadIdx.x, t = blockIdx.x, K = mp.K, U = mp.U;
   const mcp_noise nzl = noise_of_launch(nz);
@@ -387,17 +487,28 @@ __global__ __launch_bounds__(MU_NT) void mppi_mean_kernel(mcp_mppi mp, mcp_noise
     double acc = 0.0;
     for (int k = tid; k < K; k += MU_NT) {
       const double w = weights[k];
-      if (k >= 1 && w != 0.0) acc = fma(w, mppi_xi(mp, nzl, k, t, u), acc);
+      if (k >= 1 && w != 0.0) acc = fma(w, BATCH ? plan_xi(mp, pb.xi, nzl, k, t, u) : mppi_xi(mp, nzl, k, t, u), acc);
     }
     acc = mppi_block_sum(acc, red, tid);
-    if (tid == 0) a_new[(size_t)t * U + u] = RAW ? acc : mp.a[(size_t)t * U + u] + mp.sigma[u] * acc;
+    if (tid == 0) a_new[(size_t)t * U + u] = RAW ? acc : (BATCH ? pb.a : mp.a)[(size_t)t * U + u] + mp.sigma[u] * acc;
   }
+}
+template <bool RAW>
+__global__ __launch_bounds__(MU_NT) void mppi_mean_kernel(mcp_mppi mp, mcp_noise nz, const double* __restrict__ weights, double* __restrict__ a_new) {
+  mppi_mean_body<RAW, false>(mp, nz, PlanProb{}, weights, a_new);
+}
+template <bool RAW>
+__global__ __launch_bounds__(MU_NT) void mppi_mean_batch_kernel(mcp_mppi mp, mcp_noise nz, mcp_plan_batch bt, const double* __restrict__ weights,
+                                                                double* __restrict__ a_new) {
+  const size_t b = blockIdx.y;
+  mppi_mean_body<RAW, true>(mp, noise_of_problem(nz, bt, b), update_problem(mp, bt, b), weights + b * mp.K, a_new + b * (size_t)mp.H * mp.U);
 }
 
 // The perturbation sum is linear in the white normals, so the AR(1) filter runs over the H U weighted sums instead of over every candidate:
 // thread u walks the rows, X_0 = N_0, X_t = fma(beta, X_{t-1}, cnew N_t), a_new[t][u] = a[t][u] + s(t, u) X_t (in place of N_t).
-__global__ __launch_bounds__(MCP_MAX_INPUT) void mppi_filter_kernel(mcp_mppi mp, const double* __restrict__ sigma_rows, double beta, double cnew,
-                                                                    double* __restrict__ a_new) {
+template <bool BATCH>
+__device__ __forceinline__ void mppi_filter_body(const mcp_mppi& mp, const double* anom, const double* __restrict__ sigma_rows, double beta, double cnew,
+                                                 double* __restrict__ a_new) {
   const int u = threadIdx.x, U = mp.U;
   if (u >= U) return;
   double x = 0.0;
@@ -405,8 +516,17 @@ __global__ __launch_bounds__(MCP_MAX_INPUT) void mppi_filter_kernel(mcp_mppi mp,
     const size_t i = (size_t)t * U + u;
     const double n = a_new[i];
     x = t == 0 ? n : fma(beta, x, cnew * n);
-    a_new[i] = mp.a[i] + (sigma_rows ? sigma_rows[i] : mp.sigma[u]) * x;
+    a_new[i] = (BATCH ? anom : mp.a)[i] + (sigma_rows ? sigma_rows[i] : mp.sigma[u]) * x;
   }
+}
+__global__ __launch_bounds__(MCP_MAX_INPUT) void mppi_filter_kernel(mcp_mppi mp, const double* __restrict__ sigma_rows, double beta, double cnew,
+                                                                    double* __restrict__ a_new) {
+  mppi_filter_body<false>(mp, nullptr, sigma_rows, beta, cnew, a_new);
+}
+__global__ __launch_bounds__(MCP_MAX_INPUT) void mppi_filter_batch_kernel(mcp_mppi mp, const double* __restrict__ sigma_rows, double beta, double cnew,
+                                                                          double* __restrict__ a_new) {
+  const size_t o = (size_t)blockIdx.x * mp.H * mp.U;
+  mppi_filter_body<true>(mp, mp.a + o, sigma_rows ? sigma_rows + o : nullptr, beta, cnew, a_new + o);
 }
 
 // ---- the CEM update: mcp_cem_update ---------------------------------------------------------------------------------------------------------
@@ -434,8 +554,8 @@ __device__ __forceinline__ bool cem_match(unsigned long long key, int k, unsigne
   return key == tkey && (p == 8 || (k >> 8) == (tk >> 8));
 }
 
-__global__ __launch_bounds__(MU_NT) void cem_select_kernel(mcp_mppi mp, int n_elite, const double* __restrict__ traj_cost, double* __restrict__ cand_cost,
-                                                           int32_t* __restrict__ elite, double* __restrict__ stats, uint32_t* __restrict__ status) {
+__device__ __forceinline__ void cem_select_body(const mcp_mppi& mp, int n_elite, const double* __restrict__ traj_cost, double* __restrict__ cand_cost,
+                                                int32_t* __restrict__ elite, double* __restrict__ stats, uint32_t* __restrict__ status) {
   __shared__ double red[MU_NT];
   __shared__ unsigned long long skey[MCP_CEM_MAX_ELITE];
   __shared__ int sk[MCP_CEM_MAX_ELITE];
@@ -548,19 +668,31 @@ __global__ __launch_bounds__(MU_NT) void cem_select_kernel(mcp_mppi mp, int n_el
   cs = mppi_block_sum(cs, red, tid);
   if (tid == 0) stats[0] = cand_cost[sk[0]], stats[1] = (double)sk[0], stats[2] = (double)E, stats[3] = cs / (double)E;
 }
+__global__ __launch_bounds__(MU_NT) void cem_select_kernel(mcp_mppi mp, int n_elite, const double* __restrict__ traj_cost, double* __restrict__ cand_cost,
+                                                           int32_t* __restrict__ elite, double* __restrict__ stats, uint32_t* __restrict__ status) {
+  cem_select_body(mp, n_elite, traj_cost, cand_cost, elite, stats, status);
+}
+__global__ __launch_bounds__(MU_NT) void cem_select_batch_kernel(mcp_mppi mp, int n_elite, const double* __restrict__ traj_cost,
+                                                                 double* __restrict__ cand_cost, int32_t* __restrict__ elite, double* __restrict__ stats,
+                                                                 uint32_t* __restrict__ status) {
+  const size_t b = blockIdx.x;
+  cem_select_body(mp, n_elite, traj_cost + b * (size_t)mp.K * mp.P, cand_cost + b * mp.K, elite + b * (size_t)n_elite, stats + 4 * b, status + b);
+}
 
-__global__ __launch_bounds__(MU_NT) void cem_fit_kernel(mcp_mppi mp, mcp_noise nz, mcp_plan_ext ex, double cnew, const int32_t* __restrict__ elite,
-                                                        const double* __restrict__ stats, double* __restrict__ a_new, double* __restrict__ sigma_new) {
+template <bool BATCH>
+__device__ __forceinline__ void cem_fit_body(const mcp_mppi& mp, const mcp_noise& nz, const mcp_plan_ext& ex, const PlanProb& pb, double cnew,
+                                             const int32_t* __restrict__ elite, const double* __restrict__ stats, double* __restrict__ a_new,
+                                             double* __restrict__ sigma_new) {
   __shared__ double red[MU_NT];
   const int tid = threadIdx.x, u = blockIdx.x, U = mp.U, H = mp.H;
   const mcp_noise nzl = noise_of_launch(nz);
-  const double* sigma_rows = ex.sigma_rows;
+  const double* sigma_rows = BATCH ? pb.sigma_rows : ex.sigma_rows;
   const double beta = ex.beta, alpha = ex.alpha, sigma_min = ex.sigma_min[u];
   const int E = imin((int)stats[2], ex.n_elite);  // (E' of cem_select_kernel, earlier on the stream)
   if (E <= 0) {
     for (int t = tid; t < H; t += MU_NT) {
       const size_t i = (size_t)t * U + u;
-      a_new[i] = mp.a[i];
+      a_new[i] = (BATCH ? pb.a : mp.a)[i];
       sigma_new[i] = sigma_rows ? sigma_rows[i] : mp.sigma[u];
     }
     return;
@@ -579,7 +711,7 @@ __global__ __launch_bounds__(MU_NT) void cem_fit_kernel(mcp_mppi mp, mcp_noise n
 #pragma unroll
     for (int j = 0; j < CEM_SLOTS; ++j)
       if (ks[j] >= 0) {  // ascending rank
-        const double n = mppi_xi(mp, nzl, ks[j], t, u);
+        const double n = BATCH ? plan_xi(mp, pb.xi, nzl, ks[j], t, u) : mppi_xi(mp, nzl, ks[j], t, u);
         xi[j] = t == 0 ? n : fma(beta, xi[j], cnew * n);
         acc += xi[j];
       }
@@ -594,12 +726,24 @@ __global__ __launch_bounds__(MU_NT) void cem_fit_kernel(mcp_mppi mp, mcp_noise n
     const double v = mppi_block_sum(q, red, tid) / inv;
     if (tid == 0) {
       const size_t i = (size_t)t * U + u;
-      const double s = sigma_rows ? sigma_rows[i] : mp.sigma[u], a = mp.a[i];
+      const double s = sigma_rows ? sigma_rows[i] : mp.sigma[u], a = (BATCH ? pb.a : mp.a)[i];
       a_new[i] = alpha * a + (1.0 - alpha) * (a + s * mean);
       const double s2 = s * s;
       sigma_new[i] = fmax(sigma_min, sqrt(alpha * s2 + (1.0 - alpha) * s2 * v));
     }
   }
+}
+__global__ __launch_bounds__(MU_NT) void cem_fit_kernel(mcp_mppi mp, mcp_noise nz, mcp_plan_ext ex, double cnew, const int32_t* __restrict__ elite,
+                                                        const double* __restrict__ stats, double* __restrict__ a_new, double* __restrict__ sigma_new) {
+  cem_fit_body<false>(mp, nz, ex, PlanProb{}, cnew, elite, stats, a_new, sigma_new);
+}
+__global__ __launch_bounds__(MU_NT) void cem_fit_batch_kernel(mcp_mppi mp, mcp_noise nz, mcp_plan_ext ex, mcp_plan_batch bt, double cnew,
+                                                              const int32_t* __restrict__ elite, const double* __restrict__ stats,
+                                                              double* __restrict__ a_new, double* __restrict__ sigma_new) {
+  const size_t b = blockIdx.y, hu = (size_t)mp.H * mp.U;
+  PlanProb pb = update_problem(mp, bt, b);
+  pb.sigma_rows = ex.sigma_rows ? ex.sigma_rows + b * hu : nullptr;
+  cem_fit_body<true>(mp, noise_of_problem(nz, bt, b), ex, pb, cnew, elite + b * (size_t)ex.n_elite, stats + 4 * b, a_new + b * hu, sigma_new + b * hu);
 }
 
 // ---- host path: checks -> fill -> ladder (a refused call makes no HIP call) ----------------------------------------------------------------
@@ -622,19 +766,33 @@ static int mppi_values(const mcp_mppi* mp) {
   return MCP_OK;
 }
 
-template <int PT, int MAXDEG, bool NEEDVAR, bool EXT>
-static int launch_mppi(const MppiKernelArgs<EXT>& a, hipStream_t st) {
+// the descriptor of a batched call, behind mppi_sizes: its limits (MCP_ERR_LIMIT), and -- with the plan's values -- its strides (G: the
+// model's GPs, for the eps buffer; < 0: an update, which reads no eps)
+static int plan_batch_limits(const mcp_plan_batch* bt, const mcp_mppi* mp) {
+  return (bt->B > MCP_PLAN_MAX_B || (int64_t)bt->B * mp->K * mp->P > MCP_MPPI_MAX_M) ? MCP_ERR_LIMIT : MCP_OK;
+}
+static int plan_batch_values(const mcp_plan_batch* bt, const mcp_mppi* mp, int G) {
+  if (bt->particle_stride < 0) return MCP_ERR_ARG;
+  if (bt->xi_stride != 0 && bt->xi_stride < (int64_t)mp->H * mp->K * mp->U) return MCP_ERR_ARG;
+  if (G >= 0 && bt->eps_stride != 0 && bt->eps_stride < (int64_t)(mp->H - 1) * mp->P * G) return MCP_ERR_ARG;
+  return MCP_OK;
+}
+
+template <int PT, int MAXDEG, bool NEEDVAR, bool EXT, bool BATCH = false>
+static int launch_mppi(const LaunchArgs<EXT, BATCH>& a, hipStream_t st) {
   const OpenLayout L = open_layout(PT, NEEDVAR, a.model.S, a.model.D, a.model.G, a.NpadMax, false, 0, false, mppi_extra(PT, a.T, a.model.U, EXT));
   const size_t lds = (size_t)L.total * sizeof(double);
   if (lds > MCP_LDS_LIMIT) return MCP_ERR_LIMIT;
-  MCP_ENSURE_MAX_LDS((mppi_rollout_kernel<PT, MAXDEG, NEEDVAR, EXT>));
-  hipLaunchKernelGGL((mppi_rollout_kernel<PT, MAXDEG, NEEDVAR, EXT>), dim3((a.M + PT - 1) / PT), dim3(RF_NT), lds, st, a);
+  dim3 grid((a.M + PT - 1) / PT);
+  if constexpr (BATCH) grid.y = a.bt.B;  // (tiles of ONE problem, problems): a tile never spans two problems
+  MCP_ENSURE_MAX_LDS((mppi_rollout_kernel<PT, MAXDEG, NEEDVAR, EXT, BATCH>));
+  hipLaunchKernelGGL((mppi_rollout_kernel<PT, MAXDEG, NEEDVAR, EXT, BATCH>), grid, dim3(RF_NT), lds, st, a);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
 }
-template <int PT, bool NEEDVAR, bool EXT>
-static int launch_mppi_deg(const MppiKernelArgs<EXT>& a, int maxdeg, hipStream_t st) {
-  return maxdeg == 0 ? launch_mppi<PT, 0, NEEDVAR, EXT>(a, st) : launch_mppi<PT, 2, NEEDVAR, EXT>(a, st);
+template <int PT, bool NEEDVAR, bool EXT, bool BATCH = false>
+static int launch_mppi_deg(const LaunchArgs<EXT, BATCH>& a, int maxdeg, hipStream_t st) {
+  return maxdeg == 0 ? launch_mppi<PT, 0, NEEDVAR, EXT, BATCH>(a, st) : launch_mppi<PT, 2, NEEDVAR, EXT, BATCH>(a, st);
 }
 
 // the nominal's rows (the extended form: and the std's) beside the largest layout of a rung must fit the LDS: looked at BEFORE the first
@@ -645,11 +803,11 @@ static bool mppi_fits(const MppiArgs& a, int PT, bool needvar, bool ext = false)
 }
 
 // the ladder of rollout_open.hip's forward form without a record: the mean chain one trajectory per workgroup, with variances 16, then 4
-template <bool EXT>
-static int mppi_ladder(const MppiKernelArgs<EXT>& a, int maxdeg, hipStream_t st) {
-  if (!a.sample) return mppi_fits(a, 1, false, EXT) ? launch_mppi_deg<1, false, EXT>(a, maxdeg, st) : MCP_ERR_LIMIT;
-  if (mppi_fits(a, 16, true, EXT)) return launch_mppi_deg<16, true, EXT>(a, maxdeg, st);
-  return mppi_fits(a, 4, true, EXT) ? launch_mppi_deg<4, true, EXT>(a, maxdeg, st) : MCP_ERR_LIMIT;
+template <bool EXT, bool BATCH = false>
+static int mppi_ladder(const LaunchArgs<EXT, BATCH>& a, int maxdeg, hipStream_t st) {
+  if (!a.sample) return mppi_fits(a, 1, false, EXT) ? launch_mppi_deg<1, false, EXT, BATCH>(a, maxdeg, st) : MCP_ERR_LIMIT;
+  if (mppi_fits(a, 16, true, EXT)) return launch_mppi_deg<16, true, EXT, BATCH>(a, maxdeg, st);
+  return mppi_fits(a, 4, true, EXT) ? launch_mppi_deg<4, true, EXT, BATCH>(a, maxdeg, st) : MCP_ERR_LIMIT;
 }
 
 // the extension's own refusals (MCP_ERR_ARG; the device rows of sigma_rows are the caller's to check): what the rollout and the MPPI update
@@ -657,15 +815,19 @@ static int mppi_ladder(const MppiKernelArgs<EXT>& a, int maxdeg, hipStream_t st)
 static bool plan_ext_default(const mcp_plan_ext* e) { return !e || (!e->sigma_rows && !e->u_prev && e->beta == 0.0); }
 static int plan_ext_values(const mcp_plan_ext* e) { return (e && !(e->beta >= 0.0 && e->beta < 1.0)) ? MCP_ERR_ARG : MCP_OK; }
 
-// the checks of both rollout entries in their one order, then the fill
+// the checks of the rollout entries in their one order, then the fill (batch: the batched entry's descriptor, checked with the plan's sizes,
+// limits and values; NULL: a single-problem entry)
 static int mppi_rollout_fill(MppiArgs& a, int* maxdeg, const mcp_model* model, const mcp_mppi* mppi, const mcp_plan_ext* ext, const mcp_cost* cost,
                              const mcp_cost_inputs* cin, const mcp_noise* noise, int particle_pred, const double* x0, double* traj_cost,
-                             double* states, double* inputs, uint32_t* status) {
+                             double* states, double* inputs, uint32_t* status, const mcp_plan_batch* batch = nullptr) {
   if (!model || !mppi || !cost || !noise || !x0 || !traj_cost || !status) return MCP_ERR_ARG;
+  if (batch && batch->B < 1) return MCP_ERR_ARG;
   const int src = mppi_sizes(mppi);
   if (src != MCP_OK) return src;
+  if (batch && plan_batch_limits(batch, mppi) != MCP_OK) return MCP_ERR_LIMIT;
   if (!model_within_limits(model)) return MCP_ERR_LIMIT;
   if (!model_ok(model) || mppi->U != model->U || mppi_values(mppi) != MCP_OK || plan_ext_values(ext) != MCP_OK) return MCP_ERR_ARG;
+  if (batch && plan_batch_values(batch, mppi, model->G) != MCP_OK) return MCP_ERR_ARG;
   if (!cost_ok(cost) || cost->S != model->S || !cost_inputs_ok(cin) || (cin && cin->U != model->U)) return MCP_ERR_ARG;
   *maxdeg = open_fill(a, model, noise, mppi->K * mppi->P, mppi->H, particle_pred, x0, nullptr, 0, nullptr, states, nullptr, nullptr, nullptr, status);
   a.mp = *mppi;
@@ -753,6 +915,79 @@ extern "C" int mcp_cem_update(const mcp_mppi* mppi, const mcp_plan_ext* ext, con
   MCP_LAUNCH_CHECK();
   hipLaunchKernelGGL(cem_fit_kernel, dim3(mppi->U), dim3(MU_NT), 0, st, *mppi, *noise, *ext, sqrt(1.0 - ext->beta * ext->beta), elite, stats, a_new,
                      sigma_new);
+  MCP_LAUNCH_CHECK();
+  return MCP_OK;
+}
+
+// ---- the batched entries: the single-problem entries' checks with the batch descriptor's among them, the same decisions, the batched kernels ----
+extern "C" int mcp_plan_batch_rollout(const mcp_model* model, const mcp_mppi* mppi, const mcp_plan_ext* ext, const mcp_plan_batch* batch,
+                                      const mcp_cost* cost, const mcp_cost_inputs* cin, const mcp_noise* noise, int particle_pred, const double* x0,
+                                      double* traj_cost, double* states, double* inputs, uint32_t* status, void* stream) {
+  if (!batch) return MCP_ERR_ARG;
+  PlanBatchArgs<true> a;
+  int maxdeg = 0;
+  const int rc = mppi_rollout_fill(a, &maxdeg, model, mppi, ext, cost, cin, noise, particle_pred, x0, traj_cost, states, inputs, status, batch);
+  if (rc != MCP_OK) return rc;
+  a.bt = *batch;
+  if (plan_ext_default(ext)) {  // the plain kernel's batched form, as mcp_plan_rollout takes the plain kernel
+    PlanBatchArgs<false> p;
+    static_cast<MppiArgs&>(p) = a;
+    p.bt = *batch;
+    return mppi_ladder<false, true>(p, maxdeg, (hipStream_t)stream);
+  }
+  a.sigma_rows = ext->sigma_rows;
+  a.u_prev = ext->u_prev;
+  a.beta = ext->beta;
+  a.cnew = sqrt(1.0 - ext->beta * ext->beta);
+  return mppi_ladder<true, true>(a, maxdeg, (hipStream_t)stream);
+}
+
+extern "C" int mcp_plan_batch_update(const mcp_mppi* mppi, const mcp_plan_ext* ext, const mcp_plan_batch* batch, const mcp_noise* noise,
+                                     const double* traj_cost, double* a_new, double* cand_cost, double* weights, double* stats, uint32_t* status,
+                                     void* stream) {
+  if (!mppi || !batch || !noise || !traj_cost || !a_new || !cand_cost || !weights || !stats || !status) return MCP_ERR_ARG;
+  if (batch->B < 1) return MCP_ERR_ARG;
+  const int rc = mppi_sizes(mppi);
+  if (rc != MCP_OK) return rc;
+  if (plan_batch_limits(batch, mppi) != MCP_OK) return MCP_ERR_LIMIT;
+  if (mppi_values(mppi) != MCP_OK || plan_ext_values(ext) != MCP_OK || plan_batch_values(batch, mppi, -1) != MCP_OK) return MCP_ERR_ARG;
+  if (a_new == mppi->a || (ext && a_new == ext->sigma_rows)) return MCP_ERR_ARG;
+  const bool coloured = ext && (ext->sigma_rows || ext->beta != 0.0);  // (else mcp_mppi_update's two kernels, as mcp_mppi_update_ext decides)
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 rows(mppi->H, batch->B);
+  hipLaunchKernelGGL(mppi_weights_batch_kernel, dim3(batch->B), dim3(MU_NT), 0, st, *mppi, traj_cost, cand_cost, weights, stats, status);
+  MCP_LAUNCH_CHECK();
+  if (!coloured) {
+    hipLaunchKernelGGL(mppi_mean_batch_kernel<false>, rows, dim3(MU_NT), 0, st, *mppi, *noise, *batch, weights, a_new);
+    MCP_LAUNCH_CHECK();
+    return MCP_OK;
+  }
+  hipLaunchKernelGGL(mppi_mean_batch_kernel<true>, rows, dim3(MU_NT), 0, st, *mppi, *noise, *batch, weights, a_new);
+  MCP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(mppi_filter_batch_kernel, dim3(batch->B), dim3(MCP_MAX_INPUT), 0, st, *mppi, ext->sigma_rows, ext->beta,
+                     sqrt(1.0 - ext->beta * ext->beta), a_new);
+  MCP_LAUNCH_CHECK();
+  return MCP_OK;
+}
+
+extern "C" int mcp_cem_batch_update(const mcp_mppi* mppi, const mcp_plan_ext* ext, const mcp_plan_batch* batch, const mcp_noise* noise,
+                                    const double* traj_cost, double* a_new, double* sigma_new, double* cand_cost, int32_t* elite, double* stats,
+                                    uint32_t* status, void* stream) {
+  if (!mppi || !ext || !batch || !noise || !traj_cost || !a_new || !sigma_new || !cand_cost || !elite || !stats || !status) return MCP_ERR_ARG;
+  if (ext->n_elite < 1 || batch->B < 1) return MCP_ERR_ARG;
+  const int rc = mppi_sizes(mppi);
+  if (rc != MCP_OK) return rc;
+  if (ext->n_elite > MCP_CEM_MAX_ELITE || ext->n_elite > mppi->K || plan_batch_limits(batch, mppi) != MCP_OK) return MCP_ERR_LIMIT;
+  if (mppi_values(mppi) != MCP_OK || plan_ext_values(ext) != MCP_OK || !(ext->alpha >= 0.0 && ext->alpha < 1.0)) return MCP_ERR_ARG;
+  for (int k = 0; k < mppi->U; ++k)
+    if (!(ext->sigma_min[k] >= 0.0) || !mppi_finite(ext->sigma_min[k])) return MCP_ERR_ARG;
+  if (plan_batch_values(batch, mppi, -1) != MCP_OK) return MCP_ERR_ARG;
+  if (a_new == mppi->a || a_new == ext->sigma_rows || sigma_new == mppi->a || sigma_new == ext->sigma_rows || a_new == sigma_new) return MCP_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(cem_select_batch_kernel, dim3(batch->B), dim3(MU_NT), 0, st, *mppi, ext->n_elite, traj_cost, cand_cost, elite, stats, status);
+  MCP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(cem_fit_batch_kernel, dim3(mppi->U, batch->B), dim3(MU_NT), 0, st, *mppi, *noise, *ext, *batch, sqrt(1.0 - ext->beta * ext->beta),
+                     elite, stats, a_new, sigma_new);
   MCP_LAUNCH_CHECK();
   return MCP_OK;
 }

@@ -21,6 +21,7 @@ LQR_MAX_T = 2048  # rows of one mcp_lqr_pass / mcp_linearize call: MCP_LQR_MAX_T
 MPPI_MAX_K = 65536  # candidates of one plan (mcp_mppi.K): MCP_MPPI_MAX_K
 MPPI_MAX_M = 1 << 30  # trajectories of one plan (mcp_mppi.K * P): MCP_MPPI_MAX_M
 CEM_MAX_ELITE = 1024  # elites of one CEM update (mcp_plan_ext.n_elite): MCP_CEM_MAX_ELITE
+PLAN_MAX_B = 4096  # problems of one batched plan (mcp_plan_batch.B): MCP_PLAN_MAX_B
 OK = 0
 ERRORS = {-1: "MCP_ERR_ARG", -2: "MCP_ERR_LIMIT", -3: "MCP_ERR_WORKSPACE", -4: "MCP_ERR_LAUNCH", -5: "MCP_ERR_COMM"}
 ABI_VERSION = 7
@@ -157,6 +158,13 @@ class PlanExt(C.Structure):
                 ("n_elite", C.c_int32)]
 
 
+class PlanBatch(C.Structure):
+    """mcp_plan_batch: B problems of one shape in the launches of one plan -- ``x0_per_particle`` (x0 [B][P][S] instead of [B][S]), the Philox
+    particle ids of problem b shifted by b * ``particle_stride``, the doubles between the problems' xi / eps buffers (0: one shared buffer)."""
+    _fields_ = [("B", C.c_int32), ("x0_per_particle", C.c_int32), ("particle_stride", C.c_int64), ("xi_stride", C.c_int64),
+                ("eps_stride", C.c_int64)]
+
+
 class Dispatch(C.Structure):
     """include/mcpilco_hip_debug.h: struct mcp_dispatch -- the request a call carries (all zero = automatic) and what it reports back."""
     _fields_ = [("fwd_particles", C.c_int32), ("gp_sharding", C.c_int32), ("fwd_lean", C.c_int32), ("policy_split", C.c_int32), ("row_split", C.c_int32),
@@ -290,6 +298,12 @@ _SIGS = {
                                    C.c_int, dptr, dptr, dptr, dptr, dptr, dptr]),
     "mcp_mppi_update_ext": (C.c_int, [C.POINTER(MPPI), C.POINTER(PlanExt), C.POINTER(Noise), dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
     "mcp_cem_update": (C.c_int, [C.POINTER(MPPI), C.POINTER(PlanExt), C.POINTER(Noise), dptr, dptr, dptr, dptr, dptr, dptr, dptr, dptr]),
+    "mcp_plan_batch_rollout": (C.c_int, [C.POINTER(Model), C.POINTER(MPPI), C.POINTER(PlanExt), C.POINTER(PlanBatch), C.POINTER(Cost),
+                                         C.POINTER(CostInputs), C.POINTER(Noise), C.c_int, dptr, dptr, dptr, dptr, dptr, dptr]),
+    "mcp_plan_batch_update": (C.c_int, [C.POINTER(MPPI), C.POINTER(PlanExt), C.POINTER(PlanBatch), C.POINTER(Noise), dptr, dptr, dptr, dptr, dptr,
+                                        dptr, dptr]),
+    "mcp_cem_batch_update": (C.c_int, [C.POINTER(MPPI), C.POINTER(PlanExt), C.POINTER(PlanBatch), C.POINTER(Noise), dptr, dptr, dptr, dptr, dptr,
+                                       dptr, dptr, dptr]),
     "mcp_adam_step_guarded": (C.c_int, [C.c_int, C.POINTER(dptr), C.POINTER(dptr), C.POINTER(dptr), C.POINTER(dptr), C.POINTER(C.c_int64), C.c_double,
                                         C.c_double, C.c_double, C.c_double, dptr, C.c_int64, C.c_int, dptr, dptr, dptr, dptr]),
     "mcp_nll_epoch_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

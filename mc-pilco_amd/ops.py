@@ -1036,6 +1036,188 @@ def cem_update(mppi: PackedMPPI, ext: PackedPlanExt, traj_cost, a, *, sigma_rows
 
 
 # --------------------------------------------------------------------------------------
+# the batched planner: B plans of one shape in the launches of one (no autograd)
+# --------------------------------------------------------------------------------------
+class PackedPlanBatch:
+    """mcp_plan_batch without its buffer strides (include/mcpilco_hip.h): ``B`` problems of ``P`` model particles per candidate each.
+    ``x0_per_particle``: the start states are [B,P,S], trajectory k P + p of problem b starts at x0[b,p] (else [B,S]); ``particle_stride``
+    >= 0: problem b draws both Philox streams as the single-problem entry does at ``noise.particle_offset + b * particle_stride`` (0: common
+    random numbers across the problems).  Checked on the host values first: ValueError before a device is touched.  ``to_c(xi_stride,
+    eps_stride)``: the doubles between the problems' xi / eps buffers (0: one buffer for all)."""
+
+    def __init__(self, B, P, x0_per_particle=False, particle_stride=0):
+        if isinstance(particle_stride, float) and not float(particle_stride).is_integer():
+            raise ValueError("plan batch: particle_stride is a whole number (%r)" % (particle_stride,))
+        B, P, stride = int(B), int(P), int(particle_stride)
+        if not 1 <= B <= abi.PLAN_MAX_B:
+            raise ValueError("plan batch: 1..%d problems are supported (%d given)" % (abi.PLAN_MAX_B, B))
+        if P < 1 or B * P > abi.MPPI_MAX_M:
+            raise ValueError("plan batch: P >= 1 particles, and at most %d trajectories over all problems (P %d, B P %d)" % (abi.MPPI_MAX_M, P, B * P))
+        if not 0 <= stride < 2 ** 40:
+            raise ValueError("plan batch: particle_stride must be >= 0 and below 2^40, the range of a particle id (%d)" % stride)
+        self.B, self.P, self.x0_per_particle, self.particle_stride = B, P, bool(x0_per_particle), stride
+
+    def to_c(self, xi_stride=0, eps_stride=0):
+        c = abi.PlanBatch()
+        c.B, c.x0_per_particle, c.particle_stride, c.xi_stride, c.eps_stride = self.B, int(self.x0_per_particle), self.particle_stride, int(xi_stride), int(eps_stride)
+        return c
+
+
+def _batch_plan(bt, mp):
+    if not isinstance(bt, PackedPlanBatch):
+        raise ValueError("plan batch: a PackedPlanBatch is needed")
+    if bt.P != mp.P:
+        raise ValueError("plan batch: made for P %d, the plan has P %d" % (bt.P, mp.P))
+    if bt.B * mp.M > abi.MPPI_MAX_M:
+        raise ValueError("plan batch: at most %d trajectories over all problems (B K P %d)" % (abi.MPPI_MAX_M, bt.B * mp.M))
+
+
+def _batch_shared(t, one, B):
+    """(shape to check ``t`` against, stride in doubles between the problems) of a buffer that is one for all problems (``one``) or one per
+    problem ([B] + one)."""
+    if isinstance(t, torch.Tensor) and t.dim() == len(one) + 1:
+        return (B,) + tuple(one), int(np.prod(one))
+    return tuple(one), 0
+
+
+def _batch_status(status, dev, B, where):
+    if status is None:
+        return torch.zeros(B, dtype=torch.int32, device=dev)
+    if not isinstance(status, torch.Tensor) or status.dtype != torch.int32 or tuple(status.shape) != (B,) or status.device != dev or not status.is_contiguous():
+        raise ValueError("status must be a contiguous int32 tensor [%d] on %s" % (B, where))
+    return status
+
+
+def _batch_ext(ext, mp, bt, dev, sigma_rows, u_prev):
+    """``_ext_operands`` for B problems: sigma_rows [B,H,U] and u_prev [B,U] on the device -- an ext's own host rows [H,U] are every
+    problem's."""
+    if ext is not None and (ext.H != mp.H or ext.U != mp.U):
+        raise ValueError("plan ext: made for H %d, U %d, the plan has H %d, U %d" % (ext.H, ext.U, mp.H, mp.U))
+    if ext is None and (sigma_rows is not None or u_prev is not None):
+        ext = PackedPlanExt(mp.H, mp.U)
+    sigma_rows, u_prev = _lqr_operands(dev, ("sigma_rows", sigma_rows, (bt.B, mp.H, mp.U)), ("u_prev", u_prev, (bt.B, mp.U)))
+    if ext is not None and sigma_rows is None and ext.sigma_rows is not None:
+        sigma_rows = ext.rows_on(dev).unsqueeze(0).repeat(bt.B, 1, 1)
+    return ext, sigma_rows, u_prev
+
+
+def plan_batch_rollout(model: PackedModel, mppi: PackedMPPI, ext: Optional[PackedPlanExt], batch: PackedPlanBatch, cost: "PackedCost", x0, a, *,
+                       sigma_rows=None, u_prev=None, cost_inputs: Optional["PackedCostInputs"] = None, noise: Optional[NoiseSpec] = None,
+                       particle_pred=False, xi=None, w=None, t0=0, want_states=False, want_inputs=False, traj_cost=None, status=None):
+    """``plan_rollout`` for ``batch.B`` problems in ONE launch (mcp_plan_batch_rollout): ``x0`` [B,S] (or [B,P,S] with
+    batch.x0_per_particle), ``a`` [B,H,U], ``sigma_rows`` [B,H,U] and ``u_prev`` [B,U] on the device; ``xi`` [H,K,U] (one buffer for all) or
+    [B,H,K,U]; ``noise.eps`` [H-1,P,G] or [B,H-1,P,G]; model, cost, ``w``, ``t0`` and the plan's scalars are shared.  Problem b's slices
+    carry the bits of ``plan_rollout`` on its operands with noise.particle_offset + b * batch.particle_stride.  Returns (traj_cost [B,K P],
+    states [B,H,K P,S] or None, inputs [B,H,K P,U] or None, status int32 [B] -- one word per problem).  No autograd.  ValueError for an
+    operand of the wrong dtype, shape or device."""
+    dev = model.device
+    if mppi.U != model.U:
+        raise ValueError("mppi: the plan has %d inputs, the model %d" % (mppi.U, model.U))
+    _batch_plan(batch, mppi)
+    B = batch.B
+    ext, sigma_rows, u_prev = _batch_ext(ext, mppi, batch, dev, sigma_rows, u_prev)
+    xi_shape, xi_stride = _batch_shared(xi, (mppi.H, mppi.K, mppi.U), B)
+    a, xi, w, x0, traj_cost = _lqr_operands(dev, ("a", a, (B, mppi.H, mppi.U)), ("xi", xi, xi_shape), ("w", w, (mppi.H,)),
+                                            ("x0", x0, (B, mppi.P, model.S) if batch.x0_per_particle else (B, model.S)),
+                                            ("traj_cost", traj_cost, (B, mppi.M)))
+    if cost.kind == "traj" and cost.traj_len < int(t0) + mppi.H:
+        raise ValueError("target trajectory has %d rows but the plan reads rows %d .. %d" % (cost.traj_len, int(t0), int(t0) + mppi.H - 1))
+    if cost_inputs is not None and cost_inputs.U != model.U:
+        raise ValueError("mppi: the input cost is over %d inputs, the model has %d" % (cost_inputs.U, model.U))
+    noise = NoiseSpec() if noise is None else noise
+    eps_stride = 0
+    if particle_pred and noise.eps is not None:
+        eps_shape, eps_stride = _batch_shared(noise.eps, (mppi.H - 1, mppi.P, model.G), B)
+        _lqr_operands(dev, ("noise.eps", noise.eps, eps_shape))
+    status = _batch_status(status, dev, B, "the model's device")
+    if traj_cost is None:
+        traj_cost = torch.empty(B, mppi.M, dtype=DT, device=dev)
+    states = torch.empty(B, mppi.H, mppi.M, model.S, dtype=DT, device=dev) if want_states else None
+    inputs = torch.empty(B, mppi.H, mppi.M, model.U, dtype=DT, device=dev) if want_inputs else None
+    mc, nz, bc = mppi.to_c(a, xi, w, t0), noise.to_c(), batch.to_c(xi_stride, eps_stride)
+    ec = None if ext is None else ext.to_c(dev, sigma_rows, u_prev)
+    abi.check(abi.lib().mcp_plan_batch_rollout(_mc(model), C.byref(mc), None if ec is None else C.byref(ec), C.byref(bc), C.byref(cost.c),
+                                               None if cost_inputs is None else C.byref(cost_inputs.c), C.byref(nz), int(bool(particle_pred)),
+                                               abi.ptr(x0), abi.ptr(traj_cost), abi.ptr(states), abi.ptr(inputs), abi.ptr(status), abi.stream()),
+              "mcp_plan_batch_rollout")
+    return traj_cost, states, inputs, status
+
+
+def _batch_update_operands(mppi, batch, traj_cost, a, xi, named):
+    """The operands every batched update shares, checked: (dev, xi_stride, [traj_cost, a, xi] + the tensors of ``named``)."""
+    if not isinstance(traj_cost, torch.Tensor):
+        raise ValueError("traj_cost must be a float64 tensor")
+    _batch_plan(batch, mppi)
+    dev, B = traj_cost.device, batch.B
+    xi_shape, xi_stride = _batch_shared(xi, (mppi.H, mppi.K, mppi.U), B)
+    return dev, xi_stride, _lqr_operands(dev, ("traj_cost", traj_cost, (B, mppi.M)), ("a", a, (B, mppi.H, mppi.U)), ("xi", xi, xi_shape), *named)
+
+
+def plan_batch_update(mppi: PackedMPPI, ext: Optional[PackedPlanExt], batch: PackedPlanBatch, traj_cost, a, *, sigma_rows=None,
+                      noise: Optional[NoiseSpec] = None, xi=None, a_new=None, out=None, status=None):
+    """``mppi_update_ext`` for ``batch.B`` problems (mcp_plan_batch_update; two launches, three under a std per row or beta != 0):
+    ``traj_cost`` [B,K P], ``a`` [B,H,U], ``sigma_rows`` [B,H,U] on the device, ``xi`` [H,K,U] or [B,H,K,U]; ``a_new`` [B,H,U] and ``out`` =
+    (cand_cost [B,K], weights [B,K], stats [B,4]) are buffers to reuse.  Returns (a_new, cand_cost, weights, stats, status int32 [B]); problem
+    b's slices carry the bits of ``mppi_update_ext`` on its operands.  No autograd."""
+    B = batch.B if isinstance(batch, PackedPlanBatch) else 0
+    cand, wts, stats = (None, None, None) if out is None else out
+    dev, xi_stride, (traj_cost, a, xi, a_new, cand, wts, stats) = _batch_update_operands(
+        mppi, batch, traj_cost, a, xi, (("a_new", a_new, (B, mppi.H, mppi.U)), ("cand_cost", cand, (B, mppi.K)), ("weights", wts, (B, mppi.K)),
+                                        ("stats", stats, (B, 4))))
+    ext, sigma_rows, _ = _batch_ext(ext, mppi, batch, dev, sigma_rows, None)
+    if a_new is not None and a_new.data_ptr() == a.data_ptr():
+        raise ValueError("mppi: a_new must not be the nominal's own buffer")
+    new = lambda *s: torch.empty(*s, dtype=DT, device=dev)
+    a_new = new(B, mppi.H, mppi.U) if a_new is None else a_new
+    cand, wts, stats = (new(B, mppi.K) if cand is None else cand), (new(B, mppi.K) if wts is None else wts), (new(B, 4) if stats is None else stats)
+    status = _batch_status(status, dev, B, "the plan's device")
+    noise = NoiseSpec() if noise is None else noise
+    mc, nz, bc = mppi.to_c(a, xi, None, 0), noise.to_c(), batch.to_c(xi_stride, 0)
+    ec = None if ext is None else ext.to_c(dev, sigma_rows, None)
+    abi.check(abi.lib().mcp_plan_batch_update(C.byref(mc), None if ec is None else C.byref(ec), C.byref(bc), C.byref(nz), abi.ptr(traj_cost),
+                                              abi.ptr(a_new), abi.ptr(cand), abi.ptr(wts), abi.ptr(stats), abi.ptr(status), abi.stream()),
+              "mcp_plan_batch_update")
+    return a_new, cand, wts, stats, status
+
+
+def cem_batch_update(mppi: PackedMPPI, ext: PackedPlanExt, batch: PackedPlanBatch, traj_cost, a, *, sigma_rows=None, noise: Optional[NoiseSpec] = None,
+                     xi=None, a_new=None, sigma_new=None, out=None, status=None):
+    """``cem_update`` for ``batch.B`` problems (mcp_cem_batch_update; two launches): ``traj_cost`` [B,K P], ``a`` [B,H,U], ``sigma_rows``
+    [B,H,U] on the device (None: the ext's own rows, or the plan's sigma, for every problem); ``a_new``, ``sigma_new`` [B,H,U] and ``out`` =
+    (cand_cost [B,K], elite int32 [B,n_elite], stats [B,4]) are buffers to reuse.  Returns (a_new, sigma_new, cand_cost, elite, stats, status
+    int32 [B]); problem b's slices carry the bits of ``cem_update`` on its operands.  No autograd."""
+    if ext is None:
+        raise ValueError("cem: a PackedPlanExt (n_elite, alpha, sigma_min) is needed")
+    if ext.n_elite > mppi.K:
+        raise ValueError("cem: %d elites of %d candidates" % (ext.n_elite, mppi.K))
+    B = batch.B if isinstance(batch, PackedPlanBatch) else 0
+    cand, elite, stats = (None, None, None) if out is None else out
+    dev, xi_stride, (traj_cost, a, xi, a_new, sigma_new, cand, stats) = _batch_update_operands(
+        mppi, batch, traj_cost, a, xi, (("a_new", a_new, (B, mppi.H, mppi.U)), ("sigma_new", sigma_new, (B, mppi.H, mppi.U)),
+                                        ("cand_cost", cand, (B, mppi.K)), ("stats", stats, (B, 4))))
+    ext, sigma_rows, _ = _batch_ext(ext, mppi, batch, dev, sigma_rows, None)
+    if elite is not None and (not isinstance(elite, torch.Tensor) or elite.dtype != torch.int32 or tuple(elite.shape) != (B, ext.n_elite)
+                              or elite.device != dev or not elite.is_contiguous()):
+        raise ValueError("elite must be a contiguous int32 tensor [%d, %d] on the plan's device" % (B, ext.n_elite))
+    ec = ext.to_c(dev, sigma_rows, None)
+    taken = {a.data_ptr()} | ({ec._keep[0].data_ptr()} if ec._keep[0] is not None else set())
+    outs = [t.data_ptr() for t in (a_new, sigma_new) if t is not None]
+    if any(p in taken for p in outs) or len(set(outs)) != len(outs):
+        raise ValueError("cem: a_new and sigma_new are buffers of their own, neither the nominal's nor the std's")
+    new = lambda *s: torch.empty(*s, dtype=DT, device=dev)
+    a_new, sigma_new = (new(B, mppi.H, mppi.U) if a_new is None else a_new), (new(B, mppi.H, mppi.U) if sigma_new is None else sigma_new)
+    cand, stats = (new(B, mppi.K) if cand is None else cand), (new(B, 4) if stats is None else stats)
+    elite = torch.empty(B, ext.n_elite, dtype=torch.int32, device=dev) if elite is None else elite
+    status = _batch_status(status, dev, B, "the plan's device")
+    noise = NoiseSpec() if noise is None else noise
+    mc, nz, bc = mppi.to_c(a, xi, None, 0), noise.to_c(), batch.to_c(xi_stride, 0)
+    abi.check(abi.lib().mcp_cem_batch_update(C.byref(mc), C.byref(ec), C.byref(bc), C.byref(nz), abi.ptr(traj_cost), abi.ptr(a_new),
+                                             abi.ptr(sigma_new), abi.ptr(cand), abi.ptr(elite), abi.ptr(stats), abi.ptr(status), abi.stream()),
+              "mcp_cem_batch_update")
+    return a_new, sigma_new, cand, elite, stats, status
+
+
+# --------------------------------------------------------------------------------------
 # fused closed loop under a feedback policy (autograd): the PD law, the tanh MLP
 # --------------------------------------------------------------------------------------
 # What the one host path below (_closed_launch, _closed_sweep, RolloutClosedFunction, _rollout_closed) reads of a packed policy:

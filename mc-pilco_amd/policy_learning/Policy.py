@@ -342,9 +342,16 @@ class MPPI_controller(Policy):
     (K, P, sigma, lam, kappa, particle_pred, and method, n_elite, alpha, sigma_min, beta, sigma_rows); every control step starts from the
     std given here -- CEM's narrowed std is not carried over.  ``charge_first_rate``: each plan after an episode's first is handed the input
     this controller returned last as ``u_prev``, so that a cost with a rate term charges the jump from the input just applied (step 0 of an
-    episode passes nothing).  ``info``: the last plan's.  It has no trainable parameters, and ``forward`` on a batch of
-    particles is not defined: as ``MC_PILCO``'s control policy it is not wired in; ``get_np_policy()`` drives
-    ``simulation_class.Model.rollout``."""
+    episode passes nothing).  ``info``: the last plan's.  It has no trainable parameters; ``get_np_policy()`` drives
+    ``simulation_class.Model.rollout``.
+    ``forward(states [M, S], t)`` plans for M states at once -- ``policy_learning.mppi.plan_batch``: one plan per row in the launches of one,
+    a warm start per row, nothing read back -- and returns u_0 [M, U] on the device: as ``MC_PILCO``'s control policy the controller runs
+    the generic step loop of ``apply_policy`` (one model step per launch), which simulates the MPC on M particles of the model before it is
+    put on the system.  Row b plans as ``forward_np`` would under ``noise.particle_offset + b * particle_stride`` (``particle_stride``: a
+    keyword of this class, None: max(K, P); 0: common random numbers across the rows).  ``forward`` keeps its own episode state (warm starts,
+    last inputs, step) apart from ``forward_np``'s, under the contract of ``PID_controller.forward``: ``t`` is the step index, t == 0 resets,
+    every other call follows the previous t by one with the same M.  ``batch_info``: the last batched plan's (device tensors).  Training an
+    ``MPPI_controller`` in ``reinforce_policy`` is not built: it has nothing to train."""
 
     def __init__(self, state_dim, input_dim, model, cost, horizon=None, a_init=None, iterations=5, noise=None, flg_squash=True, u_max=1.0,
                  dtype=torch.float64, device=torch.device("cuda"), charge_first_rate=False, **plan_par):
@@ -358,9 +365,11 @@ class MPPI_controller(Policy):
             raise ValueError("a_init must be [H >= 2, U], got %s" % (tuple(self.a_init.shape),))
         self.__dict__.update(model=model, cost=cost)  # (kept out of this module's registry: the planner owns no parameters)
         self.iterations, self.plan_par = int(iterations), dict(plan_par)
+        self.particle_stride = self.plan_par.pop("particle_stride", None)  # (plan_batch's alone: forward_np plans one problem)
         self.noise = ops.NoiseSpec() if noise is None else noise
         self.a, self.step, self.info = self.a_init, 0, None
         self.charge_first_rate, self.u_last = bool(charge_first_rate), None
+        self._batch_a, self._batch_u, self._batch_t, self._batch_um, self.batch_info = None, None, None, None, None  # forward's own episode
 
     def _tracks(self):
         from mc_pilco_amd.policy_learning import Cost_function as cf
@@ -371,7 +380,37 @@ class MPPI_controller(Policy):
         return isinstance(c, cf.Expected_saturated_distance_from_trajectory)
 
     def forward(self, states, t=None, p_dropout=0.0):
-        raise NotImplementedError("MPPI_controller plans from one state at a time: use forward_np / get_np_policy()")
+        """One plan per row of ``states`` [M, S] in the launches of one plan (``policy_learning.mppi.plan_batch``): returns u_0 [M, U] on the
+        device, without grad and without a host synchronisation.  ``t`` is the STEP INDEX (``int(t)``), as for ``PID_controller``: t == 0
+        starts an episode, every other call must come with the previous t + 1 and the same M (ValueError otherwise).  ``p_dropout`` is accepted
+        and ignored."""
+        from mc_pilco_amd.policy_learning import mppi
+
+        if t is None:
+            raise ValueError("MPPI_controller.forward holds a warm start per particle: it needs the step index t (t == 0 resets it)")
+        t = int(t)
+        with torch.no_grad():
+            x = states.detach().reshape(-1, int(self.state_dim)).to(device=self.device, dtype=torch.float64).contiguous()
+            M = int(x.shape[0])
+            if t == 0:
+                self._batch_a, self._batch_u = self.a_init.to(self.device).unsqueeze(0).repeat(M, 1, 1), None
+            elif self._batch_t is None or t != self._batch_t + 1:
+                raise ValueError("MPPI_controller.forward holds the warm starts: called with t = %d after t = %s (t == 0 resets them)" % (t, self._batch_t))
+            elif int(self._batch_a.shape[0]) != M:
+                raise ValueError("MPPI_controller.forward holds the warm starts of %d particles, called with %d" % (int(self._batch_a.shape[0]), M))
+            nz = ops.NoiseSpec(eps=self.noise.eps, seed=self.noise.seed, call=int(self.noise.call) + t * self.iterations,
+                               particle_offset=self.noise.particle_offset, call_dev=self.noise.call_dev)
+            par = dict(self.plan_par, u_prev=self._batch_u) if self.charge_first_rate and self._batch_u is not None else self.plan_par
+            a, self.batch_info = mppi.plan_batch(self.model, x, self._batch_a, self.cost, iterations=self.iterations, u_max=self.u_max,
+                                                 flg_squash=self.flg_squash, noise=nz, t0=t if self._tracks() else 0,
+                                                 particle_stride=self.particle_stride, **par)
+            u0 = a[:, 0]
+            if self.flg_squash:
+                if self._batch_um is None or self._batch_um.device != a.device:
+                    self._batch_um = torch.as_tensor(np.asarray(self.u_max, dtype=np.float64)).to(a.device)
+                u0 = self._batch_um * torch.tanh(u0 / self._batch_um)
+            self._batch_a, self._batch_u, self._batch_t = mppi.shift_warm_start(a), u0.contiguous(), t
+            return self._batch_u
 
     def forward_np(self, state, t=None):
         from mc_pilco_amd.policy_learning import mppi

@@ -17,8 +17,12 @@ Beyond the plain planner (``method``, ``beta``, ``sigma_rows``, ``u_prev`` of ``
 (ops.cem_update: the elites selected and ranked on the device, mean and std PER ROW fitted to them, smoothed and floored), AR(1)-coloured
 perturbations and a std per row (ops.plan_rollout, ops.mppi_update_ext: the colouring happens in the kernels, still one row ahead of the
 step), and the input applied before row 0 for the rate term at t = 0.  With all of them at their defaults the calls are the plain ones.
+``plan_batch`` is ``plan`` for B start states in the launches of one plan (ops.plan_batch_rollout, ops.plan_batch_update,
+ops.cem_batch_update; mcp_plan_batch): a state, a warm start, std rows and u_prev per problem -- or a start state per model particle, for a
+set of samples of an uncertain state --, the model, the cost and t0 shared; problem b's result carries the bits of ``plan`` on its operands,
+and its statistics stay on the device.  ``Policy.MPPI_controller.forward`` runs it on a batch of particles.
 Not built: elites kept across iterations, a momentum on the mean, coloured noise other than AR(1), a throughput layout
-for mean-mode planning, GP-sharded forms, the measured (PMS) form, a state per candidate."""
+for mean-mode planning, GP-sharded forms, the measured (PMS) form, a t0 or a cost per problem of a batch."""
 import numpy as np
 import torch
 
@@ -138,6 +142,100 @@ def plan(model, x0, a_init, cost, K, P=1, iterations=1, sigma=0.3, lam=1.0, kapp
     return a, info
 
 
+def _per_problem(name, v, one, B, dev):
+    """``v`` -- host values or a tensor of the shape ``one`` (shared by the problems) or [B] + ``one`` -- as a contiguous float64 tensor
+    [B] + ``one`` of its own on ``dev``."""
+    t = torch.as_tensor(v).detach().to(device=dev, dtype=ops.DT)
+    if tuple(t.shape) == tuple(one):
+        return t.unsqueeze(0).repeat(B, *([1] * len(one)))
+    if tuple(t.shape) != (B,) + tuple(one):
+        raise ValueError("mppi.plan_batch: %s must have the shape %s or %s, not %s" % (name, list(one), [B] + list(one), list(t.shape)))
+    return t.contiguous().clone()
+
+
+def plan_batch(model, x0, a_init, cost, K, P=1, iterations=1, sigma=0.3, lam=1.0, kappa=0.0, u_max=1.0, flg_squash=True, particle_pred=False,
+               noise=None, t0=0, trial_index=None, method="mppi", n_elite=None, alpha=0.1, sigma_min=0.0, beta=0.0, sigma_rows=None, u_prev=None,
+               particle_stride=None):
+    """``plan`` for B start states in the launches of one plan: ``x0`` [B,S], or [B,P,S] for a start state per model particle (a set of
+    samples of an uncertain state estimate: trajectory k P + p of problem b starts at x0[b,p]); ``a_init`` [H,U] (one warm start for all) or
+    [B,H,U]; ``sigma_rows`` [H,U] or [B,H,U] (host values, or a tensor whose values are then read on the host); ``u_prev`` [U] or [B,U];
+    every other keyword as in ``plan`` and shared by the problems (the model, the cost, ``t0``, the plan's scalars).  ``particle_stride``:
+    problem b draws its perturbations and its model increments as ``plan`` does with ``noise.particle_offset + b * particle_stride`` --
+    None: max(K, P), the problems draw independent numbers; 0: common random numbers across the problems.  An ``eps`` buffer of ``noise`` is
+    [H-1,P,G] (read by every problem) or [B,H-1,P,G].
+
+    Problem b's result is, bit for bit, that of ``plan`` on its operands with that particle offset.  One iteration is the launches of ONE
+    plan whatever B (ops.plan_batch_rollout, ops.plan_batch_update / ops.cem_batch_update); the iterations run back to back with the buffer
+    swapping of ``plan`` and NOTHING is read back: returns (a [B,H,U], info) with info's entries DEVICE tensors -- "S_min" and
+    "nominal_cost" [iterations,B]; "ess" and "mean_cost", or under CEM "elite_cost", "n_elite_used" (int32) [iterations,B], "elite" int32
+    [iterations,B,n_elite] (-1 behind the elites used) and "sigma" [B,H,U]; "status" int32 [B], one word per problem -- and "iterations".  A
+    problem with a non-finite start state keeps its nominal, raises MCP_STATUS_NAN in its own status word and leaves the others' bits alone."""
+    pm = _packed_model(model)
+    dev = pm.device
+    x0 = torch.as_tensor(x0).detach().to(device=dev, dtype=ops.DT).contiguous()
+    if x0.dim() not in (2, 3) or x0.shape[0] < 1 or x0.shape[-1] != pm.S or (x0.dim() == 3 and x0.shape[1] != int(P)):
+        raise ValueError("mppi.plan_batch takes x0 [B,%d] or [B,P = %d,%d]" % (pm.S, int(P), pm.S))
+    B = int(x0.shape[0])
+    a = torch.as_tensor(a_init).detach()
+    if a.dim() not in (2, 3) or a.shape[-1] != pm.U or a.shape[-2] < 2:
+        raise ValueError("mppi.plan_batch takes a_init [H >= 2, %d] or [B, H >= 2, %d]" % (pm.U, pm.U))
+    H, n_it = int(a.shape[-2]), int(iterations)
+    a = _per_problem("a_init", a, (H, pm.U), B, dev)
+    if n_it < 1:
+        raise ValueError("mppi.plan_batch: at least one iteration")
+    if method not in ("mppi", "cem"):
+        raise ValueError("mppi.plan_batch: method is \"mppi\" or \"cem\" (%r)" % (method,))
+    mp = ops.PackedMPPI(K, P, H, pm.U, sigma, lam, kappa, u_max, flg_squash)
+    bt = ops.PackedPlanBatch(B, mp.P, x0.dim() == 3, max(mp.K, mp.P) if particle_stride is None else particle_stride)
+    if B * mp.M > ops.abi.MPPI_MAX_M:
+        raise ValueError("mppi.plan_batch: at most %d trajectories over all problems (B K P %d)" % (ops.abi.MPPI_MAX_M, B * mp.M))
+    plain = method == "mppi" and float(beta) == 0.0 and sigma_rows is None and u_prev is None
+    ext = srows = None
+    if not plain:
+        rows = None if sigma_rows is None else ops._host(sigma_rows)
+        if rows is not None and rows.ndim == 3:  # a std per problem: each problem's rows pass the checks of the descriptor
+            if rows.shape[0] != B:
+                raise ValueError("mppi.plan_batch: sigma_rows must have the shape %s or %s, not %s" % ([H, pm.U], [B, H, pm.U], list(rows.shape)))
+            for r in rows:
+                ops.PackedPlanExt(H, pm.U, sigma_rows=r)
+        ext = ops.PackedPlanExt(H, pm.U, beta, None if rows is None or rows.ndim == 3 else rows, max(1, int(K) // 8) if n_elite is None else n_elite, alpha,
+                                sigma_min)
+        if method == "cem" and ext.n_elite > mp.K:
+            raise ValueError("mppi.plan_batch: %d elites of %d candidates" % (ext.n_elite, mp.K))
+        if rows is not None:
+            srows = _per_problem("sigma_rows", rows, (H, pm.U), B, dev)
+            ext = ops.PackedPlanExt(H, pm.U, beta, None, ext.n_elite, alpha, sigma_min)  # (the rows travel as the device buffer)
+        if u_prev is not None:
+            u_prev = _per_problem("u_prev", u_prev, (pm.U,), B, dev)
+    pc, cin, w = kernel_cost(cost, pm.S, pm.U, H, dev, trial_index)
+    _check_rows(pc, t0, H)
+    noise = ops.NoiseSpec() if noise is None else noise
+    new = lambda *s: torch.empty(*s, dtype=ops.DT, device=dev)
+    b, traj, cand, wts, stats = new(B, H, pm.U), new(B, mp.M), new(n_it, B, mp.K), new(B, mp.K), new(n_it, B, 4)
+    status = torch.zeros(B, dtype=torch.int32, device=dev)
+    if method == "cem":
+        s = srows if srows is not None else ops._t(np.tile(mp.sigma, (B, H, 1)), dev)
+        s2, elite = new(B, H, pm.U), torch.empty(n_it, B, ext.n_elite, dtype=torch.int32, device=dev)
+    for i in range(n_it):
+        nz = ops.NoiseSpec(eps=noise.eps, seed=noise.seed, call=int(noise.call) + i, particle_offset=noise.particle_offset, call_dev=noise.call_dev)
+        if method == "mppi":
+            ops.plan_batch_rollout(pm, mp, ext, bt, pc, x0, a, sigma_rows=srows, u_prev=u_prev, cost_inputs=cin, noise=nz, particle_pred=particle_pred,
+                                   w=w, t0=t0, traj_cost=traj, status=status)
+            ops.plan_batch_update(mp, ext, bt, traj, a, sigma_rows=srows, noise=nz, a_new=b, out=(cand[i], wts, stats[i]), status=status)
+        else:
+            ops.plan_batch_rollout(pm, mp, ext, bt, pc, x0, a, sigma_rows=s, u_prev=u_prev, cost_inputs=cin, noise=nz, particle_pred=particle_pred,
+                                   w=w, t0=t0, traj_cost=traj, status=status)
+            ops.cem_batch_update(mp, ext, bt, traj, a, sigma_rows=s, noise=nz, a_new=b, sigma_new=s2, out=(cand[i], elite[i], stats[i]), status=status)
+            s, s2 = s2, s
+        a, b = b, a
+    info = dict(S_min=stats[:, :, 0], nominal_cost=cand[:, :, 0], status=status, iterations=n_it)
+    if method == "cem":
+        info.update(elite_cost=stats[:, :, 3], n_elite_used=stats[:, :, 2].to(torch.int32), elite=elite, sigma=s)
+    else:
+        info.update(ess=stats[:, :, 2], mean_cost=stats[:, :, 3])
+    return a, info
+
+
 def shift_warm_start(a):
-    """The nominal of the next control step: every row moved up by one, the last row repeated."""
-    return torch.cat([a[1:], a[-1:]], 0).contiguous()
+    """The nominal of the next control step: every row moved up by one, the last row repeated ([H,U], or [B,H,U]: every problem's)."""
+    return torch.cat([a[..., 1:, :], a[..., -1:, :]], -2).contiguous()
